@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- full-lambda-path solves/sec on BASELINE.json config 1 (the reference's README benchmark).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -22,6 +22,11 @@ one line on stderr, exit code 2).  The N > 1 line carries `rccl_ranks` (the worl
 `host_resident_ms` at opts.ngpus = N -- the in-library multi-GPU path an R caller gets (rank 0, after the process group is gone).
 
 Rank 0 prints ONE JSON line (see the repo README / DESIGN.md for the roofline and cpu_baseline fields).
+
+A plain run does only what the headline needs: set-up, the untimed solves, the K timed steps, the outputs of the last one if
+--dump-outputs DIR is given (DIR/<name>.npy, float64: what the C ABI hands its caller), and a line with the headline fields alone.
+--full adds everything else: per-stage and roofline timings (runs of their own), the live counter passes, the two-callers and RCCL
+checks, the host-resident, c2 / c3 / c4 / c5 / q8192 / p >= n legs and the CPU baselines; the --no-* options then drop single ones.
 """
 import argparse
 import ctypes as C
@@ -44,7 +49,7 @@ C4_FLOOR_US = 4.6
 README_SECONDS = 1.600241        # reference README.md:73, oem[lasso] mean over 5 runs, hardware unstated
 
 
-def c5_weak(torch, dist, world, rank, dev, backend, rows, steps, warmup):
+def c5_weak(torch, dist, world, rank, dev, backend, rows, steps, warmup, full=True, dump_dir=None):
     """BASELINE.json config 5 as its per-GPU share: big.oem() lasso, 100 lambdas, p = 256, `rows` rows on EVERY rank (weak
     scaling: n = world * rows), X ~ N(0,1) generated on the device, one all-reduce of the (p+2)^2 moment buffer."""
     import numpy as np
@@ -92,6 +97,15 @@ def c5_weak(torch, dist, world, rank, dev, backend, rows, steps, warmup):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, args)
+    nit = int(np.sum(args.niter))
+    if not full:
+        del x, xt, y
+        torch.cuda.empty_cache()
+        return {"workload": "config 5 share: big.oem() lasso, p=256, 100 lambdas, tol 1e-7 (default), %d rows per GPU, n = %d" % (rows, rows * world),
+                "value": steps / dt, "unit": "solves/s", "ms_per_step": 1e3 * dt / steps, "steps": steps, "scaling": "weak",
+                "rows_per_gpu": rows, "n_total": rows * world, "rows_per_second": rows * world * steps / dt, "oem_iterations_per_solve": nit}
     lib = L.lib()
     L.check(lib.oemgpu_set_timing(backend.ctx, 1))
     acc = np.zeros(L.NTIMERS)
@@ -109,7 +123,6 @@ def c5_weak(torch, dist, world, rank, dev, backend, rows, steps, warmup):
         ex = time_exchanges(torch, dist, backend, bufs[1])
         allreduce_ms, allgather_ms = ex["allreduce_ms"], ex["allgather_ms"]
     flops = float(rows) * p * (p + 1) + 2.0 * rows * p
-    nit = int(np.sum(args.niter))
     del x, xt, y
     torch.cuda.empty_cache()
     return {"workload": "config 5 share: big.oem() lasso, p=256, 100 lambdas, tol 1e-7 (default), %d rows per GPU, n = %d" % (rows, rows * world),
@@ -121,6 +134,14 @@ def c5_weak(torch, dist, world, rank, dev, backend, rows, steps, warmup):
             "gram_TFLOPs": flops / (acc[L.T_GRAMK] * 1e-3) / 1e12 if acc[L.T_GRAMK] > 0 else None,
             "gram_frac_of_fp64_mfma_peak": flops / (acc[L.T_GRAMK] * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS if acc[L.T_GRAMK] > 0 else None,
             "oem_iterations_per_solve": nit}
+
+
+def dump_outputs(out_dir, args):
+    """What a caller of the timed path receives from its last step -- the result buffers of the oemgpu_fit_* call -- as float64
+    DIR/<name>.npy (a few hundred KB for these workloads)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in (("beta", args.beta), ("lambda", args.lam_out), ("niter", args.niter), ("loss", args.loss), ("d", [args.d.value])):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 def time_exchanges(torch, dist, backend, buf, reps=50):
@@ -305,8 +326,12 @@ def host_resident_c5(torch, dev, ngpus, rows_per_device=2_000_000, calls=3, devi
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; --workload c5: 10)")
+    ap.add_argument("--warmup", type=int, default=None, help="warmup steps before them (default 10; --workload c5: 2)")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beyond the headline too (per-stage and roofline "
+                                                        "timings, live counters, CPU baselines, the other configurations); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                                                                        "(beta, lambda, niter, loss, d) as DIR/<name>.npy in float64")
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--p", type=int, default=100)
     ap.add_argument("--workload", choices=["c1", "c5"], default="c1",
@@ -326,6 +351,8 @@ def main():
     if not argv and "OEM_BENCH_ARGV" in os.environ and "WORLD_SIZE" in os.environ:      # a worker of self_launch()
         argv = json.loads(os.environ["OEM_BENCH_ARGV"])
     a = ap.parse_args(argv)
+    if not a.full:                               # a plain run: set-up, warmup, the timed steps, the outputs, the headline line
+        a.no_c5 = a.no_host = a.no_two_callers = a.no_rccl_check = a.no_live_pmc = a.no_cpu_baseline = True
     if a.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
         sys.exit(2)
@@ -378,23 +405,29 @@ def main():
 
     if a.workload == "c5":
         backend = HipBackend(local)
-        steps = a.steps if a.steps != 200 else 10
-        warm = a.warmup if a.warmup != 10 else 2
-        r = c5_weak(torch, dist, world, rank, dev, backend, a.c5_rows, steps, warm)
+        steps = a.steps if a.steps is not None else 10
+        warm = a.warmup if a.warmup is not None else 2
+        r = c5_weak(torch, dist, world, rank, dev, backend, a.c5_rows, steps, warm, full=a.full, dump_dir=a.dump_outputs)
         if rank == 0:
-            emit(({"metric": "full-lambda-path solves/sec (config 5 share: big.oem lasso, 1.25e7 x 256 rows per GPU)",
-                              "value": r["value"], "unit": "solves/s", "n_gpus": world, "steps": steps, "warmup": warm,
-                              "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                              "dtype": "f64", "data": "synthetic", "config": {"workload": r["workload"], "rows_per_gpu": r["rows_per_gpu"]},
-                              "roofline": {"bound": "mfma", "kernel": "gram_wd_kernel (v_mfma_f64_16x16x4_f64; one eight-wave workgroup per row chunk, one read of X)", "achieved": r["gram_TFLOPs"],
-                                           "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": r["gram_frac_of_fp64_mfma_peak"],
-                                           "traffic": None},
-                              "rccl_ranks": world if coll_backend == "nccl" else None, "collective_backend": coll_backend,
-                              "detail": r}))
+            line = {"metric": "full-lambda-path solves/sec (config 5 share: big.oem lasso, 1.25e7 x 256 rows per GPU)",
+                    "value": r["value"], "unit": "solves/s", "n_gpus": world, "steps": steps, "warmup": warm,
+                    "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                    "dtype": "f64", "data": "synthetic", "config": {"workload": r["workload"], "rows_per_gpu": r["rows_per_gpu"]}}
+            if a.full:
+                line.update({"roofline": {"bound": "mfma", "kernel": "gram_wd_kernel (v_mfma_f64_16x16x4_f64; one eight-wave workgroup per row chunk, one read of X)", "achieved": r["gram_TFLOPs"],
+                                          "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": r["gram_frac_of_fp64_mfma_peak"],
+                                          "traffic": None},
+                             "rccl_ranks": world if coll_backend == "nccl" else None, "collective_backend": coll_backend,
+                             "detail": r})
+            emit(line)
         if in_group:
             dist.destroy_process_group()
         return
 
+    if a.steps is None:
+        a.steps = 200
+    if a.warmup is None:
+        a.warmup = 10
     n, p, m = a.n, a.p, 25
     lo, hi = row_partition(n, world)[rank]
     n_loc = hi - lo
@@ -448,9 +481,11 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     beta_timed = args.beta.copy()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, args)
     # ---- the collective on its own: the (p+2)^2 moment buffer, HIP events on the stream the collectives are ordered on
     allreduce_ms = allgather_ms = None
-    if world > 1:
+    if world > 1 and a.full:
         ex = time_exchanges(torch, dist, backend, bufs[1])
         allreduce_ms, allgather_ms = ex["allreduce_ms"], ex["allgather_ms"]
     # Two callers at once (two host threads, two contexts / streams, the same resident X): the path kernel of one solve occupies ONE
@@ -493,10 +528,12 @@ def main():
                        "same_bits_as_the_single_caller": same,
                        "note": "independent solves from two host threads on two contexts for a fixed wall time; NOT the headline value"}
     # the same through the Python mirror of the R front end (argument checks, result decoration): reported, not `value`
-    t1 = time.perf_counter()
-    for _ in range(20):
-        fit = solve_py(lambdas, 1e-10)
-    dt_py = (time.perf_counter() - t1) / 20
+    fit = dt_py = None
+    if a.full:
+        t1 = time.perf_counter()
+        for _ in range(20):
+            fit = solve_py(lambdas, 1e-10)
+        dt_py = (time.perf_counter() - t1) / 20
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -504,20 +541,22 @@ def main():
 
     # ---- roofline of the dominant kernel (the MFMA moment build), HIP events on the kernel's own stream
     lib = L.lib()
-    L.check(lib.oemgpu_set_timing(backend.ctx, 1))
-    reps = max(10, min(50, a.steps))
     acc = np.zeros(L.NTIMERS)
-    ms = (C.c_double * L.NTIMERS)()
-    with backend.section():
-        for _ in range(reps):
-            solve()
-            L.check(lib.oemgpu_last_timings(backend.ctx, ms))
-            acc += np.array(list(ms))
-    L.check(lib.oemgpu_set_timing(backend.ctx, 0))
-    acc /= reps
-    _st, _cp = C.c_int32(-1), C.c_int32(-1)
-    L.lib().oemgpu_last_eigen_info(backend.ctx, C.byref(_st), C.byref(_cp))
-    eig_info = {"lanczos_steps": int(_st.value), "step_cap_reached": bool(_cp.value)}
+    eig_info = None
+    if a.full:
+        L.check(lib.oemgpu_set_timing(backend.ctx, 1))
+        reps = max(10, min(50, a.steps))
+        ms = (C.c_double * L.NTIMERS)()
+        with backend.section():
+            for _ in range(reps):
+                solve()
+                L.check(lib.oemgpu_last_timings(backend.ctx, ms))
+                acc += np.array(list(ms))
+        L.check(lib.oemgpu_set_timing(backend.ctx, 0))
+        acc /= reps
+        _st, _cp = C.c_int32(-1), C.c_int32(-1)
+        L.lib().oemgpu_last_eigen_info(backend.ctx, C.byref(_st), C.byref(_cp))
+        eig_info = {"lanczos_steps": int(_st.value), "step_cap_reached": bool(_cp.value)}
     gram_ms = acc[L.T_GRAMK]
     flops = float(n_loc) * p * (p + 1) + 2.0 * n_loc * p            # lower-triangular syrk + X'y
     bytes_alg = 8.0 * n_loc * p + 8.0 * n_loc
@@ -527,7 +566,7 @@ def main():
     # FETCH_SIZE x2 + WRITE_SIZE as /opt/skills/guides/MI355X_MICROARCH.md prescribes for gfx950; null if it does not apply.
     traffic, traffic_src = None, None
     pmcs = sorted((ROOT / "profiles").glob("r*_pmc_gram.json"))
-    if pmcs and n == 1_000_000 and p == 100 and world == 1:
+    if a.full and pmcs and n == 1_000_000 and p == 100 and world == 1:
         traffic = float(json.loads(pmcs[-1].read_text())["hbm_bytes_per_dispatch"])
         traffic_src = ("CONSTANT, not measured in this run: profiles/%s (the rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
                        "command, tools/round_artifacts.sh); counters cannot be read from inside the process" % pmcs[-1].name)
@@ -562,13 +601,13 @@ def main():
 
     mfma_util, mfma_src = None, None
     mf = sorted((ROOT / "profiles").glob("r*_pmc_gram_mfma.json"))
-    if mf and n == 1_000_000 and p == 100 and world == 1:
+    if a.full and mf and n == 1_000_000 and p == 100 and world == 1:
         mfma_util = float(json.loads(mf[-1].read_text())["mfma_util"])
         mfma_src = ("CONSTANT, not measured in this run: profiles/%s (rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE on this command): "
                     "matrix-pipe busy cycles / (GPU cycles x 1024 SIMDs), i.e. at the clock the chip held" % mf[-1].name)
     out = None
     if rank == 0:
-        niter_total = int(np.sum(fit["niter"][0]))
+        niter_total = int(np.sum(fit["niter"][0] if fit is not None else args.niter[0]))
         c1_exact = n == 1_000_000 and p == 100
         out = {
             "metric": "full-lambda-path solves/sec (n=1e6 p=100 lasso, 100 lambdas, tol 1e-10)",
@@ -581,6 +620,9 @@ def main():
                        "n": n, "p": p, "nlambda": int(len(lambdas)), "rows_per_gpu": n_loc,
                        "sharding": "rows/N + one all-reduce of the (p+2)^2 moment buffer" if world > 1 else "none",
                        "oem_iterations_per_solve": niter_total},
+        }
+    if rank == 0 and a.full:
+        out.update({
             "roofline": {"bound": "mfma", "kernel": "gram_ring_kernel<7> (v_mfma_f64_16x16x4_f64; diagonal tiles and the ragged strip as v_mfma_f64_4x4x4_4b_f64 sub-blocks)",
                          "achieved": achieved_tf, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved_tf / FP64_MFMA_PEAK_TFLOPS, "traffic": traffic, "traffic_unit": "bytes per launch",
@@ -605,7 +647,7 @@ def main():
             "allreduce_doubles": (p + 2) * (p + 2),
             "rccl_selfcheck": rccl_check,
             "throughput_two_callers": two_callers,
-        }
+        })
     # every rank takes part in the appended weak-scaling measurement (it has a collective)
     xh_full = yh_full = None
     if rank == 0 and world == 1 and not (a.no_host and a.no_cpu_baseline):
@@ -623,7 +665,7 @@ def main():
         try:
             del x
             torch.cuda.empty_cache()
-            r5 = c5_weak(torch, dist, world, rank, dev, backend, a.c5_rows, 10, 2)
+            r5 = c5_weak(torch, dist, world, rank, dev, backend, a.c5_rows, 10, 2, full=True)
             if rank == 0:
                 out["c5_weak"] = r5
                 if world == 1 and not a.no_cpu_baseline:
@@ -642,7 +684,7 @@ def main():
         except Exception as e:          # e.g. not enough free HBM on a shared device: the headline line must still print
             if rank == 0:
                 out["c5_weak"] = {"error": repr(e)}
-    if rank == 0:
+    if rank == 0 and a.full:
         # ONE object per run that explains this point of the 1 -> N curve for BOTH workloads: per-GPU rows and
         # where a step's time goes -- the moment pass on the local rows, the one all-reduce, the replicated solve
         def _point(value, ms_step, rows, st, ar, ag):

@@ -126,7 +126,7 @@ def test_config5_big_p256_reduced_n_and_shards(oa):
 def test_config1_full_size_against_the_oracle(oa):
     """BASELINE config 1 at FULL size (README.md:44-66): n = 1e6, p = 100, the 100 lambdas of a first default fit supplied back,
     tol 1e-10 -- host x through oemgpu_fit_dense and device-resident x through oemgpu_fit_dense_dev, against the native oracle
-    (one second of CPU): coefficients to 1e-9, d to 1e-10, identical iteration counts.  (bench.py checks the same on every run;
+    (one second of CPU): coefficients to 1e-9, d to 1e-10, identical iteration counts.  (bench.py --full checks the same on every run;
     this puts the headline configuration into the GPU suite itself.)"""
     import torch
     rng = np.random.default_rng(123)
@@ -322,6 +322,9 @@ def test_row_split_one_exchange_engine(oa, p, monkeypatch):
     x = rng.normal(size=(n, p)) * (1.0 + 0.5 * rng.uniform(size=p))
     b = np.zeros(p); b[rng.choice(p, 20, replace=False)] = rng.uniform(-1, 1, 20)
     y = x @ b + rng.normal(size=n)
+    # X and y on a grid of 2^-12: every product and partial sum of X'X and X'y is exact in double, so the Gram is the same bits
+    # whatever BLAS computes it with how many threads (the iteration counts below move with the last bit of the input)
+    x, y = np.round(x * 4096.0) / 4096.0, np.round(y * 4096.0) / 4096.0
     xtx, xty = x.T @ x / n, x.T @ y / n
     xd = torch.as_tensor(xtx, device="cuda")
     pf = np.ones(p); pf[:5] = 0.0; pf[5:9] = 2.5

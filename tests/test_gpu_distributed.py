@@ -52,7 +52,7 @@ def test_bench_launches_its_own_workers():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(OEM_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = _run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--n", "200000", "--no-c5", "--no-cpu-baseline"], env, 240)
+    r = _run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--n", "200000", "--full", "--no-c5", "--no-cpu-baseline"], env, 240)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -78,7 +78,7 @@ def test_bench_launcher_at_eight_ranks(route):
     env.update(OEM_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     if route == "staged through the host":
         env["OEMGPU_NO_PEER"] = "1"
-    r = _run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--n", "100003", "--no-c5", "--no-cpu-baseline"], env, 240)
+    r = _run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--n", "100003", "--full", "--no-c5", "--no-cpu-baseline"], env, 240)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

@@ -102,7 +102,7 @@ if [ -z "$quick" ]; then
 fi
 # the raw traces stay on the box: gpurun copies back at most 64 MiB
 for d in $o/${tag}_trace $o/${tag}_pmc_fetch $o/${tag}_pmc_write $o/${tag}_pmc_mfma $o/${tag}_*_pmc_mfma $o/${tag}_*_trace $o/${tag}_*_pmc_FETCH_SIZE $o/${tag}_*_pmc_WRITE_SIZE; do [ -d "$d" ] && rm -rf "$d"; done
-python3 bench.py > $o/${tag}_bench.json 2> $o/${tag}_bench.err
+python3 bench.py --full > $o/${tag}_bench.json 2> $o/${tag}_bench.err
 tail -c 300 $o/${tag}_bench.err
 head -c 1500 $o/${tag}_kernel_stats.csv
 [ -z "$quick" ] && head -c 4000 $o/${tag}_config_times.json
