@@ -344,6 +344,34 @@ int oemgpu_selftest_plan(int32_t p, int32_t q, int32_t semantics, int32_t interc
  * to n" (the folds of xval.oem, the row tiles of a sparse x) holds the plans of smaller row counts: OEMGPU_ERR_INTERNAL if not. */
 int oemgpu_selftest_gram_plan(int64_t n, int32_t p, int32_t num_cu, int64_t *out /* 8 */);
 
+/* ---------------------------------------------------------------------------------------------------------- binomial (logistic.hip)
+ * `.Call("oem_fit_logistic_dense", ...)` (ref src/oem_logistic_dense.cpp:30-313, src/oem_logistic_dense.h:397-1094): IRLS over the OEM
+ * iteration, dense x, n > p + intercept.  opts as for oemgpu_fit_dense (accelerate is ignored: the reference has no Nesterov step here);
+ * with an intercept, groups / ngroupvars cover q = p + 1 coordinates with the intercept's group first (R/oem.R:296-338 prepends group 0)
+ * and penalty_factor stays p long (the library prepends the intercept's 0, cpp :119-141).  The scalars the opts struct lacks are
+ * parameters: hessian_full (0: "upper.bound" -- X'WX, d and A from the first step of a penalty only; 1: "full" -- every step),
+ * irls_maxit >= 1 and irls_tol >= 0.  Outputs as oemgpu_fit_dense: beta[npen][nlambda][p + 1] (row 0 the intercept, 0 without one;
+ * "ols" fills slot 0 only), lambda_out[npen][nlambda], niter = IRLS steps + 1 at the cap (ref h :1035), loss = the logistic loss of
+ * the last prob computed (1e99 unless compute_loss), d = the last d = 1.0005 lambda_max(XX).
+ * Checked before any device is looked for: OEMGPU_ERR_ARG for bad arguments (hessian_full not 0 / 1, irls_maxit <= 0, ...),
+ * OEMGPU_ERR_UNSUPPORTED for p + intercept >= n (the reference's XWXt branch iterates on the raw labels, ref h :524-566) and p > 8191.
+ * opts->interrupt is polled between IRLS steps (OEMGPU_ERR_INTERRUPTED). */
+int oemgpu_fit_logistic_dense(const double *x, int64_t n, int32_t p, const double *y, int32_t standardize, int32_t intercept,
+                              int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *opts,
+                              double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+/* the same with x (column-major, leading dimension ld >= n) and y on the context's device */
+int oemgpu_fit_logistic_dense_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                                  int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol,
+                                  const oemgpu_opts *opts, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+/* Host-only plan of the binomial fit (pure arithmetic, runs without a GPU): out[0] rows per chunk of the row pass, out[1] chunks
+ * (chunk c = rows [c out[0], min(n, (c + 1) out[0]))), out[2] rows per Z block of the moment pass, out[3] Z blocks, out[4] 1 if the
+ * inner solve is one persistent workgroup (q <= 1024) and 0 for launch per iteration, out[5] 1 if the row pass stages its sub-blocks
+ * in LDS, out[6] device workspace bytes of a call, out[7] the bound out[6] stays within. */
+int oemgpu_selftest_logistic_plan(int64_t n, int32_t p, int32_t intercept, int32_t hessian_full, int32_t num_cu, int64_t *out /* 8 */);
+/* What the most recent binomial fit of THIS thread did: [0] row-pass ms [1] Z + Gram + Lanczos ms [2] inner-solve ms (the three only
+ * with oemgpu_set_timing on the context; 0 otherwise) [3] IRLS steps [4] inner iterations [5] row passes [6] Gram builds [7] wall ms */
+int oemgpu_last_logistic_stats(double *out /* 8 */);
+
 /* Self-test aid (tests/test_gpu_host.py): enqueue, on the context's stream, `blocks` workgroups that each occupy a whole CU and
  * spin for `ms` milliseconds -- "somebody else holds the CUs", for the fallback of the persistent engines.  Asynchronous. */
 int oemgpu_selftest_hold_cus(oemgpu_ctx *ctx, int32_t blocks, double ms);

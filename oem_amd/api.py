@@ -351,6 +351,77 @@ def oem_fit_dense_weighted(x, y, weights, **kw):
     return oem(x, y, _entry_weights=weights, **kw)
 
 
+class OemFitBinomial(OemFit):
+    """The list returned by `.Call("oem_fit_logistic_dense", ...)` once oem() has decorated it (class "oemfit_binomial", R/oem.R:582-649)."""
+
+    r_class = ("oemfit_binomial", "oem")
+
+
+def oem_fit_logistic_dense(x, y, penalty=None, weights=(), lambda_=(), nlambda=100, lambda_min_ratio=None, alpha=1.0, gamma=3.0, tau=0.5,
+                           groups=(), penalty_factor=None, group_weights=None, standardize=True, intercept=True, maxit=500, tol=1e-7,
+                           irls_maxit=100, irls_tol=1e-3, compute_loss=False, hessian_type="upper.bound", varnames=None, interrupt=None):
+    """The dense binomial fit (ref src/oem_logistic_dense.cpp:30-313, src/oem_logistic_dense.h:397-1094) with oem()'s checks for
+    family = "binomial" (R/oem.R:162-507): y takes at most two values (passed on as they are: the reference fits the raw 0/1 vector),
+    groups gain the intercept's group 0 in front (R/oem.R:296-338).  x: numpy (host entry) or a torch tensor on a GPU (_dev entry).
+    hessian_type: "upper.bound" (X'WX, d and A from the first IRLS step of a penalty only) or "full" (every step).  `oem(family=
+    "binomial")` still raises NotImplementedError; this is the entry below it, as oem_fit_dense_weighted is for weights."""
+    L.sync_switches()
+    penalty = _match_penalty(penalty)
+    if hessian_type not in ("upper.bound", "full"):
+        raise ValueError("'arg' should be one of 'upper.bound', 'full'")
+    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("x must have at least two columns")
+    n, p = x.shape
+    if p < 2:
+        raise ValueError("x must have at least two columns")
+    if len(weights) > 0:                                               # R/oem.R:244
+        raise L.OemgpuError(-4, "weights not implemented yet.")
+    yh = np.asarray(y.cpu() if _is_torch_cuda(y) else y, dtype=np.float64).reshape(-1)
+    if yh.shape[0] != n:
+        raise ValueError("x and y lengths do not match")
+    if len(np.unique(yh)) > 2:                                         # R/oem.R:250-252
+        raise ValueError("y must be a binary outcome")
+    if penalty_factor is None:
+        penalty_factor = np.ones(p)
+    penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
+    if len(penalty_factor) != p:
+        raise ValueError("penalty.factor must have same length as number of columns in x")
+    if varnames is None:
+        varnames = [f"V{i + 1}" for i in range(p)]
+    groups, unique_groups, group_weights = _group_setup(penalty, groups, group_weights, p, bool(intercept))
+    if lambda_min_ratio is None:
+        lambda_min_ratio = 0.01 if n < p else 0.0001
+    _common_checks(nlambda, float(lambda_min_ratio), maxit, irls_maxit, tol, irls_tol)
+    lam_list = _lambda_list(lambda_, len(penalty))
+    a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
+              compute_loss, penalty_factor, groups, unique_groups, group_weights, interrupt=interrupt)
+    hf = 1 if hessian_type == "full" else 0
+    lib = L.lib()
+    if _is_torch_cuda(x):
+        import torch
+        xp, n_, p_, ld, keep = _device_matrix(x)
+        yd = torch.as_tensor(yh, device=x.device)
+        ctx = context(x.device.index)
+        torch.cuda.current_stream(x.device).synchronize()
+        L.check(lib.oemgpu_fit_logistic_dense_dev(ctx, xp, n, ld, p, yd.data_ptr(), int(bool(standardize)), int(bool(intercept)), hf,
+                                                  int(irls_maxit), float(irls_tol), C.byref(a.c), *a.outputs(p + 1)))
+        del keep
+    else:
+        xh = np.asfortranarray(x, dtype=np.float64)
+        L.check(lib.oemgpu_fit_logistic_dense(_dptr(xh), n, p, _dptr(yh), int(bool(standardize)), int(bool(intercept)), hf,
+                                              int(irls_maxit), float(irls_tol), C.byref(a.c), *a.outputs(p + 1)))
+    res = OemFitBinomial(_decorate(a, penalty, varnames, True, n, p, family="binomial"))
+    return res
+
+
+def logistic_stats():
+    """oemgpu_last_logistic_stats of this thread, as a dict"""
+    out = (C.c_double * 8)()
+    L.check(L.lib().oemgpu_last_logistic_stats(out))
+    keys = ["rows_ms", "gram_ms", "inner_ms", "irls_steps", "inner_iters", "row_passes", "grams", "wall_ms"]
+    return dict(zip(keys, list(out)))
+
+
 # ------------------------------------------------------------------------------------------ oem.xtx()
 def oem_xtx(xtx, xty, family="gaussian", penalty=None, lambda_=(), nlambda=100, lambda_min_ratio=None, alpha=1.0,
             gamma=3.0, tau=0.5, groups=(), scale_factor=(), penalty_factor=None, group_weights=None, maxit=500,
@@ -734,7 +805,13 @@ def predict(fit, newx=None, s=None, which_model=0, type="link"):
     newx = np.asarray(newx, dtype=np.float64)
     if newx.shape[1] < nbeta.shape[0]:
         newx = np.column_stack([np.ones(newx.shape[0]), newx])
-    return newx @ nbeta
+    nfit = newx @ nbeta
+    if fit.get("family") == "binomial":                # predict.oemfit_binomial, R/methods.R:346-367
+        if type == "response":
+            return 1.0 / (1.0 + np.exp(-nfit))
+        if type == "class":
+            return np.where(nfit > 0, 1, 0)
+    return nfit
 
 
 def predict_xval(fit, newx=None, which_model="best.model", s="lambda.min", **kw):
@@ -785,5 +862,7 @@ def logLik(fit, which_model=0):
     loss = np.atleast_1d(np.asarray(fit["loss"][which_model], dtype=np.float64))
     if np.all(loss == 1e99):
         raise ValueError("oem object needed compute.loss set to TRUE. logLik not returned")
+    if fit.get("family") == "binomial":                # logLik.oem, binomial branch: -loss
+        return -1.0 * loss
     n = float(fit["nobs"])
     return -0.5 * n * (np.log(2 * np.pi) - np.log(n) + np.log(loss)) - 0.5 * n

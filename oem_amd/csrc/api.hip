@@ -287,6 +287,13 @@ int check_opts(const oemgpu_opts *o, int p, int ngroupvars_expected)
     return 0;
 }
 
+}  // namespace
+
+// the same checks for the entry points of other translation units (logistic.hip)
+int oemgpu::check_opts_export(const oemgpu_opts *o, int p, int ngroupvars_expected) { return check_opts(o, p, ngroupvars_expected); }
+
+namespace {
+
 // ---------------------------------------------------------------- host-built parameter blob
 struct Blob {
     std::vector<char> h;

@@ -295,6 +295,11 @@ int launch_path_wstream(hipStream_t s, const PathArgs &a, const WideArgs &w, int
 // opts->interrupt of the call in progress on this thread (api.hip: run_paths sets it around the engines); false if none
 bool caller_interrupted();
 
+// api.hip: the argument checks of the Gaussian entry points (check_opts) for other translation units
+int check_opts_export(const oemgpu_opts *o, int p, int ngroupvars_expected);
+// path_large.hip: out = M vec for a symmetric q x q M (skipped while *done != 0)
+int launch_gemv_sym(hipStream_t s, const double *M, int q, const double *vec, double *out, const int *done, int num_cu);
+
 int launch_eig_small(hipStream_t s, const double *a, int p, int steps, double *out /* [d, lambda_max] */);
 
 __host__ __device__ static inline bool pen_is_net(int pen)

@@ -1,0 +1,776 @@
+// logistic.hip -- the dense binomial fit: what `.Call("oem_fit_logistic_dense", ...)` computes (ref src/oem_logistic_dense.cpp:30-313,
+// src/oem_logistic_dense.h:397-1094), restated as it is, quirks included:
+//   * standardisation: colsq = sum x^2 / (n - 1), X NOT centred, 0 -> 1, s = 1 / sqrt(colsq) when `standardize` (h :727-738);
+//   * the intercept is coordinate 0 of a q = p + 1 problem with penalty factor 0 (cpp :119-141); row / column 0 of XX is
+//     [sum W, sum W x_j s_j] / n (h :463-481); without an intercept row 0 of the returned beta is 0 (cpp :246-253);
+//   * XY = s o X'Y / n with the raw 0/1 Y, lambda_0 = max |XY| over the non-intercept slots (h :762-805);
+//   * penalty -> lambda (warm start) -> IRLS step i < irls_maxit -> OEM iteration j < maxit (h :848-1036), no Nesterov step;
+//   * one IRLS step: prob = 1 / (1 + exp(-(X (beta o s) + beta_0))), W = prob (1 - prob) with the floor loop that tests W(i) with the
+//     IRLS index i (so at most element i is floored, h :953-959); XX, d = 1.0005 lambda_max(XX) (NOT 1.005, h :514) and A = dI - XX only
+//     when (i == 0 && first lambda of the penalty) or hessian.type == "full" (h :964-965); grad = s o X'(y - prob) / n, grad_0 =
+//     sum (y - prob) / n; XY = XX beta + grad (h :970-1000).  On a lambda after the first, the FIRST IRLS step skips all of that
+//     (h :861): the inner loop runs at the new lambda on the previous step's XY / A / d.  IRLS stop: stopRule(beta, beta_irls,
+//     irls_tol); niter = i + 1 (irls_maxit + 1 when the cap is hit, h :1035);
+//   * loss: get_loss (the 1e-5 clamps, h :1057-1090) of the LAST prob computed, not of the final beta; d: the last d computed.
+// Refused (api: OEMGPU_ERR_UNSUPPORTED): p + intercept >= n -- the reference's XWXt branch (h :490-496, 524-566) iterates on the raw
+// labels instead of the IRLS response, least squares on 0/1 -- and p > LOGIT_P_MAX.
+//
+// Kernels:
+//   * logit_rows_kernel: the row pass.  Workgroup c owns rows [c CH, (c + 1) CH) and walks them in sub-blocks of 64; from ONE read of
+//     a sub-block (staged in LDS when 64 x p fits, else re-read through the cache) it forms eta, prob, W, r = y - prob and the loss terms,
+//     and accumulates its partial of [sum r, X'r, sum loss] in fixed order.  With a Gram due it also writes Z = [sqrt W | sqrt W x s]
+//     for the moment pass (gram.hip), in row blocks of RBZ rows so that the workspace stays bounded;
+//   * logit_sum_kernel: the partials summed in chunk order (two calls give the same bits);
+//   * logit_inner_kernel: q <= LOGIT_WG_MAX: the OEM loop of one lambda from a warm start in ONE workgroup (A in LDS when it fits),
+//     to stopRule or maxit; beyond that launch_gemv (path_large.hip) + logit_thresh_kernel per iteration, batches of LOGIT_BATCH
+//     launches between looks at the stop word;
+//   * small kernels: XX from the moments, A = dI - XX, XY = XX beta + grad, the IRLS stop, the back-transform.
+#include "ctx.hpp"
+#include "penalty_ops.hpp"
+
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+namespace oemgpu {
+
+static const int LOGIT_WG_MAX = 1024;          // q up to which the inner solve is one persistent workgroup
+static const int LOGIT_P_MAX = 8191;           // the row pass keeps its X'r accumulators in LDS (8 p bytes)
+static const int LOGIT_STAGE_P = 192;          // p up to which a 64-row sub-block is staged in LDS (65 x 8 p bytes)
+static const int LOGIT_A_LDS_Q = 110;          // q up to which the inner kernel keeps A in LDS (8 q^2 bytes)
+static const int LOGIT_BATCH = 16;             // launch form: iterations enqueued between looks at the stop word
+static const size_t LOGIT_Z_BYTES = (size_t)256 << 20;   // Z row blocks: at most this much (or one chunk of rows)
+
+// state words (doubles) shared between the kernels and the host
+enum { ST_LOSS = 0, ST_ITERS = 1, ST_IRLS_STOP = 2, ST_DONE = 3, ST_LEN = 8 };
+
+struct LogitPlan {
+    int64_t ch;        // rows per chunk (a multiple of 64)
+    int64_t nchunk;    // chunks: chunk c = rows [c ch, min(n, (c + 1) ch))
+    int64_t rbz;       // rows per Z block (a multiple of ch; 0: no Gram pass ever, never the case today)
+    int64_t nzblk;     // Z blocks
+    int inner_wg;      // 1: one persistent workgroup; 0: launch per iteration
+    int staged;        // 1: the row pass stages its 64-row sub-blocks in LDS
+    size_t ws_bytes;   // device workspace of a call (c->aux)
+};
+
+static LogitPlan logit_plan(int64_t n, int p, int intercept, int num_cu)
+{
+    LogitPlan P;
+    const int q = p + (intercept ? 1 : 0);
+    int64_t ch = (n + 4 * (int64_t)num_cu - 1) / (4 * (int64_t)num_cu);
+    ch = (ch + 63) / 64 * 64;
+    if (ch < 64) ch = 64;
+    P.ch = ch;
+    P.nchunk = (n + ch - 1) / ch;
+    int64_t cpb = (int64_t)(LOGIT_Z_BYTES / ((size_t)ch * q * 8));
+    if (cpb < 1) cpb = 1;
+    if (cpb > P.nchunk) cpb = P.nchunk;
+    P.rbz = cpb * ch;
+    P.nzblk = (P.nchunk + cpb - 1) / cpb;
+    P.inner_wg = q <= LOGIT_WG_MAX;
+    P.staged = p <= LOGIT_STAGE_P;
+    const GramPlan gp = gram_plan_bound(P.rbz < n ? P.rbz : n, q, num_cu);
+    const size_t m2 = (size_t)(q + 2) * (q + 2);
+    Bump B;
+    B.take(8 * (size_t)p);                                  // s
+    B.take(8 * (size_t)q * 4);                              // beta, beta_irls, u, XY
+    B.take(8 * (size_t)q * q * 2);                          // XX, A
+    B.take(8 * (size_t)(p + 2));                            // g
+    B.take(8 * (size_t)P.nchunk * (p + 2));                 // chunk partials
+    B.take(8 * (size_t)P.rbz * q);                          // Z block
+    B.take(8 * m2 * 2);                                     // moments of a block, their running sum
+    B.take(8 * gp.tpart_doubles); B.take(8 * gp.vpart_doubles);
+    B.take(8 * ST_LEN); B.take(256);                        // state words, the stop word of the launch form
+    B.take(8 * (size_t)q * 2 + 4 * (size_t)q * 3 + 4 * (size_t)(q + 1) + 8);   // pf, group weights, perm / group of / starts, ngroups
+    P.ws_bytes = B.off;
+    return P;
+}
+
+namespace {
+
+// stopRule (ref src/utils.cpp:537-549): 1 = this coordinate does NOT stop the loop
+__device__ __forceinline__ int stop_violated(double c, double pv, double tol)
+{
+    const bool cn = fabs(c) > 1e-13, pn = fabs(pv) > 1e-13;
+    if (cn != pn) return 1;
+    if (cn && pn && fabs((c - pv) / pv) > tol) return 1;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- row pass
+// mode 0: r = y (X'Y for XY's first form and lambda_0); mode 1: the IRLS quantities.  zout: Z block (ldz rows), or null.
+template <bool STAGED>
+__global__ __launch_bounds__(256) void logit_rows_kernel(const double *__restrict__ x, int64_t n, int64_t ld, int p, const double *__restrict__ y,
+                                                         const double *__restrict__ beta, const double *__restrict__ s, int intercept, int mode,
+                                                         int64_t irls_i, int64_t ch, int64_t chunk0, int64_t row0, double *__restrict__ zout,
+                                                         int64_t ldz, double *__restrict__ part)
+{
+    extern __shared__ double lsh[];
+    double *acc = lsh;                               // p
+    double *tile = lsh + p;                          // 65 p (STAGED)
+    __shared__ double etap[4][64], rsh[64], wsh[64], red[2][64];
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int o = intercept ? 1 : 0;
+    const int64_t c = chunk0 + blockIdx.x;
+    const int64_t r_lo = c * ch, r_hi = (r_lo + ch < n) ? r_lo + ch : n;
+    for (int j = tid; j < p; j += 256) acc[j] = 0.0;
+    const double b0 = (mode && intercept) ? beta[0] : 0.0;
+    double rsum = 0.0, lsum = 0.0;                   // wave 0: per-lane sums of r and of the loss terms
+    for (int64_t r0 = r_lo; r0 < r_hi; r0 += 64) {
+        const int64_t row = r0 + lane;
+        const bool ok = row < r_hi;
+        // phase 1: wave w reads columns j = w (mod 4), lane = row (coalesced); eta partials
+        double e = 0.0;
+        if (mode) {
+            for (int j = w; j < p; j += 4) {
+                const double v = ok ? x[(size_t)j * ld + row] : 0.0;
+                if (STAGED) tile[j * 65 + lane] = v;
+                e = fma(v, beta[o + j] * s[j], e);
+            }
+        } else if (STAGED) {
+            for (int j = w; j < p; j += 4) tile[j * 65 + lane] = ok ? x[(size_t)j * ld + row] : 0.0;
+        }
+        etap[w][lane] = e;
+        __syncthreads();
+        // phase 2: one wave forms prob, W, r and the loss terms of its 64 rows
+        if (w == 0) {
+            double r = 0.0, sw = 0.0;
+            if (ok) {
+                const double yi = y[row];
+                if (mode) {
+                    const double eta = ((etap[0][lane] + etap[1][lane]) + (etap[2][lane] + etap[3][lane])) + b0;
+                    const double prob = 1.0 / (1.0 + exp(-eta));
+                    double W = prob * (1.0 - prob);
+                    if (row == irls_i && W < 1e-5) W = 1e-5;          // the reference's floor loop tests W(i), i the IRLS index (h :953-959)
+                    sw = sqrt(W);
+                    r = yi - prob;
+                    double lt;
+                    if (yi == 1.0) lt = prob > 1e-5 ? log(1.0 / prob) : log(1.0 / 1e-5);
+                    else lt = prob <= 1.0 - 1e-5 ? log(1.0 / (1.0 - prob)) : log(1.0 / 1e-5);
+                    lsum += lt;
+                } else {
+                    r = yi;
+                }
+                rsum += r;
+                if (zout && o) zout[row - row0] = sw;
+            }
+            rsh[lane] = r; wsh[lane] = sw;
+        }
+        __syncthreads();
+        // phase 3: thread j accumulates column j over the 64 rows, in row order
+        for (int j = tid; j < p; j += 256) {
+            double a = acc[j];
+            const int lim = (int)((r_hi - r0) < 64 ? (r_hi - r0) : 64);
+            if (STAGED) {
+                for (int i = 0; i < lim; ++i) a = fma(tile[j * 65 + i], rsh[i], a);
+            } else {
+                const double *col = x + (size_t)j * ld + r0;
+                for (int i = 0; i < lim; ++i) a = fma(col[i], rsh[i], a);
+            }
+            acc[j] = a;
+        }
+        // phase 4: Z = sqrt(W) (x s) of these rows, coalesced as in phase 1
+        if (zout && ok) {
+            for (int j = w; j < p; j += 4) {
+                const double v = STAGED ? tile[j * 65 + lane] : x[(size_t)j * ld + row];
+                zout[(size_t)(o + j) * ldz + (row - row0)] = wsh[lane] * (v * s[j]);
+            }
+        }
+        __syncthreads();
+    }
+    if (w == 0) { red[0][lane] = rsum; red[1][lane] = lsum; }
+    __syncthreads();
+    double *pc = part + (size_t)c * (p + 2);
+    for (int j = tid; j < p; j += 256) pc[1 + j] = acc[j];
+    if (tid == 0) {
+        double a = 0.0, b = 0.0;
+        for (int i = 0; i < 64; ++i) { a += red[0][i]; b += red[1][i]; }
+        pc[0] = a; pc[p + 1] = b;
+    }
+}
+
+// g[j] = ((part[0][j] + part[1][j]) + part[2][j]) + ... : chunk order
+__global__ __launch_bounds__(256) void logit_sum_kernel(const double *__restrict__ part, int64_t nchunk, int len, double *__restrict__ g)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= len) return;
+    double a = 0.0;
+    for (int64_t c = 0; c < nchunk; ++c) a += part[(size_t)c * len + j];
+    g[j] = a;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- Gram pieces
+__global__ __launch_bounds__(256) void logit_mom_add_kernel(double *__restrict__ acc, const double *__restrict__ m, size_t len, int first)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < len) acc[i] = first ? m[i] : acc[i] + m[i];
+}
+
+// XX = Z'Z / n from the lower triangle of the moments ((q + 2) x (q + 2), column-major)
+__global__ __launch_bounds__(256) void logit_xx_kernel(const double *__restrict__ M, int q, double n, double *__restrict__ xx)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (i >= q) return;
+    const int hi = i > j ? i : j, lo = i > j ? j : i;
+    xx[(size_t)j * q + i] = M[(size_t)lo * (q + 2) + hi] / n;
+}
+
+// A = dI - XX (h :518-519: A = -XX, then d added to the diagonal)
+__global__ __launch_bounds__(256) void logit_a_kernel(const double *__restrict__ xx, int q, double d, double *__restrict__ a)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (i >= q) return;
+    const size_t k = (size_t)j * q + i;
+    a[k] = i == j ? -xx[k] + d : -xx[k];
+}
+
+// XY = XX beta + grad; grad = s o X'(y - prob) / n, grad_0 = sum (y - prob) / n (h :973-999).  init: the first XY = s o X'Y / n (h :762-792)
+__global__ __launch_bounds__(256) void logit_xy_kernel(const double *__restrict__ xx, const double *__restrict__ beta, const double *__restrict__ g,
+                                                       const double *__restrict__ s, int p, int intercept, double n, int init, double *__restrict__ xy)
+{
+    const int q = p + (intercept ? 1 : 0);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= q) return;
+    const bool icpt = intercept && i == 0;
+    const int j = i - (intercept ? 1 : 0);
+    if (init) { xy[i] = icpt ? g[0] / n : (g[1 + j] * s[j]) / n; return; }
+    const double gr = icpt ? g[0] / n : (g[1 + j] / n) * s[j];
+    double a = 0.0;
+    for (int k = 0; k < q; ++k) a = fma(xx[(size_t)k * q + i], beta[k], a);
+    xy[i] = a + gr;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- threshold
+struct LogitPen {
+    PenK k;
+    const double *pf;         // q
+    const double *gw;         // ngroups (group weights, the reference's pen_fact(g) of the group operators)
+    const int *perm;          // q: coordinates ordered by group (members in index order)
+    const int *gstart;        // ngroups + 1: group g = perm[gstart[g] .. gstart[g + 1])
+    const int *gof;           // q: group index of a coordinate, -1 if its id is not among unique_groups (then beta = 0)
+    const int *gzero;         // ngroups: 1 if the group id is 0 (unpenalized, factor 1)
+    int ngroups;
+};
+
+__device__ __forceinline__ double elem_thr(const PenK &k, double u, double pf)
+{
+    const double tp = pf * k.L;
+    switch (k.kind) {
+    case K_MCP: return mcp1(u, tp, k.D, k.gamma);
+    case K_SCAD: return scad1(u, tp, k.D, k.gamma);
+    case K_OLS: return u / k.D;
+    default: return soft1(u, tp, k.D);
+    }
+}
+
+// beta[0..q) <- next_beta(u) (h :569-672) by one workgroup of any size; u is overwritten for the group operators (sparse.grp.lasso: with
+// its soft-thresholded copy); gf: LDS scratch of ngroups doubles.  Ends with a barrier.
+__device__ void logit_threshold(const LogitPen &P, double *u, double *beta, int q, double *gf)
+{
+    const PenK &k = P.k;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    if (k.kind < K_GRP) {
+        for (int i = tid; i < q; i += nt) beta[i] = elem_thr(k, u[i], P.pf[i]);
+        __syncthreads();
+        return;
+    }
+    if (k.kind == K_SGL) {                       // soft threshold with denominator 1 first (h :653-668)
+        for (int i = tid; i < q; i += nt) u[i] = soft1(u[i], P.pf[i] * k.L1, 1.0);
+        __syncthreads();
+    }
+    for (int g = tid; g < P.ngroups; g += nt) {
+        double f = 1.0;
+        if (!P.gzero[g]) {
+            double ss = 0.0;
+            for (int m = P.gstart[g]; m < P.gstart[g + 1]; ++m) { const double v = u[P.perm[m]]; ss += v * v; }
+            const double nrm = sqrt(ss), pen = k.L * P.gw[g];
+            if (k.kind == K_GRP_MCP) f = mcp_norm(nrm, pen, k.D, k.gamma);
+            else if (k.kind == K_GRP_SCAD) f = scad_norm(nrm, pen, k.D, k.gamma);
+            else f = fmax(0.0, 1.0 - pen / nrm);
+        }
+        gf[g] = f;
+    }
+    __syncthreads();
+    for (int i = tid; i < q; i += nt) {
+        const int g = P.gof[i];
+        const double f = g >= 0 ? gf[g] : 0.0;
+        beta[i] = f != 0.0 ? u[i] * f / k.D : 0.0;
+    }
+    __syncthreads();
+}
+
+// one workgroup, q <= LOGIT_WG_MAX: u = A beta_prev + XY, next_beta, stopRule -- until the rule or maxit; st[ST_ITERS] += iterations
+template <bool A_LDS>
+__global__ __launch_bounds__(1024) void logit_inner_kernel(const double *__restrict__ A, const double *__restrict__ xy, double *__restrict__ beta,
+                                                           int q, LogitPen P, int maxit, double tol, double *__restrict__ st)
+{
+    extern __shared__ double sh[];
+    double *bp = sh, *u = sh + q, *bn = sh + 2 * q, *gf = sh + 3 * q, *As = sh + 3 * q + (P.ngroups > 0 ? P.ngroups : 1);
+    const int i = threadIdx.x;
+    if (A_LDS) for (int k = i; k < q * q; k += 1024) As[k] = A[k];
+    if (i < q) bp[i] = beta[i];
+    const double xyi = i < q ? xy[i] : 0.0;
+    int it = 0;
+    for (int j = 0; j < maxit; ++j) {
+        __syncthreads();
+        if (i < q) {
+            double a = 0.0;
+            if (A_LDS) for (int k = 0; k < q; ++k) a = fma(As[k * q + i], bp[k], a);
+            else for (int k = 0; k < q; ++k) a = fma(A[(size_t)k * q + i], bp[k], a);
+            u[i] = a + xyi;
+        }
+        __syncthreads();
+        logit_threshold(P, u, bn, q, gf);
+        ++it;
+        const int go = __syncthreads_or(i < q && stop_violated(bn[i], bp[i], tol));
+        if (i < q) bp[i] = bn[i];
+        if (!go) break;
+    }
+    __syncthreads();
+    if (i < q) beta[i] = bp[i];
+    if (i == 0) st[ST_ITERS] += (double)it;
+}
+
+// launch form, after launch_gemv(A, beta_prev) -> u: u += XY, next_beta, stopRule; beta_prev <- beta; stop word set on convergence
+__global__ __launch_bounds__(1024) void logit_thresh_kernel(double *__restrict__ u, const double *__restrict__ xy, double *__restrict__ bp,
+                                                            int q, LogitPen P, double tol, int maxit, int *__restrict__ done, double *__restrict__ st)
+{
+    extern __shared__ double sh[];
+    double *us = sh, *bn = sh + q, *gf = sh + 2 * q;
+    if (*done) return;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < q; i += 1024) us[i] = u[i] + xy[i];
+    __syncthreads();
+    logit_threshold(P, us, bn, q, gf);
+    int v = 0;
+    for (int i = tid; i < q; i += 1024) v |= stop_violated(bn[i], bp[i], tol);
+    const int viol = __syncthreads_or(v);
+    for (int i = tid; i < q; i += 1024) bp[i] = bn[i];
+    if (tid == 0) {
+        st[ST_ITERS] += 1.0;
+        const int it = (int)st[ST_DONE] + 1;
+        st[ST_DONE] = it;
+        if (!viol || it >= maxit) *done = 1;
+    }
+}
+
+// IRLS stop: st[ST_IRLS_STOP] = stopRule(beta, beta_irls, irls_tol)
+__global__ __launch_bounds__(1024) void logit_irls_stop_kernel(const double *__restrict__ b, const double *__restrict__ bi, int q, double tol,
+                                                               double *__restrict__ st)
+{
+    int v = 0;
+    for (int i = threadIdx.x; i < q; i += 1024) v |= stop_violated(b[i], bi[i], tol);
+    const int viol = __syncthreads_or(v);
+    if (threadIdx.x == 0) st[ST_IRLS_STOP] = viol ? 0.0 : 1.0;
+}
+
+// get_beta (h :1038-1055): beta_j s_j on the original scale, the intercept as it is; row 0 = 0 without one
+__global__ __launch_bounds__(256) void logit_back_kernel(const double *__restrict__ beta, const double *__restrict__ s, int p, int intercept,
+                                                         double *__restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i > p) return;
+    if (i == 0) { out[0] = intercept ? beta[0] : 0.0; return; }
+    out[i] = beta[(intercept ? 1 : 0) + i - 1] * s[i - 1];
+}
+
+// colsq = sum x^2 / (n - 1), 0 -> 1, s = 1 / sqrt(colsq) (h :734-737); one workgroup per column, rank-order sum
+__global__ __launch_bounds__(256) void logit_scale_kernel(const double *__restrict__ x, int64_t n, int64_t ld, double *__restrict__ s)
+{
+    __shared__ double red[256];
+    const int j = blockIdx.x;
+    const double *col = x + (size_t)j * ld;
+    double a = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) a = fma(col[i], col[i], a);
+    red[threadIdx.x] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int k = 0; k < 256; ++k) t += red[k];
+        double cs = t / ((double)n - 1.0);
+        if (cs == 0.0) cs = 1.0;
+        s[j] = 1.0 / sqrt(cs);
+    }
+}
+
+__global__ void logit_fill_kernel(double *a, int n, double v)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) a[i] = v;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------- host driver
+struct LogitStats {
+    double ms_rows = 0, ms_gram = 0, ms_inner = 0, irls_steps = 0, inner_iters = 0, row_passes = 0, grams = 0, wall_ms = 0;
+};
+static thread_local LogitStats g_logit_stats;
+
+static int logit_rows(hipStream_t s, const LogitPlan &P, const double *x, int64_t n, int64_t ld, int p, const double *y, const double *beta,
+                      const double *sc, int intercept, int mode, int64_t irls_i, int64_t c0, int64_t nc, int64_t row0, double *z, int64_t ldz, double *part)
+{
+    const size_t lds = 8 * (size_t)p + (P.staged ? 8 * 65 * (size_t)p : 0);
+    if (P.staged) {
+        if (lds_limit_once(reinterpret_cast<const void *>(&logit_rows_kernel<true>), lds)) return OEMGPU_ERR_HIP;
+        hipLaunchKernelGGL(logit_rows_kernel<true>, dim3((unsigned)nc), dim3(256), lds, s, x, n, ld, p, y, beta, sc, intercept, mode, irls_i, P.ch, c0,
+                           row0, z, ldz, part);
+    } else {
+        if (lds_limit_once(reinterpret_cast<const void *>(&logit_rows_kernel<false>), lds)) return OEMGPU_ERR_HIP;
+        hipLaunchKernelGGL(logit_rows_kernel<false>, dim3((unsigned)nc), dim3(256), lds, s, x, n, ld, p, y, beta, sc, intercept, mode, irls_i, P.ch, c0,
+                           row0, z, ldz, part);
+    }
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+// checks that need no device: -1 / -4 before any device is looked for
+int logistic_check(int64_t n, int32_t p, int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o)
+{
+    const int q = p + (intercept ? 1 : 0);
+    int rc = check_opts_export(o, p, q);
+    if (rc) return rc;
+    if (n < 1) { set_error("fit_logistic_dense: bad n"); return OEMGPU_ERR_ARG; }
+    if (hessian_full != 0 && hessian_full != 1) { set_error("hessian.type must be \"upper.bound\" (0) or \"full\" (1)"); return OEMGPU_ERR_ARG; }
+    if (irls_maxit <= 0) { set_error("maxit and irls.maxit should be positive"); return OEMGPU_ERR_ARG; }       // ref R/oem.R:427-430
+    if (!(irls_tol >= 0.0)) { set_error("tol and irls.tol should be nonnegative"); return OEMGPU_ERR_ARG; }
+    if ((int64_t)q >= n) {
+        set_error("fit_logistic_dense: p + intercept >= n is not supported (the reference's XWXt branch iterates on the raw labels, "
+                  "ref src/oem_logistic_dense.h:524-566)");
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    if (p > LOGIT_P_MAX) { set_error("fit_logistic_dense: p > %d is not supported", LOGIT_P_MAX); return OEMGPU_ERR_UNSUPPORTED; }
+    return 0;
+}
+
+static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int32_t p, const double *y, int32_t standardize, int32_t intercept,
+                     int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
+                     double *beta_out, double *lambda_out, int32_t *niter, double *loss_out, double *d_out)
+{
+    const double t_start = now_ms();
+    g_logit_stats = LogitStats();
+    const int q = p + (intercept ? 1 : 0), o1 = intercept ? 1 : 0;
+    const int nl = (o->lambda_user && o->nlambda_user > 0) ? o->nlambda_user : o->nlambda;
+    const bool provided = o->lambda_user && o->nlambda_user > 0;
+    const LogitPlan P = logit_plan(n, p, intercept, c->num_cu);
+    // ---- host-side tables: penalty factors (0 for the intercept), groups ordered, group weights (default sqrt(size), 0 for group 0)
+    std::vector<double> pf(q);
+    for (int j = 0; j < p; ++j) pf[o1 + j] = o->penalty_factor[j];
+    if (intercept) pf[0] = 0.0;
+    bool any_grp = false;
+    for (int k = 0; k < o->npen; ++k) any_grp |= pen_is_grp(o->penalty[k]);
+    const int ng = any_grp ? o->ngroups : 0;
+    std::vector<int> perm, gstart(ng + 1, 0), gof(q, -1), gzero(ng > 0 ? ng : 1, 0);
+    std::vector<double> gw(ng > 0 ? ng : 1, 0.0);
+    if (any_grp) {
+        for (int g = 0; g < ng; ++g) {                       // get_group_indexes (h :397-439)
+            gstart[g] = (int)perm.size();
+            for (int v = 0; v < q; ++v)
+                if (o->groups[v] == o->unique_groups[g]) { perm.push_back(v); if (gof[v] < 0) gof[v] = g; }
+            gstart[g + 1] = (int)perm.size();
+            gzero[g] = o->unique_groups[g] == 0;
+            gw[g] = o->n_group_weights > 0 ? o->group_weights[g] : (gzero[g] ? 0.0 : std::sqrt((double)(gstart[g + 1] - gstart[g])));
+        }
+    }
+    const int nperm = (int)perm.size();
+    if (nperm > q) { set_error("fit_logistic_dense: unique_groups has repeated ids"); return OEMGPU_ERR_ARG; }
+    // ---- workspace (c->aux; oemgpu_eig_max_dev takes c->ws from its start)
+    Bump B;
+    const size_t a_s = B.take(8 * (size_t)p), a_b = B.take(8 * (size_t)q), a_bi = B.take(8 * (size_t)q),
+                 a_u = B.take(8 * (size_t)q), a_xy = B.take(8 * (size_t)q), a_xx = B.take(8 * (size_t)q * q), a_a = B.take(8 * (size_t)q * q),
+                 a_g = B.take(8 * (size_t)(p + 2)), a_part = B.take(8 * (size_t)P.nchunk * (p + 2)), a_z = B.take(8 * (size_t)P.rbz * q);
+    const size_t m2 = (size_t)(q + 2) * (q + 2);
+    const GramPlan gpb = gram_plan_bound(P.rbz < n ? P.rbz : n, q, c->num_cu);
+    const size_t a_mb = B.take(8 * m2), a_ma = B.take(8 * m2), a_tp = B.take(8 * gpb.tpart_doubles), a_vp = B.take(8 * gpb.vpart_doubles),
+                 a_st = B.take(8 * ST_LEN), a_done = B.take(256);
+    const size_t a_pf = B.take(8 * (size_t)q), a_gw = B.take(8 * (size_t)(ng > 0 ? ng : 1)), a_perm = B.take(4 * (size_t)(q + 1)),
+                 a_gs = B.take(4 * (size_t)(ng + 1)), a_gof = B.take(4 * (size_t)q), a_gz = B.take(4 * (size_t)(ng > 0 ? ng : 1));
+    const size_t a_out = B.take(8 * (size_t)o->npen * nl * (p + 1));
+    if (ctx_grow(c, &c->aux, &c->aux_bytes, B.off)) return OEMGPU_ERR_HIP;
+    char *W = c->aux;
+    double *sc = (double *)(W + a_s), *beta = (double *)(W + a_b), *birls = (double *)(W + a_bi), *u = (double *)(W + a_u),
+           *xy = (double *)(W + a_xy), *xx = (double *)(W + a_xx), *A = (double *)(W + a_a), *g = (double *)(W + a_g), *part = (double *)(W + a_part),
+           *z = (double *)(W + a_z), *mb = (double *)(W + a_mb), *ma = (double *)(W + a_ma), *st = (double *)(W + a_st), *bout = (double *)(W + a_out);
+    int *done = (int *)(W + a_done);
+    hipStream_t s = c->stream;
+    OEM_HIP(hipMemcpyAsync(W + a_pf, pf.data(), 8 * (size_t)q, hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemcpyAsync(W + a_gw, gw.data(), 8 * gw.size(), hipMemcpyHostToDevice, s));
+    if (nperm) OEM_HIP(hipMemcpyAsync(W + a_perm, perm.data(), 4 * (size_t)nperm, hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemcpyAsync(W + a_gs, gstart.data(), 4 * gstart.size(), hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemcpyAsync(W + a_gof, gof.data(), 4 * (size_t)q, hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemcpyAsync(W + a_gz, gzero.data(), 4 * gzero.size(), hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemsetAsync(bout, 0, 8 * (size_t)o->npen * nl * (p + 1), s));
+    OEM_HIP(hipMemsetAsync(st, 0, 8 * ST_LEN, s));
+    // ---- init_oem: s, XY = s o X'Y / n, lambda_0
+    if (standardize) hipLaunchKernelGGL(logit_scale_kernel, dim3(p), dim3(256), 0, s, x, n, ld, sc);
+    else hipLaunchKernelGGL(logit_fill_kernel, dim3((p + 255) / 256), dim3(256), 0, s, sc, p, 1.0);
+    OEM_HIP(hipGetLastError());
+    int rc = logit_rows(s, P, x, n, ld, p, y, beta, sc, intercept, 0, -1, 0, P.nchunk, 0, nullptr, 0, part);
+    if (rc) return rc;
+    hipLaunchKernelGGL(logit_sum_kernel, dim3((p + 2 + 255) / 256), dim3(256), 0, s, part, P.nchunk, p + 2, g);
+    hipLaunchKernelGGL(logit_xy_kernel, dim3((q + 255) / 256), dim3(256), 0, s, xx, beta, g, sc, p, intercept, (double)n, 1, xy);
+    OEM_HIP(hipGetLastError());
+    std::vector<double> hxy(q);
+    OEM_HIP(hipMemcpyAsync(hxy.data(), xy, 8 * (size_t)q, hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipStreamSynchronize(s));
+    double lmax = 0.0;
+    for (int j = o1; j < q; ++j) lmax = std::fmax(lmax, std::fabs(hxy[j]));       // h :795-805
+    std::vector<double> base(nl);
+    if (!provided) {                                                              // cpp :164-171: exp(linspace(log lmax, log lmin))
+        const double lmin = o->lambda_min_ratio * lmax, a = std::log(lmax), b = std::log(lmin);
+        for (int i = 0; i < nl; ++i) base[i] = std::exp(nl > 1 ? (i == nl - 1 ? b : a + (b - a) / (double)(nl - 1) * (double)i) : a);
+    }
+    LogitPen LP;
+    LP.pf = (const double *)(W + a_pf); LP.gw = (const double *)(W + a_gw); LP.perm = (const int *)(W + a_perm);
+    LP.gstart = (const int *)(W + a_gs); LP.gof = (const int *)(W + a_gof); LP.gzero = (const int *)(W + a_gz); LP.ngroups = ng;
+    double d = 0.0;
+    std::vector<double> lam(nl);
+    hipEvent_t ev[2];
+    const bool timing = c->timing;
+    if (timing) { OEM_HIP(hipEventCreate(&ev[0])); OEM_HIP(hipEventCreate(&ev[1])); }
+    auto stage = [&](double *acc, auto &&fn) -> int {
+        if (timing) (void)hipEventRecord(ev[0], s);
+        int r = fn();
+        if (r) return r;
+        if (timing) {
+            (void)hipEventRecord(ev[1], s);
+            if (hipEventSynchronize(ev[1]) != hipSuccess) { set_error("hipEventSynchronize failed"); return OEMGPU_ERR_HIP; }
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+            *acc += ms;
+        }
+        return 0;
+    };
+    int interrupted = 0;
+    for (int k = 0; k < o->npen && !rc && !interrupted; ++k) {
+        const int pen = o->penalty[k];
+        const bool is_ols = pen == OEMGPU_OLS;
+        const int nlk = is_ols ? 1 : nl;
+        // the lambda row of this penalty (cpp :205-225)
+        if (provided) for (int i = 0; i < nl; ++i) lam[i] = o->lambda_user[(size_t)k * nl + i];
+        else {
+            const bool net = pen_is_net(pen), ncv = pen == OEMGPU_MCP || pen == OEMGPU_SCAD || pen == OEMGPU_MCP_NET || pen == OEMGPU_SCAD_NET ||
+                                                    pen == OEMGPU_GRP_MCP || pen == OEMGPU_GRP_SCAD || pen == OEMGPU_GRP_MCP_NET || pen == OEMGPU_GRP_SCAD_NET;
+            for (int i = 0; i < nl; ++i) {
+                lam[i] = base[i];
+                if (net) {
+                    lam[i] = base[i] / o->alpha;
+                    if (ncv) {
+                        const double fact = 3.5 - std::fmin(3.5, o->gamma) * 5.71425 / 8.0;
+                        lam[i] = fact * base[i] / std::pow(o->alpha, 0.8);
+                    }
+                }
+            }
+        }
+        for (int i = 0; i < nl; ++i) lambda_out[(size_t)k * nl + i] = lam[i];
+        OEM_HIP(hipMemsetAsync(beta, 0, 8 * (size_t)q, s));                        // init(): cold start (h :813)
+        for (int li = 0; li < nlk && !rc && !interrupted; ++li) {
+            int i;
+            double loss_now = 1e99;
+            for (i = 0; i < irls_maxit; ++i) {
+                if (o->interrupt && o->interrupt(o->interrupt_arg)) { interrupted = 1; break; }
+                OEM_HIP(hipMemcpyAsync(birls, beta, 8 * (size_t)q, hipMemcpyDeviceToDevice, s));
+                if (!(i == 0 && li > 0)) {
+                    const bool need_xx = (i == 0 && li == 0) || hessian_full;
+                    rc = stage(&g_logit_stats.ms_rows, [&]() -> int {
+                        if (!need_xx) return logit_rows(s, P, x, n, ld, p, y, beta, sc, intercept, 1, i, 0, P.nchunk, 0, nullptr, 0, part);
+                        return 0;
+                    });
+                    if (rc) break;
+                    if (need_xx) {
+                        // Z row blocks: row pass (writes Z and the partials of its chunks) -> moment pass -> running sum in block order
+                        rc = stage(&g_logit_stats.ms_gram, [&]() -> int {
+                            for (int64_t b = 0; b < P.nzblk; ++b) {
+                                const int64_t c0 = b * (P.rbz / P.ch), c1 = std::min<int64_t>(P.nchunk, c0 + P.rbz / P.ch);
+                                const int64_t r0 = c0 * P.ch, rows = std::min<int64_t>(n, c1 * P.ch) - r0;
+                                int r = logit_rows(s, P, x, n, ld, p, y, beta, sc, intercept, 1, i, c0, c1 - c0, r0, z, P.rbz, part);
+                                if (r) return r;
+                                const GramPlan gpl = gram_plan(rows, q, c->num_cu);
+                                r = launch_gram(s, gpl, z, rows, P.rbz, z, nullptr, (double *)(W + a_tp), (double *)(W + a_vp));
+                                if (!r) r = launch_moments_reduce(s, gpl, (double *)(W + a_tp), (double *)(W + a_vp), mb);
+                                if (r) return r;
+                                hipLaunchKernelGGL(logit_mom_add_kernel, dim3((unsigned)((m2 + 255) / 256)), dim3(256), 0, s, ma, mb, m2, b == 0 ? 1 : 0);
+                            }
+                            hipLaunchKernelGGL(logit_xx_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, ma, q, (double)n, xx);
+                            OEM_HIP(hipGetLastError());
+                            double lm = 0.0;
+                            int r = oemgpu_eig_max_dev(c, xx, q, &lm);              // (synchronises)
+                            if (r) return r;
+                            d = lm * 1.0005;                                         // h :514
+                            hipLaunchKernelGGL(logit_a_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, xx, q, d, A);
+                            OEM_HIP(hipGetLastError());
+                            return 0;
+                        });
+                        if (rc) break;
+                        g_logit_stats.grams += 1;
+                    }
+                    g_logit_stats.row_passes += 1;
+                    hipLaunchKernelGGL(logit_sum_kernel, dim3((p + 2 + 255) / 256), dim3(256), 0, s, part, P.nchunk, p + 2, g);
+                    hipLaunchKernelGGL(logit_xy_kernel, dim3((q + 255) / 256), dim3(256), 0, s, xx, beta, g, sc, p, intercept, (double)n, 0, xy);
+                    OEM_HIP(hipGetLastError());
+                }
+                // the OEM loop at this lambda (h :1010-1022)
+                PenK pk;
+                {
+                    const double lamv = lam[li], al = o->alpha, ta = o->tau;
+                    pk.gamma = o->gamma; pk.L1 = 0.0; pk.L = lamv; pk.D = d; pk.kind = K_SOFT;
+                    const double Ln = lamv * al, Dn = d + (1.0 - al) * lamv;
+                    switch (pen) {
+                    case OEMGPU_LASSO: break;
+                    case OEMGPU_OLS: pk.kind = K_OLS; break;
+                    case OEMGPU_ELASTIC_NET: pk.L = Ln; pk.D = Dn; break;
+                    case OEMGPU_SCAD: pk.kind = K_SCAD; break;
+                    case OEMGPU_SCAD_NET: pk.kind = K_SCAD; pk.L = Ln; pk.D = Dn; if (al == 0.0) { pk.L = 0.0; pk.D = d + lamv; } break;
+                    case OEMGPU_MCP: pk.kind = K_MCP; break;
+                    case OEMGPU_MCP_NET: pk.kind = K_MCP; pk.L = Ln; pk.D = Dn; break;
+                    case OEMGPU_GRP_LASSO: pk.kind = K_GRP; break;
+                    case OEMGPU_GRP_LASSO_NET: pk.kind = K_GRP; pk.L = Ln; pk.D = Dn; break;
+                    case OEMGPU_GRP_MCP: pk.kind = K_GRP_MCP; break;
+                    case OEMGPU_GRP_SCAD: pk.kind = K_GRP_SCAD; break;
+                    case OEMGPU_GRP_MCP_NET: pk.kind = K_GRP_MCP; pk.L = Ln; pk.D = Dn; break;
+                    case OEMGPU_GRP_SCAD_NET: pk.kind = K_GRP_SCAD; pk.L = Ln; pk.D = Dn; break;
+                    case OEMGPU_SPARSE_GRP_LASSO: pk.kind = K_SGL; pk.L = (1.0 - ta) * lamv; pk.L1 = ta * lamv; break;
+                    default: break;
+                    }
+                }
+                LP.k = pk;
+                rc = stage(&g_logit_stats.ms_inner, [&]() -> int {
+                    if (P.inner_wg) {
+                        const bool alds = q <= LOGIT_A_LDS_Q;
+                        const size_t lds = 8 * (size_t)(3 * q + (ng > 0 ? ng : 1) + (alds ? q * q : 0));
+                        if (alds) {
+                            if (lds_limit_once(reinterpret_cast<const void *>(&logit_inner_kernel<true>), lds)) return OEMGPU_ERR_HIP;
+                            hipLaunchKernelGGL(logit_inner_kernel<true>, dim3(1), dim3(1024), lds, s, A, xy, beta, q, LP, o->maxit, o->tol, st);
+                        } else {
+                            if (lds_limit_once(reinterpret_cast<const void *>(&logit_inner_kernel<false>), lds)) return OEMGPU_ERR_HIP;
+                            hipLaunchKernelGGL(logit_inner_kernel<false>, dim3(1), dim3(1024), lds, s, A, xy, beta, q, LP, o->maxit, o->tol, st);
+                        }
+                        OEM_HIP(hipGetLastError());
+                        return 0;
+                    }
+                    // launch per iteration: beta is the loop's beta_prev (bp), u the product
+                    OEM_HIP(hipMemsetAsync(done, 0, 4, s));
+                    hipLaunchKernelGGL(logit_fill_kernel, dim3(1), dim3(256), 0, s, st + ST_DONE, 1, 0.0);
+                    const size_t lds = 8 * (size_t)(2 * q + (ng > 0 ? ng : 1));
+                    if (lds_limit_once(reinterpret_cast<const void *>(&logit_thresh_kernel), lds)) return OEMGPU_ERR_HIP;
+                    for (int j0 = 0; j0 < o->maxit; j0 += LOGIT_BATCH) {
+                        const int nb = std::min(LOGIT_BATCH, o->maxit - j0);
+                        for (int jj = 0; jj < nb; ++jj) {
+                            int r = launch_gemv_sym(s, A, q, beta, u, done, c->num_cu);
+                            if (r) return r;
+                            hipLaunchKernelGGL(logit_thresh_kernel, dim3(1), dim3(1024), lds, s, u, xy, beta, q, LP, o->tol, o->maxit, done, st);
+                        }
+                        OEM_HIP(hipGetLastError());
+                        int hd = 0;
+                        OEM_HIP(hipMemcpyAsync(&hd, done, 4, hipMemcpyDeviceToHost, s));
+                        OEM_HIP(hipStreamSynchronize(s));
+                        if (hd) break;
+                    }
+                    return 0;
+                });
+                if (rc) break;
+                hipLaunchKernelGGL(logit_irls_stop_kernel, dim3(1), dim3(1024), 0, s, beta, birls, q, irls_tol, st);
+                OEM_HIP(hipGetLastError());
+                double hst[ST_LEN];
+                OEM_HIP(hipMemcpyAsync(hst, st, sizeof hst, hipMemcpyDeviceToHost, s));
+                OEM_HIP(hipStreamSynchronize(s));                            // the one host sync of an IRLS step
+                g_logit_stats.irls_steps += 1;
+                if (hst[ST_IRLS_STOP] != 0.0) break;
+            }
+            if (rc || interrupted) break;
+            // the loss of the LAST prob computed: the partials' last entry of the most recent row pass
+            if (o->compute_loss) {
+                double gl = 0.0;
+                OEM_HIP(hipMemcpyAsync(&gl, g + p + 1, 8, hipMemcpyDeviceToHost, s));
+                OEM_HIP(hipStreamSynchronize(s));
+                loss_now = gl;
+            }
+            niter[(size_t)k * nl + li] = i + 1;
+            loss_out[(size_t)k * nl + li] = loss_now;
+            hipLaunchKernelGGL(logit_back_kernel, dim3((p + 1 + 255) / 256), dim3(256), 0, s, beta, sc, p, intercept, bout + ((size_t)k * nl + li) * (p + 1));
+            OEM_HIP(hipGetLastError());
+        }
+        if (!rc && !interrupted) {
+            for (int li = nlk; li < nl; ++li) { niter[(size_t)k * nl + li] = 0; loss_out[(size_t)k * nl + li] = 0.0; }
+        }
+    }
+    if (timing) { (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]); }
+    if (!rc && interrupted) { (void)hipStreamSynchronize(s); set_error("interrupted"); return OEMGPU_ERR_INTERRUPTED; }
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    OEM_HIP(hipMemcpyAsync(beta_out, bout, 8 * (size_t)o->npen * nl * (p + 1), hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipStreamSynchronize(s));
+    double hst[ST_LEN];
+    OEM_HIP(hipMemcpy(hst, st, sizeof hst, hipMemcpyDeviceToHost));
+    g_logit_stats.inner_iters = hst[ST_ITERS];
+    g_logit_stats.wall_ms = now_ms() - t_start;
+    *d_out = d;
+    return 0;
+}
+
+}  // namespace oemgpu
+
+using namespace oemgpu;
+
+extern "C" {
+#pragma GCC visibility push(default)
+
+int oemgpu_fit_logistic_dense_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev, int32_t standardize,
+                                  int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
+                                  double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+{
+    if (!c || !x_dev || !y_dev || !o || !beta || !lambda_out || !niter || !loss || !d) { set_error("fit_logistic_dense: NULL argument"); return OEMGPU_ERR_ARG; }
+    int rc = logistic_check(n, p, intercept, hessian_full, irls_maxit, irls_tol, o);
+    if (rc) return rc;
+    if (ld < n) { set_error("fit_logistic_dense: ld < n"); return OEMGPU_ERR_ARG; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    return logistic_fit_dev(c, x_dev, n, ld, p, y_dev, standardize, intercept, hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
+}
+
+int oemgpu_fit_logistic_dense(const double *x, int64_t n, int32_t p, const double *y, int32_t standardize, int32_t intercept, int32_t hessian_full,
+                              int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
+                              double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+{
+    if (!x || !y || !o || !beta || !lambda_out || !niter || !loss || !d) { set_error("fit_logistic_dense: NULL argument"); return OEMGPU_ERR_ARG; }
+    int rc = logistic_check(n, p, intercept, hessian_full, irls_maxit, irls_tol, o);
+    if (rc) return rc;
+    oemgpu_ctx *c = ctx_acquire(o->device);
+    if (!c) return OEMGPU_ERR_NO_DEVICE;
+    double *xd = nullptr, *yd = nullptr;
+    int64_t ld = 0;
+    rc = host_upload_resident(c, x, n, p, y, o, &xd, &ld, &yd, 0, true);
+    if (!rc) rc = logistic_fit_dev(c, xd, n, ld, p, yd, standardize, intercept, hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
+    (void)hipStreamSynchronize(c->stream);
+    ctx_release(c);
+    return rc;
+}
+
+int oemgpu_selftest_logistic_plan(int64_t n, int32_t p, int32_t intercept, int32_t hessian_full, int32_t num_cu, int64_t *out)
+{
+    if (n < 1 || p < 1 || num_cu < 1 || !out || (hessian_full != 0 && hessian_full != 1)) { set_error("selftest_logistic_plan: bad argument"); return OEMGPU_ERR_ARG; }
+    const LogitPlan P = logit_plan(n, p, intercept, num_cu);
+    const int q = p + (intercept ? 1 : 0);
+    out[0] = P.ch; out[1] = P.nchunk; out[2] = P.rbz; out[3] = P.nzblk; out[4] = P.inner_wg; out[5] = P.staged;
+    out[6] = (int64_t)P.ws_bytes;
+    // the bound: the fixed pieces (q^2 matrices, chunk partials, moments) plus a Z block of at most LOGIT_Z_BYTES or one chunk of rows
+    const size_t zb = std::max(LOGIT_Z_BYTES, (size_t)P.ch * q * 8);
+    out[7] = (int64_t)(zb + 8 * ((size_t)q * q * 2 + (size_t)(q + 2) * (q + 2) * 2 + (size_t)P.nchunk * (p + 2) + 16 * (size_t)q + (size_t)p + 64) +
+                       8 * (gram_plan_bound(P.rbz < n ? P.rbz : n, q, num_cu).tpart_doubles + gram_plan_bound(P.rbz < n ? P.rbz : n, q, num_cu).vpart_doubles) + 64 * 256);
+    (void)hessian_full;
+    return 0;
+}
+
+int oemgpu_last_logistic_stats(double *out)
+{
+    if (!out) { set_error("last_logistic_stats: NULL"); return OEMGPU_ERR_ARG; }
+    const LogitStats &s = g_logit_stats;
+    out[0] = s.ms_rows; out[1] = s.ms_gram; out[2] = s.ms_inner; out[3] = s.irls_steps; out[4] = s.inner_iters; out[5] = s.row_passes;
+    out[6] = s.grams; out[7] = s.wall_ms;
+    return 0;
+}
+
+#pragma GCC visibility pop
+}

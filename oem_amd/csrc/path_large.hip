@@ -715,6 +715,12 @@ __global__ __launch_bounds__(1024) void lanczos_update_reg_kernel(int q, int j, 
 
 }  // namespace
 
+// launch_gemv for other translation units (logistic.hip: the inner solve's launch form)
+int launch_gemv_sym(hipStream_t s, const double *M, int q, const double *vec, double *out, const int *done, int num_cu)
+{
+    return launch_gemv(s, M, q, vec, out, done, num_cu);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Fused iteration (element-wise penalties, q = 512 / 1024 / 2048 / 4096, no accelerate / loss / scale.factor):
 // ONE kernel per OEM iteration -- g = XX beta streamed exactly like gemv_sym_kernel, and the wave that finishes row r
