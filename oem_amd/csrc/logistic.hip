@@ -23,7 +23,8 @@
 //   * logit_sum_kernel: the partials summed in chunk order (two calls give the same bits);
 //   * logit_inner_kernel: q <= LOGIT_WG_MAX: the OEM loop of one lambda from a warm start in ONE workgroup (A in LDS when it fits),
 //     to stopRule or maxit; beyond that launch_gemv (path_large.hip) + logit_thresh_kernel per iteration, batches of LOGIT_BATCH
-//     launches between looks at the stop word;
+//     launches between looks at the stop word.  The threshold's scratch (u + XY, the new beta, a factor per group) is in LDS when its
+//     8 (2 q + ngroups) bytes fit LOGIT_LDS_BYTES, else in the workspace (one group per coordinate at p >= 6826);
 //   * small kernels: XX from the moments, A = dI - XX, XY = XX beta + grad, the IRLS stop, the back-transform.
 #include "ctx.hpp"
 #include "penalty_ops.hpp"
@@ -41,6 +42,7 @@ static const int LOGIT_STAGE_P = 192;          // p up to which a 64-row sub-blo
 static const int LOGIT_A_LDS_Q = 110;          // q up to which the inner kernel keeps A in LDS (8 q^2 bytes)
 static const int LOGIT_BATCH = 16;             // launch form: iterations enqueued between looks at the stop word
 static const size_t LOGIT_Z_BYTES = (size_t)256 << 20;   // Z row blocks: at most this much (or one chunk of rows)
+static const size_t LOGIT_LDS_BYTES = (size_t)160 << 10;  // LDS of a gfx950 CU: the most one workgroup may ask for
 
 // state words (doubles) shared between the kernels and the host
 enum { ST_LOSS = 0, ST_ITERS = 1, ST_IRLS_STOP = 2, ST_DONE = 3, ST_LEN = 8 };
@@ -54,6 +56,12 @@ struct LogitPlan {
     int staged;        // 1: the row pass stages its 64-row sub-blocks in LDS
     size_t ws_bytes;   // device workspace of a call (c->aux)
 };
+
+// launch form: the threshold kernel's scratch (us, bn: q each; gf: ngroups) in LDS when it fits, else in the workspace
+static bool logit_thr_in_lds(int q, int ngroups)
+{
+    return 8 * (size_t)(2 * q + (ngroups > 0 ? ngroups : 1)) <= LOGIT_LDS_BYTES;
+}
 
 static LogitPlan logit_plan(int64_t n, int p, int intercept, int num_cu)
 {
@@ -84,6 +92,7 @@ static LogitPlan logit_plan(int64_t n, int p, int intercept, int num_cu)
     B.take(8 * gp.tpart_doubles); B.take(8 * gp.vpart_doubles);
     B.take(8 * ST_LEN); B.take(256);                        // state words, the stop word of the launch form
     B.take(8 * (size_t)q * 2 + 4 * (size_t)q * 3 + 4 * (size_t)(q + 1) + 8);   // pf, group weights, perm / group of / starts, ngroups
+    if (!P.inner_wg && !logit_thr_in_lds(q, q)) B.take(8 * (size_t)q * 3);      // threshold scratch at the most groups (one per coordinate)
     P.ws_bytes = B.off;
     return P;
 }
@@ -333,12 +342,16 @@ __global__ __launch_bounds__(1024) void logit_inner_kernel(const double *__restr
     if (i == 0) st[ST_ITERS] += (double)it;
 }
 
-// launch form, after launch_gemv(A, beta_prev) -> u: u += XY, next_beta, stopRule; beta_prev <- beta; stop word set on convergence
+// launch form, after launch_gemv(A, beta_prev) -> u: u += XY, next_beta, stopRule; beta_prev <- beta; stop word set on convergence.
+// LDS: scratch [us | bn | gf] in dynamic LDS; else in gws (2 q + ngroups doubles of the workspace)
+template <bool LDS>
 __global__ __launch_bounds__(1024) void logit_thresh_kernel(double *__restrict__ u, const double *__restrict__ xy, double *__restrict__ bp,
-                                                            int q, LogitPen P, double tol, int maxit, int *__restrict__ done, double *__restrict__ st)
+                                                            int q, LogitPen P, double tol, int maxit, int *__restrict__ done, double *__restrict__ st,
+                                                            double *__restrict__ gws)
 {
     extern __shared__ double sh[];
-    double *us = sh, *bn = sh + q, *gf = sh + 2 * q;
+    double *const base = LDS ? sh : gws;
+    double *us = base, *bn = base + q, *gf = base + 2 * q;
     if (*done) return;
     const int tid = threadIdx.x;
     for (int i = tid; i < q; i += 1024) us[i] = u[i] + xy[i];
@@ -489,6 +502,8 @@ int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int3
                  a_st = B.take(8 * ST_LEN), a_done = B.take(256);
     const size_t a_pf = B.take(8 * (size_t)q), a_gw = B.take(8 * (size_t)(ng > 0 ? ng : 1)), a_perm = B.take(4 * (size_t)(q + 1)),
                  a_gs = B.take(4 * (size_t)(ng + 1)), a_gof = B.take(4 * (size_t)q), a_gz = B.take(4 * (size_t)(ng > 0 ? ng : 1));
+    const bool thr_lds = logit_thr_in_lds(q, ng);
+    const size_t a_thr = (!P.inner_wg && !thr_lds) ? B.take(8 * (size_t)(2 * q + (ng > 0 ? ng : 1))) : 0;
     const size_t a_out = B.take(8 * (size_t)o->npen * nl * (p + 1));
     if (ctx_grow(c, &c->aux, &c->aux_bytes, B.off)) return OEMGPU_ERR_HIP;
     char *W = c->aux;
@@ -655,14 +670,18 @@ int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int3
                     // launch per iteration: beta is the loop's beta_prev (bp), u the product
                     OEM_HIP(hipMemsetAsync(done, 0, 4, s));
                     hipLaunchKernelGGL(logit_fill_kernel, dim3(1), dim3(256), 0, s, st + ST_DONE, 1, 0.0);
-                    const size_t lds = 8 * (size_t)(2 * q + (ng > 0 ? ng : 1));
-                    if (lds_limit_once(reinterpret_cast<const void *>(&logit_thresh_kernel), lds)) return OEMGPU_ERR_HIP;
+                    const size_t lds = thr_lds ? 8 * (size_t)(2 * q + (ng > 0 ? ng : 1)) : 0;
+                    double *gws = thr_lds ? nullptr : (double *)(W + a_thr);
+                    if (thr_lds && lds_limit_once(reinterpret_cast<const void *>(&logit_thresh_kernel<true>), lds)) return OEMGPU_ERR_HIP;
                     for (int j0 = 0; j0 < o->maxit; j0 += LOGIT_BATCH) {
                         const int nb = std::min(LOGIT_BATCH, o->maxit - j0);
                         for (int jj = 0; jj < nb; ++jj) {
                             int r = launch_gemv_sym(s, A, q, beta, u, done, c->num_cu);
                             if (r) return r;
-                            hipLaunchKernelGGL(logit_thresh_kernel, dim3(1), dim3(1024), lds, s, u, xy, beta, q, LP, o->tol, o->maxit, done, st);
+                            if (thr_lds)
+                                hipLaunchKernelGGL(logit_thresh_kernel<true>, dim3(1), dim3(1024), lds, s, u, xy, beta, q, LP, o->tol, o->maxit, done, st, gws);
+                            else
+                                hipLaunchKernelGGL(logit_thresh_kernel<false>, dim3(1), dim3(1024), 0, s, u, xy, beta, q, LP, o->tol, o->maxit, done, st, gws);
                         }
                         OEM_HIP(hipGetLastError());
                         int hd = 0;

@@ -9,6 +9,9 @@ conditions of the penalised logistic likelihood, scikit-learn).  Quirks are kept
   * XX, d = 1.0005 lambda_max(XX), A only at (i == 0 and the first lambda) or for hessian "full" (h :964-965);
   * on a lambda after the first, the first IRLS step skips prob / XX / grad / XY (h :861);
   * niter = i + 1 (irls_maxit + 1 at the cap); loss = get_loss of the LAST prob computed (h :1057-1090); d = the last d.
+`stats` (optional dict) counts what ran: irls (IRLS steps), inner (OEM iterations), rows (row passes: IRLS steps that are not the
+skipped first step of a later lambda), grams (Hessian builds), floored (weights the W floor changed), clamped (terms of the reported
+losses that took a 1e-5 clamp).
 """
 import numpy as np
 
@@ -124,6 +127,11 @@ def next_beta(pen, u, lam, d, pf, alpha, gamma, tau, grp):
     return _block(u, L, D, kind, gamma, gidx, gw, gzero, q)
 
 
+def _clamped(y, prob):
+    """terms of get_loss that take the log(1 / 1e-5) branch"""
+    return int(np.sum(np.where(y == 1, prob <= 1e-5, prob > 1.0 - 1e-5)))
+
+
 def _loss(y, prob):
     """get_loss, ref h :1057-1090"""
     l1 = np.where(prob > 1e-5, np.log(1.0 / np.maximum(prob, 1e-300)), np.log(1.0 / 1e-5))
@@ -180,7 +188,8 @@ def fit(x, y, penalty=("lasso",), lambda_=None, nlambda=100, lambda_min_ratio=1e
     out = dict(beta=[], **{"lambda": []}, niter=[], loss=[], d=0.0)
     d = 0.0
     st = stats if stats is not None else {}
-    st.setdefault("irls", 0); st.setdefault("inner", 0)
+    for key in ("irls", "inner", "rows", "grams", "floored", "clamped"):
+        st.setdefault(key, 0)
     for k, pen in enumerate(penalty):
         if provided:
             lam = np.asarray(lambda_[k], dtype=np.float64)
@@ -205,9 +214,12 @@ def fit(x, y, penalty=("lasso",), lambda_=None, nlambda=100, lambda_min_ratio=1e
                     eta = x @ (beta[o:] * s) + (beta[0] if intercept else 0.0)
                     prob = 1.0 / (1.0 + np.exp(-eta))
                     W = prob * (1.0 - prob)
+                    st["rows"] += 1
                     if i < n and W[i] < 1e-5:
                         W[i] = 1e-5
+                        st["floored"] += 1
                     if (i == 0 and li == 0) or hessian_full:
+                        st["grams"] += 1
                         sw = np.sqrt(W)
                         Z = sw[:, None] * (x * s)
                         if intercept:
@@ -236,6 +248,7 @@ def fit(x, y, penalty=("lasso",), lambda_=None, nlambda=100, lambda_min_ratio=1e
             NI[li] = i + 1
             if compute_loss:
                 LO[li] = _loss(y, prob)
+                st["clamped"] += _clamped(y, prob)
             B[0, li] = beta[0] if intercept else 0.0
             B[1:, li] = beta[o:] * s
         if pen == "ols":
@@ -245,3 +258,20 @@ def fit(x, y, penalty=("lasso",), lambda_=None, nlambda=100, lambda_min_ratio=1e
         out["lambda"].append(np.asarray(lam, dtype=np.float64))
     out["d"] = d
     return out
+
+
+def near_separable(n, p, seed, k=4):
+    """Gaussian x whose rows 0-9 sit far out along the true beta (|eta| 20-40 under it); rows 0-6 are labelled as the true beta says,
+    rows 7-9 against it.  Once a fit has grown, the W floor (row i at IRLS step i) and the loss clamps of the mislabelled rows fire."""
+    rng = np.random.default_rng(seed)
+    x = rng.normal(size=(n, p))
+    b = np.zeros(p)
+    b[:k] = rng.choice([-1.0, 1.0], k) * rng.uniform(0.5, 1.0, k)
+    sgn = rng.choice([-1.0, 1.0], 10)
+    eta_far = sgn * rng.uniform(20.0, 40.0, 10)
+    x[:10] = np.outer(eta_far / float(b @ b), b) + 0.1 * rng.normal(size=(10, p))
+    eta = x @ b
+    y = (rng.uniform(size=n) < 1.0 / (1.0 + np.exp(-eta))).astype(np.float64)
+    y[:10] = (eta[:10] > 0).astype(np.float64)
+    y[7:10] = 1.0 - y[7:10]
+    return np.asfortranarray(x), y

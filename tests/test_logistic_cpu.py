@@ -136,6 +136,52 @@ def test_restatement_meets_lasso_kkt(hessian_full):
         assert np.all(np.abs(g[~act]) <= lam * (1 + 1e-8) + 1e-10)
 
 
+@pytest.mark.parametrize("intercept,standardize", [(False, True), (True, False), (False, False)])
+def test_restatement_meets_lasso_kkt_without_intercept_or_scaling(intercept, standardize):
+    """the same fixed point with the intercept dropped (row 0 of beta stays 0) or the columns left unscaled (s = 1)"""
+    x, y = _problem(400, 8, 6)
+    n = x.shape[0]
+    ref = R.fit(x, y, penalty=["lasso"], nlambda=6, lambda_min_ratio=0.05, tol=1e-13, irls_tol=1e-11, maxit=100000, irls_maxit=200,
+                intercept=intercept, standardize=standardize)
+    s = 1.0 / np.sqrt(np.sum(x * x, axis=0) / (n - 1.0)) if standardize else np.ones(x.shape[1])
+    xs = x * s
+    for i, lam in enumerate(ref["lambda"][0]):
+        beta = ref["beta"][0][:, i]
+        if not intercept:
+            assert beta[0] == 0.0
+        b = beta[1:] / s
+        prob = 1.0 / (1.0 + np.exp(-(xs @ b + beta[0])))
+        g = xs.T @ (y - prob) / n
+        if intercept:
+            assert abs(np.sum(y - prob) / n) < 1e-8
+        act = np.abs(b) > 0
+        assert np.all(np.abs(g[act] - lam * np.sign(b[act])) < 1e-7 * max(1.0, lam)), (i, g[act], lam)
+        assert np.all(np.abs(g[~act]) <= lam * (1 + 1e-8) + 1e-10)
+
+
+@pytest.mark.parametrize("hessian_full", [False, True])
+def test_restatement_counters(hessian_full):
+    """stats: the W floor and the loss clamps fire on near-separable data; a Hessian per penalty for upper.bound, per row pass for full;
+    a row pass per IRLS step except the skipped first step of each later lambda"""
+    x, y = R.near_separable(3000, 20, 1)
+    pens = ["lasso", "mcp", "ols"]
+    st = {}
+    ref = R.fit(x, y, penalty=pens, nlambda=8, lambda_min_ratio=1e-3, compute_loss=True, hessian_full=hessian_full, stats=st)
+    assert st["floored"] > 0 and st["clamped"] > 0, st
+    assert st["grams"] == (st["rows"] if hessian_full else len(pens)), st
+    later = sum(len(np.atleast_1d(ref["niter"][k])) - 1 for k in range(len(pens)))          # first steps skipped: one per later lambda
+    assert st["rows"] == st["irls"] - later, st
+    assert st["irls"] == sum(int(np.sum(ref["niter"][k])) for k in range(len(pens))), st     # no cap hit: niter = the steps taken
+    assert st["inner"] >= st["irls"]
+    st0 = {}
+    R.fit(x, y, penalty=pens, nlambda=8, lambda_min_ratio=1e-3, compute_loss=False, hessian_full=hessian_full, stats=st0)
+    assert st0["clamped"] == 0 and st0["floored"] == st["floored"]                           # clamps count the reported losses only
+    xs, ys = _problem(400, 5, 7)                                                             # mild data: nothing floored or clamped
+    st1 = {}
+    R.fit(xs, ys, penalty=["lasso"], nlambda=5, compute_loss=True, stats=st1)
+    assert st1["floored"] == 0 and st1["clamped"] == 0, st1
+
+
 def test_restatement_agrees_with_scikit_learn():
     pytest.importorskip("sklearn")
     from sklearn.linear_model import LogisticRegression
