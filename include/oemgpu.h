@@ -368,7 +368,25 @@ int oemgpu_fit_logistic_dense_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t 
  * inner solve is one persistent workgroup (q <= 1024) and 0 for launch per iteration, out[5] 1 if the row pass stages its sub-blocks
  * in LDS, out[6] device workspace bytes of a call, out[7] the bound out[6] stays within. */
 int oemgpu_selftest_logistic_plan(int64_t n, int32_t p, int32_t intercept, int32_t hessian_full, int32_t num_cu, int64_t *out /* 8 */);
-/* What the most recent binomial fit of THIS thread did: [0] row-pass ms [1] Z + Gram + Lanczos ms [2] inner-solve ms (the three only
+/* `.Call("oem_fit_logistic_sparse", ...)` (ref src/oem_logistic_sparse.cpp:30-313, src/oem_logistic_sparse.h): the binomial fit of a
+ * compressed-sparse-column x (a dgCMatrix: colptr[p + 1] with colptr[0] = 0, non-decreasing; rowidx[nnz] in [0, n), strictly increasing
+ * inside a column; values[nnz]; explicit zeros allowed).  opts, irls_maxit, irls_tol and the outputs as oemgpu_fit_logistic_dense.  The
+ * reference's single-thread branch (its default ncores): the Hessian X'WX at every IRLS step but the skipped first of a later lambda
+ * (hessian.type is never read), the intercept's coordinate scaled by intval = sqrt(mean diag(S X'WX S) / sum W / n) of the first
+ * Hessian build, and get_beta's in-place beta_0 *= intval after every lambda (the next lambda starts from it).
+ * Checked before any device is looked for: the checks of oemgpu_fit_logistic_dense; OEMGPU_ERR_UNSUPPORTED for p + intercept >= n,
+ * p > 8191 and an intercept without standardize (the reference reads column scales it never computed, h :724, :880); OEMGPU_ERR_ARG
+ * for malformed compressed-column arrays.  opts->interrupt is polled between IRLS steps (OEMGPU_ERR_INTERRUPTED). */
+int oemgpu_fit_logistic_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, const double *y,
+                               int32_t standardize, int32_t intercept, int32_t irls_maxit, double irls_tol, const oemgpu_opts *opts,
+                               double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+/* Host-only plan of the sparse binomial fit (pure arithmetic, runs without a GPU): out[0] 1 if X'WX takes the compressed-column kernel
+ * (it fits in LDS, nnz <= 2 % of n p, n < 2^31; the rule of oemgpu_fit_sparse) and 0 for zero-filled row tiles through the MFMA moment
+ * pass, out[1] 1 if the inner solve is one persistent workgroup (q <= 1024) and 0 for launch per iteration, out[2] device workspace
+ * bytes of the fit's data stages, out[3] the bound out[2] stays within, out[4] rows per tile (0 on the compressed-column route),
+ * out[5] workgroups of the row pass, out[6] rows per row-pass workgroup, out[7] 8192-row chunks of the compressed-column kernels. */
+int oemgpu_selftest_logistic_sparse_plan(int64_t n, int32_t p, int64_t nnz, int32_t intercept, int32_t num_cu, int64_t *out /* 8 */);
+/* What the most recent binomial fit of THIS thread did (dense or sparse): [0] row-pass ms [1] Z + Gram + Lanczos ms [2] inner-solve ms (the three only
  * with oemgpu_set_timing on the context; 0 otherwise) [3] IRLS steps [4] inner iterations [5] row passes [6] Gram builds [7] wall ms */
 int oemgpu_last_logistic_stats(double *out /* 8 */);
 

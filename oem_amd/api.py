@@ -414,6 +414,59 @@ def oem_fit_logistic_dense(x, y, penalty=None, weights=(), lambda_=(), nlambda=1
     return res
 
 
+def oem_fit_logistic_sparse(x, y, penalty=None, weights=(), lambda_=(), nlambda=100, lambda_min_ratio=None, alpha=1.0, gamma=3.0, tau=0.5,
+                            groups=(), penalty_factor=None, group_weights=None, standardize=True, intercept=True, maxit=500, tol=1e-7,
+                            irls_maxit=100, irls_tol=1e-3, compute_loss=False, hessian_type="upper.bound", varnames=None, interrupt=None):
+    """The sparse binomial fit (ref src/oem_logistic_sparse.cpp:30-313, src/oem_logistic_sparse.h), the entry `oem(x = <dgCMatrix>,
+    family = "binomial")` calls (R/oem.R:603-624), with the checks of oem_fit_logistic_dense.  x: any scipy.sparse matrix, taken as
+    compressed columns of float64 with duplicates summed and indices sorted, as R's coercion to dgCMatrix does.
+    hessian_type must be "upper.bound" or "full" and is then ignored: the reference rebuilds X'WX at every IRLS step of this fit
+    whatever it says (src/oem_logistic_sparse.h:866, :973).  An intercept needs standardize (the reference's linear predictor reads
+    column scales it only computes with standardize); p + intercept >= n is refused."""
+    import scipy.sparse as sp
+    L.sync_switches()
+    penalty = _match_penalty(penalty)
+    if hessian_type not in ("upper.bound", "full"):
+        raise ValueError("'arg' should be one of 'upper.bound', 'full'")
+    if not sp.issparse(x):
+        raise TypeError("x must be a scipy.sparse matrix (oem_fit_logistic_dense takes a dense one)")
+    if len(x.shape) != 2:
+        raise ValueError("x must have at least two columns")
+    n, p = x.shape
+    if p < 2:
+        raise ValueError("x must have at least two columns")
+    if len(weights) > 0:                                               # R/oem.R:244
+        raise L.OemgpuError(-4, "weights not implemented yet.")
+    yh = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+    if yh.shape[0] != n:
+        raise ValueError("x and y lengths do not match")
+    if len(np.unique(yh)) > 2:                                         # R/oem.R:250-252
+        raise ValueError("y must be a binary outcome")
+    if penalty_factor is None:
+        penalty_factor = np.ones(p)
+    penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
+    if len(penalty_factor) != p:
+        raise ValueError("penalty.factor must have same length as number of columns in x")
+    if varnames is None:
+        varnames = [f"V{i + 1}" for i in range(p)]
+    groups, unique_groups, group_weights = _group_setup(penalty, groups, group_weights, p, bool(intercept))
+    if lambda_min_ratio is None:
+        lambda_min_ratio = 0.01 if n < p else 0.0001
+    _common_checks(nlambda, float(lambda_min_ratio), maxit, irls_maxit, tol, irls_tol)
+    lam_list = _lambda_list(lambda_, len(penalty))
+    a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
+              compute_loss, penalty_factor, groups, unique_groups, group_weights, interrupt=interrupt)
+    xc = sp.csc_matrix(x, dtype=np.float64, copy=True)
+    xc.sum_duplicates()
+    xc.sort_indices()
+    colptr = np.ascontiguousarray(xc.indptr, dtype=np.int64)
+    rowidx = np.ascontiguousarray(xc.indices, dtype=np.int32)
+    vals = np.ascontiguousarray(xc.data, dtype=np.float64)
+    L.check(L.lib().oemgpu_fit_logistic_sparse(n, p, colptr.ctypes.data, _iptr(rowidx), _dptr(vals), _dptr(yh), int(bool(standardize)),
+                                               int(bool(intercept)), int(irls_maxit), float(irls_tol), C.byref(a.c), *a.outputs(p + 1)))
+    return OemFitBinomial(_decorate(a, penalty, varnames, True, n, p, family="binomial"))
+
+
 def logistic_stats():
     """oemgpu_last_logistic_stats of this thread, as a dict"""
     out = (C.c_double * 8)()
@@ -802,10 +855,17 @@ def predict(fit, newx=None, s=None, which_model=0, type="link"):
         return _nonzero_lists(nbeta)
     if newx is None:
         raise ValueError("A value for 'newx' must be supplied")
-    newx = np.asarray(newx, dtype=np.float64)
-    if newx.shape[1] < nbeta.shape[0]:
-        newx = np.column_stack([np.ones(newx.shape[0]), newx])
-    nfit = newx @ nbeta
+    if hasattr(newx, "tocsc") and newx.__class__.__module__.startswith("scipy.sparse"):    # a dgCMatrix newx: R multiplies it as it is (R/methods.R:48-109)
+        import scipy.sparse as sp
+        newx = sp.csc_matrix(newx, dtype=np.float64)
+        if newx.shape[1] < nbeta.shape[0]:
+            newx = sp.hstack([sp.csc_matrix(np.ones((newx.shape[0], 1))), newx], format="csc")
+        nfit = np.asarray(newx @ nbeta)
+    else:
+        newx = np.asarray(newx, dtype=np.float64)
+        if newx.shape[1] < nbeta.shape[0]:
+            newx = np.column_stack([np.ones(newx.shape[0]), newx])
+        nfit = newx @ nbeta
     if fit.get("family") == "binomial":                # predict.oemfit_binomial, R/methods.R:346-367
         if type == "response":
             return 1.0 / (1.0 + np.exp(-nfit))

@@ -64,6 +64,14 @@ size_t csc_moments_work_bytes(int64_t n, int p);
 bool csc_moments_fits(int p);
 int launch_csc_moments(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *y, int64_t n, int p,
                        void *work, double *moments);
+// the binomial fit (logistic_sparse.hip): chunk pointers once, a compressed-row copy once, X'WX at every IRLS step
+int csc_chunks(int64_t n);
+size_t csc_wgram_work_bytes(int64_t n, int p);
+int launch_csc_chunk_ptr(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, int64_t n, int p, int32_t *cptr);
+int launch_csc_to_csr(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const int32_t *cptr, int64_t n, int p,
+                      const int64_t *rowptr, int32_t *ccol, double *cval);
+int launch_csc_wgram(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *w, const int32_t *cptr,
+                     int64_t n, int p, double *part, double *M);
 // observation weights of oemDense (weighted.hip): DataStd's weighted statistics, the scaled copy, its constants into `stats`
 int launch_weighted_stats(hipStream_t s, const double *x, int64_t n, int64_t ld, int p, const double *y, const double *w, int flag, double *ws);
 int launch_weighted_apply(hipStream_t s, const double *x, int64_t n, int64_t ld, int p, const double *y, const double *w, int flag, const double *ws,

@@ -26,7 +26,9 @@
 //     launches between looks at the stop word.  The threshold's scratch (u + XY, the new beta, a factor per group) is in LDS when its
 //     8 (2 q + ngroups) bytes fit LOGIT_LDS_BYTES, else in the workspace (one group per coordinate at p >= 6826);
 //   * small kernels: XX from the moments, A = dI - XX, XY = XX beta + grad, the IRLS stop, the back-transform.
-#include "ctx.hpp"
+// The host driver (logistic_irls) is shared with the sparse fit (logistic_sparse.hip): the passes over the data reach it as the stages of
+// a LogitData (logistic.hpp); DenseLogitData below is this file's.
+#include "logistic.hpp"
 #include "penalty_ops.hpp"
 
 #include <chrono>
@@ -422,6 +424,9 @@ struct LogitStats {
 };
 static thread_local LogitStats g_logit_stats;
 
+const int LOGIT_WG_MAX_Q = LOGIT_WG_MAX;
+const int LOGIT_P_LIMIT = LOGIT_P_MAX;
+
 static int logit_rows(hipStream_t s, const LogitPlan &P, const double *x, int64_t n, int64_t ld, int p, const double *y, const double *beta,
                       const double *sc, int intercept, int mode, int64_t irls_i, int64_t c0, int64_t nc, int64_t row0, double *z, int64_t ldz, double *part)
 {
@@ -460,16 +465,102 @@ int logistic_check(int64_t n, int32_t p, int32_t intercept, int32_t hessian_full
 
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int32_t p, const double *y, int32_t standardize, int32_t intercept,
-                     int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
-                     double *beta_out, double *lambda_out, int32_t *niter, double *loss_out, double *d_out)
+namespace {
+
+// the dense x: one row pass per IRLS step (logit_rows_kernel); with a Hessian due the same pass writes the Z row blocks of the
+// moment pass instead, block after block
+struct DenseLogitData final : LogitData {
+    oemgpu_ctx *c;
+    const double *x, *y;
+    int64_t n, ld;
+    int p, q, intercept, standardize;
+    LogitPlan P;
+    size_t m2;
+    double *part = nullptr, *z = nullptr, *mb = nullptr, *ma = nullptr, *tp = nullptr, *vp = nullptr;
+
+    DenseLogitData(oemgpu_ctx *c_, const double *x_, int64_t n_, int64_t ld_, int p_, const double *y_, int standardize_, int intercept_, int hessian_full)
+        : c(c_), x(x_), y(y_), n(n_), ld(ld_), p(p_), q(p_ + (intercept_ ? 1 : 0)), intercept(intercept_), standardize(standardize_),
+          P(logit_plan(n_, p_, intercept_, c_->num_cu)), m2((size_t)(q + 2) * (q + 2))
+    {
+        hess_every = hessian_full != 0;
+    }
+    size_t ws_bytes() const override
+    {
+        Bump B;
+        const GramPlan gpb = gram_plan_bound(P.rbz < n ? P.rbz : n, q, c->num_cu);
+        B.take(8 * (size_t)P.nchunk * (p + 2)); B.take(8 * (size_t)P.rbz * q); B.take(8 * m2); B.take(8 * m2);
+        B.take(8 * gpb.tpart_doubles); B.take(8 * gpb.vpart_doubles);
+        return B.off;
+    }
+    int bind(char *ws) override
+    {
+        Bump B;
+        const GramPlan gpb = gram_plan_bound(P.rbz < n ? P.rbz : n, q, c->num_cu);
+        part = (double *)(ws + B.take(8 * (size_t)P.nchunk * (p + 2))); z = (double *)(ws + B.take(8 * (size_t)P.rbz * q));
+        mb = (double *)(ws + B.take(8 * m2)); ma = (double *)(ws + B.take(8 * m2));
+        tp = (double *)(ws + B.take(8 * gpb.tpart_doubles)); vp = (double *)(ws + B.take(8 * gpb.vpart_doubles));
+        return 0;
+    }
+    int scale(double *sc) override
+    {
+        if (standardize) hipLaunchKernelGGL(logit_scale_kernel, dim3(p), dim3(256), 0, c->stream, x, n, ld, sc);
+        else hipLaunchKernelGGL(logit_fill_kernel, dim3((p + 255) / 256), dim3(256), 0, c->stream, sc, p, 1.0);
+        OEM_HIP(hipGetLastError());
+        return 0;
+    }
+    int xy0(const double *sc, double *g) override
+    {
+        int rc = logit_rows(c->stream, P, x, n, ld, p, y, nullptr, sc, intercept, 0, -1, 0, P.nchunk, 0, nullptr, 0, part);
+        if (rc) return rc;
+        hipLaunchKernelGGL(logit_sum_kernel, dim3((p + 2 + 255) / 256), dim3(256), 0, c->stream, part, P.nchunk, p + 2, g);
+        OEM_HIP(hipGetLastError());
+        return 0;
+    }
+    int rows(const double *beta, const double *sc, int64_t i, bool gram, double *g) override
+    {
+        if (gram) return 0;                                  // the Z blocks of the Hessian build carry the row pass
+        int rc = logit_rows(c->stream, P, x, n, ld, p, y, beta, sc, intercept, 1, i, 0, P.nchunk, 0, nullptr, 0, part);
+        if (rc) return rc;
+        hipLaunchKernelGGL(logit_sum_kernel, dim3((p + 2 + 255) / 256), dim3(256), 0, c->stream, part, P.nchunk, p + 2, g);
+        OEM_HIP(hipGetLastError());
+        return 0;
+    }
+    int hessian(const double *beta, const double *sc, int64_t i, double *g, double *xx) override
+    {
+        hipStream_t s = c->stream;
+        // Z row blocks: row pass (writes Z and the partials of its chunks) -> moment pass -> running sum in block order
+        for (int64_t b = 0; b < P.nzblk; ++b) {
+            const int64_t c0 = b * (P.rbz / P.ch), c1 = std::min<int64_t>(P.nchunk, c0 + P.rbz / P.ch);
+            const int64_t r0 = c0 * P.ch, nrow = std::min<int64_t>(n, c1 * P.ch) - r0;
+            int r = logit_rows(s, P, x, n, ld, p, y, beta, sc, intercept, 1, i, c0, c1 - c0, r0, z, P.rbz, part);
+            if (r) return r;
+            const GramPlan gpl = gram_plan(nrow, q, c->num_cu);
+            r = launch_gram(s, gpl, z, nrow, P.rbz, z, nullptr, tp, vp);
+            if (!r) r = launch_moments_reduce(s, gpl, tp, vp, mb);
+            if (r) return r;
+            hipLaunchKernelGGL(logit_mom_add_kernel, dim3((unsigned)((m2 + 255) / 256)), dim3(256), 0, s, ma, mb, m2, b == 0 ? 1 : 0);
+        }
+        hipLaunchKernelGGL(logit_xx_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, ma, q, (double)n, xx);
+        hipLaunchKernelGGL(logit_sum_kernel, dim3((p + 2 + 255) / 256), dim3(256), 0, s, part, P.nchunk, p + 2, g);
+        OEM_HIP(hipGetLastError());
+        return 0;
+    }
+};
+
+// get_beta of the sparse fit (ref src/oem_logistic_sparse.h:1040-1062): beta_0 *= intval on the solver's own beta
+__global__ void logit_rescale_kernel(double *beta, const double *intval) { beta[0] *= *intval; }
+
+}  // namespace
+
+int logistic_irls(oemgpu_ctx *c, LogitData &D, int64_t n, int32_t p, int32_t intercept, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
+                  double *beta_out, double *lambda_out, int32_t *niter, double *loss_out, double *d_out)
 {
     const double t_start = now_ms();
     g_logit_stats = LogitStats();
     const int q = p + (intercept ? 1 : 0), o1 = intercept ? 1 : 0;
     const int nl = (o->lambda_user && o->nlambda_user > 0) ? o->nlambda_user : o->nlambda;
     const bool provided = o->lambda_user && o->nlambda_user > 0;
-    const LogitPlan P = logit_plan(n, p, intercept, c->num_cu);
+    const bool inner_wg = q <= LOGIT_WG_MAX;
     // ---- host-side tables: penalty factors (0 for the intercept), groups ordered, group weights (default sqrt(size), 0 for group 0)
     std::vector<double> pf(q);
     for (int j = 0; j < p; ++j) pf[o1 + j] = o->penalty_factor[j];
@@ -491,27 +582,27 @@ int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int3
     }
     const int nperm = (int)perm.size();
     if (nperm > q) { set_error("fit_logistic_dense: unique_groups has repeated ids"); return OEMGPU_ERR_ARG; }
-    // ---- workspace (c->aux; oemgpu_eig_max_dev takes c->ws from its start)
+    // ---- workspace (c->aux; oemgpu_eig_max_dev takes c->ws from its start): the driver's pieces, then the data stages'
     Bump B;
     const size_t a_s = B.take(8 * (size_t)p), a_b = B.take(8 * (size_t)q), a_bi = B.take(8 * (size_t)q),
                  a_u = B.take(8 * (size_t)q), a_xy = B.take(8 * (size_t)q), a_xx = B.take(8 * (size_t)q * q), a_a = B.take(8 * (size_t)q * q),
-                 a_g = B.take(8 * (size_t)(p + 2)), a_part = B.take(8 * (size_t)P.nchunk * (p + 2)), a_z = B.take(8 * (size_t)P.rbz * q);
-    const size_t m2 = (size_t)(q + 2) * (q + 2);
-    const GramPlan gpb = gram_plan_bound(P.rbz < n ? P.rbz : n, q, c->num_cu);
-    const size_t a_mb = B.take(8 * m2), a_ma = B.take(8 * m2), a_tp = B.take(8 * gpb.tpart_doubles), a_vp = B.take(8 * gpb.vpart_doubles),
-                 a_st = B.take(8 * ST_LEN), a_done = B.take(256);
+                 a_g = B.take(8 * (size_t)(p + 2));
+    const size_t a_st = B.take(8 * ST_LEN), a_done = B.take(256);
     const size_t a_pf = B.take(8 * (size_t)q), a_gw = B.take(8 * (size_t)(ng > 0 ? ng : 1)), a_perm = B.take(4 * (size_t)(q + 1)),
                  a_gs = B.take(4 * (size_t)(ng + 1)), a_gof = B.take(4 * (size_t)q), a_gz = B.take(4 * (size_t)(ng > 0 ? ng : 1));
     const bool thr_lds = logit_thr_in_lds(q, ng);
-    const size_t a_thr = (!P.inner_wg && !thr_lds) ? B.take(8 * (size_t)(2 * q + (ng > 0 ? ng : 1))) : 0;
+    const size_t a_thr = (!inner_wg && !thr_lds) ? B.take(8 * (size_t)(2 * q + (ng > 0 ? ng : 1))) : 0;
     const size_t a_out = B.take(8 * (size_t)o->npen * nl * (p + 1));
+    const size_t a_data = B.take(D.ws_bytes());
     if (ctx_grow(c, &c->aux, &c->aux_bytes, B.off)) return OEMGPU_ERR_HIP;
     char *W = c->aux;
     double *sc = (double *)(W + a_s), *beta = (double *)(W + a_b), *birls = (double *)(W + a_bi), *u = (double *)(W + a_u),
-           *xy = (double *)(W + a_xy), *xx = (double *)(W + a_xx), *A = (double *)(W + a_a), *g = (double *)(W + a_g), *part = (double *)(W + a_part),
-           *z = (double *)(W + a_z), *mb = (double *)(W + a_mb), *ma = (double *)(W + a_ma), *st = (double *)(W + a_st), *bout = (double *)(W + a_out);
+           *xy = (double *)(W + a_xy), *xx = (double *)(W + a_xx), *A = (double *)(W + a_a), *g = (double *)(W + a_g), *st = (double *)(W + a_st),
+           *bout = (double *)(W + a_out);
     int *done = (int *)(W + a_done);
     hipStream_t s = c->stream;
+    int rc = D.bind(W + a_data);
+    if (rc) return rc;
     OEM_HIP(hipMemcpyAsync(W + a_pf, pf.data(), 8 * (size_t)q, hipMemcpyHostToDevice, s));
     OEM_HIP(hipMemcpyAsync(W + a_gw, gw.data(), 8 * gw.size(), hipMemcpyHostToDevice, s));
     if (nperm) OEM_HIP(hipMemcpyAsync(W + a_perm, perm.data(), 4 * (size_t)nperm, hipMemcpyHostToDevice, s));
@@ -521,12 +612,9 @@ int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int3
     OEM_HIP(hipMemsetAsync(bout, 0, 8 * (size_t)o->npen * nl * (p + 1), s));
     OEM_HIP(hipMemsetAsync(st, 0, 8 * ST_LEN, s));
     // ---- init_oem: s, XY = s o X'Y / n, lambda_0
-    if (standardize) hipLaunchKernelGGL(logit_scale_kernel, dim3(p), dim3(256), 0, s, x, n, ld, sc);
-    else hipLaunchKernelGGL(logit_fill_kernel, dim3((p + 255) / 256), dim3(256), 0, s, sc, p, 1.0);
-    OEM_HIP(hipGetLastError());
-    int rc = logit_rows(s, P, x, n, ld, p, y, beta, sc, intercept, 0, -1, 0, P.nchunk, 0, nullptr, 0, part);
+    rc = D.scale(sc);
+    if (!rc) rc = D.xy0(sc, g);
     if (rc) return rc;
-    hipLaunchKernelGGL(logit_sum_kernel, dim3((p + 2 + 255) / 256), dim3(256), 0, s, part, P.nchunk, p + 2, g);
     hipLaunchKernelGGL(logit_xy_kernel, dim3((q + 255) / 256), dim3(256), 0, s, xx, beta, g, sc, p, intercept, (double)n, 1, xy);
     OEM_HIP(hipGetLastError());
     std::vector<double> hxy(q);
@@ -590,30 +678,15 @@ int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int3
                 if (o->interrupt && o->interrupt(o->interrupt_arg)) { interrupted = 1; break; }
                 OEM_HIP(hipMemcpyAsync(birls, beta, 8 * (size_t)q, hipMemcpyDeviceToDevice, s));
                 if (!(i == 0 && li > 0)) {
-                    const bool need_xx = (i == 0 && li == 0) || hessian_full;
-                    rc = stage(&g_logit_stats.ms_rows, [&]() -> int {
-                        if (!need_xx) return logit_rows(s, P, x, n, ld, p, y, beta, sc, intercept, 1, i, 0, P.nchunk, 0, nullptr, 0, part);
-                        return 0;
-                    });
+                    const bool need_xx = (i == 0 && li == 0) || D.hess_every;
+                    rc = stage(&g_logit_stats.ms_rows, [&]() -> int { return D.rows(beta, sc, i, need_xx, g); });
                     if (rc) break;
                     if (need_xx) {
-                        // Z row blocks: row pass (writes Z and the partials of its chunks) -> moment pass -> running sum in block order
                         rc = stage(&g_logit_stats.ms_gram, [&]() -> int {
-                            for (int64_t b = 0; b < P.nzblk; ++b) {
-                                const int64_t c0 = b * (P.rbz / P.ch), c1 = std::min<int64_t>(P.nchunk, c0 + P.rbz / P.ch);
-                                const int64_t r0 = c0 * P.ch, rows = std::min<int64_t>(n, c1 * P.ch) - r0;
-                                int r = logit_rows(s, P, x, n, ld, p, y, beta, sc, intercept, 1, i, c0, c1 - c0, r0, z, P.rbz, part);
-                                if (r) return r;
-                                const GramPlan gpl = gram_plan(rows, q, c->num_cu);
-                                r = launch_gram(s, gpl, z, rows, P.rbz, z, nullptr, (double *)(W + a_tp), (double *)(W + a_vp));
-                                if (!r) r = launch_moments_reduce(s, gpl, (double *)(W + a_tp), (double *)(W + a_vp), mb);
-                                if (r) return r;
-                                hipLaunchKernelGGL(logit_mom_add_kernel, dim3((unsigned)((m2 + 255) / 256)), dim3(256), 0, s, ma, mb, m2, b == 0 ? 1 : 0);
-                            }
-                            hipLaunchKernelGGL(logit_xx_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, ma, q, (double)n, xx);
-                            OEM_HIP(hipGetLastError());
+                            int r = D.hessian(beta, sc, i, g, xx);
+                            if (r) return r;
                             double lm = 0.0;
-                            int r = oemgpu_eig_max_dev(c, xx, q, &lm);              // (synchronises)
+                            r = oemgpu_eig_max_dev(c, xx, q, &lm);                   // (synchronises)
                             if (r) return r;
                             d = lm * 1.0005;                                         // h :514
                             hipLaunchKernelGGL(logit_a_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, xx, q, d, A);
@@ -624,7 +697,6 @@ int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int3
                         g_logit_stats.grams += 1;
                     }
                     g_logit_stats.row_passes += 1;
-                    hipLaunchKernelGGL(logit_sum_kernel, dim3((p + 2 + 255) / 256), dim3(256), 0, s, part, P.nchunk, p + 2, g);
                     hipLaunchKernelGGL(logit_xy_kernel, dim3((q + 255) / 256), dim3(256), 0, s, xx, beta, g, sc, p, intercept, (double)n, 0, xy);
                     OEM_HIP(hipGetLastError());
                 }
@@ -654,7 +726,7 @@ int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int3
                 }
                 LP.k = pk;
                 rc = stage(&g_logit_stats.ms_inner, [&]() -> int {
-                    if (P.inner_wg) {
+                    if (inner_wg) {
                         const bool alds = q <= LOGIT_A_LDS_Q;
                         const size_t lds = 8 * (size_t)(3 * q + (ng > 0 ? ng : 1) + (alds ? q * q : 0));
                         if (alds) {
@@ -710,6 +782,7 @@ int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int3
             }
             niter[(size_t)k * nl + li] = i + 1;
             loss_out[(size_t)k * nl + li] = loss_now;
+            if (D.intval && intercept) hipLaunchKernelGGL(logit_rescale_kernel, dim3(1), dim3(1), 0, s, beta, D.intval);
             hipLaunchKernelGGL(logit_back_kernel, dim3((p + 1 + 255) / 256), dim3(256), 0, s, beta, sc, p, intercept, bout + ((size_t)k * nl + li) * (p + 1));
             OEM_HIP(hipGetLastError());
         }
@@ -728,6 +801,14 @@ int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int3
     g_logit_stats.wall_ms = now_ms() - t_start;
     *d_out = d;
     return 0;
+}
+
+int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int32_t p, const double *y, int32_t standardize, int32_t intercept,
+                     int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
+                     double *beta_out, double *lambda_out, int32_t *niter, double *loss_out, double *d_out)
+{
+    DenseLogitData D(c, x, n, ld, p, y, standardize, intercept, hessian_full);
+    return logistic_irls(c, D, n, p, intercept, irls_maxit, irls_tol, o, beta_out, lambda_out, niter, loss_out, d_out);
 }
 
 }  // namespace oemgpu

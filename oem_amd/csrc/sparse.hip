@@ -37,10 +37,13 @@ __global__ __launch_bounds__(256) void csc_chunk_ptr_kernel(const int64_t *__res
 }
 
 // M: the (p + 2)^2 moment buffer; writes M[i][j] for i, j < p (both triangles)
+// WEIGHTED: a row weight w (the binomial fit's W): column a's chunk is scattered as w[row] * val, so G[a][b] = sum val_b (w val_a)[row]
 constexpr int GT = 1024;            // threads per workgroup: 64 sixteen-lane groups
+template <bool WEIGHTED>
 __global__ __launch_bounds__(GT) void csc_gram_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx,
                                                       const double *__restrict__ val, const int32_t *__restrict__ cptr, int p, int nchunk,
-                                                      int nrange, double *__restrict__ part /* [nrange][p][p]: row a holds G[a][b], b >= a */)
+                                                      int nrange, double *__restrict__ part /* [nrange][p][p]: row a holds G[a][b], b >= a */,
+                                                      const double *__restrict__ w)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *dense = lds;                                         // [SRC]
@@ -65,7 +68,11 @@ __global__ __launch_bounds__(GT) void csc_gram_kernel(const int64_t *__restrict_
             const int ka0 = cp0[a], ka1 = cp1[a];
             if (ka0 == ka1) continue;                            // column a has nothing in this chunk (uniform)
             const int base = c * SRC;
-            for (int k = ka0 + tid; k < ka1; k += GT) dense[rowidx[ca + k] - base] = val[ca + k];
+            if (WEIGHTED) {
+                for (int k = ka0 + tid; k < ka1; k += GT) { const int r = rowidx[ca + k]; dense[r - base] = w[r] * val[ca + k]; }
+            } else {
+                for (int k = ka0 + tid; k < ka1; k += GT) dense[rowidx[ca + k] - base] = val[ca + k];
+            }
             __syncthreads();
             for (int b = a + grp; b < p; b += GT / 16) {
                 const int kb0 = cp0[b], kb1 = cp1[b];
@@ -205,6 +212,32 @@ __global__ void resid_loss_sum_kernel(const double *__restrict__ part, int nchun
     loss[k] = t;
 }
 
+// The compressed-column arrays as compressed rows, each row's entries in column order: workgroup c owns the rows of chunk c
+// (cptr), holds a cursor per row in LDS and walks the columns in order; the entries of one column have distinct rows, so the
+// lanes of a column never share a cursor, and a barrier between columns keeps every row's cursor advancing in column order.
+__global__ __launch_bounds__(256) void csc_to_csr_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx,
+                                                         const double *__restrict__ val, const int32_t *__restrict__ cptr, int64_t n, int p,
+                                                         const int64_t *__restrict__ rowptr, int32_t *__restrict__ ccol, double *__restrict__ cval)
+{
+    __shared__ int32_t cur[SRC];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const int64_t base = (int64_t)c * SRC;
+    for (int k = tid; k < SRC; k += 256) cur[k] = 0;
+    __syncthreads();
+    for (int j = 0; j < p; ++j) {
+        const int k0 = cptr[(size_t)c * p + j], k1 = cptr[(size_t)(c + 1) * p + j];
+        if (k0 == k1) continue;                               // (uniform)
+        const int64_t cj = colptr[j];
+        for (int k = k0 + tid; k < k1; k += 256) {
+            const int64_t r = rowidx[cj + k];
+            const int64_t pos = rowptr[r] + cur[r - base]++;
+            ccol[pos] = j;
+            cval[pos] = val[cj + k];
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 int launch_gram_loss(hipStream_t s, const double *xx, const double *xy, const double *stats, int q, const double *beta, const double *sinv,
@@ -254,10 +287,44 @@ int launch_csc_moments(hipStream_t s, const int64_t *colptr, const int32_t *rowi
     double *part = reinterpret_cast<double *>((char *)work + cbytes), *ypart = part + (size_t)nrange * p * p;
     hipLaunchKernelGGL(csc_chunk_ptr_kernel, dim3(p, (nchunk + 1 + 255) / 256), dim3(256), 0, s, colptr, rowidx, p, nchunk, cptr);
     const size_t sh = (size_t)SRC * 8 + (size_t)p * 16 + 64;
-    if (sh > 64 * 1024) OEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&csc_gram_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    hipLaunchKernelGGL(csc_gram_kernel, dim3((p + 1) / 2, nrange), dim3(GT), sh, s, colptr, rowidx, val, cptr, p, nchunk, nrange, part);
+    if (sh > 64 * 1024) OEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&csc_gram_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    hipLaunchKernelGGL(csc_gram_kernel<false>, dim3((p + 1) / 2, nrange), dim3(GT), sh, s, colptr, rowidx, val, cptr, p, nchunk, nrange, part, nullptr);
     hipLaunchKernelGGL(csc_stats_kernel, dim3(p + NY), dim3(256), 0, s, colptr, rowidx, val, y, n, p, moments, ypart);
     hipLaunchKernelGGL(csc_finish_kernel, dim3((unsigned)(((size_t)p * p + 255) / 256)), dim3(256), 0, s, part, nrange, ypart, NY, n, p, moments);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- the binomial fit's pieces (logistic_sparse.hip)
+int csc_chunks(int64_t n) { return (int)((n + SRC - 1) / SRC); }
+size_t csc_wgram_work_bytes(int64_t n, int p) { return sizeof(double) * ((size_t)csc_ranges(n, p) * p * p); }
+
+// cptr: (csc_chunks(n) + 1) x p int32: where every column enters every chunk of rows
+int launch_csc_chunk_ptr(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, int64_t n, int p, int32_t *cptr)
+{
+    const int nchunk = csc_chunks(n);
+    hipLaunchKernelGGL(csc_chunk_ptr_kernel, dim3(p, (nchunk + 1 + 255) / 256), dim3(256), 0, s, colptr, rowidx, p, nchunk, cptr);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_csc_to_csr(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const int32_t *cptr, int64_t n, int p,
+                      const int64_t *rowptr, int32_t *ccol, double *cval)
+{
+    hipLaunchKernelGGL(csc_to_csr_kernel, dim3(csc_chunks(n)), dim3(256), 0, s, colptr, rowidx, val, cptr, n, p, rowptr, ccol, cval);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+// X'WX of the compressed columns into the (p + 2)^2 moment buffer M (entries i, j < p; the y entries 0, M[p + 1][p + 1] = n)
+int launch_csc_wgram(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *w, const int32_t *cptr,
+                     int64_t n, int p, double *part, double *M)
+{
+    const int nchunk = csc_chunks(n), nrange = csc_ranges(n, p);
+    const size_t sh = (size_t)SRC * 8 + (size_t)p * 16 + 64;
+    if (sh > 64 * 1024 && lds_limit_once(reinterpret_cast<const void *>(&csc_gram_kernel<true>), sh)) return OEMGPU_ERR_HIP;
+    hipLaunchKernelGGL(csc_gram_kernel<true>, dim3((p + 1) / 2, nrange), dim3(GT), sh, s, colptr, rowidx, val, cptr, p, nchunk, nrange, part, w);
+    hipLaunchKernelGGL(csc_finish_kernel, dim3((unsigned)(((size_t)p * p + 255) / 256)), dim3(256), 0, s, part, nrange, nullptr, 0, n, p, M);
     OEM_HIP(hipGetLastError());
     return 0;
 }
