@@ -121,12 +121,15 @@ int oemgpu_fit_dense_weighted(const double *x, int64_t n, int32_t p, const doubl
                               int32_t standardize, int32_t intercept, const oemgpu_opts *opts,
                               double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
 
-/* replaces oem_fit_sparse, ref src/oem_sparse.cpp:30-267 (family "gaussian", weights empty, n > p): oem() on a dgCMatrix.
- * colptr[p + 1], rowidx[nnz], values[nnz]: the compressed sparse column slots @p, @i, @x (row indices increasing inside a
- * column).  Outputs as oemgpu_fit_dense.  The semantics are oemSparse's, not oemDense's: no centring, columns scaled by
- * sqrt(sum x^2 / (n - 1)), the intercept as a Gram column of value sqrt(mean diag / n) whose coefficient is rescaled in
- * place after every lambda (ref src/oem_sparse.h:493-615, 897-917), lambda_zero without the intercept slot (:854-863).
- * compute_loss (ref :919-944) for p + intercept <= 288.  The Gram is built by the dense FP64-MFMA pass over zero-filled row tiles of x (<= 2 GiB each). */
+/* replaces oem_fit_sparse, ref src/oem_sparse.cpp:30-267 (family "gaussian", weights empty): oem() on a dgCMatrix.
+ * colptr[p + 1] with colptr[0] = 0, non-decreasing; rowidx[nnz] in [0, n), strictly increasing inside a column; values[nnz]
+ * (the compressed sparse column slots @p, @i, @x; explicit zeros allowed).  Outputs as oemgpu_fit_dense.  The semantics are
+ * oemSparse's, not oemDense's: no centring, columns scaled by sqrt(sum x^2 / (n - 1)), the intercept as a Gram column of value
+ * sqrt(mean diag / n) whose coefficient is rescaled in place after every lambda (ref src/oem_sparse.h:493-615, 897-917), lambda_zero
+ * without the intercept slot (:854-863).  compute_loss (ref :919-944) for p + intercept <= 288.  With n > p the Gram takes one of two
+ * routes: the compressed-column kernel when it fits in LDS, nnz <= 2 % of n p and n < 2^31, else the dense FP64-MFMA pass over
+ * zero-filled row tiles of x (<= 2 GiB each).  n <= p is served without an intercept (OEMGPU_ERR_UNSUPPORTED with one).
+ * Malformed compressed-column arrays get OEMGPU_ERR_ARG before any device is looked for. */
 int oemgpu_fit_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, const double *y,
                       int32_t standardize, int32_t intercept, const oemgpu_opts *o,
                       double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
@@ -381,7 +384,8 @@ int oemgpu_fit_logistic_sparse(int64_t n, int32_t p, const int64_t *colptr, cons
                                int32_t standardize, int32_t intercept, int32_t irls_maxit, double irls_tol, const oemgpu_opts *opts,
                                double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
 /* Host-only plan of the sparse binomial fit (pure arithmetic, runs without a GPU): out[0] 1 if X'WX takes the compressed-column kernel
- * (it fits in LDS, nnz <= 2 % of n p, n < 2^31; the rule of oemgpu_fit_sparse) and 0 for zero-filled row tiles through the MFMA moment
+ * (it fits in LDS, nnz <= 2 % of n p, n < 2^31: the rule of oemgpu_fit_sparse, or the route a call would be forced to by the
+ * library's OEM_SPARSE_GRAM test switch) and 0 for zero-filled row tiles through the MFMA moment
  * pass, out[1] 1 if the inner solve is one persistent workgroup (q <= 1024) and 0 for launch per iteration, out[2] device workspace
  * bytes of the fit's data stages, out[3] the bound out[2] stays within, out[4] rows per tile (0 on the compressed-column route),
  * out[5] workgroups of the row pass, out[6] rows per row-pass workgroup, out[7] 8192-row chunks of the compressed-column kernels. */

@@ -54,6 +54,19 @@ def _is_torch_cuda(x):
     return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
 
 
+def _csc_arrays(x):
+    """The compressed-column arrays of a scipy.sparse x as R's coercion to dgCMatrix leaves them: float64 values, duplicate entries
+    summed, row indices sorted inside every column.  Returns contiguous (int64 colptr, int32 rowidx, float64 values).  The caller's
+    matrix is never changed: when it is not already in that form, a copy is."""
+    import scipy.sparse as sp
+    xc = sp.csc_matrix(x, dtype=np.float64)
+    if not xc.has_canonical_format:
+        xc = xc.copy()
+        xc.sum_duplicates()                                            # sums, and sorts the indices
+    return (np.ascontiguousarray(xc.indptr, dtype=np.int64), np.ascontiguousarray(xc.indices, dtype=np.int32),
+            np.ascontiguousarray(xc.data, dtype=np.float64))
+
+
 def _dptr(a):
     return a.ctypes.data_as(L._dp) if a is not None and a.size > 0 else L._dp()
 
@@ -295,10 +308,7 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
               upload_threads=upload_threads, interrupt=interrupt)
     lib = L.lib()
     if is_sparse:                                                      # oem_fit_sparse (ref src/oem_sparse.cpp:30-267)
-        import scipy.sparse as sp
-        xc = sp.csc_matrix(x, dtype=np.float64); xc.sort_indices()
-        colptr = np.ascontiguousarray(xc.indptr, dtype=np.int64); rowidx = np.ascontiguousarray(xc.indices, dtype=np.int32)
-        vals = np.ascontiguousarray(xc.data, dtype=np.float64)
+        colptr, rowidx, vals = _csc_arrays(x)
         yh = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
         a.c.accelerate = 0                                             # oemSparse has no acceleration
         L.check(lib.oemgpu_fit_sparse(n, p, colptr.ctypes.data, _iptr(rowidx), _dptr(vals), _dptr(yh), int(bool(standardize)),
@@ -456,12 +466,7 @@ def oem_fit_logistic_sparse(x, y, penalty=None, weights=(), lambda_=(), nlambda=
     lam_list = _lambda_list(lambda_, len(penalty))
     a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
               compute_loss, penalty_factor, groups, unique_groups, group_weights, interrupt=interrupt)
-    xc = sp.csc_matrix(x, dtype=np.float64, copy=True)
-    xc.sum_duplicates()
-    xc.sort_indices()
-    colptr = np.ascontiguousarray(xc.indptr, dtype=np.int64)
-    rowidx = np.ascontiguousarray(xc.indices, dtype=np.int32)
-    vals = np.ascontiguousarray(xc.data, dtype=np.float64)
+    colptr, rowidx, vals = _csc_arrays(x)
     L.check(L.lib().oemgpu_fit_logistic_sparse(n, p, colptr.ctypes.data, _iptr(rowidx), _dptr(vals), _dptr(yh), int(bool(standardize)),
                                                int(bool(intercept)), int(irls_maxit), float(irls_tol), C.byref(a.c), *a.outputs(p + 1)))
     return OemFitBinomial(_decorate(a, penalty, varnames, True, n, p, family="binomial"))

@@ -1079,11 +1079,6 @@ __global__ __launch_bounds__(256) void sum_in_order_kernel(const double *__restr
     }
 }
 
-__global__ void accumulate_kernel(double *__restrict__ dst, const double *__restrict__ src, size_t n)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] += src[i];
-}
-
 // moments of one device-resident shard into `moments` (overwrite) ; tpart/vpart scratch from the workspace
 int shard_moments(oemgpu_ctx *c, const GramPlan &pl, const double *x, int64_t n, int64_t ld, const double *y,
                   const double *sums, double *tpart, double *vpart, double *moments)
@@ -1974,24 +1969,6 @@ static __global__ void scale_intercept_kernel(double *__restrict__ xx, double *_
     else { xx[(size_t)j * q] *= intval; xx[j] *= intval; }
 }
 
-// rows [r0, r1) of a compressed-column matrix into a zeroed dense column-major tile (row indices increase inside a column:
-// one lower_bound per workgroup finds where the tile's part of the column starts)
-static __global__ void csc_densify_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx, const double *__restrict__ val,
-                                          int64_t r0, int64_t r1, int64_t ld, double *__restrict__ xd)
-{
-    __shared__ int64_t first;
-    const int j = blockIdx.y;
-    const int64_t lo0 = colptr[j], hi0 = colptr[j + 1];
-    if (threadIdx.x == 0) {
-        int64_t lo = lo0, hi = hi0;
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (rowidx[mid] < r0) lo = mid + 1; else hi = mid; }
-        first = lo;
-    }
-    __syncthreads();
-    const int64_t k = first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < hi0) { const int64_t r = rowidx[k]; if (r < r1) xd[(size_t)j * ld + (r - r0)] = val[k]; }
-}
-
 // nbatch moment buffers (instance b at moments + b * mstride, all OUTSIDE the context workspace), one finalize each, then ONE
 // launch that walks all their paths side by side (q <= SMALL_P_MAX).  Outputs as in run_paths.
 // cs != nullptr: observation weights -- the moments are those of the p + 1 data columns [sqrt(w) | sqrt(w) X] ((p + 3)^2 each) and
@@ -2523,41 +2500,28 @@ int oemgpu_fit_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t
     const int q = p + (intercept ? 1 : 0);
     int rc = check_opts(o, p, q);             // R prepends the unpenalised group 0 for the intercept slot (ref R/oem.R:296-338); oemSparse scans all groups.size() = q slots (ref src/oem_sparse.h:465)
     if (rc) return rc;
+    if (n <= p && intercept) {
+        set_error("a sparse x with p >= n and an intercept: the reference multiplies the n x p map by a vector of p + 1 entries (src/oem_sparse.h:638-647) -- "
+                  "nothing well-formed to reproduce; intercept = FALSE is served");
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    const int64_t maxcol = csc_check("fit_sparse", n, p, colptr, rowidx, values, nullptr);
+    if (maxcol < 0) return (int)maxcol;
     if (n <= p) {
         // nobs <= nvars: the XXt branch (ref src/oem_sparse.h:607-612, 638-647) is oemBig's, line for line
-        if (intercept) {
-            set_error("a sparse x with p >= n and an intercept: the reference multiplies the n x p map by a vector of p + 1 entries (src/oem_sparse.h:638-647) -- "
-                      "nothing well-formed to reproduce; intercept = FALSE is served");
-            return OEMGPU_ERR_UNSUPPORTED;
-        }
-        const int64_t nnz0 = colptr[p];
-        if (nnz0 < 0 || (nnz0 > 0 && (!rowidx || !values))) { set_error("fit_sparse: bad compressed-column arrays"); return OEMGPU_ERR_ARG; }
         std::vector<double> xc;                                         // n <= p rows: the dense copy the wide engine reads
         try { xc.assign((size_t)n * p, 0.0); }
         catch (const std::bad_alloc &) { set_error("sparse x with p >= n: no host memory for the dense %lld x %d copy", (long long)n, p); return OEMGPU_ERR_ARG; }
         for (int j = 0; j < p; ++j)
-            for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) {
-                if (rowidx[k] < 0 || rowidx[k] >= n) { set_error("fit_sparse: row index out of range"); return OEMGPU_ERR_ARG; }
-                xc[(size_t)j * n + rowidx[k]] = values[k];
-            }
+            for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) xc[(size_t)j * n + rowidx[k]] = values[k];
         return fit_big_wide_host(xc.data(), n, p, y, standardize, o, beta, lambda_out, niter, loss, d, o->compute_loss != 0);
     }
     const int64_t nnz = colptr[p];
-    if (nnz < 0 || (nnz > 0 && (!rowidx || !values))) { set_error("fit_sparse: bad compressed-column arrays"); return OEMGPU_ERR_ARG; }
-    // rows per staging tile: the dense tile is capped at 2 GiB, whatever n is
-    int64_t rcrows = (int64_t)(2147483648.0 / (8.0 * p)) / 64 * 64;
-    if (sw().OEM_SPARSE_TILE_ROWS.set) { const long long t = sw().OEM_SPARSE_TILE_ROWS.num / 64 * 64; if (t >= 64) rcrows = t; }   // test knob: several tiles on small data
-    if (rcrows < 64) rcrows = 64;
-    if (rcrows > n) rcrows = n;
-    const int64_t ld = (rcrows + 1) / 2 * 2;
     // intval = sqrt(mean(diag(XX)) / n) with XX the (standardised) Gram before the division by n (ref src/oem_sparse.h:493-508, 577-578)
     double intval = 1.0;
-    int64_t maxcol = 0;
     {
         double xxdiag = 0.0;
         for (int j = 0; j < p; ++j) {
-            if (colptr[j + 1] < colptr[j]) { set_error("fit_sparse: colptr must be non-decreasing"); return OEMGPU_ERR_ARG; }
-            if (colptr[j + 1] - colptr[j] > maxcol) maxcol = colptr[j + 1] - colptr[j];
             double ss = 0.0;
             for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) ss += values[k] * values[k];
             double cs = ss / ((double)n - 1.0);
@@ -2569,15 +2533,7 @@ int oemgpu_fit_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t
     }
     oemgpu_ctx *c = ctx_acquire(o->device);
     if (!c) return OEMGPU_ERR_NO_DEVICE;
-    // Two ways to the moment buffer.  Compressed columns (sparse.hip): p * nnz / 2 LDS gathers, the cost follows the non-zeros --
-    // taken up to 2 % density, where it beats the dense pass (n p^2 MFMA flops whatever the density) several times over.
-    // Denser: zero-filled row tiles through the FP64-MFMA kernels.  OEM_SPARSE_GRAM=csc|dense forces one (tests compare them).
-    bool use_csc = csc_moments_fits(p) && (double)nnz <= 0.02 * (double)n * (double)p && n < ((int64_t)1 << 31);
-    if (sw().OEM_SPARSE_GRAM.set) {
-        const char *ev = sw().OEM_SPARSE_GRAM.str;
-        if (!strcmp(ev, "csc") && csc_moments_fits(p)) use_csc = true;
-        if (!strcmp(ev, "dense")) use_csc = false;
-    }
+    const SparseRoute R = sparse_route(n, p, nnz);
     double *xd = nullptr, *yd = nullptr, *vd = nullptr;
     int64_t *cd = nullptr;
     int32_t *rd = nullptr;
@@ -2585,7 +2541,7 @@ int oemgpu_fit_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t
     hipError_t e = hipSuccess;
     {                                                       // every staging buffer out of the context's grow-only input buffer
         Bump S;
-        const size_t a_x = S.take(use_csc ? csc_moments_work_bytes(n, p) : sizeof(double) * (size_t)ld * p),
+        const size_t a_x = S.take(R.csc ? csc_moments_work_bytes(n, p) : sizeof(double) * (size_t)R.ld * p),
                      a_y = S.take(sizeof(double) * (size_t)(n + 2)),
                      a_c = S.take(sizeof(int64_t) * (size_t)(p + 1)), a_r = S.take(sizeof(int32_t) * (size_t)(nnz + 1)),
                      a_v = S.take(sizeof(double) * (size_t)(nnz + 1));
@@ -2593,41 +2549,26 @@ int oemgpu_fit_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t
         xd = (double *)(c->xres + a_x); cwork = c->xres + a_x; yd = (double *)(c->xres + a_y); cd = (int64_t *)(c->xres + a_c);
         rd = (int32_t *)(c->xres + a_r); vd = (double *)(c->xres + a_v);
     }
-    if (e == hipSuccess && !use_csc) e = hipMemsetAsync(xd, 0, sizeof(double) * (size_t)ld * p, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(yd, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(cd, colptr, sizeof(int64_t) * (size_t)(p + 1), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(rd, rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(vd, values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { set_error("fit_sparse: device staging failed: %s", hipGetErrorString(e)); rc = OEMGPU_ERR_HIP; }
-    // The Gram of a sparse X through the dense FP64-MFMA pass: row tiles of at most 2 GiB are zeroed, filled with the tile's
-    // non-zeros (one 8-byte store each) and read back by the moment kernels; the tiles' moments are added in row order.  At the
-    // densities of the reference's examples (1 %) the whole x is one tile of a few hundred MB and a fraction of a millisecond.  The
-    // matrix pipe does not care about zeros: the cost is that of a dense n x p pass whatever the density, with no dense copy of x
-    // beyond one tile.  (A compressed-column Gram kernel would win below ~0.1 % density; it is not built.)
+    // The moment buffer by the route of sparse_route (sparse.hip): at the densities of the reference's examples (1 %) the compressed
+    // columns; denser, the tiles of csc_tile_moments -- with one tile of a few hundred MB and a fraction of a millisecond there.
     if (!rc) {
-        const GramPlan plmax = gram_plan_bound(rcrows, p, c->num_cu);
+        const GramPlan plmax = gram_plan_bound(R.rows, p, c->num_cu);
         Bump B;
         const size_t mlen = (size_t)oemgpu_moments_len(p);
         const size_t a_mom = B.take(mlen * 8), a_tmp = B.take(mlen * 8), a_t = B.take(plmax.tpart_doubles * 8), a_v = B.take(plmax.vpart_doubles * 8);
         const size_t a_xx = B.take((size_t)q * q * 8), a_xy = B.take((size_t)q * 8), a_st = B.take((size_t)stats_len(p) * 8);
         rc = ctx_reserve(c, B.off + paths_ws_bytes(p, q, o) + 4096) ? OEMGPU_ERR_HIP : 0;
-        double *mom = (double *)(c->ws + a_mom), *mtmp = (double *)(c->ws + a_tmp);
-        if (!rc && hipMemsetAsync(mom, 0, mlen * 8, c->stream) != hipSuccess) rc = OEMGPU_ERR_HIP;
-        if (!rc && use_csc) rc = launch_csc_moments(c->stream, cd, rd, vd, yd, n, p, cwork, mom);
-        for (int64_t r0 = 0; r0 < n && !rc && !use_csc; r0 += rcrows) {
-            const int64_t r1 = r0 + rcrows < n ? r0 + rcrows : n, nr = r1 - r0;
-            if (hipMemsetAsync(xd, 0, sizeof(double) * (size_t)ld * p, c->stream) != hipSuccess) { set_error("fit_sparse: memset failed"); rc = OEMGPU_ERR_HIP; break; }
-            if (nnz > 0) {
-                hipLaunchKernelGGL(csc_densify_kernel, dim3((unsigned)((maxcol + 255) / 256), p), dim3(256), 0, c->stream, cd, rd, vd, r0, r1, ld, xd);
-                if (hipGetLastError() != hipSuccess) { set_error("fit_sparse: densify launch failed"); rc = OEMGPU_ERR_HIP; break; }
-            }
-            const GramPlan pl = gram_plan(nr, p, c->num_cu);
-            if (pl.tpart_doubles > plmax.tpart_doubles || pl.vpart_doubles > plmax.vpart_doubles) { set_error("internal: tile plan larger than its scratch"); rc = OEMGPU_ERR_INTERNAL; break; }
-            rc = shard_moments(c, pl, xd, nr, ld, yd + r0, nullptr, (double *)(c->ws + a_t), (double *)(c->ws + a_v), mtmp);
-            if (!rc) hipLaunchKernelGGL(accumulate_kernel, dim3(64), dim3(256), 0, c->stream, mom, mtmp, mlen);
-        }
+        double *mom = (double *)(c->ws + a_mom);
+        if (!rc) rc = R.csc ? launch_csc_moments(c->stream, cd, rd, vd, yd, n, p, cwork, mom)
+                            : csc_tile_moments(c, R, cd, rd, vd, nullptr, yd, n, p, maxcol, xd, (double *)(c->ws + a_t), (double *)(c->ws + a_v),
+                                               (double *)(c->ws + a_tmp), mom);
         double *xx = (double *)(c->ws + a_xx), *xy = (double *)(c->ws + a_xy), *st = (double *)(c->ws + a_st);
-        if (!rc) rc = launch_finalize(c->stream, (double *)(c->ws + a_mom), nullptr, p, OEMGPU_SEM_BIG, standardize, intercept, xx, xy, st);
+        if (!rc) rc = launch_finalize(c->stream, mom, nullptr, p, OEMGPU_SEM_BIG, standardize, intercept, xx, xy, st);
         std::vector<double> sf;
         if (!rc && intercept) {
             hipLaunchKernelGGL(scale_intercept_kernel, dim3((q + 255) / 256), dim3(256), 0, c->stream, xx, xy, q, intval);

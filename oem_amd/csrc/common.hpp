@@ -59,7 +59,24 @@ int launch_finalize(hipStream_t s, const double *moments, const double *sums, in
 int launch_xtx_prepare(hipStream_t s, const double *xtx, const double *xty, const double *sf_inv /* or null */, int p,
                        double *xx, double *xy, double *stats);
 
+// moments of one device-resident shard into `moments` (overwrite), timed as OEMGPU_T_GRAMK (api.hip)
+int shard_moments(oemgpu_ctx *c, const GramPlan &pl, const double *x, int64_t n, int64_t ld, const double *y, const double *sums,
+                  double *tpart, double *vpart, double *moments);
+int launch_moments_add(hipStream_t s, double *acc, const double *m, size_t len, bool first);   // acc = m (first) or acc + m (sparse.hip)
+
 // ------------------------------------------------------------------ sparse x (sparse.hip): moments of a compressed-sparse-column matrix
+// both sparse fits, before any device lookup: colptr[0] = 0 and non-decreasing, row indices in [0, n) and strictly increasing inside a
+// column.  The longest column, or OEMGPU_ERR_ARG (error text prefixed by `who`); rowcount (or null): [i + 1] = non-zeros of row i
+int64_t csc_check(const char *who, int64_t n, int p, const int64_t *colptr, const int32_t *rowidx, const double *values,
+                  std::vector<int64_t> *rowcount);
+// the route to the moments: compressed columns when the kernel fits in LDS, nnz <= 2 % of n p (there it beats the n p^2 dense pass)
+// and n < 2^31; else zero-filled row tiles of `rows` rows (<= 2 GiB; set on both routes) and leading dimension ld
+struct SparseRoute { bool csc; int64_t rows, ld; };
+SparseRoute sparse_route(int64_t n, int p, int64_t nnz);
+// the tile route: per tile of R.rows rows zero it, densify (times sqrt(w[row]) if w), shard_moments -> mtile, add into M in row order.
+// y: the Gaussian fit's y, or null; tpart / vpart: the scratch of gram_plan_bound(R.rows, p)
+int csc_tile_moments(oemgpu_ctx *c, const SparseRoute &R, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *w,
+                     const double *y, int64_t n, int p, int64_t maxcol, double *tile, double *tpart, double *vpart, double *mtile, double *M);
 size_t csc_moments_work_bytes(int64_t n, int p);
 bool csc_moments_fits(int p);
 int launch_csc_moments(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *y, int64_t n, int p,

@@ -213,12 +213,6 @@ __global__ __launch_bounds__(256) void logit_sum_kernel(const double *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------------- Gram pieces
-__global__ __launch_bounds__(256) void logit_mom_add_kernel(double *__restrict__ acc, const double *__restrict__ m, size_t len, int first)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < len) acc[i] = first ? m[i] : acc[i] + m[i];
-}
-
 // XX = Z'Z / n from the lower triangle of the moments ((q + 2) x (q + 2), column-major)
 __global__ __launch_bounds__(256) void logit_xx_kernel(const double *__restrict__ M, int q, double n, double *__restrict__ xx)
 {
@@ -418,6 +412,13 @@ __global__ void logit_fill_kernel(double *a, int n, double v)
 
 }  // namespace
 
+int launch_logit_fill(hipStream_t s, double *a, int n, double v)
+{
+    hipLaunchKernelGGL(logit_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, n, v);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host driver
 struct LogitStats {
     double ms_rows = 0, ms_gram = 0, ms_inner = 0, irls_steps = 0, inner_iters = 0, row_passes = 0, grams = 0, wall_ms = 0;
@@ -537,8 +538,8 @@ struct DenseLogitData final : LogitData {
             const GramPlan gpl = gram_plan(nrow, q, c->num_cu);
             r = launch_gram(s, gpl, z, nrow, P.rbz, z, nullptr, tp, vp);
             if (!r) r = launch_moments_reduce(s, gpl, tp, vp, mb);
+            if (!r) r = launch_moments_add(s, ma, mb, m2, b == 0);
             if (r) return r;
-            hipLaunchKernelGGL(logit_mom_add_kernel, dim3((unsigned)((m2 + 255) / 256)), dim3(256), 0, s, ma, mb, m2, b == 0 ? 1 : 0);
         }
         hipLaunchKernelGGL(logit_xx_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, ma, q, (double)n, xx);
         hipLaunchKernelGGL(logit_sum_kernel, dim3((p + 2 + 255) / 256), dim3(256), 0, s, part, P.nchunk, p + 2, g);

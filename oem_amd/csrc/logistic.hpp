@@ -25,6 +25,7 @@ struct LogitData {
 int logistic_check(int64_t n, int32_t p, int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o);
 int logistic_irls(oemgpu_ctx *c, LogitData &D, int64_t n, int32_t p, int32_t intercept, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
                   double *beta_out, double *lambda_out, int32_t *niter, double *loss_out, double *d_out);
+int launch_logit_fill(hipStream_t s, double *a, int n, double v);   // a[0 .. n) = v
 extern const int LOGIT_WG_MAX_Q;                         // q up to which the inner solve is one persistent workgroup
 extern const int LOGIT_P_LIMIT;                          // the largest p served
 

@@ -20,15 +20,13 @@
 //     r = y - prob and the loss terms; writes W and r and the chunk partials of [sum r, sum W, sum loss];
 //   * lsp_cols_kernel: a workgroup per column reads its non-zeros once: X'r and X'W, fixed-order sums; one more workgroup adds the
 //     row partials in chunk order;
-//   * the weighted Gram X'WX: the compressed-column kernel with the row weight gathered at its scatter (sparse.hip: csc_gram_kernel
-//     <true>), or zero-filled row tiles of sqrt(W) x through the FP64-MFMA moment pass, the tiles' moments added in row order.
-//     The route follows oemgpu_fit_sparse's rule (the kernel fits, density <= 2 %, n < 2^31); OEM_SPARSE_GRAM=csc|dense forces one;
+//   * the weighted Gram X'WX on the route the Gaussian sparse fit takes too (sparse.hip: sparse_route): the compressed-column kernel
+//     with the row weight gathered at its scatter (csc_gram_kernel<true>), or csc_tile_moments over zero-filled row tiles of sqrt(W) x;
 //   * lsp_intval_kernel + lsp_xx_kernel: xxdiag / intval and XX.
 // No float atomics anywhere: two calls give the same bits.
 #include "logistic.hpp"
 
 #include <cmath>
-#include <cstring>
 #include <vector>
 
 namespace oemgpu {
@@ -54,12 +52,6 @@ __global__ __launch_bounds__(256) void lsp_scale_kernel(const int64_t *__restric
         if (cs == 0.0) cs = 1.0;
         s[j] = 1.0 / sqrt(cs);
     }
-}
-
-__global__ void lsp_fill_kernel(double *a, int n, double v)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) a[i] = v;
 }
 
 // the row pass: workgroup c owns rows [c ch, (c + 1) ch), a thread per row (rows tid, tid + 256, ...), the row's entries in column order
@@ -133,29 +125,6 @@ __global__ __launch_bounds__(256) void lsp_cols_kernel(const int64_t *__restrict
     if (tid == 0) { g[1 + j] = red[0][0]; if (w) cw[j] = red[1][0]; }
 }
 
-// tile route: rows [r0, r1) of sqrt(W) x into a zeroed column-major tile (api.hip's csc_densify_kernel with the row weight)
-__global__ __launch_bounds__(256) void lsp_densify_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx, const double *__restrict__ val,
-                                                          const double *__restrict__ w, int64_t r0, int64_t r1, int64_t ld, double *__restrict__ xd)
-{
-    __shared__ int64_t first;
-    const int j = blockIdx.y;
-    const int64_t lo0 = colptr[j], hi0 = colptr[j + 1];
-    if (threadIdx.x == 0) {
-        int64_t lo = lo0, hi = hi0;
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (rowidx[mid] < r0) lo = mid + 1; else hi = mid; }
-        first = lo;
-    }
-    __syncthreads();
-    const int64_t k = first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < hi0) { const int64_t r = rowidx[k]; if (r < r1) xd[(size_t)j * ld + (r - r0)] = sqrt(w[r]) * val[k]; }
-}
-
-__global__ __launch_bounds__(256) void lsp_mom_add_kernel(double *__restrict__ acc, const double *__restrict__ m, size_t len, int first)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < len) acc[i] = first ? m[i] : acc[i] + m[i];
-}
-
 // xxdiag = mean diag (S X'WX S) and intval = sqrt((xxdiag / sum W) / n), only while xxdiag <= 0 (h :477-481).  One workgroup.
 __global__ __launch_bounds__(256) void lsp_intval_kernel(const double *__restrict__ M, int p, const double *__restrict__ s, double n,
                                                          double *__restrict__ sw)
@@ -210,11 +179,6 @@ struct LspPlan {
     size_t bound;      // ws_bytes stays within this
 };
 
-static bool lsp_csc_rule(int64_t n, int p, int64_t nnz)
-{
-    return csc_moments_fits(p) && (double)nnz <= 0.02 * (double)n * (double)p && n < ((int64_t)1 << 31);
-}
-
 // the workspace of the fit, piece by piece (offsets into it when off != null)
 static size_t lsp_layout(const LspPlan &P, int64_t n, int p, int64_t nnz, int num_cu, size_t *off)
 {
@@ -250,26 +214,20 @@ static size_t lsp_layout(const LspPlan &P, int64_t n, int p, int64_t nnz, int nu
     return B.off;
 }
 
-static LspPlan lsp_plan(int64_t n, int p, int64_t nnz, int intercept, int num_cu, int force_csc /* -1: the rule */)
+static LspPlan lsp_plan(int64_t n, int p, int64_t nnz, int intercept, int num_cu)
 {
     LspPlan P;
     const int q = p + (intercept ? 1 : 0);
-    P.csc = force_csc >= 0 ? force_csc : (int)lsp_csc_rule(n, p, nnz);
+    const SparseRoute R = sparse_route(n, p, nnz);
+    P.csc = R.csc;
     P.inner_wg = q <= LOGIT_WG_MAX_Q;
     int64_t ch = (n + 4 * (int64_t)num_cu - 1) / (4 * (int64_t)num_cu);
     ch = (ch + 63) / 64 * 64;
     if (ch < 64) ch = 64;
     P.ch = ch;
     P.nchunk = (n + ch - 1) / ch;
-    P.rcrows = 0; P.ld = 0;
-    if (!P.csc) {                                           // tiles of at most 2 GiB, as oemgpu_fit_sparse stages them
-        int64_t rc = (int64_t)(2147483648.0 / (8.0 * p)) / 64 * 64;
-        if (sw().OEM_SPARSE_TILE_ROWS.set) { const long long t = sw().OEM_SPARSE_TILE_ROWS.num / 64 * 64; if (t >= 64) rc = t; }
-        if (rc < 64) rc = 64;
-        if (rc > n) rc = n;
-        P.rcrows = rc;
-        P.ld = (rc + 1) / 2 * 2;
-    }
+    P.rcrows = P.csc ? 0 : R.rows;
+    P.ld = P.csc ? 0 : R.ld;
     P.ws_bytes = lsp_layout(P, n, p, nnz, num_cu, nullptr);
     // the bound: 40 bytes a row, 24 a non-zero, the chunk pointers, the moments, and a Gram scratch that does not grow with n
     // (csc: the range sums, at most 256 MB or one p x p; tiles: at most 2 GiB or 64 rows, with their MFMA partials)
@@ -327,8 +285,8 @@ struct SparseLogitData final : LogitData {
     }
     int scale(double *sc) override
     {
-        if (standardize) hipLaunchKernelGGL(lsp_scale_kernel, dim3(p), dim3(256), 0, c->stream, colptr, val, n, sc);
-        else hipLaunchKernelGGL(lsp_fill_kernel, dim3((p + 255) / 256), dim3(256), 0, c->stream, sc, p, 1.0);
+        if (!standardize) return launch_logit_fill(c->stream, sc, p, 1.0);
+        hipLaunchKernelGGL(lsp_scale_kernel, dim3(p), dim3(256), 0, c->stream, colptr, val, n, sc);
         OEM_HIP(hipGetLastError());
         return 0;
     }
@@ -351,26 +309,11 @@ struct SparseLogitData final : LogitData {
     int hessian(const double *, const double *sc, int64_t, double *, double *xx) override
     {
         hipStream_t s = c->stream;
-        const size_t m2 = (size_t)(p + 2) * (p + 2);
-        double *M = mb;
-        if (P.csc) {
-            int rc = launch_csc_wgram(s, colptr, rowidx, val, W, cptr, n, p, gw, mb);
-            if (rc) return rc;
-        } else {
-            int tno = 0;
-            for (int64_t r0 = 0; r0 < n; r0 += P.rcrows, ++tno) {
-                const int64_t r1 = r0 + P.rcrows < n ? r0 + P.rcrows : n, nr = r1 - r0;
-                OEM_HIP(hipMemsetAsync(tile, 0, 8 * (size_t)P.ld * p, s));
-                if (maxcol > 0) hipLaunchKernelGGL(lsp_densify_kernel, dim3((unsigned)((maxcol + 255) / 256), p), dim3(256), 0, s, colptr, rowidx, val, W, r0, r1, P.ld, tile);
-                OEM_HIP(hipGetLastError());
-                const GramPlan gpl = gram_plan(nr, p, c->num_cu);
-                int rc = launch_gram(s, gpl, tile, nr, P.ld, tile, nullptr, tp, vp);
-                if (!rc) rc = launch_moments_reduce(s, gpl, tp, vp, mb);
-                if (rc) return rc;
-                hipLaunchKernelGGL(lsp_mom_add_kernel, dim3((unsigned)((m2 + 255) / 256)), dim3(256), 0, s, ma, mb, m2, tno == 0 ? 1 : 0);
-            }
-            M = ma;
-        }
+        const SparseRoute R{false, P.rcrows, P.ld};
+        const int rc = P.csc ? launch_csc_wgram(s, colptr, rowidx, val, W, cptr, n, p, gw, mb)
+                             : csc_tile_moments(c, R, colptr, rowidx, val, W, nullptr, n, p, maxcol, tile, tp, vp, mb, ma);
+        if (rc) return rc;
+        const double *M = P.csc ? mb : ma;
         if (intercept) hipLaunchKernelGGL(lsp_intval_kernel, dim3(1), dim3(256), 0, s, M, p, sc, (double)n, swd);
         hipLaunchKernelGGL(lsp_xx_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, M, p, intercept, sc, cw, swd, (double)n, xx);
         OEM_HIP(hipGetLastError());
@@ -380,7 +323,8 @@ struct SparseLogitData final : LogitData {
 
 }  // namespace
 
-// checks that need no device, the compressed-column arrays included; fills the row pointers of the row copy and the longest column
+// the checks that need no device: the refusals, then the compressed-column arrays (csc_check); fills the row pointers of the row copy
+// and the longest column
 static int lsp_check(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, int32_t standardize, int32_t intercept,
                      int32_t irls_maxit, double irls_tol, const oemgpu_opts *o, std::vector<int64_t> *rowptr, int64_t *maxcol)
 {
@@ -398,23 +342,8 @@ static int lsp_check(int64_t n, int32_t p, const int64_t *colptr, const int32_t 
     if (p > LOGIT_P_LIMIT) { set_error("fit_logistic_sparse: p > %d is not supported", LOGIT_P_LIMIT); return OEMGPU_ERR_UNSUPPORTED; }
     int rc = logistic_check(n, p, intercept, 0, irls_maxit, irls_tol, o);
     if (rc) return rc;
-    if (colptr[0] != 0) { set_error("fit_logistic_sparse: colptr[0] must be 0"); return OEMGPU_ERR_ARG; }
-    for (int j = 0; j < p; ++j)
-        if (colptr[j + 1] < colptr[j]) { set_error("fit_logistic_sparse: colptr must be non-decreasing"); return OEMGPU_ERR_ARG; }
-    const int64_t nnz = colptr[p];
-    if (nnz > 0 && (!rowidx || !values)) { set_error("fit_logistic_sparse: NULL row indices or values"); return OEMGPU_ERR_ARG; }
-    rowptr->assign((size_t)n + 1, 0);
-    int64_t mc = 0;
-    for (int j = 0; j < p; ++j) {
-        const int64_t k0 = colptr[j], k1 = colptr[j + 1];
-        if (k1 - k0 > mc) mc = k1 - k0;
-        for (int64_t k = k0; k < k1; ++k) {
-            const int32_t i = rowidx[k];
-            if (i < 0 || (int64_t)i >= n) { set_error("fit_logistic_sparse: row index %d of column %d outside [0, n)", (int)i, j); return OEMGPU_ERR_ARG; }
-            if (k > k0 && i <= rowidx[k - 1]) { set_error("fit_logistic_sparse: row indices of column %d are not strictly increasing", j); return OEMGPU_ERR_ARG; }
-            (*rowptr)[(size_t)i + 1] += 1;
-        }
-    }
+    const int64_t mc = csc_check("fit_logistic_sparse", n, p, colptr, rowidx, values, rowptr);
+    if (mc < 0) return (int)mc;
     for (int64_t i = 0; i < n; ++i) (*rowptr)[(size_t)i + 1] += (*rowptr)[(size_t)i];
     *maxcol = mc;
     return 0;
@@ -439,17 +368,11 @@ int oemgpu_fit_logistic_sparse(int64_t n, int32_t p, const int64_t *colptr, cons
     oemgpu_ctx *c = ctx_acquire(o->device);
     if (!c) return OEMGPU_ERR_NO_DEVICE;
     const int64_t nnz = colptr[p];
-    int force = -1;
-    if (sw().OEM_SPARSE_GRAM.set) {
-        const char *ev = sw().OEM_SPARSE_GRAM.str;
-        if (!strcmp(ev, "csc") && csc_moments_fits(p)) force = 1;
-        if (!strcmp(ev, "dense")) force = 0;
-    }
     SparseLogitData D;
     D.hess_every = true;                                   // h :866, :973: every step but the skipped first of a later lambda
     D.c = c; D.n = n; D.nnz = nnz; D.maxcol = maxcol; D.p = p; D.q = p + (intercept ? 1 : 0); D.intercept = intercept; D.standardize = standardize;
     D.h_colptr = colptr; D.h_rowptr = rowptr.data(); D.h_rowidx = rowidx; D.h_val = values; D.h_y = y;
-    D.P = lsp_plan(n, p, nnz, intercept, c->num_cu, force);
+    D.P = lsp_plan(n, p, nnz, intercept, c->num_cu);
     rc = logistic_irls(c, D, n, p, intercept, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
     (void)hipStreamSynchronize(c->stream);
     ctx_release(c);
@@ -462,7 +385,7 @@ int oemgpu_fit_logistic_sparse(int64_t n, int32_t p, const int64_t *colptr, cons
 int oemgpu_selftest_logistic_sparse_plan(int64_t n, int32_t p, int64_t nnz, int32_t intercept, int32_t num_cu, int64_t *out)
 {
     if (n < 1 || p < 1 || nnz < 0 || num_cu < 1 || !out) { set_error("selftest_logistic_sparse_plan: bad argument"); return OEMGPU_ERR_ARG; }
-    const LspPlan P = lsp_plan(n, p, nnz, intercept, num_cu, -1);
+    const LspPlan P = lsp_plan(n, p, nnz, intercept, num_cu);
     out[0] = P.csc; out[1] = P.inner_wg; out[2] = (int64_t)P.ws_bytes; out[3] = (int64_t)P.bound; out[4] = P.rcrows; out[5] = P.nchunk;
     out[6] = P.ch; out[7] = csc_chunks(n);
     return 0;

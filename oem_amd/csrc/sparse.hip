@@ -1,7 +1,7 @@
 // sparse.hip -- the moment buffer of a compressed-sparse-column x WITHOUT densifying it (ref src/oem_sparse.h:493-615: XtX() of a
-// dgCMatrix through Eigen's sparse product, column sums and X'y by column loops).
+// dgCMatrix through Eigen's sparse product, column sums and X'y by column loops), and the pieces both sparse fits share (common.hpp).
 //
-// The dense FP64-MFMA pass over zero-filled row tiles (api.hip: oemgpu_fit_sparse) costs n p^2 flops whatever the density.  Here the
+// The dense FP64-MFMA pass over zero-filled row tiles (csc_tile_moments) costs n p^2 flops whatever the density.  Here the
 // cost follows the non-zeros: for a column a the other columns' non-zeros are multiplied against a DENSE copy of a row chunk of
 // column a held in LDS,
 //     G[a][b] = sum over row chunks c of  sum_{k in column b, chunk c} val[k] * dense_a_c[row[k]],        b >= a,
@@ -15,7 +15,7 @@
 //     ran 1.3 ms on the man/oem.Rd example, three times the dense pass it was meant to beat.)
 //   * csc_stats_kernel: column sums, X'y (y gathered at the column's rows), sum y, sum y^2, n.
 // The result is the same (p + 2)^2 moment buffer about 0 that the MFMA kernels produce (include/oemgpu.h).
-#include "common.hpp"
+#include "ctx.hpp"
 #include "path_dev.hpp"
 
 namespace oemgpu {
@@ -238,6 +238,33 @@ __global__ __launch_bounds__(256) void csc_to_csr_kernel(const int64_t *__restri
     }
 }
 
+// rows [r0, r1) of a compressed-column matrix into a zeroed dense column-major tile, times sqrt(w[row]) when w is given (row indices
+// increase inside a column: one lower_bound per workgroup finds where the tile's part of the column starts)
+__global__ __launch_bounds__(256) void csc_densify_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx, const double *__restrict__ val,
+                                                          const double *__restrict__ w, int64_t r0, int64_t r1, int64_t ld, double *__restrict__ xd)
+{
+    __shared__ int64_t first;
+    const int j = blockIdx.y;
+    const int64_t lo0 = colptr[j], hi0 = colptr[j + 1];
+    if (threadIdx.x == 0) {
+        int64_t lo = lo0, hi = hi0;
+        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (rowidx[mid] < r0) lo = mid + 1; else hi = mid; }
+        first = lo;
+    }
+    __syncthreads();
+    const int64_t k = first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < hi0) { const int64_t r = rowidx[k]; if (r < r1) xd[(size_t)j * ld + (r - r0)] = w ? sqrt(w[r]) * val[k] : val[k]; }
+}
+
+__global__ __launch_bounds__(256) void moments_add_kernel(double *__restrict__ acc, const double *__restrict__ m, size_t len, int first)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < len) acc[i] = first ? m[i] : acc[i] + m[i];
+}
+
+// LDS of csc_gram_kernel: the dense chunk, p accumulators, 2 p chunk pointers
+size_t csc_gram_lds(int p) { return (size_t)SRC * 8 + (size_t)p * 16 + 64; }
+
 }  // namespace
 
 int launch_gram_loss(hipStream_t s, const double *xx, const double *xy, const double *stats, int q, const double *beta, const double *sinv,
@@ -270,34 +297,15 @@ static int csc_ranges(int64_t n, int p)
     return nr < 1 ? 1 : nr;
 }
 
+int csc_chunks(int64_t n) { return (int)((n + SRC - 1) / SRC); }
+
 size_t csc_moments_work_bytes(int64_t n, int p)
 {
-    return sizeof(int32_t) * ((size_t)((n + SRC - 1) / SRC) + 1) * (size_t)p + 256 + sizeof(double) * ((size_t)csc_ranges(n, p) * p * p + 2 * NY) + 256;
+    return sizeof(int32_t) * ((size_t)csc_chunks(n) + 1) * (size_t)p + 256 + sizeof(double) * ((size_t)csc_ranges(n, p) * p * p + 2 * NY) + 256;
 }
 
-// can the compressed-column kernel take this matrix (LDS: the dense chunk, p accumulators, 2 p chunk pointers)?
-bool csc_moments_fits(int p) { return (size_t)SRC * 8 + (size_t)p * 16 + 64 <= 160 * 1024; }
-
-int launch_csc_moments(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *y, int64_t n, int p,
-                       void *work, double *moments)
-{
-    const int nchunk = (int)((n + SRC - 1) / SRC), nrange = csc_ranges(n, p);
-    int32_t *cptr = reinterpret_cast<int32_t *>(work);
-    const size_t cbytes = (sizeof(int32_t) * ((size_t)nchunk + 1) * (size_t)p + 255) / 256 * 256;
-    double *part = reinterpret_cast<double *>((char *)work + cbytes), *ypart = part + (size_t)nrange * p * p;
-    hipLaunchKernelGGL(csc_chunk_ptr_kernel, dim3(p, (nchunk + 1 + 255) / 256), dim3(256), 0, s, colptr, rowidx, p, nchunk, cptr);
-    const size_t sh = (size_t)SRC * 8 + (size_t)p * 16 + 64;
-    if (sh > 64 * 1024) OEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&csc_gram_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    hipLaunchKernelGGL(csc_gram_kernel<false>, dim3((p + 1) / 2, nrange), dim3(GT), sh, s, colptr, rowidx, val, cptr, p, nchunk, nrange, part, nullptr);
-    hipLaunchKernelGGL(csc_stats_kernel, dim3(p + NY), dim3(256), 0, s, colptr, rowidx, val, y, n, p, moments, ypart);
-    hipLaunchKernelGGL(csc_finish_kernel, dim3((unsigned)(((size_t)p * p + 255) / 256)), dim3(256), 0, s, part, nrange, ypart, NY, n, p, moments);
-    OEM_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---- the binomial fit's pieces (logistic_sparse.hip)
-int csc_chunks(int64_t n) { return (int)((n + SRC - 1) / SRC); }
-size_t csc_wgram_work_bytes(int64_t n, int p) { return sizeof(double) * ((size_t)csc_ranges(n, p) * p * p); }
+// can the compressed-column kernel take this matrix?
+bool csc_moments_fits(int p) { return csc_gram_lds(p) <= 160 * 1024; }
 
 // cptr: (csc_chunks(n) + 1) x p int32: where every column enters every chunk of rows
 int launch_csc_chunk_ptr(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, int64_t n, int p, int32_t *cptr)
@@ -307,6 +315,27 @@ int launch_csc_chunk_ptr(hipStream_t s, const int64_t *colptr, const int32_t *ro
     OEM_HIP(hipGetLastError());
     return 0;
 }
+
+int launch_csc_moments(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *y, int64_t n, int p,
+                       void *work, double *moments)
+{
+    const int nchunk = csc_chunks(n), nrange = csc_ranges(n, p);
+    int32_t *cptr = reinterpret_cast<int32_t *>(work);
+    const size_t cbytes = (sizeof(int32_t) * ((size_t)nchunk + 1) * (size_t)p + 255) / 256 * 256;
+    double *part = reinterpret_cast<double *>((char *)work + cbytes), *ypart = part + (size_t)nrange * p * p;
+    int rc = launch_csc_chunk_ptr(s, colptr, rowidx, n, p, cptr);
+    if (rc) return rc;
+    const size_t sh = csc_gram_lds(p);
+    if (sh > 64 * 1024) OEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&csc_gram_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    hipLaunchKernelGGL(csc_gram_kernel<false>, dim3((p + 1) / 2, nrange), dim3(GT), sh, s, colptr, rowidx, val, cptr, p, nchunk, nrange, part, nullptr);
+    hipLaunchKernelGGL(csc_stats_kernel, dim3(p + NY), dim3(256), 0, s, colptr, rowidx, val, y, n, p, moments, ypart);
+    hipLaunchKernelGGL(csc_finish_kernel, dim3((unsigned)(((size_t)p * p + 255) / 256)), dim3(256), 0, s, part, nrange, ypart, NY, n, p, moments);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- the binomial fit's pieces (logistic_sparse.hip)
+size_t csc_wgram_work_bytes(int64_t n, int p) { return sizeof(double) * ((size_t)csc_ranges(n, p) * p * p); }
 
 int launch_csc_to_csr(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const int32_t *cptr, int64_t n, int p,
                       const int64_t *rowptr, int32_t *ccol, double *cval)
@@ -321,11 +350,85 @@ int launch_csc_wgram(hipStream_t s, const int64_t *colptr, const int32_t *rowidx
                      int64_t n, int p, double *part, double *M)
 {
     const int nchunk = csc_chunks(n), nrange = csc_ranges(n, p);
-    const size_t sh = (size_t)SRC * 8 + (size_t)p * 16 + 64;
+    const size_t sh = csc_gram_lds(p);
     if (sh > 64 * 1024 && lds_limit_once(reinterpret_cast<const void *>(&csc_gram_kernel<true>), sh)) return OEMGPU_ERR_HIP;
     hipLaunchKernelGGL(csc_gram_kernel<true>, dim3((p + 1) / 2, nrange), dim3(GT), sh, s, colptr, rowidx, val, cptr, p, nchunk, nrange, part, w);
     hipLaunchKernelGGL(csc_finish_kernel, dim3((unsigned)(((size_t)p * p + 255) / 256)), dim3(256), 0, s, part, nrange, nullptr, 0, n, p, M);
     OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+
+// ---- shared by both sparse fits
+int64_t csc_check(const char *who, int64_t n, int p, const int64_t *colptr, const int32_t *rowidx, const double *values,
+                  std::vector<int64_t> *rowcount)
+{
+    if (colptr[0] != 0) { set_error("%s: colptr[0] must be 0", who); return OEMGPU_ERR_ARG; }
+    for (int j = 0; j < p; ++j)
+        if (colptr[j + 1] < colptr[j]) { set_error("%s: colptr must be non-decreasing", who); return OEMGPU_ERR_ARG; }
+    if (colptr[p] > 0 && (!rowidx || !values)) { set_error("%s: NULL row indices or values", who); return OEMGPU_ERR_ARG; }
+    if (rowcount) rowcount->assign((size_t)n + 1, 0);
+    int64_t maxcol = 0;
+    for (int j = 0; j < p; ++j) {
+        const int64_t k0 = colptr[j], k1 = colptr[j + 1];
+        if (k1 - k0 > maxcol) maxcol = k1 - k0;
+        // strictly increasing (one branch-free pass that vectorises), so inside [0, n) when its ends are; at fault: look for the entry
+        int bad = 0;
+        for (int64_t k = k0 + 1; k < k1; ++k) bad |= rowidx[k] <= rowidx[k - 1];
+        if (k1 > k0) bad |= rowidx[k0] < 0 || (int64_t)rowidx[k1 - 1] >= n;
+        for (int64_t k = k0; k < k1 && bad; ++k) {
+            const int32_t i = rowidx[k];
+            if (i < 0 || (int64_t)i >= n) { set_error("%s: row index %d of column %d outside [0, n)", who, (int)i, j); return OEMGPU_ERR_ARG; }
+            if (k > k0 && i <= rowidx[k - 1]) { set_error("%s: row indices of column %d are not strictly increasing", who, j); return OEMGPU_ERR_ARG; }
+        }
+        if (rowcount) for (int64_t k = k0; k < k1; ++k) (*rowcount)[(size_t)rowidx[k] + 1] += 1;
+    }
+    return maxcol;
+}
+
+// OEM_SPARSE_GRAM=csc|dense forces a route (tests compare them), OEM_SPARSE_TILE_ROWS sets the rows per tile (several on small data)
+SparseRoute sparse_route(int64_t n, int p, int64_t nnz)
+{
+    SparseRoute R;
+    R.csc = csc_moments_fits(p) && (double)nnz <= 0.02 * (double)n * (double)p && n < ((int64_t)1 << 31);
+    if (sw().OEM_SPARSE_GRAM.set) {
+        const char *ev = sw().OEM_SPARSE_GRAM.str;
+        if (!strcmp(ev, "csc") && csc_moments_fits(p)) R.csc = true;
+        if (!strcmp(ev, "dense")) R.csc = false;
+    }
+    int64_t rc = (int64_t)(2147483648.0 / (8.0 * p)) / 64 * 64;
+    if (sw().OEM_SPARSE_TILE_ROWS.set) { const long long t = sw().OEM_SPARSE_TILE_ROWS.num / 64 * 64; if (t >= 64) rc = t; }
+    if (rc < 64) rc = 64;
+    if (rc > n) rc = n;
+    R.rows = rc;
+    R.ld = (rc + 1) / 2 * 2;
+    return R;
+}
+
+int launch_moments_add(hipStream_t s, double *acc, const double *m, size_t len, bool first)
+{
+    hipLaunchKernelGGL(moments_add_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, acc, m, len, first ? 1 : 0);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+int csc_tile_moments(oemgpu_ctx *c, const SparseRoute &R, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *w,
+                     const double *y, int64_t n, int p, int64_t maxcol, double *tile, double *tpart, double *vpart, double *mtile, double *M)
+{
+    hipStream_t s = c->stream;
+    const GramPlan plmax = gram_plan_bound(R.rows, p, c->num_cu);
+    const size_t mlen = (size_t)oemgpu_moments_len(p);
+    for (int64_t r0 = 0; r0 < n; r0 += R.rows) {
+        const int64_t r1 = r0 + R.rows < n ? r0 + R.rows : n, nr = r1 - r0;
+        OEM_HIP(hipMemsetAsync(tile, 0, sizeof(double) * (size_t)R.ld * p, s));
+        if (maxcol > 0) hipLaunchKernelGGL(csc_densify_kernel, dim3((unsigned)((maxcol + 255) / 256), p), dim3(256), 0, s, colptr, rowidx, val, w, r0, r1, R.ld, tile);
+        OEM_HIP(hipGetLastError());
+        const GramPlan pl = gram_plan(nr, p, c->num_cu);
+        if (pl.tpart_doubles > plmax.tpart_doubles || pl.vpart_doubles > plmax.vpart_doubles) { set_error("internal: tile plan larger than its scratch"); return OEMGPU_ERR_INTERNAL; }
+        int rc = shard_moments(c, pl, tile, nr, R.ld, y ? y + r0 : tile, nullptr, tpart, vpart, mtile);   // no y: the tile's first column stands in (its moments go unused)
+        if (!rc) rc = launch_moments_add(s, M, mtile, mlen, r0 == 0);
+        if (rc) return rc;
+    }
     return 0;
 }
 

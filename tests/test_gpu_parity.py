@@ -1263,6 +1263,20 @@ def test_sparse_x_in_several_row_tiles(oa, monkeypatch):
     for k in range(2):
         assert np.abs(one["beta"][k] - many["beta"][k]).max() < 1e-12
         assert np.abs(many["beta"][k] - r["beta"][k]).max() < 1e-9
+    # every entry stored twice as two halves, in random order inside its column: oem() sums them as R's dgCMatrix coercion does (no
+    # two stores to one slot of a tile), and leaves the caller's matrix as it was
+    xc = sp.csc_matrix(x)
+    cols = np.repeat(np.arange(p), np.diff(xc.indptr))
+    order = np.lexsort((rng.permutation(2 * xc.nnz), np.concatenate([cols, cols])))
+    dup = sp.csc_matrix((np.concatenate([xc.data, xc.data])[order] * 0.5, np.concatenate([xc.indices, xc.indices])[order], 2 * xc.indptr),
+                        shape=x.shape)
+    kept = [a.copy() for a in (dup.indptr, dup.indices, dup.data)]
+    summed = dup.copy(); summed.sum_duplicates()
+    twice, once = oa.oem(dup, y, **kw), oa.oem(summed, y, **kw)
+    for key in ("beta", "lambda", "niter", "loss"):
+        assert all(np.array_equal(u, v) for u, v in zip(twice[key], once[key])), key
+    assert twice["d"] == once["d"]
+    assert all(np.array_equal(a, b) for a, b in zip((dup.indptr, dup.indices, dup.data), kept))
 
 
 @pytest.mark.gpu

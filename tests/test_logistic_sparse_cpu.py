@@ -109,8 +109,8 @@ def _opts(penalty=("lasso",), p=5, groups=None, ug=None):
     return api._Args(list(penalty), [], 10, 1e-3, 1.0, 3.0, 0.5, 1e-7, 100, False, False, np.ones(p), g, u, np.zeros(0))
 
 
-def _csc(n=50, p=5, seed=0):
-    x = sp.random(n, p, density=0.3, format="csc", random_state=np.random.default_rng(seed))
+def _csc(n=50, p=5, seed=0, density=0.3):
+    x = sp.random(n, p, density=density, format="csc", random_state=np.random.default_rng(seed))
     return (np.ascontiguousarray(x.indptr, np.int64), np.ascontiguousarray(x.indices, np.int32), np.ascontiguousarray(x.data, np.float64))
 
 
@@ -132,20 +132,41 @@ def test_refusals_before_device_c_entry():
     assert _call(irls_maxit=0) == -1                             # the dense fit's own checks
     assert _call(irls_tol=-1.0) == -1
     assert _call(penalty=("grp.lasso",), groups=[1, 1, 2, 2, 3], ug=[1, 2, 3]) == -1
-    cp, ri, va = _csc()
+
+
+def _call_gaussian(n, p, arrays, intercept):
+    import oem_amd
+    from oem_amd import api
+    a = _opts(p=p)
+    cp, ri, va = arrays
+    y = (np.arange(n) % 2).astype(np.float64)
+    return oem_amd.lib().oemgpu_fit_sparse(n, p, cp.ctypes.data, api._iptr(ri), api._dptr(va), api._dptr(y), 1, intercept, C.byref(a.c),
+                                           *a.outputs(p + 1))
+
+
+# (entry, n, p, intercept): the binomial entry, the Gaussian entry on both of its branches (n > p: the moments; n <= p: the dense copy
+# of the wide engine, served without an intercept)
+@pytest.mark.parametrize("entry,n,p,intercept", [("logistic", 50, 5, 1), ("gaussian", 50, 5, 1), ("gaussian", 50, 5, 0),
+                                                 ("gaussian", 6, 10, 0)])
+def test_csc_arrays_refused_before_device(entry, n, p, intercept):
+    import oem_amd
+    call = (lambda arr: _call(n=n, p=p, arrays=arr, intercept=intercept)) if entry == "logistic" else \
+        (lambda arr: _call_gaussian(n, p, arr, intercept))
+    cp, ri, va = _csc(n, p, density=0.3 if n > p else 0.5)
+    assert np.any(np.diff(cp) >= 2)
     bad = cp.copy(); bad[0] = 1
-    assert _call(arrays=(bad, ri, va)) == -1                     # colptr[0] != 0
+    assert call((bad, ri, va)) == -1                             # colptr[0] != 0
     bad = cp.copy(); bad[2] = bad[3] + 1
-    assert _call(arrays=(bad, ri, va)) == -1                     # colptr decreasing
-    for v in (-1, 50, 2 ** 31 - 1):                              # a row index outside [0, n)
+    assert call((bad, ri, va)) == -1                             # colptr decreasing
+    for v in (-1, n, 2 ** 31 - 1):                               # a row index outside [0, n)
         r2 = ri.copy(); r2[3] = v
-        assert _call(arrays=(cp, r2, va)) == -1
+        assert call((cp, r2, va)) == -1
     c0 = int(np.argmax(np.diff(cp) >= 2))                        # a column with two entries
     r2 = ri.copy(); r2[cp[c0] + 1] = r2[cp[c0]]                  # repeated row
-    assert _call(arrays=(cp, r2, va)) == -1
+    assert call((cp, r2, va)) == -1
+    assert "strictly increasing" in oem_amd.lib().oemgpu_last_error().decode()
     r2 = ri.copy(); r2[cp[c0]], r2[cp[c0] + 1] = r2[cp[c0] + 1], r2[cp[c0]]   # decreasing rows
-    assert _call(arrays=(cp, r2, va)) == -1
-    import oem_amd
+    assert call((cp, r2, va)) == -1
     assert "strictly increasing" in oem_amd.lib().oemgpu_last_error().decode()
 
 
@@ -171,6 +192,20 @@ def test_refusals_through_python():
         oem_amd.oem_fit_logistic_sparse(x, np.arange(60.0) % 3)
     with pytest.raises(NotImplementedError):                     # oem(family = "binomial") is unchanged
         oem_amd.oem(x.toarray(), y, family="binomial")
+
+
+def test_csc_arrays_sums_duplicates_and_leaves_the_input():
+    from oem_amd import api
+    # column 0: rows 3, 1, 3 (a duplicate, out of order); column 1 empty; column 2: rows 2, 0
+    x = sp.csc_matrix((np.array([1.0, 2.0, 4.0, 5.0, 6.0]), np.array([3, 1, 3, 2, 0], np.int32), np.array([0, 3, 3, 5], np.int32)), shape=(4, 3))
+    kept = [a.copy() for a in (x.indptr, x.indices, x.data)]
+    cp, ri, va = api._csc_arrays(x)
+    assert (cp.dtype, ri.dtype, va.dtype) == (np.int64, np.int32, np.float64)
+    assert all(a.flags.c_contiguous for a in (cp, ri, va))
+    assert cp.tolist() == [0, 2, 2, 4] and ri.tolist() == [1, 3, 0, 2] and va.tolist() == [2.0, 5.0, 6.0, 5.0]
+    assert all(np.array_equal(a, b) and a.dtype == b.dtype for a, b in zip((x.indptr, x.indices, x.data), kept))
+    cp2, ri2, va2 = api._csc_arrays(x.tocoo().astype(np.float32))        # any format and dtype: the same arrays
+    assert cp2.tolist() == cp.tolist() and ri2.tolist() == ri.tolist() and va2.tolist() == va.tolist()
 
 
 def test_plan_sweep():
