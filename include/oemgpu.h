@@ -282,6 +282,12 @@ int oemgpu_last_path_engine(oemgpu_ctx *ctx, int32_t *engine, int32_t *persisten
  * workgroups anywhere on the device. */
 int oemgpu_last_placement(oemgpu_ctx *ctx);
 
+/* The most recent penalty x lambda path on this context, if the single-workgroup row-split kernel ran it (p <= 208; 0, 0 otherwise):
+ * how many OEM rounds ran in the short form -- the product over the first ranked columns only, taken while the non-zeros of beta stay
+ * within them (path_small.hip; OEM_NO_ACTIVE_PREFIX=1 never takes it: same bits, 0 short rounds) -- and how many rounds in all.
+ * Of penalty 0 of instance 0 when the call has several penalties or instances.  -1 for a NULL context. */
+int oemgpu_last_path_rounds(oemgpu_ctx *ctx, int64_t *short_rounds, int64_t *rounds);
+
 /* 1 if the most recent oemgpu_solve_moments_dev on this context found the shift predicate above true for its
  * sums_dev (and so read moments_dev as accumulated about c), 0 if not, -1 for a NULL context. */
 int oemgpu_last_shift_in_effect(oemgpu_ctx *ctx);

@@ -243,6 +243,13 @@ def last_path_engine(ctx=None):
     return ENGINES[e.value], f.value
 
 
+def last_path_rounds(ctx=None):
+    """(short_rounds, rounds) of the most recent path on the row-split kernel (include/oemgpu.h: oemgpu_last_path_rounds)."""
+    s, r = C.c_int64(0), C.c_int64(0)
+    L.check(L.lib().oemgpu_last_path_rounds(ctx if ctx is not None else context(), C.byref(s), C.byref(r)))
+    return int(s.value), int(r.value)
+
+
 def last_placement(ctx=None):
     """"none" / "one-xcd" / "refused": whether the cooperating engine of the most recent path launch on this context ran with all
     workgroups of an instance on one XCD (include/oemgpu.h: oemgpu_last_placement)."""

@@ -108,8 +108,9 @@ def audit_round_spills(asm_text, limit=16):
                 kind, count = int(b.group(1)), 0
                 found += 1
             elif "; oem-round-end" in line:
-                if kind is not None and kind < 8 and kind % 2 == 0 and count > limit:      # K_SOFT .. K_OLS, accelerate off
-                    problems.append(f"{name}: {count} scratch instructions in a round of operator kind {kind // 2}")
+                op = kind % 16 if kind is not None else None                               # (16 +: the short round of the same operator)
+                if op is not None and op < 8 and op % 2 == 0 and count > limit:            # K_SOFT .. K_OLS, accelerate off
+                    problems.append(f"{name}: {count} scratch instructions in a {'short' if kind >= 16 else 'full'} round of operator kind {op // 2}")
                 kind = None
             elif kind is not None and "scratch_" in line:
                 count += 1

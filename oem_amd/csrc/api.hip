@@ -829,6 +829,7 @@ int run_paths(oemgpu_ctx *c, Bump &B, const double *xx, const double *xy, const 
     }
     PathArgs a = P.ap;                                   // the scalars are the plan's; the pointers:
     a.d_fixed = launches_only ? ex->d_fixed : 0.0;
+    a.no_active_prefix = sw().OEM_NO_ACTIVE_PREFIX.set ? 1 : 0;
     a.xx = xx; a.xy = xy; a.stats = stats;
     a.penalty = (const int *)(dblob + o_pen);
     a.lambda_user = user ? (const double *)(dblob + o_lam) : nullptr;
@@ -1009,6 +1010,10 @@ int run_paths(oemgpu_ctx *c, Bump &B, const double *xx, const double *xy, const 
         if (hd[6] != 0.0) { set_error("cooperating workgroups lost each other (exchange timeout)"); return OEMGPU_ERR_INTERNAL; }
         c->diag[0] = hd[2]; c->diag[1] = hd[3];
         if (bi == 0) { c->eig_steps = (int)hd[4]; c->eig_capped = hd[5] != 0.0; }
+        if (bi == 0) {                                   // (only the row-split kernel counts its rounds)
+            const bool rows = c->last_engine == OEMGPU_ENGINE_ROWS && path_small_takes_rows(a);
+            c->path_rounds_short = rows ? (int64_t)hd[7] : 0; c->path_rounds = rows ? (int64_t)hd[8] : 0;
+        }
         c->shifted = hs[stats_shift_flag(p)] != 0.0;
         c->shift_advised = hs[stats_shift_flag(p) + 1] != 0.0;
         const double meany = hs[0], scaley = hs[1];
@@ -1860,6 +1865,14 @@ int oemgpu_last_path_engine(oemgpu_ctx *c, int32_t *engine, int32_t *persistent_
 }
 
 int oemgpu_last_placement(oemgpu_ctx *c) { return c ? c->last_placement : -1; }
+
+int oemgpu_last_path_rounds(oemgpu_ctx *c, int64_t *short_rounds, int64_t *rounds)
+{
+    if (!c) return -1;
+    if (short_rounds) *short_rounds = c->path_rounds_short;
+    if (rounds) *rounds = c->path_rounds;
+    return 0;
+}
 
 int oemgpu_last_eigen_info(oemgpu_ctx *c, int32_t *steps, int32_t *capped)
 {

@@ -154,6 +154,7 @@ struct PathArgs {
                              // [4] Lanczos steps taken, [5] 1 if the step cap ended the recurrence (neither stop rule nor breakdown),
                              // [6] exchange poison: cleared by the host before the launch, set to 1 by ANY workgroup whose exchange
                              //     timed out (a slot nobody else writes: the writer's stores cannot cover it up -- ADVICE r2)
+                             // [7], [8] (row-split kernel only) OEM rounds run in the short form / in all, of penalty 0's path
     // workspace for the large-p engine
     double *work;
     // q > 4096 on the launch-per-iteration Gram engine: sympk_doubles(q) doubles for the packed lower triangle of XX and the partial
@@ -182,6 +183,7 @@ struct PathArgs {
     // path_coop.hip, q <= 512: the cooperating workgroups of an instance all on ONE XCD (8 x as many workgroups are launched and only
     // those with blockIdx.x % 8 == (xcd_base + blockIdx.y) % 8 take part; the kernel proves the placement before it relies on it)
     int one_xcd, xcd_base;
+    int no_active_prefix;    // row-split kernel: 1 = never enter the short round (OEM_NO_ACTIVE_PREFIX; the ranked layout stays)
 };
 
 // the read of PathArgs::abort_word (system scope: the word lives in host memory)
@@ -213,7 +215,7 @@ __device__ __forceinline__ PathArgs path_instance(PathArgs A)
     return A;
 }
 
-static const int D_OUT_LEN = 7;
+static const int D_OUT_LEN = 9;
 // Stop rule of every Lanczos recurrence here: the geometric tail implied by two successive moves of the top Ritz value, relative.
 // The reference's own tolerance on this eigenvalue is 1e-10 (Spectra, ref src/oem_dense.h:494-498); the estimate is conservative
 // (config 1: it says 3e-13 where the true error is 1e-14), and the tests hold d to 1e-10 against LAPACK and the CPU restatement.  (1e-11 was tried in round 3: config 1 still takes 40 steps, config 4 still 144, and one xval fit moved: no gain.)

@@ -37,6 +37,7 @@ struct oemgpu_ctx {
     int eig_steps = 0;             // the last eigenvalue step: Lanczos steps taken ...
     int last_engine = 0;           // OEMGPU_ENGINE_* of the most recent penalty x lambda path (oemgpu_last_path_engine)
     int persistent_fallbacks = 0;  // calls of a persistent p >= n engine that timed out (CUs held by somebody else) and were made again with launches
+    int64_t path_rounds_short = 0, path_rounds = 0;   // the last path on the row-split kernel: OEM rounds in the short form / in all (oemgpu_last_path_rounds)
     bool eig_capped = false;       // ... and whether the step cap ended it (oemgpu_last_eigen_info)
     int shifted = 0;               // the last solve read its moments as accumulated about the provisional shift
     int shift_advised = 0;         // the last solve was given moments about 0 whose columns have |mean| >> sd

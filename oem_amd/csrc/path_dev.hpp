@@ -63,6 +63,13 @@ template <int N> __device__ __forceinline__ void dpp_hazard_fence(double (&B)[N]
     else if constexpr (N == 4) asm volatile("s_nop 1" : "+v"(B[0]), "+v"(B[1]), "+v"(B[2]), "+v"(B[3]));
     else { static_assert(N == 8, "extend dpp_hazard_fence"); asm volatile("s_nop 1" : "+v"(B[0]), "+v"(B[1]), "+v"(B[2]), "+v"(B[3]), "+v"(B[4]), "+v"(B[5]), "+v"(B[6]), "+v"(B[7])); }
 }
+// ... the first N registers of B only (the short round of path_small.hip gathers no more)
+template <int N, int M> __device__ __forceinline__ void dpp_hazard_fence_first(double (&B)[M])
+{
+    static_assert(N >= 1 && N <= 2 && N <= M, "extend dpp_hazard_fence_first");
+    if constexpr (N == 1) asm volatile("s_nop 1" : "+v"(B[0]));
+    else asm volatile("s_nop 1" : "+v"(B[0]), "+v"(B[1]));
+}
 // A double kept in the accumulator file: AGPRs a[2 IDX], a[2 IDX + 1], named by inline asm alone (the compiler's own values must fit
 // the architectural VGPRs of such a kernel: oem_amd/build.py audits that it never emits a v_accvgpr of its own there).  `a[%n]`, not
 // `a%n`: the printer writes immediates above 64 in hex, and `a0x41` does not assemble.

@@ -34,6 +34,7 @@ namespace {
 
 // -DOEM_PATH_DIAG: a diagnostic build that splits the round into stamped segments (cycles summed per wave 0).
 // Its fences forbid overlaps the real kernel has: read the SHARES, never the total.
+// Slots 0-4: the five segments of a full OEM round; 18, 20-23: the same five of a short round (tools/path_round_segments.py).
 #ifdef OEM_PATH_DIAG
 __device__ unsigned long long g_diag[24];
 #define OEM_STAMP(slot)                                                                    \
@@ -622,8 +623,9 @@ __global__ __launch_bounds__(NW * 64) void path_small_kernel(PathArgs A_)
 // extra 8-byte read per lane), with no overlap between the two -- the chain is serial.  So the round that wins issues
 // the fewest instructions and moves the fewest words:
 //   * four waves, one per SIMD; wave w owns rows [w RWp, (w+1) RWp), RWp = ceil(p/4) <= 32;
-//   * the 16-lane row group g of every wave multiplies the column slice [g CGp, (g+1) CGp), CGp = ceil(p/4): lane
-//     (g, l) holds a[r][k] = M[row(l, r)][g CGp + k] for its two row slots r = 0, 1 -- 2 CG FMAs, each taking its
+//   * rows and columns are RANKED (path_rows_kernel: by |xy| / pf descending), and the 16-lane row group g of every wave multiplies
+//     the ranked columns 4 k + g, k = 0 .. ceil(p/4) - 1: lane (g, l) holds a[r][k] = M[row(l, r)][4 k + g] for its two row slots
+//     r = 0, 1 -- 2 CG FMAs (2 KS in the short round, while beta's non-zeros stay within the first 4 KS ranked rows), each taking its
 //     beta entry from a neighbour lane (v_fmac_f64_dpp row_newbcast);
 //   * the four slice sums of a row meet WITHOUT LDS, and as a reduce-scatter: one v_permlane16_swap pair + add leaves
 //     slot 0's pair sums in even row groups and slot 1's in odd ones, one v_permlane32_swap pair + add finishes, so
@@ -647,6 +649,12 @@ template <int NW> __device__ __forceinline__ double lanes_sum(double v)
 // butterfly inside the 16-lane row, then one v_permlane16_swap pair joins the two groups.  Every lane gets the total.
 __device__ __forceinline__ double rows_sum(double v)
 {
+    // Invariant: every lane returns the SAME BITS.  The butterfly gives that only if its input is a rounded number: left alone,
+    // the compiler contracts a product in the caller into the first add (lane 0: fma(a0, b0, a1 b1), lane 1: fma(a1, b1, a0 b0)).
+    // The Lanczos recurrence depends on it: a lane applies its alpha to its own row and to its gathered copy of another lane's
+    // row, and a last-bit difference between an entry and its copy grows by alpha / beta (about 14) per step.  So the argument is
+    // pinned to a register first (one v_mul instead of a fused one; the accelerate and loss sums round their products too).
+    asm("" : "+v"(v));
     v += dpp_xchg<0xB1>(v);      // quad_perm [1,0,3,2]
     v += dpp_xchg<0x4E>(v);      // quad_perm [2,3,0,1]
     v += dpp_xchg<0x141>(v);     // row_half_mirror
@@ -669,14 +677,15 @@ __device__ __forceinline__ double rowgroup_reduce_scatter(double p0, double p1)
     auto h2 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
     return __hiloint2double((int)h2[0], (int)l2[0]) + __hiloint2double((int)h2[1], (int)l2[1]);
 }
-template <int CG, int C> struct GroupFma {
+// FMA pairs C .. CE - 1 of the lane's slice (the short round stops at CE = KS and, if it must, resumes there: same order, same bits)
+template <int CG, int C, int CE = CG> struct GroupFma {
     template <int NBC>
     static __device__ __forceinline__ void run(double (&acc)[2][2], const double (&B)[NBC], const double (&a)[2][CG])
     {
-        if constexpr (C < CG) {
+        if constexpr (C < CE) {
             BcFma<(C & 15)>::fmac(acc[0][C & 1], B[C >> 4], a[0][C]);
             BcFma<(C & 15)>::fmac(acc[1][C & 1], B[C >> 4], a[1][C]);
-            GroupFma<CG, C + 1>::run(acc, B, a);
+            GroupFma<CG, C + 1, CE>::run(acc, B, a);
         }
     }
 };
@@ -773,19 +782,38 @@ struct RowsLds {
 // row group's column slice and returns (M vec)[own row].  flag / aux as in gemv_sliced.
 // NORM (Lanczos): aux carries this wave's share of || vec ||^2; the gathered entries are divided by the norm before
 // the product, so the result is M (vec / || vec ||); aux returns the norm and scale its reciprocal.
-template <int NW, int CG, int CGL, bool FLAGS, bool USE_AUX, bool NORM = false>
+//
+// The flag word a wave publishes (FLAGS) is FW_MOVING if one of its rows still moves, plus -- in the short round -- the wave's PREFIX: 1 + the highest
+// ranked row of the wave whose entry is not zero (-0.0 is zero), 0 if there is none.  Rows sit in the lanes in ranked order and
+// row groups 2, 3 replicate 0, 1, so that is one ballot and a scalar find-first-bit.
+// KS > 0 (the short round): the lane multiplies FMA pairs 0 .. KS - 1 only -- ranked columns below 4 KS -- and gathers the
+// registers of B those need.  If a prefix just read is larger, the rest of the product follows in the same round (out of line),
+// in the same order as the full round takes it, and `wide` is set: a product never ignores a non-zero, and a skipped FMA would
+// have added a * 0, so both rounds give the same bits.
+constexpr int FW_MOVING = 1 << 30, FW_PREFIX = FW_MOVING - 1;
+template <int NW, int CG, int CGL, bool FLAGS, bool USE_AUX, bool NORM = false, int KS = 0>
 __device__ __forceinline__ double gemv_rows(const double (&a)[2][CG], const double *aL, double mine, int wslot,
                                             const int (&ecol)[(CG + CGL + 15) / 16],
                                             bool moving, bool &any, double &aux, const RowsLds &S, int w, int lane, int &buf,
-                                            double *scale OEM_DIAG_ARGS)
+                                            double *scale, int rtop, bool &wide OEM_DIAG_ARGS)
 {
     constexpr int NBC = (CG + CGL + 15) / 16, VS = RowsCfg<NW, CG, CGL>::VS;
+    constexpr bool SHORT = KS > 0;
+    constexpr int NBS = SHORT ? (KS + 15) / 16 : NBC;               // registers of B the FMAs in line read
+    static_assert(!SHORT || (FLAGS && !NORM && KS < CG), "the short round belongs to the OEM iteration");
     const int b = __builtin_amdgcn_readfirstlane(buf);              // provably uniform: addresses stay scalar + immediate
-    const int any_mine = FLAGS ? ((__ballot(moving) != 0ull) ? 1 : 0) : 0;
-    OEM_STAMP(0);                       // threshold, stop rule, loop control since the previous round
+    int any_mine = 0;
+    if (FLAGS) {
+        any_mine = (__ballot(moving) != 0ull) ? FW_MOVING : 0;
+        if constexpr (SHORT) {                                      // (only the short round reads prefixes: the full one pays nothing for them)
+            const unsigned long long nz = __ballot(mine != 0.0);    // (both halves alike: lanes 32 .. 63 hold replicas)
+            any_mine += nz ? rtop - (int)__builtin_clzll(nz) : 0;
+        }
+    }
+    OEM_STAMP(SHORT ? 18 : 0);                       // threshold, stop rule, loop control since the previous round
     static_assert(CGL % 2 == 0, "LDS-resident columns are streamed in pairs");
     double tl[2][2];                    // first pair of LDS-resident coefficients [column][row slot]: independent of the
-    if (CGL > 0) {                      // vector, so it is fetched before the barrier and lands in its shadow
+    if (CGL > 0 && !SHORT) {            // vector, so it is fetched before the barrier and lands in its shadow
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -795,16 +823,16 @@ __device__ __forceinline__ double gemv_rows(const double (&a)[2][CG], const doub
     if (FLAGS) S.F[(b * NW + w) * 64 + lane] = any_mine;
     if (USE_AUX) S.XA[(b * NW + w) * 64 + lane] = aux;
     __syncthreads();
-    OEM_STAMP(1);                       // stores + barrier
+    OEM_STAMP(SHORT ? 20 : 1);                       // stores + barrier
     int f = 0;
     if (FLAGS) f = S.F[(b * NW + (lane & (NW - 1))) * 64 + lane];
     double xa = 0.0;
     if (USE_AUX) xa = S.XA[(b * NW + (lane & (NW - 1))) * 64 + lane];
     double B[NBC];
 #pragma unroll
-    for (int j = 0; j < NBC; ++j) B[j] = S.V[b * VS + ecol[j]];
+    for (int j = 0; j < NBS; ++j) B[j] = S.V[b * VS + ecol[j]];
     __builtin_amdgcn_sched_barrier(0);
-    OEM_STAMP(2);                       // reads (the stamp waits for them)
+    OEM_STAMP(SHORT ? 21 : 2);                       // reads (the stamp waits for them)
     if (NORM) {
         double nb, ib;
         sqrt_rsqrt(lanes_sum<NW>(xa), nb, ib);
@@ -813,18 +841,38 @@ __device__ __forceinline__ double gemv_rows(const double (&a)[2][CG], const doub
         aux = nb; *scale = ib;
     }
     double acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+    if constexpr (SHORT) {
+        dpp_hazard_fence_first<NBS>(B);
+        GroupFma<CG, 0, KS>::run(acc, B, a);
+        const bool beyond = __any((f & FW_PREFIX) > 4 * KS);
+        wide = beyond;
+        if (__builtin_expect(beyond, 0)) {                                   // a non-zero beyond the cap: the rest of the product, now
+            if (CGL > 0) {
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) tl[c][r] = aL[(2 * c + r) * NW * 64];
+            }
+#pragma unroll
+            for (int j = NBS; j < NBC; ++j) B[j] = S.V[b * VS + ecol[j]];
+            dpp_hazard_fence(B);
+            GroupFma<CG, KS>::run(acc, B, a);
+            LdsFma<CG, CGL, NW * 64, 0>::run(acc, B, aL, tl);
+        }
+    } else {
     dpp_hazard_fence(B);                                        // VALU write of B -> DPP read: 2 wait states
     GroupFma<CG, 0>::run(acc, B, a);
     LdsFma<CG, CGL, NW * 64, 0>::run(acc, B, aL, tl);
-    OEM_STAMP(3);                       // FMAs issued
+    }
+    OEM_STAMP(SHORT ? 22 : 3);                       // FMAs issued
     const double out = rowgroup_reduce_scatter(acc[0][0] + acc[0][1], acc[1][0] + acc[1][1]);
     if (USE_AUX && !NORM) aux = lanes_sum<NW>(xa);
-    any = FLAGS ? __any(f != 0) : false;
+    any = FLAGS ? __any(f >= FW_MOVING) : false;
     buf = b ^ 1;
 #ifdef OEM_PATH_DIAG
     { unsigned sink; asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(sink) : "v"(__double2loint(out))); diag_acc[11] += sink & 1; }   // results are in before the stamp
 #endif
-    OEM_STAMP(4);                       // chain adds + reduce-scatter
+    OEM_STAMP(SHORT ? 23 : 4);                       // chain adds + reduce-scatter
     return out;
 }
 
@@ -847,14 +895,21 @@ __device__ __forceinline__ void iterate_rows_t(const PathArgs &A, const PenK &K,
                                                const double *aL, double xy, double pf, int wslot,
                                                const int (&ecol)[(CG + CGL + 15) / 16],
                                                double &beta, double &ab, double &ak, int &it, int &conv, const RowsLds &S,
-                                               int w, int lane, int &buf, const RowGrp &G OEM_DIAG_ARGS)
+                                               int w, int lane, int &buf, const RowGrp &G, int rtop, bool &wide,
+                                               int &nshort OEM_DIAG_ARGS)
 {
     const double tp = pf * K.L, tol = A.tol;
     const int maxit = A.maxit;
     constexpr int VS = RowsCfg<NW, CG, CGL>::VS;
+    // the short round's FMA pairs per lane (0: this form has none): the group operators keep the full round, and a slice of eight
+    // columns is short already
+    constexpr int KS = (KIND != K_GRP && CG > 8) ? 8 : 0;
+    bool left = false;                  // the short round met a non-zero beyond its cap
     OEM_STAMP(8);                       // per-lambda work since the last round
-    auto round = [&]() -> bool {
-        asm volatile("; oem-round-begin %0" ::"n"(KIND * 2 + (ACC ? 1 : 0)));      // markers for oem_amd/build.py: audit_round_spills
+    auto round = [&](auto KS_) -> bool {
+        constexpr int KSR = decltype(KS_)::value;
+        // markers for oem_amd/build.py: audit_round_spills, audit_dpp_hazards (16 +: the short round)
+        asm volatile("; oem-round-begin %0" ::"n"(KIND * 2 + (ACC ? 1 : 0) + (KSR > 0 ? 16 : 0)));
         const double bold = beta;
         if constexpr (KIND == K_GRP) {
             // Group operators (ref src/oem_dense.h:193-315).  A group's members are rows of other lanes and waves, so u crosses
@@ -909,17 +964,37 @@ __device__ __forceinline__ void iterate_rows_t(const PathArgs &A, const PenK &K,
         const bool cn = cu > 1e-13, qn = q > 1e-13;
         const bool moving = (cn != qn) || (cn && qn && fabs(beta - bold) > tol * q);
         bool any;
-        ab = gemv_rows<NW, CG, CGL, true, ACC>(a, aL, beta, wslot, ecol, moving, any, aux, S, w, lane, buf, nullptr OEM_DIAG_PASS);
+        ab = gemv_rows<NW, CG, CGL, true, ACC, false, KSR>(a, aL, beta, wslot, ecol, moving, any, aux, S, w, lane, buf, nullptr, rtop, left OEM_DIAG_PASS);
         if (ACC && aux > 0.0) ak = 1.0;
         conv = !any;
         asm volatile("; oem-round-end");
-        return conv || it >= maxit;
+        if constexpr (KSR > 0) return conv || it >= maxit || left;
+        else return conv || it >= maxit;
     };
     // two rounds per trip: a taken branch (fetch redirect) costs ~80 cycles on this chain, a fall-through one nothing
-    for (;;) {
-        if (round()) break;
-        if (round()) break;
+    bool done = false;
+    if constexpr (KS > 0) {
+        // The short rounds, while the vector's non-zeros stay within the first 4 KS ranked rows.  The round that finds one beyond them
+        // has completed its product itself; the lambda goes on in the full loop.
+        if (!wide) {
+            for (;;) {
+                if (round(std::integral_constant<int, KS>{})) break;
+                if (round(std::integral_constant<int, KS>{})) break;
+            }
+            nshort += it - (left ? 1 : 0);
+            done = conv || it >= maxit;
+        }
     }
+    if (!done) {
+        for (;;) {
+            if (round(std::integral_constant<int, 0>{})) break;
+            if (round(std::integral_constant<int, 0>{})) break;
+        }
+    }
+    // The next lambda starts from this vector: short while no short round has met a non-zero beyond the cap.  Once the path has
+    // left for the full loop it stays there (the full round publishes no prefixes: it is the round of a dense problem, which pays
+    // nothing for this; on a lasso path the support seldom shrinks back under the cap).
+    if constexpr (KS > 0) wide = wide || left;
 }
 template <int NW, int CG, int CGL>
 __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
@@ -936,28 +1011,57 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
     S.F = reinterpret_cast<int *>(lds + C::OFF_F);
     double *Tal = lds + C::OFF_T, *Tbe = Tal + C::ML, *LAM = lds + C::OFF_L;
 
-    const int RWp = (p + NW - 1) / NW, CGp = (p + 3) / 4;           // rows per wave, columns per row group
+    // ---- the ranked layout.  Rows and columns are taken in the order of |xy| / pf descending (an unpenalised variable first: it is
+    // never zero; ties by index): on a sparse path the non-zeros of beta then sit in the FIRST ranked rows, and a round whose vector
+    // has none beyond ranked row 4 KS multiplies KS column pairs per lane instead of CG (gemv_rows, iterate_rows_t).  Any
+    // permutation gives a correct kernel; the key only decides how often the short round applies.  Keys compare as bit patterns
+    // (of a non-negative double: the same order), so NaN or inf inputs still give a permutation.  ORIG[r] = the variable at ranked
+    // position r, RNK its inverse; both live in the Sturm scratch, which nothing else uses before the first Ritz look.
+    unsigned long long *KEY = reinterpret_cast<unsigned long long *>(lds + C::OFF_S);
+    int *ORIG = reinterpret_cast<int *>(lds + C::OFF_S + C::ML), *RNK = ORIG + C::ML;
+    static_assert(NW * 64 >= C::ML && 2 * C::ML <= C::OFF_TH - C::OFF_S, "one variable per thread; ML keys and 2 ML ints fit the Sturm scratch");
+    if (tid < p) {
+        const double f = A.pf[tid];
+        KEY[tid] = (f == 0.0) ? ~0ull : (unsigned long long)__double_as_longlong(fabs(A.xy[tid] / f));
+    }
+    __syncthreads();
+    if (tid < p) {
+        const unsigned long long kt = KEY[tid];
+        int before = 0;
+#pragma unroll 8
+        for (int i = 0; i < p; ++i) {
+            const unsigned long long ki = KEY[i];
+            before += (ki > kt || (ki == kt && i < tid)) ? 1 : 0;
+        }
+        ORIG[before] = tid; RNK[tid] = before;
+    }
+    __syncthreads();
+    const int RWp = (p + NW - 1) / NW;                               // rows per wave
     // this lane's row after the reduce-scatter: slot g & 1 of the wave's rows; groups 2, 3 replicate groups 0, 1
     const int rloc = 16 * (g & 1) + l16;
     const bool rowok = rloc < RWp && w * RWp + rloc < p;
-    const int row = rowok ? w * RWp + rloc : 0;
+    const int row = rowok ? w * RWp + rloc : 0;                      // ranked position: the slot in the exchanged vector ...
+    const int orow = rowok ? ORIG[row] : 0;                          // ... and the variable it holds
+    const int rtop = w * RWp + 32;                                   // (gemv_rows: this wave's prefix is rtop - leading zeros of its ballot)
     const bool owner = rowok && g < 2;
     const int wslot = owner ? row : 32 * NW + lane;                 // replicas and padding lanes store a word of their own
+    // column slice of row group g: ranked columns 4 k + g, so FMA pair k of every row group belongs to ranked columns 4 k .. 4 k + 3
     int ecol[NBC];
 #pragma unroll
     for (int j = 0; j < NBC; ++j) {
-        const int loc = 16 * j + l16, col = g * CGp + loc;
-        ecol[j] = (loc < CGp && col < p) ? col : 32 * NW + lane;    // own dummy word: finite, meets zero columns only
+        const int col = 4 * (16 * j + l16) + g;
+        ecol[j] = col < p ? col : 32 * NW + lane;                    // own dummy word: finite, meets zero columns only
     }
     double a[2][CG];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int lr = 16 * r + l16, grow = w * RWp + lr;
         const bool rok = lr < RWp && grow < p;
+        const int og = rok ? ORIG[grow] : 0;
 #pragma unroll
         for (int k = 0; k < CG; ++k) {
-            const int col = g * CGp + k;
-            a[r][k] = (rok && k < CGp && col < p) ? A.xx[(size_t)col * p + grow] : 0.0;
+            const int col = 4 * k + g;
+            a[r][k] = (rok && col < p) ? A.xx[(size_t)ORIG[col < p ? col : 0] * p + og] : 0.0;
         }
     }
     double *aL = lds + C::OFF_A + tid;                               // [k][r] at (2 k + r) * NW * 64: conflict-free, lane-private
@@ -965,25 +1069,30 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
     for (int r = 0; r < 2; ++r) {
         const int lr = 16 * r + l16, grow = w * RWp + lr;
         const bool rok = lr < RWp && grow < p;
+        const int og = rok ? ORIG[grow] : 0;
 #pragma unroll
         for (int k = 0; k < CGL; ++k) {
-            const int col = g * CGp + CG + k;
-            aL[(2 * k + r) * NW * 64] = (rok && CG + k < CGp && col < p) ? A.xx[(size_t)col * p + grow] : 0.0;
+            const int col = 4 * (CG + k) + g;
+            aL[(2 * k + r) * NW * 64] = (rok && col < p) ? A.xx[(size_t)ORIG[col < p ? col : 0] * p + og] : 0.0;
         }
     }
-    const double xy = rowok ? A.xy[row] : 0.0, pf = rowok ? A.pf[row] : 0.0;
-    const double sinv = (rowok && A.sinv) ? A.sinv[row] : 1.0;
+    const double xy = rowok ? A.xy[orow] : 0.0, pf = rowok ? A.pf[orow] : 0.0;
+    const double sinv = (rowok && A.sinv) ? A.sinv[orow] : 1.0;
     // dummy words must hold finite numbers before anyone reads them
     for (int k = tid; k < 2 * C::VS; k += NW * 64) S.V[k] = 0.0;
     __syncthreads();
     int buf = 0, par = 0;
-    bool any_unused;
+    bool any_unused, wide_unused = false;
     double aux_unused = 0.0;
+    int nshort = 0, nrounds = 0;                                     // OEM rounds in the short form / in all, of penalty 0
     OEM_DIAG_DECL
     if (A.ngroups > 0) {                                             // group member lists into LDS (group operators only)
         int *gx = reinterpret_cast<int *>(lds + C::OFF_GX);
         const int nm = A.gstart[A.ngroups];
-        for (int m = tid; m < nm && m < 32 * NW + 8; m += NW * 64) gx[m] = A.gidx[m];
+        for (int m = tid; m < nm && m < 32 * NW + 8; m += NW * 64) {   // (as slots of the exchanged vector: ranked positions)
+            const int v = A.gidx[m];
+            gx[m] = (v >= 0 && v < p) ? RNK[v] : C::VS - 1;
+        }
         __syncthreads();
     }
 
@@ -1014,7 +1123,7 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
     bool have_theta = false;
     auto colmask = [&](int j) { return ecol[j] < 32 * NW ? 1.0 : 0.0; };   // dummy words carry replicas' values: not part of the vector
     {
-        const unsigned h = (unsigned)row * 2654435761u + 12345u;     // deterministic non-structured start
+        const unsigned h = (unsigned)orow * 2654435761u + 12345u;    // deterministic non-structured start (of the variable, not of its rank)
         const double st = rowok ? ((double)(h >> 8) * (1.0 / 16777216.0) - 0.5) : 0.0;
         const int b = __builtin_amdgcn_readfirstlane(buf);
         S.V[b * C::VS + wslot] = st;
@@ -1088,13 +1197,13 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
         const bool rok = lr < RWp && grow < p;
 #pragma unroll
         for (int k = 0; k < CG; ++k) {
-            const int col = g * CGp + k;
-            a[r][k] = ((rok && k < CGp && col == grow) ? d : 0.0) - a[r][k];
+            const int col = 4 * k + g;
+            a[r][k] = ((rok && col == grow) ? d : 0.0) - a[r][k];
         }
 #pragma unroll
         for (int k = 0; k < CGL; ++k) {
-            const int col = g * CGp + CG + k;
-            aL[(2 * k + r) * NW * 64] = ((rok && CG + k < CGp && col == grow) ? d : 0.0) - aL[(2 * k + r) * NW * 64];
+            const int col = 4 * (CG + k) + g;
+            aL[(2 * k + r) * NW * 64] = ((rok && col == grow) ? d : 0.0) - aL[(2 * k + r) * NW * 64];
         }
     }
 
@@ -1104,8 +1213,8 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
     double lmax;
     {
         // max |xy| over all rows: wave maxima through per-lane words, then a max over the four words
-        const double xl = (A.lmax_xy && rowok) ? A.lmax_xy[row] : xy;
-        const double wm = wave_max(row >= A.lmax_from ? fabs(xl) : 0.0);      // padding lanes: xy = 0
+        const double xl = (A.lmax_xy && rowok) ? A.lmax_xy[orow] : xy;
+        const double wm = wave_max(orow >= A.lmax_from ? fabs(xl) : 0.0);     // padding lanes: xy = 0
         S.XN[(par * NW + w) * 64 + lane] = wm;
         __syncthreads();
         const double x = S.XN[(par * NW + (lane & (NW - 1))) * 64 + lane];
@@ -1129,6 +1238,8 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
         const int nlam = (pen == OEMGPU_OLS) ? 1 : nl;
         const bool isnet = pen_is_net(pen);
         double beta = 0.0, ab = 0.0, ak = 1.0;                       // cold start: A 0 = 0
+        bool wide = A.no_active_prefix != 0;                         // the zero vector fits every prefix
+        int pshort = 0, prounds = 0;
         // this lane's group, looked up here and not in the kernel's prologue: the eight-wave forms have no registers to keep it
         // alive through the loops of the element-wise operators
         RowGrp G;
@@ -1139,7 +1250,7 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
         if constexpr (KIND == K_GRP) {
             if (A.ngroups > 0) {
                 if (rowok) {
-                    G.gi = A.gid[row];
+                    G.gi = A.gid[orow];
                     if (G.gi >= 0) {
                         G.start = A.gstart[G.gi]; G.cnt = A.gstart[G.gi + 1] - G.start;
                         G.gz = A.gzero[G.gi] != 0; G.gw = A.gw[G.gi];
@@ -1182,7 +1293,7 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
             double lam_next = LAM[0];
             // output cursors: one pointer bump per lambda instead of a 64-bit multiply-add per store (lanes that own nothing
             // keep aiming at their sink word: stride 0)
-            double *bptr = owner ? &A.beta[((size_t)pp * nl + base) * p + row] : sinkd;
+            double *bptr = owner ? &A.beta[((size_t)pp * nl + base) * p + orow] : sinkd;     // beta at its ORIGINAL index
             const size_t bstride = owner ? (size_t)p : 0;
             int *nptr = t0 ? &A.niter[(size_t)pp * nl + base] : sinki;
             const size_t nstride = t0 ? 1 : 0;
@@ -1192,7 +1303,8 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
                 const PenK K = pen_from_linear(PL, il, d, A.gamma);
                 if (__builtin_expect(ridge, 0)) c = uniform_thr(thr_consts<KIND>(K, d));
                 int it = 0, conv = 0;
-                iterate_rows_t<NW, CG, CGL, KIND, ACC>(A, K, c, a, aL, xy, pf, wslot, ecol, beta, ab, ak, it, conv, S, w, lane, buf, G OEM_DIAG_PASS);
+                iterate_rows_t<NW, CG, CGL, KIND, ACC>(A, K, c, a, aL, xy, pf, wslot, ecol, beta, ab, ak, it, conv, S, w, lane, buf, G, rtop, wide, pshort OEM_DIAG_PASS);
+                prounds += it;
                 // (the loss is taken in the coordinates of the iteration, before any in-place rescale)
                 if (__builtin_expect(A.compute_loss != 0, 0)) {
                     // sum (Y - X beta)^2 through the Gram identity (ref src/oem_dense.h:759-770):
@@ -1205,10 +1317,11 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
                 *bptr = beta; bptr += bstride;
                 *nptr = conv ? it : A.maxit + 1; nptr += nstride;         // ref src/oem_base.h:94-109
                 if (__builtin_expect(A.sinv != nullptr, 0))
-                    ab = gemv_rows<NW, CG, CGL, false, false>(a, aL, beta, wslot, ecol, false, any_unused, aux_unused, S, w, lane, buf, nullptr OEM_DIAG_PASS);
+                    ab = gemv_rows<NW, CG, CGL, false, false>(a, aL, beta, wslot, ecol, false, any_unused, aux_unused, S, w, lane, buf, nullptr, rtop, wide_unused OEM_DIAG_PASS);
             }
             __syncthreads();                                             // LAM is rewritten by the next chunk
         }
+        if (pp == 0) { nshort = pshort; nrounds = prounds; }
     };
     for (int pp = A.pen_lo; pp < A.pen_hi; ++pp) {
         const int pen = A.penalty[pp];
@@ -1238,6 +1351,8 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
     if (tid == 0) {
         A.d_out[2] = (double)(__builtin_amdgcn_s_memtime() - t_cyc0);
         A.d_out[3] = (double)(__builtin_amdgcn_s_memrealtime() - t_rt0);
+        // (the penalties of a call share d_out: the first one's rounds are reported, by the workgroup that ran it)
+        if (A.pen_lo == 0) { A.d_out[7] = (double)nshort; A.d_out[8] = (double)nrounds; }
     }
     if (A.stats_out) for (int k = tid; k < A.stats_n; k += NW * 64) A.stats_out[k] = A.stats[k];      // results in host memory: stats beside them
 }

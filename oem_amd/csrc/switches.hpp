@@ -17,7 +17,7 @@ namespace oemgpu {
 #define OEM_SWITCH_TABLE(X)                                                                                                          \
     /* engine selection: Gram form */                                                                                                \
     X(OEM_NO_COOP) X(OEM_NO_SYMCOOP) X(OEM_NO_ROWCOOP) X(OEM_NO_FUSED) X(OEM_NO_SYM) \
-    X(OEM_SYMCOOP_NO_GENERAL) X(OEM_NO_ZERO_COPY)          \
+    X(OEM_SYMCOOP_NO_GENERAL) X(OEM_NO_ZERO_COPY) X(OEM_NO_ACTIVE_PREFIX) \
     /* engine selection: p >= n */                                                                                                   \
     X(OEM_WIDE) X(OEM_NO_WIDE) X(OEM_NO_WCOOP) X(OEM_WRES) X(OEM_NO_WRES) X(OEM_WSTREAM) X(OEM_NO_WSTREAM)        \
     X(OEM_WIDE_NO_GROUP_FUSED) X(OEM_WCOOP_ONE_SET) X(OEM_WCOOP_NO_GENERAL) X(OEM_WCOOP_NO_ALIGN) X(OEM_NO_PENALTY_SPLIT) \
