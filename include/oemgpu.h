@@ -372,6 +372,28 @@ int oemgpu_fit_logistic_dense(const double *x, int64_t n, int32_t p, const doubl
 int oemgpu_fit_logistic_dense_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
                                   int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol,
                                   const oemgpu_opts *opts, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+/* cv.oem's fold fit on the resident x: the fit of oemgpu_fit_logistic_dense_dev on the rows with foldid_dev[row] != leave_out, i.e. what
+ * `.Call("oem_fit_logistic_dense", ...)` computes on x[keep, ], y[keep] -- X and y are neither gathered nor copied, the passes over the
+ * rows leave the fold's rows out, and the number of kept rows stands where n enters the arithmetic (the column scales' n - 1, the / n
+ * of XX, XY and the gradient; the W floor tests the IRLS index among the kept rows).  foldid_dev: n int32 on the device, values
+ * 1 .. nfolds.  leave_out = 0 leaves nothing out and returns the bits of oemgpu_fit_logistic_dense_dev.  After leave_out the
+ * arguments and outputs are those of oemgpu_fit_logistic_dense_dev.  Checked before any device is looked for: OEMGPU_ERR_ARG for a
+ * NULL foldid_dev, nfolds < 3 and leave_out outside [0, nfolds], then the checks of oemgpu_fit_logistic_dense.  From the device:
+ * OEMGPU_ERR_ARG for a fold id outside [1, nfolds], OEMGPU_ERR_UNSUPPORTED for p + intercept >= the kept rows. */
+int oemgpu_fit_logistic_dense_fold_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                                       const int32_t *foldid_dev, int32_t nfolds, int32_t leave_out, int32_t standardize, int32_t intercept,
+                                       int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *opts,
+                                       double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+/* cv.oemfit_binomial's error terms on the resident x (logistic_cv.hip; ref R/cv_oem.R:315-327).  coef (host): nfolds x ncol x (p + 1),
+ * for fold f (1-based f - 1) and column c the intercept and the p coefficients that score the rows of fold f.  Every row with
+ * foldid 1 .. nfolds is scored with the columns of its own fold: prob = 1 / (1 + exp(-(beta_0 + x . beta))), y2 = (y == y_hi), and
+ * the terms deviance -2 [y2 log pm + (1 - y2) log(1 - pm)] with pm = prob clamped to [1e-5, 1 - 1e-5], class (y2 ? prob <= 0.5 :
+ * prob > 0.5), mse 2 (y2 - prob)^2 and mae 2 |y2 - prob|.  sums (host): nfolds x ncol x 8 = [sum, sum of squares] of deviance, class,
+ * mse, mae over the fold's rows; counts (host): the fold sizes; predmat_dev (device, n x ncol column-major, or NULL): prob.  Sums are
+ * taken in a fixed order: two calls give the same bits.  OEMGPU_ERR_UNSUPPORTED for p > 8191 (the fit's own limit). */
+int oemgpu_logistic_cv_score_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev, double y_hi,
+                                 const int32_t *foldid_dev, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts,
+                                 double *predmat_dev);
 /* Host-only plan of the binomial fit (pure arithmetic, runs without a GPU): out[0] rows per chunk of the row pass, out[1] chunks
  * (chunk c = rows [c out[0], min(n, (c + 1) out[0]))), out[2] rows per Z block of the moment pass, out[3] Z blocks, out[4] 1 if the
  * inner solve is one persistent workgroup (q <= 1024) and 0 for launch per iteration, out[5] 1 if the row pass stages its sub-blocks

@@ -376,12 +376,15 @@ class OemFitBinomial(OemFit):
 
 def oem_fit_logistic_dense(x, y, penalty=None, weights=(), lambda_=(), nlambda=100, lambda_min_ratio=None, alpha=1.0, gamma=3.0, tau=0.5,
                            groups=(), penalty_factor=None, group_weights=None, standardize=True, intercept=True, maxit=500, tol=1e-7,
-                           irls_maxit=100, irls_tol=1e-3, compute_loss=False, hessian_type="upper.bound", varnames=None, interrupt=None):
+                           irls_maxit=100, irls_tol=1e-3, compute_loss=False, hessian_type="upper.bound", varnames=None, interrupt=None,
+                           _fold=None):
     """The dense binomial fit (ref src/oem_logistic_dense.cpp:30-313, src/oem_logistic_dense.h:397-1094) with oem()'s checks for
     family = "binomial" (R/oem.R:162-507): y takes at most two values (passed on as they are: the reference fits the raw 0/1 vector),
     groups gain the intercept's group 0 in front (R/oem.R:296-338).  x: numpy (host entry) or a torch tensor on a GPU (_dev entry).
     hessian_type: "upper.bound" (X'WX, d and A from the first IRLS step of a penalty only) or "full" (every step).  `oem(family=
-    "binomial")` still raises NotImplementedError; this is the entry below it, as oem_fit_dense_weighted is for weights."""
+    "binomial")` still raises NotImplementedError; this is the entry below it, as oem_fit_dense_weighted is for weights.
+    _fold (cv_oem's fold fits; x on a GPU): (foldid as an int32 device tensor, nfolds, leave_out, y as a float64 device tensor) -- the
+    fit on the rows with foldid != leave_out of the resident x (oemgpu_fit_logistic_dense_fold_dev), which reports their number as nobs."""
     L.sync_switches()
     penalty = _match_penalty(penalty)
     if hessian_type not in ("upper.bound", "full"):
@@ -417,14 +420,23 @@ def oem_fit_logistic_dense(x, y, penalty=None, weights=(), lambda_=(), nlambda=1
     if _is_torch_cuda(x):
         import torch
         xp, n_, p_, ld, keep = _device_matrix(x)
-        yd = torch.as_tensor(yh, device=x.device)
+        yd = torch.as_tensor(yh, device=x.device) if _fold is None else _fold[3]
         ctx = context(x.device.index)
         torch.cuda.current_stream(x.device).synchronize()
-        L.check(lib.oemgpu_fit_logistic_dense_dev(ctx, xp, n, ld, p, yd.data_ptr(), int(bool(standardize)), int(bool(intercept)), hf,
-                                                  int(irls_maxit), float(irls_tol), C.byref(a.c), *a.outputs(p + 1)))
+        if _fold is None:
+            L.check(lib.oemgpu_fit_logistic_dense_dev(ctx, xp, n, ld, p, yd.data_ptr(), int(bool(standardize)), int(bool(intercept)), hf,
+                                                      int(irls_maxit), float(irls_tol), C.byref(a.c), *a.outputs(p + 1)))
+        else:
+            fd, nfolds, leave_out = _fold[:3]
+            L.check(lib.oemgpu_fit_logistic_dense_fold_dev(ctx, xp, n, ld, p, yd.data_ptr(), fd.data_ptr(), int(nfolds), int(leave_out),
+                                                           int(bool(standardize)), int(bool(intercept)), hf, int(irls_maxit), float(irls_tol),
+                                                           C.byref(a.c), *a.outputs(p + 1)))
+            n = int(n - (fd == int(leave_out)).sum().item())
         del keep
     else:
         xh = np.asfortranarray(x, dtype=np.float64)
+        if _fold is not None:
+            raise ValueError("a fold fit needs x on a GPU")
         L.check(lib.oemgpu_fit_logistic_dense(_dptr(xh), n, p, _dptr(yh), int(bool(standardize)), int(bool(intercept)), hf,
                                               int(irls_maxit), float(irls_tol), C.byref(a.c), *a.outputs(p + 1)))
     res = OemFitBinomial(_decorate(a, penalty, varnames, True, n, p, family="binomial"))
@@ -721,15 +733,183 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
 
 
 # ------------------------------------------------------------------------------------------ cv.oem()
+def logistic_cv_score(x, y, foldid, nfolds, coef, y_hi=None, predmat=False):
+    """oemgpu_logistic_cv_score_dev: the error terms of cv.oemfit_binomial (R/cv_oem.R:315-327) over the held-out rows of a resident x.
+    x: a column-major float64 matrix on a GPU; y (float64) and foldid (int32, 1 .. nfolds): device tensors; coef: nfolds x ncol x
+    (p + 1) on the host, the columns that score the rows of each fold.  Returns (sums: nfolds x ncol x 8 = [sum, sum of squares] of
+    deviance, class, mse, mae; counts: the fold sizes; predmat: n x ncol on the host, or None)."""
+    import torch
+    xp, n, p, ld, keepalive = _device_matrix(x)
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    if coef.ndim != 3 or coef.shape[0] != int(nfolds) or coef.shape[2] != p + 1:
+        raise ValueError("coef must be nfolds x ncol x (p + 1)")
+    ncol = coef.shape[1]
+    sums = np.zeros((int(nfolds), ncol, 8))
+    counts = np.zeros(int(nfolds), dtype=np.int64)
+    pm = torch.full((ncol, n), float("nan"), dtype=torch.float64, device=x.device) if predmat else None
+    if y_hi is None:
+        y_hi = float(y.max().item())
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_logistic_cv_score_dev(context(x.device.index), xp, n, ld, p, y.data_ptr(), float(y_hi), foldid.data_ptr(), int(nfolds),
+                                                 _dptr(coef), ncol, _dptr(sums), counts.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 None if pm is None else pm.data_ptr()))
+    del keepalive
+    return sums, counts, None if pm is None else pm.t().cpu().numpy()
+
+
+def _auc_rows(y2, prob):
+    """auc.mat with unit weights (R/utils.R:90-125): the rows in the order of prob -- ties in row order, where the reference draws runif
+    (any order is one of its draws) -- and, over the rows with y2 = 1, the rows with y2 = 0 in front of each."""
+    ys = y2[np.argsort(prob, kind="stable")]
+    n1 = float(ys.sum())
+    n0 = float(len(ys)) - n1
+    u = float(np.sum(np.cumsum(1.0 - ys)[ys == 1]))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return float(np.exp(np.log(u) - np.log(n1) - np.log(n0)))
+
+
+_BINOMIAL_NAMES = {"mse": "Mean-Squared Error", "mae": "Mean Absolute Error", "deviance": "Binomial Deviance", "auc": "AUC",
+                   "class": "Misclassification Error"}
+
+
+def _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, foldid, grouped, keep, rng, kw):
+    """cv.oem() for family = "binomial": R/cv_oem.R:56-221 with cv.oemfit_binomial (:224-346).  x is on the device once; the full fit,
+    the K fold fits (masked row passes over that x, one fold after another) and the scoring all read it there."""
+    for drop in ("accelerate", "ncores"):            # oem() arguments the binomial fit has no use for (no Nesterov step, no OpenMP)
+        kw.pop(drop, None)
+    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("x must have at least two columns")
+    n, p = x.shape
+    if len(weights) > 0:                                               # R/oem.R:244
+        raise L.OemgpuError(-4, "weights not implemented yet.")
+    yh = np.asarray(y.cpu() if _is_torch_cuda(y) else y, dtype=np.float64).reshape(-1)
+    if yh.shape[0] != n:
+        raise ValueError("x and y lengths do not match")
+    if len(np.unique(yh)) > 2:                                         # R/oem.R:250-252
+        raise ValueError("y must be a binary outcome")
+    import torch
+    if _is_torch_cuda(x):
+        xd = x if x.dtype == torch.float64 else x.to(torch.float64)
+        if not (xd.stride(0) == 1 and xd.stride(1) >= n):
+            xd = xd.t().contiguous().t()                               # column-major, once
+    else:
+        xd = torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float64).T), device="cuda").t()     # the one upload
+    yd = torch.as_tensor(yh, device=xd.device)
+    lam_arg = () if lambda_ is None else lambda_
+    fit0 = oem_fit_logistic_dense(xd, yh, penalty=penalty, lambda_=lam_arg, **kw)
+    nmodels = len(penalty)
+    nz = [np.array([0 if v is None else len(v) for v in predict(fit0, type="nonzero", which_model=m)]) for m in range(nmodels)]
+    if foldid is None:
+        g = np.random.default_rng() if rng is None else rng
+        foldid = g.permutation(np.resize(np.arange(1, int(nfolds) + 1), n))
+    else:
+        foldid = np.asarray(foldid).ravel()
+        nfolds = int(foldid.max())
+    if nfolds < 3:
+        raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
+    if len(foldid) != n:
+        raise ValueError("x and y lengths do not match")
+    fd = torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=xd.device)
+    outlist = [oem_fit_logistic_dense(xd, yh, penalty=penalty, lambda_=lam_arg, _fold=(fd, nfolds, i, yd), **kw) for i in range(1, nfolds + 1)]
+    # cv.oemfit_binomial
+    if type_measure == "default":
+        type_measure = "deviance"
+    if n / nfolds < 10 and type_measure == "auc":
+        warnings.warn("Too few (< 10) observations per fold for type.measure='auc' in cv.lognet; changed to type.measure='deviance'. "
+                      "Alternatively, use smaller value for nfolds")
+        type_measure = "deviance"
+    if n / nfolds < 3 and grouped:
+        warnings.warn("Option grouped=FALSE enforced in cv.glmnet, since < 3 observations per fold")
+        grouped = False
+    lam = [np.asarray(l, dtype=np.float64) for l in fit0["lambda"]]
+    nl = len(lam[0])
+    which_lam = [lam[m] >= max(np.min(o["lambda"][m]) for o in outlist) for m in range(nmodels)]     # no extrapolation to smaller lambdas
+    y_hi = float(yh.max())                                            # the second level of as.factor(y)
+    y2 = (yh == y_hi).astype(np.float64)
+    term = {"deviance": 0, "class": 2, "mse": 4, "mae": 6}.get(type_measure)
+    want_pred = bool(keep) or type_measure == "auc"
+    predlist, cvraw, w = [], [], []
+    good = np.zeros((nfolds, nl))
+    nlami = 0
+    for m in range(nmodels):
+        nlami = int(which_lam[m].sum())
+        s = lam[m][which_lam[m]]
+        coef = np.empty((nfolds, nlami, p + 1))
+        for i, o in enumerate(outlist):                                # predict.oem's interpolation (R/methods.R:48-109), coefficients only
+            left, right, frac = _lambda_interp(np.asarray(o["lambda"][m], dtype=np.float64), s)
+            b = np.asarray(o["beta"][m])
+            coef[i] = (b[:, left] * frac + b[:, right] * (1 - frac)).T
+        sums, counts, pm = logistic_cv_score(xd, yd, fd, nfolds, coef, y_hi=y_hi, predmat=want_pred)
+        if want_pred:
+            full = np.full((n, nl), np.nan)
+            full[:, :nlami] = pm
+            predlist.append(full)
+        wisum = counts.astype(np.float64)
+        if type_measure == "auc":                                      # per fold and column, on the host (R/cv_oem.R:288-307)
+            raw = np.full((nfolds, nl), np.nan)
+            for i in range(nfolds):
+                rows = foldid == i + 1
+                for j in range(nlami):
+                    raw[i, j] = _auc_rows(y2[rows], pm[rows, j])
+            cvraw.append(raw); w.append(wisum)
+        elif grouped:                                                  # cvcompute (R/utils.R:128-144): fold means, weighted by fold size
+            raw = np.full((nfolds, nl), np.nan)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                raw[:, :nlami] = sums[:, :, term] / wisum[:, None]
+            cvraw.append(raw); w.append(wisum)
+        else:
+            cvraw.append((sums[:, :, term].sum(axis=0), sums[:, :, term + 1].sum(axis=0), nlami))
+    good[:, :nlami] = 1                                               # nlams[i] = nlami of the LAST model (R/cv_oem.R:286), for every fold
+    cvm, cvsd = [], []
+    for m in range(nmodels):
+        if type_measure == "auc" or grouped:
+            Nm = good.sum(axis=0)
+            ok = ~np.isnan(cvraw[m])
+            wsum = (ok * w[m][:, None]).sum(axis=0)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                cm = np.where(ok, cvraw[m] * w[m][:, None], 0.0).sum(axis=0) / wsum
+                cs = np.sqrt(np.where(ok, (cvraw[m] - cm) ** 2 * w[m][:, None], 0.0).sum(axis=0) / wsum / (Nm - 1))
+        else:                                                          # rows as they are: mean and mean squared deviation from the sums
+            s1, s2, k = cvraw[m]
+            cm, cs = np.full(nl, np.nan), np.full(nl, np.nan)
+            cm[:k] = s1 / n
+            with np.errstate(invalid="ignore", divide="ignore"):
+                cs[:k] = np.sqrt(np.maximum((s2 - 2.0 * cm[:k] * s1 + n * cm[:k] ** 2) / n, 0.0) / (n - 1))
+        cvm.append(cm); cvsd.append(cs)
+    nas = np.zeros(nl, dtype=bool)
+    for m in range(nmodels):
+        nas |= np.isnan(cvsd[m])
+    if nas.any():
+        cvm = [c[~nas] for c in cvm]; cvsd = [c[~nas] for c in cvsd]
+        nz = [c[~nas] for c in nz]; lam = [l[~nas] for l in lam]
+    res = OemFit()
+    name = _BINOMIAL_NAMES[type_measure]
+    res.update({"lambda": lam, "cvm": cvm, "cvsd": cvsd, "cvup": [a + b for a, b in zip(cvm, cvsd)],
+                "cvlo": [a - b for a, b in zip(cvm, cvsd)], "nzero": nz, "name": name, "oem.fit": fit0})
+    if keep:
+        res["fit.preval"] = predlist; res["foldid"] = foldid
+    res.update(_getmin(lam, [-c for c in cvm] if name == "AUC" else cvm, cvsd))
+    res["best.model"] = penalty[res["model.min"] - 1]
+    res["penalty"] = list(penalty)
+    return res
+
+
 def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfolds=10, foldid=None, grouped=True, keep=False,
-           rng=None, parallel=False, **kw):
+           rng=None, parallel=False, family="gaussian", **kw):
     """cv.oem(): R/cv_oem.R:56-221 with cv.oemfit_gaussian (:349-423) and cvcompute (R/utils.R:128-144): K + 1 calls of oem(),
     every fold on its own lambda sequence, errors interpolated onto the full fit's lambdas.
+    family = "binomial" (cv.oemfit_binomial, :224-346; dense x): x goes to the device once (a numpy x is uploaded, a device tensor is used as it
+    is); the full fit, the fold fits -- row passes over that x which leave the fold's rows out, oemgpu_fit_logistic_dense_fold_dev -- and
+    the scoring of the held-out rows (oemgpu_logistic_cv_score_dev) read it there.  type_measure: "deviance" (default), "class", "mse",
+    "mae" or "auc" (on the host, from the held-out probabilities; ties in row order).  `parallel` is accepted and the folds still run
+    one after another.  The options are those of oem_fit_logistic_dense; the result has the keys below with an OemFitBinomial `oem.fit`.
     parallel (R/cv_oem.R:32, 129-150: the folds through foreach): the fold fits from a few host threads at once.  On one GPU that
     pays where a fit leaves most of the chip idle: the path kernels of n >> p fits (one CU each) overlap with other folds' moment
     kernels, and p >= n fits on the cooperating-workgroup engine (a quarter of the CUs each) run side by side -- they queue for CU
     slots by themselves.  Same results as the sequential loop.  (Measured, six folds: 300 x 1500 136 -> 117 ms; 5000 x 40 8 -> 17 ms --
     fits of a millisecond lose more to the thread hand-over than the overlap gains: the default stays sequential, as in R.)"""
+    if family not in ("gaussian", "binomial"):
+        raise ValueError("'arg' should be one of 'gaussian', 'binomial'")
     penalty = _match_penalty(penalty)
     if type_measure is None:
         type_measure = "default"
@@ -737,6 +917,8 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
         raise ValueError("'arg' should be one of " + ", ".join("'%s'" % t for t in _TYPE_MEASURES))
     if lambda_ is not None and len(lambda_) < 2:
         raise ValueError("Need more than one value of lambda for cv.oem")
+    if family == "binomial":
+        return _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, foldid, grouped, keep, rng, kw)
     if len(weights) > 0:
         raise ValueError("weights not implemented yet.")
     xh = np.asarray(x.cpu().numpy() if _is_torch_cuda(x) else x, dtype=np.float64)

@@ -26,6 +26,10 @@
 //     launches between looks at the stop word.  The threshold's scratch (u + XY, the new beta, a factor per group) is in LDS when its
 //     8 (2 q + ngroups) bytes fit LOGIT_LDS_BYTES, else in the workspace (one group per coordinate at p >= 6826);
 //   * small kernels: XX from the moments, A = dI - XX, XY = XX beta + grad, the IRLS stop, the back-transform.
+// cv.oem's fold fits (oemgpu_fit_logistic_dense_fold_dev; the scoring of the held-out rows is logistic_cv.hip): DenseLogitData with foldid /
+// leave_out is the fit on the rows with foldid != leave_out of the same resident X -- the MASKED row pass leaves those rows out (their Z
+// rows are zeros), logit_fold_scan_kernel counts the kept rows (n_eff, which stands where n enters the arithmetic) and maps the W floor's
+// IRLS index to the i-th kept row.
 // The host driver (logistic_irls) is shared with the sparse fit (logistic_sparse.hip): the passes over the data reach it as the stages of
 // a LogitData (logistic.hpp); DenseLogitData below is this file's.
 #include "logistic.hpp"
@@ -112,16 +116,20 @@ __device__ __forceinline__ int stop_violated(double c, double pv, double tol)
 
 // ---------------------------------------------------------------------------------------------------------------- row pass
 // mode 0: r = y (X'Y for XY's first form and lambda_0); mode 1: the IRLS quantities.  zout: Z block (ldz rows), or null.
-template <bool STAGED>
+// MASKED (a fold fit): rows with foldid[row] == leave_out are not in the fit.  Such a row is never loaded; it adds nothing to sum r, X'r
+// or the loss, and its Z row is written as zeros (the Z buffer is reused from block to block and from step to step, so it cannot be
+// skipped).  irls_i is then the row of the i-th KEPT row.  The unmasked instantiations are the code they were before MASKED existed.
+template <bool STAGED, bool MASKED>
 __global__ __launch_bounds__(256) void logit_rows_kernel(const double *__restrict__ x, int64_t n, int64_t ld, int p, const double *__restrict__ y,
                                                          const double *__restrict__ beta, const double *__restrict__ s, int intercept, int mode,
                                                          int64_t irls_i, int64_t ch, int64_t chunk0, int64_t row0, double *__restrict__ zout,
-                                                         int64_t ldz, double *__restrict__ part)
+                                                         int64_t ldz, double *__restrict__ part, const int32_t *__restrict__ foldid, int32_t leave_out)
 {
     extern __shared__ double lsh[];
     double *acc = lsh;                               // p
     double *tile = lsh + p;                          // 65 p (STAGED)
     __shared__ double etap[4][64], rsh[64], wsh[64], red[2][64];
+    __shared__ int ksh[64];                          // MASKED, not STAGED: 1 for a kept row of the sub-block
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const int o = intercept ? 1 : 0;
     const int64_t c = chunk0 + blockIdx.x;
@@ -132,23 +140,25 @@ __global__ __launch_bounds__(256) void logit_rows_kernel(const double *__restric
     for (int64_t r0 = r_lo; r0 < r_hi; r0 += 64) {
         const int64_t row = r0 + lane;
         const bool ok = row < r_hi;
+        bool kept = ok;                              // the row is in the fit
+        if (MASKED) kept = ok && foldid[row] != leave_out;
         // phase 1: wave w reads columns j = w (mod 4), lane = row (coalesced); eta partials
         double e = 0.0;
         if (mode) {
             for (int j = w; j < p; j += 4) {
-                const double v = ok ? x[(size_t)j * ld + row] : 0.0;
+                const double v = kept ? x[(size_t)j * ld + row] : 0.0;
                 if (STAGED) tile[j * 65 + lane] = v;
                 e = fma(v, beta[o + j] * s[j], e);
             }
         } else if (STAGED) {
-            for (int j = w; j < p; j += 4) tile[j * 65 + lane] = ok ? x[(size_t)j * ld + row] : 0.0;
+            for (int j = w; j < p; j += 4) tile[j * 65 + lane] = kept ? x[(size_t)j * ld + row] : 0.0;
         }
         etap[w][lane] = e;
         __syncthreads();
         // phase 2: one wave forms prob, W, r and the loss terms of its 64 rows
         if (w == 0) {
             double r = 0.0, sw = 0.0;
-            if (ok) {
+            if (kept) {
                 const double yi = y[row];
                 if (mode) {
                     const double eta = ((etap[0][lane] + etap[1][lane]) + (etap[2][lane] + etap[3][lane])) + b0;
@@ -165,9 +175,10 @@ __global__ __launch_bounds__(256) void logit_rows_kernel(const double *__restric
                     r = yi;
                 }
                 rsum += r;
-                if (zout && o) zout[row - row0] = sw;
             }
+            if (ok && zout && o) zout[row - row0] = sw;
             rsh[lane] = r; wsh[lane] = sw;
+            if (MASKED && !STAGED) ksh[lane] = kept ? 1 : 0;
         }
         __syncthreads();
         // phase 3: thread j accumulates column j over the 64 rows, in row order
@@ -176,6 +187,9 @@ __global__ __launch_bounds__(256) void logit_rows_kernel(const double *__restric
             const int lim = (int)((r_hi - r0) < 64 ? (r_hi - r0) : 64);
             if (STAGED) {
                 for (int i = 0; i < lim; ++i) a = fma(tile[j * 65 + i], rsh[i], a);
+            } else if (MASKED) {
+                const double *col = x + (size_t)j * ld + r0;
+                for (int i = 0; i < lim; ++i) a = fma(ksh[i] ? col[i] : 0.0, rsh[i], a);
             } else {
                 const double *col = x + (size_t)j * ld + r0;
                 for (int i = 0; i < lim; ++i) a = fma(col[i], rsh[i], a);
@@ -185,7 +199,7 @@ __global__ __launch_bounds__(256) void logit_rows_kernel(const double *__restric
         // phase 4: Z = sqrt(W) (x s) of these rows, coalesced as in phase 1
         if (zout && ok) {
             for (int j = w; j < p; j += 4) {
-                const double v = STAGED ? tile[j * 65 + lane] : x[(size_t)j * ld + row];
+                const double v = STAGED ? tile[j * 65 + lane] : (kept ? x[(size_t)j * ld + row] : 0.0);
                 zout[(size_t)(o + j) * ldz + (row - row0)] = wsh[lane] * (v * s[j]);
             }
         }
@@ -385,20 +399,27 @@ __global__ __launch_bounds__(256) void logit_back_kernel(const double *__restric
     out[i] = beta[(intercept ? 1 : 0) + i - 1] * s[i - 1];
 }
 
-// colsq = sum x^2 / (n - 1), 0 -> 1, s = 1 / sqrt(colsq) (h :734-737); one workgroup per column, rank-order sum
-__global__ __launch_bounds__(256) void logit_scale_kernel(const double *__restrict__ x, int64_t n, int64_t ld, double *__restrict__ s)
+// colsq = sum x^2 / (n - 1), 0 -> 1, s = 1 / sqrt(colsq) (h :734-737); one workgroup per column, rank-order sum.  A fold fit (foldid
+// not null): the sum over the kept rows, n_eff of them
+__global__ __launch_bounds__(256) void logit_scale_kernel(const double *__restrict__ x, int64_t n, int64_t ld, double *__restrict__ s,
+                                                          const int32_t *__restrict__ foldid, int32_t leave_out, int64_t n_eff)
 {
     __shared__ double red[256];
     const int j = blockIdx.x;
     const double *col = x + (size_t)j * ld;
     double a = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 256) a = fma(col[i], col[i], a);
+    if (foldid) {
+        for (int64_t i = threadIdx.x; i < n; i += 256)
+            if (foldid[i] != leave_out) a = fma(col[i], col[i], a);
+    } else {
+        for (int64_t i = threadIdx.x; i < n; i += 256) a = fma(col[i], col[i], a);
+    }
     red[threadIdx.x] = a;
     __syncthreads();
     if (threadIdx.x == 0) {
         double t = 0.0;
         for (int k = 0; k < 256; ++k) t += red[k];
-        double cs = t / ((double)n - 1.0);
+        double cs = t / ((double)n_eff - 1.0);
         if (cs == 0.0) cs = 1.0;
         s[j] = 1.0 / sqrt(cs);
     }
@@ -408,6 +429,43 @@ __global__ void logit_fill_kernel(double *a, int n, double v)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) a[i] = v;
+}
+
+// A fold fit's look at foldid, once per call, by ONE workgroup: out[0] = n_eff (rows with foldid != leave_out), out[1] = rows whose id
+// is outside [1, nfolds], out[2 + k] = the row of the k-th kept row for k < nmap (the W floor tests the IRLS index among the kept rows).
+__global__ __launch_bounds__(1024) void logit_fold_scan_kernel(const int32_t *__restrict__ foldid, int64_t n, int32_t nfolds, int32_t leave_out,
+                                                               int64_t nmap, int64_t *__restrict__ out)
+{
+    __shared__ long long cnt[1024], bad[1024];
+    __shared__ int wcount[16];
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    long long k = 0, b = 0;
+    for (int64_t i = tid; i < n; i += 1024) {
+        const int32_t f = foldid[i];
+        k += f != leave_out;
+        b += f < 1 || f > nfolds;
+    }
+    cnt[tid] = k; bad[tid] = b;
+    __syncthreads();
+    if (tid == 0) {
+        long long a = 0, c = 0;
+        for (int i = 0; i < 1024; ++i) { a += cnt[i]; c += bad[i]; }
+        out[0] = a; out[1] = c;
+    }
+    int64_t base = 0;                                // kept rows before this tile of 1024 rows
+    for (int64_t r0 = 0; r0 < n && base < nmap; r0 += 1024) {
+        const int64_t row = r0 + tid;
+        const bool kept = row < n && foldid[row] != leave_out;
+        const unsigned long long m = __ballot(kept);
+        if (lane == 0) wcount[w] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int i = 0; i < 16; ++i) { before += i < w ? wcount[i] : 0; total += wcount[i]; }
+        const int64_t pos = base + before + __popcll(m & ((1ull << lane) - 1ull));
+        if (kept && pos < nmap) out[2 + pos] = row;
+        base += total;
+        __syncthreads();
+    }
 }
 
 }  // namespace
@@ -428,21 +486,29 @@ static thread_local LogitStats g_logit_stats;
 const int LOGIT_WG_MAX_Q = LOGIT_WG_MAX;
 const int LOGIT_P_LIMIT = LOGIT_P_MAX;
 
-static int logit_rows(hipStream_t s, const LogitPlan &P, const double *x, int64_t n, int64_t ld, int p, const double *y, const double *beta,
-                      const double *sc, int intercept, int mode, int64_t irls_i, int64_t c0, int64_t nc, int64_t row0, double *z, int64_t ldz, double *part)
+template <bool STAGED, bool MASKED>
+static int logit_rows_launch(hipStream_t s, const LogitPlan &P, size_t lds, const double *x, int64_t n, int64_t ld, int p, const double *y,
+                             const double *beta, const double *sc, int intercept, int mode, int64_t irls_i, int64_t c0, int64_t nc, int64_t row0,
+                             double *z, int64_t ldz, double *part, const int32_t *foldid, int32_t leave_out)
 {
-    const size_t lds = 8 * (size_t)p + (P.staged ? 8 * 65 * (size_t)p : 0);
-    if (P.staged) {
-        if (lds_limit_once(reinterpret_cast<const void *>(&logit_rows_kernel<true>), lds)) return OEMGPU_ERR_HIP;
-        hipLaunchKernelGGL(logit_rows_kernel<true>, dim3((unsigned)nc), dim3(256), lds, s, x, n, ld, p, y, beta, sc, intercept, mode, irls_i, P.ch, c0,
-                           row0, z, ldz, part);
-    } else {
-        if (lds_limit_once(reinterpret_cast<const void *>(&logit_rows_kernel<false>), lds)) return OEMGPU_ERR_HIP;
-        hipLaunchKernelGGL(logit_rows_kernel<false>, dim3((unsigned)nc), dim3(256), lds, s, x, n, ld, p, y, beta, sc, intercept, mode, irls_i, P.ch, c0,
-                           row0, z, ldz, part);
-    }
+    if (lds_limit_once(reinterpret_cast<const void *>(&logit_rows_kernel<STAGED, MASKED>), lds)) return OEMGPU_ERR_HIP;
+    hipLaunchKernelGGL((logit_rows_kernel<STAGED, MASKED>), dim3((unsigned)nc), dim3(256), lds, s, x, n, ld, p, y, beta, sc, intercept, mode, irls_i,
+                       P.ch, c0, row0, z, ldz, part, foldid, leave_out);
     OEM_HIP(hipGetLastError());
     return 0;
+}
+
+// foldid null: the fit on every row; else the fold fit that leaves out the rows of fold leave_out
+static int logit_rows(hipStream_t s, const LogitPlan &P, const double *x, int64_t n, int64_t ld, int p, const double *y, const double *beta,
+                      const double *sc, int intercept, int mode, int64_t irls_i, int64_t c0, int64_t nc, int64_t row0, double *z, int64_t ldz, double *part,
+                      const int32_t *foldid, int32_t leave_out)
+{
+    const size_t lds = 8 * (size_t)p + (P.staged ? 8 * 65 * (size_t)p : 0);
+    if (foldid)
+        return P.staged ? logit_rows_launch<true, true>(s, P, lds, x, n, ld, p, y, beta, sc, intercept, mode, irls_i, c0, nc, row0, z, ldz, part, foldid, leave_out)
+                        : logit_rows_launch<false, true>(s, P, lds, x, n, ld, p, y, beta, sc, intercept, mode, irls_i, c0, nc, row0, z, ldz, part, foldid, leave_out);
+    return P.staged ? logit_rows_launch<true, false>(s, P, lds, x, n, ld, p, y, beta, sc, intercept, mode, irls_i, c0, nc, row0, z, ldz, part, nullptr, 0)
+                    : logit_rows_launch<false, false>(s, P, lds, x, n, ld, p, y, beta, sc, intercept, mode, irls_i, c0, nc, row0, z, ldz, part, nullptr, 0);
 }
 
 // checks that need no device: -1 / -4 before any device is looked for
@@ -469,7 +535,8 @@ static double now_ms() { return std::chrono::duration<double, std::milli>(std::c
 namespace {
 
 // the dense x: one row pass per IRLS step (logit_rows_kernel); with a Hessian due the same pass writes the Z row blocks of the
-// moment pass instead, block after block
+// moment pass instead, block after block.  With foldid / leave_out it is the data of the fit on the rows with foldid[row] != leave_out:
+// X and y stay where they are, the passes leave those rows out, and n_eff (the kept rows) stands where n enters the arithmetic.
 struct DenseLogitData final : LogitData {
     oemgpu_ctx *c;
     const double *x, *y;
@@ -478,10 +545,36 @@ struct DenseLogitData final : LogitData {
     LogitPlan P;
     size_t m2;
     double *part = nullptr, *z = nullptr, *mb = nullptr, *ma = nullptr, *tp = nullptr, *vp = nullptr;
+    const int32_t *foldid = nullptr;  // device, n entries; null: every row is in the fit
+    int32_t leave_out = 0;
+    int64_t n_eff;                    // rows in the fit
+    std::vector<int64_t> kept_row;    // fold fit: the row of the k-th kept row, k < min(irls_maxit, n_eff)
+
+    // The row whose W the floor tests at IRLS step i (h :953-959 tests W(i) of the rows it was given)
+    int64_t floor_row(int64_t i) const { return foldid ? (i < (int64_t)kept_row.size() ? kept_row[(size_t)i] : -1) : i; }
+    // Makes this the fold fit without fold leave_out_: counts n_eff, checks the ids' range and maps the first IRLS indices to rows, on
+    // the device, once (scratch: the start of c->ws, read back before anything else uses it)
+    int set_fold(const int32_t *foldid_, int32_t nfolds, int32_t leave_out_, int32_t irls_maxit)
+    {
+        const int64_t nmap = std::min<int64_t>(irls_maxit, n);
+        if (ctx_reserve(c, 8 * (size_t)(2 + nmap))) return OEMGPU_ERR_HIP;
+        int64_t *scan = (int64_t *)c->ws;
+        hipLaunchKernelGGL(logit_fold_scan_kernel, dim3(1), dim3(1024), 0, c->stream, foldid_, n, nfolds, leave_out_, nmap, scan);
+        OEM_HIP(hipGetLastError());
+        std::vector<int64_t> h((size_t)(2 + nmap), -1);
+        OEM_HIP(hipMemcpyAsync(h.data(), scan, 8 * 2, hipMemcpyDeviceToHost, c->stream));
+        OEM_HIP(hipStreamSynchronize(c->stream));
+        if (h[1] != 0) { set_error("fit_logistic_dense_fold: %lld fold ids are outside [1, %d]", (long long)h[1], (int)nfolds); return OEMGPU_ERR_ARG; }
+        const int64_t nk = std::min<int64_t>(nmap, h[0]);
+        if (nk > 0) OEM_HIP(hipMemcpy(h.data() + 2, scan + 2, 8 * (size_t)nk, hipMemcpyDeviceToHost));
+        foldid = foldid_; leave_out = leave_out_; n_eff = h[0];
+        kept_row.assign(h.begin() + 2, h.begin() + 2 + nk);
+        return 0;
+    }
 
     DenseLogitData(oemgpu_ctx *c_, const double *x_, int64_t n_, int64_t ld_, int p_, const double *y_, int standardize_, int intercept_, int hessian_full)
         : c(c_), x(x_), y(y_), n(n_), ld(ld_), p(p_), q(p_ + (intercept_ ? 1 : 0)), intercept(intercept_), standardize(standardize_),
-          P(logit_plan(n_, p_, intercept_, c_->num_cu)), m2((size_t)(q + 2) * (q + 2))
+          P(logit_plan(n_, p_, intercept_, c_->num_cu)), m2((size_t)(q + 2) * (q + 2)), n_eff(n_)
     {
         hess_every = hessian_full != 0;
     }
@@ -504,14 +597,14 @@ struct DenseLogitData final : LogitData {
     }
     int scale(double *sc) override
     {
-        if (standardize) hipLaunchKernelGGL(logit_scale_kernel, dim3(p), dim3(256), 0, c->stream, x, n, ld, sc);
+        if (standardize) hipLaunchKernelGGL(logit_scale_kernel, dim3(p), dim3(256), 0, c->stream, x, n, ld, sc, foldid, leave_out, n_eff);
         else hipLaunchKernelGGL(logit_fill_kernel, dim3((p + 255) / 256), dim3(256), 0, c->stream, sc, p, 1.0);
         OEM_HIP(hipGetLastError());
         return 0;
     }
     int xy0(const double *sc, double *g) override
     {
-        int rc = logit_rows(c->stream, P, x, n, ld, p, y, nullptr, sc, intercept, 0, -1, 0, P.nchunk, 0, nullptr, 0, part);
+        int rc = logit_rows(c->stream, P, x, n, ld, p, y, nullptr, sc, intercept, 0, -1, 0, P.nchunk, 0, nullptr, 0, part, foldid, leave_out);
         if (rc) return rc;
         hipLaunchKernelGGL(logit_sum_kernel, dim3((p + 2 + 255) / 256), dim3(256), 0, c->stream, part, P.nchunk, p + 2, g);
         OEM_HIP(hipGetLastError());
@@ -520,7 +613,7 @@ struct DenseLogitData final : LogitData {
     int rows(const double *beta, const double *sc, int64_t i, bool gram, double *g) override
     {
         if (gram) return 0;                                  // the Z blocks of the Hessian build carry the row pass
-        int rc = logit_rows(c->stream, P, x, n, ld, p, y, beta, sc, intercept, 1, i, 0, P.nchunk, 0, nullptr, 0, part);
+        int rc = logit_rows(c->stream, P, x, n, ld, p, y, beta, sc, intercept, 1, floor_row(i), 0, P.nchunk, 0, nullptr, 0, part, foldid, leave_out);
         if (rc) return rc;
         hipLaunchKernelGGL(logit_sum_kernel, dim3((p + 2 + 255) / 256), dim3(256), 0, c->stream, part, P.nchunk, p + 2, g);
         OEM_HIP(hipGetLastError());
@@ -533,7 +626,7 @@ struct DenseLogitData final : LogitData {
         for (int64_t b = 0; b < P.nzblk; ++b) {
             const int64_t c0 = b * (P.rbz / P.ch), c1 = std::min<int64_t>(P.nchunk, c0 + P.rbz / P.ch);
             const int64_t r0 = c0 * P.ch, nrow = std::min<int64_t>(n, c1 * P.ch) - r0;
-            int r = logit_rows(s, P, x, n, ld, p, y, beta, sc, intercept, 1, i, c0, c1 - c0, r0, z, P.rbz, part);
+            int r = logit_rows(s, P, x, n, ld, p, y, beta, sc, intercept, 1, floor_row(i), c0, c1 - c0, r0, z, P.rbz, part, foldid, leave_out);
             if (r) return r;
             const GramPlan gpl = gram_plan(nrow, q, c->num_cu);
             r = launch_gram(s, gpl, z, nrow, P.rbz, z, nullptr, tp, vp);
@@ -541,7 +634,7 @@ struct DenseLogitData final : LogitData {
             if (!r) r = launch_moments_add(s, ma, mb, m2, b == 0);
             if (r) return r;
         }
-        hipLaunchKernelGGL(logit_xx_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, ma, q, (double)n, xx);
+        hipLaunchKernelGGL(logit_xx_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, ma, q, (double)n_eff, xx);
         hipLaunchKernelGGL(logit_sum_kernel, dim3((p + 2 + 255) / 256), dim3(256), 0, s, part, P.nchunk, p + 2, g);
         OEM_HIP(hipGetLastError());
         return 0;
@@ -812,6 +905,22 @@ int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int3
     return logistic_irls(c, D, n, p, intercept, irls_maxit, irls_tol, o, beta_out, lambda_out, niter, loss_out, d_out);
 }
 
+// the fit on the rows with foldid[row] != leave_out (cv.oem's fold fit: what the dense fit computes on x[keep, ], y[keep])
+int logistic_fit_fold_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int32_t p, const double *y, const int32_t *foldid, int32_t nfolds,
+                          int32_t leave_out, int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol,
+                          const oemgpu_opts *o, double *beta_out, double *lambda_out, int32_t *niter, double *loss_out, double *d_out)
+{
+    DenseLogitData D(c, x, n, ld, p, y, standardize, intercept, hessian_full);
+    int rc = D.set_fold(foldid, nfolds, leave_out, irls_maxit);
+    if (rc) return rc;
+    if ((int64_t)D.q >= D.n_eff) {
+        set_error("fit_logistic_dense_fold: p + intercept >= the %lld rows outside fold %d is not supported (the reference's XWXt branch, "
+                  "ref src/oem_logistic_dense.h:524-566)", (long long)D.n_eff, (int)leave_out);
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    return logistic_irls(c, D, D.n_eff, p, intercept, irls_maxit, irls_tol, o, beta_out, lambda_out, niter, loss_out, d_out);
+}
+
 }  // namespace oemgpu
 
 using namespace oemgpu;
@@ -829,6 +938,25 @@ int oemgpu_fit_logistic_dense_dev(oemgpu_ctx *c, const double *x_dev, int64_t n,
     if (ld < n) { set_error("fit_logistic_dense: ld < n"); return OEMGPU_ERR_ARG; }
     if (set_device(c)) return OEMGPU_ERR_HIP;
     return logistic_fit_dev(c, x_dev, n, ld, p, y_dev, standardize, intercept, hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
+}
+
+int oemgpu_fit_logistic_dense_fold_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                                       const int32_t *foldid_dev, int32_t nfolds, int32_t leave_out, int32_t standardize, int32_t intercept,
+                                       int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
+                                       double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+{
+    if (!c || !x_dev || !y_dev || !foldid_dev || !o || !beta || !lambda_out || !niter || !loss || !d) {
+        set_error("fit_logistic_dense_fold: NULL argument");
+        return OEMGPU_ERR_ARG;
+    }
+    if (nfolds < 3) { set_error("nfolds must be bigger than 3; nfolds=10 recommended"); return OEMGPU_ERR_ARG; }            // ref R/cv_oem.R:126-127
+    if (leave_out < 0 || leave_out > nfolds) { set_error("fit_logistic_dense_fold: leave_out must be in [0, nfolds]"); return OEMGPU_ERR_ARG; }
+    int rc = logistic_check(n, p, intercept, hessian_full, irls_maxit, irls_tol, o);
+    if (rc) return rc;
+    if (ld < n) { set_error("fit_logistic_dense_fold: ld < n"); return OEMGPU_ERR_ARG; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    return logistic_fit_fold_dev(c, x_dev, n, ld, p, y_dev, foldid_dev, nfolds, leave_out, standardize, intercept, hessian_full, irls_maxit, irls_tol, o,
+                                 beta, lambda_out, niter, loss, d);
 }
 
 int oemgpu_fit_logistic_dense(const double *x, int64_t n, int32_t p, const double *y, int32_t standardize, int32_t intercept, int32_t hessian_full,
