@@ -418,6 +418,11 @@ int oemgpu_fit_logistic_sparse(int64_t n, int32_t p, const int64_t *colptr, cons
  * bytes of the fit's data stages, out[3] the bound out[2] stays within, out[4] rows per tile (0 on the compressed-column route),
  * out[5] workgroups of the row pass, out[6] rows per row-pass workgroup, out[7] 8192-row chunks of the compressed-column kernels. */
 int oemgpu_selftest_logistic_sparse_plan(int64_t n, int32_t p, int64_t nnz, int32_t intercept, int32_t num_cu, int64_t *out /* 8 */);
+/* Host-only plan of the compressed-column Gram kernel both sparse fits share (pure arithmetic, runs without a GPU): out[0] 8192-row
+ * chunks of an n-row matrix, out[1] contiguous chunk ranges the launch splits them into (the range sums cost out[1] p^2 doubles, kept
+ * under 256 MB), out[2] chunks per range (range r = chunks [r out[2], min(out[0], (r + 1) out[2])), possibly none for the last ranges),
+ * out[3] bytes of LDS a workgroup asks for (the route is open while they fit the 160 KiB of a CU).  OEMGPU_ERR_ARG on n < 1 or p < 1. */
+int oemgpu_selftest_csc_plan(int64_t n, int32_t p, int64_t *out /* 4 */);
 /* What the most recent binomial fit of THIS thread did (dense or sparse): [0] row-pass ms [1] Z + Gram + Lanczos ms [2] inner-solve ms (the three only
  * with oemgpu_set_timing on the context; 0 otherwise) [3] IRLS steps [4] inner iterations [5] row passes [6] Gram builds [7] wall ms */
 int oemgpu_last_logistic_stats(double *out /* 8 */);

@@ -63,6 +63,7 @@ _SIGS = {
     "oemgpu_fit_logistic_sparse": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                               C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_selftest_logistic_sparse_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "oemgpu_selftest_csc_plan": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_last_logistic_stats": (C.c_int, [_dp]),
     "oemgpu_fit_xtx": (C.c_int, [_dp, _dp, C.c_int32, _dp, C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_fit_big": (C.c_int, [C.POINTER(_dp), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(_dp), C.c_int32,

@@ -299,6 +299,26 @@ static int csc_ranges(int64_t n, int p)
 
 int csc_chunks(int64_t n) { return (int)((n + SRC - 1) / SRC); }
 
+}  // namespace oemgpu
+
+extern "C" {
+#pragma GCC visibility push(default)
+
+// out[0] chunks, [1] chunk ranges (blockIdx.y of csc_gram_kernel), [2] chunks per range (the kernel's cper), [3] its LDS bytes
+int oemgpu_selftest_csc_plan(int64_t n, int32_t p, int64_t *out)
+{
+    using namespace oemgpu;
+    if (n < 1 || p < 1 || !out) { set_error("selftest_csc_plan: bad argument"); return OEMGPU_ERR_ARG; }
+    const int nchunk = csc_chunks(n), nrange = csc_ranges(n, p);
+    out[0] = nchunk; out[1] = nrange; out[2] = (nchunk + nrange - 1) / nrange; out[3] = (int64_t)csc_gram_lds(p);
+    return 0;
+}
+
+#pragma GCC visibility pop
+}
+
+namespace oemgpu {
+
 size_t csc_moments_work_bytes(int64_t n, int p)
 {
     return sizeof(int32_t) * ((size_t)csc_chunks(n) + 1) * (size_t)p + 256 + sizeof(double) * ((size_t)csc_ranges(n, p) * p * p + 2 * NY) + 256;

@@ -12,9 +12,10 @@ import scipy.sparse as sp
 
 from tests import logistic_restatement as RD
 from tests import logistic_sparse_restatement as RS
+from tests.test_gpu_logistic_sparse_bounds import _edge_matrix
 
 ROOT = Path(__file__).resolve().parent.parent
-ENTRIES = ("oemgpu_fit_logistic_sparse", "oemgpu_selftest_logistic_sparse_plan")
+ENTRIES = ("oemgpu_fit_logistic_sparse", "oemgpu_selftest_logistic_sparse_plan", "oemgpu_selftest_csc_plan")
 
 
 def _problem(n, p, density, seed, intercept_shift=0.0):
@@ -39,16 +40,24 @@ def test_entries_declared_and_exported():
     assert '"logistic_sparse.hip"' in src
 
 
-@pytest.mark.parametrize("standardize", [True, False])
-def test_restatement_without_intercept_is_the_dense_full_hessian(standardize):
-    x, y = _problem(300, 7, 0.3, 1)
+# the edge matrix of the GPU bounds file ((n, p, seed)): empty columns and rows, stored zeros, a one-entry column, rows 8191 / 8192 / n - 1
+EDGE = [(8291, 9, 2), (641, 33, 62)]
+
+
+def _is_the_dense_full_hessian(standardize, shape):
+    x, y = _problem(300, 7, 0.3, 1) if shape is None else _edge_matrix(*shape, k=3)
     kw = dict(penalty=["lasso", "mcp"], nlambda=6, lambda_min_ratio=0.05, intercept=False, standardize=standardize, compute_loss=True,
               irls_tol=1e-6, tol=1e-9)
+    if shape is not None:
+        kw["irls_maxit"] = 20                                    # mcp runs away along the edge matrix's few-entry columns: a few steps of it do
     st_s, st_d = {}, {}
     a = RS.fit(x, y, stats=st_s, **kw)
     b = RD.fit(x.toarray(), y, hessian_full=True, stats=st_d, **kw)
     for k in range(2):
-        np.testing.assert_allclose(a["beta"][k], b["beta"][k], rtol=0, atol=1e-12)
+        # the two sum in different orders (a sparse product, a dense one): on the edge matrix, where |beta| grows to ~100, the 1e-12 is
+        # taken relative to it
+        atol = 1e-12 if shape is None else 1e-12 * max(1.0, float(np.abs(b["beta"][k]).max()))
+        np.testing.assert_allclose(a["beta"][k], b["beta"][k], rtol=0, atol=atol)
         assert np.array_equal(a["niter"][k], b["niter"][k])
         np.testing.assert_allclose(a["loss"][k], b["loss"][k], rtol=1e-12)
         np.testing.assert_allclose(a["lambda"][k], b["lambda"][k], rtol=1e-13)
@@ -57,21 +66,48 @@ def test_restatement_without_intercept_is_the_dense_full_hessian(standardize):
     assert st_s["grams"] == st_s["rows"] and a["intval"] == 0.0
 
 
+@pytest.mark.parametrize("standardize", [True, False])
+def test_restatement_without_intercept_is_the_dense_full_hessian(standardize):
+    _is_the_dense_full_hessian(standardize, None)
+
+
+@pytest.mark.parametrize("shape", EDGE)
+@pytest.mark.parametrize("standardize", [True, False])
+def test_restatement_without_intercept_is_the_dense_full_hessian_on_the_edge_matrix(standardize, shape):
+    _is_the_dense_full_hessian(standardize, shape)
+
+
 def test_restatement_kkt_with_intercept():
     """intercept + standardize: at every lambda (B[0] / intval, B[1:]) is a lasso-logistic KKT point -- this pins eta with beta_0 as it
     is (quirk 3), the intercept's XX row only steering the iteration (6), and the in-place rescale that the next lambda starts from (9)"""
+    _kkt_with_intercept(None)
+
+
+@pytest.mark.parametrize("shape", EDGE)
+def test_restatement_kkt_with_intercept_on_the_edge_matrix(shape):
+    _kkt_with_intercept(shape)
+
+
+def _kkt_with_intercept(shape):
     rng = np.random.default_rng(3)
-    n, p = 400, 8
-    x = sp.random(n, p, density=0.35, format="csc", random_state=rng, data_rvs=lambda k: rng.choice([-1.0, 1.0], k) * rng.uniform(0.5, 1.5, k))
-    eta = x @ np.array([1.2, -0.8, 0.6, 0, 0, 0, 0, 0]) + 0.4
-    y = (rng.uniform(size=n) < 1.0 / (1.0 + np.exp(-eta))).astype(np.float64)
+    if shape is None:
+        n, p = 400, 8
+        x = sp.random(n, p, density=0.35, format="csc", random_state=rng,
+                      data_rvs=lambda k: rng.choice([-1.0, 1.0], k) * rng.uniform(0.5, 1.5, k))
+        eta = x @ np.array([1.2, -0.8, 0.6, 0, 0, 0, 0, 0]) + 0.4
+        y = (rng.uniform(size=n) < 1.0 / (1.0 + np.exp(-eta))).astype(np.float64)
+    else:
+        n, p = shape[:2]
+        x, y = _edge_matrix(*shape, k=3, intercept=0.4)
     st = {}
     res = RS.fit(x, y, penalty=["lasso"], nlambda=6, lambda_min_ratio=0.02, tol=1e-12, irls_tol=1e-12, maxit=200000, irls_maxit=400, stats=st)
     intval = res["intval"]
     assert intval > 0 and st["intval"] == intval
     assert np.all(res["niter"][0] <= 400)                       # every lambda converged
     xd = x.toarray()
-    s = 1.0 / np.sqrt(np.sum(xd * xd, axis=0) / (n - 1.0))
+    colsq = np.sum(xd * xd, axis=0) / (n - 1.0)
+    colsq[colsq == 0.0] = 1.0                                    # an empty column (quirk 2)
+    s = 1.0 / np.sqrt(colsq)
     for li, lam in enumerate(res["lambda"][0]):
         B = res["beta"][0][:, li]
         b0 = B[0] / intval
@@ -231,6 +267,34 @@ def test_plan_sweep():
                         assert rc * p * 8 <= 2 ** 31 or rc == 64
     assert lib.oemgpu_selftest_logistic_sparse_plan(0, 5, 10, 0, 256, out) == -1
     assert lib.oemgpu_selftest_logistic_sparse_plan(100, 5, -1, 0, 256, out) == -1
+
+
+def test_csc_plan_sweep():
+    """the compressed-column Gram's own plan over the grid of test_plan_sweep: every chunk lies in a range, the range sums stay under
+    256 MB, and the route is open exactly while the kernel's LDS fits a CU"""
+    import oem_amd
+    lib = oem_amd.lib()
+    out, lsp = (C.c_int64 * 4)(), (C.c_int64 * 8)()
+    for n in (100, 9000, 2 * 10 ** 4, 2 * 10 ** 5, 10 ** 6, 3 * 10 ** 9):
+        for p in (3, 50, 200, 1000, 1023, 1024, 4000, 6200, 8191):
+            if p + 1 >= n:
+                continue
+            assert lib.oemgpu_selftest_csc_plan(n, p, out) == 0
+            chunks, ranges, cper, lds = list(out)
+            assert chunks == -(-n // 8192) and lds == 8192 * 8 + 16 * p + 64
+            assert ranges >= 1, (n, p)
+            assert ranges <= chunks, (n, p)
+            assert cper * ranges >= chunks and (cper - 1) * ranges < chunks, (n, p)
+            assert ranges * p * p * 8 <= 256e6 or ranges == 1, (n, p)
+            assert lib.oemgpu_selftest_logistic_sparse_plan(n, p, 0, 0, 256, lsp) == 0
+            assert lsp[0] == int(lds <= 160 * 1024 and n < 2 ** 31), (n, p)      # nnz = 0: only the LDS and the 32-bit rows decide
+    for n, p, want in ((24577, 101, (4, 4, 1)), (32769, 411, (5, 4, 2)), (8193, 6140, (2, 1, 2)), (8192, 33, (1, 1, 1))):
+        assert lib.oemgpu_selftest_csc_plan(n, p, out) == 0
+        assert tuple(out)[:3] == want, (n, p, list(out))
+    assert lib.oemgpu_selftest_csc_plan(8193, 6140, out) == 0 and out[3] == 160 * 1024
+    assert lib.oemgpu_selftest_csc_plan(8193, 6141, out) == 0 and out[3] > 160 * 1024
+    assert lib.oemgpu_selftest_csc_plan(0, 5, out) == -1
+    assert lib.oemgpu_selftest_csc_plan(100, 0, out) == -1
 
 
 def test_r_binding_compiles_and_marshals(tmp_path):
