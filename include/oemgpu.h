@@ -394,6 +394,12 @@ int oemgpu_fit_logistic_dense_fold_dev(oemgpu_ctx *ctx, const double *x_dev, int
 int oemgpu_logistic_cv_score_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev, double y_hi,
                                  const int32_t *foldid_dev, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts,
                                  double *predmat_dev);
+/* Host-only plan of oemgpu_logistic_cv_score_dev (pure arithmetic, runs without a GPU; the entry takes its launch shape from the same
+ * function): out[0] rows per workgroup (a multiple of 64; a workgroup walks them in tiles of 64), out[1] workgroups of a launch
+ * (workgroup c = rows [c out[0], min(n, (c + 1) out[0]))), out[2] 1 if a fold's coefficient table sits in LDS (8 (ncol (p + 9) + 1)
+ * bytes fit the 160 KiB of a CU) and 0 if it is read through the cache, out[3] columns per launch, out[4] launches per fold, out[5]
+ * dynamic LDS bytes of the largest launch.  OEMGPU_ERR_ARG on n < 1, p outside [1, 8191], ncol < 1 or num_cu < 1. */
+int oemgpu_selftest_cv_score_plan(int64_t n, int32_t p, int32_t ncol, int32_t num_cu, int64_t *out /* 6 */);
 /* Host-only plan of the binomial fit (pure arithmetic, runs without a GPU): out[0] rows per chunk of the row pass, out[1] chunks
  * (chunk c = rows [c out[0], min(n, (c + 1) out[0]))), out[2] rows per Z block of the moment pass, out[3] Z blocks, out[4] 1 if the
  * inner solve is one persistent workgroup (q <= 1024) and 0 for launch per iteration, out[5] 1 if the row pass stages its sub-blocks

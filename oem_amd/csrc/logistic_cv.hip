@@ -25,6 +25,28 @@ namespace oemgpu {
 static const size_t CV_LDS_BYTES = (size_t)160 << 10;   // LDS of a gfx950 CU
 static const int CV_COL_BATCH = 2048;                   // columns per launch when the table is not in LDS (their accumulators are)
 
+struct CvScorePlan {
+    int64_t ch;        // rows per workgroup (a multiple of 64)
+    int64_t nchunk;    // workgroups of a launch: workgroup c = rows [c ch, min(n, (c + 1) ch))
+    bool tlds;         // a fold's coefficient table sits in LDS beside the accumulators
+    int cb;            // columns per launch
+    int nlaunch;       // launches per fold
+    size_t lds;        // dynamic LDS bytes of the largest launch
+};
+
+static CvScorePlan cv_score_plan(int64_t n, int p, int ncol, int num_cu)
+{
+    CvScorePlan P;
+    int64_t ch = (n + 4 * (int64_t)num_cu - 1) / (4 * (int64_t)num_cu);
+    P.ch = std::max<int64_t>(64, (ch + 63) / 64 * 64);
+    P.nchunk = (n + P.ch - 1) / P.ch;
+    P.tlds = 8 * ((size_t)ncol * (p + 1) + 8 * (size_t)ncol + 1) <= CV_LDS_BYTES;
+    P.cb = P.tlds ? ncol : std::min<int>(ncol, CV_COL_BATCH);
+    P.nlaunch = (ncol + P.cb - 1) / P.cb;
+    P.lds = 8 * (8 * (size_t)P.cb + 1 + (P.tlds ? (size_t)P.cb * (p + 1) : 0));
+    return P;
+}
+
 namespace {
 
 __device__ __forceinline__ double wave_sum(double v)
@@ -116,12 +138,11 @@ int logistic_cv_score_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld,
 {
     hipStream_t s = c->stream;
     const int q = p + 1;
-    int64_t ch = (n + 4 * (int64_t)c->num_cu - 1) / (4 * (int64_t)c->num_cu);
-    ch = std::max<int64_t>(64, (ch + 63) / 64 * 64);
-    const int64_t nchunk = (n + ch - 1) / ch;
+    const CvScorePlan P = cv_score_plan(n, p, ncol, c->num_cu);
+    const int64_t ch = P.ch, nchunk = P.nchunk;
     const size_t tab_f = (size_t)ncol * q;                                               // doubles of a fold's table
-    const bool tlds = 8 * (tab_f + 8 * (size_t)ncol + 1) <= CV_LDS_BYTES;
-    const int cb = tlds ? ncol : std::min<int>(ncol, CV_COL_BATCH);                      // columns per launch
+    const bool tlds = P.tlds;
+    const int cb = P.cb;                                                                 // columns per launch
     const size_t out_f = 8 * (size_t)ncol + 1;
     Bump B;
     const size_t a_tab = B.take(8 * tab_f * nfolds), a_part = B.take(8 * (size_t)nchunk * (8 * (size_t)cb + 1)), a_out = B.take(8 * out_f * nfolds);
@@ -175,6 +196,14 @@ int oemgpu_logistic_cv_score_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, 
     if (p > LOGIT_P_LIMIT) { set_error("logistic_cv_score: p > %d is not supported", LOGIT_P_LIMIT); return OEMGPU_ERR_UNSUPPORTED; }
     if (set_device(c)) return OEMGPU_ERR_HIP;
     return logistic_cv_score_dev(c, x_dev, n, ld, p, y_dev, y_hi, foldid_dev, nfolds, coef, ncol, sums, counts, predmat_dev);
+}
+
+int oemgpu_selftest_cv_score_plan(int64_t n, int32_t p, int32_t ncol, int32_t num_cu, int64_t *out)
+{
+    if (n < 1 || p < 1 || p > LOGIT_P_LIMIT || ncol < 1 || num_cu < 1 || !out) { set_error("selftest_cv_score_plan: bad argument"); return OEMGPU_ERR_ARG; }
+    const CvScorePlan P = cv_score_plan(n, p, ncol, num_cu);
+    out[0] = P.ch; out[1] = P.nchunk; out[2] = P.tlds ? 1 : 0; out[3] = P.cb; out[4] = P.nlaunch; out[5] = (int64_t)P.lds;
+    return 0;
 }
 
 #pragma GCC visibility pop

@@ -1,5 +1,6 @@
-"""cv.oem for binomial fits, the part that needs no GPU: the two C entries are declared, exported and bound; their argument errors
-come back before a device is looked for; the restatement's error terms (tests/cv_logistic_restatement.py) are scikit-learn's; and
+"""cv.oem for binomial fits, the part that needs no GPU: the C entries are declared, exported and bound; their argument errors
+come back before a device is looked for; the scoring entry's launch plan (oemgpu_selftest_cv_score_plan) holds its invariants over
+n, p, ncol and the CU count; the restatement's error terms (tests/cv_logistic_restatement.py) are scikit-learn's; and
 cv_oem(family="binomial") makes oem()'s check of y."""
 import ctypes as C
 import re
@@ -11,7 +12,8 @@ import pytest
 from tests import cv_logistic_restatement as CV
 
 ROOT = Path(__file__).resolve().parent.parent
-NEW = ("oemgpu_fit_logistic_dense_fold_dev", "oemgpu_logistic_cv_score_dev")
+NEW = ("oemgpu_fit_logistic_dense_fold_dev", "oemgpu_logistic_cv_score_dev", "oemgpu_selftest_cv_score_plan")
+LDS_BYTES = 160 << 10          # LDS of a gfx950 CU
 
 
 def test_new_symbols_are_declared_exported_and_bound():
@@ -66,6 +68,90 @@ def test_score_entry_argument_errors_before_any_device():
     assert L.oemgpu_logistic_cv_score_dev(ptr, ptr, 50, 50, 4, ptr, 1.0, ptr, 5, dp, 0, dp, cnt, None) == -1
     assert L.oemgpu_logistic_cv_score_dev(ptr, ptr, 50, 40, 4, ptr, 1.0, ptr, 5, dp, 3, dp, cnt, None) == -1
     assert L.oemgpu_logistic_cv_score_dev(ptr, ptr, 10000, 10000, 8192, ptr, 1.0, ptr, 5, dp, 3, dp, cnt, None) == -4
+
+
+def _score_plan(L, n, p, ncol, num_cu, out=None):
+    out = (C.c_int64 * 6)() if out is None else out
+    assert L.oemgpu_selftest_cv_score_plan(n, p, ncol, num_cu, out) == 0, (n, p, ncol, num_cu)
+    return tuple(out)
+
+
+def _check_score_plan(P, n, p, ncol, num_cu):
+    ch, nchunk, tlds, cb, nlaunch, lds = P
+    assert ch >= 64 and ch % 64 == 0, (P, n, num_cu)
+    assert (nchunk - 1) * ch < n <= nchunk * ch, (P, n, num_cu)
+    assert nchunk <= 4 * num_cu, (P, n, num_cu)
+    assert tlds == (1 if 8 * (ncol * (p + 9) + 1) <= LDS_BYTES else 0), (P, p, ncol)
+    assert 0 < lds <= LDS_BYTES, (P, p, ncol)
+    assert cb >= 1 and cb * nlaunch >= ncol and cb * nlaunch < ncol + cb, (P, p, ncol)
+    if tlds:                                                # the whole table and its accumulators, in one launch
+        assert (cb, nlaunch, lds) == (ncol, 1, 8 * (ncol * (p + 9) + 1)), (P, p, ncol)
+    else:                                                   # the accumulators of a launch's columns alone
+        assert lds == 8 * (8 * cb + 1), (P, p, ncol)
+
+
+@pytest.mark.parametrize("num_cu", [64, 256, 304])
+def test_score_plan_rows(num_cu):
+    """n from 1 to 3e6: the neighbours of every multiple of 64 * 4 * num_cu (where the rows per workgroup grow by a tile), the small n
+    where a workgroup has one tile, and a seeded draw in between"""
+    import oem_amd
+    L = oem_amd.lib()
+    out = (C.c_int64 * 6)()
+    step = 64 * 4 * num_cu
+    ns = set(range(1, 300)) | {3 * 10 ** 6}
+    for m in range(step, 3 * 10 ** 6 + step, step):
+        ns |= {m - 1, m, m + 1, m - 64, m + 64, m + 65}
+    ns |= {int(v) for v in np.random.default_rng(num_cu).integers(1, 3 * 10 ** 6, 3000)}
+    seen = set()
+    for n in sorted(v for v in ns if 1 <= v <= 3 * 10 ** 6):
+        P = _score_plan(L, n, 5, 9, num_cu, out)
+        _check_score_plan(P, n, 5, 9, num_cu)
+        assert P[0] == max(64, -(-(-(-n // (4 * num_cu))) // 64) * 64), (P, n)
+        seen.add(P[0])
+    assert {64, 128, 192} <= seen                           # one tile and several tiles per workgroup were both looked at
+    for n, p, ncol in ((1, 8191, 5000), (3 * 10 ** 6, 1, 1), (step + 1, 200, 98), (step, 200, 97)):      # n and the table do not interact
+        P, Q = _score_plan(L, n, p, ncol, num_cu), _score_plan(L, n, 5, 9, num_cu)
+        _check_score_plan(P, n, p, ncol, num_cu)
+        assert P[:2] == Q[:2]
+
+
+def test_score_plan_table():
+    """p from 1 to 8191 against every ncol from 1 to 5000 (a set of p that holds the ends, the fits' own limits and a seeded draw), and
+    for EVERY p the two ncol on either side of the LDS limit"""
+    import oem_amd
+    L = oem_amd.lib()
+    out = (C.c_int64 * 6)()
+    rng = np.random.default_rng(12)
+    ps = sorted({1, 2, 7, 8, 9, 55, 56, 57, 110, 192, 193, 200, 1023, 1024, 2047, 2048, 2049, 4095, 4096, 6826, 8190, 8191} |
+                {int(v) for v in rng.integers(1, 8192, 24)})
+    for p in ps:
+        for ncol in range(1, 5001):
+            _check_score_plan(_score_plan(L, 1000, p, ncol, 256, out), 1000, p, ncol, 256)
+    both = set()
+    for p in range(1, 8192):
+        edge = (LDS_BYTES // 8 - 1) // (p + 9)              # the most columns whose table fits
+        for ncol in (edge, edge + 1):
+            if 1 <= ncol <= 5000:
+                P = _score_plan(L, 77, p, ncol, 64, out)
+                _check_score_plan(P, 77, p, ncol, 64)
+                assert P[2] == (1 if ncol == edge else 0), (P, p, ncol)
+                both.add(P[2])
+    assert both == {0, 1}
+    assert _score_plan(L, 200, 200, 97, 256)[2:] == (1, 97, 1, 162192)
+    assert _score_plan(L, 200, 200, 98, 256)[2:] == (0, 98, 1, 8 * (8 * 98 + 1))
+    assert _score_plan(L, 130, 8191, 2, 256)[2:] == (1, 2, 1, 8 * (2 * 8200 + 1))
+    assert _score_plan(L, 130, 8191, 3, 256)[2:] == (0, 3, 1, 8 * 25)
+    assert _score_plan(L, 200, 200, 2100, 256)[2:] == (0, 2048, 2, 8 * (8 * 2048 + 1))
+    assert _score_plan(L, 200, 1, 5000, 256)[2:] == (0, 2048, 3, 8 * (8 * 2048 + 1))
+
+
+def test_score_plan_argument_errors():
+    import oem_amd
+    L = oem_amd.lib()
+    out = (C.c_int64 * 6)()
+    for n, p, ncol, num_cu in ((0, 5, 9, 256), (100, 0, 9, 256), (100, 8192, 9, 256), (100, 5, 0, 256), (100, 5, 9, 0)):
+        assert L.oemgpu_selftest_cv_score_plan(n, p, ncol, num_cu, out) == -1
+    assert L.oemgpu_selftest_cv_score_plan(100, 5, 9, 256, None) == -1
 
 
 def _table(seed=0, n=400, p=6, k=7):

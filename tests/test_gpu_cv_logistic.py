@@ -15,6 +15,10 @@ Preconditions are asserted on the restatement, never on the library, and exclude
 `lambda`: lambda_0 = max |s o X'y| / n is a floating-point sum, which the device and numpy take in different orders, so the values are
 held to the restatement's at the dense fit's own 1e-12 (test_gpu_logistic._compare); exact are the number of lambdas that survive the
 trimming, their equality with the full fit's own sequence, nzero, and WHICH element of the sequence lambda.min / lambda.1se are.
+
+tests/test_gpu_cv_logistic_bounds.py takes the same helpers to the limits of both entries: scoring workgroups of more than one tile,
+ld > n, saturated probabilities, both sides of the table-in-LDS limit, the waves' column groups, an empty fold, the kept-row map
+beyond its first tile, poisoned left-out rows and the refusal at equality.
 """
 import numpy as np
 import pytest
@@ -28,9 +32,17 @@ pytestmark = pytest.mark.gpu
 CV_TOL = 7.2e-14         # x (1 + |value|): the first green run's largest difference was 7.2e-16 (fit.preval; cvm / cvsd 2.1e-16)
 
 
-def _dev(x, y, fid):
+def _dev(x, y, fid, pad=0):
+    """x, y, foldid on the device; pad > 0: x is a view of a taller column-major buffer (ld = n + pad) whose rows n .. n + pad - 1 are NaN"""
     import torch
-    xd = torch.as_tensor(np.ascontiguousarray(x.T), device="cuda:0").t()
+    if pad:
+        n, p = x.shape
+        buf = torch.full((p, n + pad), float("nan"), dtype=torch.float64, device="cuda:0")
+        xd = buf.t()[:n]
+        xd.copy_(torch.as_tensor(np.ascontiguousarray(x)))
+        assert xd.stride() == (1, n + pad)
+    else:
+        xd = torch.as_tensor(np.ascontiguousarray(x.T), device="cuda:0").t()
     return xd, torch.as_tensor(np.asarray(y, dtype=np.float64), device="cuda:0"), torch.as_tensor(np.ascontiguousarray(fid, dtype=np.int32), device="cuda:0")
 
 
@@ -58,9 +70,10 @@ def _same(a, b, pens):
     assert a["d"] == b["d"]
 
 
-def _check_folds(x, y, fid, pens, rkw=None, **kw):
-    """every fold of the fold entry against the restatement on the gathered rows; returns the restatement's step counts per fold"""
-    xd, yd, fd = _dev(x, y, fid)
+def _check_folds(x, y, fid, pens, rkw=None, pad=0, fits=None, **kw):
+    """every fold of the fold entry against the restatement on the gathered rows; returns the restatement's step counts per fold.
+    pad: _dev's; fits: a list that receives the fold fits"""
+    xd, yd, fd = _dev(x, y, fid, pad)
     nfolds = int(fid.max())
     stats = []
     for i in range(1, nfolds + 1):
@@ -71,6 +84,8 @@ def _check_folds(x, y, fid, pens, rkw=None, **kw):
         _compare(fit, ref, pens)
         assert fit["nobs"] == int(keep.sum())
         stats.append(st)
+        if fits is not None:
+            fits.append(fit)
     return stats
 
 
@@ -156,8 +171,9 @@ def test_fold_entry_refusals_from_the_device():
 
 
 # ------------------------------------------------------------------------------------------------------------- the scoring entry
-def _numpy_scores(x, y, fid, coef):
-    """sums (nfolds x ncol x 8), counts, predmat (n x ncol) of a coefficient table nfolds x ncol x (p + 1), term by term as R forms them"""
+def _numpy_scores(x, y, fid, coef, over="warn"):
+    """sums (nfolds x ncol x 8), counts, predmat (n x ncol) of a coefficient table nfolds x ncol x (p + 1), term by term as R forms them.
+    over: numpy's errstate for an exp that overflows (a probability of exactly 0)"""
     nfolds, ncol = coef.shape[:2]
     n = x.shape[0]
     ymat = np.column_stack([(y == y.min()).astype(np.float64), (y == y.max()).astype(np.float64)])
@@ -168,7 +184,8 @@ def _numpy_scores(x, y, fid, coef):
     for f in range(nfolds):
         rows = fid == f + 1
         counts[f] = rows.sum()
-        pred[rows] = 1.0 / (1.0 + np.exp(-(x1[rows] @ coef[f].T)))
+        with np.errstate(over=over):
+            pred[rows] = 1.0 / (1.0 + np.exp(-(x1[rows] @ coef[f].T)))
         for t, name in enumerate(("deviance", "class", "mse", "mae")):
             raw = CV.raw_errors(ymat[rows], pred[rows], name)
             sums[f, :, 2 * t] = raw.sum(axis=0)
@@ -176,11 +193,13 @@ def _numpy_scores(x, y, fid, coef):
     return sums, counts, pred
 
 
-def _check_scores(x, y, fid, coef):
+def _check_scores(x, y, fid, coef, pad=0, over="warn"):
+    """the scoring entry against numpy, twice for the same bits, and without predmat; pad: _dev's; over: _numpy_scores'.  Returns what the
+    entry gave and what numpy gave: (sums, counts, predmat), (sums, counts, predmat)"""
     from oem_amd import api
-    xd, yd, fd = _dev(x, y, fid)
+    xd, yd, fd = _dev(x, y, fid, pad)
     nfolds = coef.shape[0]
-    ref_sums, ref_counts, ref_pred = _numpy_scores(x, y, fid, coef)
+    ref_sums, ref_counts, ref_pred = _numpy_scores(x, y, fid, coef, over)
     gap = np.abs(ref_pred - 0.5).min()
     print("min |prob - 0.5| =", gap)
     assert gap > 1e-7
@@ -195,11 +214,13 @@ def _check_scores(x, y, fid, coef):
     assert sums.tobytes() == sums2.tobytes() and counts.tobytes() == counts2.tobytes() and pred.tobytes() == pred2.tobytes()
     sums3, counts3, none = api.logistic_cv_score(xd, yd, fd, nfolds, coef)              # without predmat: the same sums
     assert none is None and sums.tobytes() == sums3.tobytes() and counts.tobytes() == counts3.tobytes()
+    return (sums, counts, pred), (ref_sums, ref_counts, ref_pred)
 
 
-def _interpolated_table(x, y, fid, **kw):
-    """the table cv.oem scores with: the restatement's fold fits interpolated onto its full fit's lambdas"""
-    fit0, outlist = CV.fits(x, y, fid, penalty=["lasso"], **kw)
+def _interpolated_table(x, y, fid, fitted=None, **kw):
+    """the table cv.oem scores with: the restatement's fold fits interpolated onto its full fit's lambdas (fitted: CV.fits of the same
+    arguments, where a test has them already)"""
+    fit0, outlist = fitted if fitted is not None else CV.fits(x, y, fid, penalty=["lasso"], **kw)
     lam = np.asarray(fit0["lambda"][0])
     s = lam[lam >= max(np.min(o["lambda"][0]) for o in outlist)]
     coef = np.empty((len(outlist), len(s), x.shape[1] + 1))
@@ -221,18 +242,27 @@ def test_scoring_entry_on_the_cv_tables(case):
     _check_scores(x, y, fid, coef)
 
 
+def _case_c_rows(nrow):
+    """the first nrow rows of case c (p = 200, three folds)"""
+    x, y = _data(1500, 200, 31)
+    fid = np.random.default_rng(6).permutation(np.resize(np.arange(1, 4), 1500))
+    fid[640:768] = 2
+    return np.asfortranarray(x[:nrow]), y[:nrow], fid[:nrow]
+
+
+def _sparse_table(seed, nfolds, ncol, q, density=0.1):
+    """a coefficient table with about `density` of its entries set, growing from column to column"""
+    rng = np.random.default_rng(seed)
+    return rng.normal(size=(nfolds, ncol, q)) * (rng.uniform(size=(nfolds, ncol, q)) < density) * np.linspace(0.02, 0.6, ncol)[None, :, None]
+
+
 @pytest.mark.parametrize("nrow,ncol,seed", [(1500, 9, 8), (200, 2100, 9)])
 def test_scoring_entry_table_in_lds_and_through_the_cache(nrow, ncol, seed):
     """p = 200: nine columns sit in LDS (with a last column group of one); 2100 columns (3.4 MB a fold) are read through the cache, in two
     launches of at most 2048 columns per fold.  The wide table is scored on the first 200 rows (four chunks, the last one short): of
     the 420 000 probabilities of this seed the nearest to 0.5 is 4.2e-7 away (checked on the CPU; the precondition asserts it)"""
-    x, y = _data(1500, 200, 31)
-    fid = np.random.default_rng(6).permutation(np.resize(np.arange(1, 4), 1500))
-    fid[640:768] = 2
-    x, y, fid = np.asfortranarray(x[:nrow]), y[:nrow], fid[:nrow]
-    rng = np.random.default_rng(seed)
-    coef = rng.normal(size=(3, ncol, 201)) * (rng.uniform(size=(3, ncol, 201)) < 0.1) * np.linspace(0.02, 0.6, ncol)[None, :, None]
-    _check_scores(x, y, fid, coef)
+    x, y, fid = _case_c_rows(nrow)
+    _check_scores(x, y, fid, _sparse_table(seed, 3, ncol, 201))
 
 
 # ------------------------------------------------------------------------------------------------------------- end to end
@@ -253,24 +283,24 @@ def _rel(a, b):
     return float(np.max(np.abs(a[ok] - b[ok]) / (1.0 + np.abs(b[ok])))) if ok.any() else 0.0
 
 
-@pytest.mark.parametrize("grouped", [True, False])
-@pytest.mark.parametrize("measure", ["deviance", "class", "mse", "mae", "auc"])
-def test_cv_oem_binomial_end_to_end(measure, grouped):
+def _check_cv_oem(E, measure, grouped, **kw):
+    """cv_oem(family="binomial") on E's x, y and foldid against the restatement, with its preconditions; kw: the fit's options, those of
+    E["fitted"].  Returns the restatement's result"""
     import oem_amd
-    E = _e2e_reference()
-    ref = CV.cv(E["x"], E["y"], E["fid"], penalty=["lasso"], nlambda=20, type_measure=measure, grouped=grouped, fitted=E["fitted"])
+    nfolds = int(E["fid"].max())
+    ref = CV.cv(E["x"], E["y"], E["fid"], penalty=["lasso"], type_measure=measure, grouped=grouped, fitted=E["fitted"], **kw)
     crit = np.sort(-ref["cvm"][0] if measure == "auc" else ref["cvm"][0])
     if measure == "class":
         crit = np.unique(crit)
     assert (crit[1] - crit[0]) > 1e-5 * abs(crit[0]), crit[:3]
     if measure == "auc":
         pv = ref["fit.preval"][0]
-        for i in range(1, 6):
+        for i in range(1, nfolds + 1):
             for j in range(pv.shape[1]):
                 col = pv[E["fid"] == i, j]
                 assert np.isnan(col).all() or len(np.unique(col)) == len(col)
-    got = oem_amd.cv_oem(E["x"], E["y"], family="binomial", penalty="lasso", nlambda=20, type_measure=measure, grouped=grouped,
-                         foldid=E["fid"], keep=True)
+    got = oem_amd.cv_oem(E["x"], E["y"], family="binomial", penalty="lasso", type_measure=measure, grouped=grouped, foldid=E["fid"], keep=True,
+                         **kw)
     assert got["name"] == ref["name"] and got["penalty"] == ["lasso"] and got["best.model"] == "lasso"
     assert isinstance(got["oem.fit"], oem_amd.OemFitBinomial)
     lam_g, lam_r = np.asarray(got["lambda"][0]), np.asarray(ref["lambda"][0])
@@ -286,6 +316,13 @@ def test_cv_oem_binomial_end_to_end(measure, grouped):
     for key in ("lambda.min", "lambda.1se"):                                            # the same element of the sequence
         assert got[key] == lam_g[int(np.nonzero(lam_r == ref[key])[0][0])], key
     assert got["model.min"] == ref["model.min"]
+    return ref
+
+
+@pytest.mark.parametrize("grouped", [True, False])
+@pytest.mark.parametrize("measure", ["deviance", "class", "mse", "mae", "auc"])
+def test_cv_oem_binomial_end_to_end(measure, grouped):
+    _check_cv_oem(_e2e_reference(), measure, grouped, nlambda=20)
 
 
 def test_cv_oem_binomial_consumers_and_a_device_x():
