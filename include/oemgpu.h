@@ -253,6 +253,29 @@ int oemgpu_xval_cv_triples_dev(oemgpu_ctx *ctx, int64_t n_local, int32_t p, int3
                                const oemgpu_opts *o, double *triples);
 int oemgpu_xval_merge(const double *triples, int32_t nsets, const oemgpu_opts *o, double *cvm, double *cvsd);
 
+/* Test infrastructure (tests/test_gpu_xval_bounds.py): phase 3 of oemgpu_xval_dense_dev -- the cross-validation error -- on a coefficient
+ * table of the caller's instead of fitted ones.  x_dev (n x p, leading dimension ld >= n), y_dev, weights_dev (or NULL) and foldid_dev
+ * (1 .. nfolds) on the context's device; coef (host): [nfolds][npen][nl][p + 1], slot 0 the intercept, the table of fold k scoring the
+ * rows of fold k.  The rows go through the same fold layout, gather and weight scaling, and the same launch, as in oemgpu_xval_dense_dev.
+ * With v_i = (y_i - b_0 - x_i . b)^2 (type_measure 0) or |.| (1), times w_i with weights: triples == NULL: cvm[npen][nl] <- mean v,
+ * cvsd[npen][nl] <- sqrt(sum (v - cvm)^2 / (n - 1)) / sqrt(n); else triples[npen][nl][3] <- (n, mean, sum (v - mean)^2) and cvm / cvsd
+ * are left alone (they may be NULL).  No fit, no options, no "ols" masking, and n <= p is allowed.  The checks of oemgpu_xval_dense_dev on
+ * nfolds (2..512), type_measure, n and ld apply (OEMGPU_ERR_ARG before a device is looked for, like NULL pointers and p, npen, nl < 1);
+ * a fold id outside 1 .. nfolds is OEMGPU_ERR_ARG from the device. */
+int oemgpu_selftest_xval_cv_error_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                                      const double *weights_dev /* or NULL */, const int32_t *foldid_dev, int32_t nfolds,
+                                      const double *coef, int32_t npen, int32_t nl, int32_t type_measure, double *cvm, double *cvsd,
+                                      double *triples /* or NULL */);
+/* Host-only plan of the CV-error launch (xval.hip: cv_error_plan; pure arithmetic, runs without a GPU; the launch takes its shape from
+ * the same function) for n rows, p columns, nfolds folds, npen penalties and nl lambdas on a device of num_cu CUs: out[0] lt = 16-lambda
+ * tiles per pass (1..7: all ceil(nl / 16) tiles when there are <= 7, else the fewest passes of at most 7 made even), out[1] passes,
+ * out[2] form: 0 SINGLE (the (p + 1 rounded up to 4) x 16 lt coefficient tile of a pass fits 140 KB of LDS and p + 1 <= 56: a lane holds
+ * a row's fragments at once), 1 multi (fits, p + 1 > 56), 2 CHUNK (does not fit: 112 coefficient rows at a time), out[3] dynamic LDS
+ * bytes, out[4] coefficient chunks (1 unless CHUNK), out[5] coefficient rows of the last chunk (a multiple of 4), out[6] workgroups per
+ * (fold, penalty): floor(num_cu / (nfolds npen)), at most ceil(floor(n / nfolds) / 128), at least 1.
+ * OEMGPU_ERR_ARG for non-positive arguments, nfolds outside 2..512 or a NULL out. */
+int oemgpu_selftest_xval_cv_plan(int64_t n, int32_t p, int32_t nfolds, int32_t npen, int32_t nl, int32_t num_cu, int64_t *out /* 7 */);
+
 /* The eigenvalue step of the most recent solve (or oemgpu_eig_max_dev) on this context: *steps = Lanczos steps taken, *capped = 1
  * if the recurrence ran into its step cap (min(2 q, 288) for q <= 288, 256 / 512 on the larger engines) instead of stopping by its
  * rule or by breakdown -- d = 1.005 x the last Ritz value is then a lower estimate (the reference's Spectra call, tol 1e-10 and up

@@ -732,6 +732,38 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
 
 
 
+def xval_cv_plan(n, p, nfolds, npen, nl, num_cu):
+    """oemgpu_selftest_xval_cv_plan (needs no GPU): where the CV-error launch of xval.oem lands for this shape, as a dict -- lt (16-lambda
+    tiles per pass), passes, form ("single" / "multi" / "chunk"), lds (dynamic bytes), chunks and last (coefficient chunks, rows of the
+    last one) and nwg (workgroups per fold and penalty)."""
+    out = (C.c_int64 * 7)()
+    L.check(L.lib().oemgpu_selftest_xval_cv_plan(int(n), int(p), int(nfolds), int(npen), int(nl), int(num_cu), out))
+    lt, passes, form, lds, chunks, last, nwg = list(out)
+    return dict(lt=lt, passes=passes, form=("single", "multi", "chunk")[form], lds=lds, chunks=chunks, last=last, nwg=nwg)
+
+
+def xval_cv_error(x, y, foldid, nfolds, coef, type_measure="mse", weights=None, triples=False, ctx=None):
+    """oemgpu_selftest_xval_cv_error_dev (test infrastructure): the CV-error phase of xval.oem on a coefficient table of the caller's.
+    x: a column-major float64 matrix on a GPU; y (float64), foldid (int32, 1 .. nfolds) and weights (float64 or None): device tensors;
+    coef: nfolds x npen x nl x (p + 1) on the host, slot 0 the intercept.  Returns (cvm, cvsd), npen x nl each, or with triples=True the
+    npen x nl x 3 array of (count, mean, M2)."""
+    import torch
+    xp, n, p, ld, keepalive = _device_matrix(x)
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    if coef.ndim != 4 or coef.shape[0] != int(nfolds) or coef.shape[3] != p + 1:
+        raise ValueError("coef must be nfolds x npen x nl x (p + 1)")
+    npen, nl = coef.shape[1:3]
+    tm = {"mse": 0, "mae": 1}[type_measure]
+    cvm = np.full((npen, nl), np.nan); cvsd = np.full((npen, nl), np.nan)
+    tri = np.full((npen, nl, 3), np.nan) if triples else None
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_selftest_xval_cv_error_dev(ctx if ctx is not None else context(x.device.index), xp, n, ld, p, y.data_ptr(),
+                                                      None if weights is None else weights.data_ptr(), foldid.data_ptr(), int(nfolds),
+                                                      _dptr(coef), npen, nl, tm, _dptr(cvm), _dptr(cvsd), None if tri is None else _dptr(tri)))
+    del keepalive
+    return tri if triples else (cvm, cvsd)
+
+
 # ------------------------------------------------------------------------------------------ cv.oem()
 def logistic_cv_score(x, y, foldid, nfolds, coef, y_hi=None, predmat=False):
     """oemgpu_logistic_cv_score_dev: the error terms of cv.oemfit_binomial (R/cv_oem.R:315-327) over the held-out rows of a resident x.

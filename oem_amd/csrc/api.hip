@@ -2033,7 +2033,8 @@ static int ctx_aux(oemgpu_ctx *c, size_t bytes)
 //   cverr    per-observation error of the LOCAL rows, merged to (count, mean, M2) per (penalty, lambda)
 struct XvalLay {
     int64_t n, ldp;
-    int p, pm, K, npen, nl, nwg;
+    int p, pm, K, npen, nl;
+    CvErrPlan cv;                                                 // the CV-error launch of phase 3 (xval.hip: cv_error_plan)
     bool weighted;
     size_t mlen, cslen;
     GramPlan plmax;
@@ -2048,7 +2049,7 @@ static XvalLay xval_layout(oemgpu_ctx *c, int64_t n, int p, int K, int npen, int
     // kernels see pm = p + 1 data columns and their Gram IS X'WX with its intercept border (ref src/oem_xval_dense.h:486-623)
     L.pm = p + (weighted ? 1 : 0);
     L.mlen = (size_t)oemgpu_moments_len(L.pm); L.cslen = (size_t)p + 1;
-    L.nwg = cv_wg_per_fold(n, K, npen, c->num_cu);
+    L.cv = cv_error_plan(n, p, K, npen, nl, c->num_cu);
     L.plmax = gram_plan_bound(n, L.pm, c->num_cu);             // holds the moment plan of every fold
     Bump A;
     L.a_cs = A.take(sizeof(double) * L.cslen * (2 * (size_t)K + 1));      // per fold, then all folds / all but fold ff
@@ -2058,10 +2059,20 @@ static XvalLay xval_layout(oemgpu_ctx *c, int64_t n, int p, int K, int npen, int
     L.a_mc = A.take(sizeof(double) * L.mlen); L.a_ms = A.take(sizeof(double) * L.mlen * (K + 1));
     L.a_t = A.take(L.plmax.tpart_doubles * 8); L.a_v = A.take(L.plmax.vpart_doubles * 8);
     L.a_b = A.take(sizeof(double) * (size_t)K * npen * nl * (p + 1));
-    L.a_part = A.take(sizeof(double) * cv_part_doubles(L.nwg, K, npen, nl)); L.a_out = A.take(sizeof(double) * 3 * (size_t)npen * nl);
+    L.a_part = A.take(sizeof(double) * cv_part_doubles(L.cv.nwg, K, npen, nl)); L.a_out = A.take(sizeof(double) * 3 * (size_t)npen * nl);
     L.a_peer = A.take(sizeof(double) * (L.mlen + L.cslen) * K);            // another device's fold moments on their way into the sum
     L.total = A.off;
     return L;
+}
+
+// what every phase needs of the rows and folds, whether or not it fits anything
+static int xval_check_rows(int64_t n, int64_t ld, int K, int type_measure)
+{
+    if (K < 2 || K > 512) { set_error("xval_dense: nfolds must be in 2..512"); return OEMGPU_ERR_ARG; }
+    if (type_measure != 0 && type_measure != 1) { set_error("xval_dense: type_measure must be 0 (mse) or 1 (mae)"); return OEMGPU_ERR_ARG; }
+    if (n < 1 || ld < n) { set_error("xval_dense: bad n / ld"); return OEMGPU_ERR_ARG; }
+    if (n + 16 * (int64_t)K >= (int64_t)1 << 31) { set_error("xval_dense: n too large for 32-bit row positions"); return OEMGPU_ERR_UNSUPPORTED; }
+    return 0;
 }
 
 static int xval_check(oemgpu_ctx *c, const void *x_dev, const void *y_dev, const void *foldid_dev, int64_t n, int64_t ld, int p, int K,
@@ -2073,10 +2084,8 @@ static int xval_check(oemgpu_ctx *c, const void *x_dev, const void *y_dev, const
         int rc = check_opts(o, p, p + (intercept ? 1 : 0));
         if (rc) return rc;
     } else if (!o->penalty || o->npen < 1) { set_error("xval_dense: no penalty"); return OEMGPU_ERR_ARG; }
-    if (K < 2 || K > 512) { set_error("xval_dense: nfolds must be in 2..512"); return OEMGPU_ERR_ARG; }
-    if (type_measure != 0 && type_measure != 1) { set_error("xval_dense: type_measure must be 0 (mse) or 1 (mae)"); return OEMGPU_ERR_ARG; }
-    if (n < 1 || ld < n) { set_error("xval_dense: bad n / ld"); return OEMGPU_ERR_ARG; }
-    if (n + 16 * (int64_t)K >= (int64_t)1 << 31) { set_error("xval_dense: n too large for 32-bit row positions"); return OEMGPU_ERR_UNSUPPORTED; }
+    int rc = xval_check_rows(n, ld, K, type_measure);
+    if (rc) return rc;
     if (weighted && o->compute_loss) {
         set_error("compute.loss with observation weights: the reference's loss is the unweighted residual sum (src/oem_xval_dense.h:1122-1145), "
                   "which the weighted Gram does not hold");
@@ -2237,7 +2246,7 @@ static int xval_cverr(oemgpu_ctx *c, const XvalLay &L, int32_t type_measure, con
     int64_t *fold_n = (int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
     double *xp = (double *)(ax + L.a_xp), *yp = (double *)(ax + L.a_yp), *bdev = (double *)(ax + L.a_b);
     double *part = (double *)(ax + L.a_part), *cvout = (double *)(ax + L.a_out);
-    int rc = launch_cv_error(c->stream, xp, L.ldp, yp, fold_start, fold_n, K, p, bdev, npen, nl, type_measure, L.weighted ? 1 : 0, L.nwg, (double)L.n,
+    int rc = launch_cv_error(c->stream, xp, L.ldp, yp, fold_start, fold_n, K, p, bdev, npen, nl, type_measure, L.weighted ? 1 : 0, L.cv, (double)L.n,
                              part, cvout, triples != nullptr);
     if (rc) return rc;
     const int per = triples ? 3 : 2;
@@ -2334,6 +2343,42 @@ int oemgpu_xval_cv_triples_dev(oemgpu_ctx *c, int64_t n_local, int32_t p, int32_
     const XvalLay L = xval_layout(c, n_local, p, nfolds, o->npen, nl_of(o), weighted != 0);
     if (c->aux_bytes < L.total) { set_error("xval_cv_triples: call the first two phases with the same arguments first"); return OEMGPU_ERR_ARG; }
     return xval_cverr(c, L, type_measure, o, nullptr, nullptr, triples);
+}
+
+// Test infrastructure: phase 3 alone on a coefficient table of the caller's -- the layout, the fold-ordered (and weight-scaled) copy
+// and the launch are those of oemgpu_xval_dense_dev (xval_layout, xval_prepare, launch_cv_error); nothing is fitted, so n <= p is fine.
+int oemgpu_selftest_xval_cv_error_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                                      const double *w_dev, const int32_t *foldid_dev, int32_t nfolds, const double *coef, int32_t npen,
+                                      int32_t nl, int32_t type_measure, double *cvm, double *cvsd, double *triples)
+{
+    if (!c || !x_dev || !y_dev || !foldid_dev || !coef || (!triples && (!cvm || !cvsd))) {
+        set_error("selftest_xval_cv_error: NULL argument"); return OEMGPU_ERR_ARG;
+    }
+    if (p < 1 || npen < 1 || nl < 1) { set_error("selftest_xval_cv_error: bad p, npen or nl"); return OEMGPU_ERR_ARG; }
+    const int K = nfolds;
+    int rc = xval_check_rows(n, ld, K, type_measure);
+    if (rc) return rc;
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const XvalLay L = xval_layout(c, n, p, K, npen, nl, w_dev != nullptr);
+    if (ctx_aux(c, L.total)) return OEMGPU_ERR_HIP;
+    std::vector<int64_t> hf;
+    rc = xval_prepare(c, L, x_dev, ld, y_dev, w_dev, foldid_dev, hf);
+    if (rc) return rc;
+    char *ax = c->aux;
+    int64_t *fold_n = (int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
+    double *cvout = (double *)(ax + L.a_out);
+    OEM_HIP(hipMemcpyAsync(ax + L.a_b, coef, sizeof(double) * (size_t)K * npen * nl * (p + 1), hipMemcpyHostToDevice, c->stream));
+    rc = launch_cv_error(c->stream, (const double *)(ax + L.a_xp), L.ldp, (const double *)(ax + L.a_yp), fold_start, fold_n, K, p,
+                         (const double *)(ax + L.a_b), npen, nl, type_measure, L.weighted ? 1 : 0, L.cv, (double)L.n, (double *)(ax + L.a_part),
+                         cvout, triples != nullptr);
+    if (rc) return rc;
+    const size_t nk = (size_t)npen * nl;
+    std::vector<double> hc((triples ? 3 : 2) * nk);
+    OEM_HIP(hipMemcpyAsync(hc.data(), cvout, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, c->stream));
+    OEM_HIP(hipStreamSynchronize(c->stream));                   // coef and hc are the caller's and a local
+    if (triples) { memcpy(triples, hc.data(), sizeof(double) * hc.size()); return 0; }
+    for (size_t ki = 0; ki < nk; ++ki) { cvm[ki] = hc[2 * ki]; cvsd[ki] = hc[2 * ki + 1]; }
+    return 0;
 }
 
 // (count, mean, M2) of the union of `nsets` row sets per (penalty, lambda) by Chan, Golub & LeVeque's update, in set order; then

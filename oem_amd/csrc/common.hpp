@@ -106,10 +106,19 @@ int launch_fold_layout(hipStream_t s, const int *foldid, int64_t n, int K, int *
 int launch_gather_rows(hipStream_t s, const double *x, int64_t n, int64_t ld, int p, const double *y, const int *pos,
                        double *xo, int64_t ldo, double *yo);
 int launch_fold_sum(hipStream_t s, const double *M, int K, size_t len, int skip /* 1-based, 0: none */, double *out);
-int cv_wg_per_fold(int64_t n, int K, int npen, int num_cu);
+// the shape of the CV-error launch (xval.hip: cv_error_plan; pure host arithmetic): K4 = p + 1 rounded up to a k-step of 4, ntile 16-lambda
+// tiles in `passes` passes of lt each, form CV_FORM_*, lds dynamic bytes, the coefficient rows in `chunks` LDS chunks of which the last
+// holds `last` (chunks = 1, last = K4 unless CHUNK), nwg workgroups per fold
+enum { CV_FORM_SINGLE = 0, CV_FORM_MULTI = 1, CV_FORM_CHUNK = 2 };
+struct CvErrPlan {
+    int K4, ntile, lt, passes, form, chunks, last, nwg;
+    size_t lds;
+};
+CvErrPlan cv_error_plan(int64_t n, int p, int K, int npen, int nl, int num_cu);
 size_t cv_part_doubles(int nwg, int K, int npen, int nl);
 int launch_cv_error(hipStream_t s, const double *xp, int64_t ldp, const double *yp, const int64_t *fold_start, const int64_t *fold_n,
-                    int K, int p, const double *B, int npen, int nl, int mae, int wmode, int nwg, double n, double *part, double *out, bool triples = false);
+                    int K, int p, const double *B, int npen, int nl, int mae, int wmode, const CvErrPlan &P, double n, double *part, double *out,
+                    bool triples = false);
 // observation weights of xval.oem (ref src/oem_xval_dense.h:486-623): unweighted column sums of squares per fold, then the
 // fold-ordered copy times sqrt(w); and the weighted counterpart of launch_finalize
 int launch_weight_scale(hipStream_t s, double *xp, int64_t ldp, double *yp, int p, int K, const int64_t *fold_start, const int64_t *fold_n,

@@ -184,7 +184,9 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // over the chunks, and the chunk is staged again (from L2: the K x npen x nl x (p + 1) coefficients are a few MB) for every round.
 // X is still read ONCE per pass over the lambdas, and p has no limit: the traffic added is 16 LT / 128 bytes of L2 per byte of X.
 constexpr int CVW = 8;                   // waves per workgroup
-constexpr int CV_KCH = 112;              // coefficient rows per LDS chunk (CHUNK): two fragment loads of KC = 14 k-steps
+constexpr int CV_KC = 14;                // k-steps of X fragments a lane holds at once
+constexpr int CV_KCH = 8 * CV_KC;        // coefficient rows per LDS chunk (CHUNK): two fragment loads of KC = 14 k-steps
+constexpr size_t CV_LDS_MAX = 140 * 1024;   // the coefficient tile of a pass stays in LDS up to here
 template <int LT, int KC, bool SINGLE, bool CHUNK>
 __global__ __launch_bounds__(64 * CVW) void cv_error_kernel(const double *__restrict__ xp, int64_t ldp, const double *__restrict__ yp,
                                                             const int64_t *__restrict__ fold_start, const int64_t *__restrict__ fold_n,
@@ -428,19 +430,39 @@ int launch_fold_sum(hipStream_t s, const double *M, int K, size_t len, int skip,
     return 0;
 }
 
-// workgroups per fold for the CV pass.  One workgroup fills a CU (LDS), and all of them carry the same work: the grid must not
-// exceed the CU count by a few (260 workgroups on 256 CUs take two rounds), so round DOWN.
-int cv_wg_per_fold(int64_t n, int K, int npen, int num_cu)
+// The host plan of the CV-error launch, the ONE place its shape is decided (launch_cv_error and oemgpu_selftest_xval_cv_plan read it).
+//   workgroups per fold: one workgroup fills a CU (LDS), and all of them carry the same work: the grid must not exceed the CU count
+//     by a few (260 workgroups on 256 CUs take two rounds), so round DOWN;
+//   lambdas per pass: at most 7 16-wide tiles (accumulator registers), in even passes; all of them in one pass whenever there are
+//     <= 112 lambdas, so that X is read once;
+//   form: the coefficient tile of those lambdas stays in LDS for the whole pass when it fits 140 KB (SINGLE when a lane holds all
+//     the k-steps of a row at once, p + 1 <= 56); beyond that (p + 1 > ~160 at 100 lambdas) it goes through LDS in chunks of CV_KCH
+//     rows (CHUNK above) -- no limit on p (this used to shrink the lambda tile instead, re-reading X up to seven times, and to
+//     refuse p > 1,183).
+CvErrPlan cv_error_plan(int64_t n, int p, int K, int npen, int nl, int num_cu)
 {
+    CvErrPlan P;
+    P.K4 = (p + 1 + 3) & ~3;
+    P.ntile = (nl + 15) >> 4;
+    int lt = P.ntile < 7 ? P.ntile : 7;
+    if (P.ntile > lt) { const int np_ = (P.ntile + lt - 1) / lt; lt = (P.ntile + np_ - 1) / np_; }   // even passes
+    P.lt = lt;
+    P.passes = (P.ntile + lt - 1) / lt;                                                  // the kernel's loop over l0
+    const bool chunk = (size_t)P.K4 * 16 * lt * sizeof(double) > CV_LDS_MAX;
+    P.form = chunk ? CV_FORM_CHUNK : (P.K4 / 4 <= CV_KC ? CV_FORM_SINGLE : CV_FORM_MULTI);
+    P.lds = (size_t)(chunk ? CV_KCH : P.K4) * 16 * lt * sizeof(double);
+    P.chunks = chunk ? (P.K4 + CV_KCH - 1) / CV_KCH : 1;
+    P.last = P.K4 - (P.chunks - 1) * CV_KCH;
     int nwg = num_cu / (K * npen);
     const int64_t tiles = (n / K + 16 * CVW - 1) / (16 * CVW);
     if (nwg > tiles) nwg = (int)tiles;
-    return nwg < 1 ? 1 : nwg;
+    P.nwg = nwg < 1 ? 1 : nwg;
+    return P;
 }
 size_t cv_part_doubles(int nwg, int K, int npen, int nl) { return (size_t)nwg * K * CVW * npen * ((nl + 15) & ~15) * 4; }
 
 template <int LT>
-static int launch_cv_lt(hipStream_t s, dim3 grid, size_t lds, int ksteps, bool chunk, const double *xp, int64_t ldp, const double *yp,
+static int launch_cv_lt(hipStream_t s, dim3 grid, size_t lds, int form, const double *xp, int64_t ldp, const double *yp,
                         const int64_t *fold_start, const int64_t *fold_n, int p, const double *B, int nl, int mae, int wmode, double *part)
 {
 #define OEM_CVK(KC, SINGLE, CHUNK)                                                                                                   \
@@ -448,38 +470,27 @@ static int launch_cv_lt(hipStream_t s, dim3 grid, size_t lds, int ksteps, bool c
         OEM_HIP(hipFuncSetAttribute((const void *)cv_error_kernel<LT, KC, SINGLE, CHUNK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
         hipLaunchKernelGGL((cv_error_kernel<LT, KC, SINGLE, CHUNK>), grid, dim3(64 * CVW), lds, s, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part); \
     } while (0)
-    if (chunk) OEM_CVK(14, false, true);
-    else if (ksteps <= 14) OEM_CVK(14, true, false);
-    else OEM_CVK(14, false, false);   // 28 fragments at once spill next to 7 accumulator tiles
+    if (form == CV_FORM_CHUNK) OEM_CVK(CV_KC, false, true);
+    else if (form == CV_FORM_SINGLE) OEM_CVK(CV_KC, true, false);
+    else OEM_CVK(CV_KC, false, false);   // 28 fragments at once spill next to 7 accumulator tiles
 #undef OEM_CVK
     OEM_HIP(hipGetLastError());
     return 0;
 }
 
 int launch_cv_error(hipStream_t s, const double *xp, int64_t ldp, const double *yp, const int64_t *fold_start, const int64_t *fold_n,
-                    int K, int p, const double *B, int npen, int nl, int mae, int wmode, int nwg, double n, double *part, double *out, bool triples)
+                    int K, int p, const double *B, int npen, int nl, int mae, int wmode, const CvErrPlan &P, double n, double *part, double *out,
+                    bool triples)
 {
-    const int K4 = (p + 1 + 3) & ~3, ntile = (nl + 15) >> 4;
-    // lambdas per pass: at most 7 16-wide tiles (accumulator registers), in even passes; all of them in one pass whenever there are
-    // <= 112 lambdas, so that X is read once.  The coefficient tile of those lambdas stays in LDS for the whole pass when it fits
-    // 140 KB; beyond that (p + 1 > ~160 at 100 lambdas) it goes through LDS in chunks of CV_KCH rows (CHUNK above) -- no limit on p
-    // (this used to shrink the lambda tile instead, re-reading X up to seven times, and to refuse p > 1,183).
-    int lt = ntile < 7 ? ntile : 7;
-    if (ntile > lt) lt = (ntile + (ntile + lt - 1) / lt - 1) / ((ntile + lt - 1) / lt);      // even passes
-    const bool chunk = (size_t)K4 * 16 * lt * sizeof(double) > 140 * 1024;
-    const size_t lds = (size_t)(chunk ? CV_KCH : K4) * 16 * lt * sizeof(double);
+    const int nwg = P.nwg;
     dim3 grid(nwg, K, npen);
     int rc;
-    switch (lt) {
-    case 1: rc = launch_cv_lt<1>(s, grid, lds, K4 / 4, chunk, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part); break;
-    case 2: rc = launch_cv_lt<2>(s, grid, lds, K4 / 4, chunk, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part); break;
-    case 3: rc = launch_cv_lt<3>(s, grid, lds, K4 / 4, chunk, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part); break;
-    case 4: rc = launch_cv_lt<4>(s, grid, lds, K4 / 4, chunk, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part); break;
-    case 5: rc = launch_cv_lt<5>(s, grid, lds, K4 / 4, chunk, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part); break;
-    case 6: rc = launch_cv_lt<6>(s, grid, lds, K4 / 4, chunk, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part); break;
-    case 7: rc = launch_cv_lt<7>(s, grid, lds, K4 / 4, chunk, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part); break;
+#define OEM_CVLT(LT) case LT: rc = launch_cv_lt<LT>(s, grid, P.lds, P.form, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part); break
+    switch (P.lt) {
+    OEM_CVLT(1); OEM_CVLT(2); OEM_CVLT(3); OEM_CVLT(4); OEM_CVLT(5); OEM_CVLT(6); OEM_CVLT(7);
     default: return OEMGPU_ERR_INTERNAL;
     }
+#undef OEM_CVLT
     if (rc) return rc;
     hipLaunchKernelGGL(cv_finish_kernel, dim3(npen * nl), dim3(64), 0, s, part, nwg * K * CVW, npen, nl, n, out, triples ? 1 : 0);
     OEM_HIP(hipGetLastError());
@@ -487,3 +498,20 @@ int launch_cv_error(hipStream_t s, const double *xp, int64_t ldp, const double *
 }
 
 }  // namespace oemgpu
+
+using namespace oemgpu;
+
+extern "C" {
+#pragma GCC visibility push(default)
+
+int oemgpu_selftest_xval_cv_plan(int64_t n, int32_t p, int32_t nfolds, int32_t npen, int32_t nl, int32_t num_cu, int64_t *out)
+{
+    if (n < 1 || p < 1 || npen < 1 || nl < 1 || num_cu < 1 || !out) { set_error("selftest_xval_cv_plan: bad argument"); return OEMGPU_ERR_ARG; }
+    if (nfolds < 2 || nfolds > 512) { set_error("selftest_xval_cv_plan: nfolds must be in 2..512"); return OEMGPU_ERR_ARG; }
+    const CvErrPlan P = cv_error_plan(n, p, nfolds, npen, nl, num_cu);
+    out[0] = P.lt; out[1] = P.passes; out[2] = P.form; out[3] = (int64_t)P.lds; out[4] = P.chunks; out[5] = P.last; out[6] = P.nwg;
+    return 0;
+}
+
+#pragma GCC visibility pop
+}
