@@ -447,6 +447,40 @@ int oemgpu_fit_logistic_sparse(int64_t n, int32_t p, const int64_t *colptr, cons
  * bytes of the fit's data stages, out[3] the bound out[2] stays within, out[4] rows per tile (0 on the compressed-column route),
  * out[5] workgroups of the row pass, out[6] rows per row-pass workgroup, out[7] 8192-row chunks of the compressed-column kernels. */
 int oemgpu_selftest_logistic_sparse_plan(int64_t n, int32_t p, int64_t nnz, int32_t intercept, int32_t num_cu, int64_t *out /* 8 */);
+/* A sparse x resident on the context's device, for cv.oem on a dgCMatrix (ref R/cv_oem.R:105-175: one oem() on x, then K on
+ * x[!which, , drop = FALSE]; R/oem.R:603-624 sends each to oem_fit_logistic_sparse).  create checks the compressed-column arrays as
+ * oemgpu_fit_logistic_sparse does (OEMGPU_ERR_ARG with the same sentences, before any device is looked for), uploads them and
+ * builds, once, the per-column chunk pointers and the compressed-row copy that a fit otherwise builds per call.  The handle is an
+ * allocation of its own (24 B a non-zero, 8 (n + 1) B of row pointers, the chunk pointers), not part of the context's workspace; it
+ * may be used with any context of the same device, by one call at a time.  destroy frees it and accepts NULL. */
+typedef struct oemgpu_sparse_x oemgpu_sparse_x;
+int oemgpu_sparse_x_create(oemgpu_ctx *ctx, int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values,
+                           oemgpu_sparse_x **out);
+void oemgpu_sparse_x_destroy(oemgpu_sparse_x *x);
+/* cv.oem's fold fit on the resident sparse x (ref R/cv_oem.R:129-175): what `.Call("oem_fit_logistic_sparse", ...)` computes on
+ * x[keep, ], y[keep] with keep = foldid_dev != leave_out, every particular of oemgpu_fit_logistic_sparse included.  Nothing is sliced,
+ * uploaded or converted: the passes leave the fold's rows out and the number of kept rows stands where n enters the arithmetic (the
+ * column scales' n - 1, intval, the / n of XX, XY and the gradient; the W floor tests the IRLS index among the kept rows).  y_dev: n
+ * doubles and foldid_dev: n int32 with values 1 .. nfolds, on the device.  leave_out = 0 (foldid_dev may then be NULL) leaves nothing
+ * out and returns the bits of oemgpu_fit_logistic_sparse.  A left-out row is excluded exactly -- its y is never read, its stored
+ * values only meet a weight of 0 -- as long as those stored values are finite; NaN / Inf in a left-out row are not supported (they
+ * would poison the full fit of the same cv.oem anyway).  No floating-point atomics: two calls give the same bits.
+ * Checked before any device is looked for: OEMGPU_ERR_ARG for a NULL argument, nfolds < 3, leave_out outside [0, nfolds] and a NULL
+ * foldid_dev with leave_out > 0, then the checks of oemgpu_fit_logistic_sparse.  From the device: OEMGPU_ERR_ARG for a fold id outside
+ * [1, nfolds], OEMGPU_ERR_UNSUPPORTED (naming the fold) for p + intercept >= the kept rows. */
+int oemgpu_fit_logistic_sparse_fold_res(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
+                                        int32_t leave_out, int32_t standardize, int32_t intercept, int32_t irls_maxit, double irls_tol,
+                                        const oemgpu_opts *opts, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+/* oemgpu_logistic_cv_score_dev on the resident sparse x (ref R/cv_oem.R:224-346): the same arguments with the handle in place of
+ * x_dev, n, ld, p, the same outputs.  Every row is read from the compressed-row copy, its stored entries in column order; for finite
+ * tables the sums, counts and predmat are the bits of oemgpu_logistic_cv_score_dev on the same matrix written out densely.  The launch
+ * plan is oemgpu_selftest_cv_score_plan's.  OEMGPU_ERR_UNSUPPORTED for p > 8191. */
+int oemgpu_logistic_cv_score_sparse_res(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, const double *y_dev, double y_hi, const int32_t *foldid_dev,
+                                        int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *predmat_dev);
+/* oemgpu_selftest_logistic_sparse_plan for a fit on a resident x: the same eight numbers, out[2] (and the bound out[3] it stays
+ * within) counting the fit's own pieces only -- W, r, the row partials, X'W, the device words, the moments, the Gram scratch.  The
+ * compressed columns, the row copy, the chunk pointers (the handle's) and y (the caller's) are not in it. */
+int oemgpu_selftest_logistic_sparse_res_plan(int64_t n, int32_t p, int64_t nnz, int32_t intercept, int32_t num_cu, int64_t *out /* 8 */);
 /* Host-only plan of the compressed-column Gram kernel both sparse fits share (pure arithmetic, runs without a GPU): out[0] 8192-row
  * chunks of an n-row matrix, out[1] contiguous chunk ranges the launch splits them into (the range sums cost out[1] p^2 doubles, kept
  * under 256 MB), out[2] chunks per range (range r = chunks [r out[2], min(out[0], (r + 1) out[2])), possibly none for the last ranges),

@@ -64,6 +64,13 @@ _SIGS = {
     "oemgpu_fit_logistic_sparse": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                               C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_selftest_logistic_sparse_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "oemgpu_selftest_logistic_sparse_res_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "oemgpu_sparse_x_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "oemgpu_sparse_x_destroy": (None, [C.c_void_p]),
+    "oemgpu_fit_logistic_sparse_fold_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                       C.c_double, C.POINTER(OemgpuOpts)] + _OUT),
+    "oemgpu_logistic_cv_score_sparse_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, _dp, C.c_int32, _dp,
+                                                       C.POINTER(C.c_int64), C.c_void_p]),
     "oemgpu_selftest_csc_plan": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_last_logistic_stats": (C.c_int, [_dp]),
     "oemgpu_fit_xtx": (C.c_int, [_dp, _dp, C.c_int32, _dp, C.POINTER(OemgpuOpts)] + _OUT),

@@ -54,6 +54,10 @@ def _is_torch_cuda(x):
     return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
 
 
+def _is_scipy_sparse(x):
+    return type(x).__module__.startswith("scipy.sparse")
+
+
 def _csc_arrays(x):
     """The compressed-column arrays of a scipy.sparse x as R's coercion to dgCMatrix leaves them: float64 values, duplicate entries
     summed, row indices sorted inside every column.  Returns contiguous (int64 colptr, int32 rowidx, float64 values).  The caller's
@@ -443,21 +447,78 @@ def oem_fit_logistic_dense(x, y, penalty=None, weights=(), lambda_=(), nlambda=1
     return res
 
 
+class SparseX:
+    """A scipy.sparse x resident on a GPU (oemgpu_sparse_x_create): the compressed columns as _csc_arrays leaves them, their chunk
+    pointers and the compressed-row copy, uploaded and built once.  cv_oem(family="binomial") on a sparse x makes one and runs its full
+    fit, its fold fits and its scoring on it; oem_fit_logistic_sparse(_fold=...) and logistic_cv_score take one.  Owns the handle:
+    close() frees it (so does leaving a `with` block, and __del__); a closed SparseX refuses further use."""
+
+    def __init__(self, x, device=None):
+        import scipy.sparse as sp
+        import torch
+        self._h = None
+        if not sp.issparse(x):
+            raise TypeError("x must be a scipy.sparse matrix")
+        if len(x.shape) != 2:
+            raise ValueError("x must have at least two columns")
+        self.shape = (int(x.shape[0]), int(x.shape[1]))
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else (torch.device(device).index or 0))
+        colptr, rowidx, vals = _csc_arrays(x)
+        self.nnz = int(colptr[-1])
+        h = C.c_void_p()
+        L.check(L.lib().oemgpu_sparse_x_create(context(self.device.index), self.shape[0], self.shape[1], colptr.ctypes.data, _iptr(rowidx),
+                                               _dptr(vals), C.byref(h)))
+        self._h = h
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("this SparseX is closed")
+        return self._h
+
+    @property
+    def closed(self):
+        return self._h is None
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            L.lib().oemgpu_sparse_x_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                              # (interpreter shutdown: the library may be gone)
+            pass
+
+
 def oem_fit_logistic_sparse(x, y, penalty=None, weights=(), lambda_=(), nlambda=100, lambda_min_ratio=None, alpha=1.0, gamma=3.0, tau=0.5,
                             groups=(), penalty_factor=None, group_weights=None, standardize=True, intercept=True, maxit=500, tol=1e-7,
-                            irls_maxit=100, irls_tol=1e-3, compute_loss=False, hessian_type="upper.bound", varnames=None, interrupt=None):
+                            irls_maxit=100, irls_tol=1e-3, compute_loss=False, hessian_type="upper.bound", varnames=None, interrupt=None,
+                            _fold=None):
     """The sparse binomial fit (ref src/oem_logistic_sparse.cpp:30-313, src/oem_logistic_sparse.h), the entry `oem(x = <dgCMatrix>,
     family = "binomial")` calls (R/oem.R:603-624), with the checks of oem_fit_logistic_dense.  x: any scipy.sparse matrix, taken as
     compressed columns of float64 with duplicates summed and indices sorted, as R's coercion to dgCMatrix does.
     hessian_type must be "upper.bound" or "full" and is then ignored: the reference rebuilds X'WX at every IRLS step of this fit
     whatever it says (src/oem_logistic_sparse.h:866, :973).  An intercept needs standardize (the reference's linear predictor reads
-    column scales it only computes with standardize); p + intercept >= n is refused."""
+    column scales it only computes with standardize); p + intercept >= n is refused.
+    _fold (cv_oem's fold fits): (a SparseX, foldid as an int32 device tensor or None, nfolds, leave_out, y as a float64 device tensor) --
+    the fit on the rows with foldid != leave_out of the resident x (oemgpu_fit_logistic_sparse_fold_res; leave_out = 0: every row, the
+    bits of the plain call), which reports their number as nobs.  x is then not looked at beyond its shape (the SparseX itself may be
+    passed)."""
     import scipy.sparse as sp
     L.sync_switches()
     penalty = _match_penalty(penalty)
     if hessian_type not in ("upper.bound", "full"):
         raise ValueError("'arg' should be one of 'upper.bound', 'full'")
-    if not sp.issparse(x):
+    if not (sp.issparse(x) or (_fold is not None and isinstance(x, SparseX))):
         raise TypeError("x must be a scipy.sparse matrix (oem_fit_logistic_dense takes a dense one)")
     if len(x.shape) != 2:
         raise ValueError("x must have at least two columns")
@@ -485,6 +546,18 @@ def oem_fit_logistic_sparse(x, y, penalty=None, weights=(), lambda_=(), nlambda=
     lam_list = _lambda_list(lambda_, len(penalty))
     a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
               compute_loss, penalty_factor, groups, unique_groups, group_weights, interrupt=interrupt)
+    if _fold is not None:
+        import torch
+        sx, fd, nfolds, leave_out, yd = _fold
+        if tuple(sx.shape) != (n, p):
+            raise ValueError("the SparseX does not have the shape of x")
+        torch.cuda.current_stream(sx.device).synchronize()
+        L.check(L.lib().oemgpu_fit_logistic_sparse_fold_res(context(sx.device.index), sx.handle, yd.data_ptr(), None if fd is None else fd.data_ptr(),
+                                                            int(nfolds), int(leave_out), int(bool(standardize)), int(bool(intercept)),
+                                                            int(irls_maxit), float(irls_tol), C.byref(a.c), *a.outputs(p + 1)))
+        if fd is not None and int(leave_out) > 0:
+            n = int(n - (fd == int(leave_out)).sum().item())
+        return OemFitBinomial(_decorate(a, penalty, varnames, True, n, p, family="binomial"))
     colptr, rowidx, vals = _csc_arrays(x)
     L.check(L.lib().oemgpu_fit_logistic_sparse(n, p, colptr.ctypes.data, _iptr(rowidx), _dptr(vals), _dptr(yh), int(bool(standardize)),
                                                int(bool(intercept)), int(irls_maxit), float(irls_tol), C.byref(a.c), *a.outputs(p + 1)))
@@ -767,11 +840,16 @@ def xval_cv_error(x, y, foldid, nfolds, coef, type_measure="mse", weights=None, 
 # ------------------------------------------------------------------------------------------ cv.oem()
 def logistic_cv_score(x, y, foldid, nfolds, coef, y_hi=None, predmat=False):
     """oemgpu_logistic_cv_score_dev: the error terms of cv.oemfit_binomial (R/cv_oem.R:315-327) over the held-out rows of a resident x.
-    x: a column-major float64 matrix on a GPU; y (float64) and foldid (int32, 1 .. nfolds): device tensors; coef: nfolds x ncol x
+    x: a column-major float64 matrix on a GPU, or a SparseX (oemgpu_logistic_cv_score_sparse_res: for finite tables the bits of the
+    dense entry on the same matrix written out); y (float64) and foldid (int32, 1 .. nfolds): device tensors; coef: nfolds x ncol x
     (p + 1) on the host, the columns that score the rows of each fold.  Returns (sums: nfolds x ncol x 8 = [sum, sum of squares] of
     deviance, class, mse, mae; counts: the fold sizes; predmat: n x ncol on the host, or None)."""
     import torch
-    xp, n, p, ld, keepalive = _device_matrix(x)
+    sparse = isinstance(x, SparseX)
+    if sparse:
+        (n, p), keepalive = x.shape, None
+    else:
+        xp, n, p, ld, keepalive = _device_matrix(x)
     coef = np.ascontiguousarray(coef, dtype=np.float64)
     if coef.ndim != 3 or coef.shape[0] != int(nfolds) or coef.shape[2] != p + 1:
         raise ValueError("coef must be nfolds x ncol x (p + 1)")
@@ -782,9 +860,14 @@ def logistic_cv_score(x, y, foldid, nfolds, coef, y_hi=None, predmat=False):
     if y_hi is None:
         y_hi = float(y.max().item())
     torch.cuda.current_stream(x.device).synchronize()
-    L.check(L.lib().oemgpu_logistic_cv_score_dev(context(x.device.index), xp, n, ld, p, y.data_ptr(), float(y_hi), foldid.data_ptr(), int(nfolds),
-                                                 _dptr(coef), ncol, _dptr(sums), counts.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                 None if pm is None else pm.data_ptr()))
+    if sparse:
+        L.check(L.lib().oemgpu_logistic_cv_score_sparse_res(context(x.device.index), x.handle, y.data_ptr(), float(y_hi), foldid.data_ptr(),
+                                                            int(nfolds), _dptr(coef), ncol, _dptr(sums),
+                                                            counts.ctypes.data_as(C.POINTER(C.c_int64)), None if pm is None else pm.data_ptr()))
+    else:
+        L.check(L.lib().oemgpu_logistic_cv_score_dev(context(x.device.index), xp, n, ld, p, y.data_ptr(), float(y_hi), foldid.data_ptr(), int(nfolds),
+                                                     _dptr(coef), ncol, _dptr(sums), counts.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                     None if pm is None else pm.data_ptr()))
     del keepalive
     return sums, counts, None if pm is None else pm.t().cpu().numpy()
 
@@ -806,7 +889,8 @@ _BINOMIAL_NAMES = {"mse": "Mean-Squared Error", "mae": "Mean Absolute Error", "d
 
 def _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, foldid, grouped, keep, rng, kw):
     """cv.oem() for family = "binomial": R/cv_oem.R:56-221 with cv.oemfit_binomial (:224-346).  x is on the device once; the full fit,
-    the K fold fits (masked row passes over that x, one fold after another) and the scoring all read it there."""
+    the K fold fits (masked row passes over that x, one fold after another) and the scoring all read it there.  A dense x (numpy or
+    a device tensor) stays a column-major device matrix; a scipy.sparse x becomes one SparseX, which is closed on the way out."""
     for drop in ("accelerate", "ncores"):            # oem() arguments the binomial fit has no use for (no Nesterov step, no OpenMP)
         kw.pop(drop, None)
     if getattr(x, "ndim", 0) != 2:
@@ -820,6 +904,15 @@ def _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, fold
     if len(np.unique(yh)) > 2:                                         # R/oem.R:250-252
         raise ValueError("y must be a binary outcome")
     import torch
+    lam_arg = () if lambda_ is None else lambda_
+    if _is_scipy_sparse(x):
+        with SparseX(x) as sx:                                         # the one upload, the one compressed-row build
+            yd = torch.as_tensor(yh, device=sx.device)
+
+            def fit(fd, nfolds, leave_out):                            # the full fit is leave_out = 0 on the same handle
+                return oem_fit_logistic_sparse(sx, yh, penalty=penalty, lambda_=lam_arg, _fold=(sx, fd, max(int(nfolds), 3), leave_out, yd), **kw)
+            return _cv_oem_binomial_on(fit, lambda fd, nfolds, coef, **k: logistic_cv_score(sx, yd, fd, nfolds, coef, **k), sx.device,
+                                       n, p, yh, penalty, type_measure, nfolds, foldid, grouped, keep, rng)
     if _is_torch_cuda(x):
         xd = x if x.dtype == torch.float64 else x.to(torch.float64)
         if not (xd.stride(0) == 1 and xd.stride(1) >= n):
@@ -827,8 +920,20 @@ def _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, fold
     else:
         xd = torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float64).T), device="cuda").t()     # the one upload
     yd = torch.as_tensor(yh, device=xd.device)
-    lam_arg = () if lambda_ is None else lambda_
-    fit0 = oem_fit_logistic_dense(xd, yh, penalty=penalty, lambda_=lam_arg, **kw)
+
+    def fit(fd, nfolds, leave_out):
+        if leave_out == 0:
+            return oem_fit_logistic_dense(xd, yh, penalty=penalty, lambda_=lam_arg, **kw)
+        return oem_fit_logistic_dense(xd, yh, penalty=penalty, lambda_=lam_arg, _fold=(fd, nfolds, leave_out, yd), **kw)
+    return _cv_oem_binomial_on(fit, lambda fd, nfolds, coef, **k: logistic_cv_score(xd, yd, fd, nfolds, coef, **k), xd.device,
+                               n, p, yh, penalty, type_measure, nfolds, foldid, grouped, keep, rng)
+
+
+def _cv_oem_binomial_on(fit, score, device, n, p, yh, penalty, type_measure, nfolds, foldid, grouped, keep, rng):
+    """_cv_oem_binomial once x is resident.  fit(foldid_dev, nfolds, leave_out): the fit without fold leave_out (0: the full fit, made
+    before the folds are drawn: foldid_dev is then None); score(foldid_dev, nfolds, coef, y_hi=, predmat=): logistic_cv_score on that x."""
+    import torch
+    fit0 = fit(None, 0, 0)
     nmodels = len(penalty)
     nz = [np.array([0 if v is None else len(v) for v in predict(fit0, type="nonzero", which_model=m)]) for m in range(nmodels)]
     if foldid is None:
@@ -841,8 +946,8 @@ def _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, fold
         raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
     if len(foldid) != n:
         raise ValueError("x and y lengths do not match")
-    fd = torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=xd.device)
-    outlist = [oem_fit_logistic_dense(xd, yh, penalty=penalty, lambda_=lam_arg, _fold=(fd, nfolds, i, yd), **kw) for i in range(1, nfolds + 1)]
+    fd = torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=device)
+    outlist = [fit(fd, nfolds, i) for i in range(1, nfolds + 1)]
     # cv.oemfit_binomial
     if type_measure == "default":
         type_measure = "deviance"
@@ -871,7 +976,7 @@ def _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, fold
             left, right, frac = _lambda_interp(np.asarray(o["lambda"][m], dtype=np.float64), s)
             b = np.asarray(o["beta"][m])
             coef[i] = (b[:, left] * frac + b[:, right] * (1 - frac)).T
-        sums, counts, pm = logistic_cv_score(xd, yd, fd, nfolds, coef, y_hi=y_hi, predmat=want_pred)
+        sums, counts, pm = score(fd, nfolds, coef, y_hi=y_hi, predmat=want_pred)
         if want_pred:
             full = np.full((n, nl), np.nan)
             full[:, :nlami] = pm
@@ -935,6 +1040,11 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
     the scoring of the held-out rows (oemgpu_logistic_cv_score_dev) read it there.  type_measure: "deviance" (default), "class", "mse",
     "mae" or "auc" (on the host, from the held-out probabilities; ties in row order).  `parallel` is accepted and the folds still run
     one after another.  The options are those of oem_fit_logistic_dense; the result has the keys below with an OemFitBinomial `oem.fit`.
+    family = "binomial" with a scipy.sparse x (R/cv_oem.R:129-175 on a dgCMatrix, which reaches oem_fit_logistic_sparse): one SparseX holds
+    the compressed columns and their compressed-row copy on the device; the full fit (leave_out = 0), the fold fits (masked passes,
+    oemgpu_fit_logistic_sparse_fold_res) and the scoring (oemgpu_logistic_cv_score_sparse_res) read it there.  The options are those of
+    oem_fit_logistic_sparse (hessian_type is checked and ignored; an intercept needs standardize).  A sparse x with family = "gaussian"
+    is a ValueError.
     parallel (R/cv_oem.R:32, 129-150: the folds through foreach): the fold fits from a few host threads at once.  On one GPU that
     pays where a fit leaves most of the chip idle: the path kernels of n >> p fits (one CU each) overlap with other folds' moment
     kernels, and p >= n fits on the cooperating-workgroup engine (a quarter of the CUs each) run side by side -- they queue for CU
@@ -953,6 +1063,8 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
         return _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, foldid, grouped, keep, rng, kw)
     if len(weights) > 0:
         raise ValueError("weights not implemented yet.")
+    if _is_scipy_sparse(x):
+        raise ValueError("cv.oem on a sparse x is served for family = \"binomial\" only (a sparse Gaussian cross-validation is not built)")
     xh = np.asarray(x.cpu().numpy() if _is_torch_cuda(x) else x, dtype=np.float64)
     yh = np.asarray(y.cpu().numpy() if _is_torch_cuda(y) else y, dtype=np.float64).reshape(-1)
     n = xh.shape[0]

@@ -477,6 +477,25 @@ int launch_logit_fill(hipStream_t s, double *a, int n, double v)
     return 0;
 }
 
+int logit_fold_scan(oemgpu_ctx *c, const char *who, const int32_t *foldid, int64_t n, int32_t nfolds, int32_t leave_out, int32_t irls_maxit,
+                    int64_t *n_eff, std::vector<int64_t> *kept_row)
+{
+    const int64_t nmap = std::min<int64_t>(irls_maxit, n);
+    if (ctx_reserve(c, 8 * (size_t)(2 + nmap))) return OEMGPU_ERR_HIP;
+    int64_t *scan = (int64_t *)c->ws;
+    hipLaunchKernelGGL(logit_fold_scan_kernel, dim3(1), dim3(1024), 0, c->stream, foldid, n, nfolds, leave_out, nmap, scan);
+    OEM_HIP(hipGetLastError());
+    std::vector<int64_t> h((size_t)(2 + nmap), -1);
+    OEM_HIP(hipMemcpyAsync(h.data(), scan, 8 * 2, hipMemcpyDeviceToHost, c->stream));
+    OEM_HIP(hipStreamSynchronize(c->stream));
+    if (h[1] != 0) { set_error("%s: %lld fold ids are outside [1, %d]", who, (long long)h[1], (int)nfolds); return OEMGPU_ERR_ARG; }
+    const int64_t nk = std::min<int64_t>(nmap, h[0]);
+    if (nk > 0) OEM_HIP(hipMemcpy(h.data() + 2, scan + 2, 8 * (size_t)nk, hipMemcpyDeviceToHost));
+    *n_eff = h[0];
+    kept_row->assign(h.begin() + 2, h.begin() + 2 + nk);
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host driver
 struct LogitStats {
     double ms_rows = 0, ms_gram = 0, ms_inner = 0, irls_steps = 0, inner_iters = 0, row_passes = 0, grams = 0, wall_ms = 0;
@@ -553,22 +572,12 @@ struct DenseLogitData final : LogitData {
     // The row whose W the floor tests at IRLS step i (h :953-959 tests W(i) of the rows it was given)
     int64_t floor_row(int64_t i) const { return foldid ? (i < (int64_t)kept_row.size() ? kept_row[(size_t)i] : -1) : i; }
     // Makes this the fold fit without fold leave_out_: counts n_eff, checks the ids' range and maps the first IRLS indices to rows, on
-    // the device, once (scratch: the start of c->ws, read back before anything else uses it)
+    // the device, once (logit_fold_scan)
     int set_fold(const int32_t *foldid_, int32_t nfolds, int32_t leave_out_, int32_t irls_maxit)
     {
-        const int64_t nmap = std::min<int64_t>(irls_maxit, n);
-        if (ctx_reserve(c, 8 * (size_t)(2 + nmap))) return OEMGPU_ERR_HIP;
-        int64_t *scan = (int64_t *)c->ws;
-        hipLaunchKernelGGL(logit_fold_scan_kernel, dim3(1), dim3(1024), 0, c->stream, foldid_, n, nfolds, leave_out_, nmap, scan);
-        OEM_HIP(hipGetLastError());
-        std::vector<int64_t> h((size_t)(2 + nmap), -1);
-        OEM_HIP(hipMemcpyAsync(h.data(), scan, 8 * 2, hipMemcpyDeviceToHost, c->stream));
-        OEM_HIP(hipStreamSynchronize(c->stream));
-        if (h[1] != 0) { set_error("fit_logistic_dense_fold: %lld fold ids are outside [1, %d]", (long long)h[1], (int)nfolds); return OEMGPU_ERR_ARG; }
-        const int64_t nk = std::min<int64_t>(nmap, h[0]);
-        if (nk > 0) OEM_HIP(hipMemcpy(h.data() + 2, scan + 2, 8 * (size_t)nk, hipMemcpyDeviceToHost));
-        foldid = foldid_; leave_out = leave_out_; n_eff = h[0];
-        kept_row.assign(h.begin() + 2, h.begin() + 2 + nk);
+        const int rc = logit_fold_scan(c, "fit_logistic_dense_fold", foldid_, n, nfolds, leave_out_, irls_maxit, &n_eff, &kept_row);
+        if (rc) return rc;
+        foldid = foldid_; leave_out = leave_out_;
         return 0;
     }
 

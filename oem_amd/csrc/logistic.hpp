@@ -5,6 +5,22 @@
 #pragma once
 #include "ctx.hpp"
 
+#include <vector>
+
+// A sparse x resident on a device (oemgpu_sparse_x_create; cv.oem's fold fits and scoring read it there): the compressed columns as
+// they came, the chunk pointers of the compressed-column kernels and the compressed-row copy with every row's entries in column
+// order -- what SparseLogitData::bind builds for a single fit, built once.  One allocation of its own (`base`), not the context's.
+struct oemgpu_sparse_x {
+    int device = 0;
+    int64_t n = 0, nnz = 0, maxcol = 0;   // maxcol: the longest column
+    int32_t p = 0;
+    char *base = nullptr;
+    size_t bytes = 0;
+    int64_t *colptr = nullptr, *rowptr = nullptr;
+    int32_t *rowidx = nullptr, *ccol = nullptr, *cptr = nullptr;
+    double *val = nullptr, *cval = nullptr;
+};
+
 namespace oemgpu {
 
 // The data-dependent stages of an IRLS fit.  Every stage enqueues on the context's stream.  g: p + 2 doubles, laid out as
@@ -26,6 +42,14 @@ int logistic_check(int64_t n, int32_t p, int32_t intercept, int32_t hessian_full
 int logistic_irls(oemgpu_ctx *c, LogitData &D, int64_t n, int32_t p, int32_t intercept, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
                   double *beta_out, double *lambda_out, int32_t *niter, double *loss_out, double *d_out);
 int launch_logit_fill(hipStream_t s, double *a, int n, double v);   // a[0 .. n) = v
+// A fold fit's look at foldid (logit_fold_scan_kernel, once per call; scratch: the start of c->ws, read back before anything else uses
+// it): *n_eff = rows with foldid != leave_out, kept_row[k] = the row of the k-th kept row for k < min(irls_maxit, n_eff) (the W floor
+// tests the IRLS index among the kept rows); OEMGPU_ERR_ARG in `who`'s name when an id is outside [1, nfolds]
+int logit_fold_scan(oemgpu_ctx *c, const char *who, const int32_t *foldid, int64_t n, int32_t nfolds, int32_t leave_out, int32_t irls_maxit,
+                    int64_t *n_eff, std::vector<int64_t> *kept_row);
+// the scoring pass of cv.oem over a resident x (logistic_cv.hip): dense (x, ld) when sx is null, else the compressed-row copy of sx
+int logistic_cv_score_dev(oemgpu_ctx *c, const double *x, const oemgpu_sparse_x *sx, int64_t n, int64_t ld, int32_t p, const double *y, double y_hi,
+                          const int32_t *foldid, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *pred);
 extern const int LOGIT_WG_MAX_Q;                         // q up to which the inner solve is one persistent workgroup
 extern const int LOGIT_P_LIMIT;                          // the largest p served
 

@@ -15,6 +15,12 @@
 // coefficient table in LDS when it fits (read through the cache otherwise).  Sums: a fixed butterfly over the 64 lanes, tiles added in
 // row order into the workgroup's LDS accumulators, workgroup partials added in chunk order -- no floating-point atomics, two calls give
 // the same bits.  Scoring is a small share of a cross-validation, so the kernel is kept plain.
+//
+// The rows come through a reader (the kernel's ROWS parameter).  CvDenseRows: the column-major x, an entry per column.  CvCsrRows
+// (oemgpu_logistic_cv_score_sparse_res): the compressed-row copy of a resident sparse x -- lane = row as before, every lane walks its own
+// row's stored entries in column order, one fma each.  The dense reader adds fma(0, beta, eta) = eta for an absent entry, so on
+// finite tables the sparse entry returns the bits of the dense entry on the same matrix written out; plan, tiles, tile skip,
+// butterfly and sum order are shared.
 #include "logistic.hpp"
 
 #include <algorithm>
@@ -55,9 +61,21 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
+struct CvDenseRows {                 // x column-major, leading dimension ld
+    static constexpr bool sparse = false;
+    const double *x;
+    int64_t ld;
+};
+struct CvCsrRows {                   // row r: entries rowptr[r] .. rowptr[r + 1] of (ccol, cval), in column order
+    static constexpr bool sparse = true;
+    const int64_t *rowptr;
+    const int32_t *ccol;
+    const double *cval;
+};
+
 // tab: the fold's table, column c at tab[c (p + 1)]: [beta_0, beta (p)]; part: nchunk x (8 ncol + 1), the last entry the fold's rows
-template <bool TLDS>
-__global__ __launch_bounds__(256) void logit_cv_score_kernel(const double *__restrict__ x, int64_t n, int64_t ld, int p, const double *__restrict__ y,
+template <bool TLDS, class ROWS>
+__global__ __launch_bounds__(256) void logit_cv_score_kernel(const ROWS X, int64_t n, int p, const double *__restrict__ y,
                                                              double y_hi, const int32_t *__restrict__ foldid, int32_t fold,
                                                              const double *__restrict__ tab, int ncol, int64_t ch, double *__restrict__ part,
                                                              double *__restrict__ pred)
@@ -87,10 +105,22 @@ __global__ __launch_bounds__(256) void logit_cv_score_kernel(const double *__res
                 tc[k] = tb + (size_t)(c0 + k < ncol ? c0 + k : ncol - 1) * q;
                 eta[k] = tc[k][0];
             }
-            for (int j = 0; j < p; ++j) {
-                const double v = in ? x[(size_t)j * ld + row] : 0.0;
+            if constexpr (ROWS::sparse) {
+                const int64_t k0 = in ? X.rowptr[row] : 0, k1 = in ? X.rowptr[row + 1] : 0;
+                for (int64_t e = k0; e < k1; ++e) {
+                    const double v = X.cval[e];
+                    const int j = X.ccol[e];
 #pragma unroll
-                for (int k = 0; k < 8; ++k) eta[k] = fma(v, tc[k][1 + j], eta[k]);
+                    for (int k = 0; k < 8; ++k) eta[k] = fma(v, tc[k][1 + j], eta[k]);
+                }
+            } else {
+                const double *__restrict__ x = X.x;
+                const int64_t ld = X.ld;
+                for (int j = 0; j < p; ++j) {
+                    const double v = in ? x[(size_t)j * ld + row] : 0.0;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) eta[k] = fma(v, tc[k][1 + j], eta[k]);
+                }
             }
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -133,8 +163,9 @@ __global__ __launch_bounds__(256) void logit_cv_sum_kernel(const double *__restr
 
 }  // namespace
 
-int logistic_cv_score_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int32_t p, const double *y, double y_hi, const int32_t *foldid,
-                          int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *pred)
+template <class ROWS>
+static int cv_score_run(oemgpu_ctx *c, const ROWS X, int64_t n, int32_t p, const double *y, double y_hi, const int32_t *foldid,
+                        int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *pred)
 {
     hipStream_t s = c->stream;
     const int q = p + 1;
@@ -156,12 +187,12 @@ int logistic_cv_score_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld,
             double *pf = pred ? pred + (size_t)c0 * n : nullptr;
             const size_t lds = 8 * ((size_t)nacc + (tlds ? (size_t)nc * q : 0));
             if (tlds) {
-                if (lds_limit_once(reinterpret_cast<const void *>(&logit_cv_score_kernel<true>), lds)) return OEMGPU_ERR_HIP;
-                hipLaunchKernelGGL(logit_cv_score_kernel<true>, dim3((unsigned)nchunk), dim3(256), lds, s, x, n, ld, p, y, y_hi, foldid, f + 1, tf, nc, ch,
+                if (lds_limit_once(reinterpret_cast<const void *>(&logit_cv_score_kernel<true, ROWS>), lds)) return OEMGPU_ERR_HIP;
+                hipLaunchKernelGGL((logit_cv_score_kernel<true, ROWS>), dim3((unsigned)nchunk), dim3(256), lds, s, X, n, p, y, y_hi, foldid, f + 1, tf, nc, ch,
                                    part, pf);
             } else {
-                if (lds_limit_once(reinterpret_cast<const void *>(&logit_cv_score_kernel<false>), lds)) return OEMGPU_ERR_HIP;
-                hipLaunchKernelGGL(logit_cv_score_kernel<false>, dim3((unsigned)nchunk), dim3(256), lds, s, x, n, ld, p, y, y_hi, foldid, f + 1, tf, nc, ch,
+                if (lds_limit_once(reinterpret_cast<const void *>(&logit_cv_score_kernel<false, ROWS>), lds)) return OEMGPU_ERR_HIP;
+                hipLaunchKernelGGL((logit_cv_score_kernel<false, ROWS>), dim3((unsigned)nchunk), dim3(256), lds, s, X, n, p, y, y_hi, foldid, f + 1, tf, nc, ch,
                                    part, pf);
             }
             hipLaunchKernelGGL(logit_cv_sum_kernel, dim3((nacc + 255) / 256), dim3(256), 0, s, part, nchunk, nacc, out + (size_t)f * out_f + 8 * (size_t)c0,
@@ -177,6 +208,13 @@ int logistic_cv_score_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld,
         counts[f] = (int64_t)h[(size_t)f * out_f + out_f - 1];
     }
     return 0;
+}
+
+int logistic_cv_score_dev(oemgpu_ctx *c, const double *x, const oemgpu_sparse_x *sx, int64_t n, int64_t ld, int32_t p, const double *y, double y_hi,
+                          const int32_t *foldid, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *pred)
+{
+    if (sx) return cv_score_run(c, CvCsrRows{sx->rowptr, sx->ccol, sx->cval}, n, p, y, y_hi, foldid, nfolds, coef, ncol, sums, counts, pred);
+    return cv_score_run(c, CvDenseRows{x, ld}, n, p, y, y_hi, foldid, nfolds, coef, ncol, sums, counts, pred);
 }
 
 }  // namespace oemgpu
@@ -195,7 +233,19 @@ int oemgpu_logistic_cv_score_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, 
     if (nfolds < 3) { set_error("nfolds must be bigger than 3; nfolds=10 recommended"); return OEMGPU_ERR_ARG; }
     if (p > LOGIT_P_LIMIT) { set_error("logistic_cv_score: p > %d is not supported", LOGIT_P_LIMIT); return OEMGPU_ERR_UNSUPPORTED; }
     if (set_device(c)) return OEMGPU_ERR_HIP;
-    return logistic_cv_score_dev(c, x_dev, n, ld, p, y_dev, y_hi, foldid_dev, nfolds, coef, ncol, sums, counts, predmat_dev);
+    return logistic_cv_score_dev(c, x_dev, nullptr, n, ld, p, y_dev, y_hi, foldid_dev, nfolds, coef, ncol, sums, counts, predmat_dev);
+}
+
+int oemgpu_logistic_cv_score_sparse_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const double *y_dev, double y_hi, const int32_t *foldid_dev,
+                                        int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *predmat_dev)
+{
+    if (!c || !x || !y_dev || !foldid_dev || !coef || !sums || !counts) { set_error("logistic_cv_score_sparse: NULL argument"); return OEMGPU_ERR_ARG; }
+    if (ncol < 1) { set_error("logistic_cv_score_sparse: bad ncol"); return OEMGPU_ERR_ARG; }
+    if (nfolds < 3) { set_error("nfolds must be bigger than 3; nfolds=10 recommended"); return OEMGPU_ERR_ARG; }
+    if (x->p > LOGIT_P_LIMIT) { set_error("logistic_cv_score_sparse: p > %d is not supported", LOGIT_P_LIMIT); return OEMGPU_ERR_UNSUPPORTED; }
+    if (c->device != x->device) { set_error("logistic_cv_score_sparse: the context and the sparse x are on different devices"); return OEMGPU_ERR_ARG; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    return logistic_cv_score_dev(c, nullptr, x, x->n, x->n, x->p, y_dev, y_hi, foldid_dev, nfolds, coef, ncol, sums, counts, predmat_dev);
 }
 
 int oemgpu_selftest_cv_score_plan(int64_t n, int32_t p, int32_t ncol, int32_t num_cu, int64_t *out)

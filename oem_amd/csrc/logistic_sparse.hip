@@ -24,6 +24,13 @@
 //     with the row weight gathered at its scatter (csc_gram_kernel<true>), or csc_tile_moments over zero-filled row tiles of sqrt(W) x;
 //   * lsp_intval_kernel + lsp_xx_kernel: xxdiag / intval and XX.
 // No float atomics anywhere: two calls give the same bits.
+//
+// cv.oem on a sparse x (oemgpu_sparse_x_create, oemgpu_fit_logistic_sparse_fold_res; ref R/cv_oem.R:129-175 slices x[!which, ] and calls
+// oem()): the compressed columns, their chunk pointers and the row copy are built ONCE into a handle, and SparseLogitData binds to it
+// (resident mode: nothing is uploaded or converted, the workspace holds the fit's own pieces only).  A fold fit is the fit on the rows
+// with foldid != leave_out of that x: the MASKED column scales sum kept entries only, the MASKED row pass never reads a left-out row
+// and writes W = r = 0 there -- so the column pass and both weighted Gram routes run unchanged (fma(v, 0, a) = a for every finite
+// stored v) -- and n_eff, the kept rows (logit_fold_scan), stands where n enters the arithmetic; the W floor tests the i-th KEPT row.
 #include "logistic.hpp"
 
 #include <cmath>
@@ -35,14 +42,22 @@ namespace {
 
 enum { SW_XXDIAG = 0, SW_INTVAL = 1, SW_SUMW = 2, SW_LEN = 4 };    // device words of the sparse fit
 
-// colsq = sum x^2 / (n - 1) over a column's stored values, 0 -> 1, s = 1 / sqrt(colsq) (h :735-750); one workgroup per column
-__global__ __launch_bounds__(256) void lsp_scale_kernel(const int64_t *__restrict__ colptr, const double *__restrict__ val, int64_t n,
-                                                        double *__restrict__ s)
+// colsq = sum x^2 / (n - 1) over a column's stored values, 0 -> 1, s = 1 / sqrt(colsq) (h :735-750); one workgroup per column.
+// MASKED (a fold fit): the entries of the kept rows only, n their number -- a column with none of them gets 0 -> 1 as on x[keep, ]
+template <bool MASKED>
+__global__ __launch_bounds__(256) void lsp_scale_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx,
+                                                        const double *__restrict__ val, int64_t n, double *__restrict__ s,
+                                                        const int32_t *__restrict__ foldid, int32_t leave_out)
 {
     __shared__ double red[256];
     const int j = blockIdx.x;
     double a = 0.0;
-    for (int64_t k = colptr[j] + threadIdx.x; k < colptr[j + 1]; k += 256) a = fma(val[k], val[k], a);
+    if (MASKED) {
+        for (int64_t k = colptr[j] + threadIdx.x; k < colptr[j + 1]; k += 256)
+            if (foldid[rowidx[k]] != leave_out) a = fma(val[k], val[k], a);
+    } else {
+        for (int64_t k = colptr[j] + threadIdx.x; k < colptr[j + 1]; k += 256) a = fma(val[k], val[k], a);
+    }
     red[threadIdx.x] = a;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -54,11 +69,15 @@ __global__ __launch_bounds__(256) void lsp_scale_kernel(const int64_t *__restric
     }
 }
 
-// the row pass: workgroup c owns rows [c ch, (c + 1) ch), a thread per row (rows tid, tid + 256, ...), the row's entries in column order
+// the row pass: workgroup c owns rows [c ch, (c + 1) ch), a thread per row (rows tid, tid + 256, ...), the row's entries in column order.
+// MASKED (a fold fit): a row with foldid[row] == leave_out is not in the fit: neither its entries nor its y are read, W = r = 0 are
+// written there and nothing is added to the sums; irls_i is then the row of the i-th KEPT row (-1: none, the floor is off)
+template <bool MASKED>
 __global__ __launch_bounds__(256) void lsp_rows_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ ccol, const double *__restrict__ cval,
                                                        int64_t n, int p, const double *__restrict__ y, const double *__restrict__ beta,
                                                        const double *__restrict__ s, int intercept, int64_t irls_i, int64_t ch,
-                                                       double *__restrict__ wout, double *__restrict__ rout, double *__restrict__ part)
+                                                       double *__restrict__ wout, double *__restrict__ rout, double *__restrict__ part,
+                                                       const int32_t *__restrict__ foldid, int32_t leave_out)
 {
     extern __shared__ double bs[];                     // p: beta o s
     __shared__ double red[3][256];
@@ -69,6 +88,7 @@ __global__ __launch_bounds__(256) void lsp_rows_kernel(const int64_t *__restrict
     const int64_t c = blockIdx.x, r_lo = c * ch, r_hi = (r_lo + ch < n) ? r_lo + ch : n;
     double rs = 0.0, ws = 0.0, ls = 0.0;
     for (int64_t row = r_lo + tid; row < r_hi; row += 256) {
+        if (MASKED && foldid[row] == leave_out) { wout[row] = 0.0; rout[row] = 0.0; continue; }
         double e = 0.0;
         for (int64_t k = rowptr[row]; k < rowptr[row + 1]; ++k) e = fma(cval[k], bs[ccol[k]], e);
         const double eta = e + b0;
@@ -165,6 +185,14 @@ __global__ __launch_bounds__(256) void lsp_xx_kernel(const double *__restrict__ 
 
 __global__ void lsp_zero_words_kernel(double *sw) { if (threadIdx.x < SW_LEN) sw[threadIdx.x] = 0.0; }
 
+// a fold fit's X'y: out = kept ? y : 0 (the column pass then runs on it as on r; y of a left-out row is not read)
+__global__ __launch_bounds__(256) void lsp_kept_y_kernel(const double *__restrict__ y, const int32_t *__restrict__ foldid, int32_t leave_out, int64_t n,
+                                                         double *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = foldid[i] != leave_out ? y[i] : 0.0;
+}
+
 }  // namespace
 
 // the plan of a call: the Gram route, the row pass's chunks, the tile rows, the workspace
@@ -175,6 +203,7 @@ struct LspPlan {
     int64_t nchunk;    // row-pass workgroups
     int64_t rcrows;    // tile route: rows per tile (0 on the csc route)
     int64_t ld;        // tile route: the tile's leading dimension
+    int resident;      // 1: x is an oemgpu_sparse_x and y the caller's device vector; the workspace holds the fit's own pieces only
     size_t ws_bytes;   // the fit's own workspace (the driver's pieces come on top: q^2 matrices, the output)
     size_t bound;      // ws_bytes stays within this
 };
@@ -186,14 +215,15 @@ static size_t lsp_layout(const LspPlan &P, int64_t n, int p, int64_t nnz, int nu
     const size_t m2 = (size_t)(p + 2) * (p + 2);
     size_t t[20];
     int k = 0;
-    t[k++] = B.take(8 * (size_t)(p + 1));                   // 0 colptr
-    t[k++] = B.take(4 * (size_t)(nnz + 1));                 // 1 rowidx
-    t[k++] = B.take(8 * (size_t)(nnz + 1));                 // 2 values
-    t[k++] = B.take(8 * (size_t)n);                         // 3 y
-    t[k++] = B.take(8 * (size_t)(n + 1));                   // 4 rowptr of the row copy
-    t[k++] = B.take(4 * (size_t)(nnz + 1));                 // 5 its columns
-    t[k++] = B.take(8 * (size_t)(nnz + 1));                 // 6 its values
-    t[k++] = B.take(4 * (size_t)(csc_chunks(n) + 1) * p);   // 7 chunk pointers
+    const bool up = !P.resident;                            // pieces 0 .. 7: the handle's (and the caller's y) in resident mode
+    t[k++] = B.take(up ? 8 * (size_t)(p + 1) : 0);                   // 0 colptr
+    t[k++] = B.take(up ? 4 * (size_t)(nnz + 1) : 0);                 // 1 rowidx
+    t[k++] = B.take(up ? 8 * (size_t)(nnz + 1) : 0);                 // 2 values
+    t[k++] = B.take(up ? 8 * (size_t)n : 0);                         // 3 y
+    t[k++] = B.take(up ? 8 * (size_t)(n + 1) : 0);                   // 4 rowptr of the row copy
+    t[k++] = B.take(up ? 4 * (size_t)(nnz + 1) : 0);                 // 5 its columns
+    t[k++] = B.take(up ? 8 * (size_t)(nnz + 1) : 0);                 // 6 its values
+    t[k++] = B.take(up ? 4 * (size_t)(csc_chunks(n) + 1) * p : 0);   // 7 chunk pointers
     t[k++] = B.take(8 * (size_t)n);                         // 8 W
     t[k++] = B.take(8 * (size_t)n);                         // 9 r
     t[k++] = B.take(8 * 3 * (size_t)P.nchunk);              // 10 row partials
@@ -214,9 +244,10 @@ static size_t lsp_layout(const LspPlan &P, int64_t n, int p, int64_t nnz, int nu
     return B.off;
 }
 
-static LspPlan lsp_plan(int64_t n, int p, int64_t nnz, int intercept, int num_cu)
+static LspPlan lsp_plan(int64_t n, int p, int64_t nnz, int intercept, int num_cu, bool resident = false)
 {
     LspPlan P;
+    P.resident = resident ? 1 : 0;
     const int q = p + (intercept ? 1 : 0);
     const SparseRoute R = sparse_route(n, p, nnz);
     P.csc = R.csc;
@@ -248,51 +279,75 @@ struct SparseLogitData final : LogitData {
     oemgpu_ctx *c;
     int64_t n, nnz, maxcol;
     int p, q, intercept, standardize;
-    const int64_t *h_colptr, *h_rowptr;
-    const int32_t *h_rowidx;
-    const double *h_val, *h_y;
+    const int64_t *h_colptr = nullptr, *h_rowptr = nullptr;
+    const int32_t *h_rowidx = nullptr;
+    const double *h_val = nullptr, *h_y = nullptr;
+    const oemgpu_sparse_x *res = nullptr;   // resident mode: the arrays are the handle's, y_res the caller's device y
+    const double *y_res = nullptr;
+    const int32_t *foldid = nullptr;        // a fold fit (resident mode): device, n entries; null: every row is in the fit
+    int32_t leave_out = 0;
+    int64_t n_eff = 0;                      // rows in the fit
+    std::vector<int64_t> kept_row;          // fold fit: the row of the k-th kept row, k < min(irls_maxit, n_eff)
     LspPlan P;
-    int64_t *colptr = nullptr, *rowptr = nullptr;
-    int32_t *rowidx = nullptr, *ccol = nullptr, *cptr = nullptr;
-    double *val = nullptr, *y = nullptr, *cval = nullptr, *W = nullptr, *r = nullptr, *part = nullptr, *cw = nullptr, *swd = nullptr,
+    const int64_t *colptr = nullptr, *rowptr = nullptr;
+    const int32_t *rowidx = nullptr, *ccol = nullptr, *cptr = nullptr;
+    const double *val = nullptr, *y = nullptr, *cval = nullptr;
+    double *W = nullptr, *r = nullptr, *part = nullptr, *cw = nullptr, *swd = nullptr,
            *mb = nullptr, *ma = nullptr, *gw = nullptr, *tile = nullptr, *tp = nullptr, *vp = nullptr;
 
+    // The row whose W the floor tests at IRLS step i (h :963-969 tests W(i) of the rows it was given)
+    int64_t floor_row(int64_t i) const { return foldid ? (i < (int64_t)kept_row.size() ? kept_row[(size_t)i] : -1) : i; }
     size_t ws_bytes() const override { return P.ws_bytes; }
     int bind(char *ws) override
     {
         size_t o[20];
         lsp_layout(P, n, p, nnz, c->num_cu, o);
-        colptr = (int64_t *)(ws + o[0]); rowidx = (int32_t *)(ws + o[1]); val = (double *)(ws + o[2]); y = (double *)(ws + o[3]);
-        rowptr = (int64_t *)(ws + o[4]); ccol = (int32_t *)(ws + o[5]); cval = (double *)(ws + o[6]); cptr = (int32_t *)(ws + o[7]);
         W = (double *)(ws + o[8]); r = (double *)(ws + o[9]); part = (double *)(ws + o[10]); cw = (double *)(ws + o[11]); swd = (double *)(ws + o[12]);
         mb = (double *)(ws + o[13]); ma = (double *)(ws + o[14]);
         if (P.csc) gw = (double *)(ws + o[15]);
         else { tile = (double *)(ws + o[15]); tp = (double *)(ws + o[16]); vp = (double *)(ws + o[17]); }
         intval = swd + SW_INTVAL;
         hipStream_t s = c->stream;
-        OEM_HIP(hipMemcpyAsync(colptr, h_colptr, 8 * (size_t)(p + 1), hipMemcpyHostToDevice, s));
-        if (nnz > 0) {
-            OEM_HIP(hipMemcpyAsync(rowidx, h_rowidx, 4 * (size_t)nnz, hipMemcpyHostToDevice, s));
-            OEM_HIP(hipMemcpyAsync(val, h_val, 8 * (size_t)nnz, hipMemcpyHostToDevice, s));
+        if (res) {                                        // nothing to upload, nothing to convert
+            colptr = res->colptr; rowidx = res->rowidx; val = res->val; y = y_res;
+            rowptr = res->rowptr; ccol = res->ccol; cval = res->cval; cptr = res->cptr;
+            hipLaunchKernelGGL(lsp_zero_words_kernel, dim3(1), dim3(64), 0, s, swd);        // init_oem: xxdiag = intval = 0 (h :731-732)
+            OEM_HIP(hipGetLastError());
+            return 0;
         }
-        OEM_HIP(hipMemcpyAsync(y, h_y, 8 * (size_t)n, hipMemcpyHostToDevice, s));
-        OEM_HIP(hipMemcpyAsync(rowptr, h_rowptr, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, s));
+        int64_t *d_colptr = (int64_t *)(ws + o[0]), *d_rowptr = (int64_t *)(ws + o[4]);
+        int32_t *d_rowidx = (int32_t *)(ws + o[1]), *d_ccol = (int32_t *)(ws + o[5]), *d_cptr = (int32_t *)(ws + o[7]);
+        double *d_val = (double *)(ws + o[2]), *d_y = (double *)(ws + o[3]), *d_cval = (double *)(ws + o[6]);
+        colptr = d_colptr; rowidx = d_rowidx; val = d_val; y = d_y; rowptr = d_rowptr; ccol = d_ccol; cval = d_cval; cptr = d_cptr;
+        OEM_HIP(hipMemcpyAsync(d_colptr, h_colptr, 8 * (size_t)(p + 1), hipMemcpyHostToDevice, s));
+        if (nnz > 0) {
+            OEM_HIP(hipMemcpyAsync(d_rowidx, h_rowidx, 4 * (size_t)nnz, hipMemcpyHostToDevice, s));
+            OEM_HIP(hipMemcpyAsync(d_val, h_val, 8 * (size_t)nnz, hipMemcpyHostToDevice, s));
+        }
+        OEM_HIP(hipMemcpyAsync(d_y, h_y, 8 * (size_t)n, hipMemcpyHostToDevice, s));
+        OEM_HIP(hipMemcpyAsync(d_rowptr, h_rowptr, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(lsp_zero_words_kernel, dim3(1), dim3(64), 0, s, swd);            // init_oem: xxdiag = intval = 0 (h :731-732)
         OEM_HIP(hipGetLastError());
-        int rc = launch_csc_chunk_ptr(s, colptr, rowidx, n, p, cptr);
-        if (!rc) rc = launch_csc_to_csr(s, colptr, rowidx, val, cptr, n, p, rowptr, ccol, cval);
+        int rc = launch_csc_chunk_ptr(s, d_colptr, d_rowidx, n, p, d_cptr);
+        if (!rc) rc = launch_csc_to_csr(s, d_colptr, d_rowidx, d_val, d_cptr, n, p, d_rowptr, d_ccol, d_cval);
         return rc;
     }
     int scale(double *sc) override
     {
         if (!standardize) return launch_logit_fill(c->stream, sc, p, 1.0);
-        hipLaunchKernelGGL(lsp_scale_kernel, dim3(p), dim3(256), 0, c->stream, colptr, val, n, sc);
+        if (foldid) hipLaunchKernelGGL(lsp_scale_kernel<true>, dim3(p), dim3(256), 0, c->stream, colptr, rowidx, val, n_eff, sc, foldid, leave_out);
+        else hipLaunchKernelGGL(lsp_scale_kernel<false>, dim3(p), dim3(256), 0, c->stream, colptr, rowidx, val, n, sc, nullptr, 0);
         OEM_HIP(hipGetLastError());
         return 0;
     }
     int xy0(const double *, double *g) override
     {
-        hipLaunchKernelGGL(lsp_cols_kernel, dim3(p + 1), dim3(256), 0, c->stream, colptr, rowidx, val, p, y, nullptr, part, P.nchunk, 1, g, cw, swd);
+        const double *yk = y;
+        if (foldid) {                                      // kept ? y : 0 into the r buffer, which the first row pass overwrites
+            hipLaunchKernelGGL(lsp_kept_y_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, y, foldid, leave_out, n, r);
+            yk = r;
+        }
+        hipLaunchKernelGGL(lsp_cols_kernel, dim3(p + 1), dim3(256), 0, c->stream, colptr, rowidx, val, p, yk, nullptr, part, P.nchunk, 1, g, cw, swd);
         OEM_HIP(hipGetLastError());
         return 0;
     }
@@ -300,8 +355,15 @@ struct SparseLogitData final : LogitData {
     {
         hipStream_t s = c->stream;
         const size_t lds = 8 * (size_t)p;
-        if (lds_limit_once(reinterpret_cast<const void *>(&lsp_rows_kernel), lds)) return OEMGPU_ERR_HIP;
-        hipLaunchKernelGGL(lsp_rows_kernel, dim3((unsigned)P.nchunk), dim3(256), lds, s, rowptr, ccol, cval, n, p, y, beta, sc, intercept, i, P.ch, W, r, part);
+        if (foldid) {
+            if (lds_limit_once(reinterpret_cast<const void *>(&lsp_rows_kernel<true>), lds)) return OEMGPU_ERR_HIP;
+            hipLaunchKernelGGL(lsp_rows_kernel<true>, dim3((unsigned)P.nchunk), dim3(256), lds, s, rowptr, ccol, cval, n, p, y, beta, sc, intercept,
+                               floor_row(i), P.ch, W, r, part, foldid, leave_out);
+        } else {
+            if (lds_limit_once(reinterpret_cast<const void *>(&lsp_rows_kernel<false>), lds)) return OEMGPU_ERR_HIP;
+            hipLaunchKernelGGL(lsp_rows_kernel<false>, dim3((unsigned)P.nchunk), dim3(256), lds, s, rowptr, ccol, cval, n, p, y, beta, sc, intercept, i,
+                               P.ch, W, r, part, nullptr, 0);
+        }
         hipLaunchKernelGGL(lsp_cols_kernel, dim3(p + 1), dim3(256), 0, s, colptr, rowidx, val, p, r, W, part, P.nchunk, 0, g, cw, swd);
         OEM_HIP(hipGetLastError());
         return 0;
@@ -314,8 +376,9 @@ struct SparseLogitData final : LogitData {
                              : csc_tile_moments(c, R, colptr, rowidx, val, W, nullptr, n, p, maxcol, tile, tp, vp, mb, ma);
         if (rc) return rc;
         const double *M = P.csc ? mb : ma;
-        if (intercept) hipLaunchKernelGGL(lsp_intval_kernel, dim3(1), dim3(256), 0, s, M, p, sc, (double)n, swd);
-        hipLaunchKernelGGL(lsp_xx_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, M, p, intercept, sc, cw, swd, (double)n, xx);
+        const double ne = (double)(foldid ? n_eff : n);
+        if (intercept) hipLaunchKernelGGL(lsp_intval_kernel, dim3(1), dim3(256), 0, s, M, p, sc, ne, swd);
+        hipLaunchKernelGGL(lsp_xx_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, M, p, intercept, sc, cw, swd, ne, xx);
         OEM_HIP(hipGetLastError());
         return 0;
     }
@@ -323,26 +386,30 @@ struct SparseLogitData final : LogitData {
 
 }  // namespace
 
-// the checks that need no device: the refusals, then the compressed-column arrays (csc_check); fills the row pointers of the row copy
-// and the longest column
-static int lsp_check(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, int32_t standardize, int32_t intercept,
-                     int32_t irls_maxit, double irls_tol, const oemgpu_opts *o, std::vector<int64_t> *rowptr, int64_t *maxcol)
+// the refusals that need neither a device nor the arrays, in `who`'s name
+static int lsp_check_fit(const char *who, int64_t n, int32_t p, int32_t standardize, int32_t intercept, int32_t irls_maxit, double irls_tol,
+                         const oemgpu_opts *o)
 {
-    if (n < 1 || p < 1) { set_error("fit_logistic_sparse: bad dimensions"); return OEMGPU_ERR_ARG; }
+    if (n < 1 || p < 1) { set_error("%s: bad dimensions", who); return OEMGPU_ERR_ARG; }
     if (intercept && !standardize) {
-        set_error("fit_logistic_sparse: intercept = TRUE with standardize = FALSE is not supported (the reference scales the linear predictor by "
-                  "colsq_inv, which it never computes without standardize: ref src/oem_logistic_sparse.h:724, :880)");
+        set_error("%s: intercept = TRUE with standardize = FALSE is not supported (the reference scales the linear predictor by "
+                  "colsq_inv, which it never computes without standardize: ref src/oem_logistic_sparse.h:724, :880)", who);
         return OEMGPU_ERR_UNSUPPORTED;
     }
     if ((int64_t)p + (intercept ? 1 : 0) >= n) {
-        set_error("fit_logistic_sparse: p + intercept >= n is not supported (the reference's XWXt branch never forms grad or XY, "
-                  "ref src/oem_logistic_sparse.h:497-502, :978)");
+        set_error("%s: p + intercept >= n is not supported (the reference's XWXt branch never forms grad or XY, "
+                  "ref src/oem_logistic_sparse.h:497-502, :978)", who);
         return OEMGPU_ERR_UNSUPPORTED;
     }
-    if (p > LOGIT_P_LIMIT) { set_error("fit_logistic_sparse: p > %d is not supported", LOGIT_P_LIMIT); return OEMGPU_ERR_UNSUPPORTED; }
-    int rc = logistic_check(n, p, intercept, 0, irls_maxit, irls_tol, o);
-    if (rc) return rc;
-    const int64_t mc = csc_check("fit_logistic_sparse", n, p, colptr, rowidx, values, rowptr);
+    if (p > LOGIT_P_LIMIT) { set_error("%s: p > %d is not supported", who, LOGIT_P_LIMIT); return OEMGPU_ERR_UNSUPPORTED; }
+    return logistic_check(n, p, intercept, 0, irls_maxit, irls_tol, o);
+}
+
+// the compressed-column arrays (csc_check): fills the row pointers of the row copy and the longest column
+static int lsp_check_csc(const char *who, int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values,
+                         std::vector<int64_t> *rowptr, int64_t *maxcol)
+{
+    const int64_t mc = csc_check(who, n, p, colptr, rowidx, values, rowptr);
     if (mc < 0) return (int)mc;
     for (int64_t i = 0; i < n; ++i) (*rowptr)[(size_t)i + 1] += (*rowptr)[(size_t)i];
     *maxcol = mc;
@@ -363,7 +430,8 @@ int oemgpu_fit_logistic_sparse(int64_t n, int32_t p, const int64_t *colptr, cons
     if (!colptr || !y || !o || !beta || !lambda_out || !niter || !loss || !d) { set_error("fit_logistic_sparse: NULL argument"); return OEMGPU_ERR_ARG; }
     std::vector<int64_t> rowptr;
     int64_t maxcol = 0;
-    int rc = lsp_check(n, p, colptr, rowidx, values, standardize, intercept, irls_maxit, irls_tol, o, &rowptr, &maxcol);
+    int rc = lsp_check_fit("fit_logistic_sparse", n, p, standardize, intercept, irls_maxit, irls_tol, o);
+    if (!rc) rc = lsp_check_csc("fit_logistic_sparse", n, p, colptr, rowidx, values, &rowptr, &maxcol);
     if (rc) return rc;
     oemgpu_ctx *c = ctx_acquire(o->device);
     if (!c) return OEMGPU_ERR_NO_DEVICE;
@@ -379,16 +447,119 @@ int oemgpu_fit_logistic_sparse(int64_t n, int32_t p, const int64_t *colptr, cons
     return rc;
 }
 
+int oemgpu_sparse_x_create(oemgpu_ctx *c, int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values,
+                           oemgpu_sparse_x **out)
+{
+    if (out) *out = nullptr;
+    if (!c || !colptr || !out) { set_error("sparse_x_create: NULL argument"); return OEMGPU_ERR_ARG; }
+    if (n < 1 || p < 1) { set_error("sparse_x_create: bad dimensions"); return OEMGPU_ERR_ARG; }
+    std::vector<int64_t> rowptr;
+    int64_t maxcol = 0;
+    int rc = lsp_check_csc("sparse_x_create", n, p, colptr, rowidx, values, &rowptr, &maxcol);
+    if (rc) return rc;
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const int64_t nnz = colptr[p];
+    Bump B;
+    const size_t a_cp = B.take(8 * (size_t)(p + 1)), a_ri = B.take(4 * (size_t)(nnz + 1)), a_v = B.take(8 * (size_t)(nnz + 1)),
+                 a_rp = B.take(8 * (size_t)(n + 1)), a_cc = B.take(4 * (size_t)(nnz + 1)), a_cv = B.take(8 * (size_t)(nnz + 1)),
+                 a_ch = B.take(4 * (size_t)(csc_chunks(n) + 1) * p);
+    oemgpu_sparse_x *x = new oemgpu_sparse_x;
+    x->device = c->device; x->n = n; x->p = p; x->nnz = nnz; x->maxcol = maxcol; x->bytes = B.off;
+    if (hipMalloc((void **)&x->base, B.off) != hipSuccess) {
+        set_error("sparse_x_create: cannot allocate %zu bytes of device memory", B.off);
+        delete x;
+        return OEMGPU_ERR_HIP;
+    }
+    g_alloc_count += 1;
+    x->colptr = (int64_t *)(x->base + a_cp); x->rowidx = (int32_t *)(x->base + a_ri); x->val = (double *)(x->base + a_v);
+    x->rowptr = (int64_t *)(x->base + a_rp); x->ccol = (int32_t *)(x->base + a_cc); x->cval = (double *)(x->base + a_cv);
+    x->cptr = (int32_t *)(x->base + a_ch);
+    hipStream_t s = c->stream;
+    auto build = [&]() -> int {
+        OEM_HIP(hipMemcpyAsync(x->colptr, colptr, 8 * (size_t)(p + 1), hipMemcpyHostToDevice, s));
+        if (nnz > 0) {
+            OEM_HIP(hipMemcpyAsync(x->rowidx, rowidx, 4 * (size_t)nnz, hipMemcpyHostToDevice, s));
+            OEM_HIP(hipMemcpyAsync(x->val, values, 8 * (size_t)nnz, hipMemcpyHostToDevice, s));
+        }
+        OEM_HIP(hipMemcpyAsync(x->rowptr, rowptr.data(), 8 * (size_t)(n + 1), hipMemcpyHostToDevice, s));
+        int r = launch_csc_chunk_ptr(s, x->colptr, x->rowidx, n, p, x->cptr);
+        if (!r) r = launch_csc_to_csr(s, x->colptr, x->rowidx, x->val, x->cptr, n, p, x->rowptr, x->ccol, x->cval);
+        if (r) return r;
+        OEM_HIP(hipStreamSynchronize(s));                  // the host arrays (rowptr among them) may go once this returns
+        return 0;
+    };
+    rc = build();
+    if (rc) { (void)hipStreamSynchronize(s); (void)hipFree(x->base); delete x; return rc; }
+    *out = x;
+    return 0;
+}
+
+void oemgpu_sparse_x_destroy(oemgpu_sparse_x *x)
+{
+    if (!x) return;
+    int cur = 0;
+    const bool sw_dev = hipGetDevice(&cur) == hipSuccess && cur != x->device && hipSetDevice(x->device) == hipSuccess;
+    (void)hipFree(x->base);                                // (synchronises with the device: nothing still reads the arrays)
+    if (sw_dev) (void)hipSetDevice(cur);
+    delete x;
+}
+
+int oemgpu_fit_logistic_sparse_fold_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
+                                        int32_t leave_out, int32_t standardize, int32_t intercept, int32_t irls_maxit, double irls_tol,
+                                        const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+{
+    static const char *who = "fit_logistic_sparse_fold";
+    if (!c || !x || !y_dev || !o || !beta || !lambda_out || !niter || !loss || !d) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    if (nfolds < 3) { set_error("nfolds must be bigger than 3; nfolds=10 recommended"); return OEMGPU_ERR_ARG; }            // ref R/cv_oem.R:126-127
+    if (leave_out < 0 || leave_out > nfolds) { set_error("%s: leave_out must be in [0, nfolds]", who); return OEMGPU_ERR_ARG; }
+    if (leave_out > 0 && !foldid_dev) { set_error("%s: NULL foldid with leave_out > 0", who); return OEMGPU_ERR_ARG; }
+    int rc = lsp_check_fit(who, x->n, x->p, standardize, intercept, irls_maxit, irls_tol, o);
+    if (rc) return rc;
+    if (c->device != x->device) { set_error("%s: the context and the sparse x are on different devices", who); return OEMGPU_ERR_ARG; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const int64_t n = x->n;
+    const int p = x->p;
+    SparseLogitData D;
+    D.hess_every = true;
+    D.c = c; D.n = n; D.nnz = x->nnz; D.maxcol = x->maxcol; D.p = p; D.q = p + (intercept ? 1 : 0); D.intercept = intercept; D.standardize = standardize;
+    D.res = x; D.y_res = y_dev; D.n_eff = n;
+    if (foldid_dev) {                                      // the ids' range whatever is left out; the masks only with a fold to leave out
+        rc = logit_fold_scan(c, who, foldid_dev, n, nfolds, leave_out, irls_maxit, &D.n_eff, &D.kept_row);
+        if (rc) return rc;
+        if (leave_out > 0) { D.foldid = foldid_dev; D.leave_out = leave_out; }
+    }
+    if ((int64_t)D.q >= D.n_eff) {
+        set_error("%s: p + intercept >= the %lld rows outside fold %d is not supported (the reference's XWXt branch never forms grad or XY, "
+                  "ref src/oem_logistic_sparse.h:497-502, :978)", who, (long long)D.n_eff, (int)leave_out);
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    D.P = lsp_plan(n, p, x->nnz, intercept, c->num_cu, true);          // the plan, the route and the chunking see n
+    rc = logistic_irls(c, D, D.n_eff, p, intercept, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
 // out[0] route (1 csc, 0 row tiles), [1] inner solve (1 one workgroup, 0 launch form), [2] workspace bytes of the fit's own pieces,
 // [3] the bound they stay within, [4] rows per tile (0 on the csc route), [5] row-pass workgroups, [6] rows per row-pass workgroup,
 // [7] chunks of the compressed-column kernels
-int oemgpu_selftest_logistic_sparse_plan(int64_t n, int32_t p, int64_t nnz, int32_t intercept, int32_t num_cu, int64_t *out)
+static int lsp_plan_out(const char *who, int64_t n, int32_t p, int64_t nnz, int32_t intercept, int32_t num_cu, bool resident, int64_t *out)
 {
-    if (n < 1 || p < 1 || nnz < 0 || num_cu < 1 || !out) { set_error("selftest_logistic_sparse_plan: bad argument"); return OEMGPU_ERR_ARG; }
-    const LspPlan P = lsp_plan(n, p, nnz, intercept, num_cu);
+    if (n < 1 || p < 1 || nnz < 0 || num_cu < 1 || !out) { set_error("%s: bad argument", who); return OEMGPU_ERR_ARG; }
+    const LspPlan P = lsp_plan(n, p, nnz, intercept, num_cu, resident);
     out[0] = P.csc; out[1] = P.inner_wg; out[2] = (int64_t)P.ws_bytes; out[3] = (int64_t)P.bound; out[4] = P.rcrows; out[5] = P.nchunk;
     out[6] = P.ch; out[7] = csc_chunks(n);
     return 0;
+}
+
+int oemgpu_selftest_logistic_sparse_plan(int64_t n, int32_t p, int64_t nnz, int32_t intercept, int32_t num_cu, int64_t *out)
+{
+    return lsp_plan_out("selftest_logistic_sparse_plan", n, p, nnz, intercept, num_cu, false, out);
+}
+
+// the same for a fit on a resident x (oemgpu_fit_logistic_sparse_fold_res): out[2] without the pieces the handle and the caller hold
+int oemgpu_selftest_logistic_sparse_res_plan(int64_t n, int32_t p, int64_t nnz, int32_t intercept, int32_t num_cu, int64_t *out)
+{
+    return lsp_plan_out("selftest_logistic_sparse_res_plan", n, p, nnz, intercept, num_cu, true, out);
 }
 
 #pragma GCC visibility pop
