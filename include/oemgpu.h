@@ -423,6 +423,28 @@ int oemgpu_logistic_cv_score_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n
  * bytes fit the 160 KiB of a CU) and 0 if it is read through the cache, out[3] columns per launch, out[4] launches per fold, out[5]
  * dynamic LDS bytes of the largest launch.  OEMGPU_ERR_ARG on n < 1, p outside [1, 8191], ncol < 1 or num_cu < 1. */
 int oemgpu_selftest_cv_score_plan(int64_t n, int32_t p, int32_t ncol, int32_t num_cu, int64_t *out /* 6 */);
+/* cv.oemfit_binomial's AUC on the device (logistic_auc.hip): what R/cv_oem.R:288-307 asks of auc.mat (R/utils.R:90-125, unit weights) for
+ * every fold and column, from the predmat_dev that oemgpu_logistic_cv_score_dev wrote (ncol x n doubles, column c at c n), which stays
+ * where it is.  For fold f (the rows with foldid f, in row order) and column c the rows are ordered by prob ascending with tied
+ * probabilities in row order -- where the reference draws runif, so this order is one of its draws -- and NaN (a row the scoring did
+ * not write) behind every number, NaNs in row order: numpy's stable argsort.  With y2 = (y == y_hi): n1[f] (host, nfolds) = rows with
+ * y2 = 1, n0[f] (host, nfolds) = the rest, u[f ncol + c] (host) = the sum over the rows with y2 = 1 of the rows with y2 = 0 in front of
+ * it; the AUC is u / (n1 n0).  The three are exact integers: a stable least-significant-digit radix sort per (fold, column) segment,
+ * one workgroup each, in LDS when the segment fits and through two workspace buffers otherwise (oemgpu_selftest_cv_auc_plan), no
+ * floating-point arithmetic and no atomics outside LDS: two calls give the same integers.  predmat_dev holds probabilities: a sign
+ * bit is dropped (-0.0 is 0.0).  A fold without rows is not an error (u = n1 = n0 = 0).  OEMGPU_ERR_ARG for a NULL argument, n < 1,
+ * ncol < 1, nfolds < 1 (before any device is looked for) and, from the device, a fold id outside [1, nfolds]; OEMGPU_ERR_UNSUPPORTED
+ * for nfolds > 4096 (a chunk's fold counters sit in LDS) and n >= 2^31. */
+int oemgpu_logistic_cv_auc_dev(oemgpu_ctx *ctx, const double *predmat_dev, int64_t n, int32_t ncol, const double *y_dev, double y_hi,
+                               const int32_t *foldid_dev, int32_t nfolds, int64_t *u, int64_t *n1, int64_t *n0);
+/* Host-only plan of oemgpu_logistic_cv_auc_dev (pure arithmetic, runs without a GPU; the entry takes its launch shape from the same
+ * function) for a call whose longest fold has longest_fold rows: out[0] keys per tile of a sorting pass, out[1] the longest segment
+ * that is sorted in LDS (a longer one goes through the workspace), out[2] columns per batch, out[3] batches, out[4] workspace bytes
+ * (perm, the counting sort's tables, n1, and per column of a batch its nfolds results and -- only when out[6] is 1 -- its two key
+ * buffers, 16 n bytes: the whole kept under 256 MB while one column fits, so that out[2] below ncol depends on n and nfolds alone), out[5] dynamic LDS bytes of the largest launch, out[6] 1 if the longest fold
+ * takes the workspace form, out[7] rows per chunk of the counting sort by fold, out[8] chunks.  OEMGPU_ERR_ARG on n < 1, nfolds
+ * outside [1, 4096], ncol < 1, num_cu < 1 or longest_fold outside [0, n]. */
+int oemgpu_selftest_cv_auc_plan(int64_t n, int32_t nfolds, int32_t ncol, int32_t num_cu, int64_t longest_fold, int64_t *out /* 9 */);
 /* Host-only plan of the binomial fit (pure arithmetic, runs without a GPU): out[0] rows per chunk of the row pass, out[1] chunks
  * (chunk c = rows [c out[0], min(n, (c + 1) out[0]))), out[2] rows per Z block of the moment pass, out[3] Z blocks, out[4] 1 if the
  * inner solve is one persistent workgroup (q <= 1024) and 0 for launch per iteration, out[5] 1 if the row pass stages its sub-blocks

@@ -843,7 +843,8 @@ def logistic_cv_score(x, y, foldid, nfolds, coef, y_hi=None, predmat=False):
     x: a column-major float64 matrix on a GPU, or a SparseX (oemgpu_logistic_cv_score_sparse_res: for finite tables the bits of the
     dense entry on the same matrix written out); y (float64) and foldid (int32, 1 .. nfolds): device tensors; coef: nfolds x ncol x
     (p + 1) on the host, the columns that score the rows of each fold.  Returns (sums: nfolds x ncol x 8 = [sum, sum of squares] of
-    deviance, class, mse, mae; counts: the fold sizes; predmat: n x ncol on the host, or None)."""
+    deviance, class, mse, mae; counts: the fold sizes; predmat: n x ncol on the host, or None).  predmat="device": the third item is
+    the ncol x n device tensor the kernel wrote (column c = row c; rows of no fold stay NaN) and nothing is copied to the host."""
     import torch
     sparse = isinstance(x, SparseX)
     if sparse:
@@ -869,7 +870,54 @@ def logistic_cv_score(x, y, foldid, nfolds, coef, y_hi=None, predmat=False):
                                                      _dptr(coef), ncol, _dptr(sums), counts.ctypes.data_as(C.POINTER(C.c_int64)),
                                                      None if pm is None else pm.data_ptr()))
     del keepalive
+    if isinstance(predmat, str):
+        if predmat != "device":
+            raise ValueError("predmat must be True, False or \"device\"")
+        return sums, counts, pm
     return sums, counts, None if pm is None else pm.t().cpu().numpy()
+
+
+def logistic_cv_auc(predmat_dev, y, foldid, nfolds, y_hi=None):
+    """oemgpu_logistic_cv_auc_dev: the integers behind the AUC of cv.oemfit_binomial (R/cv_oem.R:288-307 with auc.mat, R/utils.R:90-125)
+    for every fold and column of a predmat that stays on the device.  predmat_dev: the ncol x n float64 device tensor of
+    logistic_cv_score(..., predmat="device") (contiguous, column c of predmat = row c); y (float64) and foldid (int32, 1 .. nfolds):
+    device tensors.  The rows of a fold are ordered by prob, ties in row order (numpy's stable argsort; NaN last), y2 = (y == y_hi).
+    Returns (u: nfolds x ncol, n1: nfolds, n0: nfolds) as int64 arrays -- u[f, c] = over the rows with y2 = 1, the rows with y2 = 0 in
+    front of each; n1, n0 = the fold's rows with y2 = 1 and the rest -- exact, the same on every call; _auc_from_counts turns them into
+    the AUC."""
+    import torch
+    if predmat_dev.dim() != 2 or predmat_dev.dtype != torch.float64 or not predmat_dev.is_contiguous():
+        raise ValueError("predmat_dev must be a contiguous ncol x n float64 device tensor")
+    ncol, n = predmat_dev.shape
+    if y.dtype != torch.float64 or foldid.dtype != torch.int32 or y.numel() != n or foldid.numel() != n:
+        raise ValueError("y (float64) and foldid (int32) must have one entry per row of predmat")
+    if y_hi is None:
+        y_hi = float(y.max().item())
+    u = np.zeros((int(nfolds), ncol), dtype=np.int64)
+    n1 = np.zeros(int(nfolds), dtype=np.int64)
+    n0 = np.zeros(int(nfolds), dtype=np.int64)
+    i64 = C.POINTER(C.c_int64)
+    torch.cuda.current_stream(predmat_dev.device).synchronize()
+    L.check(L.lib().oemgpu_logistic_cv_auc_dev(context(predmat_dev.device.index), predmat_dev.data_ptr(), n, ncol, y.data_ptr(), float(y_hi),
+                                               foldid.data_ptr(), int(nfolds), u.ctypes.data_as(i64), n1.ctypes.data_as(i64),
+                                               n0.ctypes.data_as(i64)))
+    return u, n1, n0
+
+
+def cv_auc_plan(n, nfolds, ncol, num_cu, longest_fold):
+    """oemgpu_selftest_cv_auc_plan (needs no GPU): where oemgpu_logistic_cv_auc_dev lands for this shape, as a dict -- tile (keys per
+    tile of a pass), lmax (the longest segment sorted in LDS), cb and batches (columns per batch, batches), ws and lds (workspace and
+    dynamic LDS bytes), form ("lds" / "hbm": the longest fold's), chunk and chunks (the counting sort by fold)."""
+    out = (C.c_int64 * 9)()
+    L.check(L.lib().oemgpu_selftest_cv_auc_plan(int(n), int(nfolds), int(ncol), int(num_cu), int(longest_fold), out))
+    tile, lmax, cb, batches, ws, lds, hbm, chunk, chunks = list(out)
+    return dict(tile=tile, lmax=lmax, cb=cb, batches=batches, ws=ws, lds=lds, form=("lds", "hbm")[hbm], chunk=chunk, chunks=chunks)
+
+
+def _auc_from_counts(u, n1, n0):
+    """u / (n1 n0) as auc.mat writes it (R/utils.R:120-124): through the logarithms; 0/0 and x/0 come out as NaN, as there."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return float(np.exp(np.log(u) - np.log(n1) - np.log(n0)))
 
 
 def _auc_rows(y2, prob):
@@ -879,8 +927,7 @@ def _auc_rows(y2, prob):
     n1 = float(ys.sum())
     n0 = float(len(ys)) - n1
     u = float(np.sum(np.cumsum(1.0 - ys)[ys == 1]))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return float(np.exp(np.log(u) - np.log(n1) - np.log(n0)))
+    return _auc_from_counts(u, n1, n0)
 
 
 _BINOMIAL_NAMES = {"mse": "Mean-Squared Error", "mae": "Mean Absolute Error", "deviance": "Binomial Deviance", "auc": "AUC",
@@ -912,7 +959,7 @@ def _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, fold
             def fit(fd, nfolds, leave_out):                            # the full fit is leave_out = 0 on the same handle
                 return oem_fit_logistic_sparse(sx, yh, penalty=penalty, lambda_=lam_arg, _fold=(sx, fd, max(int(nfolds), 3), leave_out, yd), **kw)
             return _cv_oem_binomial_on(fit, lambda fd, nfolds, coef, **k: logistic_cv_score(sx, yd, fd, nfolds, coef, **k), sx.device,
-                                       n, p, yh, penalty, type_measure, nfolds, foldid, grouped, keep, rng)
+                                       n, p, yh, penalty, type_measure, nfolds, foldid, grouped, keep, rng, yd)
     if _is_torch_cuda(x):
         xd = x if x.dtype == torch.float64 else x.to(torch.float64)
         if not (xd.stride(0) == 1 and xd.stride(1) >= n):
@@ -926,12 +973,13 @@ def _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, fold
             return oem_fit_logistic_dense(xd, yh, penalty=penalty, lambda_=lam_arg, **kw)
         return oem_fit_logistic_dense(xd, yh, penalty=penalty, lambda_=lam_arg, _fold=(fd, nfolds, leave_out, yd), **kw)
     return _cv_oem_binomial_on(fit, lambda fd, nfolds, coef, **k: logistic_cv_score(xd, yd, fd, nfolds, coef, **k), xd.device,
-                               n, p, yh, penalty, type_measure, nfolds, foldid, grouped, keep, rng)
+                               n, p, yh, penalty, type_measure, nfolds, foldid, grouped, keep, rng, yd)
 
 
-def _cv_oem_binomial_on(fit, score, device, n, p, yh, penalty, type_measure, nfolds, foldid, grouped, keep, rng):
+def _cv_oem_binomial_on(fit, score, device, n, p, yh, penalty, type_measure, nfolds, foldid, grouped, keep, rng, yd):
     """_cv_oem_binomial once x is resident.  fit(foldid_dev, nfolds, leave_out): the fit without fold leave_out (0: the full fit, made
-    before the folds are drawn: foldid_dev is then None); score(foldid_dev, nfolds, coef, y_hi=, predmat=): logistic_cv_score on that x."""
+    before the folds are drawn: foldid_dev is then None); score(foldid_dev, nfolds, coef, y_hi=, predmat=): logistic_cv_score on that x;
+    yd: y on the device (the AUC reads it there)."""
     import torch
     fit0 = fit(None, 0, 0)
     nmodels = len(penalty)
@@ -962,9 +1010,7 @@ def _cv_oem_binomial_on(fit, score, device, n, p, yh, penalty, type_measure, nfo
     nl = len(lam[0])
     which_lam = [lam[m] >= max(np.min(o["lambda"][m]) for o in outlist) for m in range(nmodels)]     # no extrapolation to smaller lambdas
     y_hi = float(yh.max())                                            # the second level of as.factor(y)
-    y2 = (yh == y_hi).astype(np.float64)
     term = {"deviance": 0, "class": 2, "mse": 4, "mae": 6}.get(type_measure)
-    want_pred = bool(keep) or type_measure == "auc"
     predlist, cvraw, w = [], [], []
     good = np.zeros((nfolds, nl))
     nlami = 0
@@ -976,18 +1022,20 @@ def _cv_oem_binomial_on(fit, score, device, n, p, yh, penalty, type_measure, nfo
             left, right, frac = _lambda_interp(np.asarray(o["lambda"][m], dtype=np.float64), s)
             b = np.asarray(o["beta"][m])
             coef[i] = (b[:, left] * frac + b[:, right] * (1 - frac)).T
-        sums, counts, pm = score(fd, nfolds, coef, y_hi=y_hi, predmat=want_pred)
-        if want_pred:
+        sums, counts, pm = score(fd, nfolds, coef, y_hi=y_hi, predmat="device" if type_measure == "auc" else bool(keep))
+        if type_measure == "auc":                                      # per fold and column, on the device (R/cv_oem.R:288-307)
+            au, an1, an0 = logistic_cv_auc(pm, yd, fd, nfolds, y_hi=y_hi)
+            pm = pm.t().cpu().numpy() if keep else None                # the host copy only for fit.preval
+        if keep:
             full = np.full((n, nl), np.nan)
             full[:, :nlami] = pm
             predlist.append(full)
         wisum = counts.astype(np.float64)
-        if type_measure == "auc":                                      # per fold and column, on the host (R/cv_oem.R:288-307)
+        if type_measure == "auc":
             raw = np.full((nfolds, nl), np.nan)
             for i in range(nfolds):
-                rows = foldid == i + 1
                 for j in range(nlami):
-                    raw[i, j] = _auc_rows(y2[rows], pm[rows, j])
+                    raw[i, j] = _auc_from_counts(float(au[i, j]), float(an1[i]), float(an0[i]))
             cvraw.append(raw); w.append(wisum)
         elif grouped:                                                  # cvcompute (R/utils.R:128-144): fold means, weighted by fold size
             raw = np.full((nfolds, nl), np.nan)
@@ -1038,7 +1086,8 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
     family = "binomial" (cv.oemfit_binomial, :224-346; dense x): x goes to the device once (a numpy x is uploaded, a device tensor is used as it
     is); the full fit, the fold fits -- row passes over that x which leave the fold's rows out, oemgpu_fit_logistic_dense_fold_dev -- and
     the scoring of the held-out rows (oemgpu_logistic_cv_score_dev) read it there.  type_measure: "deviance" (default), "class", "mse",
-    "mae" or "auc" (on the host, from the held-out probabilities; ties in row order).  `parallel` is accepted and the folds still run
+    "mae" or "auc" (on the device, from the held-out probabilities where the scoring wrote them: oemgpu_logistic_cv_auc_dev, a stable
+    sort per fold and column, ties in row order; only keep=True copies them to the host).  `parallel` is accepted and the folds still run
     one after another.  The options are those of oem_fit_logistic_dense; the result has the keys below with an OemFitBinomial `oem.fit`.
     family = "binomial" with a scipy.sparse x (R/cv_oem.R:129-175 on a dgCMatrix, which reaches oem_fit_logistic_sparse): one SparseX holds
     the compressed columns and their compressed-row copy on the device; the full fit (leave_out = 0), the fold fits (masked passes,
