@@ -144,6 +144,51 @@ int oemgpu_xval_dense(const double *x, int64_t n, int32_t p, const double *y, co
                       double *beta, double *lambda_out, int32_t *niter, double *loss, double *d,
                       double *cvm, double *cvsd);
 
+/* xval.oem on a dgCMatrix: the call R's front end names (ref R/oem_xval.R:500, .Call("oem_xval_sparse")) and the reference never
+ * shipped (ref R/oem_xval.R:196-201 stops with "sparse matrices not supported yet"; src/oem_init.c registers oem_xval_dense only).
+ * Host arrays in, the argument order of oemgpu_xval_dense without `weights`; the compressed-column arrays as in oemgpu_fit_sparse.
+ * It returns what oemgpu_xval_dense returns on the dense copy of the matrix -- oemXvalDense's semantics (centring and scaling recovered
+ * from moments about 0, the folds on the full fit's lambda grid, cvm / cvsd as there), NOT oemSparse's -- to the last bits of the
+ * moments, and never builds that copy: the columns are rewritten in fold order on the device (fold segments start on multiples of
+ * 8192 rows), the K fold moment buffers come from ONE pass over the non-zeros by the route of oemgpu_fit_sparse (compressed columns
+ * with chunk ranges cut at fold boundaries, or zero-filled row tiles per fold), the K + 1 fits are those of the dense call, and the
+ * CV error is taken over the compressed rows.  nfolds in 2..512; n + 8192 nfolds >= 2^31 is OEMGPU_ERR_UNSUPPORTED; n <= p, or a fold
+ * whose removal leaves <= p rows, is refused like the dense call; a fold id outside 1..nfolds is OEMGPU_ERR_ARG; malformed
+ * compressed-column arrays get OEMGPU_ERR_ARG before any device is looked for.  Observation weights and opts.ngpus > 1 are not served
+ * on a sparse x (OEMGPU_ERR_UNSUPPORTED for the latter). */
+int oemgpu_xval_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, const double *y,
+                       const int32_t *foldid, int32_t nfolds, int32_t standardize, int32_t intercept, int32_t type_measure,
+                       const oemgpu_opts *o,
+                       double *beta, double *lambda_out, int32_t *niter, double *loss, double *d,
+                       double *cvm, double *cvsd);
+/* HIP-event times (ms) of the phases of this thread's last oemgpu_xval_sparse call: [0] upload, [1] fold order (layout, permuted
+ * columns, chunk pointers), [2] fold moments, [3] compressed rows, [4] the K + 1 fits, [5] CV error. */
+#define OEMGPU_XVS_NPHASES 6
+int oemgpu_last_xval_sparse_timings(double *ms /* OEMGPU_XVS_NPHASES */);
+/* Host-only plan of oemgpu_xval_sparse (pure arithmetic, runs without a GPU; the call takes its shape from the same function) for
+ * n rows, p columns, nnz non-zeros, nfolds folds, npen penalties, nl lambdas on a device of num_cu CUs:
+ * out[0] route (1 compressed columns, 0 row tiles: the rule and switches of oemgpu_fit_sparse), [1] chunks of 8192 rows at most
+ * (floor(n / 8192) + nfolds), [2] chunks per range of the Gram launch, [3] ranges per fold at most, [4] ranges in all at most,
+ * [5] rows per tile (tile route), [6] CV-error workgroups (x npen x [8]), [7] CV-error waves = partials, [8] blocks of 64 lambdas,
+ * [9] device bytes of the whole call, [10] the fold alignment (8192), [11] LDS bytes of the Gram kernel (0 on the tile route); and
+ * for the folds (n - nfolds + 1, 1, 1, ...), cut by the function the call uses: [12] ranges of fold 1, [13] ranges in all,
+ * [14] rows of the fold-ordered layout, [15] the chunk at which fold 1's last range ends (= its chunks: no range goes beyond),
+ * [16] the tiles of fold 1 on the tile route (laid from the fold's first row), [17] the row of the fold at which its last tile ends
+ * (= its rows: no tile goes beyond).
+ * OEMGPU_ERR_ARG for non-positive arguments, nfolds outside 2..512 or a NULL out; OEMGPU_ERR_UNSUPPORTED for n + 8192 nfolds >= 2^31. */
+int oemgpu_selftest_xval_sparse_plan(int64_t n, int32_t p, int64_t nnz, int32_t nfolds, int32_t npen, int32_t nl, int32_t num_cu,
+                                     int64_t *out /* 18 */);
+/* Test infrastructure: the fold order and the K fold moment buffers of oemgpu_xval_sparse alone (nothing is fitted, n <= p is fine):
+ * moments_out[nfolds][(p + 2)^2], the moment buffer about 0 of every fold's rows (an absent fold: zeros). */
+int oemgpu_selftest_xval_sparse_fold_moments(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values,
+                                             const double *y, const int32_t *foldid, int32_t nfolds, double *moments_out);
+/* Test infrastructure: the fold order, the compressed rows and the CV-error phase of oemgpu_xval_sparse on a coefficient table of the
+ * caller's, coef[nfolds][npen][nl][p + 1] (slot 0 the intercept), mirroring oemgpu_selftest_xval_cv_error_dev: cvm / cvsd [npen][nl]
+ * (no "ols" masking), or with triples != NULL triples[npen][nl][3] = (count, mean, M2) for oemgpu_xval_merge. */
+int oemgpu_selftest_xval_sparse_cv_error(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values,
+                                         const double *y, const int32_t *foldid, int32_t nfolds, const double *coef, int32_t npen,
+                                         int32_t nl, int32_t type_measure, double *cvm, double *cvsd, double *triples /* or NULL */);
+
 /* -------------------------------------------------------------------------------------------
  * Device-resident / staged interface.  Used when X already lives in HBM (bench.py, repeated
  * solves) and by the one-process-per-GPU row-sharded driver (oem_amd/distributed.py), which

@@ -100,6 +100,13 @@ _SIGS = {
                                     C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_xval_dense": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.POINTER(OemgpuOpts)] + _OUT + [_dp, _dp]),
+    "oemgpu_xval_sparse": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, C.POINTER(OemgpuOpts)] + _OUT + [_dp, _dp]),
+    "oemgpu_last_xval_sparse_timings": (C.c_int, [_dp]),
+    "oemgpu_selftest_xval_sparse_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "oemgpu_selftest_xval_sparse_fold_moments": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _dp]),
+    "oemgpu_selftest_xval_sparse_cv_error": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _dp,
+                                                       C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
     "oemgpu_xval_dense_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_int32, C.POINTER(OemgpuOpts)] + _OUT + [_dp, _dp]),
     "oemgpu_xval_moments_len": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

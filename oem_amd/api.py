@@ -706,7 +706,8 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
              lambda_=(), nlambda=100, lambda_min_ratio=None, alpha=1.0, gamma=3.0, tau=0.5, groups=(), penalty_factor=None,
              group_weights=None, standardize=True, intercept=True, maxit=500, tol=1e-7, irls_maxit=100, irls_tol=1e-3,
              compute_loss=False, varnames=None, rng=None, ngpus=0, devices=None, upload_threads=0, interrupt=None):
-    """xval.oem(): R/oem_xval.R:107-460 (gaussian, dense).  foldid: values 1..nfolds; drawn with `rng` (a numpy Generator)
+    """xval.oem(): R/oem_xval.R:107-460 (gaussian; a dense x, or any scipy.sparse x -- oemgpu_xval_sparse, the same result as on
+    x.toarray() without building it; no weights, ngpus or devices there).  foldid: values 1..nfolds; drawn with `rng` (a numpy Generator)
     as sample(rep(seq(nfolds), length = n)) when None.  ngpus / devices (host x only): the rows over several devices inside the
     library, as in oem()."""
     L.sync_switches()
@@ -736,8 +737,12 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
         nfolds = int(foldid.max())
     if nfolds < 3:
         raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
-    if type(x).__module__.startswith("scipy.sparse"):
-        raise ValueError("sparse matrices not supported yet")
+    sparse = _is_scipy_sparse(x)                                 # R/oem_xval.R:196-201 stops here; :500 names the routine served now
+    if sparse and len(weights) > 0:
+        raise ValueError("observation weights of xval.oem need a dense x: the weighted call scales a fold-ordered dense copy by "
+                         "sqrt(w), which a sparse x never builds")
+    if sparse and (int(ngpus) > 1 or devices is not None):
+        raise ValueError("ngpus / devices of xval.oem need a dense x: the rows of a sparse x are not split over devices")
     ylen = y.shape[0] if hasattr(y, "shape") else len(y)
     if ylen != n or len(foldid) != n:
         raise ValueError("x and y lengths do not match")
@@ -773,7 +778,13 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
     fid = np.ascontiguousarray(foldid, dtype=np.int32)
     tm = 1 if type_measure == "mae" else 0
     lib = L.lib()
-    if _is_torch_cuda(x):
+    if sparse:
+        colptr, rowidx, vals = _csc_arrays(x)
+        yh = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+        L.check(lib.oemgpu_xval_sparse(n, p, colptr.ctypes.data, rowidx.ctypes.data, vals.ctypes.data, yh.ctypes.data, fid.ctypes.data,
+                                       int(nfolds), int(bool(standardize)), int(bool(intercept)), tm, C.byref(a.c), *out,
+                                       _dptr(cvm), _dptr(cvsd)))
+    elif _is_torch_cuda(x):
         import torch
         xp, n_, p_, ld, keep = _device_matrix(x)
         yd = y if _is_torch_cuda(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=x.device)
@@ -813,6 +824,64 @@ def xval_cv_plan(n, p, nfolds, npen, nl, num_cu):
     L.check(L.lib().oemgpu_selftest_xval_cv_plan(int(n), int(p), int(nfolds), int(npen), int(nl), int(num_cu), out))
     lt, passes, form, lds, chunks, last, nwg = list(out)
     return dict(lt=lt, passes=passes, form=("single", "multi", "chunk")[form], lds=lds, chunks=chunks, last=last, nwg=nwg)
+
+
+_XVS_PLAN_KEYS = ("csc", "chunks_max", "chunks_per_range", "ranges_per_fold_max", "ranges_max", "tile_rows", "cv_nwg", "cv_waves", "cv_lblk",
+                  "bytes", "align", "gram_lds", "worst_fold_ranges", "worst_ranges", "worst_rows", "worst_fold_end_chunk", "worst_fold_tiles", "worst_fold_tile_end")
+
+
+def xval_sparse_plan(n, p, nnz, nfolds, npen, nl, num_cu):
+    """oemgpu_selftest_xval_sparse_plan (needs no GPU): the plan of xval.oem on a sparse x as a dict -- the route (csc: True / False), the
+    chunk and range bounds, the tile rows, the CV-error launch, the device bytes of the call, and the ranges for the folds
+    (n - nfolds + 1, 1, 1, ...) as the call would cut them (include/oemgpu.h)."""
+    out = (C.c_int64 * 18)()
+    L.check(L.lib().oemgpu_selftest_xval_sparse_plan(int(n), int(p), int(nnz), int(nfolds), int(npen), int(nl), int(num_cu), out))
+    d = dict(zip(_XVS_PLAN_KEYS, list(out)))
+    d["csc"] = bool(d["csc"])
+    return d
+
+
+def xval_sparse_fold_moments(x, y, foldid, nfolds):
+    """oemgpu_selftest_xval_sparse_fold_moments (test infrastructure): the nfolds moment buffers, nfolds x (p + 2) x (p + 2), of a
+    scipy.sparse x in the fold order of xval.oem."""
+    L.sync_switches()
+    n, p = x.shape
+    colptr, rowidx, vals = _csc_arrays(x)
+    yh = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+    fid = np.ascontiguousarray(foldid, dtype=np.int32)
+    out = np.full((int(nfolds), p + 2, p + 2), np.nan)
+    L.check(L.lib().oemgpu_selftest_xval_sparse_fold_moments(n, p, colptr.ctypes.data, rowidx.ctypes.data, vals.ctypes.data, yh.ctypes.data,
+                                                             fid.ctypes.data, int(nfolds), _dptr(out)))
+    return out
+
+
+def xval_sparse_cv_error(x, y, foldid, nfolds, coef, type_measure="mse", triples=False):
+    """oemgpu_selftest_xval_sparse_cv_error (test infrastructure): the CV-error phase of xval.oem on a scipy.sparse x and a coefficient
+    table of the caller's, nfolds x npen x nl x (p + 1) with slot 0 the intercept.  Returns (cvm, cvsd), npen x nl each, or with
+    triples=True the npen x nl x 3 array of (count, mean, M2)."""
+    L.sync_switches()
+    n, p = x.shape
+    colptr, rowidx, vals = _csc_arrays(x)
+    yh = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+    fid = np.ascontiguousarray(foldid, dtype=np.int32)
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    if coef.ndim != 4 or coef.shape[0] != int(nfolds) or coef.shape[3] != p + 1:
+        raise ValueError("coef must be nfolds x npen x nl x (p + 1)")
+    npen, nl = coef.shape[1:3]
+    tm = {"mse": 0, "mae": 1}[type_measure]
+    cvm = np.full((npen, nl), np.nan); cvsd = np.full((npen, nl), np.nan)
+    tri = np.full((npen, nl, 3), np.nan) if triples else None
+    L.check(L.lib().oemgpu_selftest_xval_sparse_cv_error(n, p, colptr.ctypes.data, rowidx.ctypes.data, vals.ctypes.data, yh.ctypes.data,
+                                                         fid.ctypes.data, int(nfolds), _dptr(coef), npen, nl, tm, _dptr(cvm), _dptr(cvsd),
+                                                         None if tri is None else _dptr(tri)))
+    return tri if triples else (cvm, cvsd)
+
+
+def xval_sparse_timings():
+    """oemgpu_last_xval_sparse_timings: HIP-event times (ms) of the phases of this thread's last xval_oem call on a sparse x"""
+    out = (C.c_double * 6)()
+    L.check(L.lib().oemgpu_last_xval_sparse_timings(out))
+    return dict(zip(("upload", "fold_order", "fold_moments", "compressed_rows", "fits", "cv_error"), list(out)))
 
 
 def xval_cv_error(x, y, foldid, nfolds, coef, type_measure="mse", weights=None, triples=False, ctx=None):

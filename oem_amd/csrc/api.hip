@@ -1216,6 +1216,7 @@ void oemgpu_destroy(oemgpu_ctx *c)
     for (oemgpu_ctx *k : c->kids) oemgpu_destroy(k);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     if (c->ev_made) for (int i = 0; i < 2 * OEMGPU_NTIMERS; ++i) (void)hipEventDestroy(c->ev[i]);
+    if (c->xvs_ev_made) for (int i = 0; i <= OEMGPU_XVS_NPHASES; ++i) (void)hipEventDestroy(c->xvs_ev[i]);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2040,29 +2041,36 @@ struct XvalLay {
     GramPlan plmax;
     size_t a_cs, a_cnt, a_fn, a_bad, a_pos, a_xp, a_yp, a_mf, a_mc, a_ms, a_t, a_v, a_b, a_part, a_out, a_peer, total;
 };
-static XvalLay xval_layout(oemgpu_ctx *c, int64_t n, int p, int K, int npen, int nl, bool weighted)
+// sp (xval.oem on a sparse x): the fold segments start on multiples of CSC_CHUNK rows, there is no dense copy (a_xp and the peer
+// staging are empty, the Gram scratch is that of one tile on the tile route and empty on the compressed-column route), the CV-error
+// partials are one per wave of csr_cv_error_kernel; the sparse call's own regions follow at `total` (XvalSparsePlan's offsets)
+static XvalLay xval_layout(int num_cu, int64_t n, int p, int K, int npen, int nl, bool weighted, const XvalSparsePlan *sp = nullptr)
 {
     XvalLay L;
     L.n = n; L.p = p; L.K = K; L.npen = npen; L.nl = nl; L.weighted = weighted;
-    L.ldp = (n + 16 * (int64_t)K + 15) / 16 * 16;
+    L.ldp = sp ? sp->npad_max : (n + 16 * (int64_t)K + 15) / 16 * 16;
     // observation weights: the fold-ordered copy gets a leading column sqrt(w) and everything is scaled by sqrt(w), so the moment
     // kernels see pm = p + 1 data columns and their Gram IS X'WX with its intercept border (ref src/oem_xval_dense.h:486-623)
     L.pm = p + (weighted ? 1 : 0);
     L.mlen = (size_t)oemgpu_moments_len(L.pm); L.cslen = (size_t)p + 1;
-    L.cv = cv_error_plan(n, p, K, npen, nl, c->num_cu);
-    L.plmax = gram_plan_bound(n, L.pm, c->num_cu);             // holds the moment plan of every fold
+    L.cv = cv_error_plan(n, p, K, npen, nl, num_cu);
+    L.plmax = sp ? sp->plmax : gram_plan_bound(n, L.pm, num_cu);   // holds the moment plan of every fold
     Bump A;
     L.a_cs = A.take(sizeof(double) * L.cslen * (2 * (size_t)K + 1));      // per fold, then all folds / all but fold ff
     L.a_cnt = A.take(fold_layout_ints(n, K) * sizeof(int)); L.a_fn = A.take(sizeof(int64_t) * 2 * K); L.a_bad = A.take(256);
-    L.a_pos = A.take(sizeof(int) * (size_t)n); L.a_xp = A.take(sizeof(double) * (size_t)L.ldp * L.pm);
+    L.a_pos = A.take(sizeof(int) * (size_t)n); L.a_xp = A.take(sp ? 0 : sizeof(double) * (size_t)L.ldp * L.pm);
     L.a_yp = A.take(sizeof(double) * (size_t)L.ldp); L.a_mf = A.take(sizeof(double) * L.mlen * K);
     L.a_mc = A.take(sizeof(double) * L.mlen); L.a_ms = A.take(sizeof(double) * L.mlen * (K + 1));
     L.a_t = A.take(L.plmax.tpart_doubles * 8); L.a_v = A.take(L.plmax.vpart_doubles * 8);
     L.a_b = A.take(sizeof(double) * (size_t)K * npen * nl * (p + 1));
-    L.a_part = A.take(sizeof(double) * cv_part_doubles(L.cv.nwg, K, npen, nl)); L.a_out = A.take(sizeof(double) * 3 * (size_t)npen * nl);
-    L.a_peer = A.take(sizeof(double) * (L.mlen + L.cslen) * K);            // another device's fold moments on their way into the sum
+    L.a_part = A.take(sizeof(double) * (sp ? (size_t)sp->cv_waves * npen * sp->nl16 * 4 : cv_part_doubles(L.cv.nwg, K, npen, nl))); L.a_out = A.take(sizeof(double) * 3 * (size_t)npen * nl);
+    L.a_peer = A.take(sp ? 0 : sizeof(double) * (L.mlen + L.cslen) * K);   // another device's fold moments on their way into the sum
     L.total = A.off;
     return L;
+}
+static XvalLay xval_layout(oemgpu_ctx *c, int64_t n, int p, int K, int npen, int nl, bool weighted)
+{
+    return xval_layout(c->num_cu, n, p, K, npen, nl, weighted);
 }
 
 // what every phase needs of the rows and folds, whether or not it fits anything
@@ -2548,6 +2556,207 @@ int oemgpu_xval_dense(const double *x, int64_t n, int32_t p, const double *y, co
     (void)hipStreamSynchronize(c->stream);
     ctx_release(c);
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------- xval.oem on a sparse x
+// Thread-local phase times of the last oemgpu_xval_sparse call (HIP events on the call's stream): upload, fold order (layout, permuted
+// columns, chunk pointers), fold moments, compressed rows, the K + 1 fits, CV error
+static thread_local double g_xvs_ms[OEMGPU_XVS_NPHASES] = {0, 0, 0, 0, 0, 0};
+
+enum { XVS_FULL = 0, XVS_MOMENTS = 1, XVS_CVERR = 2 };
+
+// The call in one place; the two selftests stop early (XVS_MOMENTS: after the K moment buffers) or skip the fits (XVS_CVERR: coefficients
+// of the caller's).  mode != XVS_FULL: o is NULL, npen / nl are the caller's.
+static int xval_sparse_impl(int mode, int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, const double *y,
+                            const int32_t *foldid, int32_t K, int32_t standardize, int32_t intercept, int32_t type_measure, const oemgpu_opts *o,
+                            int npen, int nl, const double *coef, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d,
+                            double *cvm, double *cvsd, double *triples, double *moments_out)
+{
+    const char *who = mode == XVS_FULL ? "xval_sparse" : (mode == XVS_MOMENTS ? "selftest_xval_sparse_fold_moments" : "selftest_xval_sparse_cv_error");
+    int rc = 0;
+    if (mode == XVS_FULL) {
+        rc = check_opts(o, p, p + (intercept ? 1 : 0));
+        if (rc) return rc;
+        npen = o->npen; nl = nl_of(o);
+    } else if (p < 1 || npen < 1 || nl < 1) { set_error("%s: bad p, npen or nl", who); return OEMGPU_ERR_ARG; }
+    if (n < 1) { set_error("xval_sparse: bad n"); return OEMGPU_ERR_ARG; }
+    const int64_t maxcol = csc_check(who, n, p, colptr, rowidx, values, nullptr);     // first, as in oemgpu_fit_sparse (it reads rows against n: n >= 1 comes before it)
+    if (maxcol < 0) return (int)maxcol;
+    if (K < 2 || K > 512) { set_error("xval_dense: nfolds must be in 2..512"); return OEMGPU_ERR_ARG; }
+    if (type_measure != 0 && type_measure != 1) { set_error("xval_dense: type_measure must be 0 (mse) or 1 (mae)"); return OEMGPU_ERR_ARG; }
+    if (n + (int64_t)CSC_CHUNK * K >= (int64_t)1 << 31) { set_error("xval_sparse: n too large for 32-bit row positions"); return OEMGPU_ERR_UNSUPPORTED; }
+    if (mode == XVS_FULL && n <= p) { set_error("dimension of x larger than number of observations"); return OEMGPU_ERR_UNSUPPORTED; }   // ref src/oem_xval_dense.h:690-731
+    const int64_t nnz = colptr[p];
+    oemgpu_ctx *c = ctx_acquire(o ? o->device : -1);
+    if (!c) return OEMGPU_ERR_NO_DEVICE;
+    struct Release { oemgpu_ctx *c; ~Release() { (void)hipStreamSynchronize(c->stream); ctx_release(c); } } release{c};
+    hipStream_t s = c->stream;
+    if (!c->xvs_ev_made) {
+        for (int i = 0; i <= OEMGPU_XVS_NPHASES; ++i) OEM_HIP(hipEventCreate(&c->xvs_ev[i]));
+        c->xvs_ev_made = true;
+    }
+    int nmark = 0;
+    auto mark = [&]() { if (nmark <= OEMGPU_XVS_NPHASES) (void)hipEventRecord(c->xvs_ev[nmark++], s); };
+    for (double &v : g_xvs_ms) v = 0.0;
+
+    const XvalSparsePlan SP = xval_sparse_plan(n, p, nnz, K, npen, nl, c->num_cu);
+    const XvalLay L = xval_layout(c->num_cu, n, p, K, npen, nl, false, &SP);
+    if (ctx_aux(c, L.total + SP.bytes)) return OEMGPU_ERR_HIP;
+    char *ax = c->aux, *sx = c->aux + L.total;
+    int64_t *cd = (int64_t *)(sx + SP.a_col), *rowptr = (int64_t *)(sx + SP.a_rowptr);
+    int32_t *rd = (int32_t *)(sx + SP.a_row), *fd = (int32_t *)(sx + SP.a_fid), *prow = (int32_t *)(sx + SP.a_prow), *cfo = (int32_t *)(sx + SP.a_cfo),
+            *cptr = (int32_t *)(sx + SP.a_cptr), *ccol = (int32_t *)(sx + SP.a_ccol), *rtab_d = (int32_t *)(sx + SP.a_rtab);
+    double *vd = (double *)(sx + SP.a_val), *yd = (double *)(sx + SP.a_y), *pval = (double *)(sx + SP.a_pval), *cval = (double *)(sx + SP.a_cval);
+    int *blockcnt = (int *)(ax + L.a_cnt), *bad = (int *)(ax + L.a_bad), *pos = (int *)(ax + L.a_pos);
+    int64_t *fold_n = (int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
+    double *yp = (double *)(ax + L.a_yp), *mfold = (double *)(ax + L.a_mf), *bdev = (double *)(ax + L.a_b);
+
+    // ---- phase 0: the compressed columns, y and foldid up, once
+    mark();
+    OEM_HIP(hipMemcpyAsync(cd, colptr, sizeof(int64_t) * (size_t)(p + 1), hipMemcpyHostToDevice, s));
+    if (nnz > 0) {
+        OEM_HIP(hipMemcpyAsync(rd, rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, s));
+        OEM_HIP(hipMemcpyAsync(vd, values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, s));
+    }
+    OEM_HIP(hipMemcpyAsync(yd, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemcpyAsync(fd, foldid, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+    // ---- phase 1: fold order
+    mark();
+    rc = launch_fold_layout(s, fd, n, K, blockcnt, fold_n, fold_start, pos, bad, CSC_CHUNK);
+    if (rc) return rc;
+    std::vector<int64_t> hf(2 * (size_t)K, 0);
+    int hbad = 0;
+    OEM_HIP(hipMemcpyAsync(hf.data(), fold_n, sizeof(int64_t) * 2 * K, hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipStreamSynchronize(s));
+    if (hbad) { set_error("xval_dense: foldid must hold values in 1..nfolds"); return OEMGPU_ERR_ARG; }
+    std::vector<int32_t> rtab, frange;
+    int64_t npad = 0;
+    rc = xval_sparse_ranges(SP, hf.data(), rtab, frange, &npad);
+    if (rc) return rc;
+    const int nrange = (int)rtab.size() - 1, nchunk = (int)(npad / CSC_CHUNK);
+    int32_t *frange_d = rtab_d + SP.nrange_max + 1;
+    OEM_HIP(hipMemcpyAsync(rtab_d, rtab.data(), sizeof(int32_t) * rtab.size(), hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemcpyAsync(frange_d, frange.data(), sizeof(int32_t) * frange.size(), hipMemcpyHostToDevice, s));
+    rc = launch_csc_fold_permute(s, cd, rd, vd, yd, fd, pos, n, p, K, npad, cfo, prow, pval, yp);
+    if (!rc) rc = launch_csc_chunk_ptr(s, cd, prow, npad, p, cptr);
+    if (rc) return rc;
+    // ---- phase 2: the K fold moment buffers from one pass over the non-zeros
+    mark();
+    if (SP.R.csc) {
+        rc = launch_csc_fold_moments(s, cd, prow, pval, yp, cptr, cfo, fold_start, fold_n, p, K, nchunk, nrange, rtab_d, frange_d,
+                                     (double *)(sx + SP.a_gpart), (double *)(sx + SP.a_ypart), mfold);
+        if (rc) return rc;
+    } else {
+        for (int k = 0; k < K; ++k) {
+            double *Mk = mfold + L.mlen * k;
+            if (hf[k] == 0) { OEM_HIP(hipMemsetAsync(Mk, 0, sizeof(double) * L.mlen, s)); continue; }
+            rc = csc_tile_moments(c, SP.R, cd, prow, pval, nullptr, yp, npad, p, maxcol, (double *)(sx + SP.a_tile), (double *)(ax + L.a_t),
+                                  (double *)(ax + L.a_v), (double *)(sx + SP.a_mtile), Mk, hf[K + k], hf[k]);
+            if (rc) return rc;
+        }
+    }
+    mark();
+    if (mode == XVS_MOMENTS) {
+        OEM_HIP(hipMemcpyAsync(moments_out, mfold, sizeof(double) * L.mlen * K, hipMemcpyDeviceToHost, s));
+        OEM_HIP(hipStreamSynchronize(s));
+        return 0;
+    }
+    // ---- phase 3: the compressed-row copy of the fold-ordered matrix
+    rc = launch_csr_rowptr(s, cd, prow, cptr, p, nchunk, rowptr);
+    if (!rc) rc = launch_csc_to_csr(s, cd, prow, pval, cptr, npad, p, rowptr, ccol, cval);
+    if (rc) return rc;
+    mark();
+    // ---- phase 4: the K + 1 fits (xval_solve as it is: the moment buffers carry the column sums and n)
+    if (mode == XVS_FULL) rc = xval_solve(c, L, hf.data(), n, standardize, intercept, o, beta, lambda_out, niter, loss, d);
+    else OEM_HIP(hipMemcpyAsync(bdev, coef, sizeof(double) * (size_t)K * npen * nl * (p + 1), hipMemcpyHostToDevice, s));
+    if (rc) return rc;
+    mark();
+    // ---- phase 5: CV error over the compressed rows
+    double *cvout = (double *)(ax + L.a_out);
+    rc = launch_csr_cv_error(s, SP, rowptr, ccol, cval, yp, fold_start, fold_n, bdev, (double *)(sx + SP.a_bt), type_measure, (double *)(ax + L.a_part),
+                             cvout, triples != nullptr);
+    if (rc) return rc;
+    mark();
+    const size_t nk = (size_t)npen * nl;
+    std::vector<double> hc((triples ? 3 : 2) * nk);
+    OEM_HIP(hipMemcpyAsync(hc.data(), cvout, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipStreamSynchronize(s));                           // coef and hc are the caller's and a local
+    for (int i = 0; i + 1 < nmark && i < OEMGPU_XVS_NPHASES; ++i) {
+        float f = 0.f;
+        if (hipEventElapsedTime(&f, c->xvs_ev[i], c->xvs_ev[i + 1]) == hipSuccess) g_xvs_ms[i] = f;
+    }
+    if (triples) { memcpy(triples, hc.data(), sizeof(double) * hc.size()); return 0; }
+    for (int k = 0; k < npen; ++k) {
+        const int nlam = (o && o->penalty[k] == OEMGPU_OLS) ? 1 : nl;      // (the selftest masks nothing)
+        for (int i = 0; i < nl; ++i) {
+            const size_t ki = (size_t)k * nl + i;
+            cvm[ki] = i < nlam ? hc[2 * ki] : 0.0;
+            cvsd[ki] = i < nlam ? hc[2 * ki + 1] : 0.0;
+        }
+    }
+    return 0;
+}
+
+int oemgpu_xval_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, const double *y,
+                       const int32_t *foldid, int32_t nfolds, int32_t standardize, int32_t intercept, int32_t type_measure, const oemgpu_opts *o,
+                       double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, double *cvm, double *cvsd)
+{
+    if (!colptr || !y || !foldid || !o || !beta || !lambda_out || !niter || !loss || !d || !cvm || !cvsd) {
+        set_error("xval_sparse: NULL argument"); return OEMGPU_ERR_ARG;
+    }
+    if (o->ngpus > 1) { set_error("xval_sparse: the rows of a sparse x are not split over devices"); return OEMGPU_ERR_UNSUPPORTED; }
+    return xval_sparse_impl(XVS_FULL, n, p, colptr, rowidx, values, y, foldid, nfolds, standardize, intercept, type_measure, o, 0, 0, nullptr,
+                            beta, lambda_out, niter, loss, d, cvm, cvsd, nullptr, nullptr);
+}
+
+int oemgpu_last_xval_sparse_timings(double *ms)
+{
+    if (!ms) { set_error("NULL argument"); return OEMGPU_ERR_ARG; }
+    for (int i = 0; i < OEMGPU_XVS_NPHASES; ++i) ms[i] = g_xvs_ms[i];
+    return 0;
+}
+
+int oemgpu_selftest_xval_sparse_plan(int64_t n, int32_t p, int64_t nnz, int32_t nfolds, int32_t npen, int32_t nl, int32_t num_cu, int64_t *out)
+{
+    if (n < 1 || p < 1 || nnz < 0 || npen < 1 || nl < 1 || num_cu < 1 || !out) { set_error("selftest_xval_sparse_plan: bad argument"); return OEMGPU_ERR_ARG; }
+    if (nfolds < 2 || nfolds > 512) { set_error("selftest_xval_sparse_plan: nfolds must be in 2..512"); return OEMGPU_ERR_ARG; }
+    if (n + (int64_t)CSC_CHUNK * nfolds >= (int64_t)1 << 31) { set_error("xval_sparse: n too large for 32-bit row positions"); return OEMGPU_ERR_UNSUPPORTED; }
+    const XvalSparsePlan SP = xval_sparse_plan(n, p, nnz, nfolds, npen, nl, num_cu);
+    const XvalLay L = xval_layout(num_cu, n, p, nfolds, npen, nl, false, &SP);
+    // the ranges of the worst case for one fold: n - K + 1 rows in the first fold, one row in every other (n >= K), through the function the call uses
+    std::vector<int64_t> fn((size_t)nfolds, n >= nfolds ? 1 : 0);
+    fn[0] = n >= nfolds ? n - nfolds + 1 : n;
+    std::vector<int32_t> rtab, frange;
+    int64_t npad = 0;
+    int rc = xval_sparse_ranges(SP, fn.data(), rtab, frange, &npad);
+    if (rc) return rc;
+    out[0] = SP.R.csc ? 1 : 0; out[1] = SP.nchunk_max; out[2] = SP.per; out[3] = SP.rpf_max; out[4] = SP.nrange_max; out[5] = SP.R.rows;
+    out[6] = SP.cv_nwg; out[7] = SP.cv_waves; out[8] = SP.cv_lblk; out[9] = (int64_t)(L.total + SP.bytes); out[10] = CSC_CHUNK;
+    out[11] = SP.R.csc ? (int64_t)csc_gram_lds_bytes(p) : 0; out[12] = frange[1] - frange[0]; out[13] = (int64_t)rtab.size() - 1;
+    out[14] = npad; out[15] = rtab[frange[1]];
+    const int64_t ntile = csc_tiles(SP.R, fn[0]);
+    int64_t t0 = 0, t1 = 0;
+    csc_tile_rows(SP.R, 0, fn[0], ntile - 1, &t0, &t1);
+    out[16] = ntile; out[17] = t1;
+    return 0;
+}
+
+int oemgpu_selftest_xval_sparse_fold_moments(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values,
+                                             const double *y, const int32_t *foldid, int32_t nfolds, double *moments_out)
+{
+    if (!colptr || !y || !foldid || !moments_out) { set_error("selftest_xval_sparse_fold_moments: NULL argument"); return OEMGPU_ERR_ARG; }
+    return xval_sparse_impl(XVS_MOMENTS, n, p, colptr, rowidx, values, y, foldid, nfolds, 0, 0, 0, nullptr, 1, 1, nullptr, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, moments_out);
+}
+
+int oemgpu_selftest_xval_sparse_cv_error(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, const double *y,
+                                         const int32_t *foldid, int32_t nfolds, const double *coef, int32_t npen, int32_t nl, int32_t type_measure,
+                                         double *cvm, double *cvsd, double *triples)
+{
+    if (!colptr || !y || !foldid || !coef || (!triples && (!cvm || !cvsd))) { set_error("selftest_xval_sparse_cv_error: NULL argument"); return OEMGPU_ERR_ARG; }
+    return xval_sparse_impl(XVS_CVERR, n, p, colptr, rowidx, values, y, foldid, nfolds, 0, 0, type_measure, nullptr, npen, nl, coef, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, cvm, cvsd, triples, nullptr);
 }
 
 int oemgpu_fit_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, const double *y,

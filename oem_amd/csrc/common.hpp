@@ -71,12 +71,16 @@ int64_t csc_check(const char *who, int64_t n, int p, const int64_t *colptr, cons
                   std::vector<int64_t> *rowcount);
 // the route to the moments: compressed columns when the kernel fits in LDS, nnz <= 2 % of n p (there it beats the n p^2 dense pass)
 // and n < 2^31; else zero-filled row tiles of `rows` rows (<= 2 GiB; set on both routes) and leading dimension ld
+constexpr int CSC_CHUNK = 8192;     // rows per chunk of the compressed-column kernels: 64 KB of LDS
 struct SparseRoute { bool csc; int64_t rows, ld; };
 SparseRoute sparse_route(int64_t n, int p, int64_t nnz);
 // the tile route: per tile of R.rows rows zero it, densify (times sqrt(w[row]) if w), shard_moments -> mtile, add into M in row order.
 // y: the Gaussian fit's y, or null; tpart / vpart: the scratch of gram_plan_bound(R.rows, p)
 int csc_tile_moments(oemgpu_ctx *c, const SparseRoute &R, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *w,
-                     const double *y, int64_t n, int p, int64_t maxcol, double *tile, double *tpart, double *vpart, double *mtile, double *M);
+                     const double *y, int64_t n, int p, int64_t maxcol, double *tile, double *tpart, double *vpart, double *mtile, double *M,
+                     int64_t row0 = 0, int64_t nrows = -1);       // nrows >= 0: the rows [row0, row0 + nrows) only
+int64_t csc_tiles(const SparseRoute &R, int64_t nrows);           // tiles of a row range, and the rows [*r0, *r1) of tile t of the range from row0
+void csc_tile_rows(const SparseRoute &R, int64_t row0, int64_t nrows, int64_t t, int64_t *r0, int64_t *r1);
 size_t csc_moments_work_bytes(int64_t n, int p);
 bool csc_moments_fits(int p);
 int launch_csc_moments(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *y, int64_t n, int p,
@@ -102,7 +106,7 @@ int launch_resid_loss(hipStream_t s, const double *x, int64_t n, int64_t ld, int
 // ------------------------------------------------------------------ xval.oem (xval.hip)
 size_t fold_layout_ints(int64_t n, int K);
 int launch_fold_layout(hipStream_t s, const int *foldid, int64_t n, int K, int *blockcnt, int64_t *fold_n, int64_t *fold_start,
-                       int *pos, int *bad);
+                       int *pos, int *bad, int align = 16);   // align: fold segments start on multiples of it (16: the MFMA kernels; CSC_CHUNK: a sparse x)
 int launch_gather_rows(hipStream_t s, const double *x, int64_t n, int64_t ld, int p, const double *y, const int *pos,
                        double *xo, int64_t ldo, double *yo);
 int launch_fold_sum(hipStream_t s, const double *M, int K, size_t len, int skip /* 1-based, 0: none */, double *out);
@@ -119,6 +123,47 @@ size_t cv_part_doubles(int nwg, int K, int npen, int nl);
 int launch_cv_error(hipStream_t s, const double *xp, int64_t ldp, const double *yp, const int64_t *fold_start, const int64_t *fold_n,
                     int K, int p, const double *B, int npen, int nl, int mae, int wmode, const CvErrPlan &P, double n, double *part, double *out,
                     bool triples = false);
+int launch_cv_finish(hipStream_t s, const double *part, int nparts, int npen, int nl, double n, double *out, bool triples);
+
+// ------------------------------------------------------------------ xval.oem on a sparse x (xval_sparse.hip, sparse.hip)
+// The ONE host plan of the call (pure arithmetic): the route of sparse_route, the fold-ordered layout (fold segments start on multiples of
+// CSC_CHUNK rows: at most nchunk_max = floor(n / CSC_CHUNK) + K chunks, npad_max rows), the chunk ranges of csc_gram_kernel (`per` chunks
+// each and never across a fold boundary: at most nrange_max in all, rpf_max in one fold), the CV-error launch over the compressed rows
+// (cv_nwg workgroups of XVS_CVW waves x npen x cv_lblk blocks of 64 lambdas; one partial per wave) and the byte offsets of everything the
+// call keeps on the device behind the xval layout (api.hip: xval_layout), `bytes` in all.  Nothing of n p doubles on the csc route.
+constexpr int XVS_CVW = 4;
+struct XvalSparsePlan {
+    SparseRoute R;
+    int64_t n, nnz, npad_max;
+    int p, K, npen, nl, nl16;
+    int nchunk_max, per, nrange_max, rpf_max, cv_nwg, cv_waves, cv_lblk;
+    GramPlan plmax;                                              // tile route: the scratch of the MFMA pass over one tile (zero on the csc route)
+    size_t a_col, a_row, a_val, a_y, a_fid, a_prow, a_pval, a_cfo, a_cptr, a_rowptr, a_ccol, a_cval, a_gpart, a_ypart, a_rtab, a_bt, a_tile,
+           a_mtile, bytes;
+};
+XvalSparsePlan xval_sparse_plan(int64_t n, int p, int64_t nnz, int K, int npen, int nl, int num_cu);
+// the ranges of the folds as they are: rtab[r] .. rtab[r + 1] the chunks of range r, frange[k] .. frange[k + 1] the ranges of fold k; *npad
+// <- the rows of the fold-ordered layout.  OEMGPU_ERR_INTERNAL if they exceed the plan's bounds
+int xval_sparse_ranges(const XvalSparsePlan &P, const int64_t *fold_n, std::vector<int32_t> &rtab, std::vector<int32_t> &frange, int64_t *npad);
+// compressed columns into fold order (stable inside a column and fold): prow / pval, cfo[p][K + 1] where fold k's entries of a column start
+// (offsets inside the column), yp[npad] <- y in the same order (padding rows 0)
+int launch_csc_fold_permute(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *y, const int32_t *foldid,
+                            const int *pos, int64_t n, int p, int K, int64_t npad, int32_t *cfo, int32_t *prow, double *pval, double *yp);
+// the K moment buffers of the csc route: the range sums of csc_gram_kernel added in range order inside every fold, the per-fold statistics
+int launch_csc_fold_moments(hipStream_t s, const int64_t *colptr, const int32_t *prow, const double *pval, const double *yp, const int32_t *cptr,
+                            const int32_t *cfo, const int64_t *fold_start, const int64_t *fold_n, int p, int K, int nchunk, int nrange,
+                            const int32_t *rtab, const int32_t *frange, double *gpart, double *ypart, double *mfold);
+// row pointers of the fold-ordered compressed rows from the chunk pointers (rowptr[nchunk * CSC_CHUNK + 1])
+int launch_csr_rowptr(hipStream_t s, const int64_t *colptr, const int32_t *prow, const int32_t *cptr, int p, int nchunk, int64_t *rowptr);
+// CV error over the compressed rows: B [K][npen][nl][p + 1] -> bt [K][npen][p + 1][nl16], one partial per wave, then cv_finish_kernel
+int launch_csr_cv_error(hipStream_t s, const XvalSparsePlan &P, const int64_t *rowptr, const int32_t *ccol, const double *cval, const double *yp,
+                        const int64_t *fold_start, const int64_t *fold_n, const double *B, double *bt, int mae, double *part, double *out,
+                        bool triples);
+int launch_csc_gram_ranges(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const int32_t *cptr, int p, int nchunk,
+                           int nrange, const int32_t *rtab, double *part);
+size_t csc_gram_lds_bytes(int p);
+int csc_range_budget(int64_t n, int p);                           // the ~1024-workgroup range count of launch_csc_moments
+
 // observation weights of xval.oem (ref src/oem_xval_dense.h:486-623): unweighted column sums of squares per fold, then the
 // fold-ordered copy times sqrt(w); and the weighted counterpart of launch_finalize
 int launch_weight_scale(hipStream_t s, double *xp, int64_t ldp, double *yp, int p, int K, const int64_t *fold_start, const int64_t *fold_n,

@@ -31,6 +31,8 @@ struct oemgpu_ctx {
     bool timing = false;
     hipEvent_t ev[2 * OEMGPU_NTIMERS];
     bool ev_made = false;
+    hipEvent_t xvs_ev[8];          // phase marks of xval.oem on a sparse x (events of their own: Timer records into ev[] when timing is on)
+    bool xvs_ev_made = false;
     bool ev_used[OEMGPU_NTIMERS];
     double ms[OEMGPU_NTIMERS];
     double diag[2] = {0.0, 0.0};   // path kernel: shader cycles, 100 MHz ticks

@@ -22,7 +22,7 @@ namespace oemgpu {
 
 namespace {
 
-constexpr int SRC = 8192;           // rows per chunk: 64 KB of LDS
+constexpr int SRC = CSC_CHUNK;      // rows per chunk: 64 KB of LDS
 
 __global__ __launch_bounds__(256) void csc_chunk_ptr_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx, int p,
                                                             int nchunk, int32_t *__restrict__ cptr /* [nchunk + 1][p] */)
@@ -43,7 +43,7 @@ template <bool WEIGHTED>
 __global__ __launch_bounds__(GT) void csc_gram_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx,
                                                       const double *__restrict__ val, const int32_t *__restrict__ cptr, int p, int nchunk,
                                                       int nrange, double *__restrict__ part /* [nrange][p][p]: row a holds G[a][b], b >= a */,
-                                                      const double *__restrict__ w)
+                                                      const double *__restrict__ w, const int32_t *__restrict__ rtab)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *dense = lds;                                         // [SRC]
@@ -52,8 +52,11 @@ __global__ __launch_bounds__(GT) void csc_gram_kernel(const int64_t *__restrict_
     int32_t *cp1 = cp0 + p;                                      // [p] chunk end
     const int tid = threadIdx.x, grp = tid >> 4, l16 = tid & 15;
     // blockIdx.y: a contiguous range of chunks (more workgroups than CUs hide each other's memory round trips; the range sums are
-    // added in range order by csc_finish_kernel)
-    const int cper = (nchunk + nrange - 1) / nrange, c_lo = blockIdx.y * cper, c_hi = c_lo + cper < nchunk ? c_lo + cper : nchunk;
+    // added in range order by csc_finish_kernel).  rtab (xval.oem on a sparse x): range r is the chunks [rtab[r], rtab[r + 1]), cut by
+    // the host so that no range spans two folds
+    const int cper = (nchunk + nrange - 1) / nrange;
+    const int c_lo = rtab ? rtab[blockIdx.y] : blockIdx.y * cper;
+    const int c_hi = rtab ? rtab[blockIdx.y + 1] : (c_lo + cper < nchunk ? c_lo + cper : nchunk);
     double *out = part + (size_t)blockIdx.y * p * p;
     for (int k = tid; k < SRC; k += GT) dense[k] = 0.0;
     for (int half = 0; half < 2; ++half) {
@@ -347,12 +350,26 @@ int launch_csc_moments(hipStream_t s, const int64_t *colptr, const int32_t *rowi
     if (rc) return rc;
     const size_t sh = csc_gram_lds(p);
     if (sh > 64 * 1024) OEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&csc_gram_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    hipLaunchKernelGGL(csc_gram_kernel<false>, dim3((p + 1) / 2, nrange), dim3(GT), sh, s, colptr, rowidx, val, cptr, p, nchunk, nrange, part, nullptr);
+    hipLaunchKernelGGL(csc_gram_kernel<false>, dim3((p + 1) / 2, nrange), dim3(GT), sh, s, colptr, rowidx, val, cptr, p, nchunk, nrange, part, nullptr, nullptr);
     hipLaunchKernelGGL(csc_stats_kernel, dim3(p + NY), dim3(256), 0, s, colptr, rowidx, val, y, n, p, moments, ypart);
     hipLaunchKernelGGL(csc_finish_kernel, dim3((unsigned)(((size_t)p * p + 255) / 256)), dim3(256), 0, s, part, nrange, ypart, NY, n, p, moments);
     OEM_HIP(hipGetLastError());
     return 0;
 }
+
+// xval.oem on a sparse x (xval_sparse.hip): the unweighted kernel over the caller's chunk ranges, part <- [nrange][p][p]
+int launch_csc_gram_ranges(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const int32_t *cptr, int p, int nchunk,
+                           int nrange, const int32_t *rtab, double *part)
+{
+    if (nrange < 1) return 0;
+    const size_t sh = csc_gram_lds(p);
+    if (sh > 64 * 1024 && lds_limit_once(reinterpret_cast<const void *>(&csc_gram_kernel<false>), sh)) return OEMGPU_ERR_HIP;
+    hipLaunchKernelGGL(csc_gram_kernel<false>, dim3((p + 1) / 2, nrange), dim3(GT), sh, s, colptr, rowidx, val, cptr, p, nchunk, nrange, part, nullptr, rtab);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+size_t csc_gram_lds_bytes(int p) { return csc_gram_lds(p); }
+int csc_range_budget(int64_t n, int p) { return csc_ranges(n, p); }
 
 // ---- the binomial fit's pieces (logistic_sparse.hip)
 size_t csc_wgram_work_bytes(int64_t n, int p) { return sizeof(double) * ((size_t)csc_ranges(n, p) * p * p); }
@@ -372,7 +389,7 @@ int launch_csc_wgram(hipStream_t s, const int64_t *colptr, const int32_t *rowidx
     const int nchunk = csc_chunks(n), nrange = csc_ranges(n, p);
     const size_t sh = csc_gram_lds(p);
     if (sh > 64 * 1024 && lds_limit_once(reinterpret_cast<const void *>(&csc_gram_kernel<true>), sh)) return OEMGPU_ERR_HIP;
-    hipLaunchKernelGGL(csc_gram_kernel<true>, dim3((p + 1) / 2, nrange), dim3(GT), sh, s, colptr, rowidx, val, cptr, p, nchunk, nrange, part, w);
+    hipLaunchKernelGGL(csc_gram_kernel<true>, dim3((p + 1) / 2, nrange), dim3(GT), sh, s, colptr, rowidx, val, cptr, p, nchunk, nrange, part, w, nullptr);
     hipLaunchKernelGGL(csc_finish_kernel, dim3((unsigned)(((size_t)p * p + 255) / 256)), dim3(256), 0, s, part, nrange, nullptr, 0, n, p, M);
     OEM_HIP(hipGetLastError());
     return 0;
@@ -432,21 +449,35 @@ int launch_moments_add(hipStream_t s, double *acc, const double *m, size_t len, 
     return 0;
 }
 
-int csc_tile_moments(oemgpu_ctx *c, const SparseRoute &R, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *w,
-                     const double *y, int64_t n, int p, int64_t maxcol, double *tile, double *tpart, double *vpart, double *mtile, double *M)
+// the tiles of the rows [row0, row0 + nrows): laid from row0 in steps of R.rows, the last one cut at the end of the range -- a tile never
+// reaches beyond the range it was asked for (a fold's segment in xval.oem)
+int64_t csc_tiles(const SparseRoute &R, int64_t nrows) { return nrows > 0 ? (nrows + R.rows - 1) / R.rows : 0; }
+void csc_tile_rows(const SparseRoute &R, int64_t row0, int64_t nrows, int64_t t, int64_t *r0, int64_t *r1)
 {
+    *r0 = row0 + t * R.rows;
+    *r1 = *r0 + R.rows < row0 + nrows ? *r0 + R.rows : row0 + nrows;
+}
+
+int csc_tile_moments(oemgpu_ctx *c, const SparseRoute &R, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *w,
+                     const double *y, int64_t n, int p, int64_t maxcol, double *tile, double *tpart, double *vpart, double *mtile, double *M,
+                     int64_t row0, int64_t nrows)
+{
+    if (nrows >= 0) n = row0 + nrows;                              // the rows [row0, row0 + nrows) only (a fold's segment: xval.oem)
     hipStream_t s = c->stream;
     const GramPlan plmax = gram_plan_bound(R.rows, p, c->num_cu);
     const size_t mlen = (size_t)oemgpu_moments_len(p);
-    for (int64_t r0 = 0; r0 < n; r0 += R.rows) {
-        const int64_t r1 = r0 + R.rows < n ? r0 + R.rows : n, nr = r1 - r0;
+    const int64_t ntile = csc_tiles(R, n - row0);
+    for (int64_t t = 0; t < ntile; ++t) {
+        int64_t r0, r1;
+        csc_tile_rows(R, row0, n - row0, t, &r0, &r1);
+        const int64_t nr = r1 - r0;
         OEM_HIP(hipMemsetAsync(tile, 0, sizeof(double) * (size_t)R.ld * p, s));
         if (maxcol > 0) hipLaunchKernelGGL(csc_densify_kernel, dim3((unsigned)((maxcol + 255) / 256), p), dim3(256), 0, s, colptr, rowidx, val, w, r0, r1, R.ld, tile);
         OEM_HIP(hipGetLastError());
         const GramPlan pl = gram_plan(nr, p, c->num_cu);
         if (pl.tpart_doubles > plmax.tpart_doubles || pl.vpart_doubles > plmax.vpart_doubles) { set_error("internal: tile plan larger than its scratch"); return OEMGPU_ERR_INTERNAL; }
         int rc = shard_moments(c, pl, tile, nr, R.ld, y ? y + r0 : tile, nullptr, tpart, vpart, mtile);   // no y: the tile's first column stands in (its moments go unused)
-        if (!rc) rc = launch_moments_add(s, M, mtile, mlen, r0 == 0);
+        if (!rc) rc = launch_moments_add(s, M, mtile, mlen, r0 == row0);
         if (rc) return rc;
     }
     return 0;

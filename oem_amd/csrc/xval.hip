@@ -53,11 +53,11 @@ __global__ __launch_bounds__(64) void fold_scan_kernel(int *__restrict__ blockcn
     if (lane == 0) fold_n[k] = run;
 }
 
-__global__ void fold_start_kernel(const int64_t *__restrict__ fold_n, int K, int64_t *__restrict__ fold_start)
+__global__ void fold_start_kernel(const int64_t *__restrict__ fold_n, int K, int64_t *__restrict__ fold_start, int align)
 {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         int64_t s = 0;
-        for (int k = 0; k < K; ++k) { fold_start[k] = s; s += (fold_n[k] + 15) / 16 * 16; }
+        for (int k = 0; k < K; ++k) { fold_start[k] = s; s += (fold_n[k] + align - 1) / align * align; }
     }
 }
 
@@ -382,13 +382,13 @@ __global__ __launch_bounds__(64) void cv_finish_kernel(const double *__restrict_
 size_t fold_layout_ints(int64_t n, int K) { return (size_t)((n + FB - 1) / FB) * K + 8; }
 
 int launch_fold_layout(hipStream_t s, const int *foldid, int64_t n, int K, int *blockcnt, int64_t *fold_n, int64_t *fold_start,
-                       int *pos, int *bad)
+                       int *pos, int *bad, int align)
 {
     const int nblk = (int)((n + FB - 1) / FB);
     OEM_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
     hipLaunchKernelGGL(fold_count_kernel, dim3(nblk), dim3(FB), sizeof(int) * K, s, foldid, n, K, blockcnt, bad);
     hipLaunchKernelGGL(fold_scan_kernel, dim3(K), dim3(64), 0, s, blockcnt, nblk, K, fold_n);
-    hipLaunchKernelGGL(fold_start_kernel, dim3(1), dim3(64), 0, s, fold_n, K, fold_start);
+    hipLaunchKernelGGL(fold_start_kernel, dim3(1), dim3(64), 0, s, fold_n, K, fold_start, align);
     hipLaunchKernelGGL(fold_pos_kernel, dim3(nblk), dim3(FB), sizeof(int) * 16 * K, s, foldid, n, K, blockcnt, fold_start, pos);
     OEM_HIP(hipGetLastError());
     return 0;
@@ -493,6 +493,14 @@ int launch_cv_error(hipStream_t s, const double *xp, int64_t ldp, const double *
 #undef OEM_CVLT
     if (rc) return rc;
     hipLaunchKernelGGL(cv_finish_kernel, dim3(npen * nl), dim3(64), 0, s, part, nwg * K * CVW, npen, nl, n, out, triples ? 1 : 0);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+// the merge of launch_cv_error alone, for partials some other kernel wrote in the same layout (xval_sparse.hip)
+int launch_cv_finish(hipStream_t s, const double *part, int nparts, int npen, int nl, double n, double *out, bool triples)
+{
+    hipLaunchKernelGGL(cv_finish_kernel, dim3(npen * nl), dim3(64), 0, s, part, nparts, npen, nl, n, out, triples ? 1 : 0);
     OEM_HIP(hipGetLastError());
     return 0;
 }
