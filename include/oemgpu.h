@@ -311,6 +311,43 @@ int oemgpu_selftest_xval_cv_error_dev(oemgpu_ctx *ctx, const double *x_dev, int6
                                       const double *weights_dev /* or NULL */, const int32_t *foldid_dev, int32_t nfolds,
                                       const double *coef, int32_t npen, int32_t nl, int32_t type_measure, double *cvm, double *cvsd,
                                       double *triples /* or NULL */);
+/* cv.oem(family = "gaussian") on a dense x that is resident on the device (R/cv_oem.R:129-175, 349-423; R/utils.R:64-144), in two
+ * phases over the fold layout of the xval phases above (oemgpu_ctx keeps the fold-ordered rows between them).  The caller
+ * interpolates between the two (lambda.interp, R/utils.R:64-98: pure host arithmetic on K small tables).
+ *
+ * 1. oemgpu_cv_fold_fits_dev replaces the K calls `oem(x[!which, ], y[!which], ...)` of R/cv_oem.R:155-175: fold ff's fit is
+ *    oemgpu_fit_dense_dev on the rows whose id is not ff -- DataStd's constants from those rows, the fold's own lambda grid (unless
+ *    opts carries the user's), y scaling -- without gathering them: rows go into fold order once, every fold segment yields one
+ *    moment buffer, and fold ff is solved (OEMGPU_SEM_DENSE) from the sum of the others in fold order.  Moments are taken about 0
+ *    first; if any fold's solve advises a shift (oemgpu_last_shift_advised), the sample sums of ALL rows are taken once, the K
+ *    segment passes are made again about them and every fold is solved again with them (one shift keeps the buffers additive).
+ *    Host outputs: beta[nfolds][npen][nl][p + 1], lambda_out / niter / loss [nfolds][npen][nl], d[nfolds], fold_n[nfolds].
+ *    An id in 1..nfolds that never occurs is allowed: that fold's fit is the fit of all rows.
+ *    Refused before a device is looked for: NULL pointers, the options (as oemgpu_fit_dense_dev), nfolds outside 2..512, n < 1,
+ *    ld < n (OEMGPU_ERR_ARG), n + 16 nfolds >= 2^31, and n - ceil(n / nfolds) <= p -- the largest fold then leaves no more rows
+ *    than columns whatever the ids are (OEMGPU_ERR_UNSUPPORTED).  From the device: an id outside 1..nfolds (OEMGPU_ERR_ARG), and
+ *    n - n_k <= p for some fold k, named in the message (OEMGPU_ERR_UNSUPPORTED: that fit is the wide engine's, not this route's).
+ *
+ * 2. oemgpu_cv_score_dev replaces the prediction loop and the per-fold means of cv.oemfit_gaussian and cvcompute
+ *    (R/cv_oem.R:376-391, R/utils.R:128-144).  coef (host): [nfolds][npen][nl][p + 1], slot 0 the intercept, the caller's table, fold
+ *    k's scoring fold k's rows; ncol[npen] (0..nl): the leading columns of a penalty that are valid.  With v = (y - yhat)^2
+ *    (type_measure 0) or |y - yhat| (1): triples[nfolds][npen][nl][3] <- (count, mean, M2 = sum (v - mean)^2) over fold k's rows,
+ *    merged from the wave partials in a fixed order (two calls give the same bits); columns >= ncol[pen] and empty folds give
+ *    (0, NaN, NaN).  predmat_dev: NULL, or a device buffer [npen][nl][n] that receives yhat in the CALLER'S row order, NaN in columns
+ *    >= ncol[pen].  It needs the fold layout of a call of oemgpu_cv_fold_fits_dev on the same context with the same
+ *    (n, p, nfolds, npen, nl); any xval / cv layout call on that context in between voids it: OEMGPU_ERR_ARG.  Refused before a
+ *    device is looked for: NULL pointers, p, npen, nl < 1, an ncol outside 0..nl, nfolds outside 2..512, type_measure not 0 / 1. */
+int oemgpu_cv_fold_fits_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                            const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                            double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int64_t *fold_n);
+int oemgpu_cv_score_dev(oemgpu_ctx *ctx, int64_t n, int32_t p, int32_t nfolds, const double *coef, int32_t npen, int32_t nl,
+                        const int32_t *ncol, int32_t type_measure, double *triples, double *predmat_dev /* or NULL */);
+/* Test infrastructure (tests/test_gpu_cv_gaussian.py): oemgpu_cv_score_dev after the fold layout alone -- the rows of x_dev / y_dev go
+ * into fold order as in oemgpu_cv_fold_fits_dev, nothing is fitted (a fold may leave fewer rows than columns), then the scoring entry
+ * runs as it is -- so that it can be held against dense random tables.  The row checks of phase 1 and the checks of phase 2. */
+int oemgpu_selftest_cv_score_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                                 const int32_t *foldid_dev, int32_t nfolds, const double *coef, int32_t npen, int32_t nl,
+                                 const int32_t *ncol, int32_t type_measure, double *triples, double *predmat_dev /* or NULL */);
 /* Host-only plan of the CV-error launch (xval.hip: cv_error_plan; pure arithmetic, runs without a GPU; the launch takes its shape from
  * the same function) for n rows, p columns, nfolds folds, npen penalties and nl lambdas on a device of num_cu CUs: out[0] lt = 16-lambda
  * tiles per pass (1..7: all ceil(nl / 16) tiles when there are <= 7, else the fewest passes of at most 7 made even), out[1] passes,
@@ -370,6 +407,7 @@ int oemgpu_eig_max_dev(oemgpu_ctx *ctx, const double *a_dev, int32_t p, double *
 #define OEMGPU_T_FINAL   2   /* moments -> XX, XY, standardisation constants */
 #define OEMGPU_T_EIGPATH 3   /* eigenvalue + penalty x lambda loops */
 #define OEMGPU_T_GRAMK   4   /* the MFMA Gram kernel alone */
+#define OEMGPU_T_FOLDORDER 5 /* xval.oem / cv.oem: the fold layout and the gather of the rows into fold order */
 #define OEMGPU_T_PATHCYC 6   /* not a time: shader cycles of the last fused eigen+path kernel (p <= 192) */
 #define OEMGPU_T_PATHTICKS 7 /* not a time: the same span in 100 MHz ticks (cycles / ticks * 100 MHz = clock held) */
 #define OEMGPU_NTIMERS   8

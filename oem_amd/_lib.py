@@ -118,6 +118,12 @@ _SIGS = {
     "oemgpu_selftest_xval_cv_error_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                     _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
     "oemgpu_selftest_xval_cv_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "oemgpu_cv_fold_fits_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_int32, C.POINTER(OemgpuOpts)] + _OUT + [C.POINTER(C.c_int64)]),      # R/cv_oem.R:155-175
+    "oemgpu_cv_score_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _ip, C.c_int32, _dp,
+                                      C.c_void_p]),                                                                  # R/cv_oem.R:376-391, R/utils.R:128-144
+    "oemgpu_selftest_cv_score_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, _dp,
+                                               C.c_int32, C.c_int32, _ip, C.c_int32, _dp, C.c_void_p]),
     "oemgpu_xval_merge": (C.c_int, [_dp, C.c_int32, C.POINTER(OemgpuOpts), _dp, _dp]),
     "oemgpu_eig_max_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _dp]),
     "oemgpu_last_timings": (C.c_int, [C.c_void_p, _dp]),

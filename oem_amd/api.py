@@ -280,7 +280,7 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
         alpha=1.0, gamma=3.0, tau=0.5, groups=(), penalty_factor=None, group_weights=None, standardize=True,
         intercept=True, maxit=500, tol=1e-7, irls_maxit=100, irls_tol=1e-3, accelerate=False, ncores=-1,
         compute_loss=False, hessian_type="upper.bound", varnames=None, ngpus=0, devices=None, upload_threads=0,
-        interrupt=None, _entry_weights=None):
+        interrupt=None, _entry_weights=None, _args_only=False):
     """oem(): R/oem.R:162-507, dense gaussian branch.  ngpus / devices / upload_threads / interrupt: the host-resident
     options of include/oemgpu.h (`options` gains ngpus / device; absent => one GPU)."""
     L.sync_switches()
@@ -317,6 +317,8 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
     a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, accelerate,
               compute_loss, penalty_factor, groups, unique_groups, group_weights, ngpus=ngpus, devices=devices,
               upload_threads=upload_threads, interrupt=interrupt)
+    if _args_only:                                                     # cv_oem's resident route: the option block of this call, nothing run
+        return a, varnames, bool(standardize), bool(intercept)
     lib = L.lib()
     if is_sparse:                                                      # oem_fit_sparse (ref src/oem_sparse.cpp:30-267)
         colptr, rowidx, vals = _csc_arrays(x)
@@ -906,6 +908,31 @@ def xval_cv_error(x, y, foldid, nfolds, coef, type_measure="mse", weights=None, 
     return tri if triples else (cvm, cvsd)
 
 
+def cv_gaussian_score(x, y, foldid, nfolds, coef, ncol, type_measure="mse", predmat=False, ctx=None):
+    """oemgpu_selftest_cv_score_dev (test infrastructure): the scoring entry of cv.oem(family = "gaussian"), oemgpu_cv_score_dev, after the
+    fold layout alone, on a coefficient table of the caller's.  x: a float64 matrix on a GPU; y (float64), foldid (int32, 1 .. nfolds):
+    device tensors; coef: nfolds x npen x nl x (p + 1) on the host; ncol: the valid leading columns per penalty.  Returns
+    (triples: nfolds x npen x nl x 3 = (count, mean, M2) of every fold's errors; predmat: npen x nl x n on the host in the caller's row
+    order, or None)."""
+    import torch
+    xp, n, p, ld, keepalive = _device_matrix(x)
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    if coef.ndim != 4 or coef.shape[0] != int(nfolds) or coef.shape[3] != p + 1:
+        raise ValueError("coef must be nfolds x npen x nl x (p + 1)")
+    npen, nl = coef.shape[1:3]
+    ncol = np.ascontiguousarray(ncol, dtype=np.int32)
+    if ncol.shape != (npen,):
+        raise ValueError("ncol must hold one count per penalty")
+    tri = np.full((int(nfolds), npen, nl, 3), np.nan)
+    pm = torch.empty((npen, nl, n), dtype=torch.float64, device=x.device) if predmat else None
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_selftest_cv_score_dev(ctx if ctx is not None else context(x.device.index), xp, n, ld, p, y.data_ptr(),
+                                                 foldid.data_ptr(), int(nfolds), _dptr(coef), npen, nl, _iptr(ncol),
+                                                 {"mse": 0, "mae": 1}[type_measure], _dptr(tri), pm.data_ptr() if predmat else None))
+    del keepalive
+    return tri, (pm.cpu().numpy() if predmat else None)
+
+
 # ------------------------------------------------------------------------------------------ cv.oem()
 def logistic_cv_score(x, y, foldid, nfolds, coef, y_hi=None, predmat=False):
     """oemgpu_logistic_cv_score_dev: the error terms of cv.oemfit_binomial (R/cv_oem.R:315-327) over the held-out rows of a resident x.
@@ -1148,10 +1175,160 @@ def _cv_oem_binomial_on(fit, score, device, n, p, yh, penalty, type_measure, nfo
     return res
 
 
+def _cv_gaussian_resident(x, penalty, kw, foldid, nfolds):
+    """Whether cv_oem(family = "gaussian") runs on the x where it is: a dense device tensor, no "ols", one device, and every fold fit in
+    the Gram form (more kept rows than columns).  Anything else is the host loop."""
+    if not _is_torch_cuda(x) or getattr(x, "is_sparse", False) or "ols" in penalty:
+        return False
+    if kw.get("ngpus") or kw.get("devices") is not None or kw.get("_entry_weights") is not None:
+        return False
+    n, p = x.shape
+    if len(foldid) != n or not np.issubdtype(foldid.dtype, np.integer) or foldid.min() < 1 or not 2 <= nfolds <= 512:
+        return False
+    return bool(np.all(n - np.bincount(foldid, minlength=nfolds + 1)[1:] > p))
+
+
+def _cv_gaussian_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw):
+    """The K calls oem(x[!which, ], y[!which], ...) of R/cv_oem.R:155-175 on the resident x: oemgpu_cv_fold_fits_dev.  Returns the fold
+    fits as oem() returns them and what the scoring needs (the context, the shapes, the fold sizes, the option block)."""
+    import types
+    import torch
+    n, p = x.shape
+    a, varnames, standardize, intercept = oem(x, y, penalty=penalty, lambda_=lam_arg, _args_only=True, **kw)
+    xp, _, _, ld, keepalive = _device_matrix(x)
+    yd = y if _is_torch_cuda(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=x.device)
+    yd = yd.to(torch.float64).contiguous().reshape(-1)
+    fd = torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=x.device)
+    ctx = context(x.device.index)
+    K, npen, nl = int(nfolds), a.npen, a.nl
+    beta = np.zeros((K, npen, nl, p + 1))
+    lam_out, loss = np.zeros((K, npen, nl)), np.zeros((K, npen, nl))
+    niter = np.zeros((K, npen, nl), dtype=np.int32)
+    d, fold_n = np.zeros(K), np.zeros(K, dtype=np.int64)
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_cv_fold_fits_dev(ctx, xp, n, ld, p, yd.data_ptr(), fd.data_ptr(), K, int(standardize), int(intercept),
+                                            C.byref(a.c), _dptr(beta), _dptr(lam_out), _iptr(niter), _dptr(loss),
+                                            _dptr(d), fold_n.ctypes.data_as(C.POINTER(C.c_int64))))
+    del keepalive
+    outlist = [_decorate(types.SimpleNamespace(beta=beta[i], lam_out=lam_out[i], niter=niter[i], loss=loss[i],
+                                               d=types.SimpleNamespace(value=float(d[i]))), penalty, varnames, True, int(n - fold_n[i]), p)
+               for i in range(K)]
+    return outlist, {"ctx": ctx, "n": n, "p": p, "K": K, "args": a, "fold_n": fold_n, "device": x.device}
+
+
+def _cv_gaussian_table(outlist, lam, which_lam, p):
+    """coef[K][npen][nl][p + 1] and ncol[npen]: every fold's coefficients at the full fit's lambdas that no fold has to extrapolate to
+    (predict.oem's lambda.interp, R/methods.R:48-109), packed into the leading columns (R/cv_oem.R:364-391)."""
+    K, nmodels, nl = len(outlist), len(lam), len(lam[0])
+    coef = np.zeros((K, nmodels, nl, p + 1))
+    ncol = np.array([int(wl.sum()) for wl in which_lam], dtype=np.int32)
+    for m in range(nmodels):
+        if ncol[m] > 0:
+            for i, o in enumerate(outlist):
+                coef[i, m, :ncol[m]] = predict(o, type="coefficients", s=lam[m][which_lam[m]], which_model=m).T
+    return coef, ncol
+
+
+def _cv_gaussian_score(dev, outlist, lam, which_lam, type_measure, keep):
+    """The prediction loop and the per-fold statistics of cv.oemfit_gaussian (R/cv_oem.R:376-391) on the fold-ordered rows the fold fits
+    left on the device: (triples[K][npen][nl][3] = (count, mean, M2) of every fold's errors, fit.preval per model or None)."""
+    n, p, K = dev["n"], dev["p"], dev["K"]
+    coef, ncol = _cv_gaussian_table(outlist, lam, which_lam, p)
+    nmodels, nl = len(lam), len(lam[0])
+    triples = np.zeros((K, nmodels, nl, 3))
+    pm = None
+    if keep:
+        import torch
+        pm = torch.empty((nmodels, nl, n), dtype=torch.float64, device=dev["device"])
+        torch.cuda.current_stream(dev["device"]).synchronize()
+    L.check(L.lib().oemgpu_cv_score_dev(dev["ctx"], n, p, K, _dptr(coef), nmodels, nl, _iptr(ncol), int(type_measure == "mae"),
+                                        _dptr(triples), pm.data_ptr() if keep else None))
+    return triples, ([np.ascontiguousarray(a.T) for a in pm.cpu().numpy()] if keep else None)
+
+
+def _cv_gaussian_triple_stats(dev, triples, nlams, grouped):
+    """(cvm, cvsd) per model from the per-fold (count, mean, M2).  grouped: cvcompute's fold means (NaN where a fold has no error),
+    weighted by fold size, N from the valid columns (R/utils.R:128-144).  Not grouped: the K fold sets of a column are one set of rows, and
+    oemgpu_xval_merge's sd of the mean is cvcompute's for rows with unit weights (R/cv_oem.R:405-411); NaN where no row has an error."""
+    K, nmodels, nl = triples.shape[:3]
+    if grouped:
+        good = np.zeros((K, nl))
+        for i in range(K):
+            good[i, :nlams[i]] = 1
+        return _cv_weighted_stats([triples[:, m, :, 1].copy() for m in range(nmodels)], [dev["fold_n"].astype(np.float64)] * nmodels,
+                                  [good.sum(axis=0)] * nmodels)
+    cvm, cvsd = np.zeros((nmodels, nl)), np.zeros((nmodels, nl))
+    L.check(L.lib().oemgpu_xval_merge(_dptr(np.ascontiguousarray(triples)), K, C.byref(dev["args"].c), _dptr(cvm), _dptr(cvsd)))
+    for m in range(nmodels):
+        none = triples[:, m, :, 0].sum(axis=0) == 0
+        cvm[m, none] = np.nan; cvsd[m, none] = np.nan
+    return list(cvm), list(cvsd)
+
+
+def _cv_gaussian_host_fits(x, y, foldid, nfolds, penalty, lam_arg, kw, parallel):
+    """The host loop's fold fits: x and y on the host, K gathers of the kept rows, K calls of oem().  (fold fits, x, y)"""
+    xh = np.asarray(x.cpu().numpy() if _is_torch_cuda(x) else x, dtype=np.float64)
+    yh = np.asarray(y.cpu().numpy() if _is_torch_cuda(y) else y, dtype=np.float64).reshape(-1)
+
+    def fold_fit(i):
+        keep_rows = foldid != i
+        return oem(np.asfortranarray(xh[keep_rows]), yh[keep_rows], penalty=penalty, lambda_=lam_arg, **kw)
+    # the p > n warning was given once, by the full fit: only THAT message is silenced for the fold fits, and the filter list is
+    # touched by the calling thread alone, around the whole block (catch_warnings is process-global state: not for worker threads)
+    with warnings.catch_warnings():
+        warnings.filterwarnings("ignore", message=".*optimized for n >> p.*")
+        if parallel:
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(max_workers=min(int(nfolds), 3 if parallel is True else int(parallel))) as ex:
+                outlist = list(ex.map(fold_fit, range(1, nfolds + 1)))
+        else:
+            outlist = [fold_fit(i) for i in range(1, nfolds + 1)]
+    return outlist, xh, yh
+
+
+def _cv_gaussian_host_stats(predlist, yh, foldid, nfolds, nlams, type_measure, grouped):
+    """(cvm, cvsd) per model from the host loop's prediction matrices (R/cv_oem.R:392-423)"""
+    n, nmodels = len(yh), len(predlist)
+    cvraw = [(yh[:, None] - pm) ** 2 if type_measure == "mse" else np.abs(yh[:, None] - pm) for pm in predlist]
+    w = [np.ones(n) for _ in range(nmodels)]
+    N = [n - np.isnan(pm).sum(axis=0) for pm in predlist]
+    if grouped:                                                   # cvcompute: fold means, weighted by fold size
+        wisum = np.array([np.sum(foldid == i) for i in range(1, nfolds + 1)], dtype=np.float64)
+        for m in range(nmodels):
+            out = np.full((nfolds, cvraw[m].shape[1]), np.nan)
+            good = np.zeros_like(out)
+            for i in range(nfolds):
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    out[i] = np.nanmean(cvraw[m][foldid == i + 1], axis=0)
+                good[i, :nlams[i]] = 1
+            cvraw[m], w[m], N[m] = out, wisum, good.sum(axis=0)
+    return _cv_weighted_stats(cvraw, w, N)
+
+
+def _cv_weighted_stats(cvraw, w, N):
+    """cvm = the weighted mean of every column over its entries that are not NaN, cvsd = sqrt(the weighted mean squared deviation / (N - 1))
+    (R/cv_oem.R:412-416), per model"""
+    def wmean(a, wt):
+        ok = ~np.isnan(a)
+        return np.array([np.sum(a[ok[:, j], j] * wt[ok[:, j]]) / np.sum(wt[ok[:, j]]) if ok[:, j].any() else np.nan
+                         for j in range(a.shape[1])])
+    cvm = [wmean(r, wt) for r, wt in zip(cvraw, w)]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cvsd = [np.sqrt(wmean((r - c) ** 2, wt) / (nn - 1)) for r, c, wt, nn in zip(cvraw, cvm, w, N)]
+    return cvm, cvsd
+
+
 def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfolds=10, foldid=None, grouped=True, keep=False,
            rng=None, parallel=False, family="gaussian", **kw):
     """cv.oem(): R/cv_oem.R:56-221 with cv.oemfit_gaussian (:349-423) and cvcompute (R/utils.R:128-144): K + 1 calls of oem(),
     every fold on its own lambda sequence, errors interpolated onto the full fit's lambdas.
+    A dense x that is a device tensor stays there (no "ols", every fold keeps more rows than columns; `parallel` is accepted and ignored):
+    the rows go into fold order once, fold ff's fit is solved from the sum of the other folds' moment buffers -- oem()'s own
+    standardisation, lambda grid and shift rule on the kept rows, oemgpu_cv_fold_fits_dev -- the folds' coefficients are interpolated
+    here (predict's lambda.interp) and the held-out rows are scored where they lie (oemgpu_cv_score_dev: per-fold count, mean and M2;
+    fit.preval in the caller's row order only with keep=True).  Any other x takes the host loop: K gathers of the kept rows, K calls of
+    oem(), predictions and errors in numpy.  Both routes share everything from cvcompute on.
     family = "binomial" (cv.oemfit_binomial, :224-346; dense x): x goes to the device once (a numpy x is uploaded, a device tensor is used as it
     is); the full fit, the fold fits -- row passes over that x which leave the fold's rows out, oemgpu_fit_logistic_dense_fold_dev -- and
     the scoring of the held-out rows (oemgpu_logistic_cv_score_dev) read it there.  type_measure: "deviance" (default), "class", "mse",
@@ -1183,9 +1360,9 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
         raise ValueError("weights not implemented yet.")
     if _is_scipy_sparse(x):
         raise ValueError("cv.oem on a sparse x is served for family = \"binomial\" only (a sparse Gaussian cross-validation is not built)")
-    xh = np.asarray(x.cpu().numpy() if _is_torch_cuda(x) else x, dtype=np.float64)
-    yh = np.asarray(y.cpu().numpy() if _is_torch_cuda(y) else y, dtype=np.float64).reshape(-1)
-    n = xh.shape[0]
+    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("x must have at least two columns")
+    n = x.shape[0]
     lam_arg = () if lambda_ is None else lambda_
     fit0 = oem(x, y, penalty=penalty, lambda_=lam_arg, **kw)
     nz = [np.array([0 if v is None else len(v) for v in predict(fit0, type="nonzero", which_model=m)]) for m in range(len(penalty))]
@@ -1197,19 +1374,11 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
         nfolds = int(foldid.max())
     if nfolds < 3:
         raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
-    def fold_fit(i):
-        keep_rows = foldid != i
-        return oem(np.asfortranarray(xh[keep_rows]), yh[keep_rows], penalty=penalty, lambda_=lam_arg, **kw)
-    # the p > n warning was given once, by the full fit: only THAT message is silenced for the fold fits, and the filter list is
-    # touched by the calling thread alone, around the whole block (catch_warnings is process-global state: not for worker threads)
-    with warnings.catch_warnings():
-        warnings.filterwarnings("ignore", message=".*optimized for n >> p.*")
-        if parallel:
-            from concurrent.futures import ThreadPoolExecutor
-            with ThreadPoolExecutor(max_workers=min(int(nfolds), 3 if parallel is True else int(parallel))) as ex:
-                outlist = list(ex.map(fold_fit, range(1, nfolds + 1)))
-        else:
-            outlist = [fold_fit(i) for i in range(1, nfolds + 1)]
+    resident = _cv_gaussian_resident(x, penalty, kw, foldid, nfolds)
+    if resident:                                                  # x stays where it is: fold moments, K solves (oemgpu_cv_fold_fits_dev)
+        outlist, dev = _cv_gaussian_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw)
+    else:
+        outlist, xh, yh = _cv_gaussian_host_fits(x, y, foldid, nfolds, penalty, lam_arg, kw, parallel)
     # cv.oemfit_gaussian
     if type_measure in ("default", "deviance"):
         type_measure = "mse"
@@ -1219,40 +1388,23 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
     lam = [np.asarray(l, dtype=np.float64) for l in fit0["lambda"]]
     nmodels = len(penalty)
     which_lam = [lam[m] >= max(np.min(o["lambda"][m]) for o in outlist) for m in range(nmodels)]     # no extrapolation to smaller lambdas
-    predlist = [np.full((n, len(lam[0])), np.nan) for _ in range(nmodels)]
-    nlams = np.zeros(nfolds, dtype=int)
-    for i in range(1, nfolds + 1):
-        rows = foldid == i
-        for m in range(nmodels):
-            preds = predict(outlist[i - 1], xh[rows], s=lam[m][which_lam[m]], which_model=m)
-            nlami = int(which_lam[m].sum())
-            predlist[m][rows, :nlami] = preds
-        nlams[i - 1] = nlami
-    cvraw = [(yh[:, None] - pm) ** 2 if type_measure == "mse" else np.abs(yh[:, None] - pm) for pm in predlist]
+    nlams = np.full(nfolds, int(which_lam[-1].sum()))             # nlami of the LAST model, for every fold (R/cv_oem.R:386-389)
+    if resident:                                                  # interpolated tables up, per-fold (count, mean, M2) down (oemgpu_cv_score_dev)
+        triples, predlist = _cv_gaussian_score(dev, outlist, lam, which_lam, type_measure, keep)
+    else:
+        predlist = [np.full((n, len(lam[0])), np.nan) for _ in range(nmodels)]
+        for i in range(1, nfolds + 1):
+            rows = foldid == i
+            for m in range(nmodels):
+                preds = predict(outlist[i - 1], xh[rows], s=lam[m][which_lam[m]], which_model=m)
+                predlist[m][rows, :int(which_lam[m].sum())] = preds
     if n / nfolds < 3 and grouped:
         warnings.warn("Option grouped=FALSE enforced in cv.glmnet, since < 3 observations per fold")
         grouped = False
-    w = [np.ones(n) for _ in range(nmodels)]
-    N = [n - np.isnan(pm).sum(axis=0) for pm in predlist]
-    if grouped:                                                   # cvcompute: fold means, weighted by fold size
-        wisum = np.array([np.sum(foldid == i) for i in range(1, nfolds + 1)], dtype=np.float64)
-        for m in range(nmodels):
-            out = np.full((nfolds, cvraw[m].shape[1]), np.nan)
-            good = np.zeros_like(out)
-            for i in range(nfolds):
-                with warnings.catch_warnings():
-                    warnings.simplefilter("ignore")
-                    out[i] = np.nanmean(cvraw[m][foldid == i + 1], axis=0)
-                good[i, :nlams[i]] = 1
-            cvraw[m], w[m], N[m] = out, wisum, good.sum(axis=0)
-
-    def wmean(a, wt):
-        ok = ~np.isnan(a)
-        return np.array([np.sum(a[ok[:, j], j] * wt[ok[:, j]]) / np.sum(wt[ok[:, j]]) if ok[:, j].any() else np.nan
-                         for j in range(a.shape[1])])
-    cvm = [wmean(cvraw[m], w[m]) for m in range(nmodels)]
-    with np.errstate(invalid="ignore", divide="ignore"):
-        cvsd = [np.sqrt(wmean((cvraw[m] - cvm[m]) ** 2, w[m]) / (N[m] - 1)) for m in range(nmodels)]
+    if resident:
+        cvm, cvsd = _cv_gaussian_triple_stats(dev, triples, nlams, grouped)
+    else:
+        cvm, cvsd = _cv_gaussian_host_stats(predlist, yh, foldid, nfolds, nlams, type_measure, grouped)
     nas = np.zeros(len(lam[0]), dtype=bool)
     for m in range(nmodels):
         nas |= np.isnan(cvsd[m])

@@ -2103,32 +2103,48 @@ static int xval_check(oemgpu_ctx *c, const void *x_dev, const void *y_dev, const
 }
 
 // phase 1: hf <- the local fold sizes [K] and fold starts [K]; mfold (and csq) in aux <- the local rows' per-fold moments
+static int xval_fold_moments(oemgpu_ctx *c, const XvalLay &L, const std::vector<int64_t> &hf, const double *sums);
 static int xval_prepare(oemgpu_ctx *c, const XvalLay &L, const double *x_dev, int64_t ld, const double *y_dev, const double *w_dev,
-                        const int32_t *foldid_dev, std::vector<int64_t> &hf)
+                        const int32_t *foldid_dev, std::vector<int64_t> &hf, bool moments = true)
 {
     const int64_t n = L.n;
     const int K = L.K, p = L.p;
     char *ax = c->aux;
     int *blockcnt = (int *)(ax + L.a_cnt), *bad = (int *)(ax + L.a_bad), *pos = (int *)(ax + L.a_pos);
     int64_t *fold_n = (int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
-    double *xp = (double *)(ax + L.a_xp), *yp = (double *)(ax + L.a_yp), *mfold = (double *)(ax + L.a_mf);
-    // ---- rows into fold order
-    int rc = launch_fold_layout(c->stream, foldid_dev, n, K, blockcnt, fold_n, fold_start, pos, bad);
-    if (rc) return rc;
+    double *xp = (double *)(ax + L.a_xp), *yp = (double *)(ax + L.a_yp);
+    // ---- rows into fold order (whatever cv.oem's layout stamp vouched for is overwritten from here on: cv_lay_out stamps again)
+    c->cv_n = 0;
     hf.assign(2 * K, 0);
-    int hbad = 0;
-    OEM_HIP(hipMemcpyAsync(hf.data(), fold_n, sizeof(int64_t) * 2 * K, hipMemcpyDeviceToHost, c->stream));
-    OEM_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    double *csq = (double *)(ax + L.a_cs);
-    if (w_dev) {
-        rc = launch_gather_rows(c->stream, w_dev, n, n, 1, y_dev, pos, xp, L.ldp, yp);               // column 0 <- w
-        if (!rc) rc = launch_gather_rows(c->stream, x_dev, n, ld, p, y_dev, pos, xp + L.ldp, L.ldp, yp);
-        if (!rc) rc = launch_weight_scale(c->stream, xp, L.ldp, yp, p, K, fold_start, fold_n, csq);
-    } else rc = launch_gather_rows(c->stream, x_dev, n, ld, p, y_dev, pos, xp, L.ldp, yp);
-    if (rc) return rc;
+    int hbad = 0, rc;
+    {
+        Timer t(c, OEMGPU_T_FOLDORDER);
+        rc = launch_fold_layout(c->stream, foldid_dev, n, K, blockcnt, fold_n, fold_start, pos, bad);
+        if (rc) return rc;
+        OEM_HIP(hipMemcpyAsync(hf.data(), fold_n, sizeof(int64_t) * 2 * K, hipMemcpyDeviceToHost, c->stream));
+        OEM_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        double *csq = (double *)(ax + L.a_cs);
+        if (w_dev) {
+            rc = launch_gather_rows(c->stream, w_dev, n, n, 1, y_dev, pos, xp, L.ldp, yp);               // column 0 <- w
+            if (!rc) rc = launch_gather_rows(c->stream, x_dev, n, ld, p, y_dev, pos, xp + L.ldp, L.ldp, yp);
+            if (!rc) rc = launch_weight_scale(c->stream, xp, L.ldp, yp, p, K, fold_start, fold_n, csq);
+        } else rc = launch_gather_rows(c->stream, x_dev, n, ld, p, y_dev, pos, xp, L.ldp, yp);
+        if (rc) return rc;
+    }
     OEM_HIP(hipStreamSynchronize(c->stream));
     if (hbad) { set_error("xval_dense: foldid must hold values in 1..nfolds"); return OEMGPU_ERR_ARG; }
-    // ---- per-fold moments about 0 (ref src/oem_xval_dense.h:358-484), one MFMA pass per fold segment
+    // ---- per-fold moments about 0 (ref src/oem_xval_dense.h:358-484)
+    return moments ? xval_fold_moments(c, L, hf, nullptr) : 0;
+}
+
+// mfold in aux <- the moments of every fold segment of the fold-ordered rows, one MFMA pass each, about 0 or about the shift that
+// `sums` (device: oemgpu_shift_sums_dev's layout) yields -- the same sums for every fold, so that the buffers stay additive
+static int xval_fold_moments(oemgpu_ctx *c, const XvalLay &L, const std::vector<int64_t> &hf, const double *sums)
+{
+    const int K = L.K;
+    char *ax = c->aux;
+    const double *xp = (const double *)(ax + L.a_xp), *yp = (const double *)(ax + L.a_yp);
+    double *mfold = (double *)(ax + L.a_mf);
     for (int k = 0; k < K; ++k) {
         const int64_t nk = hf[k], st = hf[K + k];
         if (nk == 0) { OEM_HIP(hipMemsetAsync(mfold + L.mlen * k, 0, sizeof(double) * L.mlen, c->stream)); continue; }
@@ -2136,7 +2152,7 @@ static int xval_prepare(oemgpu_ctx *c, const XvalLay &L, const double *x_dev, in
         if (pl.tpart_doubles > L.plmax.tpart_doubles || pl.vpart_doubles > L.plmax.vpart_doubles) {
             set_error("internal: fold plan larger than its scratch"); return OEMGPU_ERR_INTERNAL;
         }
-        rc = shard_moments(c, pl, xp + st, nk, L.ldp, yp + st, nullptr, (double *)(ax + L.a_t), (double *)(ax + L.a_v), mfold + L.mlen * k);
+        int rc = shard_moments(c, pl, xp + st, nk, L.ldp, yp + st, sums, (double *)(ax + L.a_t), (double *)(ax + L.a_v), mfold + L.mlen * k);
         if (rc) return rc;
     }
     return 0;
@@ -2417,6 +2433,153 @@ int oemgpu_xval_merge(const double *triples, int32_t nsets, const oemgpu_opts *o
         }
     }
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- cv.oem, family = "gaussian"
+// The layout is xval.oem's (unweighted) with this route's own regions behind it at L.total: the per-fold triples, the valid columns
+// per penalty, the sample sums of a shifted pass, and the inverse of the fold permutation for the prediction store.
+struct CvLay {
+    XvalLay L;
+    size_t a_tri, a_ncol, a_sums, a_inv, total;
+};
+static CvLay cv_layout(oemgpu_ctx *c, int64_t n, int p, int K, int npen, int nl)
+{
+    CvLay V;
+    V.L = xval_layout(c, n, p, K, npen, nl, false);
+    Bump A; A.off = V.L.total;
+    V.a_tri = A.take(sizeof(double) * 3 * (size_t)K * npen * nl); V.a_ncol = A.take(sizeof(int) * (size_t)npen);
+    V.a_sums = A.take(sizeof(double) * (size_t)oemgpu_sums_len(p)); V.a_inv = A.take(sizeof(int) * (size_t)V.L.ldp);
+    V.total = A.off;
+    return V;
+}
+
+static int cv_check_rows(const char *who, int64_t n, int64_t ld, int p, int K)
+{
+    int rc = xval_check_rows(n, ld, K, 0);
+    if (rc) return rc;
+    if (p < 1) { set_error("%s: bad p", who); return OEMGPU_ERR_ARG; }
+    return 0;
+}
+
+// rows into fold order (and the fold moments about 0), and the stamp oemgpu_cv_score_dev looks for
+static int cv_lay_out(oemgpu_ctx *c, const CvLay &V, const double *x_dev, int64_t ld, const double *y_dev, const int32_t *foldid_dev,
+                      bool moments, std::vector<int64_t> &hf)
+{
+    if (ctx_aux(c, V.total)) return OEMGPU_ERR_HIP;
+    int rc = xval_prepare(c, V.L, x_dev, ld, y_dev, nullptr, foldid_dev, hf, moments);
+    if (rc) return rc;
+    c->cv_n = V.L.n; c->cv_p = V.L.p; c->cv_K = V.L.K; c->cv_aux = c->aux; c->cv_hf = hf;
+    return 0;
+}
+
+int oemgpu_cv_fold_fits_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                            const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                            double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int64_t *fold_n)
+{
+    if (!c || !x_dev || !y_dev || !foldid_dev || !o || !beta || !lambda_out || !niter || !loss || !d || !fold_n) {
+        set_error("cv_fold_fits: NULL argument"); return OEMGPU_ERR_ARG;
+    }
+    const int K = nfolds;
+    int rc = check_opts(o, p, p);
+    if (!rc) rc = cv_check_rows("cv_fold_fits", n, ld, p, K);
+    if (rc) return rc;
+    // the largest fold holds at least ceil(n / K) rows: some fold fit is then not the Gram form whatever the ids are
+    if (n - (n + K - 1) / K <= p) {
+        set_error("cv_fold_fits: %lld rows in %d folds leave some fold no more rows than the %d columns", (long long)n, K, p);
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const int npen = o->npen, nl = nl_of(o);
+    const CvLay V = cv_layout(c, n, p, K, npen, nl);
+    const XvalLay &L = V.L;
+    std::vector<int64_t> hf;
+    rc = cv_lay_out(c, V, x_dev, ld, y_dev, foldid_dev, true, hf);
+    if (rc) return rc;
+    for (int k = 0; k < K; ++k) {
+        fold_n[k] = hf[k];
+        if (n - hf[k] <= p) {
+            set_error("cv_fold_fits: fold %d leaves %lld rows for %d columns (the fit of p >= n is not this route's)", k + 1, (long long)(n - hf[k]), p);
+            return OEMGPU_ERR_UNSUPPORTED;
+        }
+    }
+    char *ax = c->aux;
+    const double *mfold = (const double *)(ax + L.a_mf);
+    double *msum = (double *)(ax + L.a_ms), *sums = (double *)(ax + V.a_sums);
+    const size_t blen = (size_t)npen * nl * (p + 1), nk2 = (size_t)npen * nl;
+    // fold ff: the sum of the other folds' moments in fold order, then oem()'s solve on it (R/cv_oem.R:155-175)
+    auto solve_all = [&](const double *sm, bool *advised) -> int {
+        for (int ff = 1; ff <= K; ++ff) {
+            double *ms = msum + L.mlen * ff;
+            int r = launch_fold_sum(c->stream, mfold, K, L.mlen, ff, ms);
+            if (!r) r = oemgpu_solve_moments_dev(c, ms, sm, p, OEMGPU_SEM_DENSE, standardize, intercept, o, beta + blen * (ff - 1),
+                                                 lambda_out + nk2 * (ff - 1), niter + nk2 * (ff - 1), loss + nk2 * (ff - 1), d + (ff - 1));
+            if (r) return r;
+            if (advised && c->shift_advised) *advised = true;
+        }
+        return 0;
+    };
+    bool advised = false;
+    rc = solve_all(nullptr, &advised);
+    if (rc || !advised) return rc;
+    // oemgpu_fit_dense_dev's rule, for all folds at once: sample sums of all rows, the segment passes about them, the solves again
+    rc = launch_shift_sums(c->stream, x_dev, n, ld, p, y_dev, sums);
+    if (!rc) rc = xval_fold_moments(c, L, hf, sums);
+    if (!rc) rc = solve_all(sums, nullptr);
+    return rc;
+}
+
+int oemgpu_cv_score_dev(oemgpu_ctx *c, int64_t n, int32_t p, int32_t nfolds, const double *coef, int32_t npen, int32_t nl,
+                        const int32_t *ncol, int32_t type_measure, double *triples, double *predmat_dev)
+{
+    if (!c || !coef || !ncol || !triples) { set_error("cv_score: NULL argument"); return OEMGPU_ERR_ARG; }
+    if (p < 1 || npen < 1 || nl < 1) { set_error("cv_score: bad p, npen or nl"); return OEMGPU_ERR_ARG; }
+    const int K = nfolds;
+    int rc = xval_check_rows(n, n, K, type_measure);
+    if (rc) return rc;
+    for (int k = 0; k < npen; ++k)
+        if (ncol[k] < 0 || ncol[k] > nl) { set_error("cv_score: ncol[%d] = %d is outside 0..%d", k, ncol[k], nl); return OEMGPU_ERR_ARG; }
+    if (c->cv_n != n || c->cv_p != p || c->cv_K != K || !c->aux || c->cv_aux != c->aux || (int)c->cv_hf.size() != 2 * K) {
+        set_error("cv_score: call oemgpu_cv_fold_fits_dev with the same n, p and nfolds on this context first"); return OEMGPU_ERR_ARG;
+    }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const CvLay V = cv_layout(c, n, p, K, npen, nl);
+    const XvalLay &L = V.L;
+    if (c->aux_bytes < V.total) { set_error("cv_score: npen and nl must be those of the call that laid the rows out"); return OEMGPU_ERR_ARG; }
+    char *ax = c->aux;
+    int64_t *fold_n = (int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
+    const int *pos = (const int *)(ax + L.a_pos);
+    int *ncol_dev = (int *)(ax + V.a_ncol), *inv = (int *)(ax + V.a_inv);
+    double *bdev = (double *)(ax + L.a_b), *tri = (double *)(ax + V.a_tri);
+    const size_t blen = (size_t)K * npen * nl * (p + 1), tlen = (size_t)3 * K * npen * nl;
+    // the fold sizes and starts go up again from the host copy of phase 1: what the kernels index the rows by is this call's own
+    OEM_HIP(hipMemcpyAsync(fold_n, c->cv_hf.data(), sizeof(int64_t) * 2 * K, hipMemcpyHostToDevice, c->stream));
+    OEM_HIP(hipMemcpyAsync(bdev, coef, sizeof(double) * blen, hipMemcpyHostToDevice, c->stream));
+    OEM_HIP(hipMemcpyAsync(ncol_dev, ncol, sizeof(int) * (size_t)npen, hipMemcpyHostToDevice, c->stream));
+    if (predmat_dev) { rc = launch_fold_inverse(c->stream, pos, n, L.ldp, inv); if (rc) return rc; }
+    rc = launch_cv_fold_error(c->stream, (const double *)(ax + L.a_xp), L.ldp, (const double *)(ax + L.a_yp), fold_start, fold_n, K, p, bdev,
+                              npen, nl, type_measure, L.cv, (double *)(ax + L.a_part), ncol_dev, tri, predmat_dev, inv, n);
+    if (rc) return rc;
+    OEM_HIP(hipMemcpyAsync(triples, tri, sizeof(double) * tlen, hipMemcpyDeviceToHost, c->stream));
+    OEM_HIP(hipStreamSynchronize(c->stream));                   // coef, ncol and triples are the caller's
+    return 0;
+}
+
+// Test infrastructure: phase 2 alone on a table of the caller's -- the rows are laid out as phase 1 lays them out (no moments, nothing
+// fitted, so a fold may leave fewer rows than columns), then oemgpu_cv_score_dev as it is.
+int oemgpu_selftest_cv_score_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                                 const int32_t *foldid_dev, int32_t nfolds, const double *coef, int32_t npen, int32_t nl,
+                                 const int32_t *ncol, int32_t type_measure, double *triples, double *predmat_dev)
+{
+    if (!c || !x_dev || !y_dev || !foldid_dev || !coef || !ncol || !triples) { set_error("selftest_cv_score: NULL argument"); return OEMGPU_ERR_ARG; }
+    if (npen < 1 || nl < 1) { set_error("selftest_cv_score: bad npen or nl"); return OEMGPU_ERR_ARG; }
+    int rc = cv_check_rows("selftest_cv_score", n, ld, p, nfolds);
+    if (rc) return rc;
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const CvLay V = cv_layout(c, n, p, nfolds, npen, nl);
+    std::vector<int64_t> hf;
+    rc = cv_lay_out(c, V, x_dev, ld, y_dev, foldid_dev, false, hf);
+    if (rc) return rc;
+    return oemgpu_cv_score_dev(c, n, p, nfolds, coef, npen, nl, ncol, type_measure, triples, predmat_dev);
 }
 
 // rows [r0, r1) of the host data resident on the context's device: x (leading dimension *ld), y, foldid and the weights

@@ -124,6 +124,13 @@ int launch_cv_error(hipStream_t s, const double *xp, int64_t ldp, const double *
                     int K, int p, const double *B, int npen, int nl, int mae, int wmode, const CvErrPlan &P, double n, double *part, double *out,
                     bool triples = false);
 int launch_cv_finish(hipStream_t s, const double *part, int nparts, int npen, int nl, double n, double *out, bool triples);
+// cv.oem, family = "gaussian": the same product from the same plan with one (count, mean, M2) per FOLD -- triples[K][npen][nl][3], (0, NaN, NaN)
+// in columns >= ncol[pen] and for empty folds -- and, with predmat != nullptr, yhat stored through inv (fold position -> caller's row, from
+// launch_fold_inverse) into predmat[npen][nl][n], NaN in columns >= ncol[pen]
+int launch_fold_inverse(hipStream_t s, const int *pos, int64_t n, int64_t ldp, int *inv);
+int launch_cv_fold_error(hipStream_t s, const double *xp, int64_t ldp, const double *yp, const int64_t *fold_start, const int64_t *fold_n,
+                         int K, int p, const double *B, int npen, int nl, int mae, const CvErrPlan &P, double *part, const int *ncol,
+                         double *triples, double *predmat, const int *inv, int64_t n);
 
 // ------------------------------------------------------------------ xval.oem on a sparse x (xval_sparse.hip, sparse.hip)
 // The ONE host plan of the call (pure arithmetic): the route of sparse_route, the fold-ordered layout (fold segments start on multiples of

@@ -45,6 +45,12 @@ struct oemgpu_ctx {
     int shift_advised = 0;         // the last solve was given moments about 0 whose columns have |mean| >> sd
     char *aux = nullptr;           // xval.oem: fold-ordered copy of X, fold moments, fold coefficients (grow-only)
     size_t aux_bytes = 0;
+    // cv.oem (gaussian): the fold layout oemgpu_cv_fold_fits_dev left in aux -- its shape, where aux was, the fold sizes and starts --
+    // which oemgpu_cv_score_dev checks before it reads the fold-ordered rows
+    int64_t cv_n = 0;
+    int cv_p = 0, cv_K = 0;
+    const char *cv_aux = nullptr;
+    std::vector<int64_t> cv_hf;
     std::vector<oemgpu_ctx *> kids;   // xval.oem: one child context (stream, workspace, staging) per concurrent fold fit
     hipEvent_t fork_ev = nullptr;
     // ---- host-resident inputs (hoststream.hip): everything grow-only, so repeated calls allocate nothing

@@ -187,11 +187,16 @@ constexpr int CVW = 8;                   // waves per workgroup
 constexpr int CV_KC = 14;                // k-steps of X fragments a lane holds at once
 constexpr int CV_KCH = 8 * CV_KC;        // coefficient rows per LDS chunk (CHUNK): two fragment loads of KC = 14 k-steps
 constexpr size_t CV_LDS_MAX = 140 * 1024;   // the coefficient tile of a pass stays in LDS up to here
-template <int LT, int KC, bool SINGLE, bool CHUNK>
+// PRED (cv.oem, family = "gaussian": fit.preval; no weights, wmode = 0): finish() also stores the accumulator tile -- yhat of the tile's
+// 16 rows at the pass's lambdas -- into pa.pred[npen][nl][n] at the CALLER'S row, pa.inv[fold position]; columns >= pa.ncol[pen] (the
+// penalty's valid leading columns) get NaN.  Without PRED the trailing argument is empty and the kernel is what it was without it.
+template <bool PRED> struct CvPred {};
+template <> struct CvPred<true> { double *pred; const int *inv; const int *ncol; int64_t n; };
+template <int LT, int KC, bool SINGLE, bool CHUNK, bool PRED = false>
 __global__ __launch_bounds__(64 * CVW) void cv_error_kernel(const double *__restrict__ xp, int64_t ldp, const double *__restrict__ yp,
                                                             const int64_t *__restrict__ fold_start, const int64_t *__restrict__ fold_n,
                                                             int p, const double *__restrict__ B, int nl, int mae, int wmode,
-                                                            double *__restrict__ part)
+                                                            double *__restrict__ part, CvPred<PRED> pa)
 {
     // wmode (observation weights): xp has p + 1 data columns -- column 0 = sqrt(w), columns 1..p = sqrt(w) x -- and yp = sqrt(w) y, so
     // the squared residual of the scaled row IS w (y - yhat)^2 (ref src/oem_xval_dense.cpp:389-437); |.| takes one more sqrt(w).
@@ -286,6 +291,17 @@ __global__ __launch_bounds__(64 * CVW) void cv_error_kernel(const double *__rest
                     const double dv = ok ? err_of(yv, acc[t][r], sw) - cen[t] : 0.0;
                     s1[t] += dv; s2[t] = fma(dv, dv, s2[t]);
                 }
+                if constexpr (PRED) {
+                    const int64_t orig = ok ? (int64_t)pa.inv[start + row] : -1;
+                    if (orig >= 0 && orig < pa.n) {
+                        const int ncolp = pa.ncol[pen];
+#pragma unroll
+                        for (int t = 0; t < LT; ++t) {
+                            const int lam = l0 * 16 + 16 * t + l16;
+                            if (lam < nl) pa.pred[((size_t)pen * nl + lam) * pa.n + orig] = lam < ncolp ? acc[t][r] : __builtin_nan("");
+                        }
+                    }
+                }
             }
         };
         // all fragments of a chunk are requested before its first MFMA; the second wave of the SIMD covers the wait
@@ -336,17 +352,11 @@ __global__ __launch_bounds__(64 * CVW) void cv_error_kernel(const double *__rest
     }
 }
 
-// cvm = mean error, cvsd = sqrt(sample variance / n)  (ref src/oem_xval_dense.cpp:452-461).  One wave per (penalty, lambda):
-// lanes stride over the workgroup partials, then a fixed butterfly -- reproducible.
-// triples: out[npen][nl][3] <- (count, mean, M2) of the rows seen instead (row shards: the caller merges them, oemgpu_xval_merge).
-__global__ __launch_bounds__(64) void cv_finish_kernel(const double *__restrict__ part, int nparts, int npen, int nl, double n,
-                                                       double *__restrict__ out /* [npen][nl][2] */, int triples)
-{
-    const int t = blockIdx.x, lane = threadIdx.x;
-    const int pen = t / nl, lam = t - pen * nl, nl16 = (nl + 15) & ~15;
-    // (rows, mean, M2 = sum (v - mean)^2) of a set of observations; two sets merge by Chan, Golub & LeVeque's update
+// (rows, mean, M2 = sum (v - mean)^2) of a set of observations; two sets merge by Chan, Golub & LeVeque's update
+struct CvSet {
     double na = 0.0, ma = 0.0, qa = 0.0;
-    auto merge = [&](double nb, double mb, double qb) {
+    __device__ void merge(double nb, double mb, double qb)
+    {
         if (nb > 0.0) {
             if (na > 0.0) {
                 const double nn = na + nb, dl = mb - ma;
@@ -355,25 +365,69 @@ __global__ __launch_bounds__(64) void cv_finish_kernel(const double *__restrict_
                 na = nn;
             } else { na = nb; ma = mb; qa = qb; }
         }
-    };
+    }
+};
+// One wave merges the wave partials [b0, b0 + nparts) of one (penalty, lambda): lanes stride over them, then a fixed butterfly --
+// reproducible.  Every lane returns the merged set.
+__device__ __forceinline__ CvSet cv_merge_partials(const double *__restrict__ part, int b0, int nparts, int npen, int pen, int nl16, int lam, int lane)
+{
+    CvSet a;
     for (int b = lane; b < nparts; b += 64) {
-        const double *q = part + (((size_t)b * npen + pen) * nl16 + lam) * 4;
+        const double *q = part + (((size_t)(b0 + b) * npen + pen) * nl16 + lam) * 4;
         const double nb = q[0];
-        if (nb > 0.0) { const double m1 = q[2] / nb; merge(nb, q[1] + m1, q[3] - q[2] * m1); }
+        if (nb > 0.0) { const double m1 = q[2] / nb; a.merge(nb, q[1] + m1, q[3] - q[2] * m1); }
     }
     for (int s_ = 32; s_ > 0; s_ >>= 1) {                       // fixed butterfly: reproducible
-        const double nb = __shfl_xor(na, s_, 64), mb = __shfl_xor(ma, s_, 64), qb = __shfl_xor(qa, s_, 64);
+        const double nb = __shfl_xor(a.na, s_, 64), mb = __shfl_xor(a.ma, s_, 64), qb = __shfl_xor(a.qa, s_, 64);
         // both partners must end with the same numbers: merge in lane order (lower lane's set first)
-        if (lane & s_) { const double n0 = na, m0 = ma, q0 = qa; na = nb; ma = mb; qa = qb; merge(n0, m0, q0); }
-        else merge(nb, mb, qb);
+        if (lane & s_) { const CvSet o = a; a.na = nb; a.ma = mb; a.qa = qb; a.merge(o.na, o.ma, o.qa); }
+        else a.merge(nb, mb, qb);
     }
+    return a;
+}
+
+// cvm = mean error, cvsd = sqrt(sample variance / n)  (ref src/oem_xval_dense.cpp:452-461).  One wave per (penalty, lambda) over the
+// partials of all folds.
+// triples: out[npen][nl][3] <- (count, mean, M2) of the rows seen instead (row shards: the caller merges them, oemgpu_xval_merge).
+__global__ __launch_bounds__(64) void cv_finish_kernel(const double *__restrict__ part, int nparts, int npen, int nl, double n,
+                                                       double *__restrict__ out /* [npen][nl][2] */, int triples)
+{
+    const int t = blockIdx.x, lane = threadIdx.x;
+    const int pen = t / nl, lam = t - pen * nl, nl16 = (nl + 15) & ~15;
+    const CvSet a = cv_merge_partials(part, 0, nparts, npen, pen, nl16, lam, lane);
     if (lane == 0) {
-        if (triples) { out[(size_t)t * 3] = na; out[(size_t)t * 3 + 1] = ma; out[(size_t)t * 3 + 2] = qa; }
+        if (triples) { out[(size_t)t * 3] = a.na; out[(size_t)t * 3 + 1] = a.ma; out[(size_t)t * 3 + 2] = a.qa; }
         else {
-            out[(size_t)t * 2] = ma;                            // all n observations are in: the mean
-            out[(size_t)t * 2 + 1] = sqrt((qa < 0.0 ? 0.0 : qa) / (n - 1.0)) / sqrt(n);
+            out[(size_t)t * 2] = a.ma;                          // all n observations are in: the mean
+            out[(size_t)t * 2 + 1] = sqrt((a.qa < 0.0 ? 0.0 : a.qa) / (n - 1.0)) / sqrt(n);
         }
     }
+}
+
+// cv.oem, family = "gaussian": cvcompute's fold means (R/utils.R:128-144) need one set per FOLD.  One wave per (fold, penalty, lambda)
+// merges that fold's nwg * CVW wave partials -- they are laid out [K][nwg][CVW] -- as above; out[K][npen][nl][3] <- (count, mean, M2),
+// (0, NaN, NaN) for a column >= ncol[pen] (not valid for that penalty) and for a fold without rows.
+__global__ __launch_bounds__(64) void cv_fold_finish_kernel(const double *__restrict__ part, int per_fold, int npen, int nl,
+                                                            const int *__restrict__ ncol, double *__restrict__ out)
+{
+    const int t = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+    const int pen = t / nl, lam = t - pen * nl, nl16 = (nl + 15) & ~15;
+    CvSet a;
+    if (lam < ncol[pen]) a = cv_merge_partials(part, k * per_fold, per_fold, npen, pen, nl16, lam, lane);
+    if (lane == 0) {
+        double *o = out + ((size_t)k * npen * nl + t) * 3;
+        const bool some = a.na > 0.0;
+        o[0] = some ? a.na : 0.0; o[1] = some ? a.ma : __builtin_nan(""); o[2] = some ? a.qa : __builtin_nan("");
+    }
+}
+
+// inv[fold position] = the caller's row (the inverse of fold_pos_kernel's map; the padding between the folds stays unset and is never read)
+__global__ __launch_bounds__(256) void fold_inverse_kernel(const int *__restrict__ pos, int64_t n, int64_t ldp, int *__restrict__ inv)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t d = pos[i];
+    if (d >= 0 && d < ldp) inv[d] = (int)i;
 }
 
 }  // namespace
@@ -461,14 +515,21 @@ CvErrPlan cv_error_plan(int64_t n, int p, int K, int npen, int nl, int num_cu)
 }
 size_t cv_part_doubles(int nwg, int K, int npen, int nl) { return (size_t)nwg * K * CVW * npen * ((nl + 15) & ~15) * 4; }
 
+// pred != nullptr: the PRED instantiation (no weights there)
 template <int LT>
 static int launch_cv_lt(hipStream_t s, dim3 grid, size_t lds, int form, const double *xp, int64_t ldp, const double *yp,
-                        const int64_t *fold_start, const int64_t *fold_n, int p, const double *B, int nl, int mae, int wmode, double *part)
+                        const int64_t *fold_start, const int64_t *fold_n, int p, const double *B, int nl, int mae, int wmode, double *part,
+                        double *pred = nullptr, const int *inv = nullptr, const int *ncol = nullptr, int64_t n = 0)
 {
 #define OEM_CVK(KC, SINGLE, CHUNK)                                                                                                   \
     do {                                                                                                                             \
-        OEM_HIP(hipFuncSetAttribute((const void *)cv_error_kernel<LT, KC, SINGLE, CHUNK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((cv_error_kernel<LT, KC, SINGLE, CHUNK>), grid, dim3(64 * CVW), lds, s, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part); \
+        if (pred) {                                                                                                                  \
+            OEM_HIP(hipFuncSetAttribute((const void *)cv_error_kernel<LT, KC, SINGLE, CHUNK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            hipLaunchKernelGGL((cv_error_kernel<LT, KC, SINGLE, CHUNK, true>), grid, dim3(64 * CVW), lds, s, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, 0, part, CvPred<true>{pred, inv, ncol, n}); \
+        } else {                                                                                                                     \
+            OEM_HIP(hipFuncSetAttribute((const void *)cv_error_kernel<LT, KC, SINGLE, CHUNK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            hipLaunchKernelGGL((cv_error_kernel<LT, KC, SINGLE, CHUNK>), grid, dim3(64 * CVW), lds, s, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part, CvPred<false>{}); \
+        }                                                                                                                            \
     } while (0)
     if (form == CV_FORM_CHUNK) OEM_CVK(CV_KC, false, true);
     else if (form == CV_FORM_SINGLE) OEM_CVK(CV_KC, true, false);
@@ -478,21 +539,47 @@ static int launch_cv_lt(hipStream_t s, dim3 grid, size_t lds, int form, const do
     return 0;
 }
 
-int launch_cv_error(hipStream_t s, const double *xp, int64_t ldp, const double *yp, const int64_t *fold_start, const int64_t *fold_n,
-                    int K, int p, const double *B, int npen, int nl, int mae, int wmode, const CvErrPlan &P, double n, double *part, double *out,
-                    bool triples)
+// the product alone: every wave's partial into part
+static int launch_cv_product(hipStream_t s, const double *xp, int64_t ldp, const double *yp, const int64_t *fold_start, const int64_t *fold_n,
+                             int K, int p, const double *B, int npen, int nl, int mae, int wmode, const CvErrPlan &P, double *part,
+                             double *pred = nullptr, const int *inv = nullptr, const int *ncol = nullptr, int64_t n = 0)
 {
-    const int nwg = P.nwg;
-    dim3 grid(nwg, K, npen);
+    dim3 grid(P.nwg, K, npen);
     int rc;
-#define OEM_CVLT(LT) case LT: rc = launch_cv_lt<LT>(s, grid, P.lds, P.form, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part); break
+#define OEM_CVLT(LT) case LT: rc = launch_cv_lt<LT>(s, grid, P.lds, P.form, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part, pred, inv, ncol, n); break
     switch (P.lt) {
     OEM_CVLT(1); OEM_CVLT(2); OEM_CVLT(3); OEM_CVLT(4); OEM_CVLT(5); OEM_CVLT(6); OEM_CVLT(7);
     default: return OEMGPU_ERR_INTERNAL;
     }
 #undef OEM_CVLT
+    return rc;
+}
+
+int launch_cv_error(hipStream_t s, const double *xp, int64_t ldp, const double *yp, const int64_t *fold_start, const int64_t *fold_n,
+                    int K, int p, const double *B, int npen, int nl, int mae, int wmode, const CvErrPlan &P, double n, double *part, double *out,
+                    bool triples)
+{
+    int rc = launch_cv_product(s, xp, ldp, yp, fold_start, fold_n, K, p, B, npen, nl, mae, wmode, P, part);
     if (rc) return rc;
-    hipLaunchKernelGGL(cv_finish_kernel, dim3(npen * nl), dim3(64), 0, s, part, nwg * K * CVW, npen, nl, n, out, triples ? 1 : 0);
+    hipLaunchKernelGGL(cv_finish_kernel, dim3(npen * nl), dim3(64), 0, s, part, P.nwg * K * CVW, npen, nl, n, out, triples ? 1 : 0);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_fold_inverse(hipStream_t s, const int *pos, int64_t n, int64_t ldp, int *inv)
+{
+    hipLaunchKernelGGL(fold_inverse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pos, n, ldp, inv);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_cv_fold_error(hipStream_t s, const double *xp, int64_t ldp, const double *yp, const int64_t *fold_start, const int64_t *fold_n,
+                         int K, int p, const double *B, int npen, int nl, int mae, const CvErrPlan &P, double *part, const int *ncol,
+                         double *triples, double *predmat, const int *inv, int64_t n)
+{
+    int rc = launch_cv_product(s, xp, ldp, yp, fold_start, fold_n, K, p, B, npen, nl, mae, 0, P, part, predmat, inv, ncol, n);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cv_fold_finish_kernel, dim3(npen * nl, K), dim3(64), 0, s, part, P.nwg * CVW, npen, nl, ncol, triples);
     OEM_HIP(hipGetLastError());
     return 0;
 }
