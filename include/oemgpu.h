@@ -562,6 +562,8 @@ typedef struct oemgpu_sparse_x oemgpu_sparse_x;
 int oemgpu_sparse_x_create(oemgpu_ctx *ctx, int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values,
                            oemgpu_sparse_x **out);
 void oemgpu_sparse_x_destroy(oemgpu_sparse_x *x);
+/* the bytes of device memory the handle holds (its one allocation); 0 for NULL */
+int64_t oemgpu_sparse_x_bytes(const oemgpu_sparse_x *x);
 /* cv.oem's fold fit on the resident sparse x (ref R/cv_oem.R:129-175): what `.Call("oem_fit_logistic_sparse", ...)` computes on
  * x[keep, ], y[keep] with keep = foldid_dev != leave_out, every particular of oemgpu_fit_logistic_sparse included.  Nothing is sliced,
  * uploaded or converted: the passes leave the fold's rows out and the number of kept rows stands where n enters the arithmetic (the
@@ -586,6 +588,56 @@ int oemgpu_logistic_cv_score_sparse_res(oemgpu_ctx *ctx, const oemgpu_sparse_x *
  * within) counting the fit's own pieces only -- W, r, the row partials, X'W, the device words, the moments, the Gram scratch.  The
  * compressed columns, the row copy, the chunk pointers (the handle's) and y (the caller's) are not in it. */
 int oemgpu_selftest_logistic_sparse_res_plan(int64_t n, int32_t p, int64_t nnz, int32_t intercept, int32_t num_cu, int64_t *out /* 8 */);
+/* cv.oem(family = "gaussian") on the resident sparse x (ref R/cv_oem.R:105, 129-175, 349-423; R/utils.R:64-144; a dgCMatrix reaches
+ * oem_fit_sparse, R/oem.R:532-556, src/oem_sparse.{h,cpp}), in two phases like oemgpu_cv_fold_fits_dev / oemgpu_cv_score_dev above; the
+ * caller interpolates between the two (lambda.interp).
+ *
+ * 1. oemgpu_cv_sparse_fold_fits_res replaces cv.oem's K + 1 calls of oem(): slot 0 of every output is the fit of all rows, slot ff what
+ *    oemgpu_fit_sparse computes on the rows whose id is not ff -- oemSparse's semantics: no centring, column scales sum x_j^2 / (n - 1)
+ *    with 0 -> 1 for a column that is empty among the kept rows, intval = sqrt(mean diag / n) on the intercept's coordinate, get_beta's
+ *    in-place intercept scale (ref src/oem_sparse.h:493-508, 577-593, 897-900), every fit on its own lambda grid unless opts carries the
+ *    user's -- with the kept-row count wherever n enters.  Nothing is sliced or uploaded: the handle's columns are rewritten in fold
+ *    order on the device (fold segments on multiples of 8192 rows), the K fold moment buffers about 0 come from ONE pass over the
+ *    non-zeros (compressed columns or zero-filled row tiles: the rule of oemgpu_fit_sparse, OEM_SPARSE_GRAM / OEM_SPARSE_TILE_ROWS
+ *    honoured), a fold-ordered compressed-row copy is left for phase 2, and fit ff is solved from the sum of the other folds' buffers
+ *    in fold order (slot 0: of all of them).  y_dev: n doubles, foldid_dev: n int32 with values 1..nfolds, on the handle's device.
+ *    Host outputs: beta[nfolds + 1][npen][nl][p + 1], lambda_out / niter / loss [nfolds + 1][npen][nl], d[nfolds + 1], fold_n[nfolds].
+ *    opts as for oemgpu_fit_sparse: with an intercept, groups / ngroupvars cover p + 1 coordinates with the intercept's group first.
+ *    An id in 1..nfolds that never occurs is allowed: that fold's fit is the fit of all rows.
+ *    Refused before a device is looked for: NULL pointers, the options (OEMGPU_ERR_ARG), nfolds outside 2..512 (OEMGPU_ERR_ARG),
+ *    n + 8192 nfolds >= 2^31 and n - ceil(n / nfolds) <= p (OEMGPU_ERR_UNSUPPORTED).  From the device: an id outside 1..nfolds
+ *    (OEMGPU_ERR_ARG), and n - n_k <= p for some fold k, named in the message (OEMGPU_ERR_UNSUPPORTED: that fit is the wide engine's).
+ *    oemgpu_last_xval_sparse_timings then holds this call's phases: [1] fold order [2] fold moments [3] compressed rows [4] the fits.
+ *
+ * 2. oemgpu_cv_sparse_score_res: the arguments, outputs and argument checks of oemgpu_cv_score_dev, over the fold-ordered compressed
+ *    rows phase 1 left on the context: eta = b_0 + sum of x_ij b_j over the row's stored entries in column order;
+ *    triples[nfolds][npen][nl][3] <- (count, mean, M2) of every fold's errors, merged from per-fold wave partials in a fixed order (no
+ *    atomics: two calls give the same bits), (0, NaN, NaN) in columns >= ncol[pen] and for empty folds; predmat_dev: NULL, or
+ *    [npen][nl][n] on the device <- eta in the CALLER'S row order, NaN in columns >= ncol[pen].  It needs the layout of a call of
+ *    oemgpu_cv_sparse_fold_fits_res on the same context with the same (n, p, nfolds, npen, nl); any call that lays the context's fold
+ *    buffer out anew in between (xval.oem, the dense cv entries, a binomial fit) voids it, and a dense layout never passes for a
+ *    sparse one nor a sparse one for a dense one: OEMGPU_ERR_ARG, never another call's rows scored. */
+int oemgpu_cv_sparse_fold_fits_res(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
+                                   int32_t standardize, int32_t intercept, const oemgpu_opts *opts,
+                                   double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int64_t *fold_n);
+int oemgpu_cv_sparse_score_res(oemgpu_ctx *ctx, int64_t n, int32_t p, int32_t nfolds, const double *coef, int32_t npen, int32_t nl,
+                               const int32_t *ncol, int32_t type_measure, double *triples, double *predmat_dev /* or NULL */);
+/* Test infrastructure (tests/test_gpu_cv_sparse_gaussian.py): oemgpu_cv_sparse_score_res after the fold layout and the compressed rows
+ * alone -- no moments, nothing fitted, so a fold may leave fewer rows than columns -- on a table of the caller's: the sparse sibling of
+ * oemgpu_selftest_cv_score_dev.  The row checks of phase 1 and the checks of phase 2. */
+int oemgpu_selftest_cv_sparse_score(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
+                                    const double *coef, int32_t npen, int32_t nl, const int32_t *ncol, int32_t type_measure, double *triples,
+                                    double *predmat_dev /* or NULL */);
+/* Host-only plan of the two entries above (pure arithmetic, runs without a GPU; the entries take their layout from the same function):
+ * out[0] 1 if the fold moments take the compressed-column kernel and 0 for row tiles, out[1] workgroups of the scoring launch (four waves
+ * each; x npen x out[3]), out[2] its waves (the stride over the rows), out[3] blocks of 64 lambdas, out[4] bytes of the per-fold wave
+ * partials = nfolds out[2] npen out[10] 32 (kept under 64 MB by lowering out[1], which never falls below 1), out[5] device bytes of
+ * the call = out[6] (the xval layout) + out[7] (the sparse fold plan, without upload regions) + out[8] (this route's own: the
+ * partials, 24 nfolds npen nl of triples, 4 npen, 4 out[9] of inverse positions, 8 p, each rounded up to 256), out[9] rows of the
+ * fold-ordered layout at most, out[10] nl rounded up to 16, out[11] the fold alignment (8192).  OEMGPU_ERR_ARG on bad arguments and
+ * nfolds outside 2..512, OEMGPU_ERR_UNSUPPORTED on n + 8192 nfolds >= 2^31. */
+int oemgpu_selftest_cv_sparse_plan(int64_t n, int32_t p, int64_t nnz, int32_t nfolds, int32_t npen, int32_t nl, int32_t num_cu,
+                                   int64_t *out /* 12 */);
 /* Host-only plan of the compressed-column Gram kernel both sparse fits share (pure arithmetic, runs without a GPU): out[0] 8192-row
  * chunks of an n-row matrix, out[1] contiguous chunk ranges the launch splits them into (the range sums cost out[1] p^2 doubles, kept
  * under 256 MB), out[2] chunks per range (range r = chunks [r out[2], min(out[0], (r + 1) out[2])), possibly none for the last ranges),

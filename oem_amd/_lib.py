@@ -70,6 +70,7 @@ _SIGS = {
     "oemgpu_selftest_logistic_sparse_res_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_sparse_x_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "oemgpu_sparse_x_destroy": (None, [C.c_void_p]),
+    "oemgpu_sparse_x_bytes": (C.c_int64, [C.c_void_p]),
     "oemgpu_fit_logistic_sparse_fold_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                        C.c_double, C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_logistic_cv_score_sparse_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, _dp, C.c_int32, _dp,
@@ -124,6 +125,13 @@ _SIGS = {
                                       C.c_void_p]),                                                                  # R/cv_oem.R:376-391, R/utils.R:128-144
     "oemgpu_selftest_cv_score_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, _dp,
                                                C.c_int32, C.c_int32, _ip, C.c_int32, _dp, C.c_void_p]),
+    "oemgpu_cv_sparse_fold_fits_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.POINTER(OemgpuOpts)] + _OUT + [C.POINTER(C.c_int64)]),     # R/cv_oem.R:105, 155-175 on a dgCMatrix
+    "oemgpu_cv_sparse_score_res": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _ip, C.c_int32, _dp,
+                                             C.c_void_p]),
+    "oemgpu_selftest_cv_sparse_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, _ip,
+                                                  C.c_int32, _dp, C.c_void_p]),
+    "oemgpu_selftest_cv_sparse_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_xval_merge": (C.c_int, [_dp, C.c_int32, C.POINTER(OemgpuOpts), _dp, _dp]),
     "oemgpu_eig_max_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _dp]),
     "oemgpu_last_timings": (C.c_int, [C.c_void_p, _dp]),

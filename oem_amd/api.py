@@ -287,14 +287,17 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
     if family not in ("gaussian", "binomial"):
         raise ValueError("'arg' should be one of 'gaussian', 'binomial'")
     penalty = _match_penalty(penalty)
-    if getattr(x, "ndim", 0) != 2:
+    resident_sparse = isinstance(x, SparseX)
+    if resident_sparse and not _args_only:                            # (cv_oem alone builds the sparse entry's option block for a SparseX)
+        raise ValueError("oem() on a SparseX is not built: oem() takes the scipy.sparse matrix itself; the resident handle is what cv_oem runs on")
+    if getattr(x, "ndim", 0) != 2 and not resident_sparse:
         raise ValueError("x must have at least two columns")
     n, p = x.shape
     if p > n:
         warnings.warn("oem() is optimized for n >> p settings and may be very slow when p > n")
     if p < 2:
         raise ValueError("x must have at least two columns")
-    is_sparse = type(x).__module__.startswith("scipy.sparse")         # R/oem.R:236-242: sparseMatrix -> dgCMatrix
+    is_sparse = type(x).__module__.startswith("scipy.sparse") or resident_sparse      # R/oem.R:236-242: sparseMatrix -> dgCMatrix
     if len(weights) > 0:
         raise ValueError("weights not implemented yet.")
     ylen = y.shape[0] if hasattr(y, "shape") else len(y)
@@ -318,6 +321,8 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
               compute_loss, penalty_factor, groups, unique_groups, group_weights, ngpus=ngpus, devices=devices,
               upload_threads=upload_threads, interrupt=interrupt)
     if _args_only:                                                     # cv_oem's resident route: the option block of this call, nothing run
+        if is_sparse:
+            a.c.accelerate = 0                                         # oemSparse has no acceleration
         return a, varnames, bool(standardize), bool(intercept)
     lib = L.lib()
     if is_sparse:                                                      # oem_fit_sparse (ref src/oem_sparse.cpp:30-267)
@@ -481,6 +486,11 @@ class SparseX:
     @property
     def closed(self):
         return self._h is None
+
+    @property
+    def device_bytes(self):
+        """the bytes of device memory the handle holds (oemgpu_sparse_x_bytes)"""
+        return int(L.lib().oemgpu_sparse_x_bytes(self.handle))
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -933,6 +943,45 @@ def cv_gaussian_score(x, y, foldid, nfolds, coef, ncol, type_measure="mse", pred
     return tri, (pm.cpu().numpy() if predmat else None)
 
 
+def cv_sparse_gaussian_score(x, y, foldid, nfolds, coef, ncol, type_measure="mse", predmat=False, ctx=None):
+    """oemgpu_selftest_cv_sparse_score (test infrastructure): the scoring entry of cv.oem(family = "gaussian") on a SparseX,
+    oemgpu_cv_sparse_score_res, after the fold layout and the compressed rows alone, on a coefficient table of the caller's.  x: a
+    SparseX; y (float64), foldid (int32, 1 .. nfolds): device tensors; coef: nfolds x npen x nl x (p + 1) on the host; ncol: the valid
+    leading columns per penalty.  Returns (triples: nfolds x npen x nl x 3 = (count, mean, M2) of every fold's errors; predmat: npen x nl x n
+    on the host in the caller's row order, or None)."""
+    import torch
+    L.sync_switches()
+    n, p = x.shape
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    if coef.ndim != 4 or coef.shape[0] != int(nfolds) or coef.shape[3] != p + 1:
+        raise ValueError("coef must be nfolds x npen x nl x (p + 1)")
+    npen, nl = coef.shape[1:3]
+    ncol = np.ascontiguousarray(ncol, dtype=np.int32)
+    if ncol.shape != (npen,):
+        raise ValueError("ncol must hold one count per penalty")
+    tri = np.full((int(nfolds), npen, nl, 3), np.nan)
+    pm = torch.empty((npen, nl, n), dtype=torch.float64, device=x.device) if predmat else None
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_selftest_cv_sparse_score(ctx if ctx is not None else context(x.device.index), x.handle, y.data_ptr(),
+                                                    foldid.data_ptr(), int(nfolds), _dptr(coef), npen, nl, _iptr(ncol),
+                                                    {"mse": 0, "mae": 1}[type_measure], _dptr(tri), pm.data_ptr() if predmat else None))
+    return tri, (pm.cpu().numpy() if predmat else None)
+
+
+_CVS_PLAN_KEYS = ("csc", "nwg", "waves", "lblk", "part_bytes", "bytes", "xval_bytes", "fold_bytes", "own_bytes", "rows_max", "nl16", "align")
+
+
+def cv_sparse_plan(n, p, nnz, nfolds, npen, nl, num_cu):
+    """oemgpu_selftest_cv_sparse_plan (needs no GPU): the plan of cv.oem(family = "gaussian") on a SparseX as a dict -- the route of the
+    fold moments (csc: True / False), the scoring launch (nwg workgroups, waves, lblk blocks of 64 lambdas), the bytes of its per-fold
+    wave partials, the device bytes of the call and their three terms, the most rows of the fold-ordered layout (include/oemgpu.h)."""
+    out = (C.c_int64 * 12)()
+    L.check(L.lib().oemgpu_selftest_cv_sparse_plan(int(n), int(p), int(nnz), int(nfolds), int(npen), int(nl), int(num_cu), out))
+    d = dict(zip(_CVS_PLAN_KEYS, list(out)))
+    d["csc"] = bool(d["csc"])
+    return d
+
+
 # ------------------------------------------------------------------------------------------ cv.oem()
 def logistic_cv_score(x, y, foldid, nfolds, coef, y_hi=None, predmat=False):
     """oemgpu_logistic_cv_score_dev: the error terms of cv.oemfit_binomial (R/cv_oem.R:315-327) over the held-out rows of a resident x.
@@ -1216,6 +1265,54 @@ def _cv_gaussian_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw):
     return outlist, {"ctx": ctx, "n": n, "p": p, "K": K, "args": a, "fold_n": fold_n, "device": x.device}
 
 
+def _cv_gaussian_sparse_checks(x, y, penalty, kw):
+    """What cv_oem refuses on a SparseX before any device work (the fold checks follow once foldid is known)"""
+    if "ols" in penalty:
+        raise ValueError("cv.oem on a SparseX: the \"ols\" penalty is not served")
+    if kw.get("ngpus") or kw.get("devices") is not None:
+        raise ValueError("cv.oem on a SparseX: the rows of a sparse x are not split over devices")
+    x.handle                                                      # a closed SparseX raises here
+    ylen = y.shape[0] if hasattr(y, "shape") else len(y)
+    if ylen != x.shape[0]:
+        raise ValueError("x and y lengths do not match")
+
+
+def _cv_gaussian_sparse_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw):
+    """cv.oem's K + 1 calls of oem() on a dgCMatrix (R/cv_oem.R:105, 155-175 -> oem_fit_sparse) as ONE call on the resident SparseX:
+    oemgpu_cv_sparse_fold_fits_res.  Returns the full fit and the fold fits as oem() on a scipy x returns them, and what the scoring needs."""
+    import types
+    import torch
+    n, p = x.shape
+    foldid = np.asarray(foldid)
+    if len(foldid) != n or not np.issubdtype(foldid.dtype, np.integer) or foldid.min() < 1 or foldid.max() > nfolds:
+        raise ValueError("foldid must hold one integer in 1..nfolds per row of x")
+    if not 3 <= nfolds <= 512:
+        raise ValueError("cv.oem on a SparseX: nfolds must be in 3..512")
+    kept = n - np.bincount(foldid, minlength=nfolds + 1)[1:]
+    if np.any(kept <= p):
+        i = int(np.argmax(kept <= p))
+        raise ValueError(f"cv.oem on a SparseX: fold {i + 1} leaves {int(kept[i])} rows for {p} columns (a fit of p >= n is not served here)")
+    a, varnames, standardize, intercept = oem(x, y, penalty=penalty, lambda_=lam_arg, _args_only=True, **kw)
+    yd = y if _is_torch_cuda(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=x.device)
+    yd = yd.to(device=x.device, dtype=torch.float64).contiguous().reshape(-1)
+    fd = torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=x.device)
+    ctx = context(x.device.index)
+    K, npen, nl = int(nfolds), a.npen, a.nl
+    beta = np.zeros((K + 1, npen, nl, p + 1))
+    lam_out, loss = np.zeros((K + 1, npen, nl)), np.zeros((K + 1, npen, nl))
+    niter = np.zeros((K + 1, npen, nl), dtype=np.int32)
+    d, fold_n = np.zeros(K + 1), np.zeros(K, dtype=np.int64)
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_cv_sparse_fold_fits_res(ctx, x.handle, yd.data_ptr(), fd.data_ptr(), K, int(standardize), int(intercept),
+                                                   C.byref(a.c), _dptr(beta), _dptr(lam_out), _iptr(niter), _dptr(loss), _dptr(d),
+                                                   fold_n.ctypes.data_as(C.POINTER(C.c_int64))))
+    fits = [_decorate(types.SimpleNamespace(beta=beta[i], lam_out=lam_out[i], niter=niter[i], loss=loss[i],
+                                            d=types.SimpleNamespace(value=float(d[i]))), penalty, varnames, True,
+                      int(n - fold_n[i - 1]) if i else n, p) for i in range(K + 1)]
+    return fits[0], fits[1:], {"ctx": ctx, "n": n, "p": p, "K": K, "args": a, "fold_n": fold_n, "device": x.device,
+                               "score": L.lib().oemgpu_cv_sparse_score_res}
+
+
 def _cv_gaussian_table(outlist, lam, which_lam, p):
     """coef[K][npen][nl][p + 1] and ncol[npen]: every fold's coefficients at the full fit's lambdas that no fold has to extrapolate to
     (predict.oem's lambda.interp, R/methods.R:48-109), packed into the leading columns (R/cv_oem.R:364-391)."""
@@ -1241,8 +1338,9 @@ def _cv_gaussian_score(dev, outlist, lam, which_lam, type_measure, keep):
         import torch
         pm = torch.empty((nmodels, nl, n), dtype=torch.float64, device=dev["device"])
         torch.cuda.current_stream(dev["device"]).synchronize()
-    L.check(L.lib().oemgpu_cv_score_dev(dev["ctx"], n, p, K, _dptr(coef), nmodels, nl, _iptr(ncol), int(type_measure == "mae"),
-                                        _dptr(triples), pm.data_ptr() if keep else None))
+    score = dev.get("score", L.lib().oemgpu_cv_score_dev)          # (a SparseX: oemgpu_cv_sparse_score_res, the same arguments)
+    L.check(score(dev["ctx"], n, p, K, _dptr(coef), nmodels, nl, _iptr(ncol), int(type_measure == "mae"),
+                  _dptr(triples), pm.data_ptr() if keep else None))
     return triples, ([np.ascontiguousarray(a.T) for a in pm.cpu().numpy()] if keep else None)
 
 
@@ -1338,8 +1436,17 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
     family = "binomial" with a scipy.sparse x (R/cv_oem.R:129-175 on a dgCMatrix, which reaches oem_fit_logistic_sparse): one SparseX holds
     the compressed columns and their compressed-row copy on the device; the full fit (leave_out = 0), the fold fits (masked passes,
     oemgpu_fit_logistic_sparse_fold_res) and the scoring (oemgpu_logistic_cv_score_sparse_res) read it there.  The options are those of
-    oem_fit_logistic_sparse (hessian_type is checked and ignored; an intercept needs standardize).  A sparse x with family = "gaussian"
-    is a ValueError.
+    oem_fit_logistic_sparse (hessian_type is checked and ignored; an intercept needs standardize).
+    family = "gaussian" on a sparse x (R/cv_oem.R:129-175 on a dgCMatrix, which reaches oem_fit_sparse) enters where the dense route does,
+    on an x that is already resident: an oem_amd.SparseX.  cv.oem's K + 1 calls of oem() are ONE call, oemgpu_cv_sparse_fold_fits_res: the
+    handle's columns go into fold order, the K fold moment buffers come from one pass over the non-zeros, and the full fit (`oem.fit`,
+    wrapped as oem() on a scipy x wraps its result) and fold ff's fit are oemSparse's solve -- no centring, intval, the kept-row count
+    wherever n enters -- on the sum of all buffers / of all but ff.  From there on it is the resident dense route's code: the folds'
+    coefficients interpolated here, the held-out rows scored from the fold-ordered compressed rows (oemgpu_cv_sparse_score_res), fit.preval
+    and foldid with keep=True; y may be numpy or a device tensor, `parallel` is accepted and ignored.  ValueErrors before any device work:
+    "ols" among the penalties, weights, ngpus / devices, a closed SparseX, len(y) != n, nfolds < 3, a fold id outside 1..nfolds and a fold
+    that keeps no more rows than columns (named: there is no host loop for a sparse x).  A scipy matrix itself with family = "gaussian"
+    stays a ValueError.
     parallel (R/cv_oem.R:32, 129-150: the folds through foreach): the fold fits from a few host threads at once.  On one GPU that
     pays where a fit leaves most of the chip idle: the path kernels of n >> p fits (one CU each) overlap with other folds' moment
     kernels, and p >= n fits on the cooperating-workgroup engine (a quarter of the CUs each) run side by side -- they queue for CU
@@ -1359,13 +1466,17 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
     if len(weights) > 0:
         raise ValueError("weights not implemented yet.")
     if _is_scipy_sparse(x):
-        raise ValueError("cv.oem on a sparse x is served for family = \"binomial\" only (a sparse Gaussian cross-validation is not built)")
-    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("cv.oem on a sparse x is served for family = \"binomial\" only (family = \"gaussian\" runs on a resident "
+                         "oem_amd.SparseX(x), not on the scipy matrix)")
+    on_sparse = isinstance(x, SparseX)
+    if on_sparse:
+        _cv_gaussian_sparse_checks(x, y, penalty, kw)
+    elif getattr(x, "ndim", 0) != 2:
         raise ValueError("x must have at least two columns")
     n = x.shape[0]
     lam_arg = () if lambda_ is None else lambda_
-    fit0 = oem(x, y, penalty=penalty, lambda_=lam_arg, **kw)
-    nz = [np.array([0 if v is None else len(v) for v in predict(fit0, type="nonzero", which_model=m)]) for m in range(len(penalty))]
+    if not on_sparse:
+        fit0 = oem(x, y, penalty=penalty, lambda_=lam_arg, **kw)
     if foldid is None:
         g = np.random.default_rng() if rng is None else rng
         foldid = g.permutation(np.resize(np.arange(1, int(nfolds) + 1), n))
@@ -1374,11 +1485,14 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
         nfolds = int(foldid.max())
     if nfolds < 3:
         raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
-    resident = _cv_gaussian_resident(x, penalty, kw, foldid, nfolds)
-    if resident:                                                  # x stays where it is: fold moments, K solves (oemgpu_cv_fold_fits_dev)
+    resident = on_sparse or _cv_gaussian_resident(x, penalty, kw, foldid, nfolds)
+    if on_sparse:                                                 # the full fit and the K fold fits from the fold moments of the resident columns
+        fit0, outlist, dev = _cv_gaussian_sparse_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw)
+    elif resident:                                                # x stays where it is: fold moments, K solves (oemgpu_cv_fold_fits_dev)
         outlist, dev = _cv_gaussian_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw)
     else:
         outlist, xh, yh = _cv_gaussian_host_fits(x, y, foldid, nfolds, penalty, lam_arg, kw, parallel)
+    nz = [np.array([0 if v is None else len(v) for v in predict(fit0, type="nonzero", which_model=m)]) for m in range(len(penalty))]
     # cv.oemfit_gaussian
     if type_measure in ("default", "deviance"):
         type_measure = "mse"

@@ -3,6 +3,7 @@
 // (lambda bookkeeping, result packing, DataStd::recover).  All arithmetic of the hot path runs in the HIP
 // kernels of gram.hip / path_small.hip / path_large.hip; there is no CPU fallback.
 #include "ctx.hpp"
+#include "logistic.hpp"     // oemgpu_sparse_x
 
 #include <atomic>
 #include <unistd.h>
@@ -12,6 +13,7 @@
 #include <cstdio>
 #include <condition_variable>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -1540,6 +1542,7 @@ static int fit_dense_wide_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int
     Bump X;
     const size_t a_xs = X.take(sizeof(double) * (size_t)lay.rows() * p), a_ys = X.take(sizeof(double) * (size_t)lay.rows()),
                  a_sc = X.take(sizeof(double) * wide_scratch_doubles((int)n, p));
+    ctx_void_cv(c);
     if (ctx_grow(c, &c->aux, &c->aux_bytes, X.off)) return OEMGPU_ERR_HIP;
     Bump B;
     const size_t a_xy = B.take((size_t)p * 8), a_st = B.take((size_t)stats_len(p) * 8);       // stats last: run_paths returns it with the outputs
@@ -1615,6 +1618,7 @@ static int fit_big_wide_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64
     Bump X;
     const size_t a_xs = X.take(sizeof(double) * (size_t)lay.rows() * p), a_ys = X.take(sizeof(double) * (size_t)lay.rows()),
                  a_sc = X.take(sizeof(double) * wide_scratch_doubles((int)n, p));
+    ctx_void_cv(c);
     if (ctx_grow(c, &c->aux, &c->aux_bytes, X.off)) return OEMGPU_ERR_HIP;
     Bump B;
     const size_t a_xs2 = B.take((size_t)p * 8), a_xy = B.take((size_t)p * 8), a_st = B.take((size_t)stats_len(p) * 8);       // stats last (run_paths)
@@ -1717,6 +1721,7 @@ static int fit_dense_weighted_impl(oemgpu_ctx *c, const double *x_dev, int64_t n
     // nobs <= nvars: the first pass's X'WX / n, X'(Yw) / n and constants are kept -- d, lambda_zero and the loss belong to them
     const size_t a_xx1 = wide ? Z.take(sizeof(double) * (size_t)p * p) : 0, a_xy1 = wide ? Z.take(sizeof(double) * (size_t)p) : 0,
                  a_st1 = wide ? Z.take(sizeof(double) * (size_t)stats_len(p)) : 0;
+    ctx_void_cv(c);
     if (ctx_grow(c, &c->aux, &c->aux_bytes, Z.off)) return OEMGPU_ERR_HIP;
     double *z = (double *)(c->aux + a_z), *yz = (double *)(c->aux + a_yz), *wsd = (double *)(c->aux + a_ws);
     if (w_host) {
@@ -1983,6 +1988,42 @@ static __global__ void scale_intercept_kernel(double *__restrict__ xx, double *_
     else { xx[(size_t)j * q] *= intval; xx[j] *= intval; }
 }
 
+// The oemSparse solve on one moment buffer (both triangles, about 0; its [p + 1][p + 1] entry the number of rows, which stands wherever n
+// enters: the column scales' n - 1, the / n): oemBig's XX and XY (launch_finalize), the intercept's row and column times intval, the
+// paths with get_beta's in-place intercept scale (ref src/oem_sparse.h:493-508, 577-593, 897-900).  oemgpu_fit_sparse and
+// oemgpu_cv_sparse_fold_fits_res both end here.  The workspace: whatever the caller has carved (B), then xx, xy, stats and the paths'
+// frame -- reserved (`need` bytes of c->ws) BEFORE the moments are computed if they live in c->ws themselves.
+struct SparseSolveWs { Bump B; size_t a_xx, a_xy, a_st, need; };
+static SparseSolveWs sparse_solve_ws(Bump B, int p, int q, const oemgpu_opts *o)
+{
+    SparseSolveWs W;
+    W.a_xx = B.take((size_t)q * q * 8); W.a_xy = B.take((size_t)q * 8); W.a_st = B.take((size_t)stats_len(p) * 8);
+    W.B = B;
+    W.need = B.off + paths_ws_bytes(p, q, o) + 4096;
+    return W;
+}
+static int sparse_solve(oemgpu_ctx *c, const SparseSolveWs &W, const double *mom, int p, int q, int standardize, int intercept, const oemgpu_opts *o,
+                        double intval, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+{
+    double *xx = (double *)(c->ws + W.a_xx), *xy = (double *)(c->ws + W.a_xy), *st = (double *)(c->ws + W.a_st);
+    int rc = launch_finalize(c->stream, mom, nullptr, p, OEMGPU_SEM_BIG, standardize, intercept, xx, xy, st);
+    if (rc) return rc;
+    std::vector<double> sf;
+    if (intercept) {
+        hipLaunchKernelGGL(scale_intercept_kernel, dim3((q + 255) / 256), dim3(256), 0, c->stream, xx, xy, q, intval);
+        sf.assign(q, 1.0); sf[0] = 1.0 / intval;              // get_beta multiplies the intercept slot by intval, in place (ref :897-900)
+    }
+    Bump B = W.B;
+    return run_paths(c, B, xx, xy, st, p, q, SEM_SPARSE, standardize, intercept, o, intercept ? sf.data() : nullptr, beta, lambda_out, niter, loss, d);
+}
+
+// diag[j] = sum x_j^2 of a moment buffer ((p + 2)^2), j < p
+static __global__ void moment_diag_kernel(const double *__restrict__ M, int p, double *__restrict__ diag)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < p) diag[j] = M[(size_t)j * (p + 2) + j];
+}
+
 // nbatch moment buffers (instance b at moments + b * mstride, all OUTSIDE the context workspace), one finalize each, then ONE
 // launch that walks all their paths side by side (q <= SMALL_P_MAX).  Outputs as in run_paths.
 // cs != nullptr: observation weights -- the moments are those of the p + 1 data columns [sqrt(w) | sqrt(w) X] ((p + 3)^2 each) and
@@ -2021,6 +2062,7 @@ static int any_grp_count(const oemgpu_opts *o)
 static int ctx_aux(oemgpu_ctx *c, size_t bytes)
 {
     if (bytes <= c->aux_bytes) return 0;
+    ctx_void_cv(c);                                              // (a new allocation may come back at the old address)
     if (c->aux) { OEM_HIP(hipStreamSynchronize(c->stream)); OEM_HIP(hipFree(c->aux)); c->aux = nullptr; c->aux_bytes = 0; }
     OEM_HIP(hipMalloc((void **)&c->aux, bytes)); ++g_alloc_count;
     c->aux_bytes = bytes;
@@ -2114,7 +2156,7 @@ static int xval_prepare(oemgpu_ctx *c, const XvalLay &L, const double *x_dev, in
     int64_t *fold_n = (int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
     double *xp = (double *)(ax + L.a_xp), *yp = (double *)(ax + L.a_yp);
     // ---- rows into fold order (whatever cv.oem's layout stamp vouched for is overwritten from here on: cv_lay_out stamps again)
-    c->cv_n = 0;
+    ctx_void_cv(c);
     hf.assign(2 * K, 0);
     int hbad = 0, rc;
     {
@@ -2350,6 +2392,7 @@ int oemgpu_xval_solve_folds_dev(oemgpu_ctx *c, const double *fold_moments_dev, c
     if (set_device(c)) return OEMGPU_ERR_HIP;
     const XvalLay L = xval_layout(c, n_local, p, K, o->npen, nl_of(o), weighted != 0);
     if (c->aux_bytes < L.total) { set_error("xval_solve_folds: call oemgpu_xval_fold_moments_dev with the same arguments first"); return OEMGPU_ERR_ARG; }
+    ctx_void_cv(c);                                              // the moments, sums and coefficients below land at THIS layout's offsets
     OEM_HIP(hipMemcpyAsync(c->aux + L.a_mf, fold_moments_dev, sizeof(double) * L.mlen * K, hipMemcpyDeviceToDevice, c->stream));
     if (weighted) OEM_HIP(hipMemcpyAsync(c->aux + L.a_cs, fold_moments_dev + L.mlen * K, sizeof(double) * L.cslen * K, hipMemcpyDeviceToDevice, c->stream));
     int64_t n_tot = 0;
@@ -2366,6 +2409,7 @@ int oemgpu_xval_cv_triples_dev(oemgpu_ctx *c, int64_t n_local, int32_t p, int32_
     if (set_device(c)) return OEMGPU_ERR_HIP;
     const XvalLay L = xval_layout(c, n_local, p, nfolds, o->npen, nl_of(o), weighted != 0);
     if (c->aux_bytes < L.total) { set_error("xval_cv_triples: call the first two phases with the same arguments first"); return OEMGPU_ERR_ARG; }
+    ctx_void_cv(c);                                              // the partials land at THIS layout's offsets
     return xval_cverr(c, L, type_measure, o, nullptr, nullptr, triples);
 }
 
@@ -2468,7 +2512,7 @@ static int cv_lay_out(oemgpu_ctx *c, const CvLay &V, const double *x_dev, int64_
     if (ctx_aux(c, V.total)) return OEMGPU_ERR_HIP;
     int rc = xval_prepare(c, V.L, x_dev, ld, y_dev, nullptr, foldid_dev, hf, moments);
     if (rc) return rc;
-    c->cv_n = V.L.n; c->cv_p = V.L.p; c->cv_K = V.L.K; c->cv_aux = c->aux; c->cv_hf = hf;
+    c->cv_n = V.L.n; c->cv_p = V.L.p; c->cv_K = V.L.K; c->cv_aux = c->aux; c->cv_hf = hf; c->cv_kind = CV_KIND_DENSE;
     return 0;
 }
 
@@ -2538,7 +2582,7 @@ int oemgpu_cv_score_dev(oemgpu_ctx *c, int64_t n, int32_t p, int32_t nfolds, con
     if (rc) return rc;
     for (int k = 0; k < npen; ++k)
         if (ncol[k] < 0 || ncol[k] > nl) { set_error("cv_score: ncol[%d] = %d is outside 0..%d", k, ncol[k], nl); return OEMGPU_ERR_ARG; }
-    if (c->cv_n != n || c->cv_p != p || c->cv_K != K || !c->aux || c->cv_aux != c->aux || (int)c->cv_hf.size() != 2 * K) {
+    if (c->cv_kind != CV_KIND_DENSE || c->cv_n != n || c->cv_p != p || c->cv_K != K || !c->aux || c->cv_aux != c->aux || (int)c->cv_hf.size() != 2 * K) {
         set_error("cv_score: call oemgpu_cv_fold_fits_dev with the same n, p and nfolds on this context first"); return OEMGPU_ERR_ARG;
     }
     if (set_device(c)) return OEMGPU_ERR_HIP;
@@ -2728,6 +2772,78 @@ static thread_local double g_xvs_ms[OEMGPU_XVS_NPHASES] = {0, 0, 0, 0, 0, 0};
 
 enum { XVS_FULL = 0, XVS_MOMENTS = 1, XVS_CVERR = 2 };
 
+// Phases 1 - 3 of the fold routes on a sparse x, over compressed columns (cd, rd, vd), y and foldid that are on the device -- xval.oem's
+// upload, or an oemgpu_sparse_x and the caller's vectors (cv.oem):
+//   1  fold order: launch_fold_layout with every fold segment on a multiple of CSC_CHUNK rows, hf <- the fold sizes [K] and starts [K],
+//      the chunk ranges, the columns rewritten in that row order, their chunk pointers;
+//   2  (moments) the K fold moment buffers about 0 from ONE pass over the non-zeros, on the route of sparse_route;
+//   3  (rows) the fold-ordered compressed rows.
+// mark() after every phase that ran.  From the device: OEMGPU_ERR_ARG, in `who`'s name, for a fold id outside 1..K.
+struct XvsHost { std::vector<int64_t> hf; std::vector<int32_t> rtab, frange; };   // the caller's: copies enqueued here read them
+static int xvs_fold_phases(oemgpu_ctx *c, const XvalSparsePlan &SP, const XvalLay &L, const int64_t *cd, const int32_t *rd, const double *vd,
+                           const double *yd, const int32_t *fd, int64_t maxcol, bool moments, bool rows, XvsHost &H, const std::function<void()> &mark,
+                           const char *who)
+{
+    std::vector<int64_t> &hf = H.hf;
+    std::vector<int32_t> &rtab = H.rtab, &frange = H.frange;
+    const int64_t n = L.n;
+    const int K = L.K, p = L.p;
+    hipStream_t s = c->stream;
+    char *ax = c->aux, *sx = c->aux + L.total;
+    int64_t *rowptr = (int64_t *)(sx + SP.a_rowptr);
+    int32_t *prow = (int32_t *)(sx + SP.a_prow), *cfo = (int32_t *)(sx + SP.a_cfo), *cptr = (int32_t *)(sx + SP.a_cptr), *ccol = (int32_t *)(sx + SP.a_ccol),
+            *rtab_d = (int32_t *)(sx + SP.a_rtab);
+    double *pval = (double *)(sx + SP.a_pval), *cval = (double *)(sx + SP.a_cval);
+    int *blockcnt = (int *)(ax + L.a_cnt), *bad = (int *)(ax + L.a_bad), *pos = (int *)(ax + L.a_pos);
+    int64_t *fold_n = (int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
+    double *yp = (double *)(ax + L.a_yp), *mfold = (double *)(ax + L.a_mf);
+    // ---- phase 1: fold order
+    int rc = launch_fold_layout(s, fd, n, K, blockcnt, fold_n, fold_start, pos, bad, CSC_CHUNK);
+    if (rc) return rc;
+    hf.assign(2 * (size_t)K, 0);
+    int hbad = 0;
+    OEM_HIP(hipMemcpyAsync(hf.data(), fold_n, sizeof(int64_t) * 2 * K, hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipStreamSynchronize(s));
+    if (hbad) { set_error("%s: foldid must hold values in 1..nfolds", who); return OEMGPU_ERR_ARG; }
+    int64_t npad = 0;
+    rc = xval_sparse_ranges(SP, hf.data(), rtab, frange, &npad);
+    if (rc) return rc;
+    const int nrange = (int)rtab.size() - 1, nchunk = (int)(npad / CSC_CHUNK);
+    int32_t *frange_d = rtab_d + SP.nrange_max + 1;
+    OEM_HIP(hipMemcpyAsync(rtab_d, rtab.data(), sizeof(int32_t) * rtab.size(), hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemcpyAsync(frange_d, frange.data(), sizeof(int32_t) * frange.size(), hipMemcpyHostToDevice, s));
+    rc = launch_csc_fold_permute(s, cd, rd, vd, yd, fd, pos, n, p, K, npad, cfo, prow, pval, yp);
+    if (!rc) rc = launch_csc_chunk_ptr(s, cd, prow, npad, p, cptr);
+    if (rc) return rc;
+    mark();
+    // ---- phase 2: the K fold moment buffers from one pass over the non-zeros
+    if (moments) {
+        if (SP.R.csc) {
+            rc = launch_csc_fold_moments(s, cd, prow, pval, yp, cptr, cfo, fold_start, fold_n, p, K, nchunk, nrange, rtab_d, frange_d,
+                                         (double *)(sx + SP.a_gpart), (double *)(sx + SP.a_ypart), mfold);
+            if (rc) return rc;
+        } else {
+            for (int k = 0; k < K; ++k) {
+                double *Mk = mfold + L.mlen * k;
+                if (hf[k] == 0) { OEM_HIP(hipMemsetAsync(Mk, 0, sizeof(double) * L.mlen, s)); continue; }
+                rc = csc_tile_moments(c, SP.R, cd, prow, pval, nullptr, yp, npad, p, maxcol, (double *)(sx + SP.a_tile), (double *)(ax + L.a_t),
+                                      (double *)(ax + L.a_v), (double *)(sx + SP.a_mtile), Mk, hf[K + k], hf[k]);
+                if (rc) return rc;
+            }
+        }
+        mark();
+    }
+    // ---- phase 3: the compressed-row copy of the fold-ordered matrix
+    if (rows) {
+        rc = launch_csr_rowptr(s, cd, prow, cptr, p, nchunk, rowptr);
+        if (!rc) rc = launch_csc_to_csr(s, cd, prow, pval, cptr, npad, p, rowptr, ccol, cval);
+        if (rc) return rc;
+        mark();
+    }
+    return 0;
+}
+
 // The call in one place; the two selftests stop early (XVS_MOMENTS: after the K moment buffers) or skip the fits (XVS_CVERR: coefficients
 // of the caller's).  mode != XVS_FULL: o is NULL, npen / nl are the caller's.
 static int xval_sparse_impl(int mode, int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, const double *y,
@@ -2764,13 +2880,12 @@ static int xval_sparse_impl(int mode, int64_t n, int32_t p, const int64_t *colpt
 
     const XvalSparsePlan SP = xval_sparse_plan(n, p, nnz, K, npen, nl, c->num_cu);
     const XvalLay L = xval_layout(c->num_cu, n, p, K, npen, nl, false, &SP);
+    ctx_void_cv(c);
     if (ctx_aux(c, L.total + SP.bytes)) return OEMGPU_ERR_HIP;
     char *ax = c->aux, *sx = c->aux + L.total;
     int64_t *cd = (int64_t *)(sx + SP.a_col), *rowptr = (int64_t *)(sx + SP.a_rowptr);
-    int32_t *rd = (int32_t *)(sx + SP.a_row), *fd = (int32_t *)(sx + SP.a_fid), *prow = (int32_t *)(sx + SP.a_prow), *cfo = (int32_t *)(sx + SP.a_cfo),
-            *cptr = (int32_t *)(sx + SP.a_cptr), *ccol = (int32_t *)(sx + SP.a_ccol), *rtab_d = (int32_t *)(sx + SP.a_rtab);
-    double *vd = (double *)(sx + SP.a_val), *yd = (double *)(sx + SP.a_y), *pval = (double *)(sx + SP.a_pval), *cval = (double *)(sx + SP.a_cval);
-    int *blockcnt = (int *)(ax + L.a_cnt), *bad = (int *)(ax + L.a_bad), *pos = (int *)(ax + L.a_pos);
+    int32_t *rd = (int32_t *)(sx + SP.a_row), *fd = (int32_t *)(sx + SP.a_fid), *ccol = (int32_t *)(sx + SP.a_ccol);
+    double *vd = (double *)(sx + SP.a_val), *yd = (double *)(sx + SP.a_y), *cval = (double *)(sx + SP.a_cval);
     int64_t *fold_n = (int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
     double *yp = (double *)(ax + L.a_yp), *mfold = (double *)(ax + L.a_mf), *bdev = (double *)(ax + L.a_b);
 
@@ -2783,53 +2898,17 @@ static int xval_sparse_impl(int mode, int64_t n, int32_t p, const int64_t *colpt
     }
     OEM_HIP(hipMemcpyAsync(yd, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
     OEM_HIP(hipMemcpyAsync(fd, foldid, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-    // ---- phase 1: fold order
+    // ---- phases 1 - 3: fold order, the K fold moment buffers, the fold-ordered compressed rows
     mark();
-    rc = launch_fold_layout(s, fd, n, K, blockcnt, fold_n, fold_start, pos, bad, CSC_CHUNK);
+    XvsHost H;
+    rc = xvs_fold_phases(c, SP, L, cd, rd, vd, yd, fd, maxcol, true, mode != XVS_MOMENTS, H, mark, "xval_dense");   // (the message xval.oem has always given)
     if (rc) return rc;
-    std::vector<int64_t> hf(2 * (size_t)K, 0);
-    int hbad = 0;
-    OEM_HIP(hipMemcpyAsync(hf.data(), fold_n, sizeof(int64_t) * 2 * K, hipMemcpyDeviceToHost, s));
-    OEM_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
-    OEM_HIP(hipStreamSynchronize(s));
-    if (hbad) { set_error("xval_dense: foldid must hold values in 1..nfolds"); return OEMGPU_ERR_ARG; }
-    std::vector<int32_t> rtab, frange;
-    int64_t npad = 0;
-    rc = xval_sparse_ranges(SP, hf.data(), rtab, frange, &npad);
-    if (rc) return rc;
-    const int nrange = (int)rtab.size() - 1, nchunk = (int)(npad / CSC_CHUNK);
-    int32_t *frange_d = rtab_d + SP.nrange_max + 1;
-    OEM_HIP(hipMemcpyAsync(rtab_d, rtab.data(), sizeof(int32_t) * rtab.size(), hipMemcpyHostToDevice, s));
-    OEM_HIP(hipMemcpyAsync(frange_d, frange.data(), sizeof(int32_t) * frange.size(), hipMemcpyHostToDevice, s));
-    rc = launch_csc_fold_permute(s, cd, rd, vd, yd, fd, pos, n, p, K, npad, cfo, prow, pval, yp);
-    if (!rc) rc = launch_csc_chunk_ptr(s, cd, prow, npad, p, cptr);
-    if (rc) return rc;
-    // ---- phase 2: the K fold moment buffers from one pass over the non-zeros
-    mark();
-    if (SP.R.csc) {
-        rc = launch_csc_fold_moments(s, cd, prow, pval, yp, cptr, cfo, fold_start, fold_n, p, K, nchunk, nrange, rtab_d, frange_d,
-                                     (double *)(sx + SP.a_gpart), (double *)(sx + SP.a_ypart), mfold);
-        if (rc) return rc;
-    } else {
-        for (int k = 0; k < K; ++k) {
-            double *Mk = mfold + L.mlen * k;
-            if (hf[k] == 0) { OEM_HIP(hipMemsetAsync(Mk, 0, sizeof(double) * L.mlen, s)); continue; }
-            rc = csc_tile_moments(c, SP.R, cd, prow, pval, nullptr, yp, npad, p, maxcol, (double *)(sx + SP.a_tile), (double *)(ax + L.a_t),
-                                  (double *)(ax + L.a_v), (double *)(sx + SP.a_mtile), Mk, hf[K + k], hf[k]);
-            if (rc) return rc;
-        }
-    }
-    mark();
+    const std::vector<int64_t> &hf = H.hf;
     if (mode == XVS_MOMENTS) {
         OEM_HIP(hipMemcpyAsync(moments_out, mfold, sizeof(double) * L.mlen * K, hipMemcpyDeviceToHost, s));
         OEM_HIP(hipStreamSynchronize(s));
         return 0;
     }
-    // ---- phase 3: the compressed-row copy of the fold-ordered matrix
-    rc = launch_csr_rowptr(s, cd, prow, cptr, p, nchunk, rowptr);
-    if (!rc) rc = launch_csc_to_csr(s, cd, prow, pval, cptr, npad, p, rowptr, ccol, cval);
-    if (rc) return rc;
-    mark();
     // ---- phase 4: the K + 1 fits (xval_solve as it is: the moment buffers carry the column sums and n)
     if (mode == XVS_FULL) rc = xval_solve(c, L, hf.data(), n, standardize, intercept, o, beta, lambda_out, niter, loss, d);
     else OEM_HIP(hipMemcpyAsync(bdev, coef, sizeof(double) * (size_t)K * npen * nl * (p + 1), hipMemcpyHostToDevice, s));
@@ -2922,6 +3001,212 @@ int oemgpu_selftest_xval_sparse_cv_error(int64_t n, int32_t p, const int64_t *co
                             nullptr, nullptr, nullptr, cvm, cvsd, triples, nullptr);
 }
 
+// ---------------------------------------------------------------------------------------------- cv.oem, family = "gaussian", sparse x
+// One layout function for the whole call (the entries and oemgpu_selftest_cv_sparse_plan read it): xval.oem's sparse plan without the
+// upload regions (the handle holds the columns), the xval layout in front of it, and behind both this route's own regions -- the
+// per-fold wave partials of the scoring launch, the per-fold triples, the valid columns per penalty, the inverse of the fold
+// permutation for the prediction store, the diagonal of a summed moment buffer on its way to the host (intval).
+struct CvSparseLay {
+    XvalSparsePlan SP;
+    XvalLay L;
+    CvSparseScorePlan S;
+    size_t a_part, a_tri, a_ncol, a_inv, a_diag, own, total;
+};
+static CvSparseLay cv_sparse_layout(int num_cu, int64_t n, int p, int64_t nnz, int K, int npen, int nl)
+{
+    CvSparseLay V;
+    V.SP = xval_sparse_plan(n, p, nnz, K, npen, nl, num_cu, true);
+    V.L = xval_layout(num_cu, n, p, K, npen, nl, false, &V.SP);
+    V.S = cv_sparse_score_plan(n, K, npen, nl, num_cu);
+    Bump A; A.off = V.L.total + V.SP.bytes;
+    V.a_part = A.take(V.S.part_bytes); V.a_tri = A.take(sizeof(double) * 3 * (size_t)K * npen * nl); V.a_ncol = A.take(sizeof(int) * (size_t)npen);
+    V.a_inv = A.take(sizeof(int) * (size_t)V.SP.npad_max); V.a_diag = A.take(sizeof(double) * (size_t)p);
+    V.total = A.off;
+    V.own = V.total - V.L.total - V.SP.bytes;
+    return V;
+}
+
+static int cv_sparse_check_rows(const char *who, int64_t n, int p, int K)
+{
+    if (K < 2 || K > 512) { set_error("%s: nfolds must be in 2..512", who); return OEMGPU_ERR_ARG; }
+    if (n < 1 || p < 1) { set_error("%s: bad n or p", who); return OEMGPU_ERR_ARG; }
+    if (n + (int64_t)CSC_CHUNK * K >= (int64_t)1 << 31) { set_error("%s: n too large for 32-bit row positions", who); return OEMGPU_ERR_UNSUPPORTED; }
+    return 0;
+}
+
+// phases 1 - 3 on the handle's arrays, and the stamp oemgpu_cv_sparse_score_res looks for; ms != nullptr: the phase times
+static int cv_sparse_lay_out(oemgpu_ctx *c, const CvSparseLay &V, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev,
+                             bool moments, XvsHost &H, bool timed, const char *who)
+{
+    ctx_void_cv(c);
+    if (ctx_aux(c, V.total)) return OEMGPU_ERR_HIP;
+    if (timed && !c->xvs_ev_made) {
+        for (int i = 0; i <= OEMGPU_XVS_NPHASES; ++i) OEM_HIP(hipEventCreate(&c->xvs_ev[i]));
+        c->xvs_ev_made = true;
+    }
+    int nmark = 0;
+    auto mark = [&]() { if (timed && nmark <= OEMGPU_XVS_NPHASES) (void)hipEventRecord(c->xvs_ev[nmark++], c->stream); };
+    mark(); mark();                                              // (no upload phase: the handle holds the columns)
+    int rc = xvs_fold_phases(c, V.SP, V.L, x->colptr, x->rowidx, x->val, y_dev, foldid_dev, x->maxcol, moments, true, H, mark, who);
+    if (rc) return rc;
+    c->cv_n = V.L.n; c->cv_p = V.L.p; c->cv_K = V.L.K; c->cv_aux = c->aux; c->cv_hf = H.hf; c->cv_kind = CV_KIND_SPARSE;
+    c->cv_nnz = x->nnz; c->cv_npen = V.L.npen; c->cv_nl = V.L.nl;
+    return 0;
+}
+
+int oemgpu_cv_sparse_fold_fits_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
+                                   int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                                   double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int64_t *fold_n)
+{
+    static const char *who = "cv_sparse_fold_fits";
+    if (!c || !x || !y_dev || !foldid_dev || !o || !beta || !lambda_out || !niter || !loss || !d || !fold_n) {
+        set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG;
+    }
+    const int64_t n = x->n;
+    const int p = x->p, K = nfolds, q = p + (intercept ? 1 : 0);
+    int rc = check_opts(o, p, q);                               // the intercept's group comes first, as in oemgpu_fit_sparse
+    if (!rc) rc = cv_sparse_check_rows(who, n, p, K);
+    if (rc) return rc;
+    // the largest fold holds at least ceil(n / K) rows: some fold fit is then not the Gram form whatever the ids are
+    if (n - (n + K - 1) / K <= p) {
+        set_error("%s: %lld rows in %d folds leave some fold no more rows than the %d columns", who, (long long)n, K, p);
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    if (c->device != x->device) { set_error("%s: the context and the sparse x are on different devices", who); return OEMGPU_ERR_ARG; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const int npen = o->npen, nl = nl_of(o);
+    const CvSparseLay V = cv_sparse_layout(c->num_cu, n, p, x->nnz, K, npen, nl);
+    const XvalLay &L = V.L;
+    for (double &v : g_xvs_ms) v = 0.0;
+    XvsHost H;
+    rc = cv_sparse_lay_out(c, V, x, y_dev, foldid_dev, true, H, true, who);
+    if (rc) return rc;
+    const std::vector<int64_t> &hf = H.hf;
+    for (int k = 0; k < K; ++k) {
+        fold_n[k] = hf[k];
+        if (n - hf[k] <= p) {
+            set_error("%s: fold %d leaves %lld rows for %d columns (the fit of p >= n is not this route's)", who, k + 1, (long long)(n - hf[k]), p);
+            return OEMGPU_ERR_UNSUPPORTED;
+        }
+    }
+    char *ax = c->aux;
+    const double *mfold = (const double *)(ax + L.a_mf);
+    double *msum = (double *)(ax + L.a_ms), *diag = (double *)(ax + V.a_diag);
+    const SparseSolveWs W = sparse_solve_ws(Bump{}, p, q, o);   // the moment buffers live in aux: the workspace holds the solve alone
+    if (ctx_reserve(c, W.need)) return OEMGPU_ERR_HIP;
+    const size_t blen = (size_t)npen * nl * (p + 1), nk2 = (size_t)npen * nl;
+    std::vector<double> hdiag((size_t)p);
+    // slot 0: all rows (the sum of ALL fold buffers); slot ff: the rows outside fold ff (R/cv_oem.R:105, 155-175 -> oem_fit_sparse)
+    for (int ff = 0; ff <= K; ++ff) {
+        double *ms = msum + L.mlen * ff;
+        rc = launch_fold_sum(c->stream, mfold, K, L.mlen, ff, ms);
+        if (rc) return rc;
+        // intval = sqrt(mean(diag(XX)) / n) from the summed buffer's diagonal, the expression of oemgpu_fit_sparse with the kept rows' n
+        const double nkept = (double)(n - (ff ? hf[ff - 1] : 0));
+        double intval = 1.0;
+        if (intercept) {
+            hipLaunchKernelGGL(moment_diag_kernel, dim3((p + 255) / 256), dim3(256), 0, c->stream, ms, p, diag);
+            OEM_HIP(hipGetLastError());
+            OEM_HIP(hipMemcpyAsync(hdiag.data(), diag, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, c->stream));
+            OEM_HIP(hipStreamSynchronize(c->stream));
+            double xxdiag = 0.0;
+            for (int j = 0; j < p; ++j) {
+                const double ss = hdiag[j];
+                double cs = ss / (nkept - 1.0);
+                if (cs == 0.0) cs = 1.0;                          // a column that is empty among the kept rows
+                xxdiag += standardize ? ss / cs : ss;
+            }
+            xxdiag /= (double)p;
+            intval = std::sqrt(xxdiag / nkept);
+        }
+        rc = sparse_solve(c, W, ms, p, q, standardize, intercept, o, intval, beta + blen * ff, lambda_out + nk2 * ff, niter + nk2 * ff,
+                          loss + nk2 * ff, d + ff);
+        if (rc) { if (ff) { const std::string e = oemgpu_last_error(); set_error("fold %d: %s", ff, e.c_str()); } return rc; }
+    }
+    (void)hipEventRecord(c->xvs_ev[5], c->stream);
+    OEM_HIP(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 5; ++i) {
+        float f = 0.f;
+        if (hipEventElapsedTime(&f, c->xvs_ev[i], c->xvs_ev[i + 1]) == hipSuccess) g_xvs_ms[i] = f;
+    }
+    return 0;
+}
+
+int oemgpu_cv_sparse_score_res(oemgpu_ctx *c, int64_t n, int32_t p, int32_t nfolds, const double *coef, int32_t npen, int32_t nl,
+                               const int32_t *ncol, int32_t type_measure, double *triples, double *predmat_dev)
+{
+    static const char *who = "cv_sparse_score";
+    if (!c || !coef || !ncol || !triples) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    if (p < 1 || npen < 1 || nl < 1) { set_error("%s: bad p, npen or nl", who); return OEMGPU_ERR_ARG; }
+    const int K = nfolds;
+    int rc = cv_sparse_check_rows(who, n, p, K);
+    if (rc) return rc;
+    if (type_measure != 0 && type_measure != 1) { set_error("%s: type_measure must be 0 (mse) or 1 (mae)", who); return OEMGPU_ERR_ARG; }
+    for (int k = 0; k < npen; ++k)
+        if (ncol[k] < 0 || ncol[k] > nl) { set_error("%s: ncol[%d] = %d is outside 0..%d", who, k, ncol[k], nl); return OEMGPU_ERR_ARG; }
+    if (c->cv_kind != CV_KIND_SPARSE || c->cv_n != n || c->cv_p != p || c->cv_K != K || c->cv_npen != npen || c->cv_nl != nl || !c->aux ||
+        c->cv_aux != c->aux || (int)c->cv_hf.size() != 2 * K) {
+        set_error("%s: call oemgpu_cv_sparse_fold_fits_res with the same n, p, nfolds, npen and nl on this context first", who); return OEMGPU_ERR_ARG;
+    }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const CvSparseLay V = cv_sparse_layout(c->num_cu, n, p, c->cv_nnz, K, npen, nl);
+    const XvalLay &L = V.L;
+    if (c->aux_bytes < V.total) { set_error("internal: the sparse cv layout is larger than the buffer that holds it"); return OEMGPU_ERR_INTERNAL; }
+    char *ax = c->aux, *sx = c->aux + L.total;
+    int64_t *fold_n = (int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
+    const int *pos = (const int *)(ax + L.a_pos);
+    int *ncol_dev = (int *)(ax + V.a_ncol), *inv = (int *)(ax + V.a_inv);
+    double *bdev = (double *)(ax + L.a_b), *tri = (double *)(ax + V.a_tri);
+    const size_t blen = (size_t)K * npen * nl * (p + 1), tlen = (size_t)3 * K * npen * nl;
+    // the fold sizes and starts go up again from the host copy of phase 1: what the kernels index the rows by is this call's own
+    OEM_HIP(hipMemcpyAsync(fold_n, c->cv_hf.data(), sizeof(int64_t) * 2 * K, hipMemcpyHostToDevice, c->stream));
+    OEM_HIP(hipMemcpyAsync(bdev, coef, sizeof(double) * blen, hipMemcpyHostToDevice, c->stream));
+    OEM_HIP(hipMemcpyAsync(ncol_dev, ncol, sizeof(int) * (size_t)npen, hipMemcpyHostToDevice, c->stream));
+    if (predmat_dev) { rc = launch_fold_inverse(c->stream, pos, n, V.SP.npad_max, inv); if (rc) return rc; }
+    rc = launch_csr_cv_fold_score(c->stream, V.S, p, (const int64_t *)(sx + V.SP.a_rowptr), (const int32_t *)(sx + V.SP.a_ccol),
+                                  (const double *)(sx + V.SP.a_cval), (const double *)(ax + L.a_yp), fold_start, fold_n, bdev,
+                                  (double *)(sx + V.SP.a_bt), type_measure, (double *)(ax + V.a_part), ncol_dev, tri, predmat_dev, inv, n);
+    if (rc) return rc;
+    OEM_HIP(hipMemcpyAsync(triples, tri, sizeof(double) * tlen, hipMemcpyDeviceToHost, c->stream));
+    OEM_HIP(hipStreamSynchronize(c->stream));                   // coef, ncol and triples are the caller's
+    return 0;
+}
+
+// Test infrastructure: the layout and the compressed rows alone -- no moments, nothing fitted, so a fold may leave fewer rows than
+// columns -- then oemgpu_cv_sparse_score_res as it is, on a table of the caller's.
+int oemgpu_selftest_cv_sparse_score(oemgpu_ctx *c, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
+                                    const double *coef, int32_t npen, int32_t nl, const int32_t *ncol, int32_t type_measure, double *triples,
+                                    double *predmat_dev)
+{
+    static const char *who = "selftest_cv_sparse_score";
+    if (!c || !x || !y_dev || !foldid_dev || !coef || !ncol || !triples) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    if (npen < 1 || nl < 1) { set_error("%s: bad npen or nl", who); return OEMGPU_ERR_ARG; }
+    int rc = cv_sparse_check_rows(who, x->n, x->p, nfolds);
+    if (rc) return rc;
+    if (type_measure != 0 && type_measure != 1) { set_error("%s: type_measure must be 0 (mse) or 1 (mae)", who); return OEMGPU_ERR_ARG; }
+    for (int k = 0; k < npen; ++k)
+        if (ncol[k] < 0 || ncol[k] > nl) { set_error("%s: ncol[%d] = %d is outside 0..%d", who, k, ncol[k], nl); return OEMGPU_ERR_ARG; }
+    if (c->device != x->device) { set_error("%s: the context and the sparse x are on different devices", who); return OEMGPU_ERR_ARG; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const CvSparseLay V = cv_sparse_layout(c->num_cu, x->n, x->p, x->nnz, nfolds, npen, nl);
+    XvsHost H;
+    rc = cv_sparse_lay_out(c, V, x, y_dev, foldid_dev, false, H, false, who);
+    if (rc) return rc;
+    return oemgpu_cv_sparse_score_res(c, x->n, x->p, nfolds, coef, npen, nl, ncol, type_measure, triples, predmat_dev);
+}
+
+int oemgpu_selftest_cv_sparse_plan(int64_t n, int32_t p, int64_t nnz, int32_t nfolds, int32_t npen, int32_t nl, int32_t num_cu, int64_t *out)
+{
+    if (nnz < 0 || npen < 1 || nl < 1 || num_cu < 1 || !out) { set_error("selftest_cv_sparse_plan: bad argument"); return OEMGPU_ERR_ARG; }
+    int rc = cv_sparse_check_rows("selftest_cv_sparse_plan", n, p, nfolds);
+    if (rc) return rc;
+    const CvSparseLay V = cv_sparse_layout(num_cu, n, p, nnz, nfolds, npen, nl);
+    out[0] = V.SP.R.csc ? 1 : 0; out[1] = V.S.nwg; out[2] = V.S.waves; out[3] = V.S.lblk; out[4] = (int64_t)V.S.part_bytes;
+    out[5] = (int64_t)V.total; out[6] = (int64_t)V.L.total; out[7] = (int64_t)V.SP.bytes; out[8] = (int64_t)V.own; out[9] = V.SP.npad_max;
+    out[10] = V.S.nl16; out[11] = CSC_CHUNK;
+    return 0;
+}
+
 int oemgpu_fit_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, const double *y,
                       int32_t standardize, int32_t intercept, const oemgpu_opts *o,
                       double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
@@ -2991,21 +3276,13 @@ int oemgpu_fit_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t
         Bump B;
         const size_t mlen = (size_t)oemgpu_moments_len(p);
         const size_t a_mom = B.take(mlen * 8), a_tmp = B.take(mlen * 8), a_t = B.take(plmax.tpart_doubles * 8), a_v = B.take(plmax.vpart_doubles * 8);
-        const size_t a_xx = B.take((size_t)q * q * 8), a_xy = B.take((size_t)q * 8), a_st = B.take((size_t)stats_len(p) * 8);
-        rc = ctx_reserve(c, B.off + paths_ws_bytes(p, q, o) + 4096) ? OEMGPU_ERR_HIP : 0;
+        const SparseSolveWs W = sparse_solve_ws(B, p, q, o);
+        rc = ctx_reserve(c, W.need) ? OEMGPU_ERR_HIP : 0;
         double *mom = (double *)(c->ws + a_mom);
         if (!rc) rc = R.csc ? launch_csc_moments(c->stream, cd, rd, vd, yd, n, p, cwork, mom)
                             : csc_tile_moments(c, R, cd, rd, vd, nullptr, yd, n, p, maxcol, xd, (double *)(c->ws + a_t), (double *)(c->ws + a_v),
                                                (double *)(c->ws + a_tmp), mom);
-        double *xx = (double *)(c->ws + a_xx), *xy = (double *)(c->ws + a_xy), *st = (double *)(c->ws + a_st);
-        if (!rc) rc = launch_finalize(c->stream, mom, nullptr, p, OEMGPU_SEM_BIG, standardize, intercept, xx, xy, st);
-        std::vector<double> sf;
-        if (!rc && intercept) {
-            hipLaunchKernelGGL(scale_intercept_kernel, dim3((q + 255) / 256), dim3(256), 0, c->stream, xx, xy, q, intval);
-            sf.assign(q, 1.0); sf[0] = 1.0 / intval;              // get_beta multiplies the intercept slot by intval, in place (ref :897-900)
-        }
-        if (!rc) rc = run_paths(c, B, xx, xy, st, p, q, SEM_SPARSE, standardize, intercept, o, intercept ? sf.data() : nullptr, beta,
-                                lambda_out, niter, loss, d);
+        if (!rc) rc = sparse_solve(c, W, mom, p, q, standardize, intercept, o, intval, beta, lambda_out, niter, loss, d);
     }
     (void)hipStreamSynchronize(c->stream);
     ctx_release(c);

@@ -131,6 +131,7 @@ int launch_fold_inverse(hipStream_t s, const int *pos, int64_t n, int64_t ldp, i
 int launch_cv_fold_error(hipStream_t s, const double *xp, int64_t ldp, const double *yp, const int64_t *fold_start, const int64_t *fold_n,
                          int K, int p, const double *B, int npen, int nl, int mae, const CvErrPlan &P, double *part, const int *ncol,
                          double *triples, double *predmat, const int *inv, int64_t n);
+int launch_cv_fold_finish(hipStream_t s, const double *part, int per_fold, int K, int npen, int nl, const int *ncol, double *triples);
 
 // ------------------------------------------------------------------ xval.oem on a sparse x (xval_sparse.hip, sparse.hip)
 // The ONE host plan of the call (pure arithmetic): the route of sparse_route, the fold-ordered layout (fold segments start on multiples of
@@ -148,7 +149,8 @@ struct XvalSparsePlan {
     size_t a_col, a_row, a_val, a_y, a_fid, a_prow, a_pval, a_cfo, a_cptr, a_rowptr, a_ccol, a_cval, a_gpart, a_ypart, a_rtab, a_bt, a_tile,
            a_mtile, bytes;
 };
-XvalSparsePlan xval_sparse_plan(int64_t n, int p, int64_t nnz, int K, int npen, int nl, int num_cu);
+// resident (cv.oem on an oemgpu_sparse_x): the compressed columns are the handle's, y and foldid the caller's -- their five regions are empty
+XvalSparsePlan xval_sparse_plan(int64_t n, int p, int64_t nnz, int K, int npen, int nl, int num_cu, bool resident = false);
 // the ranges of the folds as they are: rtab[r] .. rtab[r + 1] the chunks of range r, frange[k] .. frange[k + 1] the ranges of fold k; *npad
 // <- the rows of the fold-ordered layout.  OEMGPU_ERR_INTERNAL if they exceed the plan's bounds
 int xval_sparse_ranges(const XvalSparsePlan &P, const int64_t *fold_n, std::vector<int32_t> &rtab, std::vector<int32_t> &frange, int64_t *npad);
@@ -166,6 +168,23 @@ int launch_csr_rowptr(hipStream_t s, const int64_t *colptr, const int32_t *prow,
 int launch_csr_cv_error(hipStream_t s, const XvalSparsePlan &P, const int64_t *rowptr, const int32_t *ccol, const double *cval, const double *yp,
                         const int64_t *fold_start, const int64_t *fold_n, const double *B, double *bt, int mae, double *part, double *out,
                         bool triples);
+// cv.oem (family = "gaussian") on a resident sparse x: the scoring launch over the fold-ordered compressed rows.  Pure host arithmetic,
+// the ONE place its shape is decided: nwg workgroups of XVS_CVW waves x npen x lblk blocks of 64 lambdas -- about four workgroups per CU
+// over (penalty, lambda block), a wave no fewer than 16 rows, at most 1024 workgroups, and no more waves than keep the per-fold wave
+// partials [K][waves][npen][nl16][4] (part_bytes) under CVS_PART_MAX; never fewer than one workgroup (only K npen nl16 > 500,000
+// then exceeds the bound: 512 folds x 100 lambdas x 9 penalties).
+constexpr size_t CVS_PART_MAX = 64000000;
+struct CvSparseScorePlan {
+    int K, npen, nl, nl16, nwg, waves, lblk;
+    size_t part_bytes;
+};
+CvSparseScorePlan cv_sparse_score_plan(int64_t n, int K, int npen, int nl, int num_cu);
+// B [K][npen][nl][p + 1] -> bt [K][npen][p + 1][nl16]; csr_cv_fold_score_kernel flushes a wave's (rows, centre, sums) at every fold
+// boundary; cv_fold_finish_kernel merges them per fold -> triples[K][npen][nl][3], (0, NaN, NaN) in columns >= ncol[pen] and for empty
+// folds.  predmat != nullptr: eta into predmat[npen][nl][n] at the caller's row inv[fold position], NaN in columns >= ncol[pen].
+int launch_csr_cv_fold_score(hipStream_t s, const CvSparseScorePlan &P, int p, const int64_t *rowptr, const int32_t *ccol, const double *cval,
+                             const double *yp, const int64_t *fold_start, const int64_t *fold_n, const double *B, double *bt, int mae,
+                             double *part, const int *ncol, double *triples, double *predmat, const int *inv, int64_t n);
 int launch_csc_gram_ranges(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const int32_t *cptr, int p, int nchunk,
                            int nrange, const int32_t *rtab, double *part);
 size_t csc_gram_lds_bytes(int p);

@@ -46,9 +46,11 @@ struct oemgpu_ctx {
     char *aux = nullptr;           // xval.oem: fold-ordered copy of X, fold moments, fold coefficients (grow-only)
     size_t aux_bytes = 0;
     // cv.oem (gaussian): the fold layout oemgpu_cv_fold_fits_dev left in aux -- its shape, where aux was, the fold sizes and starts --
-    // which oemgpu_cv_score_dev checks before it reads the fold-ordered rows
-    int64_t cv_n = 0;
-    int cv_p = 0, cv_K = 0;
+    // which oemgpu_cv_score_dev checks before it reads the fold-ordered rows.  cv_kind says whose rows they are: a dense layout
+    // (fold-ordered columns of x) must not be scored by oemgpu_cv_sparse_score_res, nor a sparse one (fold-ordered compressed rows, whose
+    // place in aux also depends on nnz, npen and nl) by oemgpu_cv_score_dev.  Whoever lays aux out anew voids the stamp (ctx_void_cv).
+    int64_t cv_n = 0, cv_nnz = 0;
+    int cv_p = 0, cv_K = 0, cv_kind = 0, cv_npen = 0, cv_nl = 0;
     const char *cv_aux = nullptr;
     std::vector<int64_t> cv_hf;
     std::vector<oemgpu_ctx *> kids;   // xval.oem: one child context (stream, workspace, staging) per concurrent fold fit
@@ -91,6 +93,9 @@ struct oemgpu_ctx {
 namespace oemgpu {
 
 extern std::atomic<long> g_alloc_count;   // device / pinned allocations, stream / event creations (oemgpu_last_host_stats()[7])
+
+enum { CV_KIND_NONE = 0, CV_KIND_DENSE = 1, CV_KIND_SPARSE = 2 };
+inline void ctx_void_cv(oemgpu_ctx *c) { c->cv_n = 0; c->cv_kind = CV_KIND_NONE; }   // aux is about to be overwritten
 
 struct Bump {           // carve-out of a context buffer, 256-byte granules
     size_t off = 0;

@@ -697,6 +697,7 @@ int logistic_irls(oemgpu_ctx *c, LogitData &D, int64_t n, int32_t p, int32_t int
     const size_t a_thr = (!inner_wg && !thr_lds) ? B.take(8 * (size_t)(2 * q + (ng > 0 ? ng : 1))) : 0;
     const size_t a_out = B.take(8 * (size_t)o->npen * nl * (p + 1));
     const size_t a_data = B.take(D.ws_bytes());
+    ctx_void_cv(c);
     if (ctx_grow(c, &c->aux, &c->aux_bytes, B.off)) return OEMGPU_ERR_HIP;
     char *W = c->aux;
     double *sc = (double *)(W + a_s), *beta = (double *)(W + a_b), *birls = (double *)(W + a_bi), *u = (double *)(W + a_u),

@@ -321,6 +321,7 @@ static int logistic_cv_auc_run(oemgpu_ctx *c, const double *pred, int64_t n, int
     const int64_t chunk = P.chunk, nchunk = P.nchunk;
     Bump B;
     const size_t a_perm = B.take(4 * (size_t)n), a_cnt = B.take(4 * (size_t)K * nchunk), a_off = B.take(8 * ((size_t)K + 2));
+    ctx_void_cv(c);
     if (ctx_grow(c, &c->aux, &c->aux_bytes, B.off)) return OEMGPU_ERR_HIP;
     {
         int32_t *perm = (int32_t *)(c->aux + a_perm);

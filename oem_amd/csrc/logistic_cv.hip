@@ -177,6 +177,7 @@ static int cv_score_run(oemgpu_ctx *c, const ROWS X, int64_t n, int32_t p, const
     const size_t out_f = 8 * (size_t)ncol + 1;
     Bump B;
     const size_t a_tab = B.take(8 * tab_f * nfolds), a_part = B.take(8 * (size_t)nchunk * (8 * (size_t)cb + 1)), a_out = B.take(8 * out_f * nfolds);
+    ctx_void_cv(c);
     if (ctx_grow(c, &c->aux, &c->aux_bytes, B.off)) return OEMGPU_ERR_HIP;
     double *tab = (double *)(c->aux + a_tab), *part = (double *)(c->aux + a_part), *out = (double *)(c->aux + a_out);
     OEM_HIP(hipMemcpyAsync(tab, coef, 8 * tab_f * nfolds, hipMemcpyHostToDevice, s));

@@ -504,6 +504,8 @@ void oemgpu_sparse_x_destroy(oemgpu_sparse_x *x)
     delete x;
 }
 
+int64_t oemgpu_sparse_x_bytes(const oemgpu_sparse_x *x) { return x ? (int64_t)x->bytes : 0; }
+
 int oemgpu_fit_logistic_sparse_fold_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
                                         int32_t leave_out, int32_t standardize, int32_t intercept, int32_t irls_maxit, double irls_tol,
                                         const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)

@@ -579,7 +579,13 @@ int launch_cv_fold_error(hipStream_t s, const double *xp, int64_t ldp, const dou
 {
     int rc = launch_cv_product(s, xp, ldp, yp, fold_start, fold_n, K, p, B, npen, nl, mae, 0, P, part, predmat, inv, ncol, n);
     if (rc) return rc;
-    hipLaunchKernelGGL(cv_fold_finish_kernel, dim3(npen * nl, K), dim3(64), 0, s, part, P.nwg * CVW, npen, nl, ncol, triples);
+    return launch_cv_fold_finish(s, part, P.nwg * CVW, K, npen, nl, ncol, triples);
+}
+
+// the per-fold merge of launch_cv_fold_error alone, for partials [K][per_fold][npen][nl16][4] some other kernel wrote (xval_sparse.hip)
+int launch_cv_fold_finish(hipStream_t s, const double *part, int per_fold, int K, int npen, int nl, const int *ncol, double *triples)
+{
+    hipLaunchKernelGGL(cv_fold_finish_kernel, dim3(npen * nl, K), dim3(64), 0, s, part, per_fold, npen, nl, ncol, triples);
     OEM_HIP(hipGetLastError());
     return 0;
 }

@@ -12,6 +12,8 @@
 //   * CV error: csr_cv_error_kernel -- a wave per row of the fold-ordered compressed rows, lanes over the lambdas, the fold's
 //     coefficients transposed to [p + 1][nl16] so that the lambdas of one column are one 512-byte read; per-wave partials in the layout
 //     cv_finish_kernel reads.
+// cv.oem(family = "gaussian") on a resident sparse x (api.hip: oemgpu_cv_sparse_*) runs the same fold phases on an oemgpu_sparse_x and scores
+// with csr_cv_fold_score_kernel: the same walk over the compressed rows, flushed per fold into the layout cv_fold_finish_kernel merges.
 #include "ctx.hpp"
 
 namespace oemgpu {
@@ -221,10 +223,85 @@ __global__ __launch_bounds__(64 * XVS_CVW) void csr_cv_error_kernel(const int64_
     }
 }
 
+// cv.oem, family = "gaussian" (cvcompute's fold means, R/utils.R:128-144, and fit.preval): the kernel above keeps ONE running set per lane
+// over all folds; this one FLUSHES the lane's set at every fold boundary -- part [K][waves][npen][nl16][4], zeros from a wave that saw no
+// row of the fold: the layout cv_fold_finish_kernel merges with per_fold = waves -- and starts the next fold with an empty one.  The
+// wave's fixed stride over the n rows as numbered in fold order stays: folds of very unequal size are balanced, which one grid slice
+// per fold would not be.  Columns >= ncol[pen] cost no arithmetic.  PRED: eta goes to predmat[pen][lam][inv[row]] (the caller's row),
+// NaN for lam in [ncol[pen], nl): one store instruction writes 64 words n * 8 bytes apart -- the scattered pattern of cv_error_kernel's
+// PRED store, priced there and not tuned here; nothing of size n * nl exists without predmat.
+// Bound: one read of the compressed rows (12 nnz + 16 n bytes) per (penalty, 64-lambda block); the coefficient rows bt[col][lam] are
+// 512-byte reads that stay in L2 (K npen (p + 1) nl16 doubles).
+template <bool PRED>
+__global__ __launch_bounds__(64 * XVS_CVW) void csr_cv_fold_score_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ ccol,
+                                                                         const double *__restrict__ cval, const double *__restrict__ yp,
+                                                                         const int64_t *__restrict__ fold_start, const int64_t *__restrict__ fold_n,
+                                                                         int K, int p, const double *__restrict__ bt, int nl, int mae,
+                                                                         const int *__restrict__ ncol, double *__restrict__ part,
+                                                                         double *__restrict__ pred, const int *__restrict__ inv, int64_t n)
+{
+    const int npen = gridDim.y, pen = blockIdx.y, lane = threadIdx.x & 63;
+    const int64_t W = (int64_t)gridDim.x * XVS_CVW;
+    const int64_t gw = (int64_t)blockIdx.x * XVS_CVW + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nl16 = (nl + 15) & ~15, lam = blockIdx.z * 64 + lane, Kd = p + 1;
+    const int nc = ncol[pen];
+    const bool active = lam < nc;                                  // a valid column of this penalty
+    const bool any = blockIdx.z * 64 < nc;                         // wave-uniform: some lane of the block is
+    int64_t prefix = 0;
+    for (int k = 0; k < K; ++k) {
+        const int64_t nk = fold_n[k], st = fold_start[k];
+        const double *Bk = bt + ((size_t)k * npen + pen) * Kd * nl16 + (active ? lam : 0);
+        const double b0 = Bk[0];
+        double cnt = 0.0, cen = 0.0, s1 = 0.0, s2 = 0.0;
+        int64_t r = (gw - prefix % W + W) % W;                     // the first row of fold k whose number is g modulo W
+        for (; r < nk; r += W) {
+            const int64_t row = st + r;
+            double eta = b0;
+            if (any) {
+                const int64_t e0 = rowptr[row], e1 = rowptr[row + 1];
+                for (int64_t e = e0; e < e1; ++e) eta = fma(cval[e], Bk[(size_t)(ccol[e] + 1) * nl16], eta);
+                if (active) {
+                    const double res = yp[row] - eta, v = mae ? fabs(res) : res * res;
+                    if (cnt == 0.0) cen = v;
+                    const double dv = v - cen;
+                    s1 += dv; s2 = fma(dv, dv, s2); cnt += 1.0;
+                }
+            }
+            if constexpr (PRED) {
+                const int64_t orig = inv[row];
+                if (lam < nl && orig >= 0 && orig < n) pred[((size_t)pen * nl + lam) * n + orig] = active ? eta : __builtin_nan("");
+            }
+        }
+        if (lam < nl16) {                                          // the fold's flush; a wave without a row of it writes zeros
+            double *q = part + ((((size_t)k * W + gw) * npen + pen) * nl16 + lam) * 4;
+            q[0] = cnt; q[1] = cen; q[2] = s1; q[3] = s2;
+        }
+        prefix += nk;
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------- the plan
-XvalSparsePlan xval_sparse_plan(int64_t n, int p, int64_t nnz, int K, int npen, int nl, int num_cu)
+CvSparseScorePlan cv_sparse_score_plan(int64_t n, int K, int npen, int nl, int num_cu)
+{
+    CvSparseScorePlan P;
+    P.K = K; P.npen = npen; P.nl = nl; P.nl16 = (nl + 15) & ~15;
+    P.lblk = (nl + 63) / 64;
+    int64_t nwg = (int64_t)num_cu * 4 / ((int64_t)npen * P.lblk);
+    const int64_t cap = (n + 16 * XVS_CVW - 1) / (16 * XVS_CVW);
+    if (nwg > cap) nwg = cap;
+    if (nwg > 1024) nwg = 1024;
+    const size_t per_wave = (size_t)K * npen * P.nl16 * 4 * sizeof(double);
+    const int64_t fit = (int64_t)(CVS_PART_MAX / per_wave) / XVS_CVW;       // workgroups whose waves' partials stay under the bound
+    if (nwg > fit) nwg = fit;
+    P.nwg = nwg < 1 ? 1 : (int)nwg;
+    P.waves = P.nwg * XVS_CVW;
+    P.part_bytes = per_wave * P.waves;
+    return P;
+}
+
+XvalSparsePlan xval_sparse_plan(int64_t n, int p, int64_t nnz, int K, int npen, int nl, int num_cu, bool resident)
 {
     XvalSparsePlan P;
     P.n = n; P.nnz = nnz; P.p = p; P.K = K; P.npen = npen; P.nl = nl; P.nl16 = (nl + 15) & ~15;
@@ -252,8 +329,9 @@ XvalSparsePlan xval_sparse_plan(int64_t n, int p, int64_t nnz, int K, int npen, 
     if (!P.R.csc) P.plmax = gram_plan_bound(P.R.rows, p, num_cu);
     Bump A;
     const size_t ne = (size_t)nnz + 1;
-    P.a_col = A.take(sizeof(int64_t) * ((size_t)p + 1)); P.a_row = A.take(sizeof(int32_t) * ne); P.a_val = A.take(sizeof(double) * ne);
-    P.a_y = A.take(sizeof(double) * (size_t)n); P.a_fid = A.take(sizeof(int32_t) * (size_t)n);
+    P.a_col = A.take(resident ? 0 : sizeof(int64_t) * ((size_t)p + 1)); P.a_row = A.take(resident ? 0 : sizeof(int32_t) * ne);
+    P.a_val = A.take(resident ? 0 : sizeof(double) * ne);
+    P.a_y = A.take(resident ? 0 : sizeof(double) * (size_t)n); P.a_fid = A.take(resident ? 0 : sizeof(int32_t) * (size_t)n);
     P.a_prow = A.take(sizeof(int32_t) * ne); P.a_pval = A.take(sizeof(double) * ne);
     P.a_cfo = A.take(sizeof(int32_t) * (size_t)p * (K + 1));
     P.a_cptr = A.take(sizeof(int32_t) * ((size_t)P.nchunk_max + 1) * p);
@@ -328,6 +406,23 @@ int launch_csr_cv_error(hipStream_t s, const XvalSparsePlan &P, const int64_t *r
                        fold_n, P.K, P.p, bt, P.nl, mae, part);
     OEM_HIP(hipGetLastError());
     return launch_cv_finish(s, part, P.cv_waves, P.npen, P.nl, (double)P.n, out, triples);
+}
+
+int launch_csr_cv_fold_score(hipStream_t s, const CvSparseScorePlan &P, int p, const int64_t *rowptr, const int32_t *ccol, const double *cval,
+                             const double *yp, const int64_t *fold_start, const int64_t *fold_n, const double *B, double *bt, int mae,
+                             double *part, const int *ncol, double *triples, double *predmat, const int *inv, int64_t n)
+{
+    const size_t total = (size_t)P.K * P.npen * (p + 1) * P.nl16;
+    hipLaunchKernelGGL(coef_transpose_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, B, p + 1, P.nl, P.nl16, total, bt);
+    const dim3 grid(P.nwg, P.npen, P.lblk), block(64 * XVS_CVW);
+    if (predmat)
+        hipLaunchKernelGGL(csr_cv_fold_score_kernel<true>, grid, block, 0, s, rowptr, ccol, cval, yp, fold_start, fold_n, P.K, p, bt, P.nl, mae, ncol,
+                           part, predmat, inv, n);
+    else
+        hipLaunchKernelGGL(csr_cv_fold_score_kernel<false>, grid, block, 0, s, rowptr, ccol, cval, yp, fold_start, fold_n, P.K, p, bt, P.nl, mae, ncol,
+                           part, (double *)nullptr, (const int *)nullptr, n);
+    OEM_HIP(hipGetLastError());
+    return launch_cv_fold_finish(s, part, P.waves, P.K, P.npen, P.nl, ncol, triples);
 }
 
 }  // namespace oemgpu
