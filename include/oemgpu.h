@@ -251,6 +251,37 @@ int oemgpu_solve_moments_dev(oemgpu_ctx *ctx, const double *moments_dev, const d
 int oemgpu_fit_dense_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
                          int32_t standardize, int32_t intercept, const oemgpu_opts *o,
                          double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+/* The same three calls on a ROW-major x that is read where it lies: x_dev is n x p with row stride ldr >= p (in elements) of
+ * dtype OEMGPU_F64 or OEMGPU_F32, aligned to its element size only; columns p .. ldr - 1 of a row and everything past element
+ * (n - 1) ldr + p - 1 are never read.  y_dev is a contiguous float64 vector.  They replace the copies a caller with such a matrix
+ * had to make in front of the column-major calls above -- the float64 conversion and the transposed copy: one n x p float64 temporary
+ * for a float64 x, two for a float32 x, each written and read once -- and, as those calls, DataStd's passes + X'Y + XtX (ref src/DataStd.h:203-265,
+ * src/oem_dense.h:318-361,704-707) with ONE pass over X.  float32 elements become float64 as they are loaded; every product and sum
+ * is FP64 (the FP64 MFMA), in one fixed order: two calls return the same bytes, and a float32 x returns what its float64 copy does.
+ *   oemgpu_shift_sums_rm_dev: the sums buffer of oemgpu_shift_sums_dev on the column-major float64 copy, bit for bit.
+ *   oemgpu_moments_rm_dev:    the moment buffer above (both triangles written), about the shift sums_dev defines (NULL: 0); equal
+ *                             to oemgpu_moments_dev's up to the rounding of another summation order.  1 <= p <= OEMGPU_RM_P_MAX.
+ *   oemgpu_fit_dense_rm_dev:  oemgpu_fit_dense_dev with these passes (the second, shifted pass included when the first solve
+ *                             advises it; the same timers).  n > p only: where the p >= n engine would take the call, and for
+ *                             p > OEMGPU_RM_P_MAX, OEMGPU_ERR_UNSUPPORTED -- those shapes take the column-major entry.
+ * OEMGPU_ERR_ARG before any device work: a NULL ctx or pointer, dtype outside {0, 1}, n < 1, p < 1, ldr < p. */
+#define OEMGPU_F64 0
+#define OEMGPU_F32 1
+#define OEMGPU_RM_P_MAX 1024
+int oemgpu_shift_sums_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p,
+                             const double *y_dev, double *sums_dev);
+int oemgpu_moments_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p,
+                          const double *y_dev, const double *sums_dev, double *moments_dev);
+int oemgpu_fit_dense_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                            int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                            double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+/* Host-only plan of the row-major pass (pure arithmetic, runs without a GPU; the calls take their shape from the same function) for
+ * n rows, p columns on a device of num_cu CUs: out[0] tile columns of [X | y | 1], [1] 4 x 4 tile blocks per row chunk, [2] row
+ * chunks, [3] 16-row steps per chunk, [4] workgroups of the pass, [5] doubles of chunk partials, [6] the first row of the last
+ * chunk (< n: no chunk is empty), [7] OEMGPU_RM_P_MAX.  OEMGPU_ERR_ARG for n, p, num_cu < 1 or a NULL out; OEMGPU_ERR_UNSUPPORTED for
+ * p > OEMGPU_RM_P_MAX. */
+int oemgpu_selftest_gram_rm_plan(int64_t n, int32_t p, int32_t num_cu, int64_t *out /* 8 */);
+
 /* oemgpu_fit_dense_weighted with X, y and the weights already on the device. */
 int oemgpu_fit_dense_weighted_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
                                   const double *weights_dev, int32_t standardize, int32_t intercept, const oemgpu_opts *opts,

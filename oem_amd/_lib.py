@@ -14,6 +14,8 @@ PENALTIES = ["elastic.net", "lasso", "ols", "mcp", "scad", "mcp.net", "scad.net"
              "grp.scad.net", "sparse.grp.lasso"]          # R/oem.R:165-173; index = C penalty code
 
 OEMGPU_SEM_DENSE, OEMGPU_SEM_BIG = 0, 1
+OEMGPU_F64, OEMGPU_F32 = 0, 1              # element types of the row-major entries
+RM_P_MAX = 1024                            # OEMGPU_RM_P_MAX: columns the row-major pass takes
 ERR_INTERRUPTED = -6
 NHOSTSTATS = 9
 NTIMERS = 8
@@ -90,6 +92,11 @@ _SIGS = {
                                            C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_fit_dense_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
                                        C.c_int32, C.POINTER(OemgpuOpts)] + _OUT),
+    "oemgpu_shift_sums_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "oemgpu_moments_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "oemgpu_fit_dense_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_int32, C.POINTER(OemgpuOpts)] + _OUT),
+    "oemgpu_selftest_gram_rm_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_fit_xtx_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _dp, C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_last_shift_in_effect": (C.c_int, [C.c_void_p]),
     "oemgpu_last_shift_advised": (C.c_int, [C.c_void_p]),

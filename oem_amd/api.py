@@ -233,6 +233,71 @@ def _device_matrix(x):
     return xt.data_ptr(), n, p, n, xt
 
 
+def _rowmajor_dtype(x):
+    """OEMGPU_F64 / OEMGPU_F32 for a torch tensor the row-major entries can read in place (unit column stride, row stride >= p,
+    float64 or float32), else None."""
+    import torch
+    code = {torch.float64: L.OEMGPU_F64, torch.float32: L.OEMGPU_F32}.get(x.dtype)
+    if code is None or x.ndim != 2 or x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        return None
+    return code
+
+
+def _rowmajor_in_place(x):
+    """The dtype code with which oem() hands a device tensor to oemgpu_fit_dense_rm_dev as it lies, or None: then _device_matrix
+    makes the column-major float64 copy (p >= n, p beyond the row-major pass, a tensor that is already column-major or strided in
+    its columns, other element types)."""
+    n, p = x.shape
+    if n <= p or p > L.RM_P_MAX:
+        return None
+    if x.stride(0) == 1 and x.stride(1) >= n:                          # already column-major (_device_matrix takes it without a copy)
+        return None
+    return _rowmajor_dtype(x)
+
+
+def _rowmajor_args(x, y):
+    import torch
+    if not _is_torch_cuda(x):
+        raise ValueError("x must be a torch tensor on a GPU")
+    code = _rowmajor_dtype(x)
+    if code is None:
+        raise ValueError("x must be float64 or float32 with unit column stride and a row stride of at least p")
+    n, p = x.shape
+    yd = y if _is_torch_cuda(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=x.device)
+    yd = yd.to(torch.float64).contiguous().reshape(-1)
+    if yd.shape[0] != n:
+        raise ValueError("x and y lengths do not match")
+    return code, n, p, yd
+
+
+def rowmajor_shift_sums(x, y):
+    """Test infrastructure: oemgpu_shift_sums_rm_dev on a row-major device tensor x (float64 / float32, read in place) -> the sums
+    buffer as a numpy array (include/oemgpu.h: oemgpu_sums_len)."""
+    import torch
+    code, n, p, yd = _rowmajor_args(x, y)
+    sums = torch.empty(L.sums_len(p), dtype=torch.float64, device=x.device)
+    ctx = context(x.device.index)
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_shift_sums_rm_dev(ctx, x.data_ptr(), code, n, x.stride(0), p, yd.data_ptr(), sums.data_ptr()))
+    L.check(L.lib().oemgpu_synchronize(ctx))
+    return sums.cpu().numpy()
+
+
+def rowmajor_moments(x, y, sums=None):
+    """Test infrastructure: oemgpu_moments_rm_dev on a row-major device tensor x -> the (p + 2) x (p + 2) moment buffer about the shift
+    `sums` defines (a sums buffer as rowmajor_shift_sums returns it; None: about 0), as a numpy array indexed [i, j] = M[i, j]."""
+    import torch
+    code, n, p, yd = _rowmajor_args(x, y)
+    mom = torch.empty(L.moments_len(p), dtype=torch.float64, device=x.device)
+    sd = None if sums is None else torch.as_tensor(np.ascontiguousarray(sums, dtype=np.float64), device=x.device)
+    ctx = context(x.device.index)
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_moments_rm_dev(ctx, x.data_ptr(), code, n, x.stride(0), p, yd.data_ptr(), None if sd is None else sd.data_ptr(),
+                                          mom.data_ptr()))
+    L.check(L.lib().oemgpu_synchronize(ctx))
+    return mom.cpu().numpy().reshape(p + 2, p + 2).T
+
+
 _ctx_cache = {}
 
 
@@ -356,14 +421,20 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
         return _decorate(a, penalty, varnames, True, n, p)
     if _is_torch_cuda(x):
         import torch
-        xp, n_, p_, ld, keep = _device_matrix(x)
+        rm = _rowmajor_in_place(x)
+        if rm is None:
+            xp, n_, p_, ld, keep = _device_matrix(x)
         yd = y if _is_torch_cuda(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=x.device)
         yd = yd.to(torch.float64).contiguous().reshape(-1)
         ctx = context(x.device.index)
         torch.cuda.current_stream(x.device).synchronize()
-        L.check(lib.oemgpu_fit_dense_dev(ctx, xp, n, ld, p, yd.data_ptr(), int(bool(standardize)), int(bool(intercept)),
-                                         C.byref(a.c), *a.outputs(p + 1)))
-        del keep
+        if rm is not None:                                             # read where it lies: no float64 copy, no transposed copy
+            L.check(lib.oemgpu_fit_dense_rm_dev(ctx, x.data_ptr(), rm, n, x.stride(0), p, yd.data_ptr(), int(bool(standardize)),
+                                                int(bool(intercept)), C.byref(a.c), *a.outputs(p + 1)))
+        else:
+            L.check(lib.oemgpu_fit_dense_dev(ctx, xp, n, ld, p, yd.data_ptr(), int(bool(standardize)), int(bool(intercept)),
+                                             C.byref(a.c), *a.outputs(p + 1)))
+            del keep
     else:
         xh = np.asfortranarray(x, dtype=np.float64)
         yh = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))

@@ -1702,6 +1702,115 @@ int oemgpu_fit_dense_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t 
     return oemgpu_solve_moments_dev(c, mom, sums, p, OEMGPU_SEM_DENSE, standardize, intercept, o, beta, lambda_out, niter, loss, d);
 }
 
+// ---------------------------------------------------------------------------------------------- row-major x (gram_rm.hip)
+static_assert(GRAM_RM_P_MAX == OEMGPU_RM_P_MAX, "the header's limit is the kernel's");
+
+static int rm_check(const char *who, const oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const void *y_dev)
+{
+    if (!c || !x_dev || !y_dev) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    if (dtype != OEMGPU_F64 && dtype != OEMGPU_F32) { set_error("%s: dtype %d is neither OEMGPU_F64 nor OEMGPU_F32", who, dtype); return OEMGPU_ERR_ARG; }
+    if (n < 1 || p < 1 || ldr < p) { set_error("%s: bad n / p / ldr (n >= 1, p >= 1, ldr >= p)", who); return OEMGPU_ERR_ARG; }
+    return 0;
+}
+static int rm_check_p(const char *who, int32_t p)
+{
+    if (p <= GRAM_RM_P_MAX) return 0;
+    set_error("%s: the row-major pass takes p <= %d; larger p takes the column-major entry (oemgpu_fit_dense_dev / oemgpu_moments_dev)", who, GRAM_RM_P_MAX);
+    return OEMGPU_ERR_UNSUPPORTED;
+}
+
+// moments of a device-resident row-major x into `moments` (overwrite); the counterpart of shard_moments
+static int rm_moments(oemgpu_ctx *c, const GramRmPlan &pl, const void *x, int dtype, int64_t n, int64_t ldr, const double *y, const double *sums,
+                      double *tpart, double *moments)
+{
+    {
+        Timer t(c, OEMGPU_T_GRAMK);
+        int rc = launch_gram_rm(c->stream, pl, x, dtype, n, ldr, y, sums, tpart);
+        if (rc) return rc;
+    }
+    return launch_gram_rm_reduce(c->stream, pl, tpart, moments);
+}
+
+int oemgpu_selftest_gram_rm_plan(int64_t n, int32_t p, int32_t num_cu, int64_t *out)
+{
+    if (n < 1 || p < 1 || num_cu < 1 || !out) { set_error("selftest_gram_rm_plan: bad argument"); return OEMGPU_ERR_ARG; }
+    if (int rc = rm_check_p("selftest_gram_rm_plan", p)) return rc;
+    const GramRmPlan pl = gram_rm_plan(n, p, num_cu);
+    out[0] = pl.ntc; out[1] = pl.nblk; out[2] = pl.nchunk; out[3] = pl.steps; out[4] = (int64_t)pl.nchunk * pl.nblk;
+    out[5] = (int64_t)pl.tpart_doubles; out[6] = (int64_t)(pl.nchunk - 1) * pl.steps * 16; out[7] = GRAM_RM_P_MAX;
+    return 0;
+}
+
+int oemgpu_shift_sums_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                             double *sums_dev)
+{
+    if (int rc = rm_check("shift_sums_rm", c, x_dev, dtype, n, ldr, p, y_dev)) return rc;
+    if (!sums_dev) { set_error("shift_sums_rm: NULL argument"); return OEMGPU_ERR_ARG; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    Timer t(c, OEMGPU_T_SHIFT);
+    return launch_shift_sums_rm(c->stream, x_dev, dtype, n, ldr, p, y_dev, sums_dev);
+}
+
+int oemgpu_moments_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                          const double *sums_dev, double *moments_dev)
+{
+    if (int rc = rm_check("moments_rm", c, x_dev, dtype, n, ldr, p, y_dev)) return rc;
+    if (!moments_dev) { set_error("moments_rm: NULL argument"); return OEMGPU_ERR_ARG; }
+    if (int rc = rm_check_p("moments_rm", p)) return rc;
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const GramRmPlan pl = gram_rm_plan(n, p, c->num_cu);
+    if (ctx_reserve(c, pl.tpart_doubles * 8)) return OEMGPU_ERR_HIP;
+    Timer t(c, OEMGPU_T_MOMENTS);
+    return rm_moments(c, pl, x_dev, dtype, n, ldr, y_dev, sums_dev, (double *)c->ws, moments_dev);
+}
+
+// oemgpu_fit_dense_dev with the row-major passes in place of shard_moments / launch_shift_sums
+int oemgpu_fit_dense_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                            int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                            double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+{
+    int rc = rm_check("fit_dense_rm", c, x_dev, dtype, n, ldr, p, y_dev);
+    if (rc) return rc;
+    if (!beta || !lambda_out || !niter || !loss || !d) { set_error("fit_dense_rm: NULL argument"); return OEMGPU_ERR_ARG; }
+    if ((rc = check_opts(o, p, p))) return rc;
+    if (wide_pays(n, p, o)) {
+        set_error("fit_dense_rm: %lld x %d is a shape of the p >= n engines, which read a column-major x: it takes the column-major entry "
+                  "(oemgpu_fit_dense_dev)", (long long)n, p);
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    if ((rc = rm_check_p("fit_dense_rm", p))) return rc;
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const GramRmPlan pl = gram_rm_plan(n, p, c->num_cu);
+    Bump B;
+    const size_t a_sums = B.take((size_t)oemgpu_sums_len(p) * 8), a_mom = B.take((size_t)oemgpu_moments_len(p) * 8);
+    const size_t frame = B.off;
+    const size_t a_t = B.take(pl.tpart_doubles * 8);
+    size_t need = B.off;
+    const size_t need2 = frame + ((size_t)p * p + p + stats_len(p)) * 8 + 1024 + paths_ws_bytes(p, p, o) + 4096;
+    if (need2 > need) need = need2;
+    if (ctx_reserve(c, need)) return OEMGPU_ERR_HIP;
+    double *sums = (double *)(c->ws + a_sums), *mom = (double *)(c->ws + a_mom), *tpart = (double *)(c->ws + a_t);
+    // moments about 0 first, the sample pass and the shifted pass only when finalize advises them (as oemgpu_fit_dense_dev)
+    {
+        Timer t(c, OEMGPU_T_MOMENTS);
+        rc = rm_moments(c, pl, x_dev, dtype, n, ldr, y_dev, nullptr, tpart, mom);
+        if (rc) return rc;
+    }
+    rc = oemgpu_solve_moments_dev(c, mom, nullptr, p, OEMGPU_SEM_DENSE, standardize, intercept, o, beta, lambda_out, niter, loss, d);
+    if (rc || !c->shift_advised) return rc;
+    {
+        Timer t(c, OEMGPU_T_SHIFT);
+        rc = launch_shift_sums_rm(c->stream, x_dev, dtype, n, ldr, p, y_dev, sums);
+        if (rc) return rc;
+    }
+    {
+        Timer t(c, OEMGPU_T_MOMENTS);
+        rc = rm_moments(c, pl, x_dev, dtype, n, ldr, y_dev, sums, tpart, mom);
+        if (rc) return rc;
+    }
+    return oemgpu_solve_moments_dev(c, mom, sums, p, OEMGPU_SEM_DENSE, standardize, intercept, o, beta, lambda_out, niter, loss, d);
+}
+
 // oemDense with observation weights (weighted.hip has the algebra and the reference lines).  n > p.
 static int fit_dense_weighted_impl(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev, const double *w_dev,
                                    const double *w_host, int32_t standardize, int32_t intercept, const oemgpu_opts *o,

@@ -50,6 +50,27 @@ int launch_gram(hipStream_t s, const GramPlan &pl, const double *x, int64_t n, i
                 const double *sums /* p+2 or null */, double *tpart, double *vpart);
 int launch_moments_reduce(hipStream_t s, const GramPlan &pl, const double *tpart, const double *vpart, double *moments);
 
+// ------------------------------------------------------------------ Gram / moments of a row-major X (gram_rm.hip)
+// 4 x 4 tile blocks of the lower triangle of Z = [X | y | 1] over row chunks of `steps` 16-row steps; a block's partial is 16 tile slots
+constexpr int GRAM_RM_P_MAX = 1024;        // columns of X the row-major pass takes (the engines behind it: p <= 1024 never goes the p >= n way)
+constexpr int GRAM_RM_MIN_ROWS = 1024;     // a row chunk is no shorter (but for the matrix's own end)
+constexpr int64_t GRAM_RM_PART_BYTES = 512 << 20;   // the chunk partials in all, unless ~4 workgroups per CU need more
+constexpr int64_t GRAM_RM_CHUNK_BYTES = 16 << 20;   // ... and no longer than this many bytes of float64 rows, unless that leaves fewer than ~4 workgroups per CU
+struct GramRmPlan {
+    int p;          // columns of X
+    int ntc;        // tile columns = ceil((p + 2) / 16)
+    int nb;         // block rows = ceil(ntc / 4)
+    int nblk;       // blocks per row chunk = nb (nb + 1) / 2
+    int nchunk;     // row chunks
+    int64_t steps;  // 16-row steps per chunk
+    size_t tpart_doubles;   // nchunk * nblk * 16 * 256
+};
+GramRmPlan gram_rm_plan(int64_t n, int p, int num_cu);
+int launch_shift_sums_rm(hipStream_t s, const void *x, int dtype, int64_t n, int64_t ldr, int p, const double *y, double *sums);
+int launch_gram_rm(hipStream_t s, const GramRmPlan &pl, const void *x, int dtype, int64_t n, int64_t ldr, const double *y,
+                   const double *sums /* or null */, double *tpart);
+int launch_gram_rm_reduce(hipStream_t s, const GramRmPlan &pl, const double *tpart, double *moments);
+
 // stats layout written by finalize (doubles): [0] meanY [1] scaleY [2] yy (sum of squared standardised y)
 // [3] nobs [4..4+p) meanX [4+p..4+2p) scaleX (dense) or colsq_inv (big) [4+2p] 1 if the moments were read as shifted [4+2p+1] 0
 __host__ __device__ static inline int stats_len(int p) { return 4 + 2 * p + 2; }

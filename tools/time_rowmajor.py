@@ -1,0 +1,139 @@
+#!/usr/bin/env python3
+"""Times oem() on the same data handed over as a row-major float64 tensor, a row-major float32 tensor and a column-major float64
+tensor, each shape x layout in a child process of its own.
+
+    python tools/time_rowmajor.py [--out profiles/rowmajor_time.json] [--package-root DIR --label "parent commit"] [--shapes 1000000x100,...]
+
+The timing scheme is config 1's in bench.py: the lambda grid from a default fit, untimed solves for 0.2 s (the clocks settle), W
+warm-up steps, then K timed steps back to back with one synchronisation behind them; ms per call = wall time / K.  The timed step
+here is the Python call oem(x, y, lambda_=grid, tol=1e-10, ...) itself, because what is compared is what oem() does with the tensor
+it is given: reads it in place, or converts and transposes it first.  Besides the time a child reports the peak of torch's allocated
+bytes during one call (the copies show there; the library's own workspace does not) and the moment timer of the last call.
+
+--package-root: the checkout whose oem_amd is timed (default: this one).  The same script on the parent commit's tree gives the
+"before" table: there every row-major tensor goes through the float64 conversion and the transposed copy."""
+import argparse
+import json
+import subprocess
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+SHAPES = [(1_000_000, 100), (1_000_000, 512), (12_500_000, 256)]
+LAYOUTS = ["rm64", "rm32", "cm64"]
+FAULTS = (134, 139, 124, 137)
+
+
+def make_data(torch, n, p, layout):
+    """float32-representable data, the same in every layout, generated on the device in row chunks (no n x p temporary besides x)"""
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev); g.manual_seed(20240501)
+    b = torch.zeros(p, dtype=torch.float64, device=dev)
+    b[:25] = torch.rand(25, generator=g, device=dev, dtype=torch.float64) - 0.5
+    if layout == "cm64":
+        store = torch.empty((p, n), dtype=torch.float64, device=dev)       # (p, n) row-major == (n, p) column-major
+        x = store.t()
+    else:
+        x = torch.empty((n, p), dtype=torch.float64 if layout == "rm64" else torch.float32, device=dev)
+    y = torch.empty(n, dtype=torch.float64, device=dev)
+    step = 500_000
+    for r0 in range(0, n, step):
+        r1 = min(n, r0 + step)
+        c = torch.randn((r1 - r0, p), generator=g, device=dev, dtype=torch.float32)
+        x[r0:r1] = c.to(x.dtype)
+        y[r0:r1] = c.double() @ b + torch.randn(r1 - r0, generator=g, device=dev, dtype=torch.float64)
+    torch.cuda.synchronize()
+    return x, y
+
+
+def child(a):
+    sys.path.insert(0, str(Path(a.package_root).resolve()))
+    import torch
+    import oem_amd
+    from oem_amd import api
+    from oem_amd import _lib as L
+    assert Path(oem_amd.__file__).resolve().parent.parent == Path(a.package_root).resolve()
+    n, p = a.n, a.p
+    x, y = make_data(torch, n, p, a.layout)
+    kw = dict(penalty="elastic.net", alpha=1.0, intercept=True, standardize=False)
+    lambdas = oem_amd.oem(x, y, tol=1e-7, **kw)["lambda"][0]
+
+    def solve():
+        return oem_amd.oem(x, y, lambda_=lambdas, tol=1e-10, **kw)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    solve(); torch.cuda.synchronize()
+    est = time.perf_counter() - t0
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.max_memory_allocated()
+    solve(); torch.cuda.synchronize()
+    extra = torch.cuda.max_memory_allocated() - base
+    tend = time.perf_counter() + 0.2
+    prewarm = 0
+    while time.perf_counter() < tend or prewarm < 2:
+        solve(); prewarm += 1
+    steps = max(10, min(200, int(2.0 / max(est, 1e-4))))
+    warm = min(10, steps)
+    for _ in range(warm):
+        solve()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fit = solve()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    ctx = api.context()
+    lib = L.lib()
+    lib.oemgpu_set_timing(ctx, 1)
+    solve()
+    import ctypes as C
+    tm = (C.c_double * 16)()
+    lib.oemgpu_last_timings(ctx, tm)
+    lib.oemgpu_set_timing(ctx, 0)
+    print(json.dumps({"n": n, "p": p, "layout": a.layout, "ms_per_call": 1e3 * dt / steps, "steps": steps, "warmup": warm,
+                      "prewarm_solves": prewarm, "peak_extra_bytes": int(extra), "x_bytes": int(x.numel() * x.element_size()),
+                      "moments_ms": tm[L.T_MOMENTS], "gram_kernel_ms": tm[L.T_GRAMK], "shift_ms": tm[L.T_SHIFT],
+                      "beta_abs_sum": float(abs(fit["beta"][0]).sum())}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--child", action="store_true")
+    ap.add_argument("--n", type=int); ap.add_argument("--p", type=int); ap.add_argument("--layout", choices=LAYOUTS)
+    ap.add_argument("--package-root", default=str(ROOT))
+    ap.add_argument("--shapes", default=",".join(f"{n}x{p}" for n, p in SHAPES))
+    ap.add_argument("--out", default=None, help="write the table as JSON here")
+    ap.add_argument("--label", default="this commit", help="what the table is of (goes into the JSON)")
+    ap.add_argument("--timeout", type=int, default=240, help="seconds per child")
+    a = ap.parse_args()
+    if a.child:
+        return child(a)
+    rows = []
+    for shape in a.shapes.split(","):
+        n, p = (int(v) for v in shape.split("x"))
+        for layout in LAYOUTS:
+            cmd = [sys.executable, str(Path(__file__).resolve()), "--child", "--n", str(n), "--p", str(p), "--layout", layout,
+                   "--package-root", a.package_root]
+            try:
+                r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
+            except subprocess.TimeoutExpired:
+                print(f"{n} x {p} {layout}: no answer in {a.timeout} s; nothing more is started", flush=True)
+                return 1
+            if r.returncode != 0:
+                print(f"{n} x {p} {layout}: exit {r.returncode}\n{r.stderr[-2000:]}", flush=True)
+                if r.returncode < 0 or r.returncode in FAULTS:
+                    return 1                                   # a fault or a hang: nothing more is started on that device
+                continue
+            row = json.loads(r.stdout.strip().splitlines()[-1])
+            rows.append(row)
+            print(f"{n:>9} x {p:<4} {layout}: {row['ms_per_call']:9.3f} ms/call  moments {row['moments_ms']:8.3f} ms  "
+                  f"peak extra {row['peak_extra_bytes'] / 1e9:7.3f} GB of x {row['x_bytes'] / 1e9:6.3f} GB  (K = {row['steps']})", flush=True)
+    if a.out:
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(json.dumps({"tree": a.label, "rows": rows}, indent=1) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
