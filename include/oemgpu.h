@@ -564,6 +564,34 @@ int oemgpu_selftest_cv_auc_plan(int64_t n, int32_t nfolds, int32_t ncol, int32_t
  * inner solve is one persistent workgroup (q <= 1024) and 0 for launch per iteration, out[5] 1 if the row pass stages its sub-blocks
  * in LDS, out[6] device workspace bytes of a call, out[7] the bound out[6] stays within. */
 int oemgpu_selftest_logistic_plan(int64_t n, int32_t p, int32_t intercept, int32_t hessian_full, int32_t num_cu, int64_t *out /* 8 */);
+/* The binomial entries on a ROW-major x read where it lies (logistic_rm.hip): x_dev is n x p with row stride ldr >= p (elements),
+ * dtype OEMGPU_F64 or OEMGPU_F32, aligned to its element size only; columns p .. ldr - 1 of a row, rows >= n and -- in a fold fit and
+ * in the scoring -- the rows that are not asked for are never loaded.  float32 elements are widened in the register they were loaded
+ * into and all arithmetic is FP64.  Every sum is taken in the order of the column-major kernels with the same chunks and Z blocks, so
+ * each entry returns the bits of its column-major counterpart on the same values laid out column-major in float64:
+ *   oemgpu_fit_logistic_dense_rm_dev:      oemgpu_fit_logistic_dense_dev, i.e. `.Call("oem_fit_logistic_dense", ...)` (ref
+ *                                          src/oem_logistic_dense.cpp:30-313, src/oem_logistic_dense.h:397-1094);
+ *   oemgpu_fit_logistic_dense_fold_rm_dev: oemgpu_fit_logistic_dense_fold_dev, the same on x[keep, ], y[keep] (ref R/cv_oem.R:129-175);
+ *   oemgpu_logistic_cv_score_rm_dev:       oemgpu_logistic_cv_score_dev, cv.oemfit_binomial's error terms (ref R/cv_oem.R:224-346).
+ * The other arguments, the outputs and the checks are the counterpart's, with the same error codes, refused before a device is looked
+ * for; then OEMGPU_ERR_ARG for a dtype other than the two, for ldr < p and for an x_dev that is not aligned to its element. */
+int oemgpu_fit_logistic_dense_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                                     int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol,
+                                     const oemgpu_opts *opts, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+int oemgpu_fit_logistic_dense_fold_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                                          const int32_t *foldid_dev, int32_t nfolds, int32_t leave_out, int32_t standardize, int32_t intercept,
+                                          int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *opts,
+                                          double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+int oemgpu_logistic_cv_score_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                                    double y_hi, const int32_t *foldid_dev, int32_t nfolds, const double *coef, int32_t ncol, double *sums,
+                                    int64_t *counts, double *predmat_dev);
+/* Host-only plan of the row-major binomial fit (pure arithmetic, runs without a GPU).  The row pass stages a 64-row sub-block in LDS
+ * in column bands: band b = columns [b out[1], min(p, (b + 1) out[1])).  out[0] bands, out[1] columns per band (a multiple of 4 unless
+ * there is one band, which is then p wide and read once per step; several bands are read twice), out[2] columns of the last band,
+ * out[3] LDS bytes of a workgroup (at most the 160 KiB of a CU), out[4 .. 7] = out[0 .. 3] of oemgpu_selftest_logistic_plan: the chunks
+ * and Z blocks are the column-major call's.  OEMGPU_ERR_ARG on n, p, num_cu < 1, a dtype other than the two or a NULL out;
+ * OEMGPU_ERR_UNSUPPORTED for p > 8191. */
+int oemgpu_selftest_logistic_rm_plan(int64_t n, int32_t p, int32_t dtype, int32_t intercept, int32_t num_cu, int64_t *out /* 8 */);
 /* `.Call("oem_fit_logistic_sparse", ...)` (ref src/oem_logistic_sparse.cpp:30-313, src/oem_logistic_sparse.h): the binomial fit of a
  * compressed-sparse-column x (a dgCMatrix: colptr[p + 1] with colptr[0] = 0, non-decreasing; rowidx[nnz] in [0, n), strictly increasing
  * inside a column; values[nnz]; explicit zeros allowed).  opts, irls_maxit, irls_tol and the outputs as oemgpu_fit_logistic_dense.  The

@@ -61,6 +61,14 @@ _SIGS = {
                                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_logistic_cv_score_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_int32,
                                                 _dp, C.c_int32, _dp, C.POINTER(C.c_int64), C.c_void_p]),
+    "oemgpu_fit_logistic_dense_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_int32, C.c_double, C.POINTER(OemgpuOpts)] + _OUT),
+    "oemgpu_fit_logistic_dense_fold_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                                         C.POINTER(OemgpuOpts)] + _OUT),
+    "oemgpu_logistic_cv_score_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_double, C.c_void_p,
+                                                   C.c_int32, _dp, C.c_int32, _dp, C.POINTER(C.c_int64), C.c_void_p]),
+    "oemgpu_selftest_logistic_rm_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_selftest_cv_score_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_logistic_cv_auc_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_int32,
                                               C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -255,6 +255,15 @@ def _rowmajor_in_place(x):
     return _rowmajor_dtype(x)
 
 
+def _logistic_rowmajor_in_place(x):
+    """The dtype code with which the binomial entries (oem_fit_logistic_dense, its fold form, logistic_cv_score, cv_oem(family=
+    "binomial")) hand a device tensor to their _rm_dev entry as it lies, or None: then it goes the column-major way (a tensor that is
+    already column-major, one strided in its columns, other element types)."""
+    if x.ndim == 2 and x.stride(0) == 1 and x.stride(1) >= x.shape[0]:   # already column-major (_device_matrix takes it without a copy)
+        return None
+    return _rowmajor_dtype(x)
+
+
 def _rowmajor_args(x, y):
     import torch
     if not _is_torch_cuda(x):
@@ -462,7 +471,8 @@ def oem_fit_logistic_dense(x, y, penalty=None, weights=(), lambda_=(), nlambda=1
                            _fold=None):
     """The dense binomial fit (ref src/oem_logistic_dense.cpp:30-313, src/oem_logistic_dense.h:397-1094) with oem()'s checks for
     family = "binomial" (R/oem.R:162-507): y takes at most two values (passed on as they are: the reference fits the raw 0/1 vector),
-    groups gain the intercept's group 0 in front (R/oem.R:296-338).  x: numpy (host entry) or a torch tensor on a GPU (_dev entry).
+    groups gain the intercept's group 0 in front (R/oem.R:296-338).  x: numpy (host entry) or a torch tensor on a GPU (_dev entry; a
+    row-major float64 / float32 tensor is read where it lies by the _rm_dev entry, with the column-major fit's bits: DESIGN.md 3.9a).
     hessian_type: "upper.bound" (X'WX, d and A from the first IRLS step of a penalty only) or "full" (every step).  `oem(family=
     "binomial")` still raises NotImplementedError; this is the entry below it, as oem_fit_dense_weighted is for weights.
     _fold (cv_oem's fold fits; x on a GPU): (foldid as an int32 device tensor, nfolds, leave_out, y as a float64 device tensor) -- the
@@ -501,11 +511,22 @@ def oem_fit_logistic_dense(x, y, penalty=None, weights=(), lambda_=(), nlambda=1
     lib = L.lib()
     if _is_torch_cuda(x):
         import torch
-        xp, n_, p_, ld, keep = _device_matrix(x)
+        rm = _logistic_rowmajor_in_place(x)
+        keep = None
+        if rm is None:
+            xp, n_, p_, ld, keep = _device_matrix(x)
         yd = torch.as_tensor(yh, device=x.device) if _fold is None else _fold[3]
         ctx = context(x.device.index)
         torch.cuda.current_stream(x.device).synchronize()
-        if _fold is None:
+        scal = (int(bool(standardize)), int(bool(intercept)), hf, int(irls_maxit), float(irls_tol), C.byref(a.c))
+        if rm is not None and _fold is None:                           # row-major float64 / float32: read where it lies
+            L.check(lib.oemgpu_fit_logistic_dense_rm_dev(ctx, x.data_ptr(), rm, n, x.stride(0), p, yd.data_ptr(), *scal, *a.outputs(p + 1)))
+        elif rm is not None:
+            fd, nfolds, leave_out = _fold[:3]
+            L.check(lib.oemgpu_fit_logistic_dense_fold_rm_dev(ctx, x.data_ptr(), rm, n, x.stride(0), p, yd.data_ptr(), fd.data_ptr(), int(nfolds),
+                                                              int(leave_out), *scal, *a.outputs(p + 1)))
+            n = int(n - (fd == int(leave_out)).sum().item())
+        elif _fold is None:
             L.check(lib.oemgpu_fit_logistic_dense_dev(ctx, xp, n, ld, p, yd.data_ptr(), int(bool(standardize)), int(bool(intercept)), hf,
                                                       int(irls_maxit), float(irls_tol), C.byref(a.c), *a.outputs(p + 1)))
         else:
@@ -1056,7 +1077,8 @@ def cv_sparse_plan(n, p, nnz, nfolds, npen, nl, num_cu):
 # ------------------------------------------------------------------------------------------ cv.oem()
 def logistic_cv_score(x, y, foldid, nfolds, coef, y_hi=None, predmat=False):
     """oemgpu_logistic_cv_score_dev: the error terms of cv.oemfit_binomial (R/cv_oem.R:315-327) over the held-out rows of a resident x.
-    x: a column-major float64 matrix on a GPU, or a SparseX (oemgpu_logistic_cv_score_sparse_res: for finite tables the bits of the
+    x: a column-major float64 matrix on a GPU, a row-major float64 / float32 one (oemgpu_logistic_cv_score_rm_dev reads it where it
+    lies and returns the bits of the column-major entry on the same values), or a SparseX (oemgpu_logistic_cv_score_sparse_res: for finite tables the bits of the
     dense entry on the same matrix written out); y (float64) and foldid (int32, 1 .. nfolds): device tensors; coef: nfolds x ncol x
     (p + 1) on the host, the columns that score the rows of each fold.  Returns (sums: nfolds x ncol x 8 = [sum, sum of squares] of
     deviance, class, mse, mae; counts: the fold sizes; predmat: n x ncol on the host, or None).  predmat="device": the third item is
@@ -1066,7 +1088,11 @@ def logistic_cv_score(x, y, foldid, nfolds, coef, y_hi=None, predmat=False):
     if sparse:
         (n, p), keepalive = x.shape, None
     else:
-        xp, n, p, ld, keepalive = _device_matrix(x)
+        rm = _logistic_rowmajor_in_place(x)
+        if rm is None:
+            xp, n, p, ld, keepalive = _device_matrix(x)
+        else:                                                          # row-major float64 / float32: scored where it lies
+            (n, p), keepalive = x.shape, None
     coef = np.ascontiguousarray(coef, dtype=np.float64)
     if coef.ndim != 3 or coef.shape[0] != int(nfolds) or coef.shape[2] != p + 1:
         raise ValueError("coef must be nfolds x ncol x (p + 1)")
@@ -1081,6 +1107,10 @@ def logistic_cv_score(x, y, foldid, nfolds, coef, y_hi=None, predmat=False):
         L.check(L.lib().oemgpu_logistic_cv_score_sparse_res(context(x.device.index), x.handle, y.data_ptr(), float(y_hi), foldid.data_ptr(),
                                                             int(nfolds), _dptr(coef), ncol, _dptr(sums),
                                                             counts.ctypes.data_as(C.POINTER(C.c_int64)), None if pm is None else pm.data_ptr()))
+    elif rm is not None:
+        L.check(L.lib().oemgpu_logistic_cv_score_rm_dev(context(x.device.index), x.data_ptr(), rm, n, x.stride(0), p, y.data_ptr(), float(y_hi),
+                                                        foldid.data_ptr(), int(nfolds), _dptr(coef), ncol, _dptr(sums),
+                                                        counts.ctypes.data_as(C.POINTER(C.c_int64)), None if pm is None else pm.data_ptr()))
     else:
         L.check(L.lib().oemgpu_logistic_cv_score_dev(context(x.device.index), xp, n, ld, p, y.data_ptr(), float(y_hi), foldid.data_ptr(), int(nfolds),
                                                      _dptr(coef), ncol, _dptr(sums), counts.ctypes.data_as(C.POINTER(C.c_int64)),
@@ -1153,7 +1183,8 @@ _BINOMIAL_NAMES = {"mse": "Mean-Squared Error", "mae": "Mean Absolute Error", "d
 def _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, foldid, grouped, keep, rng, kw):
     """cv.oem() for family = "binomial": R/cv_oem.R:56-221 with cv.oemfit_binomial (:224-346).  x is on the device once; the full fit,
     the K fold fits (masked row passes over that x, one fold after another) and the scoring all read it there.  A dense x (numpy or
-    a device tensor) stays a column-major device matrix; a scipy.sparse x becomes one SparseX, which is closed on the way out."""
+    a device tensor) stays a column-major device matrix -- except a row-major float64 / float32 device tensor, which stays as it is
+    and is read in place (_logistic_rowmajor_in_place); a scipy.sparse x becomes one SparseX, which is closed on the way out."""
     for drop in ("accelerate", "ncores"):            # oem() arguments the binomial fit has no use for (no Nesterov step, no OpenMP)
         kw.pop(drop, None)
     if getattr(x, "ndim", 0) != 2:
@@ -1176,7 +1207,9 @@ def _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, fold
                 return oem_fit_logistic_sparse(sx, yh, penalty=penalty, lambda_=lam_arg, _fold=(sx, fd, max(int(nfolds), 3), leave_out, yd), **kw)
             return _cv_oem_binomial_on(fit, lambda fd, nfolds, coef, **k: logistic_cv_score(sx, yd, fd, nfolds, coef, **k), sx.device,
                                        n, p, yh, penalty, type_measure, nfolds, foldid, grouped, keep, rng, yd)
-    if _is_torch_cuda(x):
+    if _is_torch_cuda(x) and _logistic_rowmajor_in_place(x) is not None:
+        xd = x                                                         # row-major float64 / float32: every pass reads it where it lies
+    elif _is_torch_cuda(x):
         xd = x if x.dtype == torch.float64 else x.to(torch.float64)
         if not (xd.stride(0) == 1 and xd.stride(1) >= n):
             xd = xd.t().contiguous().t()                               # column-major, once

@@ -50,7 +50,28 @@ int logit_fold_scan(oemgpu_ctx *c, const char *who, const int32_t *foldid, int64
 // the scoring pass of cv.oem over a resident x (logistic_cv.hip): dense (x, ld) when sx is null, else the compressed-row copy of sx
 int logistic_cv_score_dev(oemgpu_ctx *c, const double *x, const oemgpu_sparse_x *sx, int64_t n, int64_t ld, int32_t p, const double *y, double y_hi,
                           const int32_t *foldid, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *pred);
-extern const int LOGIT_WG_MAX_Q;                         // q up to which the inner solve is one persistent workgroup
+// A row-major x of float64 / float32 elements read where it lies (logistic_rm.hip).  The band plan of its row pass, pure host arithmetic:
+// band b = columns [b bw, min(p, (b + 1) bw)); bw is a multiple of 4 unless there is one band (bw = p)
+struct LogitRmPlan {
+    int bw;            // columns per band
+    int nband;         // bands
+    size_t lds;        // dynamic LDS bytes of the row pass: the p accumulators and a 64-row tile of one band
+    size_t lds_total;  // with the kernel's static arrays
+};
+LogitRmPlan logit_rm_plan(int p);
+// logit_rows_kernel's launch (logistic.hip) for the row-major x: chunks c0 .. c0 + nc of ch rows, the Z block from row0 (or z null)
+int launch_logit_rows_rm(hipStream_t s, const LogitRmPlan &R, const void *x, int dtype, int64_t n, int64_t ldr, int p, const double *y,
+                         const double *beta, const double *sc, int intercept, int mode, int64_t irls_i, int64_t ch, int64_t c0, int64_t nc,
+                         int64_t row0, double *z, int64_t ldz, double *part, const int32_t *foldid, int32_t leave_out);
+// logit_scale_kernel for the row-major x; sp: 256 p doubles of workspace; fill_row: a row that is in the fit
+int launch_logit_scale_rm(hipStream_t s, const void *x, int dtype, int64_t n, int64_t ldr, int p, double *sp, double *sc, const int32_t *foldid,
+                          int32_t leave_out, int64_t n_eff, int64_t fill_row);
+// what the row-major entries add to the checks of their column-major counterparts (no device needed)
+int logistic_rm_check(const char *who, const void *x, int32_t dtype, int64_t ldr, int32_t p);
+// the scoring pass over a row-major x (logistic_cv.hip)
+int logistic_cv_score_rm_dev(oemgpu_ctx *c, const void *x, int dtype, int64_t n, int64_t ldr, int32_t p, const double *y, double y_hi,
+                             const int32_t *foldid, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *pred);
+extern const int LOGIT_WG_MAX_Q;                        // q up to which the inner solve is one persistent workgroup
 extern const int LOGIT_P_LIMIT;                          // the largest p served
 
 }  // namespace oemgpu

@@ -21,6 +21,9 @@
 // row's stored entries in column order, one fma each.  The dense reader adds fma(0, beta, eta) = eta for an absent entry, so on
 // finite tables the sparse entry returns the bits of the dense entry on the same matrix written out; plan, tiles, tile skip,
 // butterfly and sum order are shared.
+// CvRmRows<T> (oemgpu_logistic_cv_score_rm_dev): a row-major x of float64 / float32 elements read where it lies -- lane = row, every lane
+// walks its own row's consecutive elements with the dense reader's fma in the dense reader's order: the bits of the dense entry on the
+// column-major float64 copy.
 #include "logistic.hpp"
 
 #include <algorithm>
@@ -63,8 +66,16 @@ __device__ __forceinline__ double wave_sum(double v)
 
 struct CvDenseRows {                 // x column-major, leading dimension ld
     static constexpr bool sparse = false;
+    static constexpr bool rowmajor = false;
     const double *x;
     int64_t ld;
+};
+template <typename T>
+struct CvRmRows {                    // x row-major, row stride ldr, float64 / float32 elements widened in the register
+    static constexpr bool sparse = false;
+    static constexpr bool rowmajor = true;
+    const T *x;
+    int64_t ldr;
 };
 struct CvCsrRows {                   // row r: entries rowptr[r] .. rowptr[r + 1] of (ccol, cval), in column order
     static constexpr bool sparse = true;
@@ -110,6 +121,15 @@ __global__ __launch_bounds__(256) void logit_cv_score_kernel(const ROWS X, int64
                 for (int64_t e = k0; e < k1; ++e) {
                     const double v = X.cval[e];
                     const int j = X.ccol[e];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) eta[k] = fma(v, tc[k][1 + j], eta[k]);
+                }
+            } else if constexpr (ROWS::rowmajor) {
+                // lane = row as before: every lane walks its own row's consecutive elements (a cache line serves the next 8 or 16
+                // columns of the lane); a row outside the fold is not loaded.  The same fma in the same order as the dense reader
+                const auto *__restrict__ xr = X.x + (size_t)(in ? row : 0) * X.ldr;
+                for (int j = 0; j < p; ++j) {
+                    const double v = in ? (double)xr[j] : 0.0;
 #pragma unroll
                     for (int k = 0; k < 8; ++k) eta[k] = fma(v, tc[k][1 + j], eta[k]);
                 }
@@ -218,6 +238,13 @@ int logistic_cv_score_dev(oemgpu_ctx *c, const double *x, const oemgpu_sparse_x 
     return cv_score_run(c, CvDenseRows{x, ld}, n, p, y, y_hi, foldid, nfolds, coef, ncol, sums, counts, pred);
 }
 
+int logistic_cv_score_rm_dev(oemgpu_ctx *c, const void *x, int dtype, int64_t n, int64_t ldr, int32_t p, const double *y, double y_hi,
+                             const int32_t *foldid, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *pred)
+{
+    if (dtype == OEMGPU_F32) return cv_score_run(c, CvRmRows<float>{(const float *)x, ldr}, n, p, y, y_hi, foldid, nfolds, coef, ncol, sums, counts, pred);
+    return cv_score_run(c, CvRmRows<double>{(const double *)x, ldr}, n, p, y, y_hi, foldid, nfolds, coef, ncol, sums, counts, pred);
+}
+
 }  // namespace oemgpu
 
 using namespace oemgpu;
@@ -235,6 +262,19 @@ int oemgpu_logistic_cv_score_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, 
     if (p > LOGIT_P_LIMIT) { set_error("logistic_cv_score: p > %d is not supported", LOGIT_P_LIMIT); return OEMGPU_ERR_UNSUPPORTED; }
     if (set_device(c)) return OEMGPU_ERR_HIP;
     return logistic_cv_score_dev(c, x_dev, nullptr, n, ld, p, y_dev, y_hi, foldid_dev, nfolds, coef, ncol, sums, counts, predmat_dev);
+}
+
+int oemgpu_logistic_cv_score_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                                    double y_hi, const int32_t *foldid_dev, int32_t nfolds, const double *coef, int32_t ncol, double *sums,
+                                    int64_t *counts, double *predmat_dev)
+{
+    if (!c || !x_dev || !y_dev || !foldid_dev || !coef || !sums || !counts) { set_error("logistic_cv_score_rm: NULL argument"); return OEMGPU_ERR_ARG; }
+    if (int rc = logistic_rm_check("logistic_cv_score_rm", x_dev, dtype, ldr, p)) return rc;
+    if (n < 1 || p < 1 || ncol < 1) { set_error("logistic_cv_score_rm: bad n, p or ncol"); return OEMGPU_ERR_ARG; }
+    if (nfolds < 3) { set_error("nfolds must be bigger than 3; nfolds=10 recommended"); return OEMGPU_ERR_ARG; }
+    if (p > LOGIT_P_LIMIT) { set_error("logistic_cv_score_rm: p > %d is not supported", LOGIT_P_LIMIT); return OEMGPU_ERR_UNSUPPORTED; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    return logistic_cv_score_rm_dev(c, x_dev, dtype, n, ldr, p, y_dev, y_hi, foldid_dev, nfolds, coef, ncol, sums, counts, predmat_dev);
 }
 
 int oemgpu_logistic_cv_score_sparse_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const double *y_dev, double y_hi, const int32_t *foldid_dev,
