@@ -379,6 +379,36 @@ int oemgpu_cv_score_dev(oemgpu_ctx *ctx, int64_t n, int32_t p, int32_t nfolds, c
 int oemgpu_selftest_cv_score_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
                                  const int32_t *foldid_dev, int32_t nfolds, const double *coef, int32_t npen, int32_t nl,
                                  const int32_t *ncol, int32_t type_measure, double *triples, double *predmat_dev /* or NULL */);
+/* xval.oem and the fold fits of cv.oem(family = "gaussian") on a ROW-major x of float64 or float32 elements, read where it lies (every
+ * PyTorch tensor that was not transposed on purpose): x_dev as in oemgpu_fit_dense_rm_dev -- element (i, j) at x_dev[i * ldr + j], ldr
+ * >= p, dtype OEMGPU_F64 or OEMGPU_F32, aligned to its element size only; columns p .. ldr - 1 of a row and rows >= n are never read.
+ * The rows go into fold order straight from that x (xval.hip: fold_gather_rm_kernel, float32 widened in the register); the
+ * fold-ordered copy is column-major float64 as before and holds the bytes the column-major entry builds from the float64 copy of the
+ * same values, and everything behind it is that entry's code.  So
+ *   oemgpu_xval_dense_rm_dev    gives what oemgpu_xval_dense_dev gives (weights_dev included), and
+ *   oemgpu_cv_fold_fits_rm_dev  gives what oemgpu_cv_fold_fits_dev gives (the sample sums of a shifted re-pass come from the rows:
+ *                               oemgpu_shift_sums_rm_dev's buffer), and leaves the layout oemgpu_cv_score_dev scores,
+ * bit for bit.  There is no limit on p beyond the column-major entries' (OEMGPU_RM_P_MAX is the row-major MOMENT pass's; the moment
+ * passes here run on the fold-ordered copy).  Refused before a device is looked for: what the column-major entry refuses, with its
+ * codes and messages (its `ld < n` has no counterpart), and OEMGPU_ERR_ARG for a dtype that is neither code, ldr < p and an x_dev
+ * that is not a multiple of its element size. */
+int oemgpu_xval_dense_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                             const double *weights_dev /* or NULL */, const int32_t *foldid_dev, int32_t nfolds, int32_t standardize,
+                             int32_t intercept, int32_t type_measure, const oemgpu_opts *o,
+                             double *beta, double *lambda_out, int32_t *niter, double *loss, double *d,
+                             double *cvm, double *cvsd);
+int oemgpu_cv_fold_fits_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                               const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                               double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int64_t *fold_n);
+/* Test infrastructure (tests/test_gpu_cv_rowmajor.py): the fold layout and the row-major gather alone, into buffers of the caller's.
+ * xo_dev: p columns of ldo doubles, ldo >= (n + 16 nfolds) rounded up to 16; yo_dev: ldo doubles; fold_n / fold_start (host, [nfolds])
+ * <- the fold sizes and the position at which each fold's segment starts.  Row i of fold k, the r-th of its fold in the caller's
+ * order, lands at xo_dev[j * ldo + fold_start[k] + r] and yo_dev[fold_start[k] + r]; nothing else is written.  Nothing is fitted, so
+ * any n >= 1 and p >= 1 go.  The refusals of the entries above on dtype, ldr, alignment, nfolds (2..512) and n; OEMGPU_ERR_ARG for a
+ * short ldo and, from the device, for a fold id outside 1 .. nfolds (such a row is not written). */
+int oemgpu_selftest_fold_gather_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p,
+                                       const double *y_dev, const int32_t *foldid_dev, int32_t nfolds, double *xo_dev, int64_t ldo,
+                                       double *yo_dev, int64_t *fold_n, int64_t *fold_start);
 /* Host-only plan of the CV-error launch (xval.hip: cv_error_plan; pure arithmetic, runs without a GPU; the launch takes its shape from
  * the same function) for n rows, p columns, nfolds folds, npen penalties and nl lambdas on a device of num_cu CUs: out[0] lt = 16-lambda
  * tiles per pass (1..7: all ceil(nl / 16) tiles when there are <= 7, else the fewest passes of at most 7 made even), out[1] passes,

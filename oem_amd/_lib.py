@@ -140,6 +140,12 @@ _SIGS = {
                                       C.c_void_p]),                                                                  # R/cv_oem.R:376-391, R/utils.R:128-144
     "oemgpu_selftest_cv_score_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, _dp,
                                                C.c_int32, C.c_int32, _ip, C.c_int32, _dp, C.c_void_p]),
+    "oemgpu_xval_dense_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(OemgpuOpts)] + _OUT + [_dp, _dp]),
+    "oemgpu_cv_fold_fits_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                             C.c_int32, C.c_int32, C.POINTER(OemgpuOpts)] + _OUT + [C.POINTER(C.c_int64)]),
+    "oemgpu_selftest_fold_gather_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                                     C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "oemgpu_cv_sparse_fold_fits_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                                  C.POINTER(OemgpuOpts)] + _OUT + [C.POINTER(C.c_int64)]),     # R/cv_oem.R:105, 155-175 on a dgCMatrix
     "oemgpu_cv_sparse_score_res": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _ip, C.c_int32, _dp,

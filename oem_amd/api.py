@@ -264,6 +264,14 @@ def _logistic_rowmajor_in_place(x):
     return _rowmajor_dtype(x)
 
 
+def _xval_rowmajor_in_place(x):
+    """The dtype code with which xval_oem and the fold fits of cv_oem(family="gaussian") hand a device tensor to their _rm_dev entry as
+    it lies, or None: then it goes the column-major way.  _logistic_rowmajor_in_place's rule -- not already column-major, unit column
+    stride, a row stride of at least p, float64 or float32 -- and no limit on p: the rows are gathered into fold order, and the moment
+    passes run on that copy."""
+    return _logistic_rowmajor_in_place(x)
+
+
 def _rowmajor_args(x, y):
     import torch
     if not _is_torch_cuda(x):
@@ -305,6 +313,29 @@ def rowmajor_moments(x, y, sums=None):
                                           mom.data_ptr()))
     L.check(L.lib().oemgpu_synchronize(ctx))
     return mom.cpu().numpy().reshape(p + 2, p + 2).T
+
+
+def rowmajor_fold_order(x, y, foldid, nfolds):
+    """Test infrastructure: oemgpu_selftest_fold_gather_rm_dev on a row-major device tensor x (float64 / float32, read in place) -> (xo,
+    yo, fold_n, fold_start): the fold-ordered rows as numpy arrays xo[position, column] and yo[position] over every position of the
+    layout (NaN where nothing was written) and the folds' sizes and first positions."""
+    import torch
+    code, n, p, yd = _rowmajor_args(x, y)
+    K = int(nfolds)
+    fd = torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=x.device)
+    if fd.shape[0] != n:
+        raise ValueError("x and foldid lengths do not match")
+    ldo = (n + 16 * K + 15) // 16 * 16
+    xo = torch.full((p, ldo), float("nan"), dtype=torch.float64, device=x.device)
+    yo = torch.full((ldo,), float("nan"), dtype=torch.float64, device=x.device)
+    fold_n, fold_start = np.zeros(max(K, 1), dtype=np.int64), np.zeros(max(K, 1), dtype=np.int64)
+    ctx = context(x.device.index)
+    torch.cuda.current_stream(x.device).synchronize()
+    i64 = C.POINTER(C.c_int64)
+    L.check(L.lib().oemgpu_selftest_fold_gather_rm_dev(ctx, x.data_ptr(), code, n, x.stride(0), p, yd.data_ptr(), fd.data_ptr(), K, xo.data_ptr(),
+                                                       ldo, yo.data_ptr(), fold_n.ctypes.data_as(i64), fold_start.ctypes.data_as(i64)))
+    L.check(L.lib().oemgpu_synchronize(ctx))
+    return xo.cpu().numpy().T, yo.cpu().numpy(), fold_n, fold_start
 
 
 _ctx_cache = {}
@@ -813,7 +844,8 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
     """xval.oem(): R/oem_xval.R:107-460 (gaussian; a dense x, or any scipy.sparse x -- oemgpu_xval_sparse, the same result as on
     x.toarray() without building it; no weights, ngpus or devices there).  foldid: values 1..nfolds; drawn with `rng` (a numpy Generator)
     as sample(rep(seq(nfolds), length = n)) when None.  ngpus / devices (host x only): the rows over several devices inside the
-    library, as in oem()."""
+    library, as in oem().  A row-major float64 or float32 device tensor is gathered into fold order where it lies
+    (oemgpu_xval_dense_rm_dev; _xval_rowmajor_in_place): the column-major call's result bit for bit, without its copies."""
     L.sync_switches()
     if family not in ("gaussian", "binomial"):
         raise ValueError("'arg' should be one of 'gaussian', 'binomial'")
@@ -890,17 +922,24 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
                                        _dptr(cvm), _dptr(cvsd)))
     elif _is_torch_cuda(x):
         import torch
-        xp, n_, p_, ld, keep = _device_matrix(x)
+        rm = _xval_rowmajor_in_place(x)
+        if rm is None:
+            xp, n_, p_, ld, keep = _device_matrix(x)
         yd = y if _is_torch_cuda(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=x.device)
         yd = yd.to(torch.float64).contiguous().reshape(-1)
         fd = torch.as_tensor(fid, device=x.device)
         wd = None if wh is None else torch.as_tensor(wh, device=x.device)
         ctx = context(x.device.index)
         torch.cuda.current_stream(x.device).synchronize()
-        L.check(lib.oemgpu_xval_dense_dev(ctx, xp, n, ld, p, yd.data_ptr(), None if wd is None else wd.data_ptr(), fd.data_ptr(),
-                                          int(nfolds), int(bool(standardize)),
-                                          int(bool(intercept)), tm, C.byref(a.c), *out, _dptr(cvm), _dptr(cvsd)))
-        del keep
+        if rm is not None:                                         # the rows go into fold order from where they lie: no float64 copy, no transposed copy
+            L.check(lib.oemgpu_xval_dense_rm_dev(ctx, x.data_ptr(), rm, n, x.stride(0), p, yd.data_ptr(), None if wd is None else wd.data_ptr(),
+                                                 fd.data_ptr(), int(nfolds), int(bool(standardize)),
+                                                 int(bool(intercept)), tm, C.byref(a.c), *out, _dptr(cvm), _dptr(cvsd)))
+        else:
+            L.check(lib.oemgpu_xval_dense_dev(ctx, xp, n, ld, p, yd.data_ptr(), None if wd is None else wd.data_ptr(), fd.data_ptr(),
+                                              int(nfolds), int(bool(standardize)),
+                                              int(bool(intercept)), tm, C.byref(a.c), *out, _dptr(cvm), _dptr(cvsd)))
+            del keep
     else:
         xh = np.asfortranarray(x, dtype=np.float64)
         yh = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
@@ -1342,13 +1381,16 @@ def _cv_gaussian_resident(x, penalty, kw, foldid, nfolds):
 
 
 def _cv_gaussian_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw):
-    """The K calls oem(x[!which, ], y[!which], ...) of R/cv_oem.R:155-175 on the resident x: oemgpu_cv_fold_fits_dev.  Returns the fold
+    """The K calls oem(x[!which, ], y[!which], ...) of R/cv_oem.R:155-175 on the resident x: oemgpu_cv_fold_fits_dev, or
+    oemgpu_cv_fold_fits_rm_dev on a row-major float64 / float32 tensor as it lies (the same fits bit for bit).  Returns the fold
     fits as oem() returns them and what the scoring needs (the context, the shapes, the fold sizes, the option block)."""
     import types
     import torch
     n, p = x.shape
     a, varnames, standardize, intercept = oem(x, y, penalty=penalty, lambda_=lam_arg, _args_only=True, **kw)
-    xp, _, _, ld, keepalive = _device_matrix(x)
+    rm = _xval_rowmajor_in_place(x)
+    if rm is None:
+        xp, _, _, ld, keepalive = _device_matrix(x)
     yd = y if _is_torch_cuda(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=x.device)
     yd = yd.to(torch.float64).contiguous().reshape(-1)
     fd = torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=x.device)
@@ -1359,10 +1401,13 @@ def _cv_gaussian_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw):
     niter = np.zeros((K, npen, nl), dtype=np.int32)
     d, fold_n = np.zeros(K), np.zeros(K, dtype=np.int64)
     torch.cuda.current_stream(x.device).synchronize()
-    L.check(L.lib().oemgpu_cv_fold_fits_dev(ctx, xp, n, ld, p, yd.data_ptr(), fd.data_ptr(), K, int(standardize), int(intercept),
-                                            C.byref(a.c), _dptr(beta), _dptr(lam_out), _iptr(niter), _dptr(loss),
-                                            _dptr(d), fold_n.ctypes.data_as(C.POINTER(C.c_int64))))
-    del keepalive
+    outs = (C.byref(a.c), _dptr(beta), _dptr(lam_out), _iptr(niter), _dptr(loss), _dptr(d), fold_n.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rm is not None:                                             # the rows go into fold order from where they lie (oemgpu_cv_fold_fits_rm_dev)
+        L.check(L.lib().oemgpu_cv_fold_fits_rm_dev(ctx, x.data_ptr(), rm, n, x.stride(0), p, yd.data_ptr(), fd.data_ptr(), K, int(standardize),
+                                                   int(intercept), *outs))
+    else:
+        L.check(L.lib().oemgpu_cv_fold_fits_dev(ctx, xp, n, ld, p, yd.data_ptr(), fd.data_ptr(), K, int(standardize), int(intercept), *outs))
+        del keepalive
     outlist = [_decorate(types.SimpleNamespace(beta=beta[i], lam_out=lam_out[i], niter=niter[i], loss=loss[i],
                                                d=types.SimpleNamespace(value=float(d[i]))), penalty, varnames, True, int(n - fold_n[i]), p)
                for i in range(K)]

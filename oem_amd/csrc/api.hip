@@ -2255,7 +2255,24 @@ static int xval_check(oemgpu_ctx *c, const void *x_dev, const void *y_dev, const
 
 // phase 1: hf <- the local fold sizes [K] and fold starts [K]; mfold (and csq) in aux <- the local rows' per-fold moments
 static int xval_fold_moments(oemgpu_ctx *c, const XvalLay &L, const std::vector<int64_t> &hf, const double *sums);
-static int xval_prepare(oemgpu_ctx *c, const XvalLay &L, const double *x_dev, int64_t ld, const double *y_dev, const double *w_dev,
+// where the rows come from: a column-major float64 x (dtype < 0, ld the column stride: launch_gather_rows) or a row-major x of
+// OEMGPU_F64 / OEMGPU_F32 elements read where it lies (ld the row stride: launch_gather_rows_rm).  Either way the fold-ordered copy
+// is column-major float64, and the same bytes for the same values.
+struct XvalSrc {
+    const void *x;
+    int dtype;
+    int64_t ld;
+};
+static XvalSrc xval_src_cm(const double *x_dev, int64_t ld) { return XvalSrc{x_dev, -1, ld}; }
+static XvalSrc xval_src_rm(const void *x_dev, int dtype, int64_t ldr) { return XvalSrc{x_dev, dtype, ldr}; }
+static int xval_gather(oemgpu_ctx *c, const XvalSrc &X, int64_t n, int p, const double *y_dev, const int32_t *foldid_dev, int K, const int *pos,
+                       double *xo, int64_t ldo, double *yo)
+{
+    if (X.dtype < 0) return launch_gather_rows(c->stream, (const double *)X.x, n, X.ld, p, y_dev, pos, xo, ldo, yo);
+    return launch_gather_rows_rm(c->stream, X.x, X.dtype, n, X.ld, p, y_dev, foldid_dev, K, pos, xo, ldo, yo);
+}
+
+static int xval_prepare(oemgpu_ctx *c, const XvalLay &L, const XvalSrc &X, const double *y_dev, const double *w_dev,
                         const int32_t *foldid_dev, std::vector<int64_t> &hf, bool moments = true)
 {
     const int64_t n = L.n;
@@ -2277,9 +2294,9 @@ static int xval_prepare(oemgpu_ctx *c, const XvalLay &L, const double *x_dev, in
         double *csq = (double *)(ax + L.a_cs);
         if (w_dev) {
             rc = launch_gather_rows(c->stream, w_dev, n, n, 1, y_dev, pos, xp, L.ldp, yp);               // column 0 <- w
-            if (!rc) rc = launch_gather_rows(c->stream, x_dev, n, ld, p, y_dev, pos, xp + L.ldp, L.ldp, yp);
+            if (!rc) rc = xval_gather(c, X, n, p, y_dev, foldid_dev, K, pos, xp + L.ldp, L.ldp, yp);
             if (!rc) rc = launch_weight_scale(c->stream, xp, L.ldp, yp, p, K, fold_start, fold_n, csq);
-        } else rc = launch_gather_rows(c->stream, x_dev, n, ld, p, y_dev, pos, xp, L.ldp, yp);
+        } else rc = xval_gather(c, X, n, p, y_dev, foldid_dev, K, pos, xp, L.ldp, yp);
         if (rc) return rc;
     }
     OEM_HIP(hipStreamSynchronize(c->stream));
@@ -2440,26 +2457,62 @@ static int xval_cverr(oemgpu_ctx *c, const XvalLay &L, int32_t type_measure, con
     return 0;
 }
 
-int oemgpu_xval_dense_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+// X.dtype < 0: ld is the column stride (checked >= n); a row-major source was checked by rm_src_check and counts as ld = n here
+static int xval_dense_src(oemgpu_ctx *c, const XvalSrc &X, int64_t n, int32_t p, const double *y_dev,
                           const double *w_dev, const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept,
                           int32_t type_measure, const oemgpu_opts *o,
                           double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, double *cvm, double *cvsd)
 {
-    if (!c || !x_dev || !y_dev || !foldid_dev || !beta || !lambda_out || !niter || !loss || !d || !cvm || !cvsd) {
+    if (!c || !X.x || !y_dev || !foldid_dev || !beta || !lambda_out || !niter || !loss || !d || !cvm || !cvsd) {
         set_error("xval_dense: NULL argument"); return OEMGPU_ERR_ARG;
     }
     const int K = nfolds;
-    int rc = xval_check(c, x_dev, y_dev, foldid_dev, n, ld, p, K, intercept, type_measure, w_dev != nullptr, o);
+    int rc = xval_check(c, X.x, y_dev, foldid_dev, n, X.dtype < 0 ? X.ld : n, p, K, intercept, type_measure, w_dev != nullptr, o);
     if (rc) return rc;
     if (n <= p) { set_error("dimension of x larger than number of observations"); return OEMGPU_ERR_UNSUPPORTED; }   // ref src/oem_xval_dense.h:690-731
     if (set_device(c)) return OEMGPU_ERR_HIP;
     const XvalLay L = xval_layout(c, n, p, K, o->npen, nl_of(o), w_dev != nullptr);
     if (ctx_aux(c, L.total)) return OEMGPU_ERR_HIP;
     std::vector<int64_t> hf;
-    rc = xval_prepare(c, L, x_dev, ld, y_dev, w_dev, foldid_dev, hf);
+    rc = xval_prepare(c, L, X, y_dev, w_dev, foldid_dev, hf);
     if (!rc) rc = xval_solve(c, L, hf.data(), n, standardize, intercept, o, beta, lambda_out, niter, loss, d);
     if (!rc) rc = xval_cverr(c, L, type_measure, o, cvm, cvsd, nullptr);
     return rc;
+}
+
+int oemgpu_xval_dense_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                          const double *w_dev, const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept,
+                          int32_t type_measure, const oemgpu_opts *o,
+                          double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, double *cvm, double *cvsd)
+{
+    return xval_dense_src(c, xval_src_cm(x_dev, ld), n, p, y_dev, w_dev, foldid_dev, nfolds, standardize, intercept, type_measure, o, beta,
+                          lambda_out, niter, loss, d, cvm, cvsd);
+}
+
+// what a row-major source adds to its column-major counterpart's refusals (the rule of the other _rm_dev entries, and the element's
+// alignment: the gather loads one element per lane)
+static int rm_src_check(const char *who, const void *x_dev, int32_t dtype, int64_t ldr, int32_t p)
+{
+    if (dtype != OEMGPU_F64 && dtype != OEMGPU_F32) { set_error("%s: dtype %d is neither OEMGPU_F64 nor OEMGPU_F32", who, dtype); return OEMGPU_ERR_ARG; }
+    if (ldr < p) { set_error("%s: bad ldr (ldr >= p)", who); return OEMGPU_ERR_ARG; }
+    const uintptr_t el = dtype == OEMGPU_F32 ? 4 : 8;
+    if (((uintptr_t)x_dev) % el) { set_error("%s: x_dev is not aligned to its %d-byte elements", who, (int)el); return OEMGPU_ERR_ARG; }
+    return 0;
+}
+
+// oemgpu_xval_dense_dev with the rows gathered from a row-major x where it lies (xval.hip: fold_gather_rm_kernel); everything behind
+// the fold-ordered copy is that entry's, and so are the results, bit for bit
+int oemgpu_xval_dense_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                             const double *w_dev, const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept,
+                             int32_t type_measure, const oemgpu_opts *o,
+                             double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, double *cvm, double *cvsd)
+{
+    if (!c || !x_dev || !y_dev || !foldid_dev || !beta || !lambda_out || !niter || !loss || !d || !cvm || !cvsd) {
+        set_error("xval_dense: NULL argument"); return OEMGPU_ERR_ARG;
+    }
+    if (int rc = rm_src_check("xval_dense_rm", x_dev, dtype, ldr, p)) return rc;
+    return xval_dense_src(c, xval_src_rm(x_dev, dtype, ldr), n, p, y_dev, w_dev, foldid_dev, nfolds, standardize, intercept, type_measure, o, beta,
+                          lambda_out, niter, loss, d, cvm, cvsd);
 }
 
 // ---- the same three phases as separate calls, for row shards on several GPUs (one process per GPU; the caller sums the fold
@@ -2482,7 +2535,7 @@ int oemgpu_xval_fold_moments_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, 
     const XvalLay L = xval_layout(c, n, p, K, o->npen, nl_of(o), w_dev != nullptr);
     if (ctx_aux(c, L.total)) return OEMGPU_ERR_HIP;
     std::vector<int64_t> hf;
-    rc = xval_prepare(c, L, x_dev, ld, y_dev, w_dev, foldid_dev, hf);
+    rc = xval_prepare(c, L, xval_src_cm(x_dev, ld), y_dev, w_dev, foldid_dev, hf);
     if (rc) return rc;
     for (int k = 0; k < K; ++k) fold_n[k] = hf[k];
     OEM_HIP(hipMemcpyAsync(fold_moments_dev, c->aux + L.a_mf, sizeof(double) * L.mlen * K, hipMemcpyDeviceToDevice, c->stream));
@@ -2539,7 +2592,7 @@ int oemgpu_selftest_xval_cv_error_dev(oemgpu_ctx *c, const double *x_dev, int64_
     const XvalLay L = xval_layout(c, n, p, K, npen, nl, w_dev != nullptr);
     if (ctx_aux(c, L.total)) return OEMGPU_ERR_HIP;
     std::vector<int64_t> hf;
-    rc = xval_prepare(c, L, x_dev, ld, y_dev, w_dev, foldid_dev, hf);
+    rc = xval_prepare(c, L, xval_src_cm(x_dev, ld), y_dev, w_dev, foldid_dev, hf);
     if (rc) return rc;
     char *ax = c->aux;
     int64_t *fold_n = (int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
@@ -2615,26 +2668,26 @@ static int cv_check_rows(const char *who, int64_t n, int64_t ld, int p, int K)
 }
 
 // rows into fold order (and the fold moments about 0), and the stamp oemgpu_cv_score_dev looks for
-static int cv_lay_out(oemgpu_ctx *c, const CvLay &V, const double *x_dev, int64_t ld, const double *y_dev, const int32_t *foldid_dev,
+static int cv_lay_out(oemgpu_ctx *c, const CvLay &V, const XvalSrc &X, const double *y_dev, const int32_t *foldid_dev,
                       bool moments, std::vector<int64_t> &hf)
 {
     if (ctx_aux(c, V.total)) return OEMGPU_ERR_HIP;
-    int rc = xval_prepare(c, V.L, x_dev, ld, y_dev, nullptr, foldid_dev, hf, moments);
+    int rc = xval_prepare(c, V.L, X, y_dev, nullptr, foldid_dev, hf, moments);
     if (rc) return rc;
     c->cv_n = V.L.n; c->cv_p = V.L.p; c->cv_K = V.L.K; c->cv_aux = c->aux; c->cv_hf = hf; c->cv_kind = CV_KIND_DENSE;
     return 0;
 }
 
-int oemgpu_cv_fold_fits_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+static int cv_fold_fits_src(oemgpu_ctx *c, const XvalSrc &X, int64_t n, int32_t p, const double *y_dev,
                             const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept, const oemgpu_opts *o,
                             double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int64_t *fold_n)
 {
-    if (!c || !x_dev || !y_dev || !foldid_dev || !o || !beta || !lambda_out || !niter || !loss || !d || !fold_n) {
+    if (!c || !X.x || !y_dev || !foldid_dev || !o || !beta || !lambda_out || !niter || !loss || !d || !fold_n) {
         set_error("cv_fold_fits: NULL argument"); return OEMGPU_ERR_ARG;
     }
     const int K = nfolds;
     int rc = check_opts(o, p, p);
-    if (!rc) rc = cv_check_rows("cv_fold_fits", n, ld, p, K);
+    if (!rc) rc = cv_check_rows("cv_fold_fits", n, X.dtype < 0 ? X.ld : n, p, K);
     if (rc) return rc;
     // the largest fold holds at least ceil(n / K) rows: some fold fit is then not the Gram form whatever the ids are
     if (n - (n + K - 1) / K <= p) {
@@ -2646,7 +2699,7 @@ int oemgpu_cv_fold_fits_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64
     const CvLay V = cv_layout(c, n, p, K, npen, nl);
     const XvalLay &L = V.L;
     std::vector<int64_t> hf;
-    rc = cv_lay_out(c, V, x_dev, ld, y_dev, foldid_dev, true, hf);
+    rc = cv_lay_out(c, V, X, y_dev, foldid_dev, true, hf);
     if (rc) return rc;
     for (int k = 0; k < K; ++k) {
         fold_n[k] = hf[k];
@@ -2675,10 +2728,69 @@ int oemgpu_cv_fold_fits_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64
     rc = solve_all(nullptr, &advised);
     if (rc || !advised) return rc;
     // oemgpu_fit_dense_dev's rule, for all folds at once: sample sums of all rows, the segment passes about them, the solves again
-    rc = launch_shift_sums(c->stream, x_dev, n, ld, p, y_dev, sums);
+    // (launch_shift_sums_rm's buffer is launch_shift_sums' on the column-major float64 copy, bit for bit)
+    rc = X.dtype < 0 ? launch_shift_sums(c->stream, (const double *)X.x, n, X.ld, p, y_dev, sums)
+                     : launch_shift_sums_rm(c->stream, X.x, X.dtype, n, X.ld, p, y_dev, sums);
     if (!rc) rc = xval_fold_moments(c, L, hf, sums);
     if (!rc) rc = solve_all(sums, nullptr);
     return rc;
+}
+
+int oemgpu_cv_fold_fits_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                            const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                            double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int64_t *fold_n)
+{
+    return cv_fold_fits_src(c, xval_src_cm(x_dev, ld), n, p, y_dev, foldid_dev, nfolds, standardize, intercept, o, beta, lambda_out, niter, loss,
+                            d, fold_n);
+}
+
+// oemgpu_cv_fold_fits_dev with the rows gathered from a row-major x where it lies; the layout stamp is the same CV_KIND_DENSE, so
+// oemgpu_cv_score_dev scores it as it is
+int oemgpu_cv_fold_fits_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                               const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                               double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int64_t *fold_n)
+{
+    if (!c || !x_dev || !y_dev || !foldid_dev || !o || !beta || !lambda_out || !niter || !loss || !d || !fold_n) {
+        set_error("cv_fold_fits: NULL argument"); return OEMGPU_ERR_ARG;
+    }
+    if (int rc = rm_src_check("cv_fold_fits_rm", x_dev, dtype, ldr, p)) return rc;
+    return cv_fold_fits_src(c, xval_src_rm(x_dev, dtype, ldr), n, p, y_dev, foldid_dev, nfolds, standardize, intercept, o, beta, lambda_out, niter,
+                            loss, d, fold_n);
+}
+
+// Test infrastructure: the fold layout and the row-major gather alone, into buffers of the caller's -- xo_dev: p columns of ldo >=
+// 16 * ceil((n + 16 nfolds) / 16) doubles, yo_dev: ldo doubles; fold_n / fold_start (host, [nfolds]) <- the fold sizes and where each
+// fold's segment starts.  Nothing is fitted: any n >= 1, p >= 1.
+int oemgpu_selftest_fold_gather_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                                       const int32_t *foldid_dev, int32_t nfolds, double *xo_dev, int64_t ldo, double *yo_dev,
+                                       int64_t *fold_n, int64_t *fold_start)
+{
+    if (!c || !x_dev || !y_dev || !foldid_dev || !xo_dev || !yo_dev || !fold_n || !fold_start) {
+        set_error("selftest_fold_gather_rm: NULL argument"); return OEMGPU_ERR_ARG;
+    }
+    int rc = rm_src_check("selftest_fold_gather_rm", x_dev, dtype, ldr, p);
+    if (!rc) rc = cv_check_rows("selftest_fold_gather_rm", n, n, p, nfolds);
+    if (rc) return rc;
+    const int K = nfolds;
+    if (ldo < (n + 16 * (int64_t)K + 15) / 16 * 16) { set_error("selftest_fold_gather_rm: ldo is shorter than the fold-ordered rows"); return OEMGPU_ERR_ARG; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    Bump B;
+    const size_t a_cnt = B.take(fold_layout_ints(n, K) * sizeof(int)), a_fn = B.take(sizeof(int64_t) * 2 * K), a_bad = B.take(256),
+                 a_pos = B.take(sizeof(int) * (size_t)n);
+    if (ctx_reserve(c, B.off)) return OEMGPU_ERR_HIP;
+    int *blockcnt = (int *)(c->ws + a_cnt), *bad = (int *)(c->ws + a_bad), *pos = (int *)(c->ws + a_pos);
+    int64_t *fn = (int64_t *)(c->ws + a_fn);
+    rc = launch_fold_layout(c->stream, foldid_dev, n, K, blockcnt, fn, fn + K, pos, bad);
+    if (!rc) rc = launch_gather_rows_rm(c->stream, x_dev, dtype, n, ldr, p, y_dev, foldid_dev, K, pos, xo_dev, ldo, yo_dev);
+    if (rc) return rc;
+    int hbad = 0;
+    std::vector<int64_t> hf(2 * K);
+    OEM_HIP(hipMemcpyAsync(hf.data(), fn, sizeof(int64_t) * 2 * K, hipMemcpyDeviceToHost, c->stream));
+    OEM_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    OEM_HIP(hipStreamSynchronize(c->stream));
+    if (hbad) { set_error("xval_dense: foldid must hold values in 1..nfolds"); return OEMGPU_ERR_ARG; }
+    for (int k = 0; k < K; ++k) { fold_n[k] = hf[k]; fold_start[k] = hf[K + k]; }
+    return 0;
 }
 
 int oemgpu_cv_score_dev(oemgpu_ctx *c, int64_t n, int32_t p, int32_t nfolds, const double *coef, int32_t npen, int32_t nl,
@@ -2730,7 +2842,7 @@ int oemgpu_selftest_cv_score_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, 
     if (set_device(c)) return OEMGPU_ERR_HIP;
     const CvLay V = cv_layout(c, n, p, nfolds, npen, nl);
     std::vector<int64_t> hf;
-    rc = cv_lay_out(c, V, x_dev, ld, y_dev, foldid_dev, false, hf);
+    rc = cv_lay_out(c, V, xval_src_cm(x_dev, ld), y_dev, foldid_dev, false, hf);
     if (rc) return rc;
     return oemgpu_cv_score_dev(c, n, p, nfolds, coef, npen, nl, ncol, type_measure, triples, predmat_dev);
 }
@@ -2805,7 +2917,7 @@ static int xval_dense_devices(const std::vector<int> &dev, const double *x, int6
         if (r) return r;
         q.L = xval_layout(q.c, q.r1 - q.r0, p, K, npen, nl, weights != nullptr);
         if (ctx_aux(q.c, q.L.total)) return OEMGPU_ERR_HIP;
-        return xval_prepare(q.c, q.L, q.xd, q.ld, q.yd, q.wd, q.fd, q.hf);
+        return xval_prepare(q.c, q.L, xval_src_cm(q.xd, q.ld), q.yd, q.wd, q.fd, q.hf);
     });
     if (rc) { release_all(); return rc; }
     // ---- the fold moments of devices 1 .. G-1 into device 0's, in device order (bitwise reproducible); fold sizes on the host

@@ -130,6 +130,9 @@ int launch_fold_layout(hipStream_t s, const int *foldid, int64_t n, int K, int *
                        int *pos, int *bad, int align = 16);   // align: fold segments start on multiples of it (16: the MFMA kernels; CSC_CHUNK: a sparse x)
 int launch_gather_rows(hipStream_t s, const double *x, int64_t n, int64_t ld, int p, const double *y, const int *pos,
                        double *xo, int64_t ldo, double *yo);
+// the same from a row-major x of OEMGPU_F64 / OEMGPU_F32 elements (row stride ldr); a row whose foldid is outside 1..K writes nothing
+int launch_gather_rows_rm(hipStream_t s, const void *x, int dtype, int64_t n, int64_t ldr, int p, const double *y, const int *foldid, int K,
+                          const int *pos, double *xo, int64_t ldo, double *yo);
 int launch_fold_sum(hipStream_t s, const double *M, int K, size_t len, int skip /* 1-based, 0: none */, double *out);
 // the shape of the CV-error launch (xval.hip: cv_error_plan; pure host arithmetic): K4 = p + 1 rounded up to a k-step of 4, ntile 16-lambda
 // tiles in `passes` passes of lt each, form CV_FORM_*, lds dynamic bytes, the coefficient rows in `chunks` LDS chunks of which the last

@@ -100,6 +100,57 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const double *__restri
     if (blockIdx.y == 0) yo[d] = y[i];
 }
 
+// The same from a ROW-major x of float64 or float32 elements (x[i * ldr + c], read where it lies): the transposing counterpart.  A
+// workgroup takes a tile of GRM_ROWS rows x GRM_COLS columns (tile t: row tile t / nct, column tile t % nct, so the column tiles of
+// the same rows run side by side and share the lines their row segments straddle).  Read with the lanes along a row -- 32 elements,
+// 256 B (float32: 128 B) contiguous per row, two rows per wave and load, one element per lane: no load is wider than the element,
+// so x needs its element's alignment only -- widened in the register, through LDS, and written with the lanes along the 64 rows of
+// one destination column: the rows of a fold that lie in the tile land in consecutive positions (pos increases within a fold), the
+// K write streams of gather_rows_kernel.  LDS: [64][33] doubles.  The stores of a row segment (ds_write_b64: 16-lane groups, 32 banks)
+// hit consecutive doubles; the transposed loads (ds_read_b64: 32-lane halves, 64 banks) are 33 doubles apart, lane r on the bank pair
+// (2 r + 2 c) mod 64: both without conflicts.  Columns >= p and rows >= n are never loaded; a row whose fold id is outside 1..K has no
+// position (fold_pos_kernel leaves it unset) and writes nothing.  No arithmetic, no atomics, every destination written once.
+constexpr int GRM_ROWS = 64, GRM_COLS = 32;
+template <typename T>
+__global__ __launch_bounds__(256) void fold_gather_rm_kernel(const T *__restrict__ x, int64_t n, int64_t ldr, int p, int nct,
+                                                             const double *__restrict__ y, const int *__restrict__ foldid, int K,
+                                                             const int *__restrict__ pos, double *__restrict__ xo, int64_t ldo,
+                                                             double *__restrict__ yo)
+{
+    __shared__ double tile[GRM_ROWS][GRM_COLS + 1];
+    const int64_t rt = (int64_t)blockIdx.x / nct;
+    const int ct = (int)((int64_t)blockIdx.x - rt * nct);
+    const int64_t i0 = rt * GRM_ROWS;
+    const int c0 = ct * GRM_COLS;
+    const int tid = threadIdx.x;
+    // this lane's destination row first: the fold id and the position are on their way while the tile is loaded
+    const int r = tid & (GRM_ROWS - 1), cc = tid >> 6;              // (the store phase: 64 rows of 4 columns per step)
+    int64_t d = -1;
+    if (i0 + r < n) {
+        const int f = foldid[i0 + r];
+        if (f >= 1 && f <= K) d = pos[i0 + r];
+    }
+    {
+        const int lc = tid & (GRM_COLS - 1), lr = tid >> 5;         // the load phase: 8 rows of 32 columns per step
+        double v[GRM_ROWS / 8];
+#pragma unroll
+        for (int k = 0; k < GRM_ROWS / 8; ++k) {
+            const int64_t i = i0 + lr + 8 * k;
+            v[k] = (c0 + lc < p && i < n) ? (double)x[i * ldr + (c0 + lc)] : 0.0;
+        }
+#pragma unroll
+        for (int k = 0; k < GRM_ROWS / 8; ++k) tile[lr + 8 * k][lc] = v[k];
+    }
+    __syncthreads();
+    if (d < 0) return;                                              // a row >= n, or one whose fold id is outside 1..K (its pos is unset)
+#pragma unroll
+    for (int k = 0; k < GRM_COLS / 4; ++k) {
+        const int c = cc + 4 * k;
+        if (c0 + c < p) xo[(int64_t)(c0 + c) * ldo + d] = tile[r][c];
+    }
+    if (ct == 0 && cc == 0) yo[d] = y[i0 + r];
+}
+
 // out = sum of the fold moments except fold `skip` (1-based; 0: none), in fold order (ref src/oem_xval_dense.h:733-742, 801-811)
 __global__ __launch_bounds__(256) void fold_sum_kernel(const double *__restrict__ M, int K, size_t len, int skip, double *__restrict__ out)
 {
@@ -453,6 +504,22 @@ int launch_gather_rows(hipStream_t s, const double *x, int64_t n, int64_t ld, in
 {
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n + 255) / 256), (p + GCB - 1) / GCB), dim3(256), 0, s, x, n, ld, p,
                        y, pos, xo, ldo, yo);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_gather_rows_rm(hipStream_t s, const void *x, int dtype, int64_t n, int64_t ldr, int p, const double *y, const int *foldid, int K,
+                          const int *pos, double *xo, int64_t ldo, double *yo)
+{
+    const int nct = (p + GRM_COLS - 1) / GRM_COLS;
+    const int64_t tiles = ((n + GRM_ROWS - 1) / GRM_ROWS) * nct;
+    if (tiles > 0x7fffffff) { set_error("fold gather of a row-major x: %lld x %d is more tiles than one launch takes", (long long)n, p); return OEMGPU_ERR_UNSUPPORTED; }
+    if (dtype == OEMGPU_F32)
+        hipLaunchKernelGGL(fold_gather_rm_kernel<float>, dim3((unsigned)tiles), dim3(256), 0, s, (const float *)x, n, ldr, p, nct, y, foldid, K,
+                           pos, xo, ldo, yo);
+    else
+        hipLaunchKernelGGL(fold_gather_rm_kernel<double>, dim3((unsigned)tiles), dim3(256), 0, s, (const double *)x, n, ldr, p, nct, y, foldid, K,
+                           pos, xo, ldo, yo);
     OEM_HIP(hipGetLastError());
     return 0;
 }
