@@ -520,6 +520,24 @@ int oemgpu_selftest_plan(int32_t p, int32_t q, int32_t semantics, int32_t interc
  * to n" (the folds of xval.oem, the row tiles of a sparse x) holds the plans of smaller row counts: OEMGPU_ERR_INTERNAL if not. */
 int oemgpu_selftest_gram_plan(int64_t n, int32_t p, int32_t num_cu, int64_t *out /* 8 */);
 
+/* The kernel form the moment pass takes for an n x p column-major x with leading dimension ld (pure host arithmetic, no device; the
+ * launch calls the same function): out[0] = OEMGPU_GRAM_FORM_*, out[1] = strip sub-blocks of the ring kernel's last tile row (0, 1, 2;
+ * 0 for every other form).  aligned: x and y 16-byte aligned and ld even.  The scalar-base forms (RING_SADDR, SB, WD*) address a
+ * fragment as a 64-bit scalar base plus a 32-bit byte offset per lane: RING_SADDR needs p ld 8 + 65536 < 2^32 and whole-column
+ * fragments (p >= 16 (tile columns - 1)), SB / WD* need 16 ld 8 < 2^32; all three need aligned input and n >= 64.  Behind those guards
+ * the pass takes 64-bit addresses: RING_LANE, TRI (the triangle fits one wave) or BLK. */
+enum {
+    OEMGPU_GRAM_FORM_TRI = 0,        /* gram_tri_kernel: p + 2 <= 112, unaligned or n < 64 or fewer than 4 tile columns */
+    OEMGPU_GRAM_FORM_RING_SADDR = 1, /* gram_ring_kernel, scalar base + 32-bit lane offsets */
+    OEMGPU_GRAM_FORM_RING_LANE = 2,  /* gram_ring_kernel, a 64-bit pointer per lane */
+    OEMGPU_GRAM_FORM_SB = 3,         /* gram_sb.hip: shared-slab super-blocks */
+    OEMGPU_GRAM_FORM_WD3 = 4,        /* gram_wd.hip: 11-12 tile columns, one read of x, groups of three */
+    OEMGPU_GRAM_FORM_WD4 = 5,        /* gram_wd.hip: 15-16 tile columns, groups of four */
+    OEMGPU_GRAM_FORM_WD_UNITS = 6,   /* gram_wd.hip: 16 k (- 1) tile columns, k >= 2 units */
+    OEMGPU_GRAM_FORM_BLK = 7         /* gram_blk_kernel: more than 7 tile columns, unaligned, n < 64 or 16 ld 8 >= 2^32 */
+};
+int oemgpu_selftest_gram_form(int64_t n, int64_t ld, int32_t p, int32_t aligned, int32_t num_cu, int64_t *out /* 2 */);
+
 /* ---------------------------------------------------------------------------------------------------------- binomial (logistic.hip)
  * `.Call("oem_fit_logistic_dense", ...)` (ref src/oem_logistic_dense.cpp:30-313, src/oem_logistic_dense.h:397-1094): IRLS over the OEM
  * iteration, dense x, n > p + intercept.  opts as for oemgpu_fit_dense (accelerate is ignored: the reference has no Nesterov step here);

@@ -1267,6 +1267,14 @@ int oemgpu_selftest_gram_plan(int64_t n, int32_t p, int32_t num_cu, int64_t *out
     return 0;
 }
 
+int oemgpu_selftest_gram_form(int64_t n, int64_t ld, int32_t p, int32_t aligned, int32_t num_cu, int64_t *out)
+{
+    if (n < 1 || ld < 1 || p < 1 || num_cu < 1 || !out) { set_error("selftest_gram_form: bad argument"); return OEMGPU_ERR_ARG; }
+    const GramForm f = gram_form(gram_plan(n, p, num_cu), n, ld, aligned != 0);
+    out[0] = f.form; out[1] = f.strips;
+    return 0;
+}
+
 int oemgpu_selftest_hold_cus(oemgpu_ctx *c, int32_t blocks, double ms)
 {
     if (!c || blocks < 1 || blocks > 4096 || !(ms > 0.0) || ms > 30000.0) { set_error("hold_cus: bad argument"); return OEMGPU_ERR_ARG; }

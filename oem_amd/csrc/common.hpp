@@ -44,6 +44,12 @@ struct GramPlan {
 GramPlan gram_plan(int64_t n, int p, int num_cu);
 GramPlan gram_plan_bound(int64_t nmax, int p, int num_cu);   // sizes that hold the plan of any n <= nmax
 void gram_sb_deal(int ntc, int *n8, int *n6, int *n4);
+// the kernel form a pass takes (gram.hip: gram_form, the one place it is decided): OEMGPU_GRAM_FORM_* and the ring's strip count
+enum { GRAM_FORM_TRI = OEMGPU_GRAM_FORM_TRI, GRAM_FORM_RING_SADDR = OEMGPU_GRAM_FORM_RING_SADDR, GRAM_FORM_RING_LANE = OEMGPU_GRAM_FORM_RING_LANE,
+       GRAM_FORM_SB = OEMGPU_GRAM_FORM_SB, GRAM_FORM_WD3 = OEMGPU_GRAM_FORM_WD3, GRAM_FORM_WD4 = OEMGPU_GRAM_FORM_WD4,
+       GRAM_FORM_WD_UNITS = OEMGPU_GRAM_FORM_WD_UNITS, GRAM_FORM_BLK = OEMGPU_GRAM_FORM_BLK };
+struct GramForm { int form, strips; };
+GramForm gram_form(const GramPlan &pl, int64_t n, int64_t ld, bool aligned);
 
 int launch_shift_sums(hipStream_t s, const double *x, int64_t n, int64_t ld, int p, const double *y, double *sums);
 int launch_gram(hipStream_t s, const GramPlan &pl, const double *x, int64_t n, int64_t ld, const double *y,

@@ -943,11 +943,45 @@ GramPlan gram_plan_bound(int64_t nmax, int p, int num_cu)
     return pl;
 }
 
+// The ONE place the kernel form of a moment pass is decided (pure host arithmetic; launch_gram_t below only dispatches on it, and
+// oemgpu_selftest_gram_form reports it).  The scalar-base forms address a fragment as a 64-bit scalar base plus a 32-bit byte offset
+// per lane, which the hardware zero-extends: every lane offset has to lie in [0, 2^32).
+//   ring (one wave holds the triangle, 4-7 tile columns, 16-byte aligned x, n >= 64):
+//     (not for a handful of rows: the ring's pre-decremented 32-bit lane offsets assume 16 columns x ld x 8 bytes >= 1 KiB per
+//     fragment, i.e. ld >= 8 -- a 1-row shard with ld = 2 wrapped them around and read 4 GB away)
+//     scalar base where fragments 0 .. ntc-2 are whole X columns (p >= 16 (ntc - 1)) and p ld 8 + 65536 < 2^32; the strips (1: at
+//     most 4 real columns in the last tile row, 2: at most 8) exist in that form only.  Else 64-bit lane pointers.
+//   shared-slab / one-read (more than 7 tile columns, aligned, n >= 64): lane offsets within one tile column, 16 ld 8 < 2^32.
+//   everything else: gram_tri_kernel (the triangle fits one wave) or gram_blk_kernel, 64-bit addresses throughout.
+GramForm gram_form(const GramPlan &pl, int64_t n, int64_t ld, bool aligned)
+{
+    GramForm f;
+    f.strips = 0;
+    if (pl.tri) {
+        f.form = GRAM_FORM_TRI;
+        if (aligned && pl.ntc >= 4 && n >= 64) {
+            // real columns in the last tile row -> strip sub-blocks (0: the last row stays on 16x16x4 tiles)
+            const int rem = pl.p + 2 - 16 * (pl.ntc - 1);
+            // scalar-base addressing needs fragments 0 .. ntc-2 to be whole X columns and every lane offset to fit 32 bits
+            const bool saddr = pl.p >= 16 * (pl.ntc - 1) && (double)pl.p * (double)ld * 8.0 + 65536.0 < 4294967296.0;
+            f.form = saddr ? GRAM_FORM_RING_SADDR : GRAM_FORM_RING_LANE;
+            f.strips = !saddr ? 0 : (rem <= 4 ? 1 : (rem <= 8 ? 2 : 0));
+        }
+        return f;
+    }
+    if (aligned && n >= 64 && (double)ld * 16.0 * 8.0 < 4294967296.0)   // 32-bit lane offsets within a tile
+        f.form = !pl.wd ? GRAM_FORM_SB : (pl.wd_units > 1 ? GRAM_FORM_WD_UNITS : (pl.wd == 3 ? GRAM_FORM_WD3 : GRAM_FORM_WD4));
+    else
+        f.form = GRAM_FORM_BLK;
+    return f;
+}
+
 template <bool ALIGNED>
 static int launch_gram_t(hipStream_t s, const GramPlan &pl, const double *x, const double *y, const double *sums,
                          double *tpart, double *vpart, const GramDims &a)
 {
     const size_t tile_bytes = 256 * sizeof(double);
+    const GramForm gf = gram_form(pl, a.n, a.ld, ALIGNED);
 #define OEM_TRI(NT)                                                                                       \
     case NT: {                                                                                            \
         size_t sh = (size_t)(NT * (NT + 1) / 2) * tile_bytes;                                             \
@@ -956,18 +990,13 @@ static int launch_gram_t(hipStream_t s, const GramPlan &pl, const double *x, con
         hipLaunchKernelGGL((gram_tri_kernel<NT, ALIGNED>), dim3(pl.nchunk), dim3(256), sh, s, x, y, sums, tpart, vpart, a);          \
         break;                                                                                            \
     }
-    // 16-byte aligned X with at least 4 tile columns: the LDS-DMA ring form
-    // (not for a handful of rows: the ring's pre-decremented 32-bit lane offsets assume 16 columns x ld x 8 bytes >= 1 KiB per
-    // fragment, i.e. ld >= 8 -- a 1-row shard with ld = 2 wrapped them around and read 4 GB away)
-    if (pl.tri && ALIGNED && pl.ntc >= 4 && a.n >= 64) {
+    // the LDS-DMA ring form (gram_form: aligned only)
+    if (gf.form == GRAM_FORM_RING_SADDR || gf.form == GRAM_FORM_RING_LANE) {
         size_t sh = (size_t)pl.ntile * tile_bytes;
         const size_t rb = (size_t)4 * 5 * pl.ntc * 1024;                         // 4 waves x NSLOT x NF KiB ring
         if (sh < rb) sh = rb;
-        // real columns in the last tile row -> strip sub-blocks (0: the last row stays on 16x16x4 tiles)
-        const int rem = pl.p + 2 - 16 * (pl.ntc - 1);
-        // scalar-base addressing needs fragments 0 .. ntc-2 to be whole X columns and every lane offset to fit 32 bits
-        const bool saddr = pl.p >= 16 * (pl.ntc - 1) && (double)pl.p * (double)a.ld * 8.0 + 65536.0 < 4294967296.0;
-        const int sb = !saddr ? 0 : (rem <= 4 ? 1 : (rem <= 8 ? 2 : 0));
+        const bool saddr = gf.form == GRAM_FORM_RING_SADDR;
+        const int sb = gf.strips;
 #define OEM_RING(NT, SB, SA)                                                                                                   \
     if (pl.ntc == NT && sb == SB && saddr == SA) {                                                                             \
         if (sh > 64 * 1024 && lds_limit_once(reinterpret_cast<const void *>(&gram_ring_kernel<NT, SB, SA>), sh)) return OEMGPU_ERR_HIP; \
@@ -987,7 +1016,7 @@ static int launch_gram_t(hipStream_t s, const GramPlan &pl, const double *x, con
         default: set_error("gram: bad tile count %d", pl.ntc); return OEMGPU_ERR_INTERNAL;
         }
     } else {
-        if (ALIGNED && a.n >= 64 && (double)a.ld * 16.0 * 8.0 < 4294967296.0) {   // 32-bit lane offsets within a tile
+        if (gf.form != GRAM_FORM_BLK) {                                           // 32-bit lane offsets within a tile (gram_form: aligned only)
             if (pl.wd) return launch_gram_wd(s, pl, x, y, sums, tpart, vpart, a);
             return launch_gram_sb(s, pl, x, y, sums, tpart, vpart, a);
         }
