@@ -272,16 +272,47 @@ def _xval_rowmajor_in_place(x):
     return _logistic_rowmajor_in_place(x)
 
 
-def _rowmajor_args(x, y):
+class _DeviceX:
+    """A torch device matrix as the C entries take it.  `policy` (_rowmajor_in_place, _logistic_rowmajor_in_place or
+    _xval_rowmajor_in_place) says whether the _rm_dev entry reads x where it lies -- `code` is then its dtype code, `ld` the row stride
+    -- or the _dev entry reads a column-major float64 matrix (_device_matrix: x itself, or the one copy): `code` is None, `ld` the
+    column stride.  `keep` holds the memory behind `ptr`; `resident` is the n x p tensor over it."""
+
+    def __init__(self, x, policy):
+        self.code = policy(x)
+        if self.code is None:
+            self.ptr, self.n, self.p, self.ld, self.keep = _device_matrix(x)
+        else:
+            (self.n, self.p), self.ptr, self.ld, self.keep = x.shape, x.data_ptr(), x.stride(0), x
+
+    @property
+    def resident(self):                                                # (made when asked for: a torch call per fit is host time per fit)
+        if self.code is not None:
+            return self.keep
+        return self.keep.as_strided((self.n, self.p), (1, self.ld), self.keep.storage_offset())
+
+    def call(self, stem, ctx, *rest):
+        """oemgpu_<stem>_dev(ctx, x, n, ld, p, *rest), or oemgpu_<stem>_rm_dev(ctx, x, dtype, n, ldr, p, *rest) on a row-major x"""
+        if self.code is None:
+            return L.check(getattr(L.lib(), f"oemgpu_{stem}_dev")(ctx, self.ptr, self.n, self.ld, self.p, *rest))
+        return L.check(getattr(L.lib(), f"oemgpu_{stem}_rm_dev")(ctx, self.ptr, self.code, self.n, self.ld, self.p, *rest))
+
+
+def _device_y(y, device):
+    """y as a contiguous float64 device vector: a host y goes to `device`, a device tensor stays where it is"""
     import torch
+    yd = y if _is_torch_cuda(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=device)
+    return yd.to(torch.float64).contiguous().reshape(-1)
+
+
+def _rowmajor_args(x, y):
     if not _is_torch_cuda(x):
         raise ValueError("x must be a torch tensor on a GPU")
     code = _rowmajor_dtype(x)
     if code is None:
         raise ValueError("x must be float64 or float32 with unit column stride and a row stride of at least p")
     n, p = x.shape
-    yd = y if _is_torch_cuda(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=x.device)
-    yd = yd.to(torch.float64).contiguous().reshape(-1)
+    yd = _device_y(y, x.device)
     if yd.shape[0] != n:
         raise ValueError("x and y lengths do not match")
     return code, n, p, yd
@@ -461,20 +492,11 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
         return _decorate(a, penalty, varnames, True, n, p)
     if _is_torch_cuda(x):
         import torch
-        rm = _rowmajor_in_place(x)
-        if rm is None:
-            xp, n_, p_, ld, keep = _device_matrix(x)
-        yd = y if _is_torch_cuda(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=x.device)
-        yd = yd.to(torch.float64).contiguous().reshape(-1)
+        X = _DeviceX(x, _rowmajor_in_place)                            # read where it lies (no float64 copy, no transposed copy) where that serves
+        yd = _device_y(y, x.device)
         ctx = context(x.device.index)
         torch.cuda.current_stream(x.device).synchronize()
-        if rm is not None:                                             # read where it lies: no float64 copy, no transposed copy
-            L.check(lib.oemgpu_fit_dense_rm_dev(ctx, x.data_ptr(), rm, n, x.stride(0), p, yd.data_ptr(), int(bool(standardize)),
-                                                int(bool(intercept)), C.byref(a.c), *a.outputs(p + 1)))
-        else:
-            L.check(lib.oemgpu_fit_dense_dev(ctx, xp, n, ld, p, yd.data_ptr(), int(bool(standardize)), int(bool(intercept)),
-                                             C.byref(a.c), *a.outputs(p + 1)))
-            del keep
+        X.call("fit_dense", ctx, yd.data_ptr(), int(bool(standardize)), int(bool(intercept)), C.byref(a.c), *a.outputs(p + 1))
     else:
         xh = np.asfortranarray(x, dtype=np.float64)
         yh = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
@@ -542,31 +564,17 @@ def oem_fit_logistic_dense(x, y, penalty=None, weights=(), lambda_=(), nlambda=1
     lib = L.lib()
     if _is_torch_cuda(x):
         import torch
-        rm = _logistic_rowmajor_in_place(x)
-        keep = None
-        if rm is None:
-            xp, n_, p_, ld, keep = _device_matrix(x)
+        X = _DeviceX(x, _logistic_rowmajor_in_place)                   # row-major float64 / float32: read where it lies
         yd = torch.as_tensor(yh, device=x.device) if _fold is None else _fold[3]
         ctx = context(x.device.index)
         torch.cuda.current_stream(x.device).synchronize()
         scal = (int(bool(standardize)), int(bool(intercept)), hf, int(irls_maxit), float(irls_tol), C.byref(a.c))
-        if rm is not None and _fold is None:                           # row-major float64 / float32: read where it lies
-            L.check(lib.oemgpu_fit_logistic_dense_rm_dev(ctx, x.data_ptr(), rm, n, x.stride(0), p, yd.data_ptr(), *scal, *a.outputs(p + 1)))
-        elif rm is not None:
-            fd, nfolds, leave_out = _fold[:3]
-            L.check(lib.oemgpu_fit_logistic_dense_fold_rm_dev(ctx, x.data_ptr(), rm, n, x.stride(0), p, yd.data_ptr(), fd.data_ptr(), int(nfolds),
-                                                              int(leave_out), *scal, *a.outputs(p + 1)))
-            n = int(n - (fd == int(leave_out)).sum().item())
-        elif _fold is None:
-            L.check(lib.oemgpu_fit_logistic_dense_dev(ctx, xp, n, ld, p, yd.data_ptr(), int(bool(standardize)), int(bool(intercept)), hf,
-                                                      int(irls_maxit), float(irls_tol), C.byref(a.c), *a.outputs(p + 1)))
+        if _fold is None:
+            X.call("fit_logistic_dense", ctx, yd.data_ptr(), *scal, *a.outputs(p + 1))
         else:
             fd, nfolds, leave_out = _fold[:3]
-            L.check(lib.oemgpu_fit_logistic_dense_fold_dev(ctx, xp, n, ld, p, yd.data_ptr(), fd.data_ptr(), int(nfolds), int(leave_out),
-                                                           int(bool(standardize)), int(bool(intercept)), hf, int(irls_maxit), float(irls_tol),
-                                                           C.byref(a.c), *a.outputs(p + 1)))
+            X.call("fit_logistic_dense_fold", ctx, yd.data_ptr(), fd.data_ptr(), int(nfolds), int(leave_out), *scal, *a.outputs(p + 1))
             n = int(n - (fd == int(leave_out)).sum().item())
-        del keep
     else:
         xh = np.asfortranarray(x, dtype=np.float64)
         if _fold is not None:
@@ -922,24 +930,14 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
                                        _dptr(cvm), _dptr(cvsd)))
     elif _is_torch_cuda(x):
         import torch
-        rm = _xval_rowmajor_in_place(x)
-        if rm is None:
-            xp, n_, p_, ld, keep = _device_matrix(x)
-        yd = y if _is_torch_cuda(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=x.device)
-        yd = yd.to(torch.float64).contiguous().reshape(-1)
+        X = _DeviceX(x, _xval_rowmajor_in_place)                   # row-major: the rows go into fold order from where they lie, no copies
+        yd = _device_y(y, x.device)
         fd = torch.as_tensor(fid, device=x.device)
         wd = None if wh is None else torch.as_tensor(wh, device=x.device)
         ctx = context(x.device.index)
         torch.cuda.current_stream(x.device).synchronize()
-        if rm is not None:                                         # the rows go into fold order from where they lie: no float64 copy, no transposed copy
-            L.check(lib.oemgpu_xval_dense_rm_dev(ctx, x.data_ptr(), rm, n, x.stride(0), p, yd.data_ptr(), None if wd is None else wd.data_ptr(),
-                                                 fd.data_ptr(), int(nfolds), int(bool(standardize)),
-                                                 int(bool(intercept)), tm, C.byref(a.c), *out, _dptr(cvm), _dptr(cvsd)))
-        else:
-            L.check(lib.oemgpu_xval_dense_dev(ctx, xp, n, ld, p, yd.data_ptr(), None if wd is None else wd.data_ptr(), fd.data_ptr(),
-                                              int(nfolds), int(bool(standardize)),
-                                              int(bool(intercept)), tm, C.byref(a.c), *out, _dptr(cvm), _dptr(cvsd)))
-            del keep
+        X.call("xval_dense", ctx, yd.data_ptr(), None if wd is None else wd.data_ptr(), fd.data_ptr(), int(nfolds), int(bool(standardize)),
+               int(bool(intercept)), tm, C.byref(a.c), *out, _dptr(cvm), _dptr(cvsd))
     else:
         xh = np.asfortranarray(x, dtype=np.float64)
         yh = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
@@ -1124,14 +1122,8 @@ def logistic_cv_score(x, y, foldid, nfolds, coef, y_hi=None, predmat=False):
     the ncol x n device tensor the kernel wrote (column c = row c; rows of no fold stay NaN) and nothing is copied to the host."""
     import torch
     sparse = isinstance(x, SparseX)
-    if sparse:
-        (n, p), keepalive = x.shape, None
-    else:
-        rm = _logistic_rowmajor_in_place(x)
-        if rm is None:
-            xp, n, p, ld, keepalive = _device_matrix(x)
-        else:                                                          # row-major float64 / float32: scored where it lies
-            (n, p), keepalive = x.shape, None
+    X = None if sparse else _DeviceX(x, _logistic_rowmajor_in_place)   # row-major float64 / float32: scored where it lies
+    n, p = x.shape
     coef = np.ascontiguousarray(coef, dtype=np.float64)
     if coef.ndim != 3 or coef.shape[0] != int(nfolds) or coef.shape[2] != p + 1:
         raise ValueError("coef must be nfolds x ncol x (p + 1)")
@@ -1146,15 +1138,9 @@ def logistic_cv_score(x, y, foldid, nfolds, coef, y_hi=None, predmat=False):
         L.check(L.lib().oemgpu_logistic_cv_score_sparse_res(context(x.device.index), x.handle, y.data_ptr(), float(y_hi), foldid.data_ptr(),
                                                             int(nfolds), _dptr(coef), ncol, _dptr(sums),
                                                             counts.ctypes.data_as(C.POINTER(C.c_int64)), None if pm is None else pm.data_ptr()))
-    elif rm is not None:
-        L.check(L.lib().oemgpu_logistic_cv_score_rm_dev(context(x.device.index), x.data_ptr(), rm, n, x.stride(0), p, y.data_ptr(), float(y_hi),
-                                                        foldid.data_ptr(), int(nfolds), _dptr(coef), ncol, _dptr(sums),
-                                                        counts.ctypes.data_as(C.POINTER(C.c_int64)), None if pm is None else pm.data_ptr()))
     else:
-        L.check(L.lib().oemgpu_logistic_cv_score_dev(context(x.device.index), xp, n, ld, p, y.data_ptr(), float(y_hi), foldid.data_ptr(), int(nfolds),
-                                                     _dptr(coef), ncol, _dptr(sums), counts.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                     None if pm is None else pm.data_ptr()))
-    del keepalive
+        X.call("logistic_cv_score", context(x.device.index), y.data_ptr(), float(y_hi), foldid.data_ptr(), int(nfolds), _dptr(coef), ncol,
+               _dptr(sums), counts.ctypes.data_as(C.POINTER(C.c_int64)), None if pm is None else pm.data_ptr())
     if isinstance(predmat, str):
         if predmat != "device":
             raise ValueError("predmat must be True, False or \"device\"")
@@ -1246,12 +1232,8 @@ def _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, fold
                 return oem_fit_logistic_sparse(sx, yh, penalty=penalty, lambda_=lam_arg, _fold=(sx, fd, max(int(nfolds), 3), leave_out, yd), **kw)
             return _cv_oem_binomial_on(fit, lambda fd, nfolds, coef, **k: logistic_cv_score(sx, yd, fd, nfolds, coef, **k), sx.device,
                                        n, p, yh, penalty, type_measure, nfolds, foldid, grouped, keep, rng, yd)
-    if _is_torch_cuda(x) and _logistic_rowmajor_in_place(x) is not None:
-        xd = x                                                         # row-major float64 / float32: every pass reads it where it lies
-    elif _is_torch_cuda(x):
-        xd = x if x.dtype == torch.float64 else x.to(torch.float64)
-        if not (xd.stride(0) == 1 and xd.stride(1) >= n):
-            xd = xd.t().contiguous().t()                               # column-major, once
+    if _is_torch_cuda(x):                                              # row-major float64 / float32: as it lies; else column-major, once
+        xd = _DeviceX(x, _logistic_rowmajor_in_place).resident
     else:
         xd = torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float64).T), device="cuda").t()     # the one upload
     yd = torch.as_tensor(yh, device=xd.device)
@@ -1388,11 +1370,8 @@ def _cv_gaussian_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw):
     import torch
     n, p = x.shape
     a, varnames, standardize, intercept = oem(x, y, penalty=penalty, lambda_=lam_arg, _args_only=True, **kw)
-    rm = _xval_rowmajor_in_place(x)
-    if rm is None:
-        xp, _, _, ld, keepalive = _device_matrix(x)
-    yd = y if _is_torch_cuda(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=x.device)
-    yd = yd.to(torch.float64).contiguous().reshape(-1)
+    X = _DeviceX(x, _xval_rowmajor_in_place)                       # row-major: the rows go into fold order from where they lie
+    yd = _device_y(y, x.device)
     fd = torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=x.device)
     ctx = context(x.device.index)
     K, npen, nl = int(nfolds), a.npen, a.nl
@@ -1402,12 +1381,7 @@ def _cv_gaussian_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw):
     d, fold_n = np.zeros(K), np.zeros(K, dtype=np.int64)
     torch.cuda.current_stream(x.device).synchronize()
     outs = (C.byref(a.c), _dptr(beta), _dptr(lam_out), _iptr(niter), _dptr(loss), _dptr(d), fold_n.ctypes.data_as(C.POINTER(C.c_int64)))
-    if rm is not None:                                             # the rows go into fold order from where they lie (oemgpu_cv_fold_fits_rm_dev)
-        L.check(L.lib().oemgpu_cv_fold_fits_rm_dev(ctx, x.data_ptr(), rm, n, x.stride(0), p, yd.data_ptr(), fd.data_ptr(), K, int(standardize),
-                                                   int(intercept), *outs))
-    else:
-        L.check(L.lib().oemgpu_cv_fold_fits_dev(ctx, xp, n, ld, p, yd.data_ptr(), fd.data_ptr(), K, int(standardize), int(intercept), *outs))
-        del keepalive
+    X.call("cv_fold_fits", ctx, yd.data_ptr(), fd.data_ptr(), K, int(standardize), int(intercept), *outs)
     outlist = [_decorate(types.SimpleNamespace(beta=beta[i], lam_out=lam_out[i], niter=niter[i], loss=loss[i],
                                                d=types.SimpleNamespace(value=float(d[i]))), penalty, varnames, True, int(n - fold_n[i]), p)
                for i in range(K)]
@@ -1442,8 +1416,7 @@ def _cv_gaussian_sparse_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw):
         i = int(np.argmax(kept <= p))
         raise ValueError(f"cv.oem on a SparseX: fold {i + 1} leaves {int(kept[i])} rows for {p} columns (a fit of p >= n is not served here)")
     a, varnames, standardize, intercept = oem(x, y, penalty=penalty, lambda_=lam_arg, _args_only=True, **kw)
-    yd = y if _is_torch_cuda(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=x.device)
-    yd = yd.to(device=x.device, dtype=torch.float64).contiguous().reshape(-1)
+    yd = _device_y(y, x.device).to(x.device)
     fd = torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=x.device)
     ctx = context(x.device.index)
     K, npen, nl = int(nfolds), a.npen, a.nl

@@ -3,6 +3,7 @@
 // (lambda bookkeeping, result packing, DataStd::recover).  All arithmetic of the hot path runs in the HIP
 // kernels of gram.hip / path_small.hip / path_large.hip; there is no CPU fallback.
 #include "ctx.hpp"
+#include "dense_src.hpp"
 #include "logistic.hpp"     // oemgpu_sparse_x
 
 #include <atomic>
@@ -1098,6 +1099,73 @@ int shard_moments(oemgpu_ctx *c, const GramPlan &pl, const double *x, int64_t n,
     return launch_moments_reduce(c->stream, pl, tpart, vpart, moments);
 }
 
+// ---------------------------------------------------------------- where a dense x lies (dense_src.hpp)
+static_assert(GRAM_RM_P_MAX == OEMGPU_RM_P_MAX, "the header's limit is the kernel's");
+
+int dense_src_check(const char *who, const DenseSrc &X, int64_t n, int32_t p)
+{
+    if (X.colmajor()) {
+        if (X.ld < n) { set_error("%s: ld < n", who); return OEMGPU_ERR_ARG; }
+        return 0;
+    }
+    if (X.dtype != OEMGPU_F64 && X.dtype != OEMGPU_F32) { set_error("%s: dtype is neither OEMGPU_F64 nor OEMGPU_F32", who); return OEMGPU_ERR_ARG; }
+    if (X.ld < p) { set_error("%s: ldr < p", who); return OEMGPU_ERR_ARG; }
+    const int el = X.dtype == OEMGPU_F32 ? 4 : 8;              // (every row-major kernel loads one element per lane)
+    if ((uintptr_t)X.x % el) { set_error("%s: x_dev is not aligned to its %d-byte elements", who, el); return OEMGPU_ERR_ARG; }
+    return 0;
+}
+
+int dense_src_shift_sums(hipStream_t s, const DenseSrc &X, int64_t n, int p, const double *y, double *sums)
+{
+    if (X.colmajor()) return launch_shift_sums(s, X.cm(), n, X.ld, p, y, sums);
+    return launch_shift_sums_rm(s, X.x, X.dtype, n, X.ld, p, y, sums);
+}
+
+int dense_src_gather(hipStream_t s, const DenseSrc &X, int64_t n, int p, const double *y, const int32_t *foldid, int K, const int *pos,
+                     double *xo, int64_t ldo, double *yo)
+{
+    if (X.colmajor()) return launch_gather_rows(s, X.cm(), n, X.ld, p, y, pos, xo, ldo, yo);
+    return launch_gather_rows_rm(s, X.x, X.dtype, n, X.ld, p, y, foldid, K, pos, xo, ldo, yo);
+}
+
+static int rm_p_refusal(const char *who, int32_t p)
+{
+    if (p <= GRAM_RM_P_MAX) return 0;
+    set_error("%s: the row-major pass takes p <= %d; larger p takes the column-major entry (oemgpu_fit_dense_dev / oemgpu_moments_dev)", who, GRAM_RM_P_MAX);
+    return OEMGPU_ERR_UNSUPPORTED;
+}
+
+int dense_src_moment_plan(const char *who, const oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, MomentPlan *pl)
+{
+    Bump B;
+    if (X.colmajor()) {
+        pl->cm = gram_plan(n, p, c->num_cu);
+        B.take(pl->cm.tpart_doubles * 8); B.take(pl->cm.vpart_doubles * 8);
+    } else {
+        if (int rc = rm_p_refusal(who, p)) return rc;
+        pl->rm = gram_rm_plan(n, p, c->num_cu);
+        B.take(pl->rm.tpart_doubles * 8);
+    }
+    pl->scratch_bytes = B.off;
+    return 0;
+}
+
+int dense_src_moments(oemgpu_ctx *c, const MomentPlan &pl, const DenseSrc &X, int64_t n, const double *y, const double *sums, char *scratch,
+                      double *moments)
+{
+    double *tpart = (double *)scratch;
+    if (X.colmajor()) {
+        Bump B; B.take(pl.cm.tpart_doubles * 8);
+        return shard_moments(c, pl.cm, X.cm(), n, X.ld, y, sums, tpart, (double *)(scratch + B.off), moments);
+    }
+    {
+        Timer t(c, OEMGPU_T_GRAMK);
+        int rc = launch_gram_rm(c->stream, pl.rm, X.x, X.dtype, n, X.ld, y, sums, tpart);
+        if (rc) return rc;
+    }
+    return launch_gram_rm_reduce(c->stream, pl.rm, tpart, moments);
+}
+
 // self-test aid: `blocks` workgroups that each take a whole CU (150 KB of LDS) and spin for `ms` milliseconds of device time
 __global__ __launch_bounds__(256) void hold_cus_kernel(unsigned long long ticks, int *sink)
 {
@@ -1366,26 +1434,56 @@ int oemgpu_last_timings(oemgpu_ctx *c, double *ms)
 }
 
 // ---------------------------------------------------------------------------------------------- staged interface
+// what every entry below asks of (c, x, y, n, p) and of where x lies, in the called entry's name; no device work
+static int src_args_check(const char *who, const oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const void *y_dev, bool outputs)
+{
+    if (!c || !X.x || !y_dev || !outputs) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    if (n < 1 || p < 1) { set_error("%s: bad n / p (n >= 1, p >= 1)", who); return OEMGPU_ERR_ARG; }
+    return dense_src_check(who, X, n, p);
+}
+
+static int shift_sums_src(const char *who, oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const double *y_dev, double *sums_dev)
+{
+    if (int rc = src_args_check(who, c, X, n, p, y_dev, sums_dev != nullptr)) return rc;
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    Timer t(c, OEMGPU_T_SHIFT);
+    return dense_src_shift_sums(c->stream, X, n, p, y_dev, sums_dev);
+}
+
 int oemgpu_shift_sums_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
                           double *sums_dev)
 {
-    if (!c || !x_dev || !y_dev || !sums_dev || n < 1 || p < 1 || ld < n) { set_error("shift_sums: bad argument"); return OEMGPU_ERR_ARG; }
+    return shift_sums_src("shift_sums", c, dense_src_cm(x_dev, ld), n, p, y_dev, sums_dev);
+}
+
+int oemgpu_shift_sums_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                             double *sums_dev)
+{
+    return shift_sums_src("shift_sums_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, sums_dev);
+}
+
+static int moments_src(const char *who, oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const double *y_dev, const double *sums_dev,
+                       double *moments_dev)
+{
+    if (int rc = src_args_check(who, c, X, n, p, y_dev, moments_dev != nullptr)) return rc;
+    MomentPlan pl;
+    if (int rc = dense_src_moment_plan(who, c, X, n, p, &pl)) return rc;
     if (set_device(c)) return OEMGPU_ERR_HIP;
-    Timer t(c, OEMGPU_T_SHIFT);
-    return launch_shift_sums(c->stream, x_dev, n, ld, p, y_dev, sums_dev);
+    if (ctx_reserve(c, pl.scratch_bytes)) return OEMGPU_ERR_HIP;
+    Timer t(c, OEMGPU_T_MOMENTS);
+    return dense_src_moments(c, pl, X, n, y_dev, sums_dev, c->ws, moments_dev);
 }
 
 int oemgpu_moments_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
                        const double *sums_dev, double *moments_dev)
 {
-    if (!c || !x_dev || !y_dev || !moments_dev || n < 1 || p < 1 || ld < n) { set_error("moments: bad argument"); return OEMGPU_ERR_ARG; }
-    if (set_device(c)) return OEMGPU_ERR_HIP;
-    const GramPlan pl = gram_plan(n, p, c->num_cu);
-    Bump B;
-    const size_t a_t = B.take(pl.tpart_doubles * 8), a_v = B.take(pl.vpart_doubles * 8);
-    if (ctx_reserve(c, B.off)) return OEMGPU_ERR_HIP;
-    Timer t(c, OEMGPU_T_MOMENTS);
-    return shard_moments(c, pl, x_dev, n, ld, y_dev, sums_dev, (double *)(c->ws + a_t), (double *)(c->ws + a_v), moments_dev);
+    return moments_src("moments", c, dense_src_cm(x_dev, ld), n, p, y_dev, sums_dev, moments_dev);
+}
+
+int oemgpu_moments_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                          const double *sums_dev, double *moments_dev)
+{
+    return moments_src("moments_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, sums_dev, moments_dev);
 }
 
 static int run_paths_parts(oemgpu_ctx *c, Bump B, const double *xx, const double *xy, const double *st, int p, int q, int sem, int standardize, int intercept,
@@ -1541,30 +1639,48 @@ static int run_paths_parts(oemgpu_ctx *c, Bump B, const double *xx, const double
     return 0;
 }
 
-static int fit_dense_wide_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
-                              int32_t standardize, int32_t intercept, const oemgpu_opts *o,
-                              double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+// The workspace of "moments, then solve": behind the `frame` bytes the solve must find intact (sums, moments) lies the moment pass's
+// scratch (up to pass_end), and later, over it, solve_moments_impl's own frame -- the q x q matrix, xy, stats, the engines' -- plus `extra`
+static size_t moments_solve_ws(size_t frame, size_t pass_end, int32_t p, const oemgpu_opts *o, size_t extra = 0)
 {
-    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const size_t solve = frame + ((size_t)p * p + p + stats_len(p)) * 8 + 1024 + paths_ws_bytes(p, p, o) + extra + 4096;
+    return solve > pass_end ? solve : pass_end;
+}
+
+// The wide engine's staging in aux (whatever cv.oem's layout stamp vouched for is void): the blocked standardised copy xs, ys and the
+// engine's scratch, and the WideArgs that name them.  The caller fills xs / ys (launch_wide_standardize) through the writable
+// pointers handed back: WideArgs holds them const, as the engines read them.
+static int wide_stage(oemgpu_ctx *c, int64_t n, int32_t p, WideArgs *wd, double **xs, double **ys)
+{
     const WideLayout lay = wide_layout(n);
     Bump X;
     const size_t a_xs = X.take(sizeof(double) * (size_t)lay.rows() * p), a_ys = X.take(sizeof(double) * (size_t)lay.rows()),
                  a_sc = X.take(sizeof(double) * wide_scratch_doubles((int)n, p));
     ctx_void_cv(c);
     if (ctx_grow(c, &c->aux, &c->aux_bytes, X.off)) return OEMGPU_ERR_HIP;
+    *xs = (double *)(c->aux + a_xs); *ys = (double *)(c->aux + a_ys);
+    wd->xs = *xs; wd->ys = *ys; wd->lay = lay; wd->n = (int)n; wd->scratch = (double *)(c->aux + a_sc);
+    return 0;
+}
+
+static int fit_dense_wide_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                              int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                              double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+{
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    WideArgs wd;
+    double *xs, *ys;
+    int rc = wide_stage(c, n, p, &wd, &xs, &ys);
+    if (rc) return rc;
     Bump B;
     const size_t a_xy = B.take((size_t)p * 8), a_st = B.take((size_t)stats_len(p) * 8);       // stats last: run_paths returns it with the outputs
     if (ctx_reserve(c, B.off + paths_ws_bytes(p, p, o) + 4096)) return OEMGPU_ERR_HIP;
-    double *xs = (double *)(c->aux + a_xs), *ys = (double *)(c->aux + a_ys);
     double *xy = (double *)(c->ws + a_xy), *st = (double *)(c->ws + a_st);
-    int rc;
     {
         Timer t(c, OEMGPU_T_MOMENTS);             // the stage that reads X: DataStd on the data (the standardised copy, X'Y / n)
-        rc = launch_wide_standardize(c->stream, x_dev, n, ld, p, y_dev, standardize, intercept, lay, xs, ys, xy, st);
+        rc = launch_wide_standardize(c->stream, x_dev, n, ld, p, y_dev, standardize, intercept, wd.lay, xs, ys, xy, st);
         if (rc) return rc;
     }
-    WideArgs wd;
-    wd.xs = xs; wd.ys = ys; wd.lay = lay; wd.n = (int)n; wd.scratch = (double *)(c->aux + a_sc);
     return run_paths_parts(c, B, nullptr, xy, st, p, p, OEMGPU_SEM_DENSE, standardize, intercept, o, beta, lambda_out, niter, loss, d, &wd, nullptr);
 }
 
@@ -1606,10 +1722,7 @@ static int fit_big_wide_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64
         const size_t a_xs2 = B.take((size_t)p * 8), a_mom = B.take((size_t)oemgpu_moments_len(p) * 8);
         const size_t frame = B.off;
         const size_t a_t = B.take(pl.tpart_doubles * 8), a_v = B.take(pl.vpart_doubles * 8);
-        size_t need = B.off;
-        const size_t need2 = frame + ((size_t)p * p + p + stats_len(p)) * 8 + 1024 + paths_ws_bytes(p, p, o) + 4096;
-        if (need2 > need) need = need2;
-        if (ctx_reserve(c, need)) return OEMGPU_ERR_HIP;
+        if (ctx_reserve(c, moments_solve_ws(frame, B.off, p, o))) return OEMGPU_ERR_HIP;
         double *mom = (double *)(c->ws + a_mom);
         {
             Timer t(c, OEMGPU_T_MOMENTS);
@@ -1622,25 +1735,19 @@ static int fit_big_wide_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64
                                 (double *)(c->ws + a_xs2));
         return (rc || !sparse_loss) ? rc : big_wide_sparse_loss(c, x_dev, n, ld, p, y_dev, o, beta, niter, loss);
     }
-    const WideLayout lay = wide_layout(n);
-    Bump X;
-    const size_t a_xs = X.take(sizeof(double) * (size_t)lay.rows() * p), a_ys = X.take(sizeof(double) * (size_t)lay.rows()),
-                 a_sc = X.take(sizeof(double) * wide_scratch_doubles((int)n, p));
-    ctx_void_cv(c);
-    if (ctx_grow(c, &c->aux, &c->aux_bytes, X.off)) return OEMGPU_ERR_HIP;
+    WideArgs wd;
+    double *xs, *ys;
+    if ((rc = wide_stage(c, n, p, &wd, &xs, &ys))) return rc;
     Bump B;
     const size_t a_xs2 = B.take((size_t)p * 8), a_xy = B.take((size_t)p * 8), a_st = B.take((size_t)stats_len(p) * 8);       // stats last (run_paths)
     if (ctx_reserve(c, B.off + paths_ws_bytes(p, p, o) + 4096)) return OEMGPU_ERR_HIP;
-    double *xs = (double *)(c->aux + a_xs), *ys = (double *)(c->aux + a_ys);
     double *xy = (double *)(c->ws + a_xy), *st = (double *)(c->ws + a_st), *xy_std = (double *)(c->ws + a_xs2);
     {
         Timer t(c, OEMGPU_T_MOMENTS);
-        rc = launch_wide_standardize(c->stream, x_dev, n, ld, p, y_dev, 0, 0, lay, xs, ys, xy, st);
+        rc = launch_wide_standardize(c->stream, x_dev, n, ld, p, y_dev, 0, 0, wd.lay, xs, ys, xy, st);
         if (!rc && standardize) rc = launch_big_wide_scales(c->stream, x_dev, n, ld, p, xy, st, xy_std);
         if (rc) return rc;
     }
-    WideArgs wd;
-    wd.xs = xs; wd.ys = ys; wd.lay = lay; wd.n = (int)n; wd.scratch = (double *)(c->aux + a_sc);
     rc = run_paths_parts(c, B, nullptr, xy, st, p, p, OEMGPU_SEM_BIG, standardize, 0, o, beta, lambda_out, niter, loss, d, &wd, standardize ? xy_std : nullptr);
     return (rc || !sparse_loss) ? rc : big_wide_sparse_loss(c, x_dev, n, ld, p, y_dev, o, beta, niter, loss);
 }
@@ -1660,35 +1767,39 @@ static int fit_big_wide_host(const double *x, int64_t n, int32_t p, const double
     return rc;
 }
 
-int oemgpu_fit_dense_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+// oem() on a dense x wherever it lies: moments about 0, the solve, and -- only when finalize advises a shift -- the sample sums, the
+// moments about them and the solve again
+static int fit_dense_src(const char *who, oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const double *y_dev,
                          int32_t standardize, int32_t intercept, const oemgpu_opts *o,
                          double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
 {
     HT(0);
-    if (!c || !x_dev || !y_dev) { set_error("fit_dense: NULL argument"); return OEMGPU_ERR_ARG; }
-    int rc = check_opts(o, p, p);
+    int rc = src_args_check(who, c, X, n, p, y_dev, beta && lambda_out && niter && loss && d);
+    if (!rc) rc = check_opts(o, p, p);
     if (rc) return rc;
-    if (n < 1 || ld < n) { set_error("fit_dense: bad n / ld"); return OEMGPU_ERR_ARG; }
     // p >= n (ref src/oem_dense.h:476-482,513-521: d from XXt / n, u = X'(Y - X b)/n + d b): the reference's own form where it
     // pays (wide_pays), else the same iteration on the Gram: the non-zero spectra of XXt and XtX coincide and
     // X'(Y - X b)/n + d b = (dI - X'X/n) b + X'Y/n.
-    if (wide_pays(n, p, o)) return fit_dense_wide_dev(c, x_dev, n, ld, p, y_dev, standardize, intercept, o, beta, lambda_out, niter, loss, d);
+    if (wide_pays(n, p, o)) {
+        if (X.colmajor()) return fit_dense_wide_dev(c, X.cm(), n, X.ld, p, y_dev, standardize, intercept, o, beta, lambda_out, niter, loss, d);
+        set_error("%s: %lld x %d is a shape of the p >= n engines, which read a column-major x: it takes the column-major entry "
+                  "(oemgpu_fit_dense_dev)", who, (long long)n, p);
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    MomentPlan pl;
+    if ((rc = dense_src_moment_plan(who, c, X, n, p, &pl))) return rc;
     if (set_device(c)) return OEMGPU_ERR_HIP;
-    const GramPlan pl = gram_plan(n, p, c->num_cu);
     Bump B;
     const size_t a_sums = B.take((size_t)oemgpu_sums_len(p) * 8), a_mom = B.take((size_t)oemgpu_moments_len(p) * 8);
     const size_t frame = B.off;
-    const size_t a_t = B.take(pl.tpart_doubles * 8), a_v = B.take(pl.vpart_doubles * 8);
-    size_t need = B.off;
-    const size_t need2 = frame + ((size_t)p * p + p + stats_len(p)) * 8 + 1024 + paths_ws_bytes(p, p, o) + 4096;
-    if (need2 > need) need = need2;
-    if (ctx_reserve(c, need)) return OEMGPU_ERR_HIP;
+    const size_t a_scr = B.take(pl.scratch_bytes);
+    if (ctx_reserve(c, moments_solve_ws(frame, B.off, p, o))) return OEMGPU_ERR_HIP;
     double *sums = (double *)(c->ws + a_sums), *mom = (double *)(c->ws + a_mom);
     // Moments about 0 first: that is what the shift predicate yields unless some column has |mean| > 16 sd, and finalize tells
     // (from the full-data moments) when it was the wrong guess.  The sample pass and the shifted pass then run only for such data.
     {
         Timer t(c, OEMGPU_T_MOMENTS);
-        rc = shard_moments(c, pl, x_dev, n, ld, y_dev, nullptr, (double *)(c->ws + a_t), (double *)(c->ws + a_v), mom);
+        rc = dense_src_moments(c, pl, X, n, y_dev, nullptr, c->ws + a_scr, mom);
         if (rc) return rc;
     }
     HT(1);
@@ -1699,124 +1810,39 @@ int oemgpu_fit_dense_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t 
     if (rc || !c->shift_advised) return rc;
     {
         Timer t(c, OEMGPU_T_SHIFT);
-        rc = launch_shift_sums(c->stream, x_dev, n, ld, p, y_dev, sums);
+        rc = dense_src_shift_sums(c->stream, X, n, p, y_dev, sums);
         if (rc) return rc;
     }
     {
         Timer t(c, OEMGPU_T_MOMENTS);
-        rc = shard_moments(c, pl, x_dev, n, ld, y_dev, sums, (double *)(c->ws + a_t), (double *)(c->ws + a_v), mom);
+        rc = dense_src_moments(c, pl, X, n, y_dev, sums, c->ws + a_scr, mom);
         if (rc) return rc;
     }
     return oemgpu_solve_moments_dev(c, mom, sums, p, OEMGPU_SEM_DENSE, standardize, intercept, o, beta, lambda_out, niter, loss, d);
 }
 
-// ---------------------------------------------------------------------------------------------- row-major x (gram_rm.hip)
-static_assert(GRAM_RM_P_MAX == OEMGPU_RM_P_MAX, "the header's limit is the kernel's");
-
-static int rm_check(const char *who, const oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const void *y_dev)
+int oemgpu_fit_dense_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                         int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                         double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
 {
-    if (!c || !x_dev || !y_dev) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
-    if (dtype != OEMGPU_F64 && dtype != OEMGPU_F32) { set_error("%s: dtype %d is neither OEMGPU_F64 nor OEMGPU_F32", who, dtype); return OEMGPU_ERR_ARG; }
-    if (n < 1 || p < 1 || ldr < p) { set_error("%s: bad n / p / ldr (n >= 1, p >= 1, ldr >= p)", who); return OEMGPU_ERR_ARG; }
-    return 0;
-}
-static int rm_check_p(const char *who, int32_t p)
-{
-    if (p <= GRAM_RM_P_MAX) return 0;
-    set_error("%s: the row-major pass takes p <= %d; larger p takes the column-major entry (oemgpu_fit_dense_dev / oemgpu_moments_dev)", who, GRAM_RM_P_MAX);
-    return OEMGPU_ERR_UNSUPPORTED;
+    return fit_dense_src("fit_dense", c, dense_src_cm(x_dev, ld), n, p, y_dev, standardize, intercept, o, beta, lambda_out, niter, loss, d);
 }
 
-// moments of a device-resident row-major x into `moments` (overwrite); the counterpart of shard_moments
-static int rm_moments(oemgpu_ctx *c, const GramRmPlan &pl, const void *x, int dtype, int64_t n, int64_t ldr, const double *y, const double *sums,
-                      double *tpart, double *moments)
+int oemgpu_fit_dense_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                            int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                            double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
 {
-    {
-        Timer t(c, OEMGPU_T_GRAMK);
-        int rc = launch_gram_rm(c->stream, pl, x, dtype, n, ldr, y, sums, tpart);
-        if (rc) return rc;
-    }
-    return launch_gram_rm_reduce(c->stream, pl, tpart, moments);
+    return fit_dense_src("fit_dense_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, standardize, intercept, o, beta, lambda_out, niter, loss, d);
 }
 
 int oemgpu_selftest_gram_rm_plan(int64_t n, int32_t p, int32_t num_cu, int64_t *out)
 {
     if (n < 1 || p < 1 || num_cu < 1 || !out) { set_error("selftest_gram_rm_plan: bad argument"); return OEMGPU_ERR_ARG; }
-    if (int rc = rm_check_p("selftest_gram_rm_plan", p)) return rc;
+    if (int rc = rm_p_refusal("selftest_gram_rm_plan", p)) return rc;
     const GramRmPlan pl = gram_rm_plan(n, p, num_cu);
     out[0] = pl.ntc; out[1] = pl.nblk; out[2] = pl.nchunk; out[3] = pl.steps; out[4] = (int64_t)pl.nchunk * pl.nblk;
     out[5] = (int64_t)pl.tpart_doubles; out[6] = (int64_t)(pl.nchunk - 1) * pl.steps * 16; out[7] = GRAM_RM_P_MAX;
     return 0;
-}
-
-int oemgpu_shift_sums_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
-                             double *sums_dev)
-{
-    if (int rc = rm_check("shift_sums_rm", c, x_dev, dtype, n, ldr, p, y_dev)) return rc;
-    if (!sums_dev) { set_error("shift_sums_rm: NULL argument"); return OEMGPU_ERR_ARG; }
-    if (set_device(c)) return OEMGPU_ERR_HIP;
-    Timer t(c, OEMGPU_T_SHIFT);
-    return launch_shift_sums_rm(c->stream, x_dev, dtype, n, ldr, p, y_dev, sums_dev);
-}
-
-int oemgpu_moments_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
-                          const double *sums_dev, double *moments_dev)
-{
-    if (int rc = rm_check("moments_rm", c, x_dev, dtype, n, ldr, p, y_dev)) return rc;
-    if (!moments_dev) { set_error("moments_rm: NULL argument"); return OEMGPU_ERR_ARG; }
-    if (int rc = rm_check_p("moments_rm", p)) return rc;
-    if (set_device(c)) return OEMGPU_ERR_HIP;
-    const GramRmPlan pl = gram_rm_plan(n, p, c->num_cu);
-    if (ctx_reserve(c, pl.tpart_doubles * 8)) return OEMGPU_ERR_HIP;
-    Timer t(c, OEMGPU_T_MOMENTS);
-    return rm_moments(c, pl, x_dev, dtype, n, ldr, y_dev, sums_dev, (double *)c->ws, moments_dev);
-}
-
-// oemgpu_fit_dense_dev with the row-major passes in place of shard_moments / launch_shift_sums
-int oemgpu_fit_dense_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
-                            int32_t standardize, int32_t intercept, const oemgpu_opts *o,
-                            double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
-{
-    int rc = rm_check("fit_dense_rm", c, x_dev, dtype, n, ldr, p, y_dev);
-    if (rc) return rc;
-    if (!beta || !lambda_out || !niter || !loss || !d) { set_error("fit_dense_rm: NULL argument"); return OEMGPU_ERR_ARG; }
-    if ((rc = check_opts(o, p, p))) return rc;
-    if (wide_pays(n, p, o)) {
-        set_error("fit_dense_rm: %lld x %d is a shape of the p >= n engines, which read a column-major x: it takes the column-major entry "
-                  "(oemgpu_fit_dense_dev)", (long long)n, p);
-        return OEMGPU_ERR_UNSUPPORTED;
-    }
-    if ((rc = rm_check_p("fit_dense_rm", p))) return rc;
-    if (set_device(c)) return OEMGPU_ERR_HIP;
-    const GramRmPlan pl = gram_rm_plan(n, p, c->num_cu);
-    Bump B;
-    const size_t a_sums = B.take((size_t)oemgpu_sums_len(p) * 8), a_mom = B.take((size_t)oemgpu_moments_len(p) * 8);
-    const size_t frame = B.off;
-    const size_t a_t = B.take(pl.tpart_doubles * 8);
-    size_t need = B.off;
-    const size_t need2 = frame + ((size_t)p * p + p + stats_len(p)) * 8 + 1024 + paths_ws_bytes(p, p, o) + 4096;
-    if (need2 > need) need = need2;
-    if (ctx_reserve(c, need)) return OEMGPU_ERR_HIP;
-    double *sums = (double *)(c->ws + a_sums), *mom = (double *)(c->ws + a_mom), *tpart = (double *)(c->ws + a_t);
-    // moments about 0 first, the sample pass and the shifted pass only when finalize advises them (as oemgpu_fit_dense_dev)
-    {
-        Timer t(c, OEMGPU_T_MOMENTS);
-        rc = rm_moments(c, pl, x_dev, dtype, n, ldr, y_dev, nullptr, tpart, mom);
-        if (rc) return rc;
-    }
-    rc = oemgpu_solve_moments_dev(c, mom, nullptr, p, OEMGPU_SEM_DENSE, standardize, intercept, o, beta, lambda_out, niter, loss, d);
-    if (rc || !c->shift_advised) return rc;
-    {
-        Timer t(c, OEMGPU_T_SHIFT);
-        rc = launch_shift_sums_rm(c->stream, x_dev, dtype, n, ldr, p, y_dev, sums);
-        if (rc) return rc;
-    }
-    {
-        Timer t(c, OEMGPU_T_MOMENTS);
-        rc = rm_moments(c, pl, x_dev, dtype, n, ldr, y_dev, sums, tpart, mom);
-        if (rc) return rc;
-    }
-    return oemgpu_solve_moments_dev(c, mom, sums, p, OEMGPU_SEM_DENSE, standardize, intercept, o, beta, lambda_out, niter, loss, d);
 }
 
 // oemDense with observation weights (weighted.hip has the algebra and the reference lines).  n > p.
@@ -1852,10 +1878,8 @@ static int fit_dense_weighted_impl(oemgpu_ctx *c, const double *x_dev, int64_t n
     const size_t a_mom = B.take((size_t)oemgpu_moments_len(p) * 8);
     const size_t frame = B.off;
     const size_t a_t = B.take(pl.tpart_doubles * 8), a_v = B.take(pl.vpart_doubles * 8);
-    size_t need = B.off;
     const size_t large_ws = wide ? path_large_work_doubles(p, 128) * 8 + 4096 : 0;      // (the launch-per-iteration engine at any p)
-    const size_t need2 = frame + ((size_t)p * p + p + stats_len(p)) * 8 + 1024 + paths_ws_bytes(p, p, o) + large_ws + 4096;
-    if (need2 > need) need = need2;
+    const size_t need = moments_solve_ws(frame, B.off, p, o, large_ws);
     if (ctx_reserve(c, need)) return OEMGPU_ERR_HIP;
     double *mom = (double *)(c->ws + a_mom);
     {
@@ -2263,24 +2287,7 @@ static int xval_check(oemgpu_ctx *c, const void *x_dev, const void *y_dev, const
 
 // phase 1: hf <- the local fold sizes [K] and fold starts [K]; mfold (and csq) in aux <- the local rows' per-fold moments
 static int xval_fold_moments(oemgpu_ctx *c, const XvalLay &L, const std::vector<int64_t> &hf, const double *sums);
-// where the rows come from: a column-major float64 x (dtype < 0, ld the column stride: launch_gather_rows) or a row-major x of
-// OEMGPU_F64 / OEMGPU_F32 elements read where it lies (ld the row stride: launch_gather_rows_rm).  Either way the fold-ordered copy
-// is column-major float64, and the same bytes for the same values.
-struct XvalSrc {
-    const void *x;
-    int dtype;
-    int64_t ld;
-};
-static XvalSrc xval_src_cm(const double *x_dev, int64_t ld) { return XvalSrc{x_dev, -1, ld}; }
-static XvalSrc xval_src_rm(const void *x_dev, int dtype, int64_t ldr) { return XvalSrc{x_dev, dtype, ldr}; }
-static int xval_gather(oemgpu_ctx *c, const XvalSrc &X, int64_t n, int p, const double *y_dev, const int32_t *foldid_dev, int K, const int *pos,
-                       double *xo, int64_t ldo, double *yo)
-{
-    if (X.dtype < 0) return launch_gather_rows(c->stream, (const double *)X.x, n, X.ld, p, y_dev, pos, xo, ldo, yo);
-    return launch_gather_rows_rm(c->stream, X.x, X.dtype, n, X.ld, p, y_dev, foldid_dev, K, pos, xo, ldo, yo);
-}
-
-static int xval_prepare(oemgpu_ctx *c, const XvalLay &L, const XvalSrc &X, const double *y_dev, const double *w_dev,
+static int xval_prepare(oemgpu_ctx *c, const XvalLay &L, const DenseSrc &X, const double *y_dev, const double *w_dev,
                         const int32_t *foldid_dev, std::vector<int64_t> &hf, bool moments = true)
 {
     const int64_t n = L.n;
@@ -2302,9 +2309,9 @@ static int xval_prepare(oemgpu_ctx *c, const XvalLay &L, const XvalSrc &X, const
         double *csq = (double *)(ax + L.a_cs);
         if (w_dev) {
             rc = launch_gather_rows(c->stream, w_dev, n, n, 1, y_dev, pos, xp, L.ldp, yp);               // column 0 <- w
-            if (!rc) rc = xval_gather(c, X, n, p, y_dev, foldid_dev, K, pos, xp + L.ldp, L.ldp, yp);
+            if (!rc) rc = dense_src_gather(c->stream, X, n, p, y_dev, foldid_dev, K, pos, xp + L.ldp, L.ldp, yp);
             if (!rc) rc = launch_weight_scale(c->stream, xp, L.ldp, yp, p, K, fold_start, fold_n, csq);
-        } else rc = xval_gather(c, X, n, p, y_dev, foldid_dev, K, pos, xp, L.ldp, yp);
+        } else rc = dense_src_gather(c->stream, X, n, p, y_dev, foldid_dev, K, pos, xp, L.ldp, yp);
         if (rc) return rc;
     }
     OEM_HIP(hipStreamSynchronize(c->stream));
@@ -2465,8 +2472,8 @@ static int xval_cverr(oemgpu_ctx *c, const XvalLay &L, int32_t type_measure, con
     return 0;
 }
 
-// X.dtype < 0: ld is the column stride (checked >= n); a row-major source was checked by rm_src_check and counts as ld = n here
-static int xval_dense_src(oemgpu_ctx *c, const XvalSrc &X, int64_t n, int32_t p, const double *y_dev,
+// xval.oem on a dense x wherever it lies: everything behind the fold-ordered copy is the same, and so are the results, bit for bit
+static int xval_dense_src(const char *who, oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const double *y_dev,
                           const double *w_dev, const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept,
                           int32_t type_measure, const oemgpu_opts *o,
                           double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, double *cvm, double *cvsd)
@@ -2475,7 +2482,8 @@ static int xval_dense_src(oemgpu_ctx *c, const XvalSrc &X, int64_t n, int32_t p,
         set_error("xval_dense: NULL argument"); return OEMGPU_ERR_ARG;
     }
     const int K = nfolds;
-    int rc = xval_check(c, X.x, y_dev, foldid_dev, n, X.dtype < 0 ? X.ld : n, p, K, intercept, type_measure, w_dev != nullptr, o);
+    int rc = dense_src_check(who, X, n, p);
+    if (!rc) rc = xval_check(c, X.x, y_dev, foldid_dev, n, n, p, K, intercept, type_measure, w_dev != nullptr, o);
     if (rc) return rc;
     if (n <= p) { set_error("dimension of x larger than number of observations"); return OEMGPU_ERR_UNSUPPORTED; }   // ref src/oem_xval_dense.h:690-731
     if (set_device(c)) return OEMGPU_ERR_HIP;
@@ -2493,34 +2501,18 @@ int oemgpu_xval_dense_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t
                           int32_t type_measure, const oemgpu_opts *o,
                           double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, double *cvm, double *cvsd)
 {
-    return xval_dense_src(c, xval_src_cm(x_dev, ld), n, p, y_dev, w_dev, foldid_dev, nfolds, standardize, intercept, type_measure, o, beta,
+    return xval_dense_src("xval_dense", c, dense_src_cm(x_dev, ld), n, p, y_dev, w_dev, foldid_dev, nfolds, standardize, intercept, type_measure, o, beta,
                           lambda_out, niter, loss, d, cvm, cvsd);
 }
 
-// what a row-major source adds to its column-major counterpart's refusals (the rule of the other _rm_dev entries, and the element's
-// alignment: the gather loads one element per lane)
-static int rm_src_check(const char *who, const void *x_dev, int32_t dtype, int64_t ldr, int32_t p)
-{
-    if (dtype != OEMGPU_F64 && dtype != OEMGPU_F32) { set_error("%s: dtype %d is neither OEMGPU_F64 nor OEMGPU_F32", who, dtype); return OEMGPU_ERR_ARG; }
-    if (ldr < p) { set_error("%s: bad ldr (ldr >= p)", who); return OEMGPU_ERR_ARG; }
-    const uintptr_t el = dtype == OEMGPU_F32 ? 4 : 8;
-    if (((uintptr_t)x_dev) % el) { set_error("%s: x_dev is not aligned to its %d-byte elements", who, (int)el); return OEMGPU_ERR_ARG; }
-    return 0;
-}
-
-// oemgpu_xval_dense_dev with the rows gathered from a row-major x where it lies (xval.hip: fold_gather_rm_kernel); everything behind
-// the fold-ordered copy is that entry's, and so are the results, bit for bit
+// oemgpu_xval_dense_dev with the rows gathered from a row-major x where it lies (xval.hip: fold_gather_rm_kernel)
 int oemgpu_xval_dense_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
                              const double *w_dev, const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept,
                              int32_t type_measure, const oemgpu_opts *o,
                              double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, double *cvm, double *cvsd)
 {
-    if (!c || !x_dev || !y_dev || !foldid_dev || !beta || !lambda_out || !niter || !loss || !d || !cvm || !cvsd) {
-        set_error("xval_dense: NULL argument"); return OEMGPU_ERR_ARG;
-    }
-    if (int rc = rm_src_check("xval_dense_rm", x_dev, dtype, ldr, p)) return rc;
-    return xval_dense_src(c, xval_src_rm(x_dev, dtype, ldr), n, p, y_dev, w_dev, foldid_dev, nfolds, standardize, intercept, type_measure, o, beta,
-                          lambda_out, niter, loss, d, cvm, cvsd);
+    return xval_dense_src("xval_dense_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, w_dev, foldid_dev, nfolds, standardize, intercept,
+                          type_measure, o, beta, lambda_out, niter, loss, d, cvm, cvsd);
 }
 
 // ---- the same three phases as separate calls, for row shards on several GPUs (one process per GPU; the caller sums the fold
@@ -2543,7 +2535,7 @@ int oemgpu_xval_fold_moments_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, 
     const XvalLay L = xval_layout(c, n, p, K, o->npen, nl_of(o), w_dev != nullptr);
     if (ctx_aux(c, L.total)) return OEMGPU_ERR_HIP;
     std::vector<int64_t> hf;
-    rc = xval_prepare(c, L, xval_src_cm(x_dev, ld), y_dev, w_dev, foldid_dev, hf);
+    rc = xval_prepare(c, L, dense_src_cm(x_dev, ld), y_dev, w_dev, foldid_dev, hf);
     if (rc) return rc;
     for (int k = 0; k < K; ++k) fold_n[k] = hf[k];
     OEM_HIP(hipMemcpyAsync(fold_moments_dev, c->aux + L.a_mf, sizeof(double) * L.mlen * K, hipMemcpyDeviceToDevice, c->stream));
@@ -2600,7 +2592,7 @@ int oemgpu_selftest_xval_cv_error_dev(oemgpu_ctx *c, const double *x_dev, int64_
     const XvalLay L = xval_layout(c, n, p, K, npen, nl, w_dev != nullptr);
     if (ctx_aux(c, L.total)) return OEMGPU_ERR_HIP;
     std::vector<int64_t> hf;
-    rc = xval_prepare(c, L, xval_src_cm(x_dev, ld), y_dev, w_dev, foldid_dev, hf);
+    rc = xval_prepare(c, L, dense_src_cm(x_dev, ld), y_dev, w_dev, foldid_dev, hf);
     if (rc) return rc;
     char *ax = c->aux;
     int64_t *fold_n = (int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
@@ -2676,7 +2668,7 @@ static int cv_check_rows(const char *who, int64_t n, int64_t ld, int p, int K)
 }
 
 // rows into fold order (and the fold moments about 0), and the stamp oemgpu_cv_score_dev looks for
-static int cv_lay_out(oemgpu_ctx *c, const CvLay &V, const XvalSrc &X, const double *y_dev, const int32_t *foldid_dev,
+static int cv_lay_out(oemgpu_ctx *c, const CvLay &V, const DenseSrc &X, const double *y_dev, const int32_t *foldid_dev,
                       bool moments, std::vector<int64_t> &hf)
 {
     if (ctx_aux(c, V.total)) return OEMGPU_ERR_HIP;
@@ -2686,7 +2678,7 @@ static int cv_lay_out(oemgpu_ctx *c, const CvLay &V, const XvalSrc &X, const dou
     return 0;
 }
 
-static int cv_fold_fits_src(oemgpu_ctx *c, const XvalSrc &X, int64_t n, int32_t p, const double *y_dev,
+static int cv_fold_fits_src(const char *who, oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const double *y_dev,
                             const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept, const oemgpu_opts *o,
                             double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int64_t *fold_n)
 {
@@ -2694,8 +2686,9 @@ static int cv_fold_fits_src(oemgpu_ctx *c, const XvalSrc &X, int64_t n, int32_t 
         set_error("cv_fold_fits: NULL argument"); return OEMGPU_ERR_ARG;
     }
     const int K = nfolds;
-    int rc = check_opts(o, p, p);
-    if (!rc) rc = cv_check_rows("cv_fold_fits", n, X.dtype < 0 ? X.ld : n, p, K);
+    int rc = dense_src_check(who, X, n, p);
+    if (!rc) rc = check_opts(o, p, p);
+    if (!rc) rc = cv_check_rows("cv_fold_fits", n, n, p, K);
     if (rc) return rc;
     // the largest fold holds at least ceil(n / K) rows: some fold fit is then not the Gram form whatever the ids are
     if (n - (n + K - 1) / K <= p) {
@@ -2736,9 +2729,8 @@ static int cv_fold_fits_src(oemgpu_ctx *c, const XvalSrc &X, int64_t n, int32_t 
     rc = solve_all(nullptr, &advised);
     if (rc || !advised) return rc;
     // oemgpu_fit_dense_dev's rule, for all folds at once: sample sums of all rows, the segment passes about them, the solves again
-    // (launch_shift_sums_rm's buffer is launch_shift_sums' on the column-major float64 copy, bit for bit)
-    rc = X.dtype < 0 ? launch_shift_sums(c->stream, (const double *)X.x, n, X.ld, p, y_dev, sums)
-                     : launch_shift_sums_rm(c->stream, X.x, X.dtype, n, X.ld, p, y_dev, sums);
+    // (a row-major source's sums are the column-major float64 copy's, bit for bit)
+    rc = dense_src_shift_sums(c->stream, X, n, p, y_dev, sums);
     if (!rc) rc = xval_fold_moments(c, L, hf, sums);
     if (!rc) rc = solve_all(sums, nullptr);
     return rc;
@@ -2748,7 +2740,7 @@ int oemgpu_cv_fold_fits_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64
                             const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept, const oemgpu_opts *o,
                             double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int64_t *fold_n)
 {
-    return cv_fold_fits_src(c, xval_src_cm(x_dev, ld), n, p, y_dev, foldid_dev, nfolds, standardize, intercept, o, beta, lambda_out, niter, loss,
+    return cv_fold_fits_src("cv_fold_fits", c, dense_src_cm(x_dev, ld), n, p, y_dev, foldid_dev, nfolds, standardize, intercept, o, beta, lambda_out, niter, loss,
                             d, fold_n);
 }
 
@@ -2758,11 +2750,7 @@ int oemgpu_cv_fold_fits_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, 
                                const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept, const oemgpu_opts *o,
                                double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int64_t *fold_n)
 {
-    if (!c || !x_dev || !y_dev || !foldid_dev || !o || !beta || !lambda_out || !niter || !loss || !d || !fold_n) {
-        set_error("cv_fold_fits: NULL argument"); return OEMGPU_ERR_ARG;
-    }
-    if (int rc = rm_src_check("cv_fold_fits_rm", x_dev, dtype, ldr, p)) return rc;
-    return cv_fold_fits_src(c, xval_src_rm(x_dev, dtype, ldr), n, p, y_dev, foldid_dev, nfolds, standardize, intercept, o, beta, lambda_out, niter,
+    return cv_fold_fits_src("cv_fold_fits_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, foldid_dev, nfolds, standardize, intercept, o, beta, lambda_out, niter,
                             loss, d, fold_n);
 }
 
@@ -2776,7 +2764,8 @@ int oemgpu_selftest_fold_gather_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t
     if (!c || !x_dev || !y_dev || !foldid_dev || !xo_dev || !yo_dev || !fold_n || !fold_start) {
         set_error("selftest_fold_gather_rm: NULL argument"); return OEMGPU_ERR_ARG;
     }
-    int rc = rm_src_check("selftest_fold_gather_rm", x_dev, dtype, ldr, p);
+    const DenseSrc X = dense_src_rm(x_dev, dtype, ldr);
+    int rc = dense_src_check("selftest_fold_gather_rm", X, n, p);
     if (!rc) rc = cv_check_rows("selftest_fold_gather_rm", n, n, p, nfolds);
     if (rc) return rc;
     const int K = nfolds;
@@ -2789,7 +2778,7 @@ int oemgpu_selftest_fold_gather_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t
     int *blockcnt = (int *)(c->ws + a_cnt), *bad = (int *)(c->ws + a_bad), *pos = (int *)(c->ws + a_pos);
     int64_t *fn = (int64_t *)(c->ws + a_fn);
     rc = launch_fold_layout(c->stream, foldid_dev, n, K, blockcnt, fn, fn + K, pos, bad);
-    if (!rc) rc = launch_gather_rows_rm(c->stream, x_dev, dtype, n, ldr, p, y_dev, foldid_dev, K, pos, xo_dev, ldo, yo_dev);
+    if (!rc) rc = dense_src_gather(c->stream, X, n, p, y_dev, foldid_dev, K, pos, xo_dev, ldo, yo_dev);
     if (rc) return rc;
     int hbad = 0;
     std::vector<int64_t> hf(2 * K);
@@ -2850,7 +2839,7 @@ int oemgpu_selftest_cv_score_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, 
     if (set_device(c)) return OEMGPU_ERR_HIP;
     const CvLay V = cv_layout(c, n, p, nfolds, npen, nl);
     std::vector<int64_t> hf;
-    rc = cv_lay_out(c, V, xval_src_cm(x_dev, ld), y_dev, foldid_dev, false, hf);
+    rc = cv_lay_out(c, V, dense_src_cm(x_dev, ld), y_dev, foldid_dev, false, hf);
     if (rc) return rc;
     return oemgpu_cv_score_dev(c, n, p, nfolds, coef, npen, nl, ncol, type_measure, triples, predmat_dev);
 }
@@ -2925,7 +2914,7 @@ static int xval_dense_devices(const std::vector<int> &dev, const double *x, int6
         if (r) return r;
         q.L = xval_layout(q.c, q.r1 - q.r0, p, K, npen, nl, weights != nullptr);
         if (ctx_aux(q.c, q.L.total)) return OEMGPU_ERR_HIP;
-        return xval_prepare(q.c, q.L, xval_src_cm(q.xd, q.ld), q.yd, q.wd, q.fd, q.hf);
+        return xval_prepare(q.c, q.L, dense_src_cm(q.xd, q.ld), q.yd, q.wd, q.fd, q.hf);
     });
     if (rc) { release_all(); return rc; }
     // ---- the fold moments of devices 1 .. G-1 into device 0's, in device order (bitwise reproducible); fold sizes on the host

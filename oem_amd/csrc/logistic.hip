@@ -31,7 +31,7 @@
 // rows are zeros), logit_fold_scan_kernel counts the kept rows (n_eff, which stands where n enters the arithmetic) and maps the W floor's
 // IRLS index to the i-th kept row.
 // The host driver (logistic_irls) is shared with the sparse fit (logistic_sparse.hip): the passes over the data reach it as the stages of
-// a LogitData (logistic.hpp); DenseLogitData below is this file's, and RowMajorLogitData next to it is the same over a row-major x of
+// a LogitData (logistic.hpp); DenseLogitData below is this file's, over a column-major x or (the readers of logistic_rm.hip) a row-major x of
 // float64 / float32 elements read where it lies (oemgpu_fit_logistic_dense_rm_dev, ..._fold_rm_dev; kernels: logistic_rm.hip).
 #include "logistic.hpp"
 #include "penalty_ops.hpp"
@@ -557,14 +557,17 @@ namespace {
 // the dense x: one row pass per IRLS step (logit_rows_kernel); with a Hessian due the same pass writes the Z row blocks of the
 // moment pass instead, block after block.  With foldid / leave_out it is the data of the fit on the rows with foldid[row] != leave_out:
 // X and y stay where they are, the passes leave those rows out, and n_eff (the kept rows) stands where n enters the arithmetic.
-struct DenseLogitData : LogitData {
+struct DenseLogitData final : LogitData {
     oemgpu_ctx *c;
-    const double *x, *y;
-    int64_t n, ld;
+    DenseSrc X;
+    const double *y;
+    int64_t n;
     int p, q, intercept, standardize;
     LogitPlan P;
+    LogitRmPlan R;                    // a row-major x: the band plan of its row pass
     size_t m2;
     double *part = nullptr, *z = nullptr, *mb = nullptr, *ma = nullptr, *tp = nullptr, *vp = nullptr;
+    double *sp = nullptr;             // a row-major x: the scale pass's 256 partials per column
     const int32_t *foldid = nullptr;  // device, n entries; null: every row is in the fit
     int32_t leave_out = 0;
     int64_t n_eff;                    // rows in the fit
@@ -582,18 +585,20 @@ struct DenseLogitData : LogitData {
         return 0;
     }
 
-    DenseLogitData(oemgpu_ctx *c_, const double *x_, int64_t n_, int64_t ld_, int p_, const double *y_, int standardize_, int intercept_, int hessian_full)
-        : c(c_), x(x_), y(y_), n(n_), ld(ld_), p(p_), q(p_ + (intercept_ ? 1 : 0)), intercept(intercept_), standardize(standardize_),
-          P(logit_plan(n_, p_, intercept_, c_->num_cu)), m2((size_t)(q + 2) * (q + 2)), n_eff(n_)
+    DenseLogitData(oemgpu_ctx *c_, const DenseSrc &X_, int64_t n_, int p_, const double *y_, int standardize_, int intercept_, int hessian_full)
+        : c(c_), X(X_), y(y_), n(n_), p(p_), q(p_ + (intercept_ ? 1 : 0)), intercept(intercept_), standardize(standardize_),
+          P(logit_plan(n_, p_, intercept_, c_->num_cu)), R(X_.colmajor() ? LogitRmPlan{} : logit_rm_plan(p_)), m2((size_t)(q + 2) * (q + 2)), n_eff(n_)
     {
         hess_every = hessian_full != 0;
     }
+    bool wants_sp() const { return !X.colmajor() && standardize; }
     size_t ws_bytes() const override
     {
         Bump B;
         const GramPlan gpb = gram_plan_bound(P.rbz < n ? P.rbz : n, q, c->num_cu);
         B.take(8 * (size_t)P.nchunk * (p + 2)); B.take(8 * (size_t)P.rbz * q); B.take(8 * m2); B.take(8 * m2);
         B.take(8 * gpb.tpart_doubles); B.take(8 * gpb.vpart_doubles);
+        if (wants_sp()) B.take(8 * (size_t)256 * p);
         return B.off;
     }
     int bind(char *ws) override
@@ -603,19 +608,23 @@ struct DenseLogitData : LogitData {
         part = (double *)(ws + B.take(8 * (size_t)P.nchunk * (p + 2))); z = (double *)(ws + B.take(8 * (size_t)P.rbz * q));
         mb = (double *)(ws + B.take(8 * m2)); ma = (double *)(ws + B.take(8 * m2));
         tp = (double *)(ws + B.take(8 * gpb.tpart_doubles)); vp = (double *)(ws + B.take(8 * gpb.vpart_doubles));
+        if (wants_sp()) sp = (double *)(ws + B.take(8 * (size_t)256 * p));
         return 0;
     }
     int scale(double *sc) override
     {
-        if (standardize) hipLaunchKernelGGL(logit_scale_kernel, dim3(p), dim3(256), 0, c->stream, x, n, ld, sc, foldid, leave_out, n_eff);
-        else hipLaunchKernelGGL(logit_fill_kernel, dim3((p + 255) / 256), dim3(256), 0, c->stream, sc, p, 1.0);
+        if (!standardize) return launch_logit_fill(c->stream, sc, p, 1.0);
+        if (!X.colmajor()) return launch_logit_scale_rm(c->stream, X.x, X.dtype, n, X.ld, p, sp, sc, foldid, leave_out, n_eff, foldid ? kept_row[0] : 0);
+        hipLaunchKernelGGL(logit_scale_kernel, dim3(p), dim3(256), 0, c->stream, X.cm(), n, X.ld, sc, foldid, leave_out, n_eff);
         OEM_HIP(hipGetLastError());
         return 0;
     }
-    // the row pass over chunks c0 .. c0 + nc (logit_rows_kernel): the one place that reads x besides scale()
-    virtual int rows_launch(const double *beta, const double *sc, int mode, int64_t irls_row, int64_t c0, int64_t nc, int64_t row0, double *zb, int64_t ldz)
+    // the row pass over chunks c0 .. c0 + nc (logit_rows_kernel, either reader): the one place that reads x besides scale()
+    int rows_launch(const double *beta, const double *sc, int mode, int64_t irls_row, int64_t c0, int64_t nc, int64_t row0, double *zb, int64_t ldz)
     {
-        return logit_rows(c->stream, P, x, n, ld, p, y, beta, sc, intercept, mode, irls_row, c0, nc, row0, zb, ldz, part, foldid, leave_out);
+        if (X.colmajor()) return logit_rows(c->stream, P, X.cm(), n, X.ld, p, y, beta, sc, intercept, mode, irls_row, c0, nc, row0, zb, ldz, part, foldid, leave_out);
+        return launch_logit_rows_rm(c->stream, R, X.x, X.dtype, n, X.ld, p, y, beta, sc, intercept, mode, irls_row, P.ch, c0, nc, row0, zb, ldz, part, foldid,
+                                    leave_out);
     }
     int xy0(const double *sc, double *g) override
     {
@@ -653,47 +662,6 @@ struct DenseLogitData : LogitData {
         hipLaunchKernelGGL(logit_sum_kernel, dim3((p + 2 + 255) / 256), dim3(256), 0, s, part, P.nchunk, p + 2, g);
         OEM_HIP(hipGetLastError());
         return 0;
-    }
-};
-
-// the dense x as a row-major matrix of float64 / float32 elements, read where it lies (logistic_rm.hip): the same plan -- chunks, Z
-// blocks -- and the same stages with the row-major forms of the row pass and the scale pass; Z, the partials and everything behind
-// them are DenseLogitData's.  Every sum keeps the column-major kernels' order: the fit is theirs on the same values, bit for bit.
-struct RowMajorLogitData final : DenseLogitData {
-    const void *xr;
-    int dtype;
-    int64_t ldr;
-    LogitRmPlan R;
-    double *sp = nullptr;             // the scale pass's 256 partials per column
-
-    RowMajorLogitData(oemgpu_ctx *c_, const void *x_, int dtype_, int64_t n_, int64_t ldr_, int p_, const double *y_, int standardize_, int intercept_,
-                      int hessian_full)
-        : DenseLogitData(c_, nullptr, n_, 0, p_, y_, standardize_, intercept_, hessian_full), xr(x_), dtype(dtype_), ldr(ldr_), R(logit_rm_plan(p_))
-    {
-    }
-    size_t ws_bytes() const override
-    {
-        Bump B;
-        B.take(DenseLogitData::ws_bytes());
-        if (standardize) B.take(8 * (size_t)256 * p);
-        return B.off;
-    }
-    int bind(char *ws) override
-    {
-        Bump B;
-        const size_t a_d = B.take(DenseLogitData::ws_bytes());
-        if (standardize) sp = (double *)(ws + B.take(8 * (size_t)256 * p));
-        return DenseLogitData::bind(ws + a_d);
-    }
-    int scale(double *sc) override
-    {
-        if (!standardize) return launch_logit_fill(c->stream, sc, p, 1.0);
-        return launch_logit_scale_rm(c->stream, xr, dtype, n, ldr, p, sp, sc, foldid, leave_out, n_eff, foldid ? kept_row[0] : 0);
-    }
-    int rows_launch(const double *beta, const double *sc, int mode, int64_t irls_row, int64_t c0, int64_t nc, int64_t row0, double *zb, int64_t ldz) override
-    {
-        return launch_logit_rows_rm(c->stream, R, xr, dtype, n, ldr, p, y, beta, sc, intercept, mode, irls_row, P.ch, c0, nc, row0, zb, ldz, part, foldid,
-                                    leave_out);
     }
 };
 
@@ -954,56 +922,45 @@ int logistic_irls(oemgpu_ctx *c, LogitData &D, int64_t n, int32_t p, int32_t int
     return 0;
 }
 
-int logistic_fit_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int32_t p, const double *y, int32_t standardize, int32_t intercept,
-                     int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
-                     double *beta_out, double *lambda_out, int32_t *niter, double *loss_out, double *d_out)
+// The fit on a dense x wherever it lies; with foldid, on the rows with foldid[row] != leave_out (cv.oem's fold fit: what the dense fit
+// computes on x[keep, ], y[keep]), refused when p + intercept >= the kept rows
+static int logistic_fit_src(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const double *y, const int32_t *foldid, int32_t nfolds,
+                     int32_t leave_out, int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol,
+                     const oemgpu_opts *o, double *beta_out, double *lambda_out, int32_t *niter, double *loss_out, double *d_out)
 {
-    DenseLogitData D(c, x, n, ld, p, y, standardize, intercept, hessian_full);
-    return logistic_irls(c, D, n, p, intercept, irls_maxit, irls_tol, o, beta_out, lambda_out, niter, loss_out, d_out);
-}
-
-// a fold fit's refusal: p + intercept >= the kept rows
-static int fold_refusal(const DenseLogitData &D, int32_t leave_out)
-{
-    if ((int64_t)D.q < D.n_eff) return 0;
-    set_error("fit_logistic_dense_fold: p + intercept >= the %lld rows outside fold %d is not supported (the reference's XWXt branch, "
-              "ref src/oem_logistic_dense.h:524-566)", (long long)D.n_eff, (int)leave_out);
-    return OEMGPU_ERR_UNSUPPORTED;
-}
-
-// the fit on the rows with foldid[row] != leave_out (cv.oem's fold fit: what the dense fit computes on x[keep, ], y[keep])
-int logistic_fit_fold_dev(oemgpu_ctx *c, const double *x, int64_t n, int64_t ld, int32_t p, const double *y, const int32_t *foldid, int32_t nfolds,
-                          int32_t leave_out, int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol,
-                          const oemgpu_opts *o, double *beta_out, double *lambda_out, int32_t *niter, double *loss_out, double *d_out)
-{
-    DenseLogitData D(c, x, n, ld, p, y, standardize, intercept, hessian_full);
-    int rc = D.set_fold(foldid, nfolds, leave_out, irls_maxit);
-    if (rc) return rc;
-    if ((rc = fold_refusal(D, leave_out))) return rc;
-    return logistic_irls(c, D, D.n_eff, p, intercept, irls_maxit, irls_tol, o, beta_out, lambda_out, niter, loss_out, d_out);
-}
-
-// the two fits on a row-major x (foldid null: the fit on every row)
-static int logistic_fit_rm_dev(oemgpu_ctx *c, const void *x, int dtype, int64_t n, int64_t ldr, int32_t p, const double *y, const int32_t *foldid,
-                               int32_t nfolds, int32_t leave_out, int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit,
-                               double irls_tol, const oemgpu_opts *o, double *beta_out, double *lambda_out, int32_t *niter, double *loss_out, double *d_out)
-{
-    RowMajorLogitData D(c, x, dtype, n, ldr, p, y, standardize, intercept, hessian_full);
+    DenseLogitData D(c, X, n, p, y, standardize, intercept, hessian_full);
     if (foldid) {
-        int rc = D.set_fold(foldid, nfolds, leave_out, irls_maxit);
-        if (!rc) rc = fold_refusal(D, leave_out);
+        const int rc = D.set_fold(foldid, nfolds, leave_out, irls_maxit);
         if (rc) return rc;
+        if ((int64_t)D.q >= D.n_eff) {
+            set_error("fit_logistic_dense_fold: p + intercept >= the %lld rows outside fold %d is not supported (the reference's XWXt branch, "
+                      "ref src/oem_logistic_dense.h:524-566)", (long long)D.n_eff, (int)leave_out);
+            return OEMGPU_ERR_UNSUPPORTED;
+        }
     }
     return logistic_irls(c, D, D.n_eff, p, intercept, irls_maxit, irls_tol, o, beta_out, lambda_out, niter, loss_out, d_out);
 }
 
-// what the row-major entries add to the checks of their column-major counterparts (no device needed)
-int logistic_rm_check(const char *who, const void *x, int32_t dtype, int64_t ldr, int32_t p)
+// the checks of the four device entries (foldid_dev null: the plain fit), then the fit
+static int logistic_fit_checked(const char *who, bool fold, oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const double *y_dev,
+                                const int32_t *foldid_dev, int32_t nfolds, int32_t leave_out, int32_t standardize, int32_t intercept,
+                                int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
+                                double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
 {
-    if (dtype != OEMGPU_F64 && dtype != OEMGPU_F32) { set_error("%s: dtype %d is neither OEMGPU_F64 nor OEMGPU_F32", who, (int)dtype); return OEMGPU_ERR_ARG; }
-    if (ldr < p) { set_error("%s: ldr < p", who); return OEMGPU_ERR_ARG; }
-    if ((uintptr_t)x % (dtype == OEMGPU_F32 ? 4 : 8)) { set_error("%s: x_dev is not aligned to its element size", who); return OEMGPU_ERR_ARG; }
-    return 0;
+    if (!c || !X.x || !y_dev || (fold && !foldid_dev) || !o || !beta || !lambda_out || !niter || !loss || !d) {
+        set_error("%s: NULL argument", who);
+        return OEMGPU_ERR_ARG;
+    }
+    if (fold) {
+        if (nfolds < 3) { set_error("nfolds must be bigger than 3; nfolds=10 recommended"); return OEMGPU_ERR_ARG; }            // ref R/cv_oem.R:126-127
+        if (leave_out < 0 || leave_out > nfolds) { set_error("%s: leave_out must be in [0, nfolds]", who); return OEMGPU_ERR_ARG; }
+    }
+    int rc = dense_src_check(who, X, n, p);
+    if (!rc) rc = logistic_check(n, p, intercept, hessian_full, irls_maxit, irls_tol, o);
+    if (rc) return rc;
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    return logistic_fit_src(c, X, n, p, y_dev, foldid_dev, nfolds, leave_out, standardize, intercept, hessian_full, irls_maxit, irls_tol, o, beta,
+                            lambda_out, niter, loss, d);
 }
 
 }  // namespace oemgpu
@@ -1017,12 +974,8 @@ int oemgpu_fit_logistic_dense_dev(oemgpu_ctx *c, const double *x_dev, int64_t n,
                                   int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
                                   double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
 {
-    if (!c || !x_dev || !y_dev || !o || !beta || !lambda_out || !niter || !loss || !d) { set_error("fit_logistic_dense: NULL argument"); return OEMGPU_ERR_ARG; }
-    int rc = logistic_check(n, p, intercept, hessian_full, irls_maxit, irls_tol, o);
-    if (rc) return rc;
-    if (ld < n) { set_error("fit_logistic_dense: ld < n"); return OEMGPU_ERR_ARG; }
-    if (set_device(c)) return OEMGPU_ERR_HIP;
-    return logistic_fit_dev(c, x_dev, n, ld, p, y_dev, standardize, intercept, hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
+    return logistic_fit_checked("fit_logistic_dense", false, c, dense_src_cm(x_dev, ld), n, p, y_dev, nullptr, 0, 0, standardize, intercept, hessian_full,
+                                irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
 }
 
 int oemgpu_fit_logistic_dense_fold_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
@@ -1030,31 +983,16 @@ int oemgpu_fit_logistic_dense_fold_dev(oemgpu_ctx *c, const double *x_dev, int64
                                        int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
                                        double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
 {
-    if (!c || !x_dev || !y_dev || !foldid_dev || !o || !beta || !lambda_out || !niter || !loss || !d) {
-        set_error("fit_logistic_dense_fold: NULL argument");
-        return OEMGPU_ERR_ARG;
-    }
-    if (nfolds < 3) { set_error("nfolds must be bigger than 3; nfolds=10 recommended"); return OEMGPU_ERR_ARG; }            // ref R/cv_oem.R:126-127
-    if (leave_out < 0 || leave_out > nfolds) { set_error("fit_logistic_dense_fold: leave_out must be in [0, nfolds]"); return OEMGPU_ERR_ARG; }
-    int rc = logistic_check(n, p, intercept, hessian_full, irls_maxit, irls_tol, o);
-    if (rc) return rc;
-    if (ld < n) { set_error("fit_logistic_dense_fold: ld < n"); return OEMGPU_ERR_ARG; }
-    if (set_device(c)) return OEMGPU_ERR_HIP;
-    return logistic_fit_fold_dev(c, x_dev, n, ld, p, y_dev, foldid_dev, nfolds, leave_out, standardize, intercept, hessian_full, irls_maxit, irls_tol, o,
-                                 beta, lambda_out, niter, loss, d);
+    return logistic_fit_checked("fit_logistic_dense_fold", true, c, dense_src_cm(x_dev, ld), n, p, y_dev, foldid_dev, nfolds, leave_out, standardize,
+                                intercept, hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
 }
 
 int oemgpu_fit_logistic_dense_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
                                      int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol,
                                      const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
 {
-    if (!c || !x_dev || !y_dev || !o || !beta || !lambda_out || !niter || !loss || !d) { set_error("fit_logistic_dense_rm: NULL argument"); return OEMGPU_ERR_ARG; }
-    int rc = logistic_rm_check("fit_logistic_dense_rm", x_dev, dtype, ldr, p);
-    if (!rc) rc = logistic_check(n, p, intercept, hessian_full, irls_maxit, irls_tol, o);
-    if (rc) return rc;
-    if (set_device(c)) return OEMGPU_ERR_HIP;
-    return logistic_fit_rm_dev(c, x_dev, dtype, n, ldr, p, y_dev, nullptr, 0, 0, standardize, intercept, hessian_full, irls_maxit, irls_tol, o, beta,
-                               lambda_out, niter, loss, d);
+    return logistic_fit_checked("fit_logistic_dense_rm", false, c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, nullptr, 0, 0, standardize, intercept,
+                                hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
 }
 
 int oemgpu_fit_logistic_dense_fold_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
@@ -1062,18 +1000,8 @@ int oemgpu_fit_logistic_dense_fold_rm_dev(oemgpu_ctx *c, const void *x_dev, int3
                                           int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *o,
                                           double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
 {
-    if (!c || !x_dev || !y_dev || !foldid_dev || !o || !beta || !lambda_out || !niter || !loss || !d) {
-        set_error("fit_logistic_dense_fold_rm: NULL argument");
-        return OEMGPU_ERR_ARG;
-    }
-    if (nfolds < 3) { set_error("nfolds must be bigger than 3; nfolds=10 recommended"); return OEMGPU_ERR_ARG; }            // ref R/cv_oem.R:126-127
-    if (leave_out < 0 || leave_out > nfolds) { set_error("fit_logistic_dense_fold_rm: leave_out must be in [0, nfolds]"); return OEMGPU_ERR_ARG; }
-    int rc = logistic_rm_check("fit_logistic_dense_fold_rm", x_dev, dtype, ldr, p);
-    if (!rc) rc = logistic_check(n, p, intercept, hessian_full, irls_maxit, irls_tol, o);
-    if (rc) return rc;
-    if (set_device(c)) return OEMGPU_ERR_HIP;
-    return logistic_fit_rm_dev(c, x_dev, dtype, n, ldr, p, y_dev, foldid_dev, nfolds, leave_out, standardize, intercept, hessian_full, irls_maxit,
-                               irls_tol, o, beta, lambda_out, niter, loss, d);
+    return logistic_fit_checked("fit_logistic_dense_fold_rm", true, c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, foldid_dev, nfolds, leave_out,
+                                standardize, intercept, hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
 }
 
 int oemgpu_selftest_logistic_rm_plan(int64_t n, int32_t p, int32_t dtype, int32_t intercept, int32_t num_cu, int64_t *out)
@@ -1099,7 +1027,8 @@ int oemgpu_fit_logistic_dense(const double *x, int64_t n, int32_t p, const doubl
     double *xd = nullptr, *yd = nullptr;
     int64_t ld = 0;
     rc = host_upload_resident(c, x, n, p, y, o, &xd, &ld, &yd, 0, true);
-    if (!rc) rc = logistic_fit_dev(c, xd, n, ld, p, yd, standardize, intercept, hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
+    if (!rc) rc = logistic_fit_src(c, dense_src_cm(xd, ld), n, p, yd, nullptr, 0, 0, standardize, intercept, hessian_full, irls_maxit, irls_tol, o, beta,
+                                   lambda_out, niter, loss, d);
     (void)hipStreamSynchronize(c->stream);
     ctx_release(c);
     return rc;

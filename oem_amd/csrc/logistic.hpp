@@ -3,7 +3,7 @@
 // inner OEM loop (one workgroup or the launch form), d from the device Lanczos, A = dI - XX, XY = XX beta + grad and the
 // back-transform.  Only the two passes over the data differ.
 #pragma once
-#include "ctx.hpp"
+#include "dense_src.hpp"
 
 #include <vector>
 
@@ -47,9 +47,6 @@ int launch_logit_fill(hipStream_t s, double *a, int n, double v);   // a[0 .. n)
 // tests the IRLS index among the kept rows); OEMGPU_ERR_ARG in `who`'s name when an id is outside [1, nfolds]
 int logit_fold_scan(oemgpu_ctx *c, const char *who, const int32_t *foldid, int64_t n, int32_t nfolds, int32_t leave_out, int32_t irls_maxit,
                     int64_t *n_eff, std::vector<int64_t> *kept_row);
-// the scoring pass of cv.oem over a resident x (logistic_cv.hip): dense (x, ld) when sx is null, else the compressed-row copy of sx
-int logistic_cv_score_dev(oemgpu_ctx *c, const double *x, const oemgpu_sparse_x *sx, int64_t n, int64_t ld, int32_t p, const double *y, double y_hi,
-                          const int32_t *foldid, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *pred);
 // A row-major x of float64 / float32 elements read where it lies (logistic_rm.hip).  The band plan of its row pass, pure host arithmetic:
 // band b = columns [b bw, min(p, (b + 1) bw)); bw is a multiple of 4 unless there is one band (bw = p)
 struct LogitRmPlan {
@@ -66,11 +63,6 @@ int launch_logit_rows_rm(hipStream_t s, const LogitRmPlan &R, const void *x, int
 // logit_scale_kernel for the row-major x; sp: 256 p doubles of workspace; fill_row: a row that is in the fit
 int launch_logit_scale_rm(hipStream_t s, const void *x, int dtype, int64_t n, int64_t ldr, int p, double *sp, double *sc, const int32_t *foldid,
                           int32_t leave_out, int64_t n_eff, int64_t fill_row);
-// what the row-major entries add to the checks of their column-major counterparts (no device needed)
-int logistic_rm_check(const char *who, const void *x, int32_t dtype, int64_t ldr, int32_t p);
-// the scoring pass over a row-major x (logistic_cv.hip)
-int logistic_cv_score_rm_dev(oemgpu_ctx *c, const void *x, int dtype, int64_t n, int64_t ldr, int32_t p, const double *y, double y_hi,
-                             const int32_t *foldid, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *pred);
 extern const int LOGIT_WG_MAX_Q;                        // q up to which the inner solve is one persistent workgroup
 extern const int LOGIT_P_LIMIT;                          // the largest p served
 

@@ -231,18 +231,27 @@ static int cv_score_run(oemgpu_ctx *c, const ROWS X, int64_t n, int32_t p, const
     return 0;
 }
 
-int logistic_cv_score_dev(oemgpu_ctx *c, const double *x, const oemgpu_sparse_x *sx, int64_t n, int64_t ld, int32_t p, const double *y, double y_hi,
-                          const int32_t *foldid, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *pred)
+// the scoring pass with the reader of where the rows lie: the compressed-row copy of sx, or the dense source X; one of the two is null
+static int cv_score_rows(oemgpu_ctx *c, const oemgpu_sparse_x *sx, const DenseSrc *X, int64_t n, int32_t p, const double *y, double y_hi,
+                         const int32_t *foldid, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *pred)
 {
     if (sx) return cv_score_run(c, CvCsrRows{sx->rowptr, sx->ccol, sx->cval}, n, p, y, y_hi, foldid, nfolds, coef, ncol, sums, counts, pred);
-    return cv_score_run(c, CvDenseRows{x, ld}, n, p, y, y_hi, foldid, nfolds, coef, ncol, sums, counts, pred);
+    if (X->colmajor()) return cv_score_run(c, CvDenseRows{X->cm(), X->ld}, n, p, y, y_hi, foldid, nfolds, coef, ncol, sums, counts, pred);
+    if (X->dtype == OEMGPU_F32) return cv_score_run(c, CvRmRows<float>{(const float *)X->x, X->ld}, n, p, y, y_hi, foldid, nfolds, coef, ncol, sums, counts, pred);
+    return cv_score_run(c, CvRmRows<double>{(const double *)X->x, X->ld}, n, p, y, y_hi, foldid, nfolds, coef, ncol, sums, counts, pred);
 }
 
-int logistic_cv_score_rm_dev(oemgpu_ctx *c, const void *x, int dtype, int64_t n, int64_t ldr, int32_t p, const double *y, double y_hi,
-                             const int32_t *foldid, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *pred)
+// the checks of the two dense entries, then the scoring pass
+static int cv_score_src(const char *who, oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const double *y_dev, double y_hi,
+                        const int32_t *foldid_dev, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts, double *pred)
 {
-    if (dtype == OEMGPU_F32) return cv_score_run(c, CvRmRows<float>{(const float *)x, ldr}, n, p, y, y_hi, foldid, nfolds, coef, ncol, sums, counts, pred);
-    return cv_score_run(c, CvRmRows<double>{(const double *)x, ldr}, n, p, y, y_hi, foldid, nfolds, coef, ncol, sums, counts, pred);
+    if (!c || !X.x || !y_dev || !foldid_dev || !coef || !sums || !counts) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    if (int rc = dense_src_check(who, X, n, p)) return rc;
+    if (n < 1 || p < 1 || ncol < 1) { set_error("%s: bad n, p or ncol", who); return OEMGPU_ERR_ARG; }
+    if (nfolds < 3) { set_error("nfolds must be bigger than 3; nfolds=10 recommended"); return OEMGPU_ERR_ARG; }
+    if (p > LOGIT_P_LIMIT) { set_error("%s: p > %d is not supported", who, LOGIT_P_LIMIT); return OEMGPU_ERR_UNSUPPORTED; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    return cv_score_rows(c, nullptr, &X, n, p, y_dev, y_hi, foldid_dev, nfolds, coef, ncol, sums, counts, pred);
 }
 
 }  // namespace oemgpu
@@ -256,25 +265,15 @@ int oemgpu_logistic_cv_score_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, 
                                  const int32_t *foldid_dev, int32_t nfolds, const double *coef, int32_t ncol, double *sums, int64_t *counts,
                                  double *predmat_dev)
 {
-    if (!c || !x_dev || !y_dev || !foldid_dev || !coef || !sums || !counts) { set_error("logistic_cv_score: NULL argument"); return OEMGPU_ERR_ARG; }
-    if (n < 1 || p < 1 || ld < n || ncol < 1) { set_error("logistic_cv_score: bad n, p, ld or ncol"); return OEMGPU_ERR_ARG; }
-    if (nfolds < 3) { set_error("nfolds must be bigger than 3; nfolds=10 recommended"); return OEMGPU_ERR_ARG; }
-    if (p > LOGIT_P_LIMIT) { set_error("logistic_cv_score: p > %d is not supported", LOGIT_P_LIMIT); return OEMGPU_ERR_UNSUPPORTED; }
-    if (set_device(c)) return OEMGPU_ERR_HIP;
-    return logistic_cv_score_dev(c, x_dev, nullptr, n, ld, p, y_dev, y_hi, foldid_dev, nfolds, coef, ncol, sums, counts, predmat_dev);
+    return cv_score_src("logistic_cv_score", c, dense_src_cm(x_dev, ld), n, p, y_dev, y_hi, foldid_dev, nfolds, coef, ncol, sums, counts, predmat_dev);
 }
 
 int oemgpu_logistic_cv_score_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
                                     double y_hi, const int32_t *foldid_dev, int32_t nfolds, const double *coef, int32_t ncol, double *sums,
                                     int64_t *counts, double *predmat_dev)
 {
-    if (!c || !x_dev || !y_dev || !foldid_dev || !coef || !sums || !counts) { set_error("logistic_cv_score_rm: NULL argument"); return OEMGPU_ERR_ARG; }
-    if (int rc = logistic_rm_check("logistic_cv_score_rm", x_dev, dtype, ldr, p)) return rc;
-    if (n < 1 || p < 1 || ncol < 1) { set_error("logistic_cv_score_rm: bad n, p or ncol"); return OEMGPU_ERR_ARG; }
-    if (nfolds < 3) { set_error("nfolds must be bigger than 3; nfolds=10 recommended"); return OEMGPU_ERR_ARG; }
-    if (p > LOGIT_P_LIMIT) { set_error("logistic_cv_score_rm: p > %d is not supported", LOGIT_P_LIMIT); return OEMGPU_ERR_UNSUPPORTED; }
-    if (set_device(c)) return OEMGPU_ERR_HIP;
-    return logistic_cv_score_rm_dev(c, x_dev, dtype, n, ldr, p, y_dev, y_hi, foldid_dev, nfolds, coef, ncol, sums, counts, predmat_dev);
+    return cv_score_src("logistic_cv_score_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, y_hi, foldid_dev, nfolds, coef, ncol, sums, counts,
+                        predmat_dev);
 }
 
 int oemgpu_logistic_cv_score_sparse_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const double *y_dev, double y_hi, const int32_t *foldid_dev,
@@ -286,7 +285,7 @@ int oemgpu_logistic_cv_score_sparse_res(oemgpu_ctx *c, const oemgpu_sparse_x *x,
     if (x->p > LOGIT_P_LIMIT) { set_error("logistic_cv_score_sparse: p > %d is not supported", LOGIT_P_LIMIT); return OEMGPU_ERR_UNSUPPORTED; }
     if (c->device != x->device) { set_error("logistic_cv_score_sparse: the context and the sparse x are on different devices"); return OEMGPU_ERR_ARG; }
     if (set_device(c)) return OEMGPU_ERR_HIP;
-    return logistic_cv_score_dev(c, nullptr, x, x->n, x->n, x->p, y_dev, y_hi, foldid_dev, nfolds, coef, ncol, sums, counts, predmat_dev);
+    return cv_score_rows(c, x, nullptr, x->n, x->p, y_dev, y_hi, foldid_dev, nfolds, coef, ncol, sums, counts, predmat_dev);
 }
 
 int oemgpu_selftest_cv_score_plan(int64_t n, int32_t p, int32_t ncol, int32_t num_cu, int64_t *out)

@@ -138,6 +138,20 @@ def test_shapes_the_fit_does_not_serve_are_refused_before_any_device_work(dtype)
     assert str(P_MAX) in lib.oemgpu_last_error().decode()
 
 
+def test_the_helper_says_which_tensors_the_binomial_entries_read_in_place():
+    """_logistic_rowmajor_in_place reads only dtype, shape and strides: CPU tensors pin it"""
+    import torch
+    from oem_amd import api
+    from oem_amd import _lib as L
+    x = torch.zeros((6, 4), dtype=torch.float64)
+    assert api._logistic_rowmajor_in_place(x) == L.OEMGPU_F64 and api._logistic_rowmajor_in_place(x.float()) == L.OEMGPU_F32
+    assert api._logistic_rowmajor_in_place(torch.zeros((6, 9), dtype=torch.float32)[:, :4]) == L.OEMGPU_F32          # a row stride beyond p
+    assert api._logistic_rowmajor_in_place(torch.zeros((4000, 2000))) == L.OEMGPU_F32                                 # no limit on p
+    assert api._logistic_rowmajor_in_place(x.half()) is None
+    assert api._logistic_rowmajor_in_place(torch.zeros((4, 6), dtype=torch.float64).t()) is None                      # already column-major
+    assert api._logistic_rowmajor_in_place(torch.zeros((6, 8), dtype=torch.float64)[:, ::2]) is None                  # strided in its columns
+
+
 def _plan(n, p, dtype, intercept, num_cu):
     out = (C.c_int64 * 8)()
     rc = _lib().oemgpu_selftest_logistic_rm_plan(n, p, dtype, intercept, num_cu, out)

@@ -54,6 +54,8 @@ BAD = [
     ((CTX, PTR, 1, 0, 4, 4, PTR), "n = 0"),
     ((CTX, PTR, 0, 10, 4, 0, PTR), "p = 0"),
     ((CTX, PTR, 1, 10, 3, 4, PTR), "ldr < p"),
+    ((CTX, C.c_void_p(0x2004), 0, 10, 4, 4, PTR), "a float64 x at an odd multiple of 4"),
+    ((CTX, C.c_void_p(0x2002), 1, 10, 4, 4, PTR), "a float32 x at an odd multiple of 2"),
 ]
 
 
@@ -97,6 +99,35 @@ def test_shapes_of_the_column_major_entry_are_refused_by_name():
     assert lib.oemgpu_fit_dense_rm_dev(CTX, PTR, 1, 500, 2500, 2500, PTR, 1, 1, C.byref(a.c), *a.outputs(2501)) == ERR_UNSUPPORTED
     msg = lib.oemgpu_last_error().decode()
     assert "p >= n" in msg and "oemgpu_fit_dense_dev" in msg
+
+
+def test_the_helper_says_which_tensors_oem_reads_in_place():
+    """_rowmajor_in_place reads only dtype, shape and strides: CPU tensors pin it"""
+    import torch
+    from oem_amd import api
+    from oem_amd import _lib as L
+    x = torch.zeros((6, 4), dtype=torch.float64)
+    assert api._rowmajor_in_place(x) == L.OEMGPU_F64 and api._rowmajor_in_place(x.float()) == L.OEMGPU_F32
+    assert api._rowmajor_in_place(torch.zeros((6, 9), dtype=torch.float32)[:, :4]) == L.OEMGPU_F32          # a row stride beyond p
+    assert api._rowmajor_in_place(x.half()) is None
+    assert api._rowmajor_in_place(torch.zeros((4, 6), dtype=torch.float64).t()) is None                      # already column-major
+    assert api._rowmajor_in_place(torch.zeros((6, 8), dtype=torch.float64)[:, ::2]) is None                  # strided in its columns
+    assert api._rowmajor_in_place(torch.zeros((4, 4), dtype=torch.float64)) is None                          # n <= p: the p >= n engines
+    assert api._rowmajor_in_place(torch.zeros((4, 6), dtype=torch.float32)) is None
+    assert api._rowmajor_in_place(torch.zeros((L.RM_P_MAX + 1, L.RM_P_MAX), dtype=torch.float32)) == L.OEMGPU_F32
+    assert api._rowmajor_in_place(torch.zeros((L.RM_P_MAX + 2, L.RM_P_MAX + 1), dtype=torch.float32)) is None   # p beyond the row-major pass
+
+
+def test_a_float32_x_on_a_4_byte_boundary_is_not_an_alignment_error():
+    """element alignment is all that is asked: the same pointer passes as float32 (and is then refused for its shape, so that the fake
+    context is never used)"""
+    lib = _lib()
+    from oem_amd import _lib as L
+    x4 = C.c_void_p(0x2004)
+    p = L.RM_P_MAX + 1
+    assert lib.oemgpu_moments_rm_dev(CTX, x4, 1, 10 * p, p, p, PTR, None, PTR) == ERR_UNSUPPORTED
+    assert lib.oemgpu_moments_rm_dev(CTX, x4, 0, 10 * p, p, p, PTR, None, PTR) == ERR_ARG
+    assert "aligned" in lib.oemgpu_last_error().decode()
 
 
 def _plan(n, p, num_cu):
