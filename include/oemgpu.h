@@ -754,6 +754,45 @@ int oemgpu_selftest_csc_plan(int64_t n, int32_t p, int64_t *out /* 4 */);
  * with oemgpu_set_timing on the context; 0 otherwise) [3] IRLS steps [4] inner iterations [5] row passes [6] Gram builds [7] wall ms */
 int oemgpu_last_logistic_stats(double *out /* 8 */);
 
+/* predict.oem's product on the device (ref R/methods.R:48-109, 346-367; predict.hip): out_dev[c n + i] = f(coef[c][0] + sum_j x_ij
+ * coef[c][1 + j]) for i < n, c < ncol -- [ncol][n], i.e. an n x ncol column-major matrix -- with f by type: 0 "link" (identity),
+ * 1 "response" (1 / (1 + exp(-eta))), 2 "class" (eta > 0 ? 1.0 : 0.0), applied in the store.  coef (HOST): [ncol][p + 1], slot 0 of a
+ * column its intercept (0.0 for none); it may go when the call returns (the call synchronises the context's stream).  x_dev: column-major
+ * float64 with column stride ld >= n, read where it lies.  The product runs on the FP64 MFMA pipe, rows of x against 16-column tiles of
+ * the table held in LDS -- whole, or in chunks of coefficient rows when it does not fit, so p has no limit -- with the intercept as a
+ * pseudo-column of ones; x is read once while ncol <= 112 and ceil(ceil(ncol / 16) / 7) times beyond.  Rows >= n and the padding of the
+ * last k-step are never loaded and enter by selection: a NaN or Inf at x[i][j] reaches row i of out and no other element.  No atomics:
+ * two calls give the same bits, and so do the three dense layouts for the same values.
+ * OEMGPU_ERR_ARG before a device is looked for: a NULL ctx or pointer, n, p or ncol < 1, type outside 0..2, ld < n, an x_dev that is
+ * not on an 8-byte boundary. */
+int oemgpu_predict_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *coef, int32_t ncol, int32_t type,
+                       double *out_dev);
+/* oemgpu_predict_dev (ref R/methods.R:48-109, 346-367) on a ROW-major x_dev (x[i * ldr + j], ldr >= p) of dtype OEMGPU_F64 or
+ * OEMGPU_F32, aligned to its element size only, read where it lies; float32 is widened in the register it was loaded into and all
+ * arithmetic is FP64.  Columns p .. ldr - 1 of a row and rows >= n are never read.  The same operand values reach the MFMAs in the
+ * same order as from the column-major entry: the same bits for the same values.  OEMGPU_ERR_ARG before a device is looked for: the
+ * refusals of oemgpu_predict_dev (its `ld < n` has no counterpart), a dtype that is neither code, ldr < p and an x_dev that is not
+ * aligned to its element. */
+int oemgpu_predict_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *coef, int32_t ncol,
+                          int32_t type, double *out_dev);
+/* oemgpu_predict_dev (ref R/methods.R:48-109, 346-367: a dgCMatrix newx is multiplied as it is) on the resident sparse x: n and p are
+ * the handle's, coef [ncol][x->p + 1], out_dev [ncol][x->n].  Every row is read from the compressed-row copy, its stored entries in
+ * column order, with scalar FP64 FMAs from the intercept on; the table sits in LDS when its ncol (p + 1) doubles fit 140 KiB and is read
+ * through the cache otherwise.  The summation order is not the dense kernel's, so neither are the last bits; two calls give the same
+ * bits.  OEMGPU_ERR_ARG before a device is looked for: a NULL ctx, handle or pointer, ncol < 1, type outside 0..2; and for a handle on
+ * another device than the context's. */
+int oemgpu_predict_sparse_res(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, const double *coef, int32_t ncol, int32_t type, double *out_dev);
+/* Host-only plan of the two dense predict entries (ref R/methods.R:48-109, 346-367 is what they compute; pure arithmetic, runs without a
+ * GPU; the entries take their launch shape from the same function).  layout: -1 column-major, OEMGPU_F64 or OEMGPU_F32 row-major (one
+ * shape for the three: they differ in their loads only).  out[0] rows per workgroup (a multiple of 128; workgroup g takes rows
+ * [g out[0], min(n, (g + 1) out[0]))), out[1] workgroups (none empty; at most two per CU while two fit its LDS, else one), out[2]
+ * 16-column tiles per pass (<= 7), out[3] passes over x (1 while ncol <= 112), out[4] 0 if the coefficient tile of a pass -- K4 =
+ * (p + 1 rounded up to 4) rows of 16 out[2] doubles -- stays in LDS (it fits 140 KiB) and 1 if it goes through LDS in chunks, out[5]
+ * coefficient rows in LDS at once (K4, or 112 per chunk), out[6] dynamic LDS bytes (8 * 16 out[2] out[5], and 17,408 for the eight
+ * waves' transposing tiles), out[7] chunks (1 unless out[4]).  OEMGPU_ERR_ARG for n, p, ncol or num_cu < 1, a layout that is none of
+ * the three or a NULL out. */
+int oemgpu_selftest_predict_plan(int64_t n, int32_t p, int32_t ncol, int32_t layout, int32_t num_cu, int64_t *out /* 8 */);
+
 /* Self-test aid (tests/test_gpu_host.py): enqueue, on the context's stream, `blocks` workgroups that each occupy a whole CU and
  * spin for `ms` milliseconds -- "somebody else holds the CUs", for the fallback of the persistent engines.  Asynchronous. */
 int oemgpu_selftest_hold_cus(oemgpu_ctx *ctx, int32_t blocks, double ms);

@@ -85,6 +85,10 @@ _SIGS = {
                                                        C.c_double, C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_logistic_cv_score_sparse_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, _dp, C.c_int32, _dp,
                                                        C.POINTER(C.c_int64), C.c_void_p]),
+    "oemgpu_predict_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_void_p]),   # R/methods.R:48-109, 346-367
+    "oemgpu_predict_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_void_p]),
+    "oemgpu_predict_sparse_res": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_int32, C.c_int32, C.c_void_p]),
+    "oemgpu_selftest_predict_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_selftest_csc_plan": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_last_logistic_stats": (C.c_int, [_dp]),
     "oemgpu_fit_xtx": (C.c_int, [_dp, _dp, C.c_int32, _dp, C.POINTER(OemgpuOpts)] + _OUT),

@@ -1681,7 +1681,10 @@ def predict_cv(fit, newx=None, which_model="best.model", s="lambda.min", **kw):
 
 # ------------------------------------------------------------------------------------------ consumers
 def predict(fit, newx=None, s=None, which_model=0, type="link"):
-    """predict.oem, R/methods.R:48-109 (which_model is 0-based or a penalty name)."""
+    """predict.oem, R/methods.R:48-109 (which_model is 0-based or a penalty name).
+    newx: a numpy array, a scipy.sparse matrix or a CPU tensor -- multiplied on the host, a numpy result -- or a torch device tensor or
+    an open SparseX: the column choice and the interpolation stay here, the product and the link run where newx lies (_predict_device)
+    and the n x ncol result is a tensor on its device."""
     if isinstance(which_model, str):
         if which_model not in fit["penalty"]:
             raise ValueError(f"Model {which_model} specified, but {which_model} not computed.")
@@ -1699,6 +1702,8 @@ def predict(fit, newx=None, s=None, which_model=0, type="link"):
         return _nonzero_lists(nbeta)
     if newx is None:
         raise ValueError("A value for 'newx' must be supplied")
+    if isinstance(newx, SparseX) or _is_torch_cuda(newx):                                  # on the device, where newx lies
+        return _predict_device(newx, nbeta, type if fit.get("family") == "binomial" else "link")
     if hasattr(newx, "tocsc") and newx.__class__.__module__.startswith("scipy.sparse"):    # a dgCMatrix newx: R multiplies it as it is (R/methods.R:48-109)
         import scipy.sparse as sp
         newx = sp.csc_matrix(newx, dtype=np.float64)
@@ -1716,6 +1721,56 @@ def predict(fit, newx=None, s=None, which_model=0, type="link"):
         if type == "class":
             return np.where(nfit > 0, 1, 0)
     return nfit
+
+
+def _predict_rowmajor_in_place(x):
+    """The dtype code with which predict() hands a device tensor to oemgpu_predict_rm_dev as it lies, or None: then it goes the
+    column-major way (a tensor that is already column-major is read in place there; one strided in its columns, or of another element
+    type, through _device_matrix's copy).  No limit on n or p."""
+    if x.ndim == 2 and x.stride(0) == 1 and x.stride(1) >= x.shape[0]:
+        return None
+    return _rowmajor_dtype(x)
+
+
+_PREDICT_TYPES = {"link": 0, "response": 1, "class": 2}
+
+
+def _predict_device(newx, nbeta, kind):
+    """predict()'s product for a torch device tensor or an open SparseX (oemgpu_predict_dev / _rm_dev / _sparse_res): newx is read where
+    it lies and the n x ncol result -- float64, a column-major view of the [ncol][n] buffer the kernel wrote; int64 for "class", as
+    np.where gives -- stays on its device.  nbeta: the (interpolated) coefficient table, one column per value of s.  The column rule of
+    the host path: a newx with as many columns as nbeta has rows is multiplied as it is, one column fewer gets the intercept."""
+    import torch
+    sparse = isinstance(newx, SparseX)
+    if sparse:
+        handle = newx.handle                                           # (a closed SparseX: ValueError)
+    elif newx.ndim != 2:
+        raise ValueError(f"newx must be a matrix: a 2-d tensor, not one of {newx.ndim} dimensions")
+    n, p = int(newx.shape[0]), int(newx.shape[1])
+    nbeta = np.asarray(nbeta, dtype=np.float64).reshape(nbeta.shape[0], -1)
+    q, ncol = nbeta.shape
+    if p == q:
+        coef = np.zeros((ncol, p + 1))
+        coef[:, 1:] = nbeta.T
+    elif p == q - 1:
+        coef = np.ascontiguousarray(nbeta.T)
+    else:
+        raise ValueError(f"newx has {p} columns, but the model takes {q - 1} (or {q} with a column for its first coefficient)")
+    if n < 1 or ncol < 1:
+        raise ValueError("newx has no rows" if n < 1 else "no model column to predict with")
+    if kind not in _PREDICT_TYPES:
+        kind = "link"
+    device = newx.device
+    out = torch.empty((ncol, n), dtype=torch.float64, device=device)
+    ctx = context(device.index)
+    torch.cuda.current_stream(device).synchronize()
+    if sparse:
+        L.check(L.lib().oemgpu_predict_sparse_res(ctx, handle, _dptr(coef), ncol, _PREDICT_TYPES[kind], out.data_ptr()))
+    else:
+        _DeviceX(newx, _predict_rowmajor_in_place).call("predict", ctx, _dptr(coef), ncol, _PREDICT_TYPES[kind], out.data_ptr())
+    if kind == "class":
+        out = out.to(torch.int64)
+    return out.t()
 
 
 def predict_xval(fit, newx=None, which_model="best.model", s="lambda.min", **kw):
