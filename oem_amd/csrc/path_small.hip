@@ -36,7 +36,7 @@ namespace {
 // Its fences forbid overlaps the real kernel has: read the SHARES, never the total.
 // Slots 0-4: the five segments of a full OEM round; 18, 20-23: the same five of a short round (tools/path_round_segments.py).
 #ifdef OEM_PATH_DIAG
-__device__ unsigned long long g_diag[24];
+__device__ unsigned long long g_diag[48];
 #define OEM_STAMP(slot)                                                                    \
     do {                                                                                   \
         __builtin_amdgcn_sched_barrier(0);                                                 \
@@ -46,11 +46,24 @@ __device__ unsigned long long g_diag[24];
         diag_acc[slot] += t__ - diag_last;                                                 \
         diag_last = t__;                                                                   \
     } while (0)
-#define OEM_DIAG_DECL unsigned long long diag_acc[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, diag_last = __builtin_amdgcn_s_memtime();
-#define OEM_DIAG_ARGS , unsigned long long (&diag_acc)[24], unsigned long long &diag_last
+// The row-split kernel outside its rounds (tools/path_fixed_part.py), as read back after the launch:
+//   5 start vector | 6 Lanczos steps taken | 8 lambda advance | 9 all looks | 10 Lanczos steps + tests before a look | 12-16 the round
+//   slots 0-4 as the Lanczos steps used them | 17 orthogonalise + norm | 19 T stores, tests, next vector | 24 launch -> ranking done |
+//   25 matrix and vectors loaded | 26 A = dI - XX, grid constants | 27 operator constants, lambdas into LDS | 28 last stores |
+//   29 number of looks | 30 launch -> end | 31 sweeps of all looks | 32 + k, 40 + k: cycles, sweeps of look k (k < 8).
+// During the eigen step 30 and 31 hold the running totals of slot 7 and of the sweeps at the previous look.  OEM_STAMP_MEM also
+// waits for the global loads in flight, so a segment that issues loads pays for them itself.
+#define OEM_STAMP_MEM(slot)                                                                \
+    do {                                                                                   \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                   \
+        OEM_STAMP(slot);                                                                   \
+    } while (0)
+#define OEM_DIAG_DECL unsigned long long diag_acc[48] = {}, diag_last = __builtin_amdgcn_s_memtime();
+#define OEM_DIAG_ARGS , unsigned long long (&diag_acc)[48], unsigned long long &diag_last
 #define OEM_DIAG_PASS , diag_acc, diag_last
 #else
 #define OEM_STAMP(slot) do { } while (0)
+#define OEM_STAMP_MEM(slot) do { } while (0)
 #define OEM_DIAG_DECL
 #define OEM_DIAG_ARGS
 #define OEM_DIAG_PASS
@@ -890,22 +903,26 @@ __device__ __forceinline__ double waves_sum(double v, double *X, int &par, int w
 
 // ACC (the accelerate option) is a template parameter: as a run-time test it costs two taken scalar branches per round
 // on a chain where a fetch redirect is ~50 cycles.
-template <int NW, int CG, int CGL, int KIND, bool ACC>
+//
+// One call runs the lambdas k .. kend - 1 of a chunk.  `prep` (the caller's) sets lambda k's K and c and it = 0, `store` writes its
+// beta and niter.  As a call per lambda, with a short and a full round loop inside it, a lambda went through four to five taken
+// branches (loop exit, the skipped full loop, the critical edges between them, the lambda loop's back-edge): a quarter of a round each.
+template <int NW, int CG, int CGL, int KIND, bool ACC, class Prep, class Store>
 __device__ __forceinline__ void iterate_rows_t(const PathArgs &A, const PenK &K, const ThrK &c, const double (&a)[2][CG],
                                                const double *aL, double xy, double pf, int wslot,
                                                const int (&ecol)[(CG + CGL + 15) / 16],
                                                double &beta, double &ab, double &ak, int &it, int &conv, const RowsLds &S,
                                                int w, int lane, int &buf, const RowGrp &G, int rtop, bool &wide,
-                                               int &nshort OEM_DIAG_ARGS)
+                                               int &nshort, int &k, int kend, Prep &&prep, Store &&store OEM_DIAG_ARGS)
 {
-    const double tp = pf * K.L, tol = A.tol;
+    double tp = 0.0;                    // pf * K.L of the lambda at hand
+    const double tol = A.tol;
     const int maxit = A.maxit;
     constexpr int VS = RowsCfg<NW, CG, CGL>::VS;
     // the short round's FMA pairs per lane (0: this form has none): the group operators keep the full round, and a slice of eight
     // columns is short already
     constexpr int KS = (KIND != K_GRP && CG > 8) ? 8 : 0;
     bool left = false;                  // the short round met a non-zero beyond its cap
-    OEM_STAMP(8);                       // per-lambda work since the last round
     auto round = [&](auto KS_) -> bool {
         constexpr int KSR = decltype(KS_)::value;
         // markers for oem_amd/build.py: audit_round_spills, audit_dpp_hazards (16 +: the short round)
@@ -972,29 +989,50 @@ __device__ __forceinline__ void iterate_rows_t(const PathArgs &A, const PenK &K,
         else return conv || it >= maxit;
     };
     // two rounds per trip: a taken branch (fetch redirect) costs ~80 cycles on this chain, a fall-through one nothing
-    bool done = false;
+    // Two plain loop nests, lambdas outside and rounds inside: the lambdas whose rounds are short, then the rest.  In each a lambda
+    // costs the exit of its round loop (a fall-through after the second round of a trip, a taken branch after the first) and the
+    // lambda loop's back-edge.
+    bool resume = false;                // the short loop handed over in mid-lambda
     if constexpr (KS > 0) {
         // The short rounds, while the vector's non-zeros stay within the first 4 KS ranked rows.  The round that finds one beyond them
         // has completed its product itself; the lambda goes on in the full loop.
-        if (!wide) {
-            for (;;) {
-                if (round(std::integral_constant<int, KS>{})) break;
-                if (round(std::integral_constant<int, KS>{})) break;
-            }
-            nshort += it - (left ? 1 : 0);
-            done = conv || it >= maxit;
+        // (k < kend: ols has one lambda, so in a later chunk of a call with more than LCH lambdas it has none to run, and the nest below
+        // is a do-while.  The test sits HERE: around the call in lambda_loop it made hipcc allocate the round loops of every operator
+        // differently, ~50 cycles per round at c1; as a skip at the head of the chunk loop it spilled into the eight-wave rounds.)
+        if (!wide && k < kend) {
+            do {
+                prep();
+                tp = pf * K.L;
+                OEM_STAMP(8);           // per-lambda work since the last round
+                for (;;) {
+                    if (round(std::integral_constant<int, KS>{})) break;
+                    if (round(std::integral_constant<int, KS>{})) break;
+                }
+                nshort += it - (left ? 1 : 0);
+                if (__builtin_expect(!(conv || it >= maxit), 0)) { resume = true; break; }
+                store();
+                ++k;
+            } while (__builtin_expect(!left, 1) && k < kend);
+            // The next lambda starts from this vector: short while no short round has met a non-zero beyond the cap.  Once the path
+            // has left for the full loop it stays there (the full round publishes no prefixes: it is the round of a dense problem,
+            // which pays nothing for this; on a lasso path the support seldom shrinks back under the cap).
+            wide = left;
         }
     }
-    if (!done) {
+    while (k < kend) {
+        if (__builtin_expect(!resume, 1)) {
+            prep();
+            tp = pf * K.L;
+            OEM_STAMP(8);
+        }
+        resume = false;
         for (;;) {
             if (round(std::integral_constant<int, 0>{})) break;
             if (round(std::integral_constant<int, 0>{})) break;
         }
+        store();
+        ++k;
     }
-    // The next lambda starts from this vector: short while no short round has met a non-zero beyond the cap.  Once the path has
-    // left for the full loop it stays there (the full round publishes no prefixes: it is the round of a dense problem, which pays
-    // nothing for this; on a lasso path the support seldom shrinks back under the cap).
-    if constexpr (KS > 0) wide = wide || left;
 }
 template <int NW, int CG, int CGL>
 __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
@@ -1006,6 +1044,7 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
     const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, l16 = lane & 15, g = lane >> 4;
     const int p = A.p;
     const unsigned long long t_cyc0 = __builtin_amdgcn_s_memtime(), t_rt0 = __builtin_amdgcn_s_memrealtime();
+    OEM_DIAG_DECL
     RowsLds S;
     S.V = lds + C::OFF_V; S.XA = lds + C::OFF_XA; S.XN = lds + C::OFF_XN;
     S.F = reinterpret_cast<int *>(lds + C::OFF_F);
@@ -1021,8 +1060,8 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
     int *ORIG = reinterpret_cast<int *>(lds + C::OFF_S + C::ML), *RNK = ORIG + C::ML;
     static_assert(NW * 64 >= C::ML && 2 * C::ML <= C::OFF_TH - C::OFF_S, "one variable per thread; ML keys and 2 ML ints fit the Sturm scratch");
     if (tid < p) {
-        const double f = A.pf[tid];
-        KEY[tid] = (f == 0.0) ? ~0ull : (unsigned long long)__double_as_longlong(fabs(A.xy[tid] / f));
+        const double f = A.pf[tid], xyt = A.xy[tid];                 // (both loads in flight together)
+        KEY[tid] = (f == 0.0) ? ~0ull : (unsigned long long)__double_as_longlong(fabs(xyt / f));
     }
     __syncthreads();
     if (tid < p) {
@@ -1036,6 +1075,7 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
         ORIG[before] = tid; RNK[tid] = before;
     }
     __syncthreads();
+    OEM_STAMP_MEM(24);                                               // launch -> ranking done
     const int RWp = (p + NW - 1) / NW;                               // rows per wave
     // this lane's row after the reduce-scatter: slot g & 1 of the wave's rows; groups 2, 3 replicate groups 0, 1
     const int rloc = 16 * (g & 1) + l16;
@@ -1078,6 +1118,10 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
     }
     const double xy = rowok ? A.xy[orow] : 0.0, pf = rowok ? A.pf[orow] : 0.0;
     const double sinv = (rowok && A.sinv) ? A.sinv[orow] : 1.0;
+    // (read here, a memory latency before their first use after the eigen step)
+    const double stat1 = A.stats[1], yy = A.stats[2], nobs = A.stats[3];
+    const double scaley = A.yscale ? stat1 : 1.0;
+    const double xl = (A.lmax_xy && rowok) ? A.lmax_xy[orow] : xy;
     // dummy words must hold finite numbers before anyone reads them
     for (int k = tid; k < 2 * C::VS; k += NW * 64) S.V[k] = 0.0;
     __syncthreads();
@@ -1085,7 +1129,6 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
     bool any_unused, wide_unused = false;
     double aux_unused = 0.0;
     int nshort = 0, nrounds = 0;                                     // OEM rounds in the short form / in all, of penalty 0
-    OEM_DIAG_DECL
     if (A.ngroups > 0) {                                             // group member lists into LDS (group operators only)
         int *gx = reinterpret_cast<int *>(lds + C::OFF_GX);
         const int nm = A.gstart[A.ngroups];
@@ -1095,14 +1138,21 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
         }
         __syncthreads();
     }
+    OEM_STAMP_MEM(25);                                               // matrix, xy, pf in registers; vector buffers zeroed
 
     // ---- eigenvalue step: Lanczos with the vector spread over the waves (one entry per owner lane)
     int msteps = A.lanczos_steps < C::ML ? A.lanczos_steps : C::ML;
     double *theta_slot = lds + C::OFF_TH;
     double *tsink = lds + C::OFF_TH + 2 + tid;                       // a scratch word per lane: stores without exec branches
+#ifdef OEM_PATH_DIAG
+    int look_sweeps = 0;
+#define OEM_LOOK_SWEEPS , &look_sweeps
+#else
+#define OEM_LOOK_SWEEPS
+#endif
     auto top_ritz = [&](int m, double hint) {
         if (w == 0) {
-            const double th = tridiag_max(Tal, Tbe, m, lane, lds + C::OFF_S, hint);
+            const double th = tridiag_max(Tal, Tbe, m, lane, lds + C::OFF_S, hint OEM_LOOK_SWEEPS);
             if (lane == 0) theta_slot[0] = th;
         }
         __syncthreads();
@@ -1139,7 +1189,14 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
         for (int j = 0; j < NBC; ++j) { Bv[j] = Bw[j] * ib; Bvp[j] = 0.0; }
     }
     OEM_STAMP(5);                                                    // prologue: matrix and vectors into registers
-    for (int j = 0; j < msteps; ++j) {
+    // Two loops: the steps up to the next look (every 8 steps from 16 on, lanczos_check_due) or to the cap, and the looks around
+    // them.  A step then ends in one untaken branch (breakdown) and its loop's back-edge; with the look inside the step loop its tail
+    // went through two to three taken branches, ~80 cycles each on this chain.
+    bool exact = false;
+    for (int j = 0; j < msteps;) {
+        int jend = j < 16 ? 16 : j + 8;
+        jend = jend < msteps ? jend : msteps;
+        do {
         const double wv = rows_product<NW, CG, CGL>(a, aL, Bv);
         double share = rows_sum(v * wv);                             // this wave's rows of alpha = v'Av (padding lanes hold 0)
         OEM_STAMP(3);
@@ -1167,23 +1224,34 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
         OEM_STAMP(17);
         *(tid == 0 ? &Tbe[j] : tsink) = bb;
         nst = j + 1;
-        if (__builtin_expect(__any(!(bb > 1e-13 * fabs(al))), 0)) break;   // invariant subspace reached: T is exact
-        if (__builtin_expect(lanczos_check_due(nst) && nst < msteps, 0)) {
-            OEM_STAMP(6);
-            const double th = top_ritz(nst, theta_prev);
-            OEM_STAMP(7);
-            if (__any(lanczos_converged(th, theta_prev, mv_prev))) { theta = th; have_theta = true; break; }
-        }
+        exact = __any(!(bb > 1e-13 * fabs(al)));                     // invariant subspace reached: T is exact
+        if (__builtin_expect(exact, 0)) break;
         vp = v; v = wn * ib; bprev = bb;
 #pragma unroll
         for (int jj = 0; jj < NBC; ++jj) { Bvp[jj] = Bv[jj]; Bv[jj] = Bw[jj] * ib; }
         OEM_STAMP(19);
+        } while (++j < jend);
+        if (exact || j >= msteps) break;
+        {                                                            // (nst = j is 16, 24, ...: a look is due, and steps are left)
+            OEM_STAMP(6);
+            const double th = top_ritz(nst, theta_prev);
+            OEM_STAMP(7);
+#ifdef OEM_PATH_DIAG
+            if (diag_acc[29] < 8) { diag_acc[32 + diag_acc[29]] = diag_acc[7] - diag_acc[30]; diag_acc[40 + diag_acc[29]] = (unsigned long long)look_sweeps - diag_acc[31]; }
+            ++diag_acc[29]; diag_acc[30] = diag_acc[7]; diag_acc[31] = (unsigned long long)look_sweeps;
+#endif
+            if (__any(lanczos_converged(th, theta_prev, mv_prev))) { theta = th; have_theta = true; break; }
+        }
     }
     if (!have_theta) theta = top_ritz(nst, theta_prev);
     const double d = theta * 1.005;                                  // ref src/oem_dense.h:498
     if (tid == 0) { A.d_out[0] = d; A.d_out[1] = theta; A.d_out[4] = (double)nst; A.d_out[5] = (!have_theta && nst >= msteps && nst < p) ? 1.0 : 0.0; A.d_out[6] = 0.0; }
 #ifdef OEM_PATH_DIAG
     OEM_STAMP(7);                                                    // the final top_ritz (slot 7: all top_ritz calls)
+    if (!have_theta) {                                               // (slots 32 + k / 40 + k: cycles / sweeps of look k; 29: looks)
+        if (diag_acc[29] < 8) { diag_acc[32 + diag_acc[29]] = diag_acc[7] - diag_acc[30]; diag_acc[40 + diag_acc[29]] = (unsigned long long)look_sweeps - diag_acc[31]; }
+        ++diag_acc[29];
+    }
     unsigned long long lz[5];
     for (int k = 0; k < 5; ++k) { lz[k] = diag_acc[k]; diag_acc[12 + k] = lz[k]; diag_acc[k] = 0; }
     diag_acc[10] = lz[0] + lz[1] + lz[2] + lz[3] + lz[4] + diag_acc[6];   // Lanczos steps: gemv_rows + vector work
@@ -1208,23 +1276,21 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
     }
 
     // ---- lambda grid constants (ref src/oem_dense.cpp:175-192)
-    const double scaley = A.yscale ? A.stats[1] : 1.0;
-    const double yy = A.stats[2], nobs = A.stats[3];
-    double lmax;
-    {
+    double llo = 0.0, lhi = 0.0;
+    if (!A.user_lambda) {                                            // (a supplied sequence needs none of this: no exchange, no logarithms)
         // max |xy| over all rows: wave maxima through per-lane words, then a max over the four words
-        const double xl = (A.lmax_xy && rowok) ? A.lmax_xy[orow] : xy;
         const double wm = wave_max(orow >= A.lmax_from ? fabs(xl) : 0.0);     // padding lanes: xy = 0
         S.XN[(par * NW + w) * 64 + lane] = wm;
         __syncthreads();
         const double x = S.XN[(par * NW + (lane & (NW - 1))) * 64 + lane];
         par ^= 1;
-        lmax = wave_max(x) * scaley;
+        const double lmax = wave_max(x) * scaley;
+        llo = log(lmax); lhi = log(A.lambda_min_ratio * lmax);
     }
     const int nl = A.nl;
-    const double llo = log(lmax), lhi = log(A.lambda_min_ratio * lmax);
     const double lstep = nl > 1 ? (lhi - llo) / (double)(nl - 1) : 0.0;
     const bool lflip = fabs(lhi) < fabs(llo);
+    OEM_STAMP_MEM(26);                                               // A = d I - XX, lambda-grid constants
 
     // Stores without exec-masked branches (a taken branch is ~80 cycles on this chain and three of the four waves would
     // take every one of them): lanes that own nothing aim at a scratch word of their own in A.work.
@@ -1297,13 +1363,18 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
             const size_t bstride = owner ? (size_t)p : 0;
             int *nptr = t0 ? &A.niter[(size_t)pp * nl + base] : sinki;
             const size_t nstride = t0 ? 1 : 0;
-            for (int k = 0; k < kend; ++k) {
+            OEM_STAMP_MEM(27);                                           // operator constants, lambda values into LDS
+            // lambda k's constants and its stores, for the loops of iterate_rows_t
+            int k = 0, it = 0, conv = 0;
+            PenK K;
+            auto prep = [&]() {
                 const double il = lam_next;
                 lam_next = LAM[k + 1 < cnt ? k + 1 : k];
-                const PenK K = pen_from_linear(PL, il, d, A.gamma);
+                K = pen_from_linear(PL, il, d, A.gamma);
                 if (__builtin_expect(ridge, 0)) c = uniform_thr(thr_consts<KIND>(K, d));
-                int it = 0, conv = 0;
-                iterate_rows_t<NW, CG, CGL, KIND, ACC>(A, K, c, a, aL, xy, pf, wslot, ecol, beta, ab, ak, it, conv, S, w, lane, buf, G, rtop, wide, pshort OEM_DIAG_PASS);
+                it = 0; conv = 0;
+            };
+            auto store = [&]() {
                 prounds += it;
                 // (the loss is taken in the coordinates of the iteration, before any in-place rescale)
                 if (__builtin_expect(A.compute_loss != 0, 0)) {
@@ -1318,8 +1389,10 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
                 *nptr = conv ? it : A.maxit + 1; nptr += nstride;         // ref src/oem_base.h:94-109
                 if (__builtin_expect(A.sinv != nullptr, 0))
                     ab = gemv_rows<NW, CG, CGL, false, false>(a, aL, beta, wslot, ecol, false, any_unused, aux_unused, S, w, lane, buf, nullptr, rtop, wide_unused OEM_DIAG_PASS);
-            }
+            };
+            iterate_rows_t<NW, CG, CGL, KIND, ACC>(A, K, c, a, aL, xy, pf, wslot, ecol, beta, ab, ak, it, conv, S, w, lane, buf, G, rtop, wide, pshort, k, kend, prep, store OEM_DIAG_PASS);
             __syncthreads();                                             // LAM is rewritten by the next chunk
+            OEM_STAMP_MEM(28);                                           // the last lambda's stores
         }
         if (pp == 0) { nshort = pshort; nrounds = prounds; }
     };
@@ -1346,7 +1419,8 @@ __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
         }
     }
 #ifdef OEM_PATH_DIAG
-    if (tid == 0) for (int k = 0; k < 24; ++k) g_diag[k] = diag_acc[k];
+    diag_acc[30] = __builtin_amdgcn_s_memtime() - t_cyc0;            // launch -> here, stamps included
+    if (tid == 0) for (int k = 0; k < 48; ++k) g_diag[k] = diag_acc[k];
 #endif
     if (tid == 0) {
         A.d_out[2] = (double)(__builtin_amdgcn_s_memtime() - t_cyc0);
@@ -1396,6 +1470,10 @@ template <int R, int NW, int CW, int G = 1> int launch_cfg(hipStream_t s, const 
 extern "C" __attribute__((visibility("default"))) int oemgpu_diag_read(unsigned long long *out)
 {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_diag), sizeof(unsigned long long) * 24) == hipSuccess ? 0 : -1;
+}
+extern "C" __attribute__((visibility("default"))) int oemgpu_diag_read_all(unsigned long long *out)      // all 48 slots
+{
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_diag), sizeof(unsigned long long) * 48) == hipSuccess ? 0 : -1;
 }
 #endif
 

@@ -2,7 +2,10 @@
 """Cost model of the small-p path kernel from whole-kernel cycle counts (no stamps, the product library):
 cycles(nlambda, maxit) = lanczos + nlambda * per_lambda + rounds * per_round, fitted from a few runs.
 
-    python tools/path_cost.py [p] [penalty]
+    python tools/path_cost.py [p] [penalty] [heavy]
+
+heavy: two more rows, 100 lambdas with 32 and 64 rounds each, and the cycles per round between them -- the round's cost with the
+fixed part and the lambda advance cancelled, where the fit's three terms trade cycles among themselves.
 """
 import ctypes as C
 import sys
@@ -50,6 +53,13 @@ for nl, maxit in ((1, 1), (100, 1), (100, 2), (100, 4), (100, 8), (50, 8)):
     c, r = cycles(lambda_=lam[:nl], maxit=maxit, tol=1e-300)
     rows.append((nl, maxit, r, c))
     print(f"nlambda={nl:4d} maxit={maxit:2d} rounds={r:5d} cycles={c:10.0f}")
+if len(sys.argv) > 3 and sys.argv[3] == "heavy":
+    heavy = []
+    for maxit in (32, 64):
+        c, r = cycles(lambda_=lam[:100], maxit=maxit, tol=1e-300)
+        heavy.append((r, c))
+        print(f"nlambda= 100 maxit={maxit:2d} rounds={r:5d} cycles={c:10.0f}")
+    print(f"p={p} {pen}: {(heavy[1][1] - heavy[0][1]) / (heavy[1][0] - heavy[0][0]):.1f} cycles per round between the rows of 32 and 64 rounds per lambda")
 A = np.array([[1.0, nl, r] for nl, _, r, _ in rows]); bvec = np.array([c for *_, c in rows])
 sol, *_ = np.linalg.lstsq(A, bvec, rcond=None)
 print(f"p={p} {pen}: lanczos+fixed {sol[0]:.0f} cycles, per lambda {sol[1]:.0f}, per round {sol[2]:.0f}")
