@@ -128,7 +128,10 @@ int oemgpu_fit_dense_weighted(const double *x, int64_t n, int32_t p, const doubl
  * sqrt(mean diag / n) whose coefficient is rescaled in place after every lambda (ref src/oem_sparse.h:493-615, 897-917), lambda_zero
  * without the intercept slot (:854-863).  compute_loss (ref :919-944) for p + intercept <= 288.  With n > p the Gram takes one of two
  * routes: the compressed-column kernel when it fits in LDS, nnz <= 2 % of n p and n < 2^31, else the dense FP64-MFMA pass over
- * zero-filled row tiles of x (<= 2 GiB each).  n <= p is served without an intercept (OEMGPU_ERR_UNSUPPORTED with one).
+ * zero-filled row tiles of x (<= 2 GiB each).  n <= p is served without an intercept (OEMGPU_ERR_UNSUPPORTED with one, said before
+ * the arrays are checked and before any device is looked for): with nnz <= 2 % of n p and p > 1024 from the non-zeros themselves
+ * (oemgpu_fit_sparse_wide_res on a handle built for the call and freed after it: nothing of n p entries on the host or the device,
+ * any n the int32 row indices can name), else through a dense n x p copy and the dense p >= n engines as before.
  * Malformed compressed-column arrays get OEMGPU_ERR_ARG before any device is looked for. */
 int oemgpu_fit_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, const double *y,
                       int32_t standardize, int32_t intercept, const oemgpu_opts *o,
@@ -438,9 +441,13 @@ enum {
     OEMGPU_ENGINE_WCOOP = 6,     /* p >= n: the standardised X in vector registers (path_wcoop.hip) */
     OEMGPU_ENGINE_WRES = 7,      /* p >= n: ... and in the accumulator file (path_wcoop.hip: path_wres_kernel) */
     OEMGPU_ENGINE_WSTREAM = 8,   /* p >= n: persistent, X re-read every iteration (path_wcoop.hip: path_wstream_kernel) */
-    OEMGPU_ENGINE_WLAUNCHES = 9  /* p >= n: launch-per-iteration (path_large.hip: run_path_wide) */
+    OEMGPU_ENGINE_WLAUNCHES = 9, /* p >= n: launch-per-iteration (path_large.hip: run_path_wide) */
+    OEMGPU_ENGINE_SPARSE_WIDE = 10 /* p >= n on a sparse x: both products over the non-zeros (sparse_wide.hip) */
 };
 int oemgpu_last_path_engine(oemgpu_ctx *ctx, int32_t *engine, int32_t *persistent_fallbacks);
+/* The same for the entries that take host arrays and run on a context of the library's own (oemgpu_fit_sparse, oemgpu_fit_dense, ...):
+ * the engine of the most recent penalty x lambda path run by the calling thread, on whatever context.  -1 for a NULL engine. */
+int oemgpu_last_host_path_engine(int32_t *engine);
 /* OEMGPU_ENGINE_COOP with q <= 512 puts the cooperating workgroups of an instance on ONE XCD where the device's layout allows (the
  * exchange then stays in that XCD's L2).  Of the most recent path launch on this context: 0 not asked for, 1 ran on one XCD, 2 asked for,
  * refused by the launch's own proof of placement and made again with the exchange at device scope (this context does not ask again),
@@ -685,6 +692,29 @@ int64_t oemgpu_sparse_x_bytes(const oemgpu_sparse_x *x);
 int oemgpu_fit_logistic_sparse_fold_res(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
                                         int32_t leave_out, int32_t standardize, int32_t intercept, int32_t irls_maxit, double irls_tol,
                                         const oemgpu_opts *opts, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+/* oem() on the resident sparse x with n <= p and no intercept (ref src/oem_sparse.h:607-612, 638-647, 932-941; src/oem_big.h:537-541,
+ * 568-584, 743-764, 880-897): the data as they are (no centring, no scaling of y), u = X'(y - X beta)/n + d beta with
+ * d = 1.005 lambda_max(X X'/n); with standardize only lambda_zero (max |x_j'y| colsq_inv_j / n) and the returned coefficients
+ * (beta colsq_inv) carry the column scales, colsq = sum x^2 / (n - 1) with a zero made 1; compute_loss from the residual of the
+ * returned coefficients (1e99 where niter is 0).  Both products of an iteration run over the handle's non-zeros -- the compressed rows
+ * for X beta, the compressed columns for X't -- a few rows or columns to a wave, a long one to a workgroup, every sum in one fixed
+ * order (no floating-point atomics: two calls give the same bits); nothing of n p entries is allocated.  All 14 penalties, any group
+ * layout, several penalties in one call; opts.interrupt is polled between batches of iterations.  y_dev: n doubles on the device.
+ * Outputs as oemgpu_fit_sparse (row 0 of every coefficient column is the absent intercept, 0).  Checked before any device work:
+ * OEMGPU_ERR_ARG for a NULL argument, a handle on another device than the context's and n < 2; OEMGPU_ERR_UNSUPPORTED for n > p
+ * (oemgpu_fit_sparse serves that); then the checks of the options.  n is limited by the int32 row indices alone.
+ * oemgpu_last_path_engine reports OEMGPU_ENGINE_SPARSE_WIDE. */
+int oemgpu_fit_sparse_wide_res(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, const double *y_dev, int32_t standardize, const oemgpu_opts *opts,
+                               double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+/* Host-only plan of oemgpu_fit_sparse_wide_res and of oemgpu_fit_sparse's choice of it (pure arithmetic, runs without a GPU) for n rows,
+ * p columns, nnz non-zeros, a longest row / column of that many stored entries, on a device of num_cu CUs: out[0] 1 if
+ * oemgpu_fit_sparse sends an n <= p call this way (nnz <= 2 % of n p and p > 1024; OEM_SPARSE_GRAM=wide / nowide forces / forbids it; 0 for
+ * n > p), [1] rows per wave of the row pass (64 / lanes per row), [2] columns per wave of the column pass, [3] 1 if the long-row form
+ * (a workgroup per row of more than 32 x lanes entries) is used, [4] the same for columns, [5] workgroups of the row pass,
+ * [6] of the column pass (short forms), [7] bytes of the engine's own device workspace (four n-vectors, the Lanczos table, the lists
+ * of long rows and columns).  OEMGPU_ERR_ARG for non-positive n, p or num_cu, a negative count or a NULL out. */
+int oemgpu_selftest_sparse_wide_plan(int64_t n, int32_t p, int64_t nnz, int64_t longest_row, int64_t longest_col, int32_t num_cu,
+                                     int64_t *out /* 8 */);
 /* oemgpu_logistic_cv_score_dev on the resident sparse x (ref R/cv_oem.R:224-346): the same arguments with the handle in place of
  * x_dev, n, ld, p, the same outputs.  Every row is read from the compressed-row copy, its stored entries in column order; for finite
  * tables the sums, counts and predmat are the bits of oemgpu_logistic_cv_score_dev on the same matrix written out densely.  The launch

@@ -114,10 +114,13 @@ _SIGS = {
     "oemgpu_last_shift_advised": (C.c_int, [C.c_void_p]),
     "oemgpu_last_eigen_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "oemgpu_last_path_engine": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "oemgpu_last_host_path_engine": (C.c_int, [C.POINTER(C.c_int32)]),
     "oemgpu_last_placement": (C.c_int, [C.c_void_p]),
     "oemgpu_last_path_rounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "oemgpu_fit_sparse": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                     C.POINTER(OemgpuOpts)] + _OUT),
+    "oemgpu_fit_sparse_wide_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(OemgpuOpts)] + _OUT),
+    "oemgpu_selftest_sparse_wide_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_xval_dense": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.POINTER(OemgpuOpts)] + _OUT + [_dp, _dp]),
     "oemgpu_xval_sparse": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

@@ -372,7 +372,7 @@ def rowmajor_fold_order(x, y, foldid, nfolds):
 _ctx_cache = {}
 
 
-ENGINES = ("none", "rows", "coop", "rowcoop", "symcoop", "launches", "wcoop", "wres", "wstream", "wlaunches")   # OEMGPU_ENGINE_* (include/oemgpu.h)
+ENGINES = ("none", "rows", "coop", "rowcoop", "symcoop", "launches", "wcoop", "wres", "wstream", "wlaunches", "sparse-wide")   # OEMGPU_ENGINE_* (include/oemgpu.h)
 
 
 def last_path_engine(ctx=None):
@@ -381,6 +381,14 @@ def last_path_engine(ctx=None):
     e, f = C.c_int32(0), C.c_int32(0)
     L.check(L.lib().oemgpu_last_path_engine(ctx if ctx is not None else context(), C.byref(e), C.byref(f)))
     return ENGINES[e.value], f.value
+
+
+def last_host_path_engine():
+    """name of the kernel family that ran the calling thread's most recent penalty x lambda path, on whatever context -- for host
+    inputs (numpy, scipy.sparse), whose calls run on a context of the library's own (include/oemgpu.h: oemgpu_last_host_path_engine)."""
+    e = C.c_int32(0)
+    L.check(L.lib().oemgpu_last_host_path_engine(C.byref(e)))
+    return ENGINES[e.value]
 
 
 def last_path_rounds(ctx=None):

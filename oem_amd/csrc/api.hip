@@ -385,6 +385,7 @@ struct PlanIn {
     bool launches_only = false;      // d handed over (PathExtras::d_fixed): the launch-per-iteration Gram engine only
     bool loss_ext = false;           // the loss of ANOTHER Gram (PathExtras::loss_xx)
     int wide_n = 0;                  // > 0: the p >= n iteration through the standardised X itself (WideArgs::n rows), no Gram matrix
+    bool wide_sparse = false;        // ... through the non-zeros of a resident sparse x (WideArgs::sparse): the launches of run_path_sparse_wide only
 };
 // Which XCD does workgroup i of a launch run on?  The one-XCD form of the cooperating engine (path_coop.hip) assumes "i mod 8" up to a
 // rotation; this asks the hardware once per context (64 workgroups report HW_REG_XCC_ID), and every such launch proves its own
@@ -451,7 +452,7 @@ static int plan_paths(const PlanIn &in, PathPlan &P)
     // p >= n on the cooperating engine with group penalties: where every group is a run of neighbouring columns the columns are dealt
     // to the workgroups in whole groups (<= 4 CW columns each), so that no group's norm needs a value from another workgroup
     std::vector<int> &cst = P.cst;
-    if (wide && og.ngroups > 0 && !sw().OEM_WCOOP_NO_ALIGN.set) {
+    if (wide && !in.wide_sparse && og.ngroups > 0 && !sw().OEM_WCOOP_NO_ALIGN.set) {
         const int cpg = path_wcoop_cpg(in.wide_n), gmax = path_wcoop_max_workgroups(in.wide_n, q);
         bool ok = cpg > 0 && gmax > 0;
         cst.push_back(0);
@@ -473,7 +474,7 @@ static int plan_paths(const PlanIn &in, PathPlan &P)
     // p >= n beyond the persistent engines, group penalties: where every group is a run of neighbouring columns (<= WIDE_GRUN_MAX of
     // them) the runs are dealt to the workgroups of the fused group kernel (path_large.hip: wide_groups_kernel) in whole runs
     std::vector<int> &grs = P.grs, &grg = P.grg, &grw = P.grw;
-    if (wide && og.ngroups > 0) {
+    if (wide && !in.wide_sparse && og.ngroups > 0) {
         bool ok = true;
         int maxrun = 1;
         for (int j = 0; j < q && ok;) {
@@ -625,7 +626,7 @@ static int plan_paths(const PlanIn &in, PathPlan &P)
     P.rowcoop = P.symc && path_rowcoop_eligible(a, any_grp) && path_rowcoop_workgroups(q) <= num_cu * 3 / 4 &&
                 symcoop_work_bytes(symplan) >= path_rowcoop_xchg_bytes();
     P.symcoop = P.symc && (P.rowcoop || path_symcoop_eligible(a, any_grp, symplan.runs));
-    if (wide) {
+    if (wide && !in.wide_sparse) {
         WideArgs wd;                                   // (sizes only: the eligibility rules read the layout and n)
         wd.xs = nullptr; wd.ys = nullptr; wd.lay = wide_layout(in.wide_n); wd.n = in.wide_n; wd.scratch = nullptr;
         // p >= n with Xs small enough for the register files of <= 192 CUs: one persistent launch (path_wcoop.hip)
@@ -646,7 +647,7 @@ static int plan_paths(const PlanIn &in, PathPlan &P)
         P.wstream = !P.wcoop && !P.wres && (path_wcoop_workgroups(wd.n, q) > WCOOP_GMAX || sw().OEM_WSTREAM.set) && path_wstream_eligible(a, wd, P.wsg);      // (where it pays: measured there)
     }
     P.engine = P.rowcoop ? OEMGPU_ENGINE_ROWCOOP : P.symcoop ? OEMGPU_ENGINE_SYMCOOP : P.wres ? OEMGPU_ENGINE_WRES : P.wcoop ? OEMGPU_ENGINE_WCOOP
-               : P.wstream ? OEMGPU_ENGINE_WSTREAM : wide ? OEMGPU_ENGINE_WLAUNCHES : P.small ? OEMGPU_ENGINE_ROWS : P.coop ? OEMGPU_ENGINE_COOP : OEMGPU_ENGINE_LAUNCHES;
+               : P.wstream ? OEMGPU_ENGINE_WSTREAM : in.wide_sparse ? OEMGPU_ENGINE_SPARSE_WIDE : wide ? OEMGPU_ENGINE_WLAUNCHES : P.small ? OEMGPU_ENGINE_ROWS : P.coop ? OEMGPU_ENGINE_COOP : OEMGPU_ENGINE_LAUNCHES;
     return 0;
 }
 
@@ -705,6 +706,7 @@ static std::vector<int> group_run_permutation(const oemgpu_opts *o, int q, int m
 }
 
 static thread_local bool g_in_permuted_call = false;
+static thread_local int g_thread_engine = OEMGPU_ENGINE_NONE;      // c->last_engine of this thread's most recent path, whatever the context (oemgpu_last_host_path_engine)
 
 int run_paths(oemgpu_ctx *c, Bump &B, const double *xx, const double *xy, const double *stats, int p, int q, int sem,
               int standardize, int intercept, const oemgpu_opts *o, const double *scale_factor,
@@ -758,6 +760,7 @@ int run_paths(oemgpu_ctx *c, Bump &B, const double *xx, const double *xy, const 
     PlanIn pin;
     pin.num_cu = c->num_cu; pin.p = p; pin.q = q; pin.sem = sem; pin.intercept = intercept; pin.nbatch = nbatch; pin.o = o;
     pin.has_scale = scale_factor != nullptr; pin.launches_only = launches_only; pin.loss_ext = ex && ex->loss_xx; pin.wide_n = wide ? wide->n : 0;
+    pin.wide_sparse = wide && wide->sparse;
     PathPlan P;
     if (int prc = plan_paths(pin, P)) return prc;
     const bool any_grp = P.any_grp, symc = P.symc, coop = P.coop, small = P.small, pen_split = P.pen_split, loss_post = P.loss_post;
@@ -915,11 +918,13 @@ int run_paths(oemgpu_ctx *c, Bump &B, const double *xx, const double *xy, const 
             int rc;
             c->last_engine = (persistent && rowcoop) ? OEMGPU_ENGINE_ROWCOOP : (persistent && symcoop) ? OEMGPU_ENGINE_SYMCOOP : (persistent && wres) ? OEMGPU_ENGINE_WRES
                              : (persistent && wcoop) ? OEMGPU_ENGINE_WCOOP : (persistent && wstream) ? OEMGPU_ENGINE_WSTREAM : persistent ? OEMGPU_ENGINE_COOP
-                             : wide ? OEMGPU_ENGINE_WLAUNCHES : small ? OEMGPU_ENGINE_ROWS : (coop && attempt == 0) ? OEMGPU_ENGINE_COOP : OEMGPU_ENGINE_LAUNCHES;
+                             : (wide && wide->sparse) ? OEMGPU_ENGINE_SPARSE_WIDE : wide ? OEMGPU_ENGINE_WLAUNCHES : small ? OEMGPU_ENGINE_ROWS : (coop && attempt == 0) ? OEMGPU_ENGINE_COOP : OEMGPU_ENGINE_LAUNCHES;
+            g_thread_engine = c->last_engine;
             if (persistent && rowcoop) rc = launch_path_rowcoop(c->stream, a, a.work + sym_off_d);
             else if (persistent && symcoop) rc = launch_path_symcoop(c->stream, a, symplan, (const int *)(dblob + o_symp), a.work + sym_off_d);
             else if (persistent && wres) rc = launch_path_wres(c->stream, a, *wide);
             else if (persistent) rc = wcoop ? launch_path_wcoop(c->stream, a, *wide, wsets, wcst, wg_n) : wstream ? launch_path_wstream(c->stream, a, *wide, wsg) : launch_path_coop(c->stream, a);
+            else if (wide && wide->sparse) rc = run_path_sparse_wide(c->stream, a, *wide->sparse, (double *)c->pinned);
             else if (wide) rc = run_path_wide(c->stream, a, *wide, (double *)c->pinned);
             else if (small) rc = launch_path_small(c->stream, a);
             else if (coop && attempt == 0) rc = launch_path_coop(c->stream, a);                 // (several instances: no second engine takes them)
@@ -1597,7 +1602,8 @@ static int run_paths_parts(oemgpu_ctx *c, Bump B, const double *xx, const double
     std::vector<int> ie, ig;
     for (int k = 0; k < o->npen; ++k) (pen_is_grp(o->penalty[k]) ? ig : ie).push_back(k);
     bool split = !ie.empty() && !ig.empty() && !o->accelerate && !sw().OEM_NO_PENALTY_SPLIT.set;
-    if (split && wd) {
+    if (split && wd && wd->sparse) split = false;              // (one engine there: the launches over the non-zeros take every penalty)
+    else if (split && wd) {
         const int gw = path_wres_workgroups(wd->n, p);
         const bool wcoop_fits = path_wcoop_workgroups(wd->n, p) >= 1 && path_wcoop_workgroups(wd->n, p) <= (c->num_cu * 3 / 4 < WCOOP_GMAX ? c->num_cu * 3 / 4 : WCOOP_GMAX);
         split = !wcoop_fits && gw >= 1 && gw <= c->num_cu - 8 && path_wres_xchg_doubles(wd->n, p) > 0 && !sw().OEM_NO_WRES.set && !sw().OEM_NO_WCOOP.set;
@@ -2008,6 +2014,13 @@ int oemgpu_last_path_engine(oemgpu_ctx *c, int32_t *engine, int32_t *persistent_
     if (!c) return -1;
     if (engine) *engine = c->last_engine;
     if (persistent_fallbacks) *persistent_fallbacks = c->persistent_fallbacks;
+    return 0;
+}
+
+int oemgpu_last_host_path_engine(int32_t *engine)
+{
+    if (!engine) return -1;
+    *engine = g_thread_engine;
     return 0;
 }
 
@@ -3425,6 +3438,78 @@ int oemgpu_selftest_cv_sparse_plan(int64_t n, int32_t p, int64_t nnz, int32_t nf
     return 0;
 }
 
+// oem() on a resident sparse x with nobs <= nvars and no intercept: fit_big_wide_dev's iteration (the comment there) with both products
+// over the non-zeros of the handle (sparse_wide.hip; path_large.hip: run_path_sparse_wide).  Nothing of n p entries is allocated.
+int oemgpu_fit_sparse_wide_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const double *y_dev, int32_t standardize, const oemgpu_opts *o,
+                               double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+{
+    static const char *who = "fit_sparse_wide_res";
+    if (!c || !x || !y_dev || !o || !beta || !lambda_out || !niter || !loss || !d) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    if (c->device != x->device) { set_error("%s: the context and the sparse x are on different devices", who); return OEMGPU_ERR_ARG; }
+    if (x->n < 2) { set_error("%s: at least two rows", who); return OEMGPU_ERR_ARG; }
+    if (x->n > x->p) {
+        set_error("%s: n > p (%lld x %d) is the Gram form's: oemgpu_fit_sparse serves it", who, (long long)x->n, (int)x->p);
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    const int p = x->p, n = (int)x->n;                       // (n <= p: an int)
+    int rc = check_opts(o, p, p);
+    if (rc) return rc;
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    hipStream_t s = c->stream;
+    SpwArgs A;
+    A.colptr = x->colptr; A.rowptr = x->rowptr; A.rowidx = x->rowidx; A.ccol = x->ccol; A.val = x->val; A.cval = x->cval;
+    A.n = n; A.p = p;
+    A.plan = spw_plan(n, p, x->nnz, 0, 0, c->num_cu);        // (the lanes; the long forms once the lines have been looked at)
+    A.long_row_list = A.long_col_list = nullptr; A.n_long_rows = A.n_long_cols = 0;
+    Bump X;
+    const size_t a_vec = X.take(sizeof(double) * (4 * (size_t)n + SPW_T_DOUBLES)), a_lr = X.take(sizeof(int32_t) * ((size_t)n + 1)),
+                 a_lc = X.take(sizeof(int32_t) * ((size_t)p + 1)), a_cnt = X.take(64);
+    if (X.off != A.plan.ws_bytes) { set_error("internal: the sparse wide plan and its workspace disagree"); return OEMGPU_ERR_INTERNAL; }
+    ctx_void_cv(c);
+    if (ctx_grow(c, &c->aux, &c->aux_bytes, X.off)) return OEMGPU_ERR_HIP;
+    A.vec = (double *)(c->aux + a_vec);
+    int32_t *lrow = (int32_t *)(c->aux + a_lr), *lcol = (int32_t *)(c->aux + a_lc);
+    int *cnt = (int *)(c->aux + a_cnt);
+    if (ctx_pinned(c, 16384)) return OEMGPU_ERR_HIP;
+    if ((rc = launch_spw_scan(s, A, lrow, lcol, cnt))) return rc;
+    OEM_HIP(hipMemcpyAsync(c->pinned, cnt, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipStreamSynchronize(s));
+    {
+        const int *h = (const int *)c->pinned;
+        const int nlr = h[0], nlc = h[2];
+        A.plan = spw_plan(n, p, x->nnz, h[1], h[3], c->num_cu);
+        if (nlr < 0 || nlr > n || nlc < 0 || nlc > p || (nlr > 0) != (A.plan.long_rows != 0) || (nlc > 0) != (A.plan.long_cols != 0)) {
+            set_error("internal: the sparse wide plan and the lists of long lines disagree"); return OEMGPU_ERR_INTERNAL;
+        }
+        A.long_row_list = lrow; A.long_col_list = lcol; A.n_long_rows = nlr; A.n_long_cols = nlc;
+    }
+    Bump B;
+    const size_t a_xs2 = B.take((size_t)p * 8), a_xy = B.take((size_t)p * 8), a_st = B.take((size_t)stats_len(p) * 8);       // stats last (run_paths)
+    if (ctx_reserve(c, B.off + paths_ws_bytes(p, p, o) + 4096)) return OEMGPU_ERR_HIP;
+    double *xy = (double *)(c->ws + a_xy), *st = (double *)(c->ws + a_st), *xy_std = (double *)(c->ws + a_xs2);
+    {
+        Timer t(c, OEMGPU_T_MOMENTS);
+        if ((rc = launch_spw_stats(s, A, y_dev, standardize, xy, st, xy_std))) return rc;
+    }
+    WideArgs wd;
+    wd.xs = nullptr; wd.ys = nullptr; wd.lay = WideLayout{0, 0, 0}; wd.n = n; wd.scratch = nullptr; wd.sparse = &A;
+    rc = run_paths(c, B, nullptr, xy, st, p, p, OEMGPU_SEM_BIG, standardize, 0, o, nullptr, beta, lambda_out, niter, loss, d, 1, 0, false, &wd,
+                   standardize ? xy_std : nullptr);
+    if (rc || !o->compute_loss) return rc;
+    // oemSparse::get_loss with nobs <= nvars (ref src/oem_sparse.h:932-941): the residual of the RETURNED coefficients
+    const size_t nk = (size_t)o->npen * nl_of(o), nchunk = (size_t)((n + 2047) / 2048);
+    Bump L;
+    const size_t a_b = L.take(nk * (size_t)(p + 1) * 8), a_p = L.take(nk * nchunk * 8), a_l = L.take(nk * 8);
+    if (ctx_reserve(c, L.off + 4096)) return OEMGPU_ERR_HIP;          // (the paths are done: their frame may be overlaid)
+    double *bd = (double *)(c->ws + a_b), *ld_ = (double *)(c->ws + a_l);
+    OEM_HIP(hipMemcpyAsync(bd, beta, nk * (size_t)(p + 1) * 8, hipMemcpyHostToDevice, s));
+    if ((rc = launch_spw_loss(s, A, y_dev, bd, p + 1, (int)nk, A.vec, (double *)(c->ws + a_p), ld_))) return rc;
+    OEM_HIP(hipMemcpyAsync(loss, ld_, nk * 8, hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipStreamSynchronize(s));
+    for (size_t k = 0; k < nk; ++k) if (niter[k] == 0) loss[k] = 1e99;
+    return 0;
+}
+
 int oemgpu_fit_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, const double *y,
                       int32_t standardize, int32_t intercept, const oemgpu_opts *o,
                       double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
@@ -3438,8 +3523,37 @@ int oemgpu_fit_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t
                   "nothing well-formed to reproduce; intercept = FALSE is served");
         return OEMGPU_ERR_UNSUPPORTED;
     }
-    const int64_t maxcol = csc_check("fit_sparse", n, p, colptr, rowidx, values, nullptr);
+    // nobs <= nvars, sparse by sparse_wide_route's rule: from the non-zeros (sparse_wide.hip) -- the handle of oemgpu_sparse_x_create
+    // built once, y uploaded, oemgpu_fit_sparse_wide_res, the handle freed; nothing of n p entries on either side
+    const bool from_nnz = n >= 2 && n <= p && sparse_wide_route(n, p, colptr[p]);
+    std::vector<int64_t> rowptr;
+    const int64_t maxcol = csc_check("fit_sparse", n, p, colptr, rowidx, values, from_nnz ? &rowptr : nullptr);
     if (maxcol < 0) return (int)maxcol;
+    if (from_nnz) {
+        const int64_t nnz = colptr[p];
+        for (int64_t i = 0; i < n; ++i) rowptr[(size_t)i + 1] += rowptr[(size_t)i];
+        // the row copy on the host, every row's entries in column order (the columns are walked in order)
+        std::vector<int32_t> ccol;
+        std::vector<double> cval;
+        std::vector<int64_t> cur;
+        try { ccol.resize((size_t)nnz + 1); cval.resize((size_t)nnz + 1); cur.assign(rowptr.begin(), rowptr.end() - 1); }
+        catch (const std::bad_alloc &) { set_error("sparse x with p >= n: no host memory for the row copy of %lld non-zeros", (long long)nnz); return OEMGPU_ERR_ARG; }
+        for (int j = 0; j < p; ++j)
+            for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) { const int64_t pos = cur[(size_t)rowidx[k]]++; ccol[(size_t)pos] = j; cval[(size_t)pos] = values[k]; }
+        oemgpu_ctx *c = ctx_acquire(o->device);
+        if (!c) return OEMGPU_ERR_NO_DEVICE;
+        oemgpu_sparse_x *xh = nullptr;
+        rc = sparse_x_build(c, n, p, colptr, rowidx, values, rowptr, maxcol, &xh, ccol.data(), cval.data());
+        if (!rc && ctx_grow(c, &c->xres, &c->xres_bytes, sizeof(double) * (size_t)(n + 2))) rc = OEMGPU_ERR_HIP;
+        if (!rc && hipMemcpyAsync(c->xres, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+            set_error("fit_sparse: device staging failed"); rc = OEMGPU_ERR_HIP;
+        }
+        if (!rc) rc = oemgpu_fit_sparse_wide_res(c, xh, (const double *)c->xres, standardize, o, beta, lambda_out, niter, loss, d);
+        (void)hipStreamSynchronize(c->stream);
+        oemgpu_sparse_x_destroy(xh);
+        ctx_release(c);
+        return rc;
+    }
     if (n <= p) {
         // nobs <= nvars: the XXt branch (ref src/oem_sparse.h:607-612, 638-647) is oemBig's, line for line
         std::vector<double> xc;                                         // n <= p rows: the dense copy the wide engine reads

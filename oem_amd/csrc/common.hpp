@@ -101,6 +101,10 @@ int64_t csc_check(const char *who, int64_t n, int p, const int64_t *colptr, cons
 constexpr int CSC_CHUNK = 8192;     // rows per chunk of the compressed-column kernels: 64 KB of LDS
 struct SparseRoute { bool csc; int64_t rows, ld; };
 SparseRoute sparse_route(int64_t n, int p, int64_t nnz);
+// n <= p: does the fit run from the non-zeros (sparse_wide.hip) instead of the dense copy?  nnz <= 2 % of n p (sparse_route's density
+// limit) and p > 1024 (wide_pays's bound: below it the register engines run the p x p Gram form and the dense copy is small);
+// OEM_SPARSE_GRAM=wide forces it for any n <= p, =nowide forbids it
+bool sparse_wide_route(int64_t n, int p, int64_t nnz);
 // the tile route: per tile of R.rows rows zero it, densify (times sqrt(w[row]) if w), shard_moments -> mtile, add into M in row order.
 // y: the Gaussian fit's y, or null; tpart / vpart: the scratch of gram_plan_bound(R.rows, p)
 int csc_tile_moments(oemgpu_ctx *c, const SparseRoute &R, const int64_t *colptr, const int32_t *rowidx, const double *val, const double *w,
@@ -398,7 +402,46 @@ struct WideArgs {
     const int *grun_gid = nullptr;     // device: group index of each run
     const int *grun_wg = nullptr;      // device: grun_W + 1 run indices
     int grun_W = 0, grun_cpw = 0;      // workgroups; most columns in one workgroup
+    // not null: X is a resident sparse x and the two products run over its non-zeros (sparse_wide.hip; path_large.hip:
+    // run_path_sparse_wide).  xs, ys, lay and scratch are then unused, and n is bounded by the int32 row indices alone.
+    const struct SpwArgs *sparse = nullptr;
 };
+// ------------------------------------------------------------------ p >= n on a sparse x (sparse_wide.hip)
+// Both products are one gather over compressed lines: the row pass t_i = sum_k cval[k] v[ccol[k]] over the compressed rows, the
+// column pass g_j = sum_k val[k] w[rowidx[k]] over the compressed columns.  A line is taken by L = 1 .. 64 lanes of a wave (64 / L
+// lines to a wave, four waves to a workgroup), or -- longer than SPW_LONG_PER_LANE L entries -- by a whole workgroup (the long
+// form, over a list of such lines made once per call).  Every sum has one fixed order.  The plan is pure host arithmetic.
+constexpr int SPW_LONG_PER_LANE = 32;
+constexpr int SPW_T_DOUBLES = 1024;      // the Lanczos table behind the engine's vectors (path_large.hip: 2 MAXL)
+struct SpwPlan {
+    int route;               // sparse_wide_route
+    int row_L, col_L;        // lanes per row / per column in the short form
+    int long_rows, long_cols;    // is the long form used (the longest line exceeds SPW_LONG_PER_LANE L)?
+    int row_wgs, col_wgs;    // workgroups of the short form of either pass
+    size_t ws_bytes;         // the engine's own vectors, the Lanczos table and the two lists of long lines
+};
+SpwPlan spw_plan(int64_t n, int p, int64_t nnz, int64_t longest_row, int64_t longest_col, int num_cu);
+struct SpwArgs {
+    const int64_t *colptr, *rowptr;
+    const int32_t *rowidx, *ccol;
+    const double *val, *cval;
+    int n, p;
+    SpwPlan plan;
+    const int32_t *long_row_list, *long_col_list;    // device: the lines of the long form
+    int n_long_rows, n_long_cols;
+    double *vec;             // device: t | v | v_prev | w (n doubles each) | the Lanczos table
+};
+// out[i] = scale * sum over compressed row i (n of them) of cval v[ccol]; skipped while *done != 0 (done may be null)
+int launch_spw_rows(hipStream_t s, const SpwArgs &A, const double *v, double *out, double scale, const int *done);
+// out[j] = scale * sum over compressed column j (p of them) of val w[rowidx]
+int launch_spw_cols(hipStream_t s, const SpwArgs &A, const double *w, double *out, double scale, const int *done);
+int run_path_sparse_wide(hipStream_t s, const PathArgs &a, const SpwArgs &A, double *host_scratch);
+// the two lists of long lines (by A.plan's lanes) and the longest row and column: cnt (device, 4 ints) <- rows: number, longest | columns
+int launch_spw_scan(hipStream_t s, const SpwArgs &A, int32_t *row_list, int32_t *col_list, int *cnt);
+// xy = X'y / n, the scale slots of stats (colsq_inv with standardize, else 1) and xy_std = xy colsq_inv in one pass over the columns
+int launch_spw_stats(hipStream_t s, const SpwArgs &A, const double *y, int standardize, double *xy, double *stats, double *xy_std);
+// loss[k] = sum (y - X b_k)^2 of the returned coefficients b [nk][rows] (slot 0: the intercept); t: n doubles, part: nk ceil(n / 2048)
+int launch_spw_loss(hipStream_t s, const SpwArgs &A, const double *y, const double *b, int rows, int nk, double *t, double *part, double *loss);
 static const int WIDE_GRUN_MAX = 64;  // longest run (group) the fused group kernel takes
 static const int WIDE_MAX_N = 32768;         // 16 row blocks of 2048 rows
 int wide_workgroups(int n, int p);

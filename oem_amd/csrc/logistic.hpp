@@ -23,6 +23,12 @@ struct oemgpu_sparse_x {
 
 namespace oemgpu {
 
+// logistic_sparse.hip: the handle from compressed columns csc_check has passed (rowptr: the n + 1 row pointers of the row copy; h_ccol /
+// h_cval: that copy where the caller has made it on the host, else it is made on the device)
+int sparse_x_build(oemgpu_ctx *c, int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values,
+                   const std::vector<int64_t> &rowptr, int64_t maxcol, oemgpu_sparse_x **out, const int32_t *h_ccol = nullptr,
+                   const double *h_cval = nullptr);
+
 // The data-dependent stages of an IRLS fit.  Every stage enqueues on the context's stream.  g: p + 2 doubles, laid out as
 // [sum r, X'r (p), sum of the loss terms] (logit_xy_kernel and the loss read it so).
 struct LogitData {

@@ -416,6 +416,55 @@ static int lsp_check_csc(const char *who, int64_t n, int32_t p, const int64_t *c
     return 0;
 }
 
+// the handle itself from arrays csc_check has passed: rowptr the row pointers of the row copy (n + 1), maxcol the longest column.
+// h_ccol / h_cval: the row copy made by the caller on the host (every row's entries in column order), or null: csc_to_csr_kernel
+// makes it -- one workgroup per 8192 rows walking the columns in turn, which a wide x (few rows, very many columns) would wait on
+int sparse_x_build(oemgpu_ctx *c, int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values,
+                   const std::vector<int64_t> &rowptr, int64_t maxcol, oemgpu_sparse_x **out, const int32_t *h_ccol, const double *h_cval)
+{
+    *out = nullptr;
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const int64_t nnz = colptr[p];
+    Bump B;
+    const size_t a_cp = B.take(8 * (size_t)(p + 1)), a_ri = B.take(4 * (size_t)(nnz + 1)), a_v = B.take(8 * (size_t)(nnz + 1)),
+                 a_rp = B.take(8 * (size_t)(n + 1)), a_cc = B.take(4 * (size_t)(nnz + 1)), a_cv = B.take(8 * (size_t)(nnz + 1)),
+                 a_ch = B.take(4 * (size_t)(csc_chunks(n) + 1) * p);
+    oemgpu_sparse_x *x = new oemgpu_sparse_x;
+    x->device = c->device; x->n = n; x->p = p; x->nnz = nnz; x->maxcol = maxcol; x->bytes = B.off;
+    if (hipMalloc((void **)&x->base, B.off) != hipSuccess) {
+        set_error("sparse_x_create: cannot allocate %zu bytes of device memory", B.off);
+        delete x;
+        return OEMGPU_ERR_HIP;
+    }
+    g_alloc_count += 1;
+    x->colptr = (int64_t *)(x->base + a_cp); x->rowidx = (int32_t *)(x->base + a_ri); x->val = (double *)(x->base + a_v);
+    x->rowptr = (int64_t *)(x->base + a_rp); x->ccol = (int32_t *)(x->base + a_cc); x->cval = (double *)(x->base + a_cv);
+    x->cptr = (int32_t *)(x->base + a_ch);
+    hipStream_t s = c->stream;
+    auto build = [&]() -> int {
+        OEM_HIP(hipMemcpyAsync(x->colptr, colptr, 8 * (size_t)(p + 1), hipMemcpyHostToDevice, s));
+        if (nnz > 0) {
+            OEM_HIP(hipMemcpyAsync(x->rowidx, rowidx, 4 * (size_t)nnz, hipMemcpyHostToDevice, s));
+            OEM_HIP(hipMemcpyAsync(x->val, values, 8 * (size_t)nnz, hipMemcpyHostToDevice, s));
+        }
+        OEM_HIP(hipMemcpyAsync(x->rowptr, rowptr.data(), 8 * (size_t)(n + 1), hipMemcpyHostToDevice, s));
+        int r = launch_csc_chunk_ptr(s, x->colptr, x->rowidx, n, p, x->cptr);
+        if (!r && h_ccol && h_cval) {
+            if (nnz > 0) {
+                OEM_HIP(hipMemcpyAsync(x->ccol, h_ccol, 4 * (size_t)nnz, hipMemcpyHostToDevice, s));
+                OEM_HIP(hipMemcpyAsync(x->cval, h_cval, 8 * (size_t)nnz, hipMemcpyHostToDevice, s));
+            }
+        } else if (!r) r = launch_csc_to_csr(s, x->colptr, x->rowidx, x->val, x->cptr, n, p, x->rowptr, x->ccol, x->cval);
+        if (r) return r;
+        OEM_HIP(hipStreamSynchronize(s));                  // the host arrays (rowptr among them) may go once this returns
+        return 0;
+    };
+    const int rc = build();
+    if (rc) { (void)hipStreamSynchronize(s); (void)hipFree(x->base); delete x; return rc; }
+    *out = x;
+    return 0;
+}
+
 }  // namespace oemgpu
 
 using namespace oemgpu;
@@ -457,41 +506,7 @@ int oemgpu_sparse_x_create(oemgpu_ctx *c, int64_t n, int32_t p, const int64_t *c
     int64_t maxcol = 0;
     int rc = lsp_check_csc("sparse_x_create", n, p, colptr, rowidx, values, &rowptr, &maxcol);
     if (rc) return rc;
-    if (set_device(c)) return OEMGPU_ERR_HIP;
-    const int64_t nnz = colptr[p];
-    Bump B;
-    const size_t a_cp = B.take(8 * (size_t)(p + 1)), a_ri = B.take(4 * (size_t)(nnz + 1)), a_v = B.take(8 * (size_t)(nnz + 1)),
-                 a_rp = B.take(8 * (size_t)(n + 1)), a_cc = B.take(4 * (size_t)(nnz + 1)), a_cv = B.take(8 * (size_t)(nnz + 1)),
-                 a_ch = B.take(4 * (size_t)(csc_chunks(n) + 1) * p);
-    oemgpu_sparse_x *x = new oemgpu_sparse_x;
-    x->device = c->device; x->n = n; x->p = p; x->nnz = nnz; x->maxcol = maxcol; x->bytes = B.off;
-    if (hipMalloc((void **)&x->base, B.off) != hipSuccess) {
-        set_error("sparse_x_create: cannot allocate %zu bytes of device memory", B.off);
-        delete x;
-        return OEMGPU_ERR_HIP;
-    }
-    g_alloc_count += 1;
-    x->colptr = (int64_t *)(x->base + a_cp); x->rowidx = (int32_t *)(x->base + a_ri); x->val = (double *)(x->base + a_v);
-    x->rowptr = (int64_t *)(x->base + a_rp); x->ccol = (int32_t *)(x->base + a_cc); x->cval = (double *)(x->base + a_cv);
-    x->cptr = (int32_t *)(x->base + a_ch);
-    hipStream_t s = c->stream;
-    auto build = [&]() -> int {
-        OEM_HIP(hipMemcpyAsync(x->colptr, colptr, 8 * (size_t)(p + 1), hipMemcpyHostToDevice, s));
-        if (nnz > 0) {
-            OEM_HIP(hipMemcpyAsync(x->rowidx, rowidx, 4 * (size_t)nnz, hipMemcpyHostToDevice, s));
-            OEM_HIP(hipMemcpyAsync(x->val, values, 8 * (size_t)nnz, hipMemcpyHostToDevice, s));
-        }
-        OEM_HIP(hipMemcpyAsync(x->rowptr, rowptr.data(), 8 * (size_t)(n + 1), hipMemcpyHostToDevice, s));
-        int r = launch_csc_chunk_ptr(s, x->colptr, x->rowidx, n, p, x->cptr);
-        if (!r) r = launch_csc_to_csr(s, x->colptr, x->rowidx, x->val, x->cptr, n, p, x->rowptr, x->ccol, x->cval);
-        if (r) return r;
-        OEM_HIP(hipStreamSynchronize(s));                  // the host arrays (rowptr among them) may go once this returns
-        return 0;
-    };
-    rc = build();
-    if (rc) { (void)hipStreamSynchronize(s); (void)hipFree(x->base); delete x; return rc; }
-    *out = x;
-    return 0;
+    return sparse_x_build(c, n, p, colptr, rowidx, values, rowptr, maxcol, out);
 }
 
 void oemgpu_sparse_x_destroy(oemgpu_sparse_x *x)

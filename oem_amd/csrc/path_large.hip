@@ -2436,6 +2436,45 @@ __global__ __launch_bounds__(256) void wide_block_sum_kernel(const double *__res
     g[j] = s;
 }
 
+// lambda_max(X X'/n) of every p >= n engine of this file: Lanczos on vectors of `len` entries (v, v_prev, w; T the tridiagonal), the
+// product w = X (X' v) / n enqueued by `product()`, the host's look every 16 steps -- the breakdown rule (T is exact), the tail rule
+// of run_path_large, the stagnation rule -- and at most min(n, MAXL) steps.  hT: pinned host memory for T.
+template <typename F>
+static int lanczos_wide_host(hipStream_t s, int len, int n, double *v, double *vp, double *w, double *T, double *hT, F &&product,
+                             double *theta_out, int *steps_out, bool *capped_out)
+{
+    const int mmax = n < MAXL ? n : MAXL;
+    double theta = 0.0, theta_prev = -1.0;
+    bool lz_capped = true;
+    int m = 0;
+    hipLaunchKernelGGL(lanczos_init_kernel, dim3(1), dim3(1024), 0, s, len, v, vp);
+    while (m < mmax) {
+        const int chunk = (mmax - m) < 16 ? (mmax - m) : 16;
+        for (int k = 0; k < chunk; ++k, ++m) {
+            product();
+            hipLaunchKernelGGL(lanczos_update_kernel, dim3(1), dim3(1024), 0, s, len, m, v, vp, w, T);
+        }
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipMemcpyAsync(hT, T, sizeof(double) * 2 * MAXL, hipMemcpyDeviceToHost, s));
+        OEM_HIP(hipStreamSynchronize(s));
+        int mm = m;
+        for (int k = 0; k < m; ++k)
+            if (!(hT[MAXL + k] > 1e-13 * std::fabs(hT[k]))) { mm = k + 1; break; }     // breakdown: T is exact
+        theta = tridiag_max_host(hT, hT + MAXL, mm);
+        if (mm < m) { lz_capped = false; break; }
+        if (m >= 24) {                                                  // the stop rule of run_path_large
+            const double t1 = tridiag_max_host(hT, hT + MAXL, m - 8), t0 = tridiag_max_host(hT, hT + MAXL, m - 16);
+            const double mv = theta - t1, mvp = t1 - t0, ath = std::fabs(theta);
+            if (mv <= 1e-14 * ath || (mv < 0.01 * mvp && mv * mv <= OEM_LANCZOS_TAIL_TOL * ath * (mvp - mv))) { lz_capped = false; break; }
+        }
+        if (theta_prev > 0 && std::fabs(theta - theta_prev) <= 1e-12 * std::fabs(theta)) { lz_capped = false; break; }
+        theta_prev = theta;
+    }
+    if (mmax >= n) lz_capped = false;
+    *theta_out = theta; *steps_out = m; *capped_out = lz_capped;
+    return 0;
+}
+
 // n > 2048: the rows in nb blocks of <= 2048 (a column of a block fits a wave's registers).  A dot product x_j . r now spans the
 // blocks, so an iteration is the two products as passes of their own -- t = Xs beta block by block (W_XB + reduction), g = Xs' t / n
 // as per-block partial g_b (W_XTV) added in block order -- around path_update_kernel: every penalty, accelerate, compute.loss; 16 n p
@@ -2474,36 +2513,10 @@ static int run_path_wide_blocks(hipStream_t s, const PathArgs &a, const WideArgs
         hipLaunchKernelGGL(wide_block_sum_kernel, dim3((q + 255) / 256), dim3(256), 0, s, gb, nb, q, gout, done);
     };
     // ---- d = 1.005 lambda_max(Xs Xs'/n)
-    const int mmax = n < MAXL ? n : MAXL;
-    double theta = 0.0, theta_prev = -1.0;
+    double theta = 0.0;
     bool lz_capped = true;
-    double *hT = host_scratch;
     int m = 0;
-    hipLaunchKernelGGL(lanczos_init_kernel, dim3(1), dim3(1024), 0, s, (int)rows, v, vp);
-    while (m < mmax) {
-        const int chunk = (mmax - m) < 16 ? (mmax - m) : 16;
-        for (int k = 0; k < chunk; ++k, ++m) {
-            xtv(v, g, nullptr);
-            xb(g, w, nullptr);
-            hipLaunchKernelGGL(lanczos_update_kernel, dim3(1), dim3(1024), 0, s, (int)rows, m, v, vp, w, T);
-        }
-        OEM_HIP(hipGetLastError());
-        OEM_HIP(hipMemcpyAsync(hT, T, sizeof(double) * 2 * MAXL, hipMemcpyDeviceToHost, s));
-        OEM_HIP(hipStreamSynchronize(s));
-        int mm = m;
-        for (int k = 0; k < m; ++k)
-            if (!(hT[MAXL + k] > 1e-13 * std::fabs(hT[k]))) { mm = k + 1; break; }
-        theta = tridiag_max_host(hT, hT + MAXL, mm);
-        if (mm < m) { lz_capped = false; break; }
-        if (m >= 24) {
-            const double t1 = tridiag_max_host(hT, hT + MAXL, m - 8), t0 = tridiag_max_host(hT, hT + MAXL, m - 16);
-            const double mv = theta - t1, mvp = t1 - t0, ath = std::fabs(theta);
-            if (mv <= 1e-14 * ath || (mv < 0.01 * mvp && mv * mv <= OEM_LANCZOS_TAIL_TOL * ath * (mvp - mv))) { lz_capped = false; break; }
-        }
-        if (theta_prev > 0 && std::fabs(theta - theta_prev) <= 1e-12 * std::fabs(theta)) { lz_capped = false; break; }
-        theta_prev = theta;
-    }
-    if (mmax >= n) lz_capped = false;
+    if (int lrc = lanczos_wide_host(s, (int)rows, n, v, vp, w, T, host_scratch, [&] { xtv(v, g, nullptr); xb(g, w, nullptr); }, &theta, &m, &lz_capped)) return lrc;
     const double d = theta * 1.005;                     // ref src/oem_dense.h:498
     OEM_HIP(hipMemsetAsync(g, 0, sizeof(double) * (size_t)(q + 8), s));
     hipLaunchKernelGGL(path_init_kernel, dim3(1), dim3(1024), 0, s, a, st, beta, d, theta, m, lz_capped ? 1 : 0);
@@ -2575,37 +2588,15 @@ static int run_path_wide_nr(hipStream_t s, const PathArgs &a, const WideArgs &wd
 #undef OEM_WIDE_ATTR
     const int rblocks = (int)(npad / 64);
     // ---- d = 1.005 lambda_max(Xs Xs'/n): Lanczos on n-vectors, the product as the two passes of ONE kernel (ref :476-498)
-    const int mmax = n < MAXL ? n : MAXL;
-    double theta = 0.0, theta_prev = -1.0;
+    double theta = 0.0;
     bool lz_capped = true;
-    double *hT = host_scratch;
     int m = 0;
-    hipLaunchKernelGGL(lanczos_init_kernel, dim3(1), dim3(1024), 0, s, n, v, vp);
-    while (m < mmax) {
-        const int chunk = (mmax - m) < 16 ? (mmax - m) : 16;
-        for (int k = 0; k < chunk; ++k, ++m) {
-            hipLaunchKernelGGL((wide_cols_kernel<NR, W_EIG>), dim3(W), dim3(NT), lds, s, a, wd.xs, v, wd.ys, P, (double *)nullptr, (double *)nullptr,
-                               (SState *)nullptr, (int *)nullptr, (int *)nullptr, (const int *)nullptr, 0, 0.0, n, cpw);
-            hipLaunchKernelGGL((wide_reduce_kernel<W_EIG>), dim3(rblocks), dim3(1024), 0, s, P, W, npad, n, wd.ys, w, (const int *)nullptr);
-            hipLaunchKernelGGL(lanczos_update_kernel, dim3(1), dim3(1024), 0, s, n, m, v, vp, w, T);
-        }
-        OEM_HIP(hipGetLastError());
-        OEM_HIP(hipMemcpyAsync(hT, T, sizeof(double) * 2 * MAXL, hipMemcpyDeviceToHost, s));
-        OEM_HIP(hipStreamSynchronize(s));
-        int mm = m;
-        for (int k = 0; k < m; ++k)
-            if (!(hT[MAXL + k] > 1e-13 * std::fabs(hT[k]))) { mm = k + 1; break; }     // breakdown: T is exact
-        theta = tridiag_max_host(hT, hT + MAXL, mm);
-        if (mm < m) { lz_capped = false; break; }
-        if (m >= 24) {                                                  // the stop rule of run_path_large
-            const double t1 = tridiag_max_host(hT, hT + MAXL, m - 8), t0 = tridiag_max_host(hT, hT + MAXL, m - 16);
-            const double mv = theta - t1, mvp = t1 - t0, ath = std::fabs(theta);
-            if (mv <= 1e-14 * ath || (mv < 0.01 * mvp && mv * mv <= OEM_LANCZOS_TAIL_TOL * ath * (mvp - mv))) { lz_capped = false; break; }
-        }
-        if (theta_prev > 0 && std::fabs(theta - theta_prev) <= 1e-12 * std::fabs(theta)) { lz_capped = false; break; }
-        theta_prev = theta;
-    }
-    if (mmax >= n) lz_capped = false;
+    auto eig_product = [&] {
+        hipLaunchKernelGGL((wide_cols_kernel<NR, W_EIG>), dim3(W), dim3(NT), lds, s, a, wd.xs, v, wd.ys, P, (double *)nullptr, (double *)nullptr,
+                           (SState *)nullptr, (int *)nullptr, (int *)nullptr, (const int *)nullptr, 0, 0.0, n, cpw);
+        hipLaunchKernelGGL((wide_reduce_kernel<W_EIG>), dim3(rblocks), dim3(1024), 0, s, P, W, npad, n, wd.ys, w, (const int *)nullptr);
+    };
+    if (int lrc = lanczos_wide_host(s, n, n, v, vp, w, T, host_scratch, eig_product, &theta, &m, &lz_capped)) return lrc;
     const double d = theta * 1.005;                     // ref src/oem_dense.h:498
     hipLaunchKernelGGL(path_init_kernel, dim3(1), dim3(1024), 0, s, a, st, beta, d, theta, m, lz_capped ? 1 : 0);
     OEM_HIP(hipGetLastError());
@@ -2688,6 +2679,52 @@ int run_path_wide(hipStream_t s, const PathArgs &a, const WideArgs &wd, double *
     }
     set_error("p >= n: the wide engine holds n <= %d rows", WIDE_MAX_N);
     return OEMGPU_ERR_UNSUPPORTED;
+}
+
+// p >= n on a resident sparse x: the general form of run_path_wide_nr with both products over the non-zeros (sparse_wide.hip) --
+// t = X beta (row pass), g = X't / n (column pass), path_update_kernel<0>: every penalty, any group layout, several penalties in one
+// call.  The eigen step is the shared Lanczos on n-vectors, w = X (X'v) / n as the column pass followed by the row pass.  Nothing of
+// n p entries anywhere; n is bounded by the int32 row indices only.  The batches of iterations are one serial chain (replay_batches).
+int run_path_sparse_wide(hipStream_t s, const PathArgs &a, const SpwArgs &A, double *host_scratch)
+{
+    const int q = a.p, n = A.n;
+    if (q != A.p) { set_error("internal: sparse wide engine dimensions"); return OEMGPU_ERR_INTERNAL; }
+    double *t = A.vec, *v = t + n, *vp = v + n, *w = vp + n, *T = w + n;
+    LState *st = reinterpret_cast<LState *>(a.work);
+    double *beta = a.work + STATE_DBL, *g = beta + (q + 8);
+    OEM_HIP(hipMemsetAsync(a.work, 0, sizeof(double) * path_large_work_doubles(q, 0), s));
+    static_assert(SPW_T_DOUBLES >= 2 * MAXL, "the Lanczos table fits the sparse engine's workspace");
+    OEM_HIP(hipMemsetAsync(A.vec, 0, sizeof(double) * (4 * (size_t)n + SPW_T_DOUBLES), s));
+    const double rn = 1.0 / (double)n;
+    int rc = 0;
+    // ---- d = 1.005 lambda_max(X X'/n)
+    double theta = 0.0;
+    bool lz_capped = true;
+    int m = 0;
+    auto eig_product = [&] {
+        if (!rc) rc = launch_spw_cols(s, A, v, g, 1.0, nullptr);
+        if (!rc) rc = launch_spw_rows(s, A, g, w, rn, nullptr);
+    };
+    if (int lrc = lanczos_wide_host(s, n, n, v, vp, w, T, host_scratch, eig_product, &theta, &m, &lz_capped)) return lrc;
+    if (rc) return rc;
+    const double d = theta * 1.005;                     // ref src/oem_sparse.h:607-612
+    OEM_HIP(hipMemsetAsync(g, 0, sizeof(double) * (size_t)(q + 8), s));
+    hipLaunchKernelGGL(path_init_kernel, dim3(1), dim3(1024), 0, s, a, st, beta, d, theta, m, lz_capped ? 1 : 0);
+    OEM_HIP(hipGetLastError());
+    if (a.npen == 0) return 0;
+    double *uf = nullptr;
+    const size_t shu = update_lds(a, &uf);
+    if (shu > 64 * 1024) OEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&path_update_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shu));
+    auto enq = [&](int count) {
+        for (int k = 0; k < count; ++k) {
+            if (!rc) rc = launch_spw_rows(s, A, beta, t, 1.0, (const int *)&st->done);
+            if (!rc) rc = launch_spw_cols(s, A, t, g, rn, (const int *)&st->done);
+            hipLaunchKernelGGL(path_update_kernel<0>, dim3(1), dim3(1024), shu, s, a, st, beta, g, uf, (int *)nullptr);
+        }
+    };
+    const long long max_it = (long long)a.npen * a.nl * ((long long)a.maxit + 3) + 8;
+    const int prc = replay_batches(s, enq, (const int *)&st->done, reinterpret_cast<int *>(host_scratch), max_it, "sparse wide engine");
+    return prc ? prc : rc;
 }
 
 

@@ -442,6 +442,22 @@ SparseRoute sparse_route(int64_t n, int p, int64_t nnz)
     return R;
 }
 
+// n <= p: the fit from the non-zeros (sparse_wide.hip) where the matrix is sparse by sparse_route's own measure and p lies beyond the
+// register engines (wide_pays: up to 1024 they run the p x p Gram form, and the dense copy is a few MB); OEM_SPARSE_GRAM=wide | nowide
+// forces / forbids it for any n <= p (tests hold it against the dense copy; the switch table is full, so the route has no name of
+// its own there: csc | dense keep their meaning for n > p and mean nothing here)
+bool sparse_wide_route(int64_t n, int p, int64_t nnz)
+{
+    if (n > p) return false;
+    bool take = (double)nnz <= 0.02 * (double)n * (double)p && p > 1024;
+    if (sw().OEM_SPARSE_GRAM.set) {
+        const char *ev = sw().OEM_SPARSE_GRAM.str;
+        if (!strcmp(ev, "wide")) take = true;
+        if (!strcmp(ev, "nowide")) take = false;
+    }
+    return take;
+}
+
 int launch_moments_add(hipStream_t s, double *acc, const double *m, size_t len, bool first)
 {
     hipLaunchKernelGGL(moments_add_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, acc, m, len, first ? 1 : 0);
