@@ -715,6 +715,50 @@ int oemgpu_fit_sparse_wide_res(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, const 
  * of long rows and columns).  OEMGPU_ERR_ARG for non-positive n, p or num_cu, a negative count or a NULL out. */
 int oemgpu_selftest_sparse_wide_plan(int64_t n, int32_t p, int64_t nnz, int64_t longest_row, int64_t longest_col, int32_t num_cu,
                                      int64_t *out /* 8 */);
+/* cv.oem's fold fit on the resident sparse x with n <= p and no intercept (ref R/cv_oem.R:155-175 calls oem() on x[!which, ], which
+ * reaches src/oem_sparse.h:607-612, 638-647, 932-941): what oemgpu_fit_sparse_wide_res computes on x[keep, ], y[keep] with
+ * keep = foldid_dev != leave_out.  Nothing is sliced, gathered or uploaded: every row pass (X beta, the second half of the eigen
+ * product, the loss) skips a left-out row -- it is not read and its output is an exact 0.0 -- the once-per-fit pass over the columns
+ * (x_j'y, sum x_j^2, sum y^2) excludes left-out entries by a select, and the kept-row count n_k stands wherever n enters: X'y / n_k,
+ * colsq = sum over the kept rows of x^2 / (n_k - 1) with a column emptied by the fold -> 1, g = X't / n_k,
+ * d = 1.005 lambda_max(X_k X_k' / n_k) by Lanczos from a start vector that is zero in the left-out rows (the Krylov space is the kept
+ * rows'; n_k in the step cap), the lambda grid from the masked X'y.  The column pass of an iteration is not masked: its input is
+ * exactly zero in the left-out rows.  As for oemgpu_fit_logistic_sparse_fold_res, the stored values of a left-out row must therefore
+ * be finite (a NaN or Inf there would reach the sums through x * 0); y of a left-out row is never read and may be anything.
+ * y_dev: n doubles, foldid_dev: n int32 with values 1..nfolds, on the handle's device; *kept <- n_k.  leave_out = 0 (foldid_dev may
+ * then be NULL) leaves nothing out and returns the bits of oemgpu_fit_sparse_wide_res, which is a call of this entry; so does a
+ * leave_out that no row carries.  No floating-point atomics, one summation order per line: two calls give the same bits.  The lane
+ * that adds an entry follows the entry's position in the STORED line, left-out entries included, so a fold fit matches the fit of
+ * the sliced matrix to rounding (tolerance), not bit for bit.
+ * Checked before a device is looked for: OEMGPU_ERR_ARG for a NULL argument, nfolds outside 3..512, leave_out outside [0, nfolds], a
+ * NULL foldid_dev with leave_out > 0, a handle on another device and n < 2; OEMGPU_ERR_UNSUPPORTED for n > p (oemgpu_fit_sparse serves
+ * it); then the checks of the options.  From the device: OEMGPU_ERR_ARG for a fold id outside 1..nfolds and for n_k < 2 (the fold is
+ * named). */
+int oemgpu_fit_sparse_wide_fold_res(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
+                                    int32_t leave_out, int32_t standardize, const oemgpu_opts *opts, double *beta, double *lambda_out,
+                                    int32_t *niter, double *loss, double *d, int64_t *kept);
+/* cv.oem's scoring of the held-out rows on the resident sparse x (ref R/cv_oem.R:376-391, 392-423; R/utils.R:128-144), the companion
+ * of the fold fits above: the outputs of oemgpu_cv_sparse_score_res -- triples[nfolds][npen][nl][3] <- (count, mean, M2) of fold k's
+ * errors (type_measure 0 mse, 1 mae) over its own rows under ITS coefficients coef[k] (host, [nfolds][npen][nl][p + 1], slot 0 the
+ * intercept), (0, NaN, NaN) in columns >= ncol[pen] and for a fold without rows; predmat_dev: NULL, or [npen][nl][n] on the device <-
+ * eta in the caller's row order, NaN in columns >= ncol[pen] -- without a fold-ordered layout: the handle's compressed rows are walked
+ * where they lie, fold k's rows come from foldid_dev, and ONE fold's transposed tables are on the device at a time.  The context's
+ * fold buffer and the layout another cv call left there are neither read nor voided.  Per-wave partials merged in wave order, no
+ * atomics: two calls give the same bits.  OEMGPU_ERR_ARG before any device work for a NULL argument, npen or nl < 1, nfolds outside
+ * 3..512, a type_measure other than 0 / 1, an ncol outside 0..nl, a handle on another device; from the device for a fold id outside
+ * 1..nfolds. */
+int oemgpu_cv_sparse_wide_score_res(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
+                                    const double *coef, int32_t npen, int32_t nl, const int32_t *ncol, int32_t type_measure, double *triples,
+                                    double *predmat_dev /* or NULL */);
+/* Host-only plan of the entry above (pure arithmetic, runs without a GPU; the entry takes its launch from the same function; it
+ * replaces nothing of the reference, whose cv.oem predicts in R): out[0] waves per fold (the stride over a fold's held-out rows),
+ * [1] workgroups per fold (four waves each; x npen x out[2]) -- about four per CU over (penalty, lambda block), no more waves than a
+ * fold of ceil(n / nfolds) rows has rows, at most 1024 workgroups, never fewer than one --, [2] blocks of 64 lambdas, [3] bytes of one
+ * staged table (p + 1) out[5] 8 (npen of them per fold), [4] bytes of the wave partials = nfolds out[0] npen out[5] 32 (kept under
+ * 64 MB by lowering out[1]), [5] nl rounded up to 16, [6] workspace bytes of the call.  OEMGPU_ERR_ARG on bad arguments and nfolds
+ * outside 3..512. */
+int oemgpu_selftest_cv_sparse_wide_score_plan(int64_t n, int32_t p, int32_t nfolds, int32_t npen, int32_t nl, int32_t num_cu,
+                                              int64_t *out /* 7 */);
 /* oemgpu_logistic_cv_score_dev on the resident sparse x (ref R/cv_oem.R:224-346): the same arguments with the handle in place of
  * x_dev, n, ld, p, the same outputs.  Every row is read from the compressed-row copy, its stored entries in column order; for finite
  * tables the sums, counts and predmat are the bits of oemgpu_logistic_cv_score_dev on the same matrix written out densely.  The launch

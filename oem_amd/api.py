@@ -432,8 +432,11 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
         raise ValueError("'arg' should be one of 'gaussian', 'binomial'")
     penalty = _match_penalty(penalty)
     resident_sparse = isinstance(x, SparseX)
-    if resident_sparse and not _args_only:                            # (cv_oem alone builds the sparse entry's option block for a SparseX)
-        raise ValueError("oem() on a SparseX is not built: oem() takes the scipy.sparse matrix itself; the resident handle is what cv_oem runs on")
+    if resident_sparse and not _args_only:
+        if getattr(x, "_h", None) is None:
+            raise ValueError("this SparseX is closed")
+        if x.shape[0] > x.shape[1]:                                   # n > p: the Gram form's fit needs the host arrays (cv_oem builds its option block here)
+            raise ValueError("oem() on a SparseX is not built: oem() takes the scipy.sparse matrix itself; the resident handle is what cv_oem runs on")
     if getattr(x, "ndim", 0) != 2 and not resident_sparse:
         raise ValueError("x must have at least two columns")
     n, p = x.shape
@@ -469,6 +472,18 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
             a.c.accelerate = 0                                         # oemSparse has no acceleration
         return a, varnames, bool(standardize), bool(intercept)
     lib = L.lib()
+    if resident_sparse:                                                # n <= p on the handle: from its non-zeros, nothing uploaded but y
+        if ngpus or devices is not None:
+            raise ValueError("oem() on a SparseX: the rows of a sparse x are not split over devices")
+        a.c.accelerate = 0                                             # oemSparse has no acceleration
+        if intercept:
+            _sparse_wide_intercept_refusal(n, p, a, standardize)
+        import torch
+        yd = _device_y(y, x.device).to(x.device)
+        torch.cuda.current_stream(x.device).synchronize()
+        L.check(lib.oemgpu_fit_sparse_wide_res(context(x.device.index), x.handle, yd.data_ptr(), int(bool(standardize)), C.byref(a.c),
+                                               *a.outputs(p + 1)))
+        return _decorate(a, penalty, varnames, True, n, p)
     if is_sparse:                                                      # oem_fit_sparse (ref src/oem_sparse.cpp:30-267)
         colptr, rowidx, vals = _csc_arrays(x)
         yh = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
@@ -1105,6 +1120,45 @@ def cv_sparse_gaussian_score(x, y, foldid, nfolds, coef, ncol, type_measure="mse
     return tri, (pm.cpu().numpy() if predmat else None)
 
 
+def cv_sparse_wide_score(x, y, foldid, nfolds, coef, ncol, type_measure="mse", predmat=False, ctx=None):
+    """oemgpu_cv_sparse_wide_score_res on a coefficient table of the caller's: the arguments and results of cv_sparse_gaussian_score,
+    from the SparseX's compressed rows in the caller's order (no fold layout, one fold's table on the device at a time)."""
+    import torch
+    L.sync_switches()
+    n, p = x.shape
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    if coef.ndim != 4 or coef.shape[0] != int(nfolds) or coef.shape[3] != p + 1:
+        raise ValueError("coef must be nfolds x npen x nl x (p + 1)")
+    npen, nl = coef.shape[1:3]
+    ncol = np.ascontiguousarray(ncol, dtype=np.int32)
+    if ncol.shape != (npen,):
+        raise ValueError("ncol must hold one count per penalty")
+    tri = np.full((int(nfolds), npen, nl, 3), np.nan)
+    pm = torch.empty((npen, nl, n), dtype=torch.float64, device=x.device) if predmat else None
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_cv_sparse_wide_score_res(ctx if ctx is not None else context(x.device.index), x.handle, y.data_ptr(),
+                                                    foldid.data_ptr(), int(nfolds), _dptr(coef), npen, nl, _iptr(ncol),
+                                                    {"mse": 0, "mae": 1}[type_measure], _dptr(tri), pm.data_ptr() if predmat else None))
+    return tri, (pm.cpu().numpy() if predmat else None)
+
+
+def sparse_wide_fold_fit(x, y, foldid, nfolds, leave_out, penalty=None, **kw):
+    """oemgpu_fit_sparse_wide_fold_res: oem(x[foldid != leave_out], y[foldid != leave_out], intercept=False, ...) on a SparseX with
+    n <= p where it lies (leave_out = 0: every row; foldid may then be None).  y (float64) and foldid (int32, 1 .. nfolds): device
+    tensors.  Returns the fit as oem() decorates it, with nobs = the kept rows."""
+    import torch
+    penalty = _match_penalty(penalty)
+    n, p = x.shape
+    with warnings.catch_warnings():
+        warnings.filterwarnings("ignore", message=".*optimized for n >> p.*")
+        a, varnames, standardize, _ = oem(x, y, penalty=penalty, intercept=False, _args_only=True, **kw)
+    kept = C.c_int64(0)
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_fit_sparse_wide_fold_res(context(x.device.index), x.handle, y.data_ptr(), None if foldid is None else foldid.data_ptr(),
+                                                    int(nfolds), int(leave_out), int(standardize), C.byref(a.c), *a.outputs(p + 1), C.byref(kept)))
+    return _decorate(a, penalty, varnames, True, int(kept.value), p)
+
+
 _CVS_PLAN_KEYS = ("csc", "nwg", "waves", "lblk", "part_bytes", "bytes", "xval_bytes", "fold_bytes", "own_bytes", "rows_max", "nl16", "align")
 
 
@@ -1414,11 +1468,7 @@ def _cv_gaussian_sparse_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw):
     import types
     import torch
     n, p = x.shape
-    foldid = np.asarray(foldid)
-    if len(foldid) != n or not np.issubdtype(foldid.dtype, np.integer) or foldid.min() < 1 or foldid.max() > nfolds:
-        raise ValueError("foldid must hold one integer in 1..nfolds per row of x")
-    if not 3 <= nfolds <= 512:
-        raise ValueError("cv.oem on a SparseX: nfolds must be in 3..512")
+    foldid = _cv_sparse_foldid(foldid, n, nfolds)
     kept = n - np.bincount(foldid, minlength=nfolds + 1)[1:]
     if np.any(kept <= p):
         i = int(np.argmax(kept <= p))
@@ -1441,6 +1491,55 @@ def _cv_gaussian_sparse_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw):
                       int(n - fold_n[i - 1]) if i else n, p) for i in range(K + 1)]
     return fits[0], fits[1:], {"ctx": ctx, "n": n, "p": p, "K": K, "args": a, "fold_n": fold_n, "device": x.device,
                                "score": L.lib().oemgpu_cv_sparse_score_res}
+
+
+def _sparse_wide_intercept_refusal(n, p, a, standardize):
+    """raises the library's own sentence for a sparse x with p >= n and an intercept: oemgpu_fit_sparse says it before it looks at the
+    arrays or for a device, so the call carries the shape and the option block alone"""
+    none = np.zeros(1, dtype=np.int64)
+    L.check(L.lib().oemgpu_fit_sparse(n, p, none.ctypes.data, None, None, _dptr(np.zeros(1)), int(bool(standardize)), 1, C.byref(a.c),
+                                      *a.outputs(1)))
+    raise AssertionError("oemgpu_fit_sparse accepted a sparse x with p >= n and an intercept")
+
+
+def _cv_gaussian_sparse_wide_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw):
+    """cv.oem's K + 1 calls of oem() (R/cv_oem.R:105, 155-175) on a resident SparseX with n <= p and no intercept: K + 1 calls of
+    oemgpu_fit_sparse_wide_fold_res on the handle where it lies -- leave_out = 0 the full fit, leave_out = k the masked fold fit with
+    the kept-row count wherever n enters.  Returns what _cv_gaussian_sparse_fold_fits returns; the scoring is
+    oemgpu_cv_sparse_wide_score_res on the same handle, y and fold ids."""
+    import torch
+    n, p = x.shape
+    foldid = _cv_sparse_foldid(foldid, n, nfolds)
+    a, varnames, standardize, intercept = oem(x, y, penalty=penalty, lambda_=lam_arg, _args_only=True, **kw)
+    if intercept:
+        _sparse_wide_intercept_refusal(n, p, a, standardize)
+    yd = _device_y(y, x.device).to(x.device)
+    fd = torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=x.device)
+    ctx = context(x.device.index)
+    K = int(nfolds)
+    fold_n = np.bincount(foldid, minlength=K + 1)[1:].astype(np.int64)
+    lib = L.lib()
+    fits = []
+    torch.cuda.current_stream(x.device).synchronize()
+    for k in range(K + 1):
+        kept = C.c_int64(0)
+        L.check(lib.oemgpu_fit_sparse_wide_fold_res(ctx, x.handle, yd.data_ptr(), fd.data_ptr(), K, k, int(standardize), C.byref(a.c),
+                                                    *a.outputs(p + 1), C.byref(kept)))
+        fits.append(_decorate(a, penalty, varnames, True, int(kept.value), p))
+
+    def score(ctx_, n_, p_, K_, *rest):                            # (yd and fd live as long as the scoring may run)
+        return lib.oemgpu_cv_sparse_wide_score_res(ctx_, x.handle, yd.data_ptr(), fd.data_ptr(), K_, *rest)
+    return fits[0], fits[1:], {"ctx": ctx, "n": n, "p": p, "K": K, "args": a, "fold_n": fold_n, "device": x.device, "score": score}
+
+
+def _cv_sparse_foldid(foldid, n, nfolds):
+    """the fold ids of cv_oem on a SparseX, checked before any device work"""
+    foldid = np.asarray(foldid)
+    if len(foldid) != n or not np.issubdtype(foldid.dtype, np.integer) or foldid.min() < 1 or foldid.max() > nfolds:
+        raise ValueError("foldid must hold one integer in 1..nfolds per row of x")
+    if not 3 <= nfolds <= 512:
+        raise ValueError("cv.oem on a SparseX: nfolds must be in 3..512")
+    return foldid
 
 
 def _cv_gaussian_table(outlist, lam, which_lam, p):
@@ -1577,6 +1676,11 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
     "ols" among the penalties, weights, ngpus / devices, a closed SparseX, len(y) != n, nfolds < 3, a fold id outside 1..nfolds and a fold
     that keeps no more rows than columns (named: there is no host loop for a sparse x).  A scipy matrix itself with family = "gaussian"
     stays a ValueError.
+    A SparseX with n <= p (and intercept=False: with an intercept the library's refusal of a sparse x with p >= n is raised) takes the
+    wide form of all of it: the full fit and the K fold fits are K + 1 calls of oemgpu_fit_sparse_wide_fold_res on the handle where it
+    lies (leave_out = 0, then 1..K: masked passes over the non-zeros, the kept-row count wherever n enters), the held-out rows are scored
+    from the handle's compressed rows in the caller's order (oemgpu_cv_sparse_wide_score_res, one fold's table on the device at a time);
+    the same refusals otherwise.
     parallel (R/cv_oem.R:32, 129-150: the folds through foreach): the fold fits from a few host threads at once.  On one GPU that
     pays where a fit leaves most of the chip idle: the path kernels of n >> p fits (one CU each) overlap with other folds' moment
     kernels, and p >= n fits on the cooperating-workgroup engine (a quarter of the CUs each) run side by side -- they queue for CU
@@ -1616,7 +1720,9 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
     if nfolds < 3:
         raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
     resident = on_sparse or _cv_gaussian_resident(x, penalty, kw, foldid, nfolds)
-    if on_sparse:                                                 # the full fit and the K fold fits from the fold moments of the resident columns
+    if on_sparse and x.shape[0] <= x.shape[1]:                    # n <= p: the full fit and the K masked fold fits over the handle's non-zeros
+        fit0, outlist, dev = _cv_gaussian_sparse_wide_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw)
+    elif on_sparse:                                               # the full fit and the K fold fits from the fold moments of the resident columns
         fit0, outlist, dev = _cv_gaussian_sparse_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw)
     elif resident:                                                # x stays where it is: fold moments, K solves (oemgpu_cv_fold_fits_dev)
         outlist, dev = _cv_gaussian_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw)

@@ -3438,13 +3438,101 @@ int oemgpu_selftest_cv_sparse_plan(int64_t n, int32_t p, int64_t nnz, int32_t nf
     return 0;
 }
 
+// cv.oem's scoring on a resident sparse x with n <= p (ref R/cv_oem.R:376-391; R/utils.R:128-144): the handle's compressed rows in the
+// caller's order, the folds' rows from foldid, one fold's table on the device at a time (xval_sparse.hip: csr_cv_wide_score_kernel).
+// Everything lives in the context's workspace: the fold buffer (aux) and its cv stamp are neither read nor touched.
+static int cv_wide_score_checks(const char *who, int64_t n, int32_t p, int32_t nfolds, int32_t npen, int32_t nl)
+{
+    if (n < 1 || p < 1 || npen < 1 || nl < 1) { set_error("%s: bad n, p, npen or nl", who); return OEMGPU_ERR_ARG; }
+    if (nfolds < 3 || nfolds > 512) { set_error("%s: nfolds must be in 3..512", who); return OEMGPU_ERR_ARG; }
+    if (n >= 2147483647LL) { set_error("%s: n must be below 2^31", who); return OEMGPU_ERR_UNSUPPORTED; }
+    return 0;
+}
+
+int oemgpu_cv_sparse_wide_score_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
+                                    const double *coef, int32_t npen, int32_t nl, const int32_t *ncol, int32_t type_measure, double *triples,
+                                    double *predmat_dev)
+{
+    static const char *who = "cv_sparse_wide_score_res";
+    if (!c || !x || !y_dev || !foldid_dev || !coef || !ncol || !triples) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    int rc = cv_wide_score_checks(who, x->n, x->p, nfolds, npen, nl);
+    if (rc) return rc;
+    if (type_measure != 0 && type_measure != 1) { set_error("%s: type_measure must be 0 (mse) or 1 (mae)", who); return OEMGPU_ERR_ARG; }
+    for (int k = 0; k < npen; ++k)
+        if (ncol[k] < 0 || ncol[k] > nl) { set_error("%s: ncol[%d] = %d is outside 0..%d", who, k, ncol[k], nl); return OEMGPU_ERR_ARG; }
+    if (c->device != x->device) { set_error("%s: the context and the sparse x are on different devices", who); return OEMGPU_ERR_ARG; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const int n = (int)x->n, p = x->p, K = nfolds;
+    hipStream_t s = c->stream;
+    // the per-fold row lists, ascending rows, once per call: n ids down, n rows up (n <= p is small next to the non-zeros)
+    std::vector<int32_t> fid((size_t)n), list((size_t)n);
+    std::vector<int> start((size_t)K + 1, 0);
+    OEM_HIP(hipMemcpyAsync(fid.data(), foldid_dev, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipStreamSynchronize(s));
+    long long bad = 0;
+    for (int i = 0; i < n; ++i) { if (fid[i] < 1 || fid[i] > K) ++bad; else ++start[fid[i]]; }
+    if (bad) { set_error("%s: %lld fold ids are outside [1, %d]", who, bad, K); return OEMGPU_ERR_ARG; }
+    for (int k = 0; k < K; ++k) start[k + 1] += start[k];
+    {
+        std::vector<int> cur(start.begin(), start.end() - 1);
+        for (int i = 0; i < n; ++i) list[(size_t)cur[fid[i] - 1]++] = i;
+    }
+    const CvWideScorePlan P = cv_wide_score_plan(n, p, K, npen, nl, c->num_cu);
+    if (ctx_reserve(c, P.bytes + 4096)) return OEMGPU_ERR_HIP;
+    int32_t *list_dev = (int32_t *)(c->ws + P.a_list);
+    double *raw = (double *)(c->ws + P.a_raw), *bt = (double *)(c->ws + P.a_bt), *part = (double *)(c->ws + P.a_part), *tri = (double *)(c->ws + P.a_tri);
+    int *ncol_dev = (int *)(c->ws + P.a_ncol);
+    const size_t flen = (size_t)npen * nl * (p + 1), tlen = (size_t)3 * K * npen * nl, pk = P.part_bytes / sizeof(double) / K;
+    OEM_HIP(hipMemcpyAsync(list_dev, list.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemcpyAsync(ncol_dev, ncol, sizeof(int) * (size_t)npen, hipMemcpyHostToDevice, s));
+    for (int k = 0; k < K; ++k) {                             // fold by fold: its table up, its rows scored (one stream: the order is the stream's)
+        const int nk = start[k + 1] - start[k];
+        if (nk > 0) OEM_HIP(hipMemcpyAsync(raw, coef + (size_t)k * flen, sizeof(double) * flen, hipMemcpyHostToDevice, s));
+        rc = launch_csr_cv_wide_score_fold(s, P, p, x->rowptr, x->ccol, x->cval, y_dev, list_dev + start[k], nk, raw, bt, type_measure, ncol_dev,
+                                           part + (size_t)k * pk, predmat_dev, n);
+        if (rc) return rc;
+    }
+    if ((rc = launch_cv_fold_finish(s, part, P.waves, K, npen, nl, ncol_dev, tri))) return rc;
+    OEM_HIP(hipMemcpyAsync(triples, tri, sizeof(double) * tlen, hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipStreamSynchronize(s));                           // coef, ncol and triples are the caller's
+    return 0;
+}
+
+// out[0] waves per fold, [1] workgroups per fold (x npen x out[2]), [2] blocks of 64 lambdas, [3] bytes of ONE staged table
+// (p + 1) nl16 8 (npen of them are staged per fold), [4] bytes of the wave partials of all folds, [5] nl16, [6] workspace bytes of the call
+int oemgpu_selftest_cv_sparse_wide_score_plan(int64_t n, int32_t p, int32_t nfolds, int32_t npen, int32_t nl, int32_t num_cu, int64_t *out)
+{
+    static const char *who = "selftest_cv_sparse_wide_score_plan";
+    if (num_cu < 1 || !out) { set_error("%s: bad argument", who); return OEMGPU_ERR_ARG; }
+    int rc = cv_wide_score_checks(who, n, p, nfolds, npen, nl);
+    if (rc) return rc;
+    const CvWideScorePlan P = cv_wide_score_plan(n, p, nfolds, npen, nl, num_cu);
+    out[0] = P.waves; out[1] = P.nwg; out[2] = P.lblk; out[3] = (int64_t)P.table_bytes; out[4] = (int64_t)P.part_bytes; out[5] = P.nl16;
+    out[6] = (int64_t)P.bytes;
+    return 0;
+}
+
 // oem() on a resident sparse x with nobs <= nvars and no intercept: fit_big_wide_dev's iteration (the comment there) with both products
 // over the non-zeros of the handle (sparse_wide.hip; path_large.hip: run_path_sparse_wide).  Nothing of n p entries is allocated.
+// The ONE body is the fold entry's: leave_out = 0 (or a fold without rows) sets no mask and launches what this entry always launched.
 int oemgpu_fit_sparse_wide_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const double *y_dev, int32_t standardize, const oemgpu_opts *o,
                                double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
 {
-    static const char *who = "fit_sparse_wide_res";
-    if (!c || !x || !y_dev || !o || !beta || !lambda_out || !niter || !loss || !d) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    int64_t kept = 0;
+    return oemgpu_fit_sparse_wide_fold_res(c, x, y_dev, nullptr, 3, 0, standardize, o, beta, lambda_out, niter, loss, d, &kept);
+}
+
+// cv.oem's fold fit on the same engine (ref R/cv_oem.R:155-175 -> src/oem_sparse.h:607-612, 638-647, 932-941 on x[keep, ], y[keep]):
+// the rows with foldid == leave_out are left out by the masked passes of sparse_wide.hip, the kept-row count stands for n.
+int oemgpu_fit_sparse_wide_fold_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
+                                    int32_t leave_out, int32_t standardize, const oemgpu_opts *o, double *beta, double *lambda_out,
+                                    int32_t *niter, double *loss, double *d, int64_t *kept)
+{
+    static const char *who = "fit_sparse_wide";
+    if (!c || !x || !y_dev || !o || !beta || !lambda_out || !niter || !loss || !d || !kept) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    if (nfolds < 3 || nfolds > 512) { set_error("%s: nfolds must be in 3..512", who); return OEMGPU_ERR_ARG; }
+    if (leave_out < 0 || leave_out > nfolds) { set_error("%s: leave_out must be in [0, nfolds]", who); return OEMGPU_ERR_ARG; }
+    if (leave_out > 0 && !foldid_dev) { set_error("%s: NULL foldid with leave_out > 0", who); return OEMGPU_ERR_ARG; }
     if (c->device != x->device) { set_error("%s: the context and the sparse x are on different devices", who); return OEMGPU_ERR_ARG; }
     if (x->n < 2) { set_error("%s: at least two rows", who); return OEMGPU_ERR_ARG; }
     if (x->n > x->p) {
@@ -3456,7 +3544,19 @@ int oemgpu_fit_sparse_wide_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const do
     if (rc) return rc;
     if (set_device(c)) return OEMGPU_ERR_HIP;
     hipStream_t s = c->stream;
+    int64_t nk = n;
+    if (foldid_dev) {                                        // the ids' range whatever is left out; the kept rows
+        std::vector<int64_t> none;
+        if ((rc = logit_fold_scan(c, who, foldid_dev, n, nfolds, leave_out, 0, &nk, &none))) return rc;
+        if (nk < 2) {
+            set_error("%s: fold %d keeps %lld of the %d rows: a fit needs at least two", who, (int)leave_out, (long long)nk, n);
+            return OEMGPU_ERR_ARG;
+        }
+    }
+    *kept = nk;
     SpwArgs A;
+    if (leave_out > 0 && nk < n) { A.foldid = foldid_dev; A.leave_out = leave_out; }      // (a fold without rows: the fit of all rows, unmasked)
+    A.nk = (int)nk;
     A.colptr = x->colptr; A.rowptr = x->rowptr; A.rowidx = x->rowidx; A.ccol = x->ccol; A.val = x->val; A.cval = x->cval;
     A.n = n; A.p = p;
     A.plan = spw_plan(n, p, x->nnz, 0, 0, c->num_cu);        // (the lanes; the long forms once the lines have been looked at)
@@ -3497,16 +3597,16 @@ int oemgpu_fit_sparse_wide_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const do
                    standardize ? xy_std : nullptr);
     if (rc || !o->compute_loss) return rc;
     // oemSparse::get_loss with nobs <= nvars (ref src/oem_sparse.h:932-941): the residual of the RETURNED coefficients
-    const size_t nk = (size_t)o->npen * nl_of(o), nchunk = (size_t)((n + 2047) / 2048);
+    const size_t nfit = (size_t)o->npen * nl_of(o), nchunk = (size_t)((n + 2047) / 2048);
     Bump L;
-    const size_t a_b = L.take(nk * (size_t)(p + 1) * 8), a_p = L.take(nk * nchunk * 8), a_l = L.take(nk * 8);
+    const size_t a_b = L.take(nfit * (size_t)(p + 1) * 8), a_p = L.take(nfit * nchunk * 8), a_l = L.take(nfit * 8);
     if (ctx_reserve(c, L.off + 4096)) return OEMGPU_ERR_HIP;          // (the paths are done: their frame may be overlaid)
     double *bd = (double *)(c->ws + a_b), *ld_ = (double *)(c->ws + a_l);
-    OEM_HIP(hipMemcpyAsync(bd, beta, nk * (size_t)(p + 1) * 8, hipMemcpyHostToDevice, s));
-    if ((rc = launch_spw_loss(s, A, y_dev, bd, p + 1, (int)nk, A.vec, (double *)(c->ws + a_p), ld_))) return rc;
-    OEM_HIP(hipMemcpyAsync(loss, ld_, nk * 8, hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipMemcpyAsync(bd, beta, nfit * (size_t)(p + 1) * 8, hipMemcpyHostToDevice, s));
+    if ((rc = launch_spw_loss(s, A, y_dev, bd, p + 1, (int)nfit, A.vec, (double *)(c->ws + a_p), ld_))) return rc;
+    OEM_HIP(hipMemcpyAsync(loss, ld_, nfit * 8, hipMemcpyDeviceToHost, s));
     OEM_HIP(hipStreamSynchronize(s));
-    for (size_t k = 0; k < nk; ++k) if (niter[k] == 0) loss[k] = 1e99;
+    for (size_t k = 0; k < nfit; ++k) if (niter[k] == 0) loss[k] = 1e99;
     return 0;
 }
 

@@ -219,6 +219,20 @@ CvSparseScorePlan cv_sparse_score_plan(int64_t n, int K, int npen, int nl, int n
 int launch_csr_cv_fold_score(hipStream_t s, const CvSparseScorePlan &P, int p, const int64_t *rowptr, const int32_t *ccol, const double *cval,
                              const double *yp, const int64_t *fold_start, const int64_t *fold_n, const double *B, double *bt, int mae,
                              double *part, const int *ncol, double *triples, double *predmat, const int *inv, int64_t n);
+// cv.oem on a resident sparse x with n <= p (oemgpu_cv_sparse_wide_score_res): no fold-ordered layout -- the handle's compressed rows
+// in the caller's order, the held-out rows of a fold from a row list, ONE fold's transposed table [npen][p + 1][nl16] staged at a time
+// (table_bytes: one penalty's).  Pure host arithmetic, the one place the launch is decided: nwg workgroups of XVS_CVW waves x npen x
+// lblk blocks of 64 lambdas per fold -- about four workgroups per CU over (penalty, lambda block), no more waves than a fold of
+// ceil(n / K) rows has rows, at most 1024 workgroups, the wave partials of all folds [K][waves][npen][nl16][4] under CVS_PART_MAX,
+// never fewer than one workgroup -- and the offsets of the call's pieces in the context's workspace (bytes in all).
+struct CvWideScorePlan {
+    int K, npen, nl, nl16, nwg, waves, lblk;
+    size_t table_bytes, part_bytes, a_list, a_raw, a_bt, a_part, a_tri, a_ncol, bytes;
+};
+CvWideScorePlan cv_wide_score_plan(int64_t n, int p, int K, int npen, int nl, int num_cu);
+int launch_csr_cv_wide_score_fold(hipStream_t s, const CvWideScorePlan &P, int p, const int64_t *rowptr, const int32_t *ccol, const double *cval,
+                                  const double *y, const int32_t *list, int nk, const double *raw, double *bt, int mae, const int *ncol,
+                                  double *part_k, double *predmat, int64_t n);
 int launch_csc_gram_ranges(hipStream_t s, const int64_t *colptr, const int32_t *rowidx, const double *val, const int32_t *cptr, int p, int nchunk,
                            int nrange, const int32_t *rtab, double *part);
 size_t csc_gram_lds_bytes(int p);
@@ -430,8 +444,13 @@ struct SpwArgs {
     const int32_t *long_row_list, *long_col_list;    // device: the lines of the long form
     int n_long_rows, n_long_cols;
     double *vec;             // device: t | v | v_prev | w (n doubles each) | the Lanczos table
+    // cv.oem's fold fit (oemgpu_fit_sparse_wide_fold_res): not null -- the rows with foldid[i] == leave_out are left out of every row
+    // pass and of the STATS pass, and nk, the kept rows (2 <= nk < n), stands wherever n enters the arithmetic
+    const int32_t *foldid = nullptr;
+    int leave_out = 0, nk = 0;
 };
-// out[i] = scale * sum over compressed row i (n of them) of cval v[ccol]; skipped while *done != 0 (done may be null)
+// out[i] = scale * sum over compressed row i (n of them) of cval v[ccol]; skipped while *done != 0 (done may be null).  A fold fit
+// (A.foldid): a left-out row is not read and out[i] = 0.0 exactly.  The column pass is never masked (its input is 0 in those rows).
 int launch_spw_rows(hipStream_t s, const SpwArgs &A, const double *v, double *out, double scale, const int *done);
 // out[j] = scale * sum over compressed column j (p of them) of val w[rowidx]
 int launch_spw_cols(hipStream_t s, const SpwArgs &A, const double *w, double *out, double scale, const int *done);

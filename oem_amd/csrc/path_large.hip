@@ -2439,15 +2439,17 @@ __global__ __launch_bounds__(256) void wide_block_sum_kernel(const double *__res
 // lambda_max(X X'/n) of every p >= n engine of this file: Lanczos on vectors of `len` entries (v, v_prev, w; T the tridiagonal), the
 // product w = X (X' v) / n enqueued by `product()`, the host's look every 16 steps -- the breakdown rule (T is exact), the tail rule
 // of run_path_large, the stagnation rule -- and at most min(n, MAXL) steps.  hT: pinned host memory for T.
-template <typename F>
+// after_init(): enqueued between lanczos_init_kernel and the first product (a fold fit restricts the start vector to its kept rows there).
+template <typename F, typename G>
 static int lanczos_wide_host(hipStream_t s, int len, int n, double *v, double *vp, double *w, double *T, double *hT, F &&product,
-                             double *theta_out, int *steps_out, bool *capped_out)
+                             double *theta_out, int *steps_out, bool *capped_out, G &&after_init)
 {
     const int mmax = n < MAXL ? n : MAXL;
     double theta = 0.0, theta_prev = -1.0;
     bool lz_capped = true;
     int m = 0;
     hipLaunchKernelGGL(lanczos_init_kernel, dim3(1), dim3(1024), 0, s, len, v, vp);
+    after_init();
     while (m < mmax) {
         const int chunk = (mmax - m) < 16 ? (mmax - m) : 16;
         for (int k = 0; k < chunk; ++k, ++m) {
@@ -2473,6 +2475,12 @@ static int lanczos_wide_host(hipStream_t s, int len, int n, double *v, double *v
     if (mmax >= n) lz_capped = false;
     *theta_out = theta; *steps_out = m; *capped_out = lz_capped;
     return 0;
+}
+template <typename F>
+static int lanczos_wide_host(hipStream_t s, int len, int n, double *v, double *vp, double *w, double *T, double *hT, F &&product,
+                             double *theta_out, int *steps_out, bool *capped_out)
+{
+    return lanczos_wide_host(s, len, n, v, vp, w, T, hT, product, theta_out, steps_out, capped_out, [] {});
 }
 
 // n > 2048: the rows in nb blocks of <= 2048 (a column of a block fits a wave's registers).  A dot product x_j . r now spans the
@@ -2681,21 +2689,39 @@ int run_path_wide(hipStream_t s, const PathArgs &a, const WideArgs &wd, double *
     return OEMGPU_ERR_UNSUPPORTED;
 }
 
+// a fold fit's Lanczos start vector: zero in the left-out rows, then unit length again -- the Krylov space is the kept rows' (every
+// later vector is a masked row pass's output or a combination of such vectors: zero there too).  One workgroup, one order.
+__global__ __launch_bounds__(1024) void spw_mask_start_kernel(int n, const int32_t *__restrict__ foldid, int leave_out, double *__restrict__ v)
+{
+    __shared__ double sh[16];
+    double nn = 0.0;
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        const double x = foldid[j] == leave_out ? 0.0 : v[j];
+        v[j] = x;
+        nn = fma(x, x, nn);
+    }
+    const double inv = 1.0 / sqrt(block_sum(nn, sh));
+    for (int j = threadIdx.x; j < n; j += blockDim.x) v[j] *= inv;
+}
+
 // p >= n on a resident sparse x: the general form of run_path_wide_nr with both products over the non-zeros (sparse_wide.hip) --
 // t = X beta (row pass), g = X't / n (column pass), path_update_kernel<0>: every penalty, any group layout, several penalties in one
 // call.  The eigen step is the shared Lanczos on n-vectors, w = X (X'v) / n as the column pass followed by the row pass.  Nothing of
 // n p entries anywhere; n is bounded by the int32 row indices only.  The batches of iterations are one serial chain (replay_batches).
+// A fold fit (A.foldid: cv.oem, ref R/cv_oem.R:155-175): the row passes leave the fold's rows out (their t and w are exact zeros, so
+// the unmasked column pass adds nothing for them), nk = the kept rows stands for n in g = X't / nk and in X (X'v) / nk, and Lanczos
+// runs in the kept rows' subspace of the n-vectors with nk in its step cap and its "not capped" rule.
 int run_path_sparse_wide(hipStream_t s, const PathArgs &a, const SpwArgs &A, double *host_scratch)
 {
-    const int q = a.p, n = A.n;
-    if (q != A.p) { set_error("internal: sparse wide engine dimensions"); return OEMGPU_ERR_INTERNAL; }
+    const int q = a.p, n = A.n, nk = A.foldid ? A.nk : A.n;
+    if (q != A.p || nk < 1 || nk > n) { set_error("internal: sparse wide engine dimensions"); return OEMGPU_ERR_INTERNAL; }
     double *t = A.vec, *v = t + n, *vp = v + n, *w = vp + n, *T = w + n;
     LState *st = reinterpret_cast<LState *>(a.work);
     double *beta = a.work + STATE_DBL, *g = beta + (q + 8);
     OEM_HIP(hipMemsetAsync(a.work, 0, sizeof(double) * path_large_work_doubles(q, 0), s));
     static_assert(SPW_T_DOUBLES >= 2 * MAXL, "the Lanczos table fits the sparse engine's workspace");
     OEM_HIP(hipMemsetAsync(A.vec, 0, sizeof(double) * (4 * (size_t)n + SPW_T_DOUBLES), s));
-    const double rn = 1.0 / (double)n;
+    const double rn = 1.0 / (double)nk;
     int rc = 0;
     // ---- d = 1.005 lambda_max(X X'/n)
     double theta = 0.0;
@@ -2705,7 +2731,10 @@ int run_path_sparse_wide(hipStream_t s, const PathArgs &a, const SpwArgs &A, dou
         if (!rc) rc = launch_spw_cols(s, A, v, g, 1.0, nullptr);
         if (!rc) rc = launch_spw_rows(s, A, g, w, rn, nullptr);
     };
-    if (int lrc = lanczos_wide_host(s, n, n, v, vp, w, T, host_scratch, eig_product, &theta, &m, &lz_capped)) return lrc;
+    auto mask_start = [&] {
+        if (A.foldid) hipLaunchKernelGGL(spw_mask_start_kernel, dim3(1), dim3(1024), 0, s, n, A.foldid, A.leave_out, v);
+    };
+    if (int lrc = lanczos_wide_host(s, n, nk, v, vp, w, T, host_scratch, eig_product, &theta, &m, &lz_capped, mask_start)) return lrc;
     if (rc) return rc;
     const double d = theta * 1.005;                     // ref src/oem_sparse.h:607-612
     OEM_HIP(hipMemsetAsync(g, 0, sizeof(double) * (size_t)(q + 8), s));

@@ -17,6 +17,19 @@
 // The iteration around the passes is path_large.hip: run_path_sparse_wide.  This file also holds what else the fit reads from
 // the data: X'y / n, colsq and the scaled lambda_zero vector from the compressed columns in one pass (the gather with STATS), and
 // the loss of the returned coefficients as a row pass and a sum in row-chunk order.
+//
+// cv.oem's fold fit (oemgpu_fit_sparse_wide_fold_res; ref R/cv_oem.R:155-175 slices x[!which, ] and calls oem()): the same kernels with
+// MASK, on the handle as it lies.  SpwMask names the rows with foldid == leave_out.
+//   row pass      a left-out row is not read and its output is an exact 0.0 (the gather writes it whatever the row's length; a
+//                 left-out long row's workgroup returns at once).  EVERY row pass of a fold fit is masked: t = X beta, the second
+//                 half of the eigen product, the loss.
+//   column pass   not masked in the iteration and the eigen product: its input vector is exactly zero in the left-out rows, so a
+//                 finite stored value contributes fma(x, 0, s) = s.  (Stored values of a left-out row must be finite.)
+//   STATS pass    a left-out entry is excluded by a select on foldid[idx[k]] -- from x_j'y and from sum x_j^2 -- so y of a left-out
+//                 row is never read; spw_y_kernel and spw_resid_sq_kernel select the same way.
+// The lane of an entry follows its position in the stored line, left-out entries included, so a column's sum over the kept rows is
+// added in another order than on the sliced matrix: a fold fit matches the fit of x[keep, ] to tolerance, not bit for bit.  The
+// unmasked instantiations are what they were (the mask is a trailing argument they never touch).
 #include "ctx.hpp"
 #include "path_dev.hpp"
 
@@ -44,10 +57,19 @@ __device__ __forceinline__ void spw_store_stats(const SpwStats &S, int j, double
     S.xy_std[j] = xy * inv;
 }
 
-template <int L, bool STATS>
+// the rows a fold fit leaves out: foldid[row] == leave_out (MASK forms only)
+struct SpwMask {
+    const int32_t *foldid;
+    int leave_out;
+};
+
+// MASK without STATS: the lines are ROWS and a left-out line is not read, its output an exact 0.0 (a long one's too: written here).
+// MASK with STATS: the lines are columns and a left-out ENTRY is excluded by a select; vec (y) is not read there.
+template <int L, bool STATS, bool MASK>
 __global__ __launch_bounds__(256) void spw_gather_kernel(const int64_t *__restrict__ ptr, const int32_t *__restrict__ idx,
                                                          const double *__restrict__ val, int nlines, const double *__restrict__ vec,
-                                                         double *__restrict__ out, double scale, const int *__restrict__ done, SpwStats S)
+                                                         double *__restrict__ out, double scale, const int *__restrict__ done, SpwStats S,
+                                                         SpwMask M)
 {
     if (done && *done) return;
     const int64_t gt = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -56,14 +78,23 @@ __global__ __launch_bounds__(256) void spw_gather_kernel(const int64_t *__restri
     double s = 0.0, s2 = 0.0;
     bool mine = false;
     if (line < nlines) {
-        const int64_t k0 = ptr[line], k1 = ptr[line + 1];
-        mine = k1 - k0 <= (int64_t)SPW_LONG_PER_LANE * L;                 // (a longer line: spw_long_kernel's)
-        if (mine) {
+        if (MASK && !STATS && M.foldid[line] == M.leave_out) {
+            if (sub == 0) out[line] = 0.0;
+        } else {
+            const int64_t k0 = ptr[line], k1 = ptr[line + 1];
+            mine = k1 - k0 <= (int64_t)SPW_LONG_PER_LANE * L;             // (a longer line: spw_long_kernel's)
+            if (mine) {
 #pragma unroll 4
-            for (int64_t k = k0 + sub; k < k1; k += L) {
-                const double x = val[k];
-                s = fma(x, vec[idx[k]], s);
-                if (STATS) s2 = fma(x, x, s2);
+                for (int64_t k = k0 + sub; k < k1; k += L) {
+                    const double x = val[k];
+                    if (MASK && STATS) {
+                        const int32_t r = idx[k];
+                        if (M.foldid[r] != M.leave_out) { s = fma(x, vec[r], s); s2 = fma(x, x, s2); }
+                    } else {
+                        s = fma(x, vec[idx[k]], s);
+                        if (STATS) s2 = fma(x, x, s2);
+                    }
+                }
             }
         }
     }
@@ -78,23 +109,29 @@ __global__ __launch_bounds__(256) void spw_gather_kernel(const int64_t *__restri
     }
 }
 
-template <bool STATS>
+template <bool STATS, bool MASK>
 __global__ __launch_bounds__(256) void spw_long_kernel(const int64_t *__restrict__ ptr, const int32_t *__restrict__ idx,
                                                        const double *__restrict__ val, const int32_t *__restrict__ list,
                                                        const double *__restrict__ vec, double *__restrict__ out, double scale,
-                                                       const int *__restrict__ done, SpwStats S)
+                                                       const int *__restrict__ done, SpwStats S, SpwMask M)
 {
     if (done && *done) return;
     __shared__ double sh[2][4];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int line = list[blockIdx.x];
+    if (MASK && !STATS && M.foldid[line] == M.leave_out) return;          // (its 0.0 is the gather's; uniform over the workgroup)
     const int64_t k0 = ptr[line], k1 = ptr[line + 1];
     double s = 0.0, s2 = 0.0;
 #pragma unroll 4
     for (int64_t k = k0 + tid; k < k1; k += 256) {
         const double x = val[k];
-        s = fma(x, vec[idx[k]], s);
-        if (STATS) s2 = fma(x, x, s2);
+        if (MASK && STATS) {
+            const int32_t r = idx[k];
+            if (M.foldid[r] != M.leave_out) { s = fma(x, vec[r], s); s2 = fma(x, x, s2); }
+        } else {
+            s = fma(x, vec[idx[k]], s);
+            if (STATS) s2 = fma(x, x, s2);
+        }
     }
     s = wave_sum(s);
     if (STATS) s2 = wave_sum(s2);
@@ -122,26 +159,33 @@ __global__ __launch_bounds__(256) void spw_scan_kernel(const int64_t *__restrict
     if ((threadIdx.x & 63) == 0 && len > 0) atomicMax(&cnt[1], len);
 }
 
-// stats[0 .. 3] of the data as they are: no centring and no scaling of y (0, 1, sum y^2, n); the shift flags 0
-__global__ __launch_bounds__(1024) void spw_y_kernel(const double *__restrict__ y, int n, int p, double *__restrict__ stats)
+// stats[0 .. 3] of the data as they are: no centring and no scaling of y (0, 1, sum y^2, n); the shift flags 0.  MASK: the sum over
+// the kept rows (y of a left-out row is not read) and nobs = the kept rows in stats[3]
+template <bool MASK>
+__global__ __launch_bounds__(1024) void spw_y_kernel(const double *__restrict__ y, int n, int p, double *__restrict__ stats, SpwMask M, int nobs)
 {
     __shared__ double sh[16];
     const int tid = threadIdx.x;
     double yy = 0.0;
-    for (int i = tid; i < n; i += 1024) yy = fma(y[i], y[i], yy);
+    for (int i = tid; i < n; i += 1024) {
+        if (MASK) { if (M.foldid[i] != M.leave_out) yy = fma(y[i], y[i], yy); }
+        else yy = fma(y[i], y[i], yy);
+    }
     yy = wave_sum(yy);
     if ((tid & 63) == 0) sh[tid >> 6] = yy;
     __syncthreads();
     if (tid == 0) {
         double t = 0.0;
         for (int k = 0; k < 16; ++k) t += sh[k];
-        stats[0] = 0.0; stats[1] = 1.0; stats[2] = t; stats[3] = (double)n;
+        stats[0] = 0.0; stats[1] = 1.0; stats[2] = t; stats[3] = (double)(MASK ? nobs : n);
         stats[stats_shift_flag(p)] = 0.0; stats[stats_shift_flag(p) + 1] = 0.0;
     }
 }
 
-// sum over the chunk's 2048 rows of (y - t)^2 -> part[c]
-__global__ __launch_bounds__(256) void spw_resid_sq_kernel(const double *__restrict__ y, const double *__restrict__ t, int n, double *__restrict__ part)
+// sum over the chunk's 2048 rows of (y - t)^2 -> part[c]; MASK: over its kept rows (the chunks and their order stay)
+template <bool MASK>
+__global__ __launch_bounds__(256) void spw_resid_sq_kernel(const double *__restrict__ y, const double *__restrict__ t, int n, double *__restrict__ part,
+                                                           SpwMask M)
 {
     __shared__ double ws[4];
     const int c = blockIdx.x, tid = threadIdx.x;
@@ -149,7 +193,7 @@ __global__ __launch_bounds__(256) void spw_resid_sq_kernel(const double *__restr
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
         const int64_t i = (int64_t)c * 2048 + m * 256 + tid;
-        if (i < n) { const double r = y[i] - t[i]; s = fma(r, r, s); }
+        if (i < n && !(MASK && M.foldid[i] == M.leave_out)) { const double r = y[i] - t[i]; s = fma(r, r, s); }
     }
     s = wave_sum(s);
     if ((tid & 63) == 0) ws[tid >> 6] = s;
@@ -176,18 +220,18 @@ int spw_lanes(int64_t lines, int64_t nnz, int num_cu)
     return L;
 }
 
-template <bool STATS>
+template <bool STATS, bool MASK>
 int spw_launch(hipStream_t s, const int64_t *ptr, const int32_t *idx, const double *val, int nlines, int L, const int32_t *list, int nlong,
-               const double *vec, double *out, double scale, const int *done, const SpwStats &S)
+               const double *vec, double *out, double scale, const int *done, const SpwStats &S, const SpwMask &M = SpwMask{nullptr, 0})
 {
     const unsigned wgs = (unsigned)(((int64_t)nlines * L + 255) / 256);
-#define OEM_SPW_CASE(LL) case LL: hipLaunchKernelGGL((spw_gather_kernel<LL, STATS>), dim3(wgs), dim3(256), 0, s, ptr, idx, val, nlines, vec, out, scale, done, S); break
+#define OEM_SPW_CASE(LL) case LL: hipLaunchKernelGGL((spw_gather_kernel<LL, STATS, MASK>), dim3(wgs), dim3(256), 0, s, ptr, idx, val, nlines, vec, out, scale, done, S, M); break
     switch (L) {
     OEM_SPW_CASE(1); OEM_SPW_CASE(2); OEM_SPW_CASE(4); OEM_SPW_CASE(8); OEM_SPW_CASE(16); OEM_SPW_CASE(32); OEM_SPW_CASE(64);
     default: set_error("internal: sparse wide engine lanes"); return OEMGPU_ERR_INTERNAL;
     }
 #undef OEM_SPW_CASE
-    if (nlong > 0) hipLaunchKernelGGL((spw_long_kernel<STATS>), dim3(nlong), dim3(256), 0, s, ptr, idx, val, list, vec, out, scale, done, S);
+    if (nlong > 0) hipLaunchKernelGGL((spw_long_kernel<STATS, MASK>), dim3(nlong), dim3(256), 0, s, ptr, idx, val, list, vec, out, scale, done, S, M);
     return 0;
 }
 
@@ -214,12 +258,15 @@ SpwPlan spw_plan(int64_t n, int p, int64_t nnz, int64_t longest_row, int64_t lon
 
 int launch_spw_rows(hipStream_t s, const SpwArgs &A, const double *v, double *out, double scale, const int *done)
 {
-    return spw_launch<false>(s, A.rowptr, A.ccol, A.cval, A.n, A.plan.row_L, A.long_row_list, A.n_long_rows, v, out, scale, done, SpwStats());
+    if (A.foldid)                                            // a fold fit: every row pass leaves the fold's rows out
+        return spw_launch<false, true>(s, A.rowptr, A.ccol, A.cval, A.n, A.plan.row_L, A.long_row_list, A.n_long_rows, v, out, scale, done, SpwStats(),
+                                       SpwMask{A.foldid, A.leave_out});
+    return spw_launch<false, false>(s, A.rowptr, A.ccol, A.cval, A.n, A.plan.row_L, A.long_row_list, A.n_long_rows, v, out, scale, done, SpwStats());
 }
 
 int launch_spw_cols(hipStream_t s, const SpwArgs &A, const double *w, double *out, double scale, const int *done)
 {
-    return spw_launch<false>(s, A.colptr, A.rowidx, A.val, A.p, A.plan.col_L, A.long_col_list, A.n_long_cols, w, out, scale, done, SpwStats());
+    return spw_launch<false, false>(s, A.colptr, A.rowidx, A.val, A.p, A.plan.col_L, A.long_col_list, A.n_long_cols, w, out, scale, done, SpwStats());
 }
 
 // the two lists of long lines and the longest row and column: cnt (device, 4 ints) <- rows: number, longest | columns: number, longest
@@ -238,10 +285,18 @@ int launch_spw_scan(hipStream_t s, const SpwArgs &A, int32_t *row_list, int32_t 
 int launch_spw_stats(hipStream_t s, const SpwArgs &A, const double *y, int standardize, double *xy, double *stats, double *xy_std)
 {
     SpwStats S;
-    S.xy = xy; S.stats = stats; S.xy_std = xy_std; S.standardize = standardize; S.p = A.p; S.n = (double)A.n;
-    hipLaunchKernelGGL(spw_y_kernel, dim3(1), dim3(1024), 0, s, y, A.n, A.p, stats);
-    const int rc = spw_launch<true>(s, A.colptr, A.rowidx, A.val, A.p, A.plan.col_L, A.long_col_list, A.n_long_cols, y, (double *)nullptr, 1.0,
-                                    (const int *)nullptr, S);
+    S.xy = xy; S.stats = stats; S.xy_std = xy_std; S.standardize = standardize; S.p = A.p; S.n = (double)(A.foldid ? A.nk : A.n);
+    const SpwMask M{A.foldid, A.leave_out};
+    int rc;
+    if (A.foldid) {
+        hipLaunchKernelGGL(spw_y_kernel<true>, dim3(1), dim3(1024), 0, s, y, A.n, A.p, stats, M, A.nk);
+        rc = spw_launch<true, true>(s, A.colptr, A.rowidx, A.val, A.p, A.plan.col_L, A.long_col_list, A.n_long_cols, y, (double *)nullptr, 1.0,
+                                    (const int *)nullptr, S, M);
+    } else {
+        hipLaunchKernelGGL(spw_y_kernel<false>, dim3(1), dim3(1024), 0, s, y, A.n, A.p, stats, M, A.n);
+        rc = spw_launch<true, false>(s, A.colptr, A.rowidx, A.val, A.p, A.plan.col_L, A.long_col_list, A.n_long_cols, y, (double *)nullptr, 1.0,
+                                     (const int *)nullptr, S);
+    }
     if (rc) return rc;
     OEM_HIP(hipGetLastError());
     return 0;
@@ -255,7 +310,8 @@ int launch_spw_loss(hipStream_t s, const SpwArgs &A, const double *y, const doub
     for (int k = 0; k < nk; ++k) {
         const int rc = launch_spw_rows(s, A, b + (size_t)k * rows + 1, t, 1.0, nullptr);
         if (rc) return rc;
-        hipLaunchKernelGGL(spw_resid_sq_kernel, dim3(nchunk), dim3(256), 0, s, y, t, A.n, part + (size_t)k * nchunk);
+        if (A.foldid) hipLaunchKernelGGL(spw_resid_sq_kernel<true>, dim3(nchunk), dim3(256), 0, s, y, t, A.n, part + (size_t)k * nchunk, SpwMask{A.foldid, A.leave_out});
+        else hipLaunchKernelGGL(spw_resid_sq_kernel<false>, dim3(nchunk), dim3(256), 0, s, y, t, A.n, part + (size_t)k * nchunk, SpwMask{nullptr, 0});
     }
     hipLaunchKernelGGL(spw_loss_sum_kernel, dim3((nk + 255) / 256), dim3(256), 0, s, part, nchunk, nk, loss);
     OEM_HIP(hipGetLastError());

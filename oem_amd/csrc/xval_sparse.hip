@@ -280,9 +280,86 @@ __global__ __launch_bounds__(64 * XVS_CVW) void csr_cv_fold_score_kernel(const i
     }
 }
 
+// cv.oem on a resident sparse x with n <= p (oemgpu_cv_sparse_wide_score_res; ref R/cv_oem.R:376-391): ONE fold's held-out rows against
+// that fold's table, on the handle's compressed rows in the caller's order -- no fold-ordered layout.  The kernel above keeps all K
+// tables on the device (K npen (p + 1) nl16 doubles: 1.8 GB at p = 200,000, K = 10, nl = 100); here bt [npen][p + 1][nl16] is one
+// fold's, staged fold by fold.  grid (workgroups, npen, blocks of 64 lambdas), XVS_CVW waves each: wave g of W takes the rows
+// list[g], list[g + W], .. of the fold's row list (ascending rows), its 64 lanes are 64 lambdas, the loop over the row's stored
+// entries reads bt[ccol + 1][lam] (coalesced in lambda), a lane keeps (count, centre, sum (v - c), sum (v - c)^2) in row order and
+// every wave leaves one partial [npen][nl16][4] (zeros from a wave without a row): cv_fold_finish_kernel's layout, per_fold = W.
+// Bound: 12 bytes per held-out non-zero per (penalty, 64-lambda block), plus the table rows -- 512-byte reads that stay in L2 while
+// npen (p + 1) nl16 doubles fit there and are HBM gathers beyond.
+template <bool PRED>
+__global__ __launch_bounds__(64 * XVS_CVW) void csr_cv_wide_score_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ ccol,
+                                                                         const double *__restrict__ cval, const double *__restrict__ y,
+                                                                         const int32_t *__restrict__ list, int nk, int p,
+                                                                         const double *__restrict__ bt, int nl, int mae,
+                                                                         const int *__restrict__ ncol, double *__restrict__ part,
+                                                                         double *__restrict__ pred, int64_t n)
+{
+    const int npen = gridDim.y, pen = blockIdx.y, lane = threadIdx.x & 63;
+    const int W = (int)gridDim.x * XVS_CVW;
+    const int gw = (int)blockIdx.x * XVS_CVW + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nl16 = (nl + 15) & ~15, lam = blockIdx.z * 64 + lane, Kd = p + 1;
+    const int nc = ncol[pen];
+    const bool active = lam < nc;                                  // a valid column of this penalty
+    const bool any = blockIdx.z * 64 < nc;                         // wave-uniform: some lane of the block is
+    const double *Bk = bt + (size_t)pen * Kd * nl16 + (active ? lam : 0);
+    const double b0 = Bk[0];
+    double cnt = 0.0, cen = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int r = gw; r < nk; r += W) {
+        const int64_t row = list[r];
+        double eta = b0;
+        if (any) {
+            const int64_t e0 = rowptr[row], e1 = rowptr[row + 1];
+            for (int64_t e = e0; e < e1; ++e) eta = fma(cval[e], Bk[(size_t)(ccol[e] + 1) * nl16], eta);
+            if (active) {
+                const double res = y[row] - eta, v = mae ? fabs(res) : res * res;
+                if (cnt == 0.0) cen = v;
+                const double dv = v - cen;
+                s1 += dv; s2 = fma(dv, dv, s2); cnt += 1.0;
+            }
+        }
+        if constexpr (PRED) {
+            if (lam < nl) pred[((size_t)pen * nl + lam) * n + row] = active ? eta : __builtin_nan("");
+        }
+    }
+    if (lam < nl16) {
+        double *q = part + (((size_t)gw * npen + pen) * nl16 + lam) * 4;
+        q[0] = cnt; q[1] = cen; q[2] = s1; q[3] = s2;
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------- the plan
+CvWideScorePlan cv_wide_score_plan(int64_t n, int p, int K, int npen, int nl, int num_cu)
+{
+    CvWideScorePlan P;
+    P.K = K; P.npen = npen; P.nl = nl; P.nl16 = (nl + 15) & ~15;
+    P.lblk = (nl + 63) / 64;
+    int64_t nwg = (int64_t)num_cu * 4 / ((int64_t)npen * P.lblk);
+    const int64_t per_fold = (n + K - 1) / K, cap = (per_fold + XVS_CVW - 1) / XVS_CVW;     // a wave per held-out row of a fold of the usual size
+    if (nwg > cap) nwg = cap;
+    if (nwg > 1024) nwg = 1024;
+    const size_t per_wave = (size_t)K * npen * P.nl16 * 4 * sizeof(double);
+    const int64_t fit = (int64_t)(CVS_PART_MAX / per_wave) / XVS_CVW;
+    if (nwg > fit) nwg = fit;
+    P.nwg = nwg < 1 ? 1 : (int)nwg;
+    P.waves = P.nwg * XVS_CVW;
+    P.table_bytes = (size_t)(p + 1) * P.nl16 * sizeof(double);
+    P.part_bytes = per_wave * P.waves;
+    Bump B;
+    P.a_list = B.take(sizeof(int32_t) * (size_t)n);
+    P.a_raw = B.take(sizeof(double) * (size_t)npen * nl * (p + 1));
+    P.a_bt = B.take(P.table_bytes * npen);
+    P.a_part = B.take(P.part_bytes);
+    P.a_tri = B.take(sizeof(double) * 3 * (size_t)K * npen * nl);
+    P.a_ncol = B.take(sizeof(int) * (size_t)npen);
+    P.bytes = B.off;
+    return P;
+}
+
 CvSparseScorePlan cv_sparse_score_plan(int64_t n, int K, int npen, int nl, int num_cu)
 {
     CvSparseScorePlan P;
@@ -423,6 +500,25 @@ int launch_csr_cv_fold_score(hipStream_t s, const CvSparseScorePlan &P, int p, c
                            part, (double *)nullptr, (const int *)nullptr, n);
     OEM_HIP(hipGetLastError());
     return launch_cv_fold_finish(s, part, P.waves, P.K, P.npen, P.nl, ncol, triples);
+}
+
+// fold k of the wide scoring: raw [npen][nl][p + 1] (that fold's coefficients, already on the device) -> bt, then its nk held-out rows
+// list[0 .. nk) -> the fold's wave partials part_k [waves][npen][nl16][4].  nk = 0: the partials are zeroed, nothing is read.
+int launch_csr_cv_wide_score_fold(hipStream_t s, const CvWideScorePlan &P, int p, const int64_t *rowptr, const int32_t *ccol, const double *cval,
+                                  const double *y, const int32_t *list, int nk, const double *raw, double *bt, int mae, const int *ncol,
+                                  double *part_k, double *predmat, int64_t n)
+{
+    if (nk <= 0) {
+        OEM_HIP(hipMemsetAsync(part_k, 0, P.part_bytes / P.K, s));
+        return 0;
+    }
+    const size_t total = (size_t)P.npen * (p + 1) * P.nl16;
+    hipLaunchKernelGGL(coef_transpose_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, raw, p + 1, P.nl, P.nl16, total, bt);
+    const dim3 grid(P.nwg, P.npen, P.lblk), block(64 * XVS_CVW);
+    if (predmat) hipLaunchKernelGGL(csr_cv_wide_score_kernel<true>, grid, block, 0, s, rowptr, ccol, cval, y, list, nk, p, bt, P.nl, mae, ncol, part_k, predmat, n);
+    else hipLaunchKernelGGL(csr_cv_wide_score_kernel<false>, grid, block, 0, s, rowptr, ccol, cval, y, list, nk, p, bt, P.nl, mae, ncol, part_k, (double *)nullptr, n);
+    OEM_HIP(hipGetLastError());
+    return 0;
 }
 
 }  // namespace oemgpu
