@@ -678,6 +678,57 @@ int oemgpu_sparse_x_create(oemgpu_ctx *ctx, int64_t n, int32_t p, const int64_t 
 void oemgpu_sparse_x_destroy(oemgpu_sparse_x *x);
 /* the bytes of device memory the handle holds (its one allocation); 0 for NULL */
 int64_t oemgpu_sparse_x_bytes(const oemgpu_sparse_x *x);
+/* The same handle from arrays that are ALREADY on the context's device (a torch sparse_csr / sparse_csc / coalesced sparse_coo tensor's
+ * components): compressed columns (layout OEMGPU_SPARSE_CSC: ptr_dev p + 1 pointers, idx_dev row indices) or compressed rows
+ * (OEMGPU_SPARSE_CSR: n + 1 pointers, column indices).  Pointers and indices are OEMGPU_I32 or OEMGPU_I64 each, values OEMGPU_F64 or
+ * OEMGPU_F32 (widened in the register, exactly); every array need only be aligned to its element.  The handle owns copies of
+ * everything: the caller's arrays may be freed when the call returns.  The result is the handle oemgpu_sparse_x_create makes of the
+ * same matrix, array for array (oemgpu_sparse_x_export): the other orientation comes from a stable least-significant-digit counting
+ * sort of the non-zeros by their index (digits of <= 11 bits: 1 pass up to 2048 target lines, 2 up to 2^22, 3 beyond; integer LDS
+ * atomics only, values moved as bit patterns, no floating-point arithmetic: two calls give the same arrays), its pointers from one
+ * lower bound per line.  Nothing is copied to the host but a few flag words.
+ * OEMGPU_ERR_ARG before any device work: a NULL ctx, ptr_dev or out, a layout or dtype code that is none of the above, n < 1, p < 1,
+ * nnz < 0, NULL idx_dev or val_dev with nnz > 0; OEMGPU_ERR_UNSUPPORTED for n >= 2^31 and for nnz >= 2^31.  From the device, with
+ * csc_check's sentences (their row-wise counterparts for compressed rows) and nothing of the input used: ptr[0] != 0, ptr[last] != nnz,
+ * a decreasing pointer, an index outside its range and a line whose indices are not strictly increasing (duplicates, unsorted
+ * lines) -- the message names the first offending entry's line (an integer minimum over the entries).  OEMGPU_ERR_ARG each. */
+#define OEMGPU_SPARSE_CSC 0
+#define OEMGPU_SPARSE_CSR 1
+#define OEMGPU_I32 0
+#define OEMGPU_I64 1
+int oemgpu_sparse_x_create_dev(oemgpu_ctx *ctx, int64_t n, int32_t p, int32_t layout, const void *ptr_dev, int32_t ptr_dtype,
+                               const void *idx_dev, int32_t idx_dtype, const void *val_dev, int32_t val_dtype, int64_t nnz,
+                               oemgpu_sparse_x **out);
+/* Host-only plan of oemgpu_sparse_x_create_dev (pure arithmetic, runs without a GPU): out[0] passes of the sort, [1] bits per digit,
+ * [2] workgroups of a pass, [3] bytes of the context's workspace the call takes (the line numbers and the sorted indices, 4 B a
+ * non-zero each; one 16 B-a-non-zero buffer from two passes on, a second from three; the digit table 4 B x 2^bits x workgroups; all
+ * in 256-byte granules), [4] bytes of the handle, [5] non-zeros per workgroup (a multiple of 2048), [6] bits of the largest index,
+ * [7] target lines (n for compressed columns, p for compressed rows).  OEMGPU_ERR_ARG for n, p or num_cu < 1, nnz < 0, an unknown
+ * layout or a NULL out; OEMGPU_ERR_UNSUPPORTED for n >= 2^31 or nnz >= 2^31. */
+int oemgpu_selftest_sparse_build_plan(int64_t n, int32_t p, int64_t nnz, int32_t layout, int32_t num_cu, int64_t *out /* 8 */);
+/* The handle's arrays copied to host buffers (any pointer may be NULL: that array is skipped): colptr p + 1, rowidx and val nnz (every
+ * column's entries by ascending row), rowptr n + 1, ccol and cval nnz (every row's entries by ascending column), cptr
+ * (ceil(n / 8192) + 1) x p.  dims: out[0] n, [1] p, [2] nnz, [3] the longest column. */
+int oemgpu_sparse_x_export(const oemgpu_sparse_x *x, int64_t *colptr, int32_t *rowidx, double *val, int64_t *rowptr, int32_t *ccol,
+                           double *cval, int32_t *cptr);
+int oemgpu_sparse_x_dims(const oemgpu_sparse_x *x, int64_t *out /* 4 */);
+/* HIP-event times (ms) of this thread's last oemgpu_sparse_x_create_dev with nnz > 0: ms[0] check and widen (with its read-back),
+ * ms[1] the sort passes, ms[2] the other orientation's pointers, the chunk pointers and the longest column. */
+int oemgpu_last_sparse_build_timings(double *ms /* 3 */);
+/* oem() on a resident sparse x: what oemgpu_fit_sparse computes, with y_dev (n doubles) on the device and nothing uploaded.  n > p:
+ * the moment buffer from the handle's compressed columns by oemgpu_fit_sparse's route (the same kernels on the same values: without an
+ * intercept the results carry the bits of oemgpu_fit_sparse; with one, intval is taken from the moment buffer's diagonal, as
+ * oemgpu_cv_sparse_fold_fits_res takes it, and agrees to rounding), then the same solve.  n <= p: oemgpu_fit_sparse_wide_res, and
+ * OEMGPU_ERR_UNSUPPORTED with an intercept (oemgpu_fit_sparse's sentence).  OEMGPU_ERR_ARG for a NULL argument, bad options and a
+ * handle on another device than the context's. */
+int oemgpu_fit_sparse_res(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, const double *y_dev, int32_t standardize, int32_t intercept,
+                          const oemgpu_opts *opts, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+/* xval.oem on a resident sparse x: oemgpu_xval_sparse with its upload phase replaced by the handle's arrays and the caller's y_dev (n
+ * doubles) and foldid_dev (n int32, 1 .. nfolds) -- every later phase, output and refusal unchanged (the same kernels on the same
+ * values: the same bits); also OEMGPU_ERR_ARG for a handle on another device than the context's. */
+int oemgpu_xval_sparse_res(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
+                           int32_t standardize, int32_t intercept, int32_t type_measure, const oemgpu_opts *opts, double *beta,
+                           double *lambda_out, int32_t *niter, double *loss, double *d, double *cvm, double *cvsd);
 /* cv.oem's fold fit on the resident sparse x (ref R/cv_oem.R:129-175): what `.Call("oem_fit_logistic_sparse", ...)` computes on
  * x[keep, ], y[keep] with keep = foldid_dev != leave_out, every particular of oemgpu_fit_logistic_sparse included.  Nothing is sliced,
  * uploaded or converted: the passes leave the fold's rows out and the number of kept rows stands where n enters the arithmetic (the

@@ -15,6 +15,8 @@ PENALTIES = ["elastic.net", "lasso", "ols", "mcp", "scad", "mcp.net", "scad.net"
 
 OEMGPU_SEM_DENSE, OEMGPU_SEM_BIG = 0, 1
 OEMGPU_F64, OEMGPU_F32 = 0, 1              # element types of the row-major entries
+OEMGPU_SPARSE_CSC, OEMGPU_SPARSE_CSR = 0, 1    # layouts of oemgpu_sparse_x_create_dev
+OEMGPU_I32, OEMGPU_I64 = 0, 1              # its pointer / index types
 RM_P_MAX = 1024                            # OEMGPU_RM_P_MAX: columns the row-major pass takes
 ERR_INTERRUPTED = -6
 NHOSTSTATS = 9
@@ -81,6 +83,15 @@ _SIGS = {
     "oemgpu_sparse_x_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "oemgpu_sparse_x_destroy": (None, [C.c_void_p]),
     "oemgpu_sparse_x_bytes": (C.c_int64, [C.c_void_p]),
+    "oemgpu_sparse_x_create_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                             C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
+    "oemgpu_selftest_sparse_build_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "oemgpu_sparse_x_export": (C.c_int, [C.c_void_p] + [C.c_void_p] * 7),
+    "oemgpu_sparse_x_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "oemgpu_last_sparse_build_timings": (C.c_int, [_dp]),
+    "oemgpu_fit_sparse_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(OemgpuOpts)] + _OUT),
+    "oemgpu_xval_sparse_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.POINTER(OemgpuOpts)] + _OUT + [_dp, _dp]),
     "oemgpu_fit_logistic_sparse_fold_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                        C.c_double, C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_logistic_cv_score_sparse_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, _dp, C.c_int32, _dp,

@@ -58,6 +58,68 @@ def _is_scipy_sparse(x):
     return type(x).__module__.startswith("scipy.sparse")
 
 
+def _is_torch_sparse(x):
+    """a torch tensor of any sparse layout (host or device)"""
+    if not type(x).__module__.startswith("torch") or not hasattr(x, "layout"):
+        return False
+    import torch
+    return isinstance(x, torch.Tensor) and x.layout != torch.strided
+
+
+def _torch_sparse_parts(x):
+    """The component tensors of a 2-d torch sparse tensor as (layout code, pointers, indices, values), where it lies: compressed rows
+    or columns as they are; a COO tensor coalesced by torch (on its device) and its row pointers made with dense ops (bincount,
+    cumsum) -- no torch sparse-library call.  ValueError, naming the cause, for a block layout, more than two dimensions, dense
+    (hybrid) dimensions and a dtype that is not served."""
+    import torch
+    if x.layout not in (torch.sparse_csr, torch.sparse_csc, torch.sparse_coo):
+        raise ValueError(f"a sparse tensor of layout {x.layout} is not served: torch.sparse_csr, torch.sparse_csc or torch.sparse_coo")
+    if x.ndim != 2:
+        raise ValueError(f"x must be a matrix: a 2-d sparse tensor, not one of {x.ndim} dimensions")
+    n = int(x.shape[0])
+    if x.dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"the values of a sparse tensor must be float64 or float32, not {x.dtype}")
+    if x.layout == torch.sparse_coo:
+        if x.dense_dim() != 0:
+            raise ValueError("a hybrid sparse tensor (dense dimensions) is not served")
+        x = x.coalesce()                                               # sorted by (row, column), duplicates summed: on the tensor's device
+        ind, val = x.indices(), x.values()
+        ptr = torch.zeros(n + 1, dtype=torch.int64, device=ind.device)
+        if ind.shape[1] > 0:
+            ptr[1:] = torch.cumsum(torch.bincount(ind[0], minlength=n), 0)
+        layout, idx = L.OEMGPU_SPARSE_CSR, ind[1]
+    elif x.layout == torch.sparse_csr:
+        layout, ptr, idx, val = L.OEMGPU_SPARSE_CSR, x.crow_indices(), x.col_indices(), x.values()
+    else:
+        layout, ptr, idx, val = L.OEMGPU_SPARSE_CSC, x.ccol_indices(), x.row_indices(), x.values()
+    if val.ndim != 1:
+        raise ValueError("a hybrid sparse tensor (dense dimensions) is not served")
+    if val.dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"the values of a sparse tensor must be float64 or float32, not {val.dtype}")
+    for t in (ptr, idx):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"the indices of a sparse tensor must be int32 or int64, not {t.dtype}")
+    return layout, ptr.contiguous(), idx.contiguous(), val.contiguous()
+
+
+def _torch_sparse_to_scipy(x):
+    """A sparse torch tensor ON THE HOST as the scipy matrix of its component arrays (values float64; float32 widened)"""
+    import scipy.sparse as sp
+    if x.is_cuda:
+        raise ValueError("a device tensor stays on its device: SparseX(x) takes it there")
+    layout, ptr, idx, val = _torch_sparse_parts(x)
+    cls = sp.csr_matrix if layout == L.OEMGPU_SPARSE_CSR else sp.csc_matrix
+    return cls((val.numpy().astype(np.float64), idx.numpy(), ptr.numpy()), shape=(int(x.shape[0]), int(x.shape[1])))
+
+
+def _sparse_tensor_arg(x):
+    """What a front end makes of its x: a sparse torch tensor on the host becomes its scipy matrix (the scipy route); anything else,
+    a sparse device tensor among it, is returned as it is"""
+    if _is_torch_sparse(x) and not x.is_cuda:
+        return _torch_sparse_to_scipy(x)
+    return x
+
+
 def _csc_arrays(x):
     """The compressed-column arrays of a scipy.sparse x as R's coercion to dgCMatrix leaves them: float64 values, duplicate entries
     summed, row indices sorted inside every column.  Returns contiguous (int64 colptr, int32 rowidx, float64 values).  The caller's
@@ -424,9 +486,13 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
         alpha=1.0, gamma=3.0, tau=0.5, groups=(), penalty_factor=None, group_weights=None, standardize=True,
         intercept=True, maxit=500, tol=1e-7, irls_maxit=100, irls_tol=1e-3, accelerate=False, ncores=-1,
         compute_loss=False, hessian_type="upper.bound", varnames=None, ngpus=0, devices=None, upload_threads=0,
-        interrupt=None, _entry_weights=None, _args_only=False):
+        interrupt=None, _entry_weights=None, _args_only=False, _res_fit=False):
     """oem(): R/oem.R:162-507, dense gaussian branch.  ngpus / devices / upload_threads / interrupt: the host-resident
-    options of include/oemgpu.h (`options` gains ngpus / device; absent => one GPU)."""
+    options of include/oemgpu.h (`options` gains ngpus / device; absent => one GPU).
+    A sparse torch tensor (sparse_csr, sparse_csc, sparse_coo) is oem_fit_sparse's: on a device it is fitted where it lies."""
+    if _is_torch_sparse(x):
+        kw = {k: v for k, v in locals().items() if k not in ("x", "y", "_entry_weights", "_args_only", "_res_fit")}
+        return oem_fit_sparse(x, y, **kw)
     L.sync_switches()
     if family not in ("gaussian", "binomial"):
         raise ValueError("'arg' should be one of 'gaussian', 'binomial'")
@@ -435,7 +501,7 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
     if resident_sparse and not _args_only:
         if getattr(x, "_h", None) is None:
             raise ValueError("this SparseX is closed")
-        if x.shape[0] > x.shape[1]:                                   # n > p: the Gram form's fit needs the host arrays (cv_oem builds its option block here)
+        if x.shape[0] > x.shape[1] and not _res_fit:                  # n > p through oem() itself: the sentence stays (oem_fit_sparse serves the handle)
             raise ValueError("oem() on a SparseX is not built: oem() takes the scipy.sparse matrix itself; the resident handle is what cv_oem runs on")
     if getattr(x, "ndim", 0) != 2 and not resident_sparse:
         raise ValueError("x must have at least two columns")
@@ -476,11 +542,15 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
         if ngpus or devices is not None:
             raise ValueError("oem() on a SparseX: the rows of a sparse x are not split over devices")
         a.c.accelerate = 0                                             # oemSparse has no acceleration
-        if intercept:
+        if intercept and n <= p:
             _sparse_wide_intercept_refusal(n, p, a, standardize)
         import torch
         yd = _device_y(y, x.device).to(x.device)
         torch.cuda.current_stream(x.device).synchronize()
+        if n > p:                                                      # oem_fit_sparse on the handle: the Gram form from the resident columns
+            L.check(lib.oemgpu_fit_sparse_res(context(x.device.index), x.handle, yd.data_ptr(), int(bool(standardize)), int(bool(intercept)),
+                                              C.byref(a.c), *a.outputs(p + 1)))
+            return _decorate(a, penalty, varnames, True, n, p)
         L.check(lib.oemgpu_fit_sparse_wide_res(context(x.device.index), x.handle, yd.data_ptr(), int(bool(standardize)), C.byref(a.c),
                                                *a.outputs(p + 1)))
         return _decorate(a, penalty, varnames, True, n, p)
@@ -526,6 +596,23 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
         L.check(lib.oemgpu_fit_dense(_dptr(xh), n, p, _dptr(yh), int(bool(standardize)), int(bool(intercept)),
                                      C.byref(a.c), *a.outputs(p + 1)))
     return _decorate(a, penalty, varnames, True, n, p)
+
+
+def oem_fit_sparse(x, y, **kw):
+    """`.Call("oem_fit_sparse", ...)` (ref src/oem_sparse.cpp:30-267), the entry oem() reaches with a sparse x, with oem()'s arguments
+    and result.  x: a scipy.sparse matrix (oem()'s own route: oemgpu_fit_sparse), a SparseX of any shape (oemgpu_fit_sparse_res: the
+    moment buffer from the resident columns, nothing uploaded but y; n <= p from the non-zeros, without an intercept), or a sparse
+    torch tensor -- on a device it is wrapped in a SparseX for the length of the call, on the host it becomes its scipy matrix.
+    y: numpy or a device tensor.  On a handle: no weights, no ngpus / devices."""
+    x = _sparse_tensor_arg(x)
+    if _is_torch_sparse(x):
+        with SparseX(x) as sx:
+            return oem(sx, y, _res_fit=True, **kw)
+    if isinstance(x, SparseX):
+        return oem(x, y, _res_fit=True, **kw)
+    if not _is_scipy_sparse(x):
+        raise TypeError("x must be a scipy.sparse matrix, a SparseX or a sparse torch tensor (oem takes a dense one)")
+    return oem(x, y, **kw)
 
 
 def oem_fit_dense_weighted(x, y, weights, **kw):
@@ -611,13 +698,22 @@ def oem_fit_logistic_dense(x, y, penalty=None, weights=(), lambda_=(), nlambda=1
 class SparseX:
     """A scipy.sparse x resident on a GPU (oemgpu_sparse_x_create): the compressed columns as _csc_arrays leaves them, their chunk
     pointers and the compressed-row copy, uploaded and built once.  cv_oem(family="binomial") on a sparse x makes one and runs its full
-    fit, its fold fits and its scoring on it; oem_fit_logistic_sparse(_fold=...) and logistic_cv_score take one.  Owns the handle:
-    close() frees it (so does leaving a `with` block, and __del__); a closed SparseX refuses further use."""
+    fit, its fold fits and its scoring on it; oem_fit_sparse, oem_fit_logistic_sparse, xval_oem, cv_oem, predict and logistic_cv_score
+    take one.  Owns the handle: close() frees it (so does leaving a `with` block, and __del__); a closed SparseX refuses further use.
+    x may also be a sparse torch tensor (sparse_csr, sparse_csc or sparse_coo; float64 / float32 values, int32 / int64 indices).  On a
+    device the handle is built there from the tensor's components (oemgpu_sparse_x_create_dev: checked, copied and transposed in HIP;
+    nothing goes to the host; unsorted lines and duplicates are refused, a COO tensor is coalesced by torch first); on the host it
+    becomes the scipy matrix of its components.  The handle holds copies: the tensor may be freed afterwards."""
 
     def __init__(self, x, device=None):
         import scipy.sparse as sp
         import torch
         self._h = None
+        if _is_torch_sparse(x):
+            if x.is_cuda:
+                self._from_device_tensor(x)
+                return
+            x = _torch_sparse_to_scipy(x)
         if not sp.issparse(x):
             raise TypeError("x must be a scipy.sparse matrix")
         if len(x.shape) != 2:
@@ -630,6 +726,42 @@ class SparseX:
         L.check(L.lib().oemgpu_sparse_x_create(context(self.device.index), self.shape[0], self.shape[1], colptr.ctypes.data, _iptr(rowidx),
                                                _dptr(vals), C.byref(h)))
         self._h = h
+
+    def _from_device_tensor(self, x):
+        import torch
+        layout, ptr, idx, val = _torch_sparse_parts(x)
+        self.shape = (int(x.shape[0]), int(x.shape[1]))
+        self.device = val.device
+        self.nnz = int(val.shape[0])
+        code = {torch.int32: L.OEMGPU_I32, torch.int64: L.OEMGPU_I64, torch.float64: L.OEMGPU_F64, torch.float32: L.OEMGPU_F32}
+        h = C.c_void_p()
+        torch.cuda.current_stream(self.device).synchronize()           # the components (a coalesce, the row pointers) are in place
+        L.check(L.lib().oemgpu_sparse_x_create_dev(context(self.device.index), self.shape[0], self.shape[1], layout, ptr.data_ptr(), code[ptr.dtype],
+                                                   idx.data_ptr() if self.nnz else None, code[idx.dtype],
+                                                   val.data_ptr() if self.nnz else None, code[val.dtype], self.nnz, C.byref(h)))
+        self._h = h
+
+    def export(self):
+        """oemgpu_sparse_x_export: the handle's arrays on the host, as a dict -- colptr, rowidx, val (compressed columns), rowptr, ccol,
+        cval (compressed rows), cptr (the chunk pointers, chunks + 1 rows of p) and maxcol"""
+        n, p = self.shape
+        dims = (C.c_int64 * 4)()
+        L.check(L.lib().oemgpu_sparse_x_dims(self.handle, dims))
+        nnz, chunks = int(dims[2]), (n + 8191) // 8192
+        out = {"colptr": np.zeros(p + 1, np.int64), "rowidx": np.zeros(nnz, np.int32), "val": np.zeros(nnz, np.float64),
+               "rowptr": np.zeros(n + 1, np.int64), "ccol": np.zeros(nnz, np.int32), "cval": np.zeros(nnz, np.float64),
+               "cptr": np.zeros((chunks + 1, p), np.int32)}
+        L.check(L.lib().oemgpu_sparse_x_export(self.handle, *[out[k].ctypes.data for k in ("colptr", "rowidx", "val", "rowptr", "ccol", "cval", "cptr")]))
+        out["maxcol"] = int(dims[3])
+        return out
+
+    def to_scipy(self):
+        """the matrix as a scipy.sparse.csc_matrix (float64, sorted indices) from the handle's compressed columns"""
+        import scipy.sparse as sp
+        n, p = self.shape
+        colptr, rowidx, val = np.zeros(p + 1, np.int64), np.zeros(self.nnz, np.int32), np.zeros(self.nnz, np.float64)
+        L.check(L.lib().oemgpu_sparse_x_export(self.handle, colptr.ctypes.data, rowidx.ctypes.data, val.ctypes.data, None, None, None, None))
+        return sp.csc_matrix((val, rowidx, colptr), shape=(n, p))
 
     @property
     def handle(self):
@@ -678,13 +810,20 @@ def oem_fit_logistic_sparse(x, y, penalty=None, weights=(), lambda_=(), nlambda=
     _fold (cv_oem's fold fits): (a SparseX, foldid as an int32 device tensor or None, nfolds, leave_out, y as a float64 device tensor) --
     the fit on the rows with foldid != leave_out of the resident x (oemgpu_fit_logistic_sparse_fold_res; leave_out = 0: every row, the
     bits of the plain call), which reports their number as nobs.  x is then not looked at beyond its shape (the SparseX itself may be
-    passed)."""
+    passed).
+    x may also be an open SparseX (the fit on the handle: leave_out = 0, the plain call's bits) or a sparse torch tensor: on a device it
+    is wrapped in a SparseX for the length of the call, on the host it becomes its scipy matrix.  y: numpy or a device tensor."""
     import scipy.sparse as sp
+    x = _sparse_tensor_arg(x)
+    if _is_torch_sparse(x):                                            # a sparse device tensor: a SparseX for the length of the call
+        kw = {k: v for k, v in locals().items() if k not in ("x", "y", "sp", "_fold")}
+        with SparseX(x) as sx:
+            return oem_fit_logistic_sparse(sx, y, **kw)
     L.sync_switches()
     penalty = _match_penalty(penalty)
     if hessian_type not in ("upper.bound", "full"):
         raise ValueError("'arg' should be one of 'upper.bound', 'full'")
-    if not (sp.issparse(x) or (_fold is not None and isinstance(x, SparseX))):
+    if not (sp.issparse(x) or isinstance(x, SparseX)):
         raise TypeError("x must be a scipy.sparse matrix (oem_fit_logistic_dense takes a dense one)")
     if len(x.shape) != 2:
         raise ValueError("x must have at least two columns")
@@ -693,7 +832,7 @@ def oem_fit_logistic_sparse(x, y, penalty=None, weights=(), lambda_=(), nlambda=
         raise ValueError("x must have at least two columns")
     if len(weights) > 0:                                               # R/oem.R:244
         raise L.OemgpuError(-4, "weights not implemented yet.")
-    yh = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+    yh = np.ascontiguousarray(np.asarray(y.cpu() if _is_torch_cuda(y) else y, dtype=np.float64).reshape(-1))
     if yh.shape[0] != n:
         raise ValueError("x and y lengths do not match")
     if len(np.unique(yh)) > 2:                                         # R/oem.R:250-252
@@ -712,6 +851,9 @@ def oem_fit_logistic_sparse(x, y, penalty=None, weights=(), lambda_=(), nlambda=
     lam_list = _lambda_list(lambda_, len(penalty))
     a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
               compute_loss, penalty_factor, groups, unique_groups, group_weights, interrupt=interrupt)
+    if _fold is None and isinstance(x, SparseX):                       # the fit on a handle: leave_out = 0, the bits of the plain call
+        import torch
+        _fold = (x, None, 3, 0, torch.as_tensor(yh, device=x.device))
     if _fold is not None:
         import torch
         sx, fd, nfolds, leave_out, yd = _fold
@@ -876,7 +1018,14 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
     x.toarray() without building it; no weights, ngpus or devices there).  foldid: values 1..nfolds; drawn with `rng` (a numpy Generator)
     as sample(rep(seq(nfolds), length = n)) when None.  ngpus / devices (host x only): the rows over several devices inside the
     library, as in oem().  A row-major float64 or float32 device tensor is gathered into fold order where it lies
-    (oemgpu_xval_dense_rm_dev; _xval_rowmajor_in_place): the column-major call's result bit for bit, without its copies."""
+    (oemgpu_xval_dense_rm_dev; _xval_rowmajor_in_place): the column-major call's result bit for bit, without its copies.
+    An open SparseX runs oemgpu_xval_sparse_res on the resident columns (the scipy call's bits, nothing uploaded but y and foldid); a
+    sparse torch tensor on a device is wrapped in one for the length of the call, one on the host becomes its scipy matrix."""
+    x = _sparse_tensor_arg(x)
+    if _is_torch_sparse(x):                                            # a sparse device tensor: a SparseX for the length of the call
+        kw = {k: v for k, v in locals().items() if k not in ("x", "y")}
+        with SparseX(x) as sx:
+            return xval_oem(sx, y, **kw)
     L.sync_switches()
     if family not in ("gaussian", "binomial"):
         raise ValueError("'arg' should be one of 'gaussian', 'binomial'")
@@ -887,7 +1036,7 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
         raise ValueError("'arg' should be one of " + ", ".join("'%s'" % t for t in _TYPE_MEASURES))
     if family == "binomial":
         raise ValueError("binomial models not yet supported for xval, use cv.oem() instead")
-    if getattr(x, "ndim", 0) != 2:
+    if getattr(x, "ndim", 0) != 2 and not isinstance(x, SparseX):
         raise ValueError("x must have at least two columns")
     n, p = x.shape
     if p >= n:
@@ -904,7 +1053,10 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
         nfolds = int(foldid.max())
     if nfolds < 3:
         raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
-    sparse = _is_scipy_sparse(x)                                 # R/oem_xval.R:196-201 stops here; :500 names the routine served now
+    on_handle = isinstance(x, SparseX)                           # the resident columns: oemgpu_xval_sparse_res, nothing uploaded but y and foldid
+    if on_handle:
+        x.handle                                                 # (a closed SparseX raises here)
+    sparse = _is_scipy_sparse(x) or on_handle                    # R/oem_xval.R:196-201 stops here; :500 names the routine served now
     if sparse and len(weights) > 0:
         raise ValueError("observation weights of xval.oem need a dense x: the weighted call scales a fold-ordered dense copy by "
                          "sqrt(w), which a sparse x never builds")
@@ -945,7 +1097,14 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
     fid = np.ascontiguousarray(foldid, dtype=np.int32)
     tm = 1 if type_measure == "mae" else 0
     lib = L.lib()
-    if sparse:
+    if on_handle:
+        import torch
+        yd = _device_y(y, x.device).to(x.device)
+        fd = torch.as_tensor(fid, device=x.device)
+        torch.cuda.current_stream(x.device).synchronize()
+        L.check(lib.oemgpu_xval_sparse_res(context(x.device.index), x.handle, yd.data_ptr(), fd.data_ptr(), int(nfolds), int(bool(standardize)),
+                                           int(bool(intercept)), tm, C.byref(a.c), *out, _dptr(cvm), _dptr(cvsd)))
+    elif sparse:
         colptr, rowidx, vals = _csc_arrays(x)
         yh = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
         L.check(lib.oemgpu_xval_sparse(n, p, colptr.ctypes.data, rowidx.ctypes.data, vals.ctypes.data, yh.ctypes.data, fid.ctypes.data,
@@ -1286,8 +1445,8 @@ def _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, fold
         raise ValueError("y must be a binary outcome")
     import torch
     lam_arg = () if lambda_ is None else lambda_
-    if _is_scipy_sparse(x):
-        with SparseX(x) as sx:                                         # the one upload, the one compressed-row build
+    if _is_scipy_sparse(x) or _is_torch_sparse(x):
+        with SparseX(x) as sx:                                         # the one upload (a device tensor: none), the one compressed-row build
             yd = torch.as_tensor(yh, device=sx.device)
 
             def fit(fd, nfolds, leave_out):                            # the full fit is leave_out = 0 on the same handle
@@ -1695,10 +1854,15 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
         raise ValueError("'arg' should be one of " + ", ".join("'%s'" % t for t in _TYPE_MEASURES))
     if lambda_ is not None and len(lambda_) < 2:
         raise ValueError("Need more than one value of lambda for cv.oem")
+    x = _sparse_tensor_arg(x)
     if family == "binomial":
         return _cv_oem_binomial(x, y, penalty, weights, lambda_, type_measure, nfolds, foldid, grouped, keep, rng, kw)
     if len(weights) > 0:
         raise ValueError("weights not implemented yet.")
+    if _is_torch_sparse(x):                                       # a sparse device tensor: a SparseX for the length of the call
+        with SparseX(x) as sx:
+            return cv_oem(sx, y, penalty=penalty, lambda_=lambda_, type_measure=None if type_measure == "default" else type_measure, nfolds=nfolds, foldid=foldid, grouped=grouped,
+                          keep=keep, rng=rng, parallel=parallel, family=family, **kw)
     if _is_scipy_sparse(x):
         raise ValueError("cv.oem on a sparse x is served for family = \"binomial\" only (family = \"gaussian\" runs on a resident "
                          "oem_amd.SparseX(x), not on the scipy matrix)")
@@ -1816,6 +1980,10 @@ def predict(fit, newx=None, s=None, which_model=0, type="link"):
         return _nonzero_lists(nbeta)
     if newx is None:
         raise ValueError("A value for 'newx' must be supplied")
+    newx = _sparse_tensor_arg(newx)
+    if _is_torch_sparse(newx):                                                             # a sparse device tensor: a SparseX for the length of the call
+        with SparseX(newx) as sx:
+            return _predict_device(sx, nbeta, type if fit.get("family") == "binomial" else "link")
     if isinstance(newx, SparseX) or _is_torch_cuda(newx):                                  # on the device, where newx lies
         return _predict_device(newx, nbeta, type if fit.get("family") == "binomial" else "link")
     if hasattr(newx, "tocsc") and newx.__class__.__module__.startswith("scipy.sparse"):    # a dgCMatrix newx: R multiplies it as it is (R/methods.R:48-109)

@@ -3080,8 +3080,10 @@ static int xvs_fold_phases(oemgpu_ctx *c, const XvalSparsePlan &SP, const XvalLa
 static int xval_sparse_impl(int mode, int64_t n, int32_t p, const int64_t *colptr, const int32_t *rowidx, const double *values, const double *y,
                             const int32_t *foldid, int32_t K, int32_t standardize, int32_t intercept, int32_t type_measure, const oemgpu_opts *o,
                             int npen, int nl, const double *coef, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d,
-                            double *cvm, double *cvsd, double *triples, double *moments_out)
+                            double *cvm, double *cvsd, double *triples, double *moments_out, oemgpu_ctx *cres = nullptr,
+                            const oemgpu_sparse_x *xres = nullptr)
 {
+    // xres (oemgpu_xval_sparse_res): the columns are the handle's, y and foldid the caller's device vectors, cres the caller's context
     const char *who = mode == XVS_FULL ? "xval_sparse" : (mode == XVS_MOMENTS ? "selftest_xval_sparse_fold_moments" : "selftest_xval_sparse_cv_error");
     int rc = 0;
     if (mode == XVS_FULL) {
@@ -3090,16 +3092,17 @@ static int xval_sparse_impl(int mode, int64_t n, int32_t p, const int64_t *colpt
         npen = o->npen; nl = nl_of(o);
     } else if (p < 1 || npen < 1 || nl < 1) { set_error("%s: bad p, npen or nl", who); return OEMGPU_ERR_ARG; }
     if (n < 1) { set_error("xval_sparse: bad n"); return OEMGPU_ERR_ARG; }
-    const int64_t maxcol = csc_check(who, n, p, colptr, rowidx, values, nullptr);     // first, as in oemgpu_fit_sparse (it reads rows against n: n >= 1 comes before it)
+    const int64_t maxcol = xres ? xres->maxcol : csc_check(who, n, p, colptr, rowidx, values, nullptr);     // first, as in oemgpu_fit_sparse (it reads rows against n: n >= 1 comes before it)
     if (maxcol < 0) return (int)maxcol;
     if (K < 2 || K > 512) { set_error("xval_dense: nfolds must be in 2..512"); return OEMGPU_ERR_ARG; }
     if (type_measure != 0 && type_measure != 1) { set_error("xval_dense: type_measure must be 0 (mse) or 1 (mae)"); return OEMGPU_ERR_ARG; }
     if (n + (int64_t)CSC_CHUNK * K >= (int64_t)1 << 31) { set_error("xval_sparse: n too large for 32-bit row positions"); return OEMGPU_ERR_UNSUPPORTED; }
     if (mode == XVS_FULL && n <= p) { set_error("dimension of x larger than number of observations"); return OEMGPU_ERR_UNSUPPORTED; }   // ref src/oem_xval_dense.h:690-731
-    const int64_t nnz = colptr[p];
-    oemgpu_ctx *c = ctx_acquire(o ? o->device : -1);
+    const int64_t nnz = xres ? xres->nnz : colptr[p];
+    if (xres && set_device(cres)) return OEMGPU_ERR_HIP;
+    oemgpu_ctx *c = xres ? cres : ctx_acquire(o ? o->device : -1);
     if (!c) return OEMGPU_ERR_NO_DEVICE;
-    struct Release { oemgpu_ctx *c; ~Release() { (void)hipStreamSynchronize(c->stream); ctx_release(c); } } release{c};
+    struct Release { oemgpu_ctx *c; bool own; ~Release() { (void)hipStreamSynchronize(c->stream); if (own) ctx_release(c); } } release{c, xres == nullptr};
     hipStream_t s = c->stream;
     if (!c->xvs_ev_made) {
         for (int i = 0; i <= OEMGPU_XVS_NPHASES; ++i) OEM_HIP(hipEventCreate(&c->xvs_ev[i]));
@@ -3109,26 +3112,31 @@ static int xval_sparse_impl(int mode, int64_t n, int32_t p, const int64_t *colpt
     auto mark = [&]() { if (nmark <= OEMGPU_XVS_NPHASES) (void)hipEventRecord(c->xvs_ev[nmark++], s); };
     for (double &v : g_xvs_ms) v = 0.0;
 
-    const XvalSparsePlan SP = xval_sparse_plan(n, p, nnz, K, npen, nl, c->num_cu);
+    const XvalSparsePlan SP = xval_sparse_plan(n, p, nnz, K, npen, nl, c->num_cu, xres != nullptr);     // (resident: no slots for the uploaded copies)
     const XvalLay L = xval_layout(c->num_cu, n, p, K, npen, nl, false, &SP);
     ctx_void_cv(c);
     if (ctx_aux(c, L.total + SP.bytes)) return OEMGPU_ERR_HIP;
     char *ax = c->aux, *sx = c->aux + L.total;
-    int64_t *cd = (int64_t *)(sx + SP.a_col), *rowptr = (int64_t *)(sx + SP.a_rowptr);
-    int32_t *rd = (int32_t *)(sx + SP.a_row), *fd = (int32_t *)(sx + SP.a_fid), *ccol = (int32_t *)(sx + SP.a_ccol);
-    double *vd = (double *)(sx + SP.a_val), *yd = (double *)(sx + SP.a_y), *cval = (double *)(sx + SP.a_cval);
+    const int64_t *cd = xres ? xres->colptr : (int64_t *)(sx + SP.a_col);
+    int64_t *rowptr = (int64_t *)(sx + SP.a_rowptr);
+    const int32_t *rd = xres ? xres->rowidx : (int32_t *)(sx + SP.a_row), *fd = xres ? foldid : (int32_t *)(sx + SP.a_fid);
+    int32_t *ccol = (int32_t *)(sx + SP.a_ccol);
+    const double *vd = xres ? xres->val : (double *)(sx + SP.a_val), *yd = xres ? y : (double *)(sx + SP.a_y);
+    double *cval = (double *)(sx + SP.a_cval);
     int64_t *fold_n = (int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
     double *yp = (double *)(ax + L.a_yp), *mfold = (double *)(ax + L.a_mf), *bdev = (double *)(ax + L.a_b);
 
     // ---- phase 0: the compressed columns, y and foldid up, once
     mark();
-    OEM_HIP(hipMemcpyAsync(cd, colptr, sizeof(int64_t) * (size_t)(p + 1), hipMemcpyHostToDevice, s));
-    if (nnz > 0) {
-        OEM_HIP(hipMemcpyAsync(rd, rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, s));
-        OEM_HIP(hipMemcpyAsync(vd, values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, s));
+    if (!xres) {
+        OEM_HIP(hipMemcpyAsync((void *)cd, colptr, sizeof(int64_t) * (size_t)(p + 1), hipMemcpyHostToDevice, s));
+        if (nnz > 0) {
+            OEM_HIP(hipMemcpyAsync((void *)rd, rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, s));
+            OEM_HIP(hipMemcpyAsync((void *)vd, values, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, s));
+        }
+        OEM_HIP(hipMemcpyAsync((void *)yd, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+        OEM_HIP(hipMemcpyAsync((void *)fd, foldid, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
     }
-    OEM_HIP(hipMemcpyAsync(yd, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-    OEM_HIP(hipMemcpyAsync(fd, foldid, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
     // ---- phases 1 - 3: fold order, the K fold moment buffers, the fold-ordered compressed rows
     mark();
     XvsHost H;
@@ -3718,6 +3726,72 @@ int oemgpu_fit_sparse(int64_t n, int32_t p, const int64_t *colptr, const int32_t
     }
     (void)hipStreamSynchronize(c->stream);
     ctx_release(c);
+    return rc;
+}
+
+int oemgpu_xval_sparse_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
+                           int32_t standardize, int32_t intercept, int32_t type_measure, const oemgpu_opts *o, double *beta,
+                           double *lambda_out, int32_t *niter, double *loss, double *d, double *cvm, double *cvsd)
+{
+    if (!c || !x || !y_dev || !foldid_dev || !o || !beta || !lambda_out || !niter || !loss || !d || !cvm || !cvsd) {
+        set_error("xval_sparse: NULL argument"); return OEMGPU_ERR_ARG;
+    }
+    if (o->ngpus > 1) { set_error("xval_sparse: the rows of a sparse x are not split over devices"); return OEMGPU_ERR_UNSUPPORTED; }
+    if (c->device != x->device) { set_error("xval_sparse: the context and the sparse x are on different devices"); return OEMGPU_ERR_ARG; }
+    return xval_sparse_impl(XVS_FULL, x->n, x->p, nullptr, nullptr, nullptr, y_dev, foldid_dev, nfolds, standardize, intercept, type_measure, o,
+                            0, 0, nullptr, beta, lambda_out, niter, loss, d, cvm, cvsd, nullptr, nullptr, c, x);
+}
+
+// oemgpu_fit_sparse on a resident x: the same route, kernels and solve, nothing uploaded; intval from the moment buffer's diagonal
+int oemgpu_fit_sparse_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, const double *y_dev, int32_t standardize, int32_t intercept,
+                          const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+{
+    if (!c || !x || !y_dev || !o || !beta || !lambda_out || !niter || !loss || !d) { set_error("fit_sparse: NULL argument"); return OEMGPU_ERR_ARG; }
+    const int64_t n = x->n, nnz = x->nnz;
+    const int p = x->p, q = p + (intercept ? 1 : 0);
+    int rc = check_opts(o, p, q);
+    if (rc) return rc;
+    if (n <= p && intercept) {
+        set_error("a sparse x with p >= n and an intercept: the reference multiplies the n x p map by a vector of p + 1 entries (src/oem_sparse.h:638-647) -- "
+                  "nothing well-formed to reproduce; intercept = FALSE is served");
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    if (c->device != x->device) { set_error("fit_sparse: the context and the sparse x are on different devices"); return OEMGPU_ERR_ARG; }
+    if (n <= p) return oemgpu_fit_sparse_wide_res(c, x, y_dev, standardize, o, beta, lambda_out, niter, loss, d);
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    hipStream_t s = c->stream;
+    const SparseRoute R = sparse_route(n, p, nnz);
+    if (ctx_grow(c, &c->xres, &c->xres_bytes, R.csc ? csc_moments_work_bytes(n, p) : sizeof(double) * (size_t)R.ld * p)) return OEMGPU_ERR_HIP;
+    const GramPlan plmax = gram_plan_bound(R.rows, p, c->num_cu);
+    Bump B;
+    const size_t mlen = (size_t)oemgpu_moments_len(p);
+    const size_t a_mom = B.take(mlen * 8), a_tmp = B.take(mlen * 8), a_t = B.take(plmax.tpart_doubles * 8), a_v = B.take(plmax.vpart_doubles * 8),
+                 a_diag = B.take(sizeof(double) * (size_t)p);
+    const SparseSolveWs W = sparse_solve_ws(B, p, q, o);
+    if (ctx_reserve(c, W.need)) return OEMGPU_ERR_HIP;
+    double *mom = (double *)(c->ws + a_mom), *diag = (double *)(c->ws + a_diag);
+    rc = R.csc ? launch_csc_moments(s, x->colptr, x->rowidx, x->val, y_dev, n, p, c->xres, mom)
+               : csc_tile_moments(c, R, x->colptr, x->rowidx, x->val, nullptr, y_dev, n, p, x->maxcol, (double *)c->xres, (double *)(c->ws + a_t),
+                                  (double *)(c->ws + a_v), (double *)(c->ws + a_tmp), mom);
+    double intval = 1.0;
+    if (!rc && intercept) {                                  // sqrt(mean(diag(XX)) / n), the expression of oemgpu_fit_sparse
+        std::vector<double> hdiag((size_t)p);
+        hipLaunchKernelGGL(moment_diag_kernel, dim3((p + 255) / 256), dim3(256), 0, s, mom, p, diag);
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipMemcpyAsync(hdiag.data(), diag, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, s));
+        OEM_HIP(hipStreamSynchronize(s));
+        double xxdiag = 0.0;
+        for (int j = 0; j < p; ++j) {
+            const double ss = hdiag[j];
+            double cs = ss / ((double)n - 1.0);
+            if (cs == 0.0) cs = 1.0;
+            xxdiag += standardize ? ss / cs : ss;
+        }
+        xxdiag /= (double)p;
+        intval = std::sqrt(xxdiag / (double)n);
+    }
+    if (!rc) rc = sparse_solve(c, W, mom, p, q, standardize, intercept, o, intval, beta, lambda_out, niter, loss, d);
+    (void)hipStreamSynchronize(s);
     return rc;
 }
 
