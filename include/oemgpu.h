@@ -788,6 +788,30 @@ int oemgpu_selftest_sparse_wide_plan(int64_t n, int32_t p, int64_t nnz, int64_t 
 int oemgpu_fit_sparse_wide_fold_res(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, const double *y_dev, const int32_t *foldid_dev, int32_t nfolds,
                                     int32_t leave_out, int32_t standardize, const oemgpu_opts *opts, double *beta, double *lambda_out,
                                     int32_t *niter, double *loss, double *d, int64_t *kept);
+/* Test infrastructure: ONE pass of the engine of oemgpu_fit_sparse_wide_fold_res, after that entry's own setup (the same internal
+ * function: the engine's workspace, the lists of the long rows and columns, the check of the plan against them, the mask only when
+ * leave_out > 0 and the fold has rows, the kept rows n_k for n), with the lanes per row and per column forced: row_lanes / col_lanes
+ * are 0 -- what oemgpu_selftest_sparse_wide_plan gives for the context's CUs, as in the fit -- or one of 1, 2, 4, 8, 16, 32, 64, and
+ * the long form then takes the lines of more than 32 x THAT many entries.  Every pointer ending in _dev is on the handle's device.
+ *   OEMGPU_SPW_PASS_ROWS   out_dev[n] <- scale * sum over row i of x_ij in_dev[j] (in_dev: p doubles); masked, a left-out row: +0.0
+ *   OEMGPU_SPW_PASS_COLS   out_dev[p] <- scale * sum over column j of x_ij in_dev[i] (in_dev: n doubles); never masked
+ *   OEMGPU_SPW_PASS_STATS  in_dev = y: out_dev[p] <- x_j'y / n_k, out2_dev[p] <- that times the column's scale, stats_dev[4 + 2 p + 2]
+ *                          <- (0, 1, sum y^2, n_k), p zeros, the p column scales 1 / sqrt(sum x_j^2 / (n_k - 1)) (1 for a zero column
+ *                          and without standardize), the two shift flags 0 -- all sums over the kept rows
+ *   OEMGPU_SPW_PASS_LOSS   in_dev = y: out_dev[ncoef] <- sum over the kept rows of (y - X b_k)^2 for the ncoef coefficient tables
+ *                          coef_dev[ncoef][p + 1] (slot 0 of a table, the intercept, is not read)
+ * scale is read by the first two passes, standardize by the third, coef_dev and ncoef by the fourth; out2_dev and stats_dev may be NULL
+ * except in the third.  info: [0] the lanes per row in force, [1] per column, [2] the number of long rows, [3] of long columns,
+ * [4] the longest row, [5] the longest column (stored entries), [6] n_k, [7] 1 if the pass was masked.  long_rows (n int32) /
+ * long_cols (p int32): NULL, or host arrays whose first info[2] / info[3] slots <- the long lines, in no particular order.
+ * The call returns after the pass has finished.  Checked before any device work: OEMGPU_ERR_ARG for a NULL argument, a pass or lanes
+ * outside the values above, and what oemgpu_fit_sparse_wide_fold_res refuses for nfolds, leave_out, a NULL foldid_dev, a handle on
+ * another device and n < 2; OEMGPU_ERR_UNSUPPORTED for n > p.  From the device: a fold id outside 1..nfolds and n_k < 2. */
+enum { OEMGPU_SPW_PASS_ROWS = 0, OEMGPU_SPW_PASS_COLS = 1, OEMGPU_SPW_PASS_STATS = 2, OEMGPU_SPW_PASS_LOSS = 3 };
+int oemgpu_selftest_sparse_wide_pass(oemgpu_ctx *ctx, const oemgpu_sparse_x *x, int32_t pass, int32_t row_lanes, int32_t col_lanes,
+                                     const int32_t *foldid_dev, int32_t nfolds, int32_t leave_out, int32_t standardize, double scale,
+                                     const double *in_dev, const double *coef_dev, int32_t ncoef, double *out_dev, double *out2_dev,
+                                     double *stats_dev, int64_t *info /* 8 */, int32_t *long_rows, int32_t *long_cols);
 /* cv.oem's scoring of the held-out rows on the resident sparse x (ref R/cv_oem.R:376-391, 392-423; R/utils.R:128-144), the companion
  * of the fold fits above: the outputs of oemgpu_cv_sparse_score_res -- triples[nfolds][npen][nl][3] <- (count, mean, M2) of fold k's
  * errors (type_measure 0 mse, 1 mae) over its own rows under ITS coefficients coef[k] (host, [nfolds][npen][nl][p + 1], slot 0 the

@@ -134,6 +134,9 @@ _SIGS = {
     "oemgpu_selftest_sparse_wide_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_fit_sparse_wide_fold_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                                   C.POINTER(OemgpuOpts)] + _OUT + [C.POINTER(C.c_int64)]),     # R/cv_oem.R:155-175 with n <= p
+    "oemgpu_selftest_sparse_wide_pass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
     "oemgpu_cv_sparse_wide_score_res": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, _ip,
                                                   C.c_int32, _dp, C.c_void_p]),                                  # R/cv_oem.R:376-391
     "oemgpu_selftest_cv_sparse_wide_score_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),

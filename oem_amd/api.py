@@ -1318,6 +1318,45 @@ def sparse_wide_fold_fit(x, y, foldid, nfolds, leave_out, penalty=None, **kw):
     return _decorate(a, penalty, varnames, True, int(kept.value), p)
 
 
+SPW_PASSES = ("rows", "cols", "stats", "loss")
+
+
+def sparse_wide_pass(x, kind, vec, row_lanes=0, col_lanes=0, foldid=None, nfolds=3, leave_out=0, standardize=False, scale=1.0, coef=None,
+                     ctx=None):
+    """oemgpu_selftest_sparse_wide_pass (test infrastructure): one pass of the sparse wide engine on a SparseX with n <= p after the
+    fit's own setup, with the lanes per row / per column forced (0: the plan's).  kind: "rows" (vec: p doubles), "cols" (vec: n), "stats"
+    or "loss" (vec = y: n; loss: coef = the tables, ncoef x (p + 1)); vec, foldid (int32) and coef: device tensors.  Every output is
+    filled with NaN before the call.  Returns a dict: out (rows: n, cols: p, loss: ncoef; stats: xy), for stats also xy_std and stats
+    (4 + 2 p + 2), info (row_lanes, col_lanes, long_rows, long_cols, longest_row, longest_col, kept, masked) and the two lists of long
+    lines, sorted."""
+    import torch
+    n, p = x.shape
+    pass_ = SPW_PASSES.index(kind)
+    ncoef = 0 if coef is None else int(coef.shape[0])
+    if coef is not None and (coef.dim() != 2 or coef.shape[1] != p + 1 or not coef.is_contiguous()):
+        raise ValueError("coef must be a contiguous ncoef x (p + 1) tensor")
+    if vec is not None and vec.numel() != (p if kind == "rows" else n):
+        raise ValueError("vec has the wrong length for this pass")
+    nan = lambda m: torch.full((m,), float("nan"), dtype=torch.float64, device=x.device)
+    out = nan({"rows": n, "cols": p, "stats": p, "loss": max(ncoef, 1)}[kind])
+    out2, st = (nan(p), nan(4 + 2 * p + 2)) if kind == "stats" else (None, None)
+    info = (C.c_int64 * 8)()
+    lrow, lcol = np.full(n, -1, np.int32), np.full(p, -1, np.int32)
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_selftest_sparse_wide_pass(ctx if ctx is not None else context(x.device.index), x.handle, pass_, int(row_lanes), int(col_lanes),
+                                                     None if foldid is None else foldid.data_ptr(), int(nfolds), int(leave_out),
+                                                     int(bool(standardize)), float(scale), None if vec is None else vec.data_ptr(),
+                                                     None if coef is None else coef.data_ptr(), ncoef, out.data_ptr(),
+                                                     None if out2 is None else out2.data_ptr(), None if st is None else st.data_ptr(), info,
+                                                     lrow.ctypes.data, lcol.ctypes.data))
+    keys = ("row_lanes", "col_lanes", "long_rows", "long_cols", "longest_row", "longest_col", "kept", "masked")
+    r = {"out": out.cpu().numpy(), "info": dict(zip(keys, (int(v) for v in info)))}
+    if kind == "stats":
+        r["xy_std"], r["stats"] = out2.cpu().numpy(), st.cpu().numpy()
+    r["long_row_list"], r["long_col_list"] = np.sort(lrow[:int(info[2])]), np.sort(lcol[:int(info[3])])
+    return r
+
+
 _CVS_PLAN_KEYS = ("csc", "nwg", "waves", "lblk", "part_bytes", "bytes", "xval_bytes", "fold_bytes", "own_bytes", "rows_max", "nl16", "align")
 
 

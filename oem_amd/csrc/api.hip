@@ -3520,6 +3520,76 @@ int oemgpu_selftest_cv_sparse_wide_score_plan(int64_t n, int32_t p, int32_t nfol
     return 0;
 }
 
+// What the sparse wide engine's entries check after their NULL arguments, before any device work (the sentences of the fold fit)
+static int spw_entry_checks(const char *who, const oemgpu_ctx *c, const oemgpu_sparse_x *x, const int32_t *foldid_dev, int32_t nfolds, int32_t leave_out)
+{
+    if (nfolds < 3 || nfolds > 512) { set_error("%s: nfolds must be in 3..512", who); return OEMGPU_ERR_ARG; }
+    if (leave_out < 0 || leave_out > nfolds) { set_error("%s: leave_out must be in [0, nfolds]", who); return OEMGPU_ERR_ARG; }
+    if (leave_out > 0 && !foldid_dev) { set_error("%s: NULL foldid with leave_out > 0", who); return OEMGPU_ERR_ARG; }
+    if (c->device != x->device) { set_error("%s: the context and the sparse x are on different devices", who); return OEMGPU_ERR_ARG; }
+    if (x->n < 2) { set_error("%s: at least two rows", who); return OEMGPU_ERR_ARG; }
+    if (x->n > x->p) {
+        set_error("%s: n > p (%lld x %d) is the Gram form's: oemgpu_fit_sparse serves it", who, (long long)x->n, (int)x->p);
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    return 0;
+}
+
+// The kept rows of a fold (the ids' range whatever is left out); nk = n without fold ids
+static int spw_kept_rows(oemgpu_ctx *c, const char *who, const int32_t *foldid_dev, int n, int32_t nfolds, int32_t leave_out, int64_t *nk)
+{
+    *nk = n;
+    if (!foldid_dev) return 0;
+    std::vector<int64_t> none;
+    const int rc = logit_fold_scan(c, who, foldid_dev, n, nfolds, leave_out, 0, nk, &none);
+    if (rc) return rc;
+    if (*nk < 2) {
+        set_error("%s: fold %d keeps %lld of the %d rows: a fit needs at least two", who, (int)leave_out, (long long)*nk, n);
+        return OEMGPU_ERR_ARG;
+    }
+    return 0;
+}
+
+// The engine's setup before its first pass, once for the fit and for oemgpu_selftest_sparse_wide_pass: the mask (only when the fold has
+// rows), the lanes -- spw_plan's for the context's CUs, or row_lanes / col_lanes where not 0 --, the engine's workspace in c->aux, the
+// lists of the lines longer than 32 x the lanes in force, and the check of the plan's long forms against the lists.  longest: NULL, or
+// <- the longest row and column.
+static int spw_setup(oemgpu_ctx *c, const oemgpu_sparse_x *x, const int32_t *foldid_dev, int32_t leave_out, int64_t nk, int row_lanes,
+                     int col_lanes, SpwArgs &A, int64_t *longest)
+{
+    const int p = x->p, n = (int)x->n;                       // (n <= p: an int)
+    hipStream_t s = c->stream;
+    int rc;
+    if (leave_out > 0 && nk < n) { A.foldid = foldid_dev; A.leave_out = leave_out; }      // (a fold without rows: the fit of all rows, unmasked)
+    A.nk = (int)nk;
+    A.colptr = x->colptr; A.rowptr = x->rowptr; A.rowidx = x->rowidx; A.ccol = x->ccol; A.val = x->val; A.cval = x->cval;
+    A.n = n; A.p = p;
+    A.plan = spw_plan(n, p, x->nnz, 0, 0, c->num_cu, row_lanes, col_lanes);       // (the lanes; the long forms once the lines have been looked at)
+    A.long_row_list = A.long_col_list = nullptr; A.n_long_rows = A.n_long_cols = 0;
+    Bump X;
+    const size_t a_vec = X.take(sizeof(double) * (4 * (size_t)n + SPW_T_DOUBLES)), a_lr = X.take(sizeof(int32_t) * ((size_t)n + 1)),
+                 a_lc = X.take(sizeof(int32_t) * ((size_t)p + 1)), a_cnt = X.take(64);
+    if (X.off != A.plan.ws_bytes) { set_error("internal: the sparse wide plan and its workspace disagree"); return OEMGPU_ERR_INTERNAL; }
+    ctx_void_cv(c);
+    if (ctx_grow(c, &c->aux, &c->aux_bytes, X.off)) return OEMGPU_ERR_HIP;
+    A.vec = (double *)(c->aux + a_vec);
+    int32_t *lrow = (int32_t *)(c->aux + a_lr), *lcol = (int32_t *)(c->aux + a_lc);
+    int *cnt = (int *)(c->aux + a_cnt);
+    if (ctx_pinned(c, 16384)) return OEMGPU_ERR_HIP;
+    if ((rc = launch_spw_scan(s, A, lrow, lcol, cnt))) return rc;
+    OEM_HIP(hipMemcpyAsync(c->pinned, cnt, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipStreamSynchronize(s));
+    const int *h = (const int *)c->pinned;
+    const int nlr = h[0], nlc = h[2];
+    A.plan = spw_plan(n, p, x->nnz, h[1], h[3], c->num_cu, row_lanes, col_lanes);
+    if (nlr < 0 || nlr > n || nlc < 0 || nlc > p || (nlr > 0) != (A.plan.long_rows != 0) || (nlc > 0) != (A.plan.long_cols != 0)) {
+        set_error("internal: the sparse wide plan and the lists of long lines disagree"); return OEMGPU_ERR_INTERNAL;
+    }
+    A.long_row_list = lrow; A.long_col_list = lcol; A.n_long_rows = nlr; A.n_long_cols = nlc;
+    if (longest) { longest[0] = h[1]; longest[1] = h[3]; }
+    return 0;
+}
+
 // oem() on a resident sparse x with nobs <= nvars and no intercept: fit_big_wide_dev's iteration (the comment there) with both products
 // over the non-zeros of the handle (sparse_wide.hip; path_large.hip: run_path_sparse_wide).  Nothing of n p entries is allocated.
 // The ONE body is the fold entry's: leave_out = 0 (or a fold without rows) sets no mask and launches what this entry always launched.
@@ -3538,59 +3608,17 @@ int oemgpu_fit_sparse_wide_fold_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, con
 {
     static const char *who = "fit_sparse_wide";
     if (!c || !x || !y_dev || !o || !beta || !lambda_out || !niter || !loss || !d || !kept) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
-    if (nfolds < 3 || nfolds > 512) { set_error("%s: nfolds must be in 3..512", who); return OEMGPU_ERR_ARG; }
-    if (leave_out < 0 || leave_out > nfolds) { set_error("%s: leave_out must be in [0, nfolds]", who); return OEMGPU_ERR_ARG; }
-    if (leave_out > 0 && !foldid_dev) { set_error("%s: NULL foldid with leave_out > 0", who); return OEMGPU_ERR_ARG; }
-    if (c->device != x->device) { set_error("%s: the context and the sparse x are on different devices", who); return OEMGPU_ERR_ARG; }
-    if (x->n < 2) { set_error("%s: at least two rows", who); return OEMGPU_ERR_ARG; }
-    if (x->n > x->p) {
-        set_error("%s: n > p (%lld x %d) is the Gram form's: oemgpu_fit_sparse serves it", who, (long long)x->n, (int)x->p);
-        return OEMGPU_ERR_UNSUPPORTED;
-    }
-    const int p = x->p, n = (int)x->n;                       // (n <= p: an int)
-    int rc = check_opts(o, p, p);
+    int rc = spw_entry_checks(who, c, x, foldid_dev, nfolds, leave_out);
     if (rc) return rc;
+    const int p = x->p, n = (int)x->n;                       // (n <= p: an int)
+    if ((rc = check_opts(o, p, p))) return rc;
     if (set_device(c)) return OEMGPU_ERR_HIP;
     hipStream_t s = c->stream;
     int64_t nk = n;
-    if (foldid_dev) {                                        // the ids' range whatever is left out; the kept rows
-        std::vector<int64_t> none;
-        if ((rc = logit_fold_scan(c, who, foldid_dev, n, nfolds, leave_out, 0, &nk, &none))) return rc;
-        if (nk < 2) {
-            set_error("%s: fold %d keeps %lld of the %d rows: a fit needs at least two", who, (int)leave_out, (long long)nk, n);
-            return OEMGPU_ERR_ARG;
-        }
-    }
+    if ((rc = spw_kept_rows(c, who, foldid_dev, n, nfolds, leave_out, &nk))) return rc;
     *kept = nk;
     SpwArgs A;
-    if (leave_out > 0 && nk < n) { A.foldid = foldid_dev; A.leave_out = leave_out; }      // (a fold without rows: the fit of all rows, unmasked)
-    A.nk = (int)nk;
-    A.colptr = x->colptr; A.rowptr = x->rowptr; A.rowidx = x->rowidx; A.ccol = x->ccol; A.val = x->val; A.cval = x->cval;
-    A.n = n; A.p = p;
-    A.plan = spw_plan(n, p, x->nnz, 0, 0, c->num_cu);        // (the lanes; the long forms once the lines have been looked at)
-    A.long_row_list = A.long_col_list = nullptr; A.n_long_rows = A.n_long_cols = 0;
-    Bump X;
-    const size_t a_vec = X.take(sizeof(double) * (4 * (size_t)n + SPW_T_DOUBLES)), a_lr = X.take(sizeof(int32_t) * ((size_t)n + 1)),
-                 a_lc = X.take(sizeof(int32_t) * ((size_t)p + 1)), a_cnt = X.take(64);
-    if (X.off != A.plan.ws_bytes) { set_error("internal: the sparse wide plan and its workspace disagree"); return OEMGPU_ERR_INTERNAL; }
-    ctx_void_cv(c);
-    if (ctx_grow(c, &c->aux, &c->aux_bytes, X.off)) return OEMGPU_ERR_HIP;
-    A.vec = (double *)(c->aux + a_vec);
-    int32_t *lrow = (int32_t *)(c->aux + a_lr), *lcol = (int32_t *)(c->aux + a_lc);
-    int *cnt = (int *)(c->aux + a_cnt);
-    if (ctx_pinned(c, 16384)) return OEMGPU_ERR_HIP;
-    if ((rc = launch_spw_scan(s, A, lrow, lcol, cnt))) return rc;
-    OEM_HIP(hipMemcpyAsync(c->pinned, cnt, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-    OEM_HIP(hipStreamSynchronize(s));
-    {
-        const int *h = (const int *)c->pinned;
-        const int nlr = h[0], nlc = h[2];
-        A.plan = spw_plan(n, p, x->nnz, h[1], h[3], c->num_cu);
-        if (nlr < 0 || nlr > n || nlc < 0 || nlc > p || (nlr > 0) != (A.plan.long_rows != 0) || (nlc > 0) != (A.plan.long_cols != 0)) {
-            set_error("internal: the sparse wide plan and the lists of long lines disagree"); return OEMGPU_ERR_INTERNAL;
-        }
-        A.long_row_list = lrow; A.long_col_list = lcol; A.n_long_rows = nlr; A.n_long_cols = nlc;
-    }
+    if ((rc = spw_setup(c, x, foldid_dev, leave_out, nk, 0, 0, A, nullptr))) return rc;
     Bump B;
     const size_t a_xs2 = B.take((size_t)p * 8), a_xy = B.take((size_t)p * 8), a_st = B.take((size_t)stats_len(p) * 8);       // stats last (run_paths)
     if (ctx_reserve(c, B.off + paths_ws_bytes(p, p, o) + 4096)) return OEMGPU_ERR_HIP;
@@ -3615,6 +3643,47 @@ int oemgpu_fit_sparse_wide_fold_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, con
     OEM_HIP(hipMemcpyAsync(loss, ld_, nfit * 8, hipMemcpyDeviceToHost, s));
     OEM_HIP(hipStreamSynchronize(s));
     for (size_t k = 0; k < nfit; ++k) if (niter[k] == 0) loss[k] = 1e99;
+    return 0;
+}
+
+// ONE pass of the engine above after the fit's own setup (spw_setup), with the lanes of either orientation forced where not 0: what
+// the tests hold every instantiation of sparse_wide.hip's kernels to (include/oemgpu.h)
+int oemgpu_selftest_sparse_wide_pass(oemgpu_ctx *c, const oemgpu_sparse_x *x, int32_t pass, int32_t row_lanes, int32_t col_lanes,
+                                     const int32_t *foldid_dev, int32_t nfolds, int32_t leave_out, int32_t standardize, double scale,
+                                     const double *in_dev, const double *coef_dev, int32_t ncoef, double *out_dev, double *out2_dev,
+                                     double *stats_dev, int64_t *info, int32_t *long_rows, int32_t *long_cols)
+{
+    static const char *who = "selftest_sparse_wide_pass";
+    if (!c || !x || !in_dev || !out_dev || !info) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    if (pass < OEMGPU_SPW_PASS_ROWS || pass > OEMGPU_SPW_PASS_LOSS) { set_error("%s: pass must be 0 (rows), 1 (columns), 2 (stats) or 3 (loss)", who); return OEMGPU_ERR_ARG; }
+    if (pass == OEMGPU_SPW_PASS_STATS && (!out2_dev || !stats_dev)) { set_error("%s: NULL argument (the stats pass writes out2_dev and stats_dev)", who); return OEMGPU_ERR_ARG; }
+    if (pass == OEMGPU_SPW_PASS_LOSS && (!coef_dev || ncoef < 1)) { set_error("%s: NULL argument or ncoef < 1 (the loss pass reads coef_dev)", who); return OEMGPU_ERR_ARG; }
+    for (const int32_t L : {row_lanes, col_lanes})
+        if (L != 0 && (L < 1 || L > 64 || (L & (L - 1)))) { set_error("%s: lanes must be 0 (the plan's) or one of 1, 2, 4, 8, 16, 32, 64", who); return OEMGPU_ERR_ARG; }
+    int rc = spw_entry_checks(who, c, x, foldid_dev, nfolds, leave_out);
+    if (rc) return rc;
+    const int p = x->p, n = (int)x->n;
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    hipStream_t s = c->stream;
+    int64_t nk = n, longest[2] = {0, 0};
+    if ((rc = spw_kept_rows(c, who, foldid_dev, n, nfolds, leave_out, &nk))) return rc;
+    SpwArgs A;
+    if ((rc = spw_setup(c, x, foldid_dev, leave_out, nk, row_lanes, col_lanes, A, longest))) return rc;
+    info[0] = A.plan.row_L; info[1] = A.plan.col_L; info[2] = A.n_long_rows; info[3] = A.n_long_cols; info[4] = longest[0]; info[5] = longest[1];
+    info[6] = nk; info[7] = A.foldid ? 1 : 0;
+    if (long_rows && A.n_long_rows > 0) OEM_HIP(hipMemcpyAsync(long_rows, A.long_row_list, sizeof(int32_t) * (size_t)A.n_long_rows, hipMemcpyDeviceToHost, s));
+    if (long_cols && A.n_long_cols > 0) OEM_HIP(hipMemcpyAsync(long_cols, A.long_col_list, sizeof(int32_t) * (size_t)A.n_long_cols, hipMemcpyDeviceToHost, s));
+    if (pass == OEMGPU_SPW_PASS_ROWS) rc = launch_spw_rows(s, A, in_dev, out_dev, scale, nullptr);
+    else if (pass == OEMGPU_SPW_PASS_COLS) rc = launch_spw_cols(s, A, in_dev, out_dev, scale, nullptr);
+    else if (pass == OEMGPU_SPW_PASS_STATS) rc = launch_spw_stats(s, A, in_dev, standardize, out_dev, stats_dev, out2_dev);
+    else {
+        const size_t nchunk = (size_t)((n + 2047) / 2048);
+        if (ctx_reserve(c, (size_t)ncoef * nchunk * 8 + 4096)) return OEMGPU_ERR_HIP;
+        rc = launch_spw_loss(s, A, in_dev, coef_dev, p + 1, ncoef, A.vec, (double *)c->ws, out_dev);
+    }
+    if (rc) return rc;
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipStreamSynchronize(s));
     return 0;
 }
 

@@ -434,7 +434,9 @@ struct SpwPlan {
     int row_wgs, col_wgs;    // workgroups of the short form of either pass
     size_t ws_bytes;         // the engine's own vectors, the Lanczos table and the two lists of long lines
 };
-SpwPlan spw_plan(int64_t n, int p, int64_t nnz, int64_t longest_row, int64_t longest_col, int num_cu);
+// force_row_L / force_col_L: 0, or the lanes to use instead of the planned ones (oemgpu_selftest_sparse_wide_pass; the fit passes 0, 0);
+// the long flags and the workgroups follow the lanes in force
+SpwPlan spw_plan(int64_t n, int p, int64_t nnz, int64_t longest_row, int64_t longest_col, int num_cu, int force_row_L = 0, int force_col_L = 0);
 struct SpwArgs {
     const int64_t *colptr, *rowptr;
     const int32_t *rowidx, *ccol;

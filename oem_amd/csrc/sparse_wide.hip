@@ -237,12 +237,12 @@ int spw_launch(hipStream_t s, const int64_t *ptr, const int32_t *idx, const doub
 
 }  // namespace
 
-SpwPlan spw_plan(int64_t n, int p, int64_t nnz, int64_t longest_row, int64_t longest_col, int num_cu)
+SpwPlan spw_plan(int64_t n, int p, int64_t nnz, int64_t longest_row, int64_t longest_col, int num_cu, int force_row_L, int force_col_L)
 {
     SpwPlan P;
     P.route = sparse_wide_route(n, p, nnz) ? 1 : 0;
-    P.row_L = spw_lanes(n, nnz, num_cu);
-    P.col_L = spw_lanes(p, nnz, num_cu);
+    P.row_L = force_row_L ? force_row_L : spw_lanes(n, nnz, num_cu);
+    P.col_L = force_col_L ? force_col_L : spw_lanes(p, nnz, num_cu);
     P.long_rows = longest_row > (int64_t)SPW_LONG_PER_LANE * P.row_L ? 1 : 0;
     P.long_cols = longest_col > (int64_t)SPW_LONG_PER_LANE * P.col_L ? 1 : 0;
     P.row_wgs = (int)((n * P.row_L + 255) / 256);

@@ -1,7 +1,10 @@
 """oem() on a sparse x with p >= n from its non-zeros (oem_amd/csrc/sparse_wide.hip) on the GPU: parity with the oracle on the route
 the library chooses, the structures a compressed matrix can have with the route forced, the dense-copy route it replaces, bit
 identity, a shape past the dense wide engine's row limit, and a seeded sweep (OEM_FUZZ_SCALE scales it, as in test_gpu_fuzz).
-tests/test_sparse_wide_cpu.py shows on the CPU that the parity inputs stay inside the agreement rule on the reference side alone."""
+tests/test_sparse_wide_cpu.py shows on the CPU that the parity inputs stay inside the agreement rule on the reference side alone.
+The lanes per row and per column of these fits follow the shape and the device's CU count (on 256 CUs: rows at 64 or 4 lanes, columns
+at 4 .. 64; DESIGN.md section 3.6a has the table); tests/test_gpu_sparse_wide_pass.py holds the single passes at all seven lane counts
+to exact sums."""
 import ctypes as C
 import os
 import warnings
@@ -225,7 +228,9 @@ def test_past_the_dense_wide_engines_row_limit(oa, monkeypatch):
 @pytest.mark.parametrize("seed", range(12 * SCALE))
 def test_seeded_sweep(oa, seed, monkeypatch):
     """small n and p around the plan's switches: 63 / 64 / 65 rows (a wave of lanes), rows on either side of 32 x 64 = 2048 stored
-    entries (the long-row form), n = p, very sparse and dense-ish, either value of standardize"""
+    entries (the switch to the long-row form AT 64 LANES PER ROW, which is what these few rows get on a device of 256 CUs; the switch
+    at the other lane counts, 32 L against 32 L + 1 entries, is tests/test_gpu_sparse_wide_pass.py's), n = p, very sparse and dense-ish,
+    either value of standardize"""
     monkeypatch.setenv("OEM_SPARSE_GRAM", "wide")
     rng = np.random.default_rng(1000 + seed)
     n = int(rng.choice([2, 3, 17, 63, 64, 65, 70]))
