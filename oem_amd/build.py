@@ -14,7 +14,7 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 OUT = HERE / "liboemgpu.so"
-SOURCES = ["api.hip", "hoststream.hip", "gram.hip", "gram_sb.hip", "gram_wd.hip", "gram_rm.hip", "path_small.hip", "path_coop.hip", "path_symcoop.hip", "path_wcoop.hip", "path_wres.hip", "path_large.hip", "xval.hip", "xval_sparse.hip", "sparse.hip", "sparse_build.hip", "sparse_wide.hip", "wide.hip", "weighted.hip", "logistic.hip", "logistic_rm.hip", "logistic_sparse.hip", "logistic_cv.hip", "logistic_auc.hip", "predict.hip"]
+SOURCES = ["api.hip", "paths.hip", "hoststream.hip", "gram.hip", "gram_sb.hip", "gram_wd.hip", "gram_rm.hip", "path_small.hip", "path_coop.hip", "path_symcoop.hip", "path_wcoop.hip", "path_wres.hip", "path_large.hip", "xval.hip", "xval_sparse.hip", "sparse.hip", "sparse_build.hip", "sparse_wide.hip", "wide.hip", "weighted.hip", "logistic.hip", "logistic_rm.hip", "logistic_sparse.hip", "logistic_cv.hip", "logistic_auc.hip", "predict.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 
 
@@ -218,28 +218,22 @@ def build(force=False, verbose=False):
                     if f != isa_path(s):
                         f.unlink()
 
-        class _Listing:                                  # (the shape the audits below were written against)
-            def __init__(self, path):
-                self.stdout = Path(path).read_text()
-
-            def result(self):
-                return self
-        listing = {src: _Listing(isa_path(src)) for src in AUDITED}
+        listing = {src: isa_path(src).read_text() for src in AUDITED}
         for src in ("gram.hip", "gram_sb.hip", "gram_wd.hip"):
-            problems = audit_gram_isa(listing[src].result().stdout)
+            problems = audit_gram_isa(listing[src])
             if problems:
                 raise RuntimeError(src + " ISA audit failed:\n  " + "\n  ".join(problems[:20]))
         for src in ("path_small.hip", "path_coop.hip", "path_wcoop.hip", "path_wres.hip"):
-            problems = audit_dpp_hazards(listing[src].result().stdout)
+            problems = audit_dpp_hazards(listing[src])
             if problems:
                 raise RuntimeError(src + " ISA audit failed:\n  " + "\n  ".join(problems[:20]))
-        problems = audit_wres_isa(listing["path_wres.hip"].result().stdout)
+        problems = audit_wres_isa(listing["path_wres.hip"])
         if problems:
             raise RuntimeError("path_wres.hip (path_wres_kernel) ISA audit failed:\n  " + "\n  ".join(problems[:20]))
-        problems = audit_symcoop_isa(listing["path_symcoop.hip"].result().stdout)
+        problems = audit_symcoop_isa(listing["path_symcoop.hip"])
         if problems:
             raise RuntimeError("path_symcoop.hip ISA audit failed:\n  " + "\n  ".join(problems[:20]))
-        problems = audit_round_spills(listing["path_small.hip"].result().stdout)
+        problems = audit_round_spills(listing["path_small.hip"])
         if problems:
             raise RuntimeError("path_small.hip round-spill audit failed:\n  " + "\n  ".join(problems[:20]))
     subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(OUT), *objs], check=True)

@@ -1,24 +1,20 @@
-// api.hip -- C ABI of liboemgpu: contexts, workspace, argument checks, and the host-side driver that the
-// reference keeps in src/oem_dense.cpp:30-309, src/oem_xtx.cpp:29-219 and src/oem_big.cpp:30-258
-// (lambda bookkeeping, result packing, DataStd::recover).  All arithmetic of the hot path runs in the HIP
+// api.hip -- C ABI of liboemgpu: contexts, workspace, argument checks, and the entry points of the host-side driver that the
+// reference keeps in src/oem_dense.cpp:30-309, src/oem_xtx.cpp:29-219 and src/oem_big.cpp:30-258; what they all end in
+// (engine choice, lambda bookkeeping, result packing, DataStd::recover) is paths.hip.  All arithmetic of the hot path runs in the HIP
 // kernels of gram.hip / path_small.hip / path_large.hip; there is no CPU fallback.
-#include "ctx.hpp"
+#include "paths.hpp"
 #include "dense_src.hpp"
 #include "logistic.hpp"     // oemgpu_sparse_x
 
 #include <atomic>
-#include <unistd.h>
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <condition_variable>
 #include <cstring>
 #include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 namespace oemgpu {
@@ -65,71 +61,6 @@ void set_error(const char *fmt, ...)
     va_end(ap);
 }
 
-// The cooperating-workgroup engine (path_coop.hip) spins on its partners, so every workgroup of every such kernel in flight must
-// be resident at once: concurrent callers (xval.oem's fold threads, user threads) queue here for CU slots.
-// The count is per DEVICE: launches on different GPUs share no CUs and must not queue behind each other (the penalty split of
-// solve_summed and xval.oem over devices run one such kernel per device side by side -- ADVICE r2).
-static const int COOP_MAX_DEV = 64;
-static std::mutex g_coop_mu;
-static std::condition_variable g_coop_cv;
-static int g_coop_in_flight[COOP_MAX_DEV] = {0};
-static int g_xcd_load[COOP_MAX_DEV][8] = {{0}};                    // CUs of every XCD booked by persistent launches in flight (per device, under g_coop_mu)
-static std::atomic<unsigned> g_xcd_next{(unsigned)getpid()};      // (processes that share a GPU start at different XCDs more often than not)
-// CU slots of the persistent engines: all workgroups of all such kernels in flight must be resident at once, so concurrent callers queue.
-// Booked per device AND per XCD: a device-scope launch of `want` workgroups is dealt round the XCDs by the dispatcher
-// (ceil(want / 8) CUs of each); a one-XCD launch (path_coop.hip, q <= 512) puts the W workgroups of instance y on XCD (base + y) mod 8
-// and gets the base for which the fullest XCD it touches stays emptiest -- and waits while no base leaves every XCD within its CUs.
-struct CoopSlots {
-    int n = 0, dev = 0;
-    int add[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    void take(int device, int want, int capacity)
-    {
-        dev = (device >= 0 && device < COOP_MAX_DEV) ? device : COOP_MAX_DEV - 1;
-        std::unique_lock<std::mutex> lk(g_coop_mu);
-        g_coop_cv.wait(lk, [&] { return g_coop_in_flight[dev] == 0 || g_coop_in_flight[dev] + want <= capacity; });
-        g_coop_in_flight[dev] += want; n += want;
-        for (int x = 0; x < 8; ++x) { const int a = (want + 7) / 8; add[x] += a; g_xcd_load[dev][x] += a; }
-    }
-    // `ninst` instances of W workgroups, each on ONE XCD of a device with num_cu CUs; returns the XCD of instance 0
-    int take_local(int device, int W, int ninst, int num_cu, int capacity)
-    {
-        dev = (device >= 0 && device < COOP_MAX_DEV) ? device : COOP_MAX_DEV - 1;
-        const int per = num_cu / 8, want = W * ninst, start = (int)(g_xcd_next.fetch_add(1u, std::memory_order_relaxed) & 7u);
-        int best = -1;
-        auto fits = [&](bool must) {
-            best = -1;
-            int best_peak = 0;
-            for (int k = 0; k < 8; ++k) {
-                const int base = (start + k) & 7;
-                int peak = 0;
-                for (int x = 0; x < 8; ++x) {
-                    const int cnt = ninst / 8 + (((x - base) & 7) < ninst % 8 ? 1 : 0);       // instances y with (base + y) mod 8 == x
-                    if (cnt) { const int l = g_xcd_load[dev][x] + cnt * W; if (l > peak) peak = l; }
-                }
-                if (best < 0 || peak < best_peak) { best = base; best_peak = peak; }
-            }
-            return must || best_peak <= per;
-        };
-        std::unique_lock<std::mutex> lk(g_coop_mu);
-        g_coop_cv.wait(lk, [&] { return g_coop_in_flight[dev] == 0 ? fits(true) : (g_coop_in_flight[dev] + want <= capacity && fits(false)); });
-        g_coop_in_flight[dev] += want; n += want;
-        for (int x = 0; x < 8; ++x) {
-            const int a = (ninst / 8 + (((x - best) & 7) < ninst % 8 ? 1 : 0)) * W;
-            add[x] += a; g_xcd_load[dev][x] += a;
-        }
-        return best;
-    }
-    void release()
-    {
-        if (n) {
-            { std::lock_guard<std::mutex> lk(g_coop_mu); g_coop_in_flight[dev] -= n; for (int x = 0; x < 8; ++x) { g_xcd_load[dev][x] -= add[x]; add[x] = 0; } }
-            n = 0;
-            g_coop_cv.notify_all();
-        }
-    }
-    ~CoopSlots() { release(); }
-};
-
 // (kernel, device) -> largest dynamic-LDS limit set so far
 int lds_limit_once(const void *fn, size_t bytes)
 {
@@ -148,14 +79,6 @@ int lds_limit_once(const void *fn, size_t bytes)
     seen.push_back(Key{fn, dev, bytes});
     return 0;
 }
-
-static thread_local int (*g_poll)(void *) = nullptr;
-static thread_local void *g_poll_arg = nullptr;
-bool caller_interrupted() { return g_poll && g_poll(g_poll_arg) != 0; }
-struct PollScope {          // the engines poll the caller's interrupt between batches of iterations, on the calling thread only
-    PollScope(const oemgpu_opts *o) { g_poll = o->interrupt; g_poll_arg = o->interrupt_arg; }
-    ~PollScope() { g_poll = nullptr; g_poll_arg = nullptr; }
-};
 
 }  // namespace oemgpu
 
@@ -205,7 +128,7 @@ oemgpu_ctx *ctx_acquire(int device)
 }
 
 // A cached context keeps its grow-only buffers between calls (no allocation in the steady state) -- up to a bound: the copy of the
-// host rows (c->xres: up to half of HBM for one large fit) xval.oem's fold-ordered copy (c->aux) and the packed triangle of a q > 4096 Gram (c->pack_buf) are freed on release when they
+// host rows (c->xres: up to half of HBM for one large fit) xval.oem's fold-ordered copy (c->aux) and the packed triangle of a q > 1024 Gram on the launch engines (c->pack_buf) are freed on release when they
 // exceed OEMGPU_CACHE_KEEP_BYTES (default: an eighth of the device's memory, 36 GB on MI355X), so that one large oem() / big.oem()
 // call does not starve torch or other users of the GPU for the rest of the session.  Streams, pinned staging lanes
 // and the workspace stay.  The caller has synchronised the context's stream.
@@ -224,20 +147,6 @@ void ctx_release(oemgpu_ctx *c)
     c->busy = false;
 }
 
-}  // namespace oemgpu
-
-namespace {
-
-int ctx_pinned_in(oemgpu_ctx *c, size_t bytes)
-{
-    if (bytes <= c->pinned_in_bytes) return 0;
-    if (c->pinned_in) { OEM_HIP(hipStreamSynchronize(c->stream)); OEM_HIP(hipHostFree(c->pinned_in)); c->pinned_in = nullptr; c->pinned_in_bytes = 0; }
-    bytes = (bytes + 4095) / 4096 * 4096;
-    OEM_HIP(hipHostMalloc((void **)&c->pinned_in, bytes, hipHostMallocDefault)); ++g_alloc_count;
-    c->pinned_in_bytes = bytes;
-    return 0;
-}
-
 int ctx_pinned(oemgpu_ctx *c, size_t bytes)
 {
     if (bytes <= c->pinned_bytes) return 0;
@@ -248,18 +157,11 @@ int ctx_pinned(oemgpu_ctx *c, size_t bytes)
     return 0;
 }
 
-struct Timer {
-    oemgpu_ctx *c; int id;
-    Timer(oemgpu_ctx *c_, int id_) : c(c_), id(id_)
-    {
-        if (c->timing) { (void)hipEventRecord(c->ev[2 * id], c->stream); c->ev_used[id] = true; }
-    }
-    ~Timer() { if (c->timing) (void)hipEventRecord(c->ev[2 * id + 1], c->stream); }
-};
+}  // namespace oemgpu
+
+namespace {
 
 // ---------------------------------------------------------------- argument checks (the R front ends stop() on these)
-int nl_of(const oemgpu_opts *o) { return (o->lambda_user && o->nlambda_user > 0) ? o->nlambda_user : o->nlambda; }
-
 int check_opts(const oemgpu_opts *o, int p, int ngroupvars_expected)
 {
     if (!o) { set_error("opts is NULL"); return OEMGPU_ERR_ARG; }
@@ -295,792 +197,11 @@ int check_opts(const oemgpu_opts *o, int p, int ngroupvars_expected)
 // the same checks for the entry points of other translation units (logistic.hip)
 int oemgpu::check_opts_export(const oemgpu_opts *o, int p, int ngroupvars_expected) { return check_opts(o, p, ngroupvars_expected); }
 
-namespace {
-
-// ---------------------------------------------------------------- host-built parameter blob
-struct Blob {
-    std::vector<char> h;
-    size_t add(const void *src, size_t bytes)
-    {
-        size_t o = (h.size() + 15) / 16 * 16;
-        h.resize(o + bytes);
-        if (bytes) memcpy(h.data() + o, src, bytes);
-        return o;
-    }
-};
-
-}  // namespace oemgpu
 #ifdef OEM_HOST_TIMING
-#include <chrono>
-namespace { struct HostT { double acc[8] = {0}; long n = 0; ~HostT() { if (n) fprintf(stderr, "host timing over %ld calls (us): entry->moments enqueued %.2f | ->path enqueued %.2f | ->copy enqueued %.2f | ->synced %.2f | ->unpacked/returned %.2f\n", n, acc[0] / n, acc[1] / n, acc[2] / n, acc[3] / n, acc[4] / n); } } g_ht;
-  double g_tp[6]; inline double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); } }
-#define HT(i) g_tp[i] = now_us()
-#else
-#define HT(i) do { } while (0)
+namespace { struct HostT { double acc[8] = {0}; long n = 0; ~HostT() { if (n) fprintf(stderr, "host timing over %ld calls (us): entry->moments enqueued %.2f | ->path enqueued %.2f | ->copy enqueued %.2f | ->synced %.2f | ->unpacked/returned %.2f\n", n, acc[0] / n, acc[1] / n, acc[2] / n, acc[3] / n, acc[4] / n); } } g_ht; }
+double oemgpu::g_tp[6];
 #endif
 namespace oemgpu {
-// group bookkeeping of get_group_indexes (ref src/oem_dense.h:421-456).  q = dimension of beta;
-// nscan = number of leading beta positions whose group entry is looked at (oemBig: nvars of nvars+1, quirk Q17).
-struct Groups {
-    std::vector<int> gid, gstart, gidx, gzero;
-    std::vector<double> gw;
-};
-void build_groups(const oemgpu_opts *o, int q, int nscan, Groups &G)
-{
-    G.gid.assign(q, -1);
-    G.gstart.assign(o->ngroups + 1, 0);
-    G.gzero.assign(o->ngroups > 0 ? o->ngroups : 1, 0);
-    G.gw.assign(o->ngroups > 0 ? o->ngroups : 1, 0.0);
-    G.gidx.clear();
-    // the reference matches every variable against every unique value (ref src/oem_dense.h:421-456): ngroups x nvars comparisons -- 2.5e9
-    // of them for 25,000 groups over 100,000 columns, seconds of host time per call.  Same members in the same order from a value -> index
-    // map and a counting sort, whenever the unique values ARE unique (R's sort(unique(groups)), R/oem.R:292); else the reference's loops.
-    const int nv = nscan < o->ngroupvars ? nscan : o->ngroupvars;
-    std::unordered_map<int, int> index;
-    bool distinct = true;
-    for (int g = 0; g < o->ngroups && distinct; ++g) distinct = index.emplace(o->unique_groups[g], g).second;
-    if (distinct && o->ngroups > 0) {
-        std::vector<int> cnt(o->ngroups + 1, 0), gv(nv > 0 ? nv : 1, -1);
-        for (int v = 0; v < nv; ++v) {
-            const auto it = index.find(o->groups[v]);
-            if (it != index.end()) { gv[v] = it->second; ++cnt[it->second + 1]; }
-        }
-        for (int g = 0; g < o->ngroups; ++g) { cnt[g + 1] += cnt[g]; G.gstart[g] = cnt[g]; G.gzero[g] = o->unique_groups[g] == 0; }
-        G.gidx.assign(cnt[o->ngroups], 0);
-        std::vector<int> at(cnt.begin(), cnt.end() - 1);
-        for (int v = 0; v < nv; ++v) if (gv[v] >= 0) { G.gidx[at[gv[v]]++] = v; G.gid[v] = gv[v]; }
-    } else {
-        for (int g = 0; g < o->ngroups; ++g) {
-            G.gstart[g] = (int)G.gidx.size();
-            for (int v = 0; v < nv; ++v)
-                if (o->groups[v] == o->unique_groups[g]) { G.gidx.push_back(v); G.gid[v] = g; }
-            G.gzero[g] = o->unique_groups[g] == 0;
-        }
-    }
-    if (o->ngroups > 0) G.gstart[o->ngroups] = (int)G.gidx.size();
-    for (int g = 0; g < o->ngroups; ++g)
-        G.gw[g] = (o->n_group_weights < 1) ? std::sqrt((double)(G.gstart[g + 1] - G.gstart[g])) : o->group_weights[g];
-    if (G.gidx.empty()) G.gidx.push_back(0);
-}
-
-// ---------------------------------------------------------------- the driver behind all entry points
-// xx (q x q), xy (q), stats already on the device (in the workspace).  sem: OEMGPU_SEM_*, or 2 for oem.xtx.
-enum { SEM_XTX = 2, SEM_SPARSE = 4 };        // OEMGPU_SEM_XVAL = 3 (oemgpu.h): oemBig's algebra with xval.oem's lambda_zero, groups and loss;
-                                              // SEM_SPARSE: oemSparse (the intercept slot rescaled in place through `scale_factor`, groups = q entries, slot 0 the intercept's group 0)
-
-// nbatch > 1: that many independent problems (instance b at xx + b * bstride, ... ; outputs of instance b at beta + b * npen * nl *
-// rows, lambda_out / niter / loss + b * npen * nl, d_out[b]) solved by ONE launch, one workgroup (set) each; q <= SMALL_P_MAX only.
-// Weighted oemDense with nobs <= nvars (weighted.hip): d comes from one matrix, the iteration runs on another and the loss belongs to
-// the first again -- d handed over (launch-per-iteration Gram engine only), the loss as a pass of its own over (loss_xx, loss_xy, loss_stats).
-struct PathExtras { double d_fixed = 0.0; const double *loss_xx = nullptr, *loss_xy = nullptr, *loss_stats = nullptr; };
-
-// ---- PLAN: everything run_paths decides before it touches the device, as a pure host function of sizes and options (VERDICT r4:
-// ten path engines chosen inside one 350-line function; the class of bug ADVICE r3 found -- a launch that rejects the workspace its
-// own caller sized -- now has a CPU test: oemgpu_selftest_plan, tests/test_host_api.py sweeps it over q, penalty families and options).
-struct PlanIn {
-    int num_cu = 256;
-    int p = 0, q = 0, sem = 0, intercept = 0, nbatch = 1;
-    const oemgpu_opts *o = nullptr;
-    bool has_scale = false;          // oem.xtx's scale.factor / oemSparse's in-place rescale of the intercept slot
-    bool launches_only = false;      // d handed over (PathExtras::d_fixed): the launch-per-iteration Gram engine only
-    bool loss_ext = false;           // the loss of ANOTHER Gram (PathExtras::loss_xx)
-    int wide_n = 0;                  // > 0: the p >= n iteration through the standardised X itself (WideArgs::n rows), no Gram matrix
-    bool wide_sparse = false;        // ... through the non-zeros of a resident sparse x (WideArgs::sparse): the launches of run_path_sparse_wide only
-};
-// Which XCD does workgroup i of a launch run on?  The one-XCD form of the cooperating engine (path_coop.hip) assumes "i mod 8" up to a
-// rotation; this asks the hardware once per context (64 workgroups report HW_REG_XCC_ID), and every such launch proves its own
-// placement again before it relies on it.
-__global__ void xcc_probe_kernel(int *out)
-{
-    unsigned id;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(id));
-    if (threadIdx.x == 0) out[blockIdx.x] = (int)(id & 0xfu);
-}
-
-static bool ctx_xcd_layout_ok(oemgpu_ctx *c)
-{
-    if (c->xcd_layout == 0) {
-        c->xcd_layout = -1;
-        int *dv = nullptr, h[64];
-        if (hipMalloc((void **)&dv, sizeof h) == hipSuccess) {          // (once per context, outside the workspace a call in progress has carved)
-            hipLaunchKernelGGL(xcc_probe_kernel, dim3(64), dim3(64), 0, c->stream, dv);
-            if (hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess &&
-                hipMemcpy(h, dv, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
-                bool ok = true;
-                unsigned seen = 0;
-                for (int i = 0; i < 64; ++i) ok = ok && h[i] == h[i & 7];
-                for (int i = 0; i < 8; ++i) seen |= 1u << (h[i] & 15);
-                if (ok && __builtin_popcount(seen) == 8) c->xcd_layout = 1;
-            }
-            (void)hipFree(dv);
-        }
-    }
-    return c->xcd_layout == 1;
-}
-
-struct PathPlan {
-    int engine = OEMGPU_ENGINE_NONE;                 // of the first attempt
-    bool any_grp = false, loss_on = false, loss_post = false;
-    bool small = false, coop = false, symc = false, rowcoop = false, symcoop = false, pen_split = false;
-    bool one_xcd = false;                            // path_coop.hip with all workgroups of an instance on ONE XCD (if the device's layout allows: run_paths)
-    bool wcoop = false, wres = false, wstream = false, cut = false;
-    int lan = 0, wg_n = 0, wsets = 1, wsg = 0, grcpw = 0;
-    size_t work_d = 0, sym_off_d = 0;                // doubles of `work` per instance; where path_symcoop.hip's exchange area starts in it
-    size_t out_stride = 0, out_bytes = 0, nb = 0, nk = 0;
-    Groups G;
-    std::vector<int> cst, grs, grg, grw;
-    int grp_head = 0;                                // group operators in the head of the packed-triangle pairs (PathArgs::grp_head: 1 .. 3)
-    std::vector<int> grun;                           // ... [2 q]
-    std::vector<double> gwc;                         // ... [q]
-    SymcoopPlan *symplan = nullptr;                  // (thread-local cache: a pure function of q, the CUs and the group runs)
-    PathArgs ap;                                     // the scalar fields of the kernels' arguments (the eligibility rules read them)
-    size_t frame_bytes() const { const int np = pen_split ? ap.npen : 1; Bump t; t.take(out_stride * ap.nbatch); t.take(work_d * sizeof(double) * ap.nbatch * np); return t.off; }
-};
-
-static int plan_paths(const PlanIn &in, PathPlan &P)
-{
-    const oemgpu_opts *o = in.o;
-    const int q = in.q, p = in.p, sem = in.sem, nbatch = in.nbatch, num_cu = in.num_cu;
-    const int nl = nl_of(o), npen = o->npen;
-    const bool wide = in.wide_n > 0, launches_only = in.launches_only;
-    for (int k = 0; k < npen; ++k) P.any_grp |= pen_is_grp(o->penalty[k]);
-    const bool any_grp = P.any_grp;
-    oemgpu_opts og = *o;
-    if (!any_grp) og.ngroups = 0;
-    Groups &G = P.G;
-    build_groups(&og, q, sem == OEMGPU_SEM_BIG ? p : q, G);      // quirk Q17 is oemBig's alone (ref src/oem_xval_dense.h:636 and src/oem_sparse.h:465 scan all groups.size() slots)
-    // p >= n on the cooperating engine with group penalties: where every group is a run of neighbouring columns the columns are dealt
-    // to the workgroups in whole groups (<= 4 CW columns each), so that no group's norm needs a value from another workgroup
-    std::vector<int> &cst = P.cst;
-    if (wide && !in.wide_sparse && og.ngroups > 0 && !sw().OEM_WCOOP_NO_ALIGN.set) {
-        const int cpg = path_wcoop_cpg(in.wide_n), gmax = path_wcoop_max_workgroups(in.wide_n, q);
-        bool ok = cpg > 0 && gmax > 0;
-        cst.push_back(0);
-        int fill = 0;
-        for (int j = 0; j < q && ok;) {
-            int len = 1;
-            const int g = G.gid[j];
-            if (g >= 0) {
-                len = G.gstart[g + 1] - G.gstart[g];
-                for (int k = 0; k < len && ok; ++k) ok = G.gidx[G.gstart[g] + k] == j + k;      // a run of neighbouring columns starting here
-            }
-            if (len > cpg) ok = false;
-            if (fill + len > cpg) { cst.push_back(j); fill = 0; }
-            fill += len; j += len;
-        }
-        cst.push_back(q);
-        if (!ok || (int)cst.size() - 1 > gmax || (int)cst.size() - 1 > num_cu * 3 / 4) cst.clear();
-    }
-    // p >= n beyond the persistent engines, group penalties: where every group is a run of neighbouring columns (<= WIDE_GRUN_MAX of
-    // them) the runs are dealt to the workgroups of the fused group kernel (path_large.hip: wide_groups_kernel) in whole runs
-    std::vector<int> &grs = P.grs, &grg = P.grg, &grw = P.grw;
-    if (wide && !in.wide_sparse && og.ngroups > 0) {
-        bool ok = true;
-        int maxrun = 1;
-        for (int j = 0; j < q && ok;) {
-            const int g = G.gid[j];
-            if (g < 0) { ok = false; break; }
-            const int len = G.gstart[g + 1] - G.gstart[g];
-            for (int k = 0; k < len && ok; ++k) ok = G.gidx[G.gstart[g] + k] == j + k;
-            if (len > WIDE_GRUN_MAX) ok = false;
-            grs.push_back(j); grg.push_back(g);
-            if (len > maxrun) maxrun = len;
-            j += len;
-        }
-        if (ok) {
-            grs.push_back(q);
-            const int Wt = wide_workgroups(in.wide_n, q), target = (q + Wt - 1) / Wt + maxrun - 1;      // (whole runs: never more than Wt workgroups)
-            int fill = 0;
-            grw.push_back(0);
-            for (int r = 0; r + 1 < (int)grs.size(); ++r) {
-                const int len = grs[r + 1] - grs[r];
-                if (fill > 0 && fill + len > target) { grw.push_back(r); if (fill > P.grcpw) P.grcpw = fill; fill = 0; }
-                fill += len;
-            }
-            grw.push_back((int)grs.size() - 1);
-            if (fill > P.grcpw) P.grcpw = fill;
-        } else { grs.clear(); grg.clear(); }
-    }
-    // 1024 < q <= 4096, element-wise penalties: the lower triangle of XX in the registers of <= 3/4 of the CUs (path_symcoop.hip);
-    // the plan is a pure function of (q, CUs): kept from call to call (until the switches are read again)
-    static thread_local SymcoopPlan symplan_plain, symplan_runs;
-    static thread_local int symplan_q = 0, symplan_gmax = 0;
-    static thread_local unsigned plans_gen = 0;
-    static thread_local std::vector<int> runs_key;
-    static thread_local int runs_q = 0, runs_gmax = 0;
-    if (plans_gen != sw().generation) { symplan_q = 0; runs_q = 0; runs_key.clear(); plans_gen = sw().generation; }
-    SymcoopPlan *symplan_p = &symplan_plain;
-    if (!wide && !launches_only && nbatch == 1 && q > 1024 && q <= 4096 && !sw().OEM_NO_SYMCOOP.set && !sw().OEM_NO_COOP.set) {
-        const int gmax = num_cu * 3 / 4 < WCOOP_GMAX ? num_cu * 3 / 4 : WCOOP_GMAX;
-        if (any_grp) {
-            // group operators: every group must be a run of neighbouring coordinates -- the owners' slices are cut there (and inside runs of more than 32)
-            std::vector<int> rs;
-            bool ok = true;
-            for (int j = 0; j < q && ok;) {
-                const int g = G.gid[j];
-                int len = 1;
-                if (g >= 0) {
-                    len = G.gstart[g + 1] - G.gstart[g];
-                    for (int k = 0; k < len && ok; ++k) ok = G.gidx[G.gstart[g] + k] == j + k;
-                }
-                rs.push_back(j);
-                j += len;
-            }
-            rs.push_back(q);
-            symplan_p = &symplan_runs;
-            // (the partition of the runs over the owners is a dynamic programme of some milliseconds: kept while q, the CUs and the runs are the same)
-            if (!ok) symplan_runs = SymcoopPlan();
-            else if (runs_q != q || runs_gmax != gmax || runs_key != rs) {
-                if (!symcoop_plan(q, gmax, symplan_runs, rs.data(), (int)rs.size() - 1)) symplan_runs = SymcoopPlan();
-                runs_key = rs; runs_q = q; runs_gmax = gmax;
-            }
-            if (!ok) { runs_key.clear(); runs_q = 0; }
-        } else if (symplan_q != q || symplan_gmax != gmax) {
-            if (!symcoop_plan(q, gmax, symplan_plain)) symplan_plain = SymcoopPlan();
-            symplan_q = q; symplan_gmax = gmax;
-        }
-        P.symc = !symplan_p->tab.empty();
-    }
-    P.symplan = symplan_p;
-    const SymcoopPlan &symplan = *symplan_p;
-
-    // ---- outputs region (device) : beta | lambda | loss | d[2] | niter | stats copy
-    P.nb = (size_t)npen * nl * q; P.nk = (size_t)npen * nl;
-    const size_t out_doubles = P.nb + 2 * P.nk + D_OUT_LEN + (size_t)stats_len(p);
-    P.out_bytes = out_doubles * sizeof(double) + P.nk * sizeof(int32_t);
-    P.out_stride = (P.out_bytes + 255) / 256 * 256;
-    P.loss_on = (sem == OEMGPU_SEM_DENSE || sem == OEMGPU_SEM_XVAL || sem == SEM_SPARSE) && o->compute_loss != 0;
-    // several instances (xval.oem's K + 1 fits) on the cooperating engine: only if all their workgroup sets are resident at once
-    // wide: the p >= n iteration through the standardised X itself (there is no Gram matrix)
-    P.coop = !wide && !launches_only && path_coop_eligible(q, in.has_scale, P.loss_on && !(in.has_scale && nbatch == 1), og.ngroups, nbatch) &&
-             (nbatch == 1 || path_coop_workgroups(q) * nbatch <= num_cu * 3 / 4);
-    P.small = !wide && !launches_only && q <= SMALL_P_MAX && !P.coop;
-    if (nbatch > 1 && !P.small && !P.coop) { set_error("internal: batched paths need p <= %d", SMALL_P_MAX); return OEMGPU_ERR_INTERNAL; }
-    // Lanczos step cap: q up to 288 (the whole Krylov space: the recurrence stops by itself when the top Ritz value has settled, and
-    // a spectrum that needs more than 128 steps gets them -- ADVICE r1); the large-p engines keep their own caps (256 / 512)
-    // (more steps than rows: without re-orthogonalisation a clustered spectrum does not exhaust the Krylov space in q steps -- a 9 x 9
-    // standardised sparse Gram was 1.1e-7 short after 9 -- but the top Ritz value keeps converging; the stagnation test ends it)
-    int lan = 2 * q < 32 ? 32 : (2 * q < 288 ? 2 * q : 288);
-    if (sw().OEMGPU_LANCZOS_CAP.set) { const int k = (int)sw().OEMGPU_LANCZOS_CAP.num; if (k >= 2 && k < lan) lan = k; }     // test knob: reach the cap
-    P.lan = lan;
-    size_t work_d = P.small ? path_small_xchg_bytes() / 8 : path_large_work_doubles(q, lan);
-    if (P.coop && work_d < path_coop_xchg_bytes() / 8) work_d = path_coop_xchg_bytes() / 8;
-    P.sym_off_d = (work_d + 31) / 32 * 32;             // the exchange area of path_symcoop.hip behind the launch-per-iteration engines' workspace (the fallback needs both)
-    if (P.symc) work_d = P.sym_off_d + (symcoop_work_bytes(symplan) + 7) / 8;
-    P.work_d = work_d;
-    // one workgroup (set) per penalty: they are independent cold starts (the cooperating sets must all be resident: <= half the CUs)
-    P.pen_split = npen > 1 && (P.small || (P.coop && path_coop_workgroups(q) * npen * nbatch <= num_cu / 2));
-    // q <= 512: the <= 16 cooperating workgroups of an instance fit ONE XCD (an eighth of the CUs), where an exchange through the local L2
-    // costs 0.65 us instead of 1.05 (path_coop.hip: LOCAL); instance y goes to XCD (base + y) mod 8, so the instances that share an XCD
-    // must fit it together
-    {
-        const int ninst = nbatch * (P.pen_split ? npen : 1), per_xcd = (ninst + 7) / 8;
-        P.one_xcd = P.coop && q <= 512 && num_cu >= 64 && num_cu % 8 == 0 && !sw().OEM_NO_ONE_XCD.set && path_coop_workgroups(q) * per_xcd <= num_cu / 8;
-    }
-
-    // ---- the scalar part of the kernels' arguments
-    PathArgs &a = P.ap;
-    memset(&a, 0, sizeof a);
-    a.p = q; a.npen = npen; a.nl = nl; a.user_lambda = o->lambda_user && o->nlambda_user > 0; a.maxit = o->maxit;
-    a.accelerate = (sem == OEMGPU_SEM_DENSE) ? (o->accelerate != 0) : 0;           // only oemDense accelerates (quirk Q12)
-    a.compute_loss = P.loss_on ? 1 : 0;
-    // oemSparse with an intercept beyond the single-workgroup kernels: the engines rescale the member in place before the product their
-    // loss would come from, so the loss is a pass of its own behind them (sparse.hip: gram_loss_kernel)
-    // (weighted oemDense, nobs <= nvars: the loss of ANOTHER Gram, see PathExtras)
-    P.loss_post = (P.loss_on && in.loss_ext) || (P.loss_on && in.has_scale && !P.small && !wide && nbatch == 1);
-    if (P.loss_post) a.compute_loss = 0;
-    a.ngroups = og.ngroups; a.lanczos_steps = lan; a.yscale = (sem == OEMGPU_SEM_DENSE);
-    const bool biglike = sem == OEMGPU_SEM_BIG || sem == OEMGPU_SEM_XVAL || sem == SEM_SPARSE;
-    a.lmax_from = (sem == OEMGPU_SEM_XVAL || sem == SEM_SPARSE) ? ((biglike && in.intercept) ? 1 : 0) : 0;              // ref src/oem_xval_dense.h:1025-1032
-    a.alpha = o->alpha; a.gamma = o->gamma; a.tau = o->tau; a.tol = o->tol; a.lambda_min_ratio = o->lambda_min_ratio;
-    a.sinv = in.has_scale ? reinterpret_cast<const double *>(8) : nullptr;      // (a marker for the eligibility rules; run_paths sets the pointer)
-    a.pen_split = P.pen_split; a.pen_lo = 0; a.pen_hi = npen;
-    a.nbatch = nbatch;
-
-    // the launch engines at q > 1024 (the packed triangle): groups that are runs of <= 96 neighbouring coordinates
-    // -- the group operators run in the head of the (head, product) pairs (path_large.hip), one launch fewer per iteration
-    // and no single-workgroup update kernel (q = 8,192: 65 -> 52 us per iteration)
-    if (!wide && any_grp && q > 1024 && nbatch == 1 && (int)G.gidx.size() <= q) {
-        bool ok = true;
-        int longest = 0;
-        for (int g = 0; g < og.ngroups && ok; ++g) {
-            const int m0 = G.gstart[g], len = G.gstart[g + 1] - m0;
-            ok = len <= 96;
-            if (len > longest) longest = len;
-            for (int k = 0; k < len && ok; ++k) ok = G.gidx[m0 + k] == G.gidx[m0] + k && G.gid[G.gidx[m0 + k]] == g;
-        }
-        if (ok) {
-            P.grp_head = longest <= 32 ? 1 : (longest <= 64 ? 2 : 3);      // blocks of 32 coordinates on either side of a head workgroup's own
-            P.grun.assign(2 * (size_t)q, 0); P.gwc.assign(q, 0.0);
-            for (int j = 0; j < q; ++j) {
-                const int g = G.gid[j];
-                if (g < 0) { P.grun[2 * j] = 1; P.grun[2 * j + 1] = 0; continue; }
-                const int gs = G.gidx[G.gstart[g]], ge = gs + (G.gstart[g + 1] - G.gstart[g]);
-                P.grun[2 * j] = gs; P.grun[2 * j + 1] = ge | (G.gzero[g] ? (1 << 30) : 0);
-                P.gwc[j] = G.gw[g];
-            }
-        }
-    }
-
-    // 1024 < q <= 2048, element-wise penalties: the row-split form with ONE exchange per iteration, else the symmetric one
-    P.rowcoop = P.symc && path_rowcoop_eligible(a, any_grp) && path_rowcoop_workgroups(q) <= num_cu * 3 / 4 &&
-                symcoop_work_bytes(symplan) >= path_rowcoop_xchg_bytes();
-    P.symcoop = P.symc && (P.rowcoop || path_symcoop_eligible(a, any_grp, symplan.runs));
-    if (wide && !in.wide_sparse) {
-        WideArgs wd;                                   // (sizes only: the eligibility rules read the layout and n)
-        wd.xs = nullptr; wd.ys = nullptr; wd.lay = wide_layout(in.wide_n); wd.n = in.wide_n; wd.scratch = nullptr;
-        // p >= n with Xs small enough for the register files of <= 192 CUs: one persistent launch (path_wcoop.hip)
-        // (all of a set's workgroups must be resident at once: never more of them than three quarters of this device's CUs)
-        const bool wcoop0 = path_wcoop_eligible(a, wd) && path_wcoop_workgroups(wd.n, q) <= num_cu * 3 / 4;
-        // (... unless the few extra workgroups of the cut partition cost a whole penalty set its place beside the others)
-        P.cut = wcoop0 && !cst.empty() && path_wcoop_sets(wd.n, q, npen, num_cu, (int)cst.size() - 1) >= 1 &&
-                path_wcoop_sets(wd.n, q, npen, num_cu, (int)cst.size() - 1) >= path_wcoop_sets(wd.n, q, npen, num_cu, 0);
-        P.wg_n = P.cut ? (int)cst.size() - 1 : (wcoop0 ? path_wcoop_workgroups(wd.n, q) : 0);
-        P.wsets = wcoop0 ? path_wcoop_sets(wd.n, q, npen, num_cu, P.wg_n) : 1;
-        const bool wres_forced = sw().OEM_WRES.set && path_wres_eligible(a, wd, num_cu - 8);      // (tests: also where the vector registers would do)
-        P.wcoop = wcoop0 && P.wsets >= 1 && !wres_forced;          // (0 sets: the exchange scratch cannot hold this partition -- the launches of run_path_wide take the call)
-        // ... where the vector registers alone cannot hold Xs: more column sets of every wave in the ACCUMULATOR file (path_wres_kernel: Xs up to
-        // ~11 M entries; 500 x 20,000 on 209 CUs).  That is more than three quarters of the CUs: every CU but a few, and alone on the device.
-        P.wres = !P.wcoop && path_wres_eligible(a, wd, num_cu - 8);
-        // ... and where it does not fit: the same persistent launch re-reading its column tiles every iteration (path_wstream_kernel)
-        P.wsg = num_cu * 3 / 4 < WCOOP_GMAX ? num_cu * 3 / 4 : WCOOP_GMAX;
-        P.wstream = !P.wcoop && !P.wres && (path_wcoop_workgroups(wd.n, q) > WCOOP_GMAX || sw().OEM_WSTREAM.set) && path_wstream_eligible(a, wd, P.wsg);      // (where it pays: measured there)
-    }
-    P.engine = P.rowcoop ? OEMGPU_ENGINE_ROWCOOP : P.symcoop ? OEMGPU_ENGINE_SYMCOOP : P.wres ? OEMGPU_ENGINE_WRES : P.wcoop ? OEMGPU_ENGINE_WCOOP
-               : P.wstream ? OEMGPU_ENGINE_WSTREAM : in.wide_sparse ? OEMGPU_ENGINE_SPARSE_WIDE : wide ? OEMGPU_ENGINE_WLAUNCHES : P.small ? OEMGPU_ENGINE_ROWS : P.coop ? OEMGPU_ENGINE_COOP : OEMGPU_ENGINE_LAUNCHES;
-    return 0;
-}
-
-size_t paths_ws_bytes(int p, int q, const oemgpu_opts *o, int nbatch = 1);
-
-// ---- scattered groups at 1024 < q <= 4096: the register-resident engine (path_symcoop.hip) cuts the owners' slices at group boundaries (and
-// inside runs of more than 32), so it takes group penalties only where every group is a RUN of neighbouring coordinates; other layouts went to the
-// launch-per-iteration engines (q = 3,000: 22 against 6-8 us per iteration -- the reference has no such cliff between group layouts, ref
-// src/oem_dense.h:421-456).  The OEM iteration does not care where a coordinate sits: u = A beta + XY, coordinate- / group-wise operators, a stop
-// rule over all coordinates, d an eigenvalue.  So groups that are not runs are MADE runs: coordinates reordered group by group (groups in
-// the order of their first member, members in their own order -- the order the reference sums their squares in), XX, XY, the column
-// constants, penalty factors and scale factors permuted alike, the path solved there, the coefficients put back.  One gather of q^2
-// doubles per call.
-__global__ __launch_bounds__(256) void permute_sym_kernel(const double *__restrict__ xx, const double *__restrict__ xy, const double *__restrict__ st, int q, int p_stats,
-                                                           const int *__restrict__ perm, double *__restrict__ xx2, double *__restrict__ xy2, double *__restrict__ st2)
-{
-    const int j = blockIdx.x, pj = perm[j];
-    for (int i = threadIdx.x; i < q; i += blockDim.x) xx2[(size_t)j * q + i] = xx[(size_t)pj * q + perm[i]];
-    if (threadIdx.x == 0) {
-        xy2[j] = xy[pj];
-        if (j < p_stats) { st2[4 + j] = st[4 + pj]; st2[4 + p_stats + j] = st[4 + p_stats + pj]; }      // meanX | scaleX (stats layout, common.hpp)
-    }
-    if (j == 0) {
-        for (int k = threadIdx.x; k < 4; k += blockDim.x) st2[k] = st[k];
-        for (int k = 4 + 2 * p_stats + threadIdx.x; k < stats_len(p_stats); k += blockDim.x) st2[k] = st[k];
-    }
-}
-
-// new position -> old position, or empty when the groups need no reordering / cannot be made runs
-static std::vector<int> group_run_permutation(const oemgpu_opts *o, int q, int max_len)
-{
-    std::vector<int> perm;
-    if (o->ngroups <= 0 || o->ngroupvars != q) return perm;
-    oemgpu_opts og = *o;
-    Groups G;
-    build_groups(&og, q, q, G);
-    bool runs = true;
-    int longest = 0;
-    for (int g = 0; g < o->ngroups; ++g) {
-        const int len = G.gstart[g + 1] - G.gstart[g];
-        if (len > longest) longest = len;
-        for (int k = 1; k < len && runs; ++k) runs = G.gidx[G.gstart[g] + k] == G.gidx[G.gstart[g]] + k;
-    }
-    // (groups of more than 32 members: the register engine sums their norms over several owners, path_symcoop.hip -- max_len = q;
-    //  the launches' head form beyond 4096 takes runs of <= 96: max_len = 96, nothing to gain otherwise)
-    if (runs || longest > max_len) return perm;
-    perm.reserve(q);
-    std::vector<char> done(o->ngroups, 0);
-    for (int j = 0; j < q; ++j) {
-        const int g = G.gid[j];
-        if (g < 0) perm.push_back(j);
-        else if (!done[g]) { done[g] = 1; for (int m = G.gstart[g]; m < G.gstart[g + 1]; ++m) perm.push_back(G.gidx[m]); }
-    }
-    if ((int)perm.size() != q) perm.clear();            // (a variable listed in two groups: not ours to untangle)
-    return perm;
-}
-
-static thread_local bool g_in_permuted_call = false;
-static thread_local int g_thread_engine = OEMGPU_ENGINE_NONE;      // c->last_engine of this thread's most recent path, whatever the context (oemgpu_last_host_path_engine)
-
-int run_paths(oemgpu_ctx *c, Bump &B, const double *xx, const double *xy, const double *stats, int p, int q, int sem,
-              int standardize, int intercept, const oemgpu_opts *o, const double *scale_factor,
-              double *beta, double *lambda_out, int32_t *niter, double *loss, double *d_out,
-              int nbatch = 1, size_t bstride = 0, bool shared_lmax = false, const WideArgs *wide = nullptr, const double *lmax_xy_dev = nullptr,
-              const PathExtras *ex = nullptr)
-{
-    const bool launches_only = ex && ex->d_fixed > 0.0;
-    const int nl = nl_of(o), npen = o->npen;
-    const bool user = o->lambda_user && o->nlambda_user > 0;
-    // (beyond 4096 the same reordering where it buys the launches their head form -- every group <= 96 members, PathArgs::grp_head)
-    const bool perm_reg = q > 1024 && q <= 4096 && !sw().OEM_NO_SYMCOOP.set && !sw().OEM_NO_COOP.set && !sw().OEM_SYMCOOP_NO_GENERAL.set;
-    // (... and below 4096 when the register engine is switched off: the launches are what runs)
-    const bool perm_large = q > 1024 && !perm_reg && !sw().OEM_NO_SYM.set && !sw().OEM_NO_FUSED.set;
-    if (!g_in_permuted_call && (perm_reg || perm_large) && nbatch == 1 && !wide && !ex && !lmax_xy_dev && xx && (sem == OEMGPU_SEM_DENSE || sem == SEM_XTX) &&
-        o->ngroups > 0) {
-        bool any_group_penalty = false;
-        for (int k = 0; k < npen; ++k) any_group_penalty |= pen_is_grp(o->penalty[k]);
-        const std::vector<int> perm = any_group_penalty ? group_run_permutation(o, q, perm_reg ? q : 96) : std::vector<int>();
-        if (!perm.empty()) {
-            // the permuted problem in a buffer of its own (xx2 | xy2 | stats2 | perm), the options with their per-coordinate arrays permuted
-            const size_t nd = (size_t)q * q + q + stats_len(p) + 8;
-            if (ctx_grow(c, &c->perm_buf, &c->perm_bytes, nd * sizeof(double) + (size_t)q * sizeof(int) + 256)) return OEMGPU_ERR_HIP;
-            double *xx2 = (double *)c->perm_buf, *xy2 = xx2 + (size_t)q * q, *st2 = xy2 + q;
-            int *perm_dev = (int *)(st2 + stats_len(p) + 8);
-            OEM_HIP(hipMemcpyAsync(perm_dev, perm.data(), sizeof(int) * q, hipMemcpyHostToDevice, c->stream));
-            OEM_HIP(hipStreamSynchronize(c->stream));                  // (perm is a pageable vector of this frame)
-            hipLaunchKernelGGL(permute_sym_kernel, dim3(q), dim3(256), 0, c->stream, xx, xy, stats, q, p, perm_dev, xx2, xy2, st2);
-            OEM_HIP(hipGetLastError());
-            std::vector<int32_t> g2(q);
-            std::vector<double> pf2(p), sf2(scale_factor ? q : 0);
-            for (int j = 0; j < q; ++j) { g2[j] = o->groups[perm[j]]; pf2[j] = o->penalty_factor[perm[j]]; if (scale_factor) sf2[j] = scale_factor[perm[j]]; }
-            oemgpu_opts o2 = *o;
-            o2.groups = g2.data(); o2.penalty_factor = pf2.data();
-            g_in_permuted_call = true;
-            const int rc = run_paths(c, B, xx2, xy2, st2, p, q, sem, standardize, intercept, &o2, scale_factor ? sf2.data() : nullptr, beta, lambda_out, niter, loss, d_out,
-                                     nbatch, bstride, shared_lmax, wide, lmax_xy_dev, ex);
-            g_in_permuted_call = false;
-            if (rc) return rc;
-            // the coefficients back to where the caller's variables are (row 0 of oem()'s result is the intercept)
-            const int rows = (sem == SEM_XTX) ? p : p + 1, off = rows - q;
-            std::vector<double> row(rows);
-            for (size_t ki = 0; ki < (size_t)npen * nl; ++ki) {
-                double *ob = beta + ki * rows;
-                memcpy(row.data(), ob, sizeof(double) * rows);
-                for (int j = 0; j < q; ++j) ob[off + perm[j]] = row[off + j];
-            }
-            return 0;
-        }
-    }
-    PlanIn pin;
-    pin.num_cu = c->num_cu; pin.p = p; pin.q = q; pin.sem = sem; pin.intercept = intercept; pin.nbatch = nbatch; pin.o = o;
-    pin.has_scale = scale_factor != nullptr; pin.launches_only = launches_only; pin.loss_ext = ex && ex->loss_xx; pin.wide_n = wide ? wide->n : 0;
-    pin.wide_sparse = wide && wide->sparse;
-    PathPlan P;
-    if (int prc = plan_paths(pin, P)) return prc;
-    const bool any_grp = P.any_grp, symc = P.symc, coop = P.coop, small = P.small, pen_split = P.pen_split, loss_post = P.loss_post;
-    const bool loss_ext = P.loss_on && pin.loss_ext;
-    const Groups &G = P.G;
-    const std::vector<int> &cst = P.cst, &grs = P.grs, &grg = P.grg, &grw = P.grw;
-    const int grcpw = P.grcpw;
-    SymcoopPlan &symplan = *P.symplan;
-    const size_t nb = P.nb, nk = P.nk, out_bytes = P.out_bytes, out_stride = P.out_stride, work_d = P.work_d, sym_off_d = P.sym_off_d;
-    (void)any_grp;
-
-    // ---- parameter blob
-    Blob bl;
-    std::vector<double> pf(q, 0.0), sinv;
-    const bool biglike = sem == OEMGPU_SEM_BIG || sem == OEMGPU_SEM_XVAL || sem == SEM_SPARSE;
-    const int off = (biglike && intercept) ? 1 : 0;       // leading 0 for the intercept, ref src/oem_big.cpp:105-113, src/oem_xval_dense.cpp:139-146
-    for (int j = 0; j < p; ++j) pf[j + off] = o->penalty_factor[j];
-    if (scale_factor) { sinv.resize(q); for (int j = 0; j < q; ++j) sinv[j] = 1.0 / scale_factor[j]; }
-    const size_t o_pen = bl.add(o->penalty, sizeof(int32_t) * npen);
-    const size_t o_lam = user ? bl.add(o->lambda_user, sizeof(double) * (size_t)npen * nl) : 0;
-    const size_t o_pf = bl.add(pf.data(), sizeof(double) * q);
-    const size_t o_sinv = scale_factor ? bl.add(sinv.data(), sizeof(double) * q) : 0;
-    const size_t o_gid = bl.add(G.gid.data(), sizeof(int) * q);
-    const size_t o_gst = bl.add(G.gstart.data(), sizeof(int) * G.gstart.size());
-    const size_t o_gix = bl.add(G.gidx.data(), sizeof(int) * G.gidx.size());
-    const size_t o_gz = bl.add(G.gzero.data(), sizeof(int) * G.gzero.size());
-    const size_t o_gw = bl.add(G.gw.data(), sizeof(double) * G.gw.size());
-    const size_t o_cst = cst.empty() ? 0 : bl.add(cst.data(), sizeof(int) * cst.size());
-    const size_t o_grs = grw.empty() ? 0 : bl.add(grs.data(), sizeof(int) * grs.size());
-    const size_t o_grg = grw.empty() ? 0 : bl.add(grg.data(), sizeof(int) * grg.size());
-    const size_t o_grw = grw.empty() ? 0 : bl.add(grw.data(), sizeof(int) * grw.size());
-    const size_t o_symp = symc ? bl.add(symplan.tab.data(), sizeof(int) * symplan.tab.size()) : 0;
-    const size_t o_grun = P.grp_head ? bl.add(P.grun.data(), sizeof(int) * P.grun.size()) : 0;
-    const size_t o_gwc = P.grp_head ? bl.add(P.gwc.data(), sizeof(double) * P.gwc.size()) : 0;
-
-    // the outputs come first: when the caller's frame ends with `stats` (both callers), stats | outputs is one
-    // contiguous range and one device-to-host copy returns both
-    const size_t a_out = B.take(out_stride * nbatch), a_blob = B.take(bl.h.size()),
-                 a_work = B.take(work_d * sizeof(double) * nbatch * (pen_split ? npen : 1));
-    // the workspace may be re-allocated by ctx_reserve: xx/xy/stats are offsets into it, so recompute after
-    const size_t off_xx = xx ? (const char *)xx - c->ws : 0, off_xy = (const char *)xy - c->ws, off_st = (const char *)stats - c->ws;
-    if (B.off > c->ws_bytes) { set_error("internal: workspace under-reserved (%zu > %zu)", B.off, c->ws_bytes); return OEMGPU_ERR_INTERNAL; }
-    if (xx) xx = (const double *)(c->ws + off_xx);
-    xy = (const double *)(c->ws + off_xy); stats = (const double *)(c->ws + off_st);
-    (void)a_blob;                                     // (the frame keeps its slot; the blob itself lives in a buffer of its own)
-    // its own grow-only buffer, not the workspace: the Gram partials of the NEXT call overlay this frame, and a blob that survives
-    // between calls is what lets run_paths skip an identical upload
-    if (bl.h.size() + 256 > c->blob_bytes) c->blob_dev = nullptr;      // a re-allocation may land on the old address
-    if (ctx_grow(c, &c->blob_buf, &c->blob_bytes, bl.h.size() + 256)) return OEMGPU_ERR_HIP;
-    char *dblob = c->blob_buf;
-    double *dout = (double *)(c->ws + a_out);
-    if (ctx_pinned_in(c, bl.h.size())) return OEMGPU_ERR_HIP;       // the previous call ended with a stream sync: the buffer is free
-    // Repeated solves with the same options (a lambda path re-fitted on new data, bench.py's loop) find the parameter blob already on
-    // the device: same bytes at the same workspace address as the last upload of this context => no copy (a 2 KB H2D copy is a
-    // 4 us node plus a boundary on a 570 us chain).
-    if (!(c->blob_dev == dblob && c->blob_len == bl.h.size() && memcmp(c->pinned_in, bl.h.data(), bl.h.size()) == 0)) {
-        memcpy(c->pinned_in, bl.h.data(), bl.h.size());
-        OEM_HIP(hipMemcpyAsync(dblob, c->pinned_in, bl.h.size(), hipMemcpyHostToDevice, c->stream));
-        c->blob_dev = dblob; c->blob_len = bl.h.size();
-    }
-    // Every output the host reads below is written by the path kernels, so the region is not cleared.  OEM_POISON_OUT=1
-    // fills it with NaN bit patterns first: the GPU suite run that way proves nothing depends on stale contents.
-    const bool poison = sw().OEM_POISON_OUT.set;
-    if (poison) { OEM_HIP(hipMemsetAsync(dout, 0xFF, out_stride * nbatch, c->stream)); c->blob_dev = nullptr; }
-
-    WideArgs wide_loc;
-    if (wide && !grw.empty()) {
-        wide_loc = *wide;
-        wide_loc.grun_start = (const int *)(dblob + o_grs); wide_loc.grun_gid = (const int *)(dblob + o_grg); wide_loc.grun_wg = (const int *)(dblob + o_grw);
-        wide_loc.grun_W = (int)grw.size() - 1; wide_loc.grun_cpw = grcpw;
-        wide = &wide_loc;
-    }
-    PathArgs a = P.ap;                                   // the scalars are the plan's; the pointers:
-    a.d_fixed = launches_only ? ex->d_fixed : 0.0;
-    a.no_active_prefix = sw().OEM_NO_ACTIVE_PREFIX.set ? 1 : 0;
-    a.xx = xx; a.xy = xy; a.stats = stats;
-    a.penalty = (const int *)(dblob + o_pen);
-    a.lambda_user = user ? (const double *)(dblob + o_lam) : nullptr;
-    a.pf = (const double *)(dblob + o_pf);
-    a.sinv = scale_factor ? (const double *)(dblob + o_sinv) : nullptr;
-    a.gid = (const int *)(dblob + o_gid); a.gstart = (const int *)(dblob + o_gst); a.gidx = (const int *)(dblob + o_gix);
-    a.gzero = (const int *)(dblob + o_gz); a.gw = (const double *)(dblob + o_gw);
-    a.grp_head = P.grp_head;
-    a.grun = P.grp_head ? (const int *)(dblob + o_grun) : nullptr; a.gwc = P.grp_head ? (const double *)(dblob + o_gwc) : nullptr;
-    a.beta = dout; a.lambda_out = dout + nb; a.loss = a.lambda_out + nk; a.d_out = a.loss + nk;
-    double *dstats = a.d_out + D_OUT_LEN;
-    a.niter = (int *)(dstats + stats_len(p));
-    a.work = (double *)(c->ws + a_work);
-    a.lmax_xy = (nbatch > 1 && shared_lmax) ? xy : lmax_xy_dev;    // instance 0's X'Y; or the caller's (big.oem with p >= n: the scaled X'y)
-    a.bs_xx = a.bs_xy = a.bs_stats = (long long)bstride; a.bs_out = (long long)out_stride; a.bs_work = (long long)work_d;
-
-    const size_t st_gap = (size_t)((const char *)dout - (const char *)stats);
-    // Results straight into pinned host memory (row-split kernel, one instance): that kernel only ever STORES to its outputs, so they
-    // may live in host memory the device writes over PCIe while it runs (a few hundred bytes per lambda); the device-to-host copy
-    // node behind the kernel -- a launch boundary and a DMA set-up with the GPU idle -- disappears.  OEM_NO_ZERO_COPY=1: the copy.
-    a.stats_out = nullptr; a.stats_n = 0;
-    const bool zero_copy = small && nbatch == 1 && !poison && path_small_takes_rows(a) && !sw().OEM_NO_ZERO_COPY.set;
-    const bool joined = !zero_copy && nbatch == 1 && (const char *)stats < (const char *)dout && st_gap == ((size_t)stats_len(p) * 8 + 255) / 256 * 256;
-    const size_t back_bytes = nbatch > 1 ? out_stride * nbatch : out_bytes + (joined ? st_gap : 0);
-    if (ctx_pinned(c, back_bytes > 16384 ? back_bytes : 16384)) return OEMGPU_ERR_HIP;
-    if (zero_copy) {
-        double *hout = (double *)c->pinned;
-        a.beta = hout; a.lambda_out = hout + nb; a.loss = a.lambda_out + nk; a.d_out = a.loss + nk;
-        a.stats_out = a.d_out + D_OUT_LEN; a.stats_n = stats_len(p);
-        a.niter = (int *)(a.stats_out + stats_len(p));
-    }
-    const bool rowcoop = P.rowcoop, symcoop = P.symcoop, wcoop = P.wcoop, wres = P.wres, wstream = P.wstream;
-    const int wg_n = P.wg_n, wsets = P.wsets, wsg = P.wsg;
-    const int *wcst = P.cut ? (const int *)(dblob + o_cst) : nullptr;
-    // The persistent engines spin on their partners: every workgroup of every such kernel in flight must be resident at once, so
-    // concurrent callers queue for CU slots (held until the stream has been synchronised below)
-    CoopSlots slots;
-    // (one XCD: an instance's <= 16 workgroups compete for the 32 CUs of ITS XCD -- booked per XCD, the first XCD chosen where the load is lowest)
-    // (a reload of the switches -- tests -- also forgets a timed-out engine's back-off and a refused placement)
-    if (c->sw_generation != sw().generation) { c->sw_generation = sw().generation; c->persistent_backoff = 0; c->persistent_skip = 0; if (c->xcd_layout < 0) c->xcd_layout = 0; }
-    bool local = P.one_xcd && ctx_xcd_layout_ok(c);
-    const int coop_ninst = (pen_split ? npen : 1) * nbatch;
-    int local_base = 0;
-    if (coop) {
-        if (local) local_base = slots.take_local(c->device, path_coop_workgroups(q), coop_ninst, c->num_cu, c->num_cu * 3 / 4);
-        else slots.take(c->device, path_coop_workgroups(q) * coop_ninst, c->num_cu * 3 / 4);
-    }
-    c->last_placement = 0;
-    if (symcoop) slots.take(c->device, rowcoop ? path_rowcoop_workgroups(q) : symplan.G, c->num_cu * 3 / 4);
-    if (wcoop) slots.take(c->device, wg_n * wsets, c->num_cu * 3 / 4);
-    if (wres) slots.take(c->device, path_wres_workgroups(wide->n, q) > c->num_cu * 3 / 4 ? c->num_cu : path_wres_workgroups(wide->n, q), c->num_cu * 3 / 4);
-    if (wstream) slots.take(c->device, wsg, c->num_cu * 3 / 4);
-    // The persistent engines (p >= n; 208 < p <= 1024) need all their workgroups resident at once.  If somebody else holds the CUs (another process on a
-    // shared GPU) their exchanges time out after about a second and poison the result: the call is then made again on the
-    // launch-per-iteration engines, which wait for nobody.
-    // A persistent launch runs the whole penalty x lambda path (config 4: 23 ms; p >= n at maxit: seconds) and the reference polls for user
-    // interrupts every third lambda (ref src/oem_dense.cpp:235-238): with an interrupt callback the kernel gets an abort word in
-    // host-coherent memory, and the host waits for the launch by polling the stream AND the callback (on the calling thread).
-    const bool abortable = o->interrupt != nullptr && (wcoop || wres || wstream || symcoop || coop);
-    if (abortable) {
-        if (!c->abort_host) {
-            OEM_HIP(hipHostMalloc((void **)&c->abort_host, 64, hipHostMallocMapped)); ++g_alloc_count;
-            OEM_HIP(hipHostGetDevicePointer((void **)&c->abort_dev, c->abort_host, 0));
-        }
-        __atomic_store_n(c->abort_host, 0, __ATOMIC_SEQ_CST);
-    }
-    const bool any_persistent = wcoop || wres || wstream || symcoop || (coop && nbatch == 1);
-    auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    // (ctx.hpp: a caller on a shared GPU does not pay the second of a timeout on every call -- VERDICT r4)
-    const bool skip_persistent = any_persistent && c->persistent_skip > 0 && now_s() < c->persistent_skip_until;
-    if (skip_persistent) --c->persistent_skip;
-    for (int attempt = skip_persistent ? 1 : 0;; ++attempt) {
-        const bool persistent = any_persistent && attempt == 0;
-        a.abort_word = (abortable && (persistent || (coop && attempt == 0))) ? c->abort_dev : nullptr;
-        a.one_xcd = (coop && attempt == 0 && local) ? (sw().OEM_FAKE_XCD_MISMATCH.set ? 2 : 1) : 0;
-        a.xcd_base = a.one_xcd ? local_base : 0;          // (CoopSlots::take_local: where this device's XCDs are emptiest)
-        {
-            Timer t(c, OEMGPU_T_EIGPATH);
-            PollScope poll(o);
-            int rc;
-            c->last_engine = (persistent && rowcoop) ? OEMGPU_ENGINE_ROWCOOP : (persistent && symcoop) ? OEMGPU_ENGINE_SYMCOOP : (persistent && wres) ? OEMGPU_ENGINE_WRES
-                             : (persistent && wcoop) ? OEMGPU_ENGINE_WCOOP : (persistent && wstream) ? OEMGPU_ENGINE_WSTREAM : persistent ? OEMGPU_ENGINE_COOP
-                             : (wide && wide->sparse) ? OEMGPU_ENGINE_SPARSE_WIDE : wide ? OEMGPU_ENGINE_WLAUNCHES : small ? OEMGPU_ENGINE_ROWS : (coop && attempt == 0) ? OEMGPU_ENGINE_COOP : OEMGPU_ENGINE_LAUNCHES;
-            g_thread_engine = c->last_engine;
-            if (persistent && rowcoop) rc = launch_path_rowcoop(c->stream, a, a.work + sym_off_d);
-            else if (persistent && symcoop) rc = launch_path_symcoop(c->stream, a, symplan, (const int *)(dblob + o_symp), a.work + sym_off_d);
-            else if (persistent && wres) rc = launch_path_wres(c->stream, a, *wide);
-            else if (persistent) rc = wcoop ? launch_path_wcoop(c->stream, a, *wide, wsets, wcst, wg_n) : wstream ? launch_path_wstream(c->stream, a, *wide, wsg) : launch_path_coop(c->stream, a);
-            else if (wide && wide->sparse) rc = run_path_sparse_wide(c->stream, a, *wide->sparse, (double *)c->pinned);
-            else if (wide) rc = run_path_wide(c->stream, a, *wide, (double *)c->pinned);
-            else if (small) rc = launch_path_small(c->stream, a);
-            else if (coop && attempt == 0) rc = launch_path_coop(c->stream, a);                 // (several instances: no second engine takes them)
-            else {
-                PathArgs al = a;                                  // (after a timed-out cooperating launch: one instance, its penalties in turn)
-                al.pen_split = 0; al.pen_lo = 0; al.pen_hi = npen;
-                if (const size_t pkd = sympk_doubles(q)) {         // q > 4096: the products stream a packed copy of the lower triangle
-                    if (ctx_grow(c, &c->pack_buf, &c->pack_bytes, pkd * sizeof(double))) return OEMGPU_ERR_HIP;
-                    al.sympk = (double *)c->pack_buf;
-                }
-                rc = run_path_large(c->stream, al, (double *)c->pinned);
-            }
-            if (rc) return rc;
-            if (loss_post && (rc = launch_gram_loss(c->stream, loss_ext ? ex->loss_xx : xx, loss_ext ? ex->loss_xy : xy, loss_ext ? ex->loss_stats : stats, q,
-                                                    a.beta, a.sinv, a.niter, a.loss, (int)nk))) return rc;
-        }
-        HT(2);
-        if (!zero_copy) {
-            if (!joined && nbatch == 1) OEM_HIP(hipMemcpyAsync(dstats, stats, sizeof(double) * stats_len(p), hipMemcpyDeviceToDevice, c->stream));      // (stats outside the frame: the permuted problem)
-            else if (!joined) OEM_HIP(hipMemcpy2DAsync(dstats, out_stride, stats, bstride * sizeof(double), sizeof(double) * stats_len(p), nbatch,
-                                                       hipMemcpyDeviceToDevice, c->stream));
-            OEM_HIP(hipMemcpyAsync(c->pinned, joined ? (const void *)stats : (const void *)dout, back_bytes, hipMemcpyDeviceToHost, c->stream));
-        }
-        HT(3);
-        if (a.abort_word) {
-            bool asked = false;
-            const auto t0 = std::chrono::steady_clock::now();
-            auto last = t0;
-            for (;;) {
-                const hipError_t qe = hipStreamQuery(c->stream);
-                if (qe == hipSuccess) break;
-                if (qe != hipErrorNotReady) OEM_HIP(qe);
-                const auto now = std::chrono::steady_clock::now();
-                if (!asked && now - last >= std::chrono::milliseconds(1)) {          // the callback at most once per millisecond
-                    last = now;
-                    if (o->interrupt(o->interrupt_arg)) { __atomic_store_n(c->abort_host, 1, __ATOMIC_SEQ_CST); asked = true; }
-                }
-                if (now - t0 < std::chrono::milliseconds(2)) std::this_thread::yield();
-                else std::this_thread::sleep_for(std::chrono::microseconds(100));
-            }
-            OEM_HIP(hipStreamSynchronize(c->stream));
-            if (asked) { set_error("interrupted by the caller"); return OEMGPU_ERR_INTERRUPTED; }
-        }
-        OEM_HIP(hipStreamSynchronize(c->stream));
-        HT(4);
-        if (a.one_xcd) {
-            // the launch's own proof of placement (path_coop.hip): poison value 2 in any instance = its workgroups were NOT on one XCD and
-            // nothing was computed; this context does not ask again, and the call is made again with the exchange at device scope
-            // Poison 3 = a partner never came to the proof: the instance's workgroups were not co-resident on ITS XCD (somebody this process does
-            // not know of holds CUs there) -- and, for several instances (which have no second engine), a later exchange that timed out the same
-            // way: the call is made again ONCE with the workgroups anywhere on the device; no back-off, the context keeps asking.
-            bool refused = false, crowded = false;
-            for (int bi = 0; bi < nbatch; ++bi) {
-                const double *hdb = (const double *)((const char *)c->pinned + (joined ? st_gap : 0) + (size_t)bi * out_stride) + nb + 2 * nk;
-                refused = refused || hdb[6] == 2.0;
-                crowded = crowded || hdb[6] == 3.0 || (nbatch > 1 && hdb[6] == 1.0);
-            }
-            c->last_placement = refused ? 2 : crowded ? 3 : 1;
-            if (refused) c->xcd_layout = -1;
-            if (refused || crowded) {
-                local = false; --attempt;
-                slots.release();
-                slots.take(c->device, path_coop_workgroups(q) * coop_ninst, c->num_cu * 3 / 4);
-                continue;
-            }
-        }
-        if (persistent) {
-            const double *hd0 = (const double *)((const char *)c->pinned + (joined ? st_gap : 0)) + nb + 2 * nk;
-            if (hd0[6] != 0.0) {
-                ++c->persistent_fallbacks;
-                c->persistent_backoff = c->persistent_backoff < 4 ? 4 : (c->persistent_backoff < 64 ? 2 * c->persistent_backoff : 64);
-                c->persistent_skip = c->persistent_backoff; c->persistent_skip_until = now_s() + 30.0;
-                continue;
-            }
-            c->persistent_backoff = 0; c->persistent_skip = 0;
-        }
-        break;
-    }
-
-    // ---- unpack (ref src/oem_dense.cpp:249-294, src/DataStd.h:269-293, src/oem_big.h:880-897, src/oem_big.cpp:213-220)
-    const int flag = (standardize ? 1 : 0) + 2 * (intercept ? 1 : 0);
-    const int rows = (sem == SEM_XTX) ? p : p + 1;
-    for (int bi = 0; bi < nbatch; ++bi) {
-        const double *hb = (const double *)((const char *)c->pinned + (joined ? st_gap : 0) + (size_t)bi * out_stride), *hl = hb + nb,
-                     *hloss = hl + nk, *hd = hloss + nk, *hs = joined ? (const double *)c->pinned : hd + D_OUT_LEN;
-        const int32_t *hn = (const int32_t *)(hd + D_OUT_LEN + stats_len(p));
-        double *beta_b = beta + (size_t)bi * nk * rows, *lambda_b = lambda_out + (size_t)bi * nk, *loss_b = loss + (size_t)bi * nk;
-        int32_t *niter_b = niter + (size_t)bi * nk;
-        d_out[bi] = hd[0];
-        // poison slot (common.hpp): cleared by the launchers of the multi-workgroup engines, written 0 by the others
-        if (hd[6] != 0.0) { set_error("cooperating workgroups lost each other (exchange timeout)"); return OEMGPU_ERR_INTERNAL; }
-        c->diag[0] = hd[2]; c->diag[1] = hd[3];
-        if (bi == 0) { c->eig_steps = (int)hd[4]; c->eig_capped = hd[5] != 0.0; }
-        if (bi == 0) {                                   // (only the row-split kernel counts its rounds)
-            const bool rows = c->last_engine == OEMGPU_ENGINE_ROWS && path_small_takes_rows(a);
-            c->path_rounds_short = rows ? (int64_t)hd[7] : 0; c->path_rounds = rows ? (int64_t)hd[8] : 0;
-        }
-        c->shifted = hs[stats_shift_flag(p)] != 0.0;
-        c->shift_advised = hs[stats_shift_flag(p) + 1] != 0.0;
-        const double meany = hs[0], scaley = hs[1];
-        const double *meanx = hs + 4, *scalex = hs + 4 + p;
-        for (int k = 0; k < npen; ++k) {
-            const int nlam = (o->penalty[k] == OEMGPU_OLS) ? 1 : nl;
-            for (int i = 0; i < nl; ++i) {
-                const size_t ki = (size_t)k * nl + i;
-                lambda_b[ki] = hl[ki];
-                niter_b[ki] = (i < nlam) ? hn[ki] : 0;
-                loss_b[ki] = (i < nlam && (a.compute_loss || loss_post)) ? hloss[ki] : 1e99;
-                double *ob = beta_b + ki * rows;
-                const double *b = hb + ki * q;
-                if (i >= nlam) { for (int j = 0; j < rows; ++j) ob[j] = 0.0; continue; }
-                if (sem == SEM_XTX) {
-                    for (int j = 0; j < p; ++j) ob[j] = b[j];
-                } else if (biglike) {
-                    ob[0] = intercept ? b[0] : 0.0;
-                    for (int j = 0; j < p; ++j) ob[j + 1] = b[j + off] * (standardize ? scalex[j] : 1.0);
-                } else {
-                    // DataStd::recover (ref src/DataStd.h:269-293), one loop per flag: the tests inside the loop kept it scalar
-                    // (12 us of host time per config-1 solve with the GPU idle; the same operations in the same order now)
-                    double s = 0.0;
-                    switch (flag) {
-                    case 0: for (int j = 0; j < p; ++j) ob[j + 1] = b[j]; break;
-                    case 1: for (int j = 0; j < p; ++j) ob[j + 1] = b[j] / scalex[j] * scaley; break;
-                    case 2: for (int j = 0; j < p; ++j) { const double cf = b[j] * scaley; ob[j + 1] = cf; } break;
-                    default: for (int j = 0; j < p; ++j) { const double cf = b[j] / scalex[j] * scaley; ob[j + 1] = cf; } break;
-                    }
-                    if (flag & 2) for (int j = 0; j < p; ++j) s += ob[j + 1] * meanx[j];
-                    ob[0] = (flag & 2) ? meany - s : 0.0;
-                }
-            }
-        }
-    }
-    return 0;
-}
-
-size_t paths_ws_bytes(int p, int q, const oemgpu_opts *o, int nbatch)
-{
-    const int nl = nl_of(o);
-    if (nbatch > 1) return (size_t)nbatch * (paths_ws_bytes(p, q, o) + 1024) + (q >= path_coop_min_q(true) ? (size_t)nbatch * o->npen * path_coop_xchg_bytes() : 0);
-    const size_t splits = (q <= 1024 && o->npen > 1) ? (size_t)o->npen : 1;
-    size_t b = 0;
-    b += (size_t)o->npen * 4 + (size_t)o->npen * nl * 8 + (size_t)q * (8 + 8 + 4) + (size_t)(o->ngroups + 2) * 16 +
-         (size_t)(o->ngroupvars + q + 2) * 4 + (q > 1024 ? (size_t)q * 16 : 0) + 4096;      // (+ the per-coordinate group runs and weights of PathArgs::grp_head)
-    b += ((size_t)o->npen * nl * (q + 3) + 4 + stats_len(p)) * 8 + 4096;
-    // (from the cooperating engine's smallest q on -- 209, below the single-workgroup limit of 288 -- a call that is not small keeps the
-    // launch-per-iteration engines' workspace as its fallback: oemgpu_selftest_plan found 209 <= q <= 288 with several penalties sized for
-    // the small engine's exchange alone, 18 KB short at q = 209 x 8 penalties and covered only by ctx_reserve's slack)
-    size_t wk = (q > SMALL_P_MAX || q >= path_coop_min_q(true)) ? path_large_work_doubles(q, 128) * 8 : path_small_xchg_bytes();
-    if (wk < path_small_xchg_bytes()) wk = path_small_xchg_bytes();
-    if (q >= path_coop_min_q(true) && q <= 1024 && wk < path_coop_xchg_bytes()) wk = path_coop_xchg_bytes();
-    b += wk * splits + 4096;
-    b += (size_t)q * 12 + 64;                                          // the runs of the fused group kernel (p >= n)
-    if (q > 1024 && q <= 4096) b += symcoop_xchg_bytes_max(q) + (size_t)(80 + WCOOP_GMAX * 96) * 4 + (size_t)q * 8 + 1024;      // path_symcoop.hip's exchange area and plan (+ the fragment table of split groups)
-    return b;
-}
-
 // out[i] = ((parts[0][i] + parts[1][i]) + parts[2][i]) + ...: the shards' moment buffers added in shard (= rank = device) order -- the order
 // hoststream.hip adds them in, so the one-process-per-GPU form (all-gather + this kernel) and the in-library form return the same bits
 __global__ __launch_bounds__(256) void sum_in_order_kernel(const double *__restrict__ parts, int nparts, size_t len, double *__restrict__ out)
@@ -1188,37 +309,6 @@ extern "C" {
 
 void oemgpu_reload_switches(void) { sw_reload(); }
 
-int oemgpu_selftest_plan(int32_t p, int32_t q, int32_t semantics, int32_t intercept, const oemgpu_opts *o, int32_t has_scale, int32_t nbatch,
-                         int64_t wide_n, int32_t num_cu, int32_t *engine, int64_t *frame_bytes, int64_t *reserved_bytes,
-                         int64_t *scratch_need_doubles, int64_t *scratch_have_doubles)
-{
-    if (!o || !engine || !frame_bytes || !reserved_bytes || !scratch_need_doubles || !scratch_have_doubles) { set_error("selftest_plan: NULL argument"); return OEMGPU_ERR_ARG; }
-    if (int rc = check_opts(o, p, semantics == OEMGPU_SEM_DENSE || semantics == SEM_XTX ? p : q)) return rc;
-    PlanIn in;
-    in.num_cu = num_cu; in.p = p; in.q = q; in.sem = semantics; in.intercept = intercept; in.nbatch = nbatch; in.o = o;
-    in.has_scale = has_scale != 0; in.wide_n = (int)wide_n;
-    PathPlan P;
-    if (int rc = plan_paths(in, P)) return rc;
-    *engine = P.engine | (P.one_xcd ? 256 : 0) | (P.grp_head << 9);      // (bit 8: OEMGPU_ENGINE_COOP planned with every instance on one XCD; bits 9-10: PathArgs::grp_head, what the launches would do with the groups)
-    // the frame run_paths carves (outputs | blob slot | work) against what every caller reserves for it (paths_ws_bytes); the blob
-    // slot is bounded by the reservation's first two terms, which this adds back as the groups' and lambdas' actual sizes
-    const int nl = nl_of(o);
-    size_t blob = (size_t)o->npen * 4 + ((o->lambda_user && o->nlambda_user > 0) ? (size_t)o->npen * nl * 8 : 0) + (size_t)q * (8 + 8 + 4) +
-                  P.G.gstart.size() * 4 + P.G.gidx.size() * 4 + P.G.gzero.size() * 4 + P.G.gw.size() * 8 + P.cst.size() * 4 +
-                  (P.grw.empty() ? 0 : (P.grs.size() + P.grg.size() + P.grw.size()) * 4) + (P.symc ? P.symplan->tab.size() * 4 : 0) +
-                  (P.grp_head ? P.grun.size() * 4 + P.gwc.size() * 8 : 0) + 18 * 16;
-    *frame_bytes = (int64_t)(P.frame_bytes() + (blob + 255) / 256 * 256);
-    *reserved_bytes = (int64_t)(paths_ws_bytes(p, q, o, nbatch) + 4096);
-    // p >= n: the exchange buffers of the persistent engine chosen against the scratch every caller allocates (wide_scratch_doubles)
-    *scratch_need_doubles = 0; *scratch_have_doubles = 0;
-    if (wide_n > 0) {
-        *scratch_have_doubles = (int64_t)wide_scratch_doubles((int)wide_n, q);
-        if (P.wres) *scratch_need_doubles = (int64_t)path_wres_xchg_doubles((int)wide_n, q);
-        else if (P.wstream) *scratch_need_doubles = (int64_t)path_wstream_xchg_doubles((int)wide_n);
-        else if (P.wcoop) *scratch_need_doubles = (int64_t)path_wcoop_launch_doubles((int)wide_n, q, P.wg_n, P.wsets);
-    }
-    return 0;
-}
 const char *oemgpu_switch_names(void)
 {
 #define OEM_SW_NAME(name) #name " "
@@ -1366,39 +456,6 @@ int oemgpu_sum_in_order_dev(oemgpu_ctx *c, const double *parts_dev, int32_t npar
     const int blocks = (int)std::min<int64_t>((len + 255) / 256, 2048);
     hipLaunchKernelGGL(sum_in_order_kernel, dim3(blocks), dim3(256), 0, c->stream, parts_dev, (int)nparts, (size_t)len, out_dev);
     OEM_HIP(hipGetLastError());
-    return 0;
-}
-
-int oemgpu_selftest_group_permutation(const oemgpu_opts *o, int32_t q, int32_t *perm)
-{
-    if (!o || !perm || q < 1) { set_error("selftest_group_permutation: bad argument"); return OEMGPU_ERR_ARG; }
-    const std::vector<int> pm = group_run_permutation(o, q, q);
-    for (size_t j = 0; j < pm.size(); ++j) perm[j] = pm[j];
-    return (int)pm.size();
-}
-
-int oemgpu_selftest_symcoop_owners(int32_t q, int32_t num_cu, const int32_t *runs, int32_t nruns, int32_t *owner_c0, int32_t *owner_n, int32_t *frag,
-                                   int32_t *nowners, int32_t *split)
-{
-    if (q <= 1024 || q > 4096 || num_cu < 8 || !runs || nruns < 1 || !owner_c0 || !owner_n || !frag || !nowners || !split || runs[0] != 0 || runs[nruns] != q) {
-        set_error("selftest_symcoop_owners: bad argument (1024 < q <= 4096, runs[0] = 0, runs[nruns] = q)"); return OEMGPU_ERR_ARG;
-    }
-    const int gmax = num_cu * 3 / 4 < WCOOP_GMAX ? num_cu * 3 / 4 : WCOOP_GMAX;
-    int G = 0, sp = 0;
-    if (!symcoop_plan_owners(q, gmax, runs, nruns, owner_c0, owner_n, frag, &G, &sp)) { *nowners = 0; *split = 0; return 0; }      // (no plan: the launches take the call)
-    *nowners = G; *split = sp;
-    return 0;
-}
-
-int oemgpu_selftest_coop_slots(int32_t num_cu, int32_t W, int32_t ninst, int32_t calls, int32_t *bases, int32_t *peak)
-{
-    if (num_cu < 8 || num_cu % 8 || W < 1 || ninst < 1 || calls < 1 || calls > 64 || !bases || !peak) { set_error("selftest_coop_slots: bad argument"); return OEMGPU_ERR_ARG; }
-    if ((long long)W * ninst * calls > num_cu * 3 / 4) { set_error("selftest_coop_slots: %d calls of %d x %d workgroups would wait for each other", calls, ninst, W); return OEMGPU_ERR_ARG; }
-    std::vector<CoopSlots> held(calls);
-    const int dev = COOP_MAX_DEV - 2;                    // (a device index no GPU of this process has: the book of a device of its own)
-    *peak = 0;
-    for (int k = 0; k < calls; ++k) bases[k] = held[k].take_local(dev, W, ninst, num_cu, num_cu * 3 / 4);
-    { std::lock_guard<std::mutex> lk(g_coop_mu); for (int x = 0; x < 8; ++x) if (g_xcd_load[dev][x] > *peak) *peak = g_xcd_load[dev][x]; }
     return 0;
 }
 
@@ -1554,8 +611,9 @@ static int solve_moments_impl(oemgpu_ctx *c, const double *moments_dev, const do
         if (rc) return rc;
     }
     if (!ex) return run_paths_parts(c, B2, xx, xy, st, p, q, semantics, standardize, intercept, o, beta, lambda_out, niter, loss, d, nullptr, lmax_xy);
-    return run_paths(c, B2, xx, xy, st, p, q, semantics, standardize, intercept, o, nullptr, beta, lambda_out, niter, loss, d,
-                     1, 0, false, nullptr, lmax_xy, ex);
+    PathExtras x = *ex;
+    x.lmax_xy_dev = lmax_xy;
+    return run_paths(c, B2, xx, xy, st, p, q, semantics, standardize, intercept, o, nullptr, beta, lambda_out, niter, loss, d, x);
 }
 
 // p >= n.  The reference switches to its two-GEMV iteration when nobs <= nvars (ref src/oem_dense.h:476-482); here that form is
@@ -1610,8 +668,9 @@ static int run_paths_parts(oemgpu_ctx *c, Bump B, const double *xx, const double
     } else if (split)
         split = q > 1024 && q <= 2048 && sem == OEMGPU_SEM_DENSE && path_rowcoop_workgroups(q) <= c->num_cu * 3 / 4 &&
                 !sw().OEM_NO_ROWCOOP.set && !sw().OEM_NO_SYMCOOP.set && !sw().OEM_NO_COOP.set;
-    if (!split)
-        return run_paths(c, B, xx, xy, st, p, q, sem, standardize, intercept, o, nullptr, beta, lambda_out, niter, loss, d, 1, 0, false, wd, lmax_xy);
+    PathExtras x;
+    x.wide = wd; x.lmax_xy_dev = lmax_xy;
+    if (!split) return run_paths(c, B, xx, xy, st, p, q, sem, standardize, intercept, o, nullptr, beta, lambda_out, niter, loss, d, x);
     const int nl = nl_of(o), rows = p + 1;
     const bool user = o->lambda_user && o->nlambda_user > 0;
     bool first = true;
@@ -1629,8 +688,7 @@ static int run_paths_parts(oemgpu_ctx *c, Bump B, const double *xx, const double
         std::vector<int32_t> ni((size_t)m * nl);
         double dd = 0.0;
         Bump Bp = B;                                             // (each part takes the same frame behind xy / stats)
-        const int rc = run_paths(c, Bp, xx, xy, st, p, q, sem, standardize, intercept, &os, nullptr, b.data(), lo.data(), ni.data(), ls.data(), &dd,
-                                 1, 0, false, wd, lmax_xy);
+        const int rc = run_paths(c, Bp, xx, xy, st, p, q, sem, standardize, intercept, &os, nullptr, b.data(), lo.data(), ni.data(), ls.data(), &dd, x);
         if (rc) return rc;
         for (int k = 0; k < m; ++k) {
             const size_t dst = (size_t)(*part)[k] * nl, src = (size_t)k * nl;
@@ -2017,13 +1075,6 @@ int oemgpu_last_path_engine(oemgpu_ctx *c, int32_t *engine, int32_t *persistent_
     return 0;
 }
 
-int oemgpu_last_host_path_engine(int32_t *engine)
-{
-    if (!engine) return -1;
-    *engine = g_thread_engine;
-    return 0;
-}
-
 int oemgpu_last_placement(oemgpu_ctx *c) { return c ? c->last_placement : -1; }
 
 int oemgpu_last_path_rounds(oemgpu_ctx *c, int64_t *short_rounds, int64_t *rounds)
@@ -2202,8 +1253,10 @@ static int solve_moments_batch(oemgpu_ctx *c, const double *moments, size_t mstr
         if (rc) return rc;
     }
     char *f0 = c->ws + a_0;
+    PathExtras x;
+    x.nbatch = nbatch; x.bstride = per / 8; x.shared_lmax = shared_lmax;
     return run_paths(c, B, (const double *)f0, (const double *)(f0 + o_xy), (const double *)(f0 + o_st), p, q, semantics, standardize,
-                     intercept, o, nullptr, beta, lambda_out, niter, loss, d, nbatch, per / 8, shared_lmax);
+                     intercept, o, nullptr, beta, lambda_out, niter, loss, d, x);
 }
 
 // ---------------------------------------------------------------------------------------------- xval.oem
@@ -3629,8 +2682,9 @@ int oemgpu_fit_sparse_wide_fold_res(oemgpu_ctx *c, const oemgpu_sparse_x *x, con
     }
     WideArgs wd;
     wd.xs = nullptr; wd.ys = nullptr; wd.lay = WideLayout{0, 0, 0}; wd.n = n; wd.scratch = nullptr; wd.sparse = &A;
-    rc = run_paths(c, B, nullptr, xy, st, p, p, OEMGPU_SEM_BIG, standardize, 0, o, nullptr, beta, lambda_out, niter, loss, d, 1, 0, false, &wd,
-                   standardize ? xy_std : nullptr);
+    PathExtras px;
+    px.wide = &wd; px.lmax_xy_dev = standardize ? xy_std : nullptr;
+    rc = run_paths(c, B, nullptr, xy, st, p, p, OEMGPU_SEM_BIG, standardize, 0, o, nullptr, beta, lambda_out, niter, loss, d, px);
     if (rc || !o->compute_loss) return rc;
     // oemSparse::get_loss with nobs <= nvars (ref src/oem_sparse.h:932-941): the residual of the RETURNED coefficients
     const size_t nfit = (size_t)o->npen * nl_of(o), nchunk = (size_t)((n + 2047) / 2048);

@@ -285,7 +285,7 @@ struct PathArgs {
                              // [7], [8] (row-split kernel only) OEM rounds run in the short form / in all, of penalty 0's path
     // workspace for the large-p engine
     double *work;
-    // q > 4096 on the launch-per-iteration Gram engine: sympk_doubles(q) doubles for the packed lower triangle of XX and the partial
+    // q > 1024 on the launch-per-iteration Gram engine: sympk_doubles(q) doubles for the packed lower triangle of XX and the partial
     // vectors of its products (path_large.hip: sympk_*; a buffer of the context, outside the workspace frame); null: the row-streaming product
     double *sympk;
     // nbatch > 1 (p <= SMALL_P_MAX only): blockIdx.y selects one of nbatch independent problems that share everything above
@@ -361,7 +361,7 @@ bool path_small_takes_rows(const PathArgs &a);                    // will launch
 int lds_limit_once(const void *fn, size_t bytes);
 int run_path_large(hipStream_t s, const PathArgs &a, double *host_scratch);   // any p: multi-launch engine
 size_t path_large_work_doubles(int p, int nsteps);
-size_t sympk_doubles(int q);                                      // 0 for q <= 4096
+size_t sympk_doubles(int q);                                      // 0 for q <= 1024
 int sympk_gemv_probe(hipStream_t s, const double *xx, int q, double *pk, const double *vec, double *out, int reps, double *us_per_product);
 // 288 < p <= 1024: one persistent launch of cooperating workgroups (path_coop.hip)
 bool path_coop_eligible(int q, bool has_sinv, bool compute_loss, int ngroups, int nbatch);
@@ -493,7 +493,7 @@ int launch_path_wres(hipStream_t s, const PathArgs &a, const WideArgs &wd);
 bool path_wstream_eligible(const PathArgs &a, const WideArgs &w, int G);
 int launch_path_wstream(hipStream_t s, const PathArgs &a, const WideArgs &w, int G);
 
-// opts->interrupt of the call in progress on this thread (api.hip: run_paths sets it around the engines); false if none
+// opts->interrupt of the call in progress on this thread (paths.hip: run_paths sets it around the engines); false if none
 bool caller_interrupted();
 
 // api.hip: the argument checks of the Gaussian entry points (check_opts) for other translation units

@@ -1,4 +1,4 @@
-// ctx.hpp -- the context behind the C ABI (internal to liboemgpu; api.hip owns the functions, hoststream.hip uses them).
+// ctx.hpp -- the context behind the C ABI (internal to liboemgpu; api.hip owns the functions, paths.hip and hoststream.hip use them).
 #pragma once
 
 #include "common.hpp"
@@ -68,10 +68,10 @@ struct oemgpu_ctx {
     size_t xfer_host_bytes = 0;                   // are not peers (hoststream.hip: hand_over); grow-only
     char *blob_buf = nullptr;      // the parameter blob of run_paths (grow-only, outside the workspace: it survives between calls)
     size_t blob_bytes = 0;
-    char *pack_buf = nullptr;      // q > 4096: the packed lower triangle of XX and its products' partial vectors (PathArgs::sympk; grow-only,
+    char *pack_buf = nullptr;      // q > 1024 on the launch engines: the packed lower triangle of XX and its products' partial vectors (PathArgs::sympk; grow-only,
     size_t pack_bytes = 0;         // released with the cache's other big buffers when it exceeds OEMGPU_CACHE_KEEP_BYTES)
     char *perm_buf = nullptr;      // 1024 < q <= 4096 with scattered groups: XX, XY and the column constants reordered so that every group is a run
-    size_t perm_bytes = 0;         // of neighbours (api.hip: group_run_permutation; grow-only)
+    size_t perm_bytes = 0;         // of neighbours (paths.hip: group_run_permutation; grow-only)
     const char *blob_dev = nullptr;   // where the last parameter blob was uploaded (run_paths skips an identical upload)
     size_t blob_len = 0;
     // A persistent engine that timed out (somebody else holds the CUs) is not tried again at once: the next `persistent_skip` calls
@@ -104,7 +104,17 @@ struct Bump {           // carve-out of a context buffer, 256-byte granules
 
 int ctx_reserve(oemgpu_ctx *c, size_t bytes);           // c->ws
 int ctx_grow(oemgpu_ctx *c, char **buf, size_t *have, size_t bytes);   // any grow-only device buffer of the context
+int ctx_pinned(oemgpu_ctx *c, size_t bytes);            // c->pinned
 int set_device(const oemgpu_ctx *c);
+
+struct Timer {          // a stage of a call between two events of the context's stream (oemgpu_set_timing)
+    oemgpu_ctx *c; int id;
+    Timer(oemgpu_ctx *c_, int id_) : c(c_), id(id_)
+    {
+        if (c->timing) { (void)hipEventRecord(c->ev[2 * id], c->stream); c->ev_used[id] = true; }
+    }
+    ~Timer() { if (c->timing) (void)hipEventRecord(c->ev[2 * id + 1], c->stream); }
+};
 
 // A context from the process-wide cache (created on first use, kept afterwards: no stream / workspace / pinned-memory
 // churn in the steady state of repeated host-level calls).  Contexts are checked out, so concurrent callers never share one.

@@ -752,7 +752,7 @@ bool path_coop_eligible(int q, bool has_sinv, bool compute_loss, int ngroups, in
     if (sw().OEM_NO_COOP.set || q < path_coop_min_q(ngroups > 0) || q > 1024) return false;      // OEM_NO_COOP: the launch-per-iteration engines
     if (has_sinv && compute_loss) return false;          // the loss of the un-rescaled member would need a product of its own
     if (ngroups > (q <= 512 ? 512 : 1024)) return false;
-    (void)nbatch;                                        // nbatch > 1: the caller checks that all workgroup sets fit (api.hip: run_paths)
+    (void)nbatch;                                        // nbatch > 1: the caller checks that all workgroup sets fit (paths.hip: run_paths)
     return true;
 }
 

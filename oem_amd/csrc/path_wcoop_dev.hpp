@@ -394,7 +394,7 @@ __device__ __forceinline__ double wc_op(double u, double tp, const WThr &c)
 // ACC: Nesterov's step.  GEN: a group penalty in the call.  A group's norm needs u of all its members: one more exchange per iteration, of the members of this
 // workgroup's own groups (wc_gather_u_list); every lane then forms the factor of its column's group.  The group tables live in LDS.
 // cstart (GEN only, or null): the columns of workgroup g are [cstart[g], cstart[g + 1]) -- at most 4 CW of them, cut at group
-// boundaries by the host (api.hip) when every group is a run of neighbouring columns: then no group reaches into another workgroup
+// boundaries by the host (paths.hip: plan_paths) when every group is a run of neighbouring columns: then no group reaches into another workgroup
 // and the exchange of u has nobody to serve.  Null: 4 CW columns each.
 }  // namespace
 

@@ -17,7 +17,7 @@ namespace {
 // accumulator value costs two v_accvgpr_read_b32 on its way into an FMA, in each of the two products; everything else -- the
 // all-reduce of the n-vector, the state machine, the eigenvalue step -- is path_wcoop_kernel's.  Element-wise operators and
 // compute.loss; one workgroup set (the penalties in turn); up to WRES_GMAX workgroups, i.e. MORE than three quarters of the CUs:
-// the exchanges are bounded and a timeout sends the call to the launch-per-iteration engine as everywhere (api.hip: run_paths).
+// the exchanges are bounded and a timeout sends the call to the launch-per-iteration engine as everywhere (paths.hip: run_paths).
 __device__ __forceinline__ double wc_uni(double v)              // a wave-uniform value into scalar registers
 {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(WNTH) void path_wres_kernel(PathArgs A, const doubl
         A.d_out[2] = (double)(__builtin_amdgcn_s_memtime() - t_cyc0);
         A.d_out[3] = (double)(__builtin_amdgcn_s_memrealtime() - t_rt0);
     }
-    if (__syncthreads_or(X.failed ? 1 : 0) && tid == 0) A.d_out[6] = 1.0;          // exchange timeout: poison (api.hip: run_paths falls back)
+    if (__syncthreads_or(X.failed ? 1 : 0) && tid == 0) A.d_out[6] = 1.0;          // exchange timeout: poison (paths.hip: run_paths falls back)
 }
 
 // ================================================================================================
@@ -708,7 +708,7 @@ size_t path_wres_xchg_doubles(int n, int p)
     return 2 * ((size_t)G * G * SL * 2) + 2 * ((size_t)L.npad() * 2) + 64;
 }
 // Where the VGPR-only form (path_wcoop_kernel) cannot hold Xs: element-wise operators, one instance.  max_wg: what this device may
-// keep resident at once (api.hip: all CUs but a few).  OEM_NO_WRES=1: the streamed / launch-per-iteration engines; OEM_WRES=1:
+// keep resident at once (paths.hip: all CUs but a few).  OEM_NO_WRES=1: the streamed / launch-per-iteration engines; OEM_WRES=1:
 // also where path_wcoop_kernel would have run (tests).
 bool path_wres_eligible(const PathArgs &a, const WideArgs &wd, int max_wg)
 {

@@ -91,7 +91,7 @@ def test_group_operators_in_the_head_of_the_packed_triangle_pairs(oa, p, layout,
     instead of the product + slot sum + single-workgroup update kernel.  'runs': groups of 1 .. 32 neighbouring coordinates in a random
     order of sizes (they straddle the workgroups' 32-coordinate blocks), group 0 unpenalised, weights, penalty factors, every group kind
     with a lasso beside them; 'scattered': the same sizes dealt at random over the coordinates of an odd ragged q -- reordered into runs
-    first (api.hip: group_run_permutation, beyond 4096 where every group has <= 32 members); 'launches below 4096': what the register
+    first (paths.hip: group_run_permutation, beyond 4096 where every group has <= 32 members); 'launches below 4096': what the register
     engine's second attempt runs (OEM_NO_SYMCOOP=1).  Against the oracle; the same bits run to run; groups of 40 and (scattered) 90 members on
     the wider windows, groups of 120 on the update-kernel form."""
     import torch

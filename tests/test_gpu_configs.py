@@ -407,7 +407,7 @@ def test_nesterov_step_on_the_one_exchange_engine(oa, p, monkeypatch):
 def test_scattered_groups_stay_on_the_register_resident_engine(oa, p):
     """1024 < q <= 4096 with groups that are NOT runs of neighbouring coordinates (dealt round robin: the members of a group are 75 / 100
     coordinates apart; group 0 unpenalised, custom weights, penalty factors): the coordinates are reordered group by group, the path solved
-    on path_symcoop_kernel<.., GEN> and the coefficients put back (api.hip: group_run_permutation) -- until round 6 such calls ran the
+    on path_symcoop_kernel<.., GEN> and the coefficients put back (paths.hip: group_run_permutation) -- until round 6 such calls ran the
     launch-per-iteration engines at 3-10 x the time per iteration; the reference has no cliff between group layouts (ref
     src/oem_dense.h:421-456, 193-315).  oem.xtx (+ scale.factor) and oem() with standardisation and an intercept, against the oracle."""
     import torch

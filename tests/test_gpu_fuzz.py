@@ -626,7 +626,7 @@ def test_random_register_resident_symmetric_engine(oa, seed):
 @pytest.mark.parametrize("seed", list(range(170, 173)) + list(range(97000, 97000 + 3 * (SCALE - 1))))
 def test_random_scattered_groups_on_the_register_resident_engine(oa, seed):
     """oem.xtx at a random 1024 < p <= 4096 with group penalties whose groups are NOT runs of neighbouring coordinates (sizes 1-400 in a
-    random layout, group 0 unpenalised, weights, penalty factors, now and then `scale.factor`): reordered into runs (api.hip:
+    random layout, group 0 unpenalised, weights, penalty factors, now and then `scale.factor`): reordered into runs (paths.hip:
     group_run_permutation), solved on path_symcoop_kernel<.., GEN>, put back -- against the oracle (d handed over), also where there are
     fewer runs than workgroups (some owners own nothing)."""
     import torch

@@ -294,7 +294,7 @@ def test_handover_staged_through_the_host():
 @pytest.mark.gpu
 def test_concurrent_callers_of_the_cooperating_wide_engine(oa):
     """five host threads fit p >= n problems at once, each through ONE persistent launch of 63 cooperating workgroups per penalty set
-    (path_wcoop.hip): the callers queue for CU slots (api.hip: CoopSlots -- all workgroups of all such kernels in flight must be
+    (path_wcoop.hip): the callers queue for CU slots (paths.hip: CoopSlots -- all workgroups of all such kernels in flight must be
     resident), nobody times out, and every thread gets the bits of the same call made alone"""
     import threading, warnings
     rng = np.random.default_rng(17)

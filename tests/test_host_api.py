@@ -227,7 +227,7 @@ def test_moment_plan_deals_the_tile_columns_into_eights_sixes_and_a_four():
         assert lo - 0.1 <= rounds <= hi + 0.1, (n, p, rounds)
 
 
-# ---------------------------------------------------------------------------------------------- the engine plan (api.hip: plan_paths)
+# ---------------------------------------------------------------------------------------------- the engine plan (paths.hip: plan_paths)
 _ENGINES = api.ENGINES
 _SEM_DENSE, _SEM_BIG, _SEM_XTX, _SEM_XVAL = 0, 1, 2, 3
 
@@ -294,7 +294,7 @@ def test_the_plan_puts_the_cooperating_engine_on_one_xcd_only_where_its_instance
 
 
 def test_scattered_groups_are_reordered_into_runs():
-    """api.hip: group_run_permutation (host arithmetic): groups of <= 32 members that are not runs of neighbouring coordinates are made runs --
+    """paths.hip: group_run_permutation (host arithmetic): groups of <= 32 members that are not runs of neighbouring coordinates are made runs --
     groups in the order of their first member, members in their own order, ungrouped coordinates where they stood between them -- so that
     the register-resident engine at 1024 < q <= 4096 takes them (ref src/oem_dense.h:421-456: the reference knows no group layout)."""
     import ctypes as C
