@@ -285,6 +285,51 @@ int oemgpu_fit_dense_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, i
  * p > OEMGPU_RM_P_MAX. */
 int oemgpu_selftest_gram_rm_plan(int64_t n, int32_t p, int32_t num_cu, int64_t *out /* 8 */);
 
+/* Many responses on one resident x: the m fits oemgpu_fit_dense_dev(ctx, x, ..., Y[:, r], ...) returns for r = 0 .. m - 1, from TWO reads
+ * of x.  It replaces the loop of m such calls -- the only way so far, and what sklearn.linear_model.Lasso does with a 2-D y -- in
+ * which every call runs the whole moment pass again although the Gram block, the column sums and the row count of the moment buffer
+ * above depend on x alone: here ONE moment pass about 0 (response 0 riding as y; up to p = OEMGPU_RM_P_MAX the row-major pass's summation order whichever way x
+ * lies, so that the fits are the same bytes from every layout of x; beyond, oemgpu_moments_dev's), ONE X'Y pass that forms sum_i x_ij y_ir, sum_i y_ir^2
+ * and sum_i y_ir of every response on the FP64 MFMA in a fixed order (no atomics: two calls return the same bytes, and the three
+ * layouts of x the same bytes for the same values), and the paths of up to 513 responses side by side in one launch (one workgroup
+ * or one cooperating workgroup set per response, all the waiting workgroups of a launch within 3/4 of the CUs), every response with
+ * the lambda grid of its own X'y; a user lambda grid is shared by all responses.
+ * y_dev is float64, element (i, r) at y_dev[i * y_rs + r * y_cs] with either y_cs == 1 && y_rs >= m (a row-major n x m matrix) or
+ * y_rs == 1 && y_cs >= n (a column-major one); nothing in the padding of x or y and nothing past element (n - 1, m - 1) is read.
+ * Outputs (host): beta[m][npen][nl][p + 1], lambda_out / niter / loss [m][npen][nl], d[m], and route[m]: 0 the response was solved
+ * in a batched launch, 1 one by one from its composed moment buffer (p > 1024, the cooperating engine switched off, or a device too
+ * small for one cooperating set), 2 fitted again by the route of oemgpu_fit_dense_dev -- the sample pass and the shifted pass --
+ * because its solve advised a shift (oemgpu_last_shift_advised: then x itself advises for every response, or this response does).
+ * n > p only: n <= p (the shapes of the p >= n engines) is OEMGPU_ERR_UNSUPPORTED, as is p > OEMGPU_RM_P_MAX on a row-major x;
+ * OEMGPU_ERR_ARG before any device is looked for: a NULL pointer, m < 1, a stride pair that is neither form, ld < n, ldr < p, a dtype
+ * outside {0, 1}; opts.interrupt is polled between the batched launches (OEMGPU_ERR_INTERRUPTED). */
+int oemgpu_fit_dense_multi_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p,
+                               const double *y_dev, int64_t y_rs, int64_t y_cs, int32_t m,
+                               int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                               double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int32_t *route);
+/* The same on a row-major x read where it lies (the x arguments of oemgpu_fit_dense_rm_dev; float32 widened in the register): it
+ * replaces the loop of m oemgpu_fit_dense_rm_dev calls. */
+int oemgpu_fit_dense_multi_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p,
+                                  const double *y_dev, int64_t y_rs, int64_t y_cs, int32_t m,
+                                  int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                                  double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int32_t *route);
+/* Host-only plan of the two calls above (pure arithmetic, runs without a GPU; the calls take their shape from the same function) for
+ * n rows, p columns, m responses and npen element-wise penalties of 100 lambdas on a device of num_cu CUs; layout 0: column-major x, 1: row-major.
+ * out[0] rows per chunk of the X'Y pass (a multiple of 64), [1] row chunks (none empty), [2] responses per block of the X'Y kernel
+ * (16, 32 or 64), [3] X'Y passes = response blocks = reads of x by that kernel, [4] responses per batched launch at most (1 where
+ * they are solved one by one), [5] batched launches (or single solves), [6] the batch engine (OEMGPU_ENGINE_ROWS or
+ * OEMGPU_ENGINE_COOP; 0: one by one), [7] device bytes of the call's buffers (base moments, one response column, chunk partials, the
+ * composed buffers of one launch) plus the workspace reserved for the passes and the paths.
+ * OEMGPU_ERR_ARG for n, p, m, npen, num_cu < 1, a layout outside {0, 1} or a NULL out; OEMGPU_ERR_UNSUPPORTED for n <= p and for
+ * p > OEMGPU_RM_P_MAX with layout 1.  It stands where oemgpu_selftest_gram_rm_plan stands for the row-major pass. */
+int oemgpu_selftest_multi_plan(int64_t n, int32_t p, int32_t m, int32_t npen, int32_t layout, int32_t num_cu, int64_t *out /* 8 */);
+/* Test infrastructure: the moment pass, the X'Y pass and the composition of the two calls above alone (nothing is fitted, n <= p is
+ * fine): moments_out_dev[m][(p + 2)^2] (device) <- buffer r = the moment buffer about 0 of (x, Y[:, 0]) with M[p, j], M[p, p],
+ * M[p + 1, p] and their mirror images replaced by response r's.  dtype < 0: x_dev is column-major float64 with column stride ld;
+ * else row-major of that dtype with row stride ld.  It replaces m calls of oemgpu_moments_dev / oemgpu_moments_rm_dev. */
+int oemgpu_selftest_multi_moments_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ld, int32_t p,
+                                      const double *y_dev, int64_t y_rs, int64_t y_cs, int32_t m, double *moments_out_dev);
+
 /* oemgpu_fit_dense_weighted with X, y and the weights already on the device. */
 int oemgpu_fit_dense_weighted_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
                                   const double *weights_dev, int32_t standardize, int32_t intercept, const oemgpu_opts *opts,

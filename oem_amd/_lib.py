@@ -120,6 +120,14 @@ _SIGS = {
     "oemgpu_fit_dense_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
                                           C.c_int32, C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_selftest_gram_rm_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    # many responses on one x: the loop of m oemgpu_fit_dense_dev / _rm_dev calls (sklearn's Lasso with a 2-D y)
+    "oemgpu_fit_dense_multi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                             C.c_int32, C.c_int32, C.POINTER(OemgpuOpts)] + _OUT + [_ip]),
+    "oemgpu_fit_dense_multi_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+                                                C.c_int32, C.c_int32, C.c_int32, C.POINTER(OemgpuOpts)] + _OUT + [_ip]),
+    "oemgpu_selftest_multi_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "oemgpu_selftest_multi_moments_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+                                                    C.c_int32, C.c_void_p]),
     "oemgpu_fit_xtx_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _dp, C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_last_shift_in_effect": (C.c_int, [C.c_void_p]),
     "oemgpu_last_shift_advised": (C.c_int, [C.c_void_p]),

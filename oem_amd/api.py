@@ -598,6 +598,116 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
     return _decorate(a, penalty, varnames, True, n, p)
 
 
+class _OneOfMany:
+    """The outputs of response r of a many-response call, as _decorate reads an _Args"""
+
+    def __init__(self, beta, lam_out, niter, loss, d):
+        self.beta, self.lam_out, self.niter, self.loss, self.d = beta, lam_out, niter, loss, C.c_double(float(d))
+
+
+def _device_responses(Y, device):
+    """Y (n x m) as the many-response entries read it: (tensor, row stride, column stride).  A float64 device tensor with a unit stride
+    in one dimension (and the other at least the extent it steps over) is read where it lies; any other device tensor is converted
+    once, a host array uploaded once."""
+    import torch
+    Yd = Y if _is_torch_cuda(Y) else torch.as_tensor(np.ascontiguousarray(np.asarray(Y, dtype=np.float64)), device=device)
+    if Yd.device != device:
+        Yd = Yd.to(device)
+    n, m = Yd.shape
+    rs, cs = Yd.stride()
+    if Yd.dtype != torch.float64 or not ((cs == 1 and rs >= m) or (rs == 1 and cs >= n)):
+        Yd = Yd.to(torch.float64).contiguous()
+        rs, cs = Yd.stride()
+        if not (cs == 1 and rs >= m):                                  # (n x 1 contiguous has strides (1, 1))
+            rs, cs = m, 1
+    return Yd, int(rs), int(cs)
+
+
+def multi_plan(n, p, m, npen=1, layout=0, num_cu=256):
+    """oemgpu_selftest_multi_plan (pure host arithmetic) as a dict"""
+    out = (C.c_int64 * 8)()
+    L.check(L.lib().oemgpu_selftest_multi_plan(int(n), int(p), int(m), int(npen), int(layout), int(num_cu), out))
+    keys = ["rows", "row_chunks", "block", "passes", "cap", "solve_chunks", "engine", "bytes"]
+    return dict(zip(keys, [int(v) for v in out]))
+
+
+def multi_moments(x, Y):
+    """Test infrastructure: oemgpu_selftest_multi_moments_dev -> the m composed moment buffers, numpy [m, p + 2, p + 2] indexed
+    [r, i, j] = M_r[i, j].  x: a torch device tensor, read where it lies when it is column-major float64 or row-major float64 / float32."""
+    import torch
+    if not _is_torch_cuda(x) or x.ndim != 2:
+        raise ValueError("x must be a 2-D torch tensor on a GPU")
+    n, p = x.shape
+    if x.dtype == torch.float64 and x.stride(0) == 1 and x.stride(1) >= n:
+        code, ld = -1, x.stride(1)
+    else:
+        code, ld = _rowmajor_dtype(x), x.stride(0)
+        if code is None:
+            raise ValueError("x must be column-major float64, or row-major float64 / float32 with unit column stride")
+    Yd, rs, cs = _device_responses(Y, x.device)
+    m = Yd.shape[1]
+    out = torch.full((m, p + 2, p + 2), float("nan"), dtype=torch.float64, device=x.device)
+    ctx = context(x.device.index)
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_selftest_multi_moments_dev(ctx, x.data_ptr(), code, n, ld, p, Yd.data_ptr(), rs, cs, m, out.data_ptr()))
+    return out.cpu().numpy().transpose(0, 2, 1).copy()                # (the buffers are column-major)
+
+
+def oem_multi(x, Y, family="gaussian", weights=(), ngpus=0, devices=None, **kw):
+    """m responses on one resident x: [oem(x, Y[:, r], **kw) for r in range(m)] from two reads of x -- one moment pass, one X'Y pass
+    (multi.hip) -- and the paths of up to 513 responses per launch (include/oemgpu.h: oemgpu_fit_dense_multi_dev).  x: a torch device
+    tensor, n x p with n > p, taken as oem() takes it (row-major float64 / float32 read in place, else column-major float64).
+    Y: n x m, a torch device tensor (float64 with a unit stride in one dimension: read where it lies) or a host array (uploaded once).
+    oem()'s keyword arguments and checks; a user lambda is shared by all responses.  Returns a list of m OemFit, each with one more key,
+    `route`: 0 solved in a batched launch, 1 one by one from its composed moments, 2 fitted again about a shift (oem()'s own route)."""
+    if getattr(Y, "ndim", None) != 2:
+        raise ValueError("Y must be a matrix of n rows and one column per response")
+    if family != "gaussian":
+        if family == "binomial":
+            raise ValueError("family='binomial' is outside the dense Gaussian hot path (ref src/oem_logistic_dense.cpp)")
+        raise ValueError("'arg' should be one of 'gaussian', 'binomial'")
+    if len(weights) > 0:
+        raise ValueError("weights not implemented yet.")
+    if ngpus or devices is not None:
+        raise ValueError("oem_multi(): the rows of a resident x are not split over devices (ngpus / devices)")
+    host_or_sparse = "oem_multi() takes a dense torch tensor on a GPU: a host or sparse x is fitted one response at a time with oem()"
+    if isinstance(x, SparseX) or _is_scipy_sparse(x) or _is_torch_sparse(x):
+        raise ValueError(host_or_sparse)
+    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("x must have at least two columns")
+    n, p = x.shape
+    if Y.shape[0] != n:
+        raise ValueError("x and y lengths do not match")
+    m = int(Y.shape[1])
+    if m < 1:
+        raise ValueError("Y must have at least one column")
+    if n <= p:
+        raise ValueError("oem_multi() serves n > p only: with n <= p fit each column with oem(x, Y[:, r])")
+    if not _is_torch_cuda(x):
+        raise ValueError(host_or_sparse)
+    penalty =_match_penalty(kw.pop("penalty", None))
+    a, varnames, standardize, intercept = oem(x, Y, penalty=penalty, _args_only=True, **kw)
+    import torch
+    X = _DeviceX(x, _rowmajor_in_place)
+    Yd, rs, cs = _device_responses(Y, x.device)
+    beta = np.zeros((m, a.npen, a.nl, p + 1))
+    lam_out = np.zeros((m, a.npen, a.nl))
+    niter = np.zeros((m, a.npen, a.nl), dtype=np.int32)
+    loss = np.zeros((m, a.npen, a.nl))
+    d = np.zeros(m)
+    route = np.zeros(m, dtype=np.int32)
+    ctx = context(x.device.index)
+    torch.cuda.current_stream(x.device).synchronize()
+    X.call("fit_dense_multi", ctx, Yd.data_ptr(), rs, cs, m, int(standardize), int(intercept), C.byref(a.c),
+           _dptr(beta), _dptr(lam_out), _iptr(niter), _dptr(loss), _dptr(d), _iptr(route))
+    fits = []
+    for r in range(m):
+        fit = _decorate(_OneOfMany(beta[r], lam_out[r], niter[r], loss[r], d[r]), penalty, varnames, True, n, p)
+        fit["route"] = int(route[r])
+        fits.append(fit)
+    return fits
+
+
 def oem_fit_sparse(x, y, **kw):
     """`.Call("oem_fit_sparse", ...)` (ref src/oem_sparse.cpp:30-267), the entry oem() reaches with a sparse x, with oem()'s arguments
     and result.  x: a scipy.sparse matrix (oem()'s own route: oemgpu_fit_sparse), a SparseX of any shape (oemgpu_fit_sparse_res: the

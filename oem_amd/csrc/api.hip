@@ -4,6 +4,7 @@
 // kernels of gram.hip / path_small.hip / path_large.hip; there is no CPU fallback.
 #include "paths.hpp"
 #include "dense_src.hpp"
+#include "multi.hpp"
 #include "logistic.hpp"     // oemgpu_sparse_x
 
 #include <atomic>
@@ -261,19 +262,26 @@ static int rm_p_refusal(const char *who, int32_t p)
     return OEMGPU_ERR_UNSUPPORTED;
 }
 
-int dense_src_moment_plan(const char *who, const oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, MomentPlan *pl)
+// (by the CU count alone: the host-only plans have no context)
+static int moment_plan_cus(const char *who, int num_cu, bool colmajor, int64_t n, int32_t p, MomentPlan *pl)
 {
     Bump B;
-    if (X.colmajor()) {
-        pl->cm = gram_plan(n, p, c->num_cu);
+    if (colmajor) {
+        pl->cm = gram_plan(n, p, num_cu);
         B.take(pl->cm.tpart_doubles * 8); B.take(pl->cm.vpart_doubles * 8);
     } else {
         if (int rc = rm_p_refusal(who, p)) return rc;
-        pl->rm = gram_rm_plan(n, p, c->num_cu);
+        pl->rm = gram_rm_plan(n, p, num_cu);
         B.take(pl->rm.tpart_doubles * 8);
     }
     pl->scratch_bytes = B.off;
     return 0;
+}
+
+int dense_src_moment_plan(const char *who, const oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, MomentPlan *pl)
+{
+    if (!X.colmajor()) if (int rc = rm_p_refusal(who, p)) return rc;      // (before the context is looked at)
+    return moment_plan_cus(who, c->num_cu, X.colmajor(), n, p, pl);
 }
 
 int dense_src_moments(oemgpu_ctx *c, const MomentPlan &pl, const DenseSrc &X, int64_t n, const double *y, const double *sums, char *scratch,
@@ -1229,6 +1237,18 @@ static __global__ void moment_diag_kernel(const double *__restrict__ M, int p, d
     if (j < p) diag[j] = M[(size_t)j * (p + 2) + j];
 }
 
+// the frame of one instance of solve_moments_batch (xx | xy | stats), and the workspace a batch of `nbatch` reserves
+static size_t batch_instance_bytes(int p, int q)
+{
+    return ((size_t)q * q * 8 + 255) / 256 * 256 + ((size_t)q * 8 + 255) / 256 * 256 + ((size_t)stats_len(p) * 8 + 255) / 256 * 256;
+}
+static size_t batch_ws_bytes(int p, int q, const oemgpu_opts *o, int nbatch)
+{
+    Bump B;
+    B.take(batch_instance_bytes(p, q) * nbatch);
+    return B.off + paths_ws_bytes(p, q, o, nbatch) + 4096;
+}
+
 // nbatch moment buffers (instance b at moments + b * mstride, all OUTSIDE the context workspace), one finalize each, then ONE
 // launch that walks all their paths side by side (q <= SMALL_P_MAX).  Outputs as in run_paths.
 // cs != nullptr: observation weights -- the moments are those of the p + 1 data columns [sqrt(w) | sqrt(w) X] ((p + 3)^2 each) and
@@ -1236,13 +1256,13 @@ static __global__ void moment_diag_kernel(const double *__restrict__ M, int p, d
 static int solve_moments_batch(oemgpu_ctx *c, const double *moments, size_t mstride, int nbatch, int32_t p, int32_t semantics,
                                int32_t standardize, int32_t intercept, const oemgpu_opts *o,
                                double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, bool shared_lmax,
-                               const double *cs = nullptr, size_t cstride = 0)
+                               const double *cs = nullptr, size_t cstride = 0, int32_t *shift_advised = nullptr)
 {
     const int q = p + ((semantics != OEMGPU_SEM_DENSE && intercept) ? 1 : 0);
     Bump B;
-    const size_t per = ((size_t)q * q * 8 + 255) / 256 * 256 + ((size_t)q * 8 + 255) / 256 * 256 + ((size_t)stats_len(p) * 8 + 255) / 256 * 256;
+    const size_t per = batch_instance_bytes(p, q);
     const size_t a_0 = B.take(per * nbatch);
-    if (ctx_reserve(c, B.off + paths_ws_bytes(p, q, o, nbatch) + 4096)) return OEMGPU_ERR_HIP;
+    if (ctx_reserve(c, batch_ws_bytes(p, q, o, nbatch))) return OEMGPU_ERR_HIP;
     const size_t o_xy = ((size_t)q * q * 8 + 255) / 256 * 256, o_st = o_xy + ((size_t)q * 8 + 255) / 256 * 256;
     for (int b = 0; b < nbatch; ++b) {
         char *f = c->ws + a_0 + per * b;
@@ -1254,7 +1274,7 @@ static int solve_moments_batch(oemgpu_ctx *c, const double *moments, size_t mstr
     }
     char *f0 = c->ws + a_0;
     PathExtras x;
-    x.nbatch = nbatch; x.bstride = per / 8; x.shared_lmax = shared_lmax;
+    x.nbatch = nbatch; x.bstride = per / 8; x.shared_lmax = shared_lmax; x.shift_advised_out = shift_advised;
     return run_paths(c, B, (const double *)f0, (const double *)(f0 + o_xy), (const double *)(f0 + o_st), p, q, semantics, standardize,
                      intercept, o, nullptr, beta, lambda_out, niter, loss, d, x);
 }
@@ -1273,6 +1293,211 @@ static int ctx_aux(oemgpu_ctx *c, size_t bytes)
     if (c->aux) { OEM_HIP(hipStreamSynchronize(c->stream)); OEM_HIP(hipFree(c->aux)); c->aux = nullptr; c->aux_bytes = 0; }
     OEM_HIP(hipMalloc((void **)&c->aux, bytes)); ++g_alloc_count;
     c->aux_bytes = bytes;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- many responses on one x (multi.hip)
+// How many responses one batched launch takes, and on which engine: plan_paths' rules for nbatch > 1, read from the side of the caller
+// who chooses nbatch.  Never more than 513 instances (the most the batch launch has been run at: xval.oem with 512 folds); and wherever
+// an instance is more than one workgroup -- the cooperating engine's set, the four workgroups per penalty of path_small.hip at
+// 208 < q <= 288 -- those workgroups wait for each other, so all of a launch together stay within 3/4 of the CUs.  (The cooperating
+// engine splits the penalties over sets of their own only while instances x penalties x workgroups <= half the CUs, plan_paths'
+// pen_split rule, so the factor npen never breaks the bound there; path_small.hip always splits.)  Engine 0: no batch engine takes
+// the shape -- q > 1024, the cooperating engine switched off beyond 288, or fewer CUs than one set needs -- and the responses are
+// solved one after another.
+struct MultiSolve { int cap = 1, engine = OEMGPU_ENGINE_NONE; };
+static MultiSolve multi_solve_plan(int num_cu, int q, int npen, int ngroups)
+{
+    MultiSolve S;
+    const int cus = num_cu * 3 / 4;
+    int cap = 0, engine = OEMGPU_ENGINE_NONE;
+    if (path_coop_eligible(q, false, false, ngroups, 2)) { cap = cus / path_coop_workgroups(q); engine = OEMGPU_ENGINE_COOP; }
+    else if (q <= 208) { cap = 513; engine = OEMGPU_ENGINE_ROWS; }                     // (path_small_takes_rows: one workgroup per instance and penalty, which waits for nobody)
+    else if (q <= SMALL_P_MAX) { cap = cus / (4 * (npen > 1 ? npen : 1)); engine = OEMGPU_ENGINE_ROWS; }
+    if (cap >= 1) { S.cap = cap < 513 ? cap : 513; S.engine = engine; }
+    return S;
+}
+
+// The buffers of the call in oemgpu_ctx::aux -- the one moment buffer, one response as a contiguous vector, the chunk partials of the
+// X'Y pass, the composed buffers of ONE batched launch -- and the workspace reserved once for the passes and the largest launch.
+struct MultiLay {
+    MultiPlan xp;
+    MultiSolve sv;
+    MomentPlan mp;
+    bool one_order = false;
+    int nsolve = 0;
+    size_t a_base = 0, a_col = 0, a_part = 0, a_comp = 0, total = 0, ws = 0;
+};
+static int multi_layout(const char *who, int num_cu, bool colmajor, int64_t n, int32_t p, int32_t m, const oemgpu_opts *o, bool solve, MultiLay *L)
+{
+    // The Gram block of every layout from ONE summation order wherever there is one: gram_rm.hip's pass, which reads a column-major x
+    // too (its CM form), up to its p; beyond, a column-major x keeps gram.hip's pass (a row-major one is refused there)
+    L->one_order = !colmajor || p <= GRAM_RM_P_MAX;
+    if (int rc = moment_plan_cus(who, num_cu, !L->one_order, n, p, &L->mp)) return rc;
+    L->xp = multi_plan(n, p, m, num_cu);
+    const size_t mlen = (size_t)oemgpu_moments_len(p) * 8;
+    Bump A;
+    L->a_base = A.take(mlen); L->a_col = A.take((size_t)n * 8); L->a_part = A.take(L->xp.part_doubles * 8);
+    L->ws = L->mp.scratch_bytes + 4096;
+    if (solve) {
+        L->sv = multi_solve_plan(num_cu, p, o->npen, any_grp_count(o));
+        L->nsolve = (m + L->sv.cap - 1) / L->sv.cap;
+        const int nb = m < L->sv.cap ? m : L->sv.cap;
+        L->a_comp = A.take(mlen * nb);
+        const size_t w = L->sv.engine != OEMGPU_ENGINE_NONE ? batch_ws_bytes(p, p, o, nb) : moments_solve_ws(0, 0, p, o);
+        if (w > L->ws) L->ws = w;
+    }
+    L->total = A.off;
+    return 0;
+}
+
+static int multi_y_check(const char *who, int64_t n, int64_t rs, int64_t cs, int32_t m)
+{
+    if (m < 1) { set_error("%s: m < 1 (at least one response)", who); return OEMGPU_ERR_ARG; }
+    if (!((cs == 1 && rs >= m) || (rs == 1 && cs >= n))) {
+        set_error("%s: y strides (%lld, %lld) are neither a row-major n x m matrix (y_cs == 1, y_rs >= m) nor a column-major one (y_rs == 1, y_cs >= n)",
+                  who, (long long)rs, (long long)cs);
+        return OEMGPU_ERR_ARG;
+    }
+    return 0;
+}
+
+// the one moment pass about 0 (response 0 riding as y) into `base`, the X'Y pass into `part`
+static int multi_passes(oemgpu_ctx *c, const MultiLay &L, const DenseSrc &X, const MultiY &Y)
+{
+    char *ax = c->aux;
+    double *col = (double *)(ax + L.a_col);
+    const double *y0 = Y.y;
+    int rc = 0;
+    if (Y.rs != 1) { if ((rc = launch_multi_column(c->stream, Y, L.xp.n, 0, col))) return rc; y0 = col; }
+    Timer t(c, OEMGPU_T_MOMENTS);                                    // (both passes over x: the moment build of this call)
+    if (L.one_order) {
+        {
+            Timer tk(c, OEMGPU_T_GRAMK);
+            if ((rc = launch_gram_rm(c->stream, L.mp.rm, X.x, X.colmajor() ? -1 : X.dtype, L.xp.n, X.ld, y0, nullptr, (double *)c->ws))) return rc;
+        }
+        if ((rc = launch_gram_rm_reduce(c->stream, L.mp.rm, (const double *)c->ws, (double *)(ax + L.a_base)))) return rc;
+    } else if ((rc = dense_src_moments(c, L.mp, X, L.xp.n, y0, nullptr, c->ws, (double *)(ax + L.a_base)))) return rc;
+    return launch_multi_xty(c->stream, L.xp, X, Y, (double *)(ax + L.a_part));
+}
+
+// oem() for every column of Y on one dense x, wherever it lies: one moment pass about 0, one X'Y pass, the paths in batched launches
+// (route 0) or one by one (1); a response whose solve advises a shift is fitted again by fit_dense_src (2)
+static int fit_dense_multi_src(const char *who, oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const double *y_dev, int64_t rs, int64_t cs,
+                               int32_t m, int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                               double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int32_t *route)
+{
+    int rc = src_args_check(who, c, X, n, p, y_dev, beta && lambda_out && niter && loss && d && route);
+    if (!rc) rc = multi_y_check(who, n, rs, cs, m);
+    if (!rc) rc = check_opts(o, p, p);
+    if (rc) return rc;
+    if (n <= p) {
+        set_error("%s: %lld x %d has n <= p, a shape of the p >= n engines, which this call does not serve: such responses are fitted one at a "
+                  "time (oemgpu_fit_dense_dev)", who, (long long)n, p);
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    if (!X.colmajor()) if ((rc = rm_p_refusal(who, p))) return rc;      // (before the context is looked at)
+    MultiLay L;
+    if ((rc = multi_layout(who, c->num_cu, X.colmajor(), n, p, m, o, true, &L))) return rc;
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    ctx_void_cv(c);
+    if (ctx_aux(c, L.total)) return OEMGPU_ERR_HIP;
+    if (ctx_reserve(c, L.ws)) return OEMGPU_ERR_HIP;                 // once, for the passes and the largest launch
+    const MultiY Y{y_dev, rs, cs};
+    if ((rc = multi_passes(c, L, X, Y))) return rc;
+    const double *base = (const double *)(c->aux + L.a_base), *part = (const double *)(c->aux + L.a_part);
+    double *comp = (double *)(c->aux + L.a_comp), *col = (double *)(c->aux + L.a_col);
+    const size_t nk = (size_t)o->npen * nl_of(o), blen = nk * (size_t)(p + 1), mlen = (size_t)oemgpu_moments_len(p);
+    auto interrupted = [&]() {
+        if (!(o->interrupt && o->interrupt(o->interrupt_arg))) return false;
+        set_error("interrupted by the caller");
+        return true;
+    };
+    std::vector<int32_t> adv(m, 0);
+    for (int r0 = 0; r0 < m; r0 += L.sv.cap) {
+        const int nb = m - r0 < L.sv.cap ? m - r0 : L.sv.cap;
+        if (r0 > 0 && interrupted()) return OEMGPU_ERR_INTERRUPTED;
+        if ((rc = launch_multi_compose(c->stream, L.xp, base, part, r0, nb, comp))) return rc;
+        if (L.sv.engine != OEMGPU_ENGINE_NONE) {
+            rc = solve_moments_batch(c, comp, mlen, nb, p, OEMGPU_SEM_DENSE, standardize, intercept, o, beta + blen * r0, lambda_out + nk * r0,
+                                     niter + nk * r0, loss + nk * r0, d + r0, false, nullptr, 0, adv.data() + r0);
+            for (int b = 0; b < nb; ++b) route[r0 + b] = 0;
+        } else {
+            rc = solve_moments_impl(c, comp, nullptr, p, OEMGPU_SEM_DENSE, standardize, intercept, o, beta + blen * r0, lambda_out + nk * r0,
+                                    niter + nk * r0, loss + nk * r0, d + r0, nullptr);
+            adv[r0] = c->shift_advised ? 1 : 0;
+            route[r0] = 1;
+        }
+        if (rc) return rc;
+    }
+    // the shift predicate looks at x AND y (finalize_kernel): if x advises, every response does; else only those whose own y does
+    for (int r = 0; r < m; ++r) {
+        if (!adv[r]) continue;
+        if (interrupted()) return OEMGPU_ERR_INTERRUPTED;
+        const double *yr = y_dev + (int64_t)r * cs;
+        if (rs != 1) { if ((rc = launch_multi_column(c->stream, Y, n, r, col))) return rc; yr = col; }
+        if ((rc = fit_dense_src(who, c, X, n, p, yr, standardize, intercept, o, beta + blen * r, lambda_out + nk * r, niter + nk * r, loss + nk * r, d + r)))
+            return rc;
+        route[r] = 2;
+    }
+    return 0;
+}
+
+int oemgpu_fit_dense_multi_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev, int64_t y_rs, int64_t y_cs,
+                               int32_t m, int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                               double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int32_t *route)
+{
+    return fit_dense_multi_src("fit_dense_multi", c, dense_src_cm(x_dev, ld), n, p, y_dev, y_rs, y_cs, m, standardize, intercept, o, beta, lambda_out,
+                               niter, loss, d, route);
+}
+
+int oemgpu_fit_dense_multi_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev, int64_t y_rs,
+                                  int64_t y_cs, int32_t m, int32_t standardize, int32_t intercept, const oemgpu_opts *o,
+                                  double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int32_t *route)
+{
+    return fit_dense_multi_src("fit_dense_multi_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, y_rs, y_cs, m, standardize, intercept, o, beta,
+                               lambda_out, niter, loss, d, route);
+}
+
+int oemgpu_selftest_multi_plan(int64_t n, int32_t p, int32_t m, int32_t npen, int32_t layout, int32_t num_cu, int64_t *out)
+{
+    if (n < 1 || p < 1 || m < 1 || npen < 1 || num_cu < 1 || (layout != 0 && layout != 1) || !out) { set_error("selftest_multi_plan: bad argument"); return OEMGPU_ERR_ARG; }
+    if (n <= p) { set_error("selftest_multi_plan: n <= p, a shape of the p >= n engines, which the call does not serve"); return OEMGPU_ERR_UNSUPPORTED; }
+    // (the workspace of the paths grows with the penalties and lambdas: npen element-wise penalties of 100 lambdas stand for the call's)
+    std::vector<int32_t> pen(npen, OEMGPU_LASSO);
+    oemgpu_opts o;
+    memset(&o, 0, sizeof o);
+    o.npen = npen; o.penalty = pen.data(); o.nlambda = 100;
+    MultiLay L;
+    if (int rc = multi_layout("selftest_multi_plan", num_cu, layout == 0, n, p, m, &o, true, &L)) return rc;
+    out[0] = L.xp.rows; out[1] = L.xp.nchunk; out[2] = L.xp.mb; out[3] = L.xp.npass; out[4] = L.sv.cap; out[5] = L.nsolve; out[6] = L.sv.engine;
+    out[7] = (int64_t)(L.total + L.ws);
+    return 0;
+}
+
+int oemgpu_selftest_multi_moments_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                                      int64_t y_rs, int64_t y_cs, int32_t m, double *moments_out_dev)
+{
+    const char *who = "selftest_multi_moments";
+    const DenseSrc X = dtype < 0 ? dense_src_cm((const double *)x_dev, ld) : dense_src_rm(x_dev, dtype, ld);
+    int rc = src_args_check(who, c, X, n, p, y_dev, moments_out_dev != nullptr);
+    if (!rc) rc = multi_y_check(who, n, y_rs, y_cs, m);
+    if (rc) return rc;
+    if (!X.colmajor()) if ((rc = rm_p_refusal(who, p))) return rc;
+    MultiLay L;
+    if ((rc = multi_layout(who, c->num_cu, X.colmajor(), n, p, m, nullptr, false, &L))) return rc;
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    ctx_void_cv(c);
+    if (ctx_aux(c, L.total)) return OEMGPU_ERR_HIP;
+    if (ctx_reserve(c, L.ws)) return OEMGPU_ERR_HIP;
+    if ((rc = multi_passes(c, L, X, MultiY{y_dev, y_rs, y_cs}))) return rc;
+    const size_t mlen = (size_t)oemgpu_moments_len(p);
+    for (int r0 = 0; r0 < m; r0 += 4096) {
+        const int nb = m - r0 < 4096 ? m - r0 : 4096;
+        if ((rc = launch_multi_compose(c->stream, L.xp, (const double *)(c->aux + L.a_base), (const double *)(c->aux + L.a_part), r0, nb,
+                                       moments_out_dev + mlen * r0))) return rc;
+    }
+    OEM_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -116,7 +116,10 @@ struct RmDims {
     int p, ntc, nblk;
 };
 
-template <typename T, bool DIAG>
+// CM: the same pass -- the same fragments, steps, waves and sums, so the same bits -- over a COLUMN-major float64 x (ldr its column stride):
+// the many-response call (api.hip: multi_passes) takes its Gram block from here whichever way x lies, so that its fits do not depend on
+// the layout; a lane then reads 8 bytes of each of 16 columns, which is why oem() itself keeps gram.hip for such an x
+template <typename T, bool DIAG, bool CM = false>
 __device__ __forceinline__ void gram_rm_body(const T *__restrict__ x, const double *__restrict__ y, const double *__restrict__ sums,
                                              double *__restrict__ tdst, const RmDims &a, int bi, int bj, int64_t row_begin,
                                              int64_t row_end, double *lds)
@@ -154,9 +157,14 @@ __device__ __forceinline__ void gram_rm_body(const T *__restrict__ x, const doub
     double buf[DEPTH][NF], ybuf[DEPTH];
     auto load = [&](double (&v)[NF], double &yv, int64_t r0) {
         const int64_t r = r0 + k, rl = r < n ? r : n - 1;
-        const T *__restrict__ xr = x + (size_t)rl * ldr;
+        if constexpr (CM) {
 #pragma unroll
-        for (int f = 0; f < NF; ++f) v[f] = (double)xr[colc[f]];
+            for (int f = 0; f < NF; ++f) v[f] = (double)x[(size_t)colc[f] * ldr + rl];
+        } else {
+            const T *__restrict__ xr = x + (size_t)rl * ldr;
+#pragma unroll
+            for (int f = 0; f < NF; ++f) v[f] = (double)xr[colc[f]];
+        }
         yv = y[rl];
     };
     auto consume = [&](double (&v)[NF], double yv, int64_t r0) {
@@ -235,7 +243,7 @@ __device__ __forceinline__ void gram_rm_body(const T *__restrict__ x, const doub
     }
 }
 
-template <typename T>
+template <typename T, bool CM = false>
 __global__ __launch_bounds__(256, 2) void gram_rm_kernel(const T *__restrict__ x, const double *__restrict__ y,
                                                        const double *__restrict__ sums, double *__restrict__ tpart, RmDims a)
 {
@@ -248,8 +256,8 @@ __global__ __launch_bounds__(256, 2) void gram_rm_kernel(const T *__restrict__ x
     int64_t row_end = row_begin + a.steps * 16;
     if (row_end > a.n) row_end = a.n;
     double *tdst = tpart + (size_t)blockIdx.x * 16 * 256;
-    if (bi == bj) gram_rm_body<T, true>(x, y, sums, tdst, a, bi, bj, row_begin, row_end, lds);
-    else gram_rm_body<T, false>(x, y, sums, tdst, a, bi, bj, row_begin, row_end, lds);
+    if (bi == bj) gram_rm_body<T, true, CM>(x, y, sums, tdst, a, bi, bj, row_begin, row_end, lds);
+    else gram_rm_body<T, false, CM>(x, y, sums, tdst, a, bi, bj, row_begin, row_end, lds);
 }
 
 // chunk partials -> the (p + 2)^2 moment buffer: one workgroup per tile slot, four thread groups over the chunks (c = g mod 4, each in
@@ -296,7 +304,8 @@ int launch_gram_rm(hipStream_t s, const GramRmPlan &pl, const void *x, int dtype
     RmDims a;
     a.n = n; a.ldr = ldr; a.steps = pl.steps; a.p = pl.p; a.ntc = pl.ntc; a.nblk = pl.nblk;
     const dim3 grid((unsigned)((size_t)pl.nchunk * pl.nblk));
-    if (dtype == OEMGPU_F32) hipLaunchKernelGGL(gram_rm_kernel<float>, grid, dim3(256), 0, s, (const float *)x, y, sums, tpart, a);
+    if (dtype < 0) hipLaunchKernelGGL((gram_rm_kernel<double, true>), grid, dim3(256), 0, s, (const double *)x, y, sums, tpart, a);      // column-major, ldr the column stride
+    else if (dtype == OEMGPU_F32) hipLaunchKernelGGL(gram_rm_kernel<float>, grid, dim3(256), 0, s, (const float *)x, y, sums, tpart, a);
     else hipLaunchKernelGGL(gram_rm_kernel<double>, grid, dim3(256), 0, s, (const double *)x, y, sums, tpart, a);
     OEM_HIP(hipGetLastError());
     return 0;

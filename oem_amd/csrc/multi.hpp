@@ -1,0 +1,35 @@
+// multi.hpp -- many responses on one dense x (multi.hip): the plan of the X'Y pass and its launches; the driver is api.hip's fit_dense_multi_src.
+#pragma once
+
+#include "dense_src.hpp"
+
+namespace oemgpu {
+
+constexpr int MULTI_ROWS = 64;               // rows of one block of 16 k-steps; a row chunk is a multiple of it
+constexpr int MULTI_NW = 4;                  // waves per workgroup,
+constexpr int MULTI_CPW = 2;                 // 16-column tiles of [X | 1] per wave: a workgroup covers MULTI_NW * MULTI_CPW * 16 = 128 columns
+
+// Y as the caller gave it: element (i, r) at y[i * rs + r * cs]
+struct MultiY {
+    const double *y;
+    int64_t rs, cs;
+};
+
+// The X'Y pass as pure host arithmetic (oemgpu_selftest_multi_plan): rows are cut into `nchunk` chunks of `rows` rows (a multiple of
+// 64; the last may be short, none is empty), the responses into `npass` blocks of mb = 16 lt, the columns of [X | 1] into `cgroups`
+// groups of 128; workgroup (chunk, group, block) writes its part of the chunk's (p + 2) x mb panel:
+// part[((chunk * npass + block) * (p + 2) + row) * mb + response], row j < p: sum x_j y, row p: sum y^2, row p + 1: sum y.
+struct MultiPlan {
+    int64_t n = 0, rows = 0, nchunk = 0;
+    int p = 0, m = 0, lt = 0, mb = 0, npass = 0, cgroups = 0;
+    size_t part_doubles = 0;
+};
+MultiPlan multi_plan(int64_t n, int p, int m, int num_cu);
+
+int launch_multi_xty(hipStream_t s, const MultiPlan &pl, const DenseSrc &X, const MultiY &Y, double *part);
+// out[b] (b < nb, (p + 2)^2 doubles each) <- base with the y entries of response r0 + b: the partials added in chunk order
+int launch_multi_compose(hipStream_t s, const MultiPlan &pl, const double *base, const double *part, int r0, int nb, double *out);
+// out[i] <- Y(i, r), i < n: one response as the contiguous vector the single-response passes read
+int launch_multi_column(hipStream_t s, const MultiY &Y, int64_t n, int r, double *out);
+
+}  // namespace oemgpu

@@ -817,6 +817,7 @@ static int unpack(const Call &k, const PathPlan &P, const Bound &b)
         }
         c->shifted = hs[stats_shift_flag(p)] != 0.0;
         c->shift_advised = hs[stats_shift_flag(p) + 1] != 0.0;
+        if (k.x.shift_advised_out) k.x.shift_advised_out[bi] = c->shift_advised ? 1 : 0;
         const double meany = hs[0], scaley = hs[1];
         const double *meanx = hs + 4, *scalex = hs + 4 + p;
         for (int kp = 0; kp < npen; ++kp) {

@@ -23,6 +23,7 @@ struct PathExtras {
     const double *lmax_xy_dev = nullptr;     // the lambda grid from the caller's vector (big.oem with p >= n: the scaled X'y)
     double d_fixed = 0.0;
     const double *loss_xx = nullptr, *loss_xy = nullptr, *loss_stats = nullptr;
+    int32_t *shift_advised_out = nullptr;    // [nbatch] (host) <- what finalize advised for every instance (oemgpu_ctx::shift_advised keeps the last one's)
 };
 
 // xx (q x q), xy (q), stats already on the device (in the workspace, B the frame behind them).
