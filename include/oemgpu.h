@@ -467,6 +467,64 @@ int oemgpu_selftest_fold_gather_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32
  * OEMGPU_ERR_ARG for non-positive arguments, nfolds outside 2..512 or a NULL out. */
 int oemgpu_selftest_xval_cv_plan(int64_t n, int32_t p, int32_t nfolds, int32_t npen, int32_t nl, int32_t num_cu, int64_t *out /* 7 */);
 
+/* xval.oem for m responses on ONE dense x: it replaces the loop of m oemgpu_xval_dense_dev calls with the same foldid, every one of
+ * which lays out the folds, gathers x into fold order and runs the K fold Gram passes again although none of that depends on the
+ * response.  Here: one fold layout, one gather of x and one of Y (read through its strides, as oemgpu_fit_dense_multi_dev reads it),
+ * the K fold Gram passes once (response 0 riding as y), ONE X'Y pass over the fold-ordered rows for all responses (row chunks that never
+ * straddle a fold; partials added in chunk order, no atomics: two calls return the same bytes, and so do the three layouts of x) --
+ * then, per chunk of nb responses: their nb (K + 1) sums "all folds" / "all but fold ff" in one launch (folds in ascending order), the
+ * nb (K + 1) paths in one batched launch of at most 513 instances, instance r (K + 1) + ff, every response's K + 1 fits on the lambda
+ * grid of ITS full-data X'y, and the CV error of the nb responses in one launch and one finish launch.  A user lambda grid and foldid
+ * are shared by all responses; there are no observation weights.
+ * Outputs (host): beta[m][npen][nl][p + 1], lambda_out / niter / loss [m][npen][nl], d[m] (loss and d the full-data fit's), cvm / cvsd
+ * [m][npen][nl], and route[m]: 0 the response's fits ran in a batched launch, 1 no batch engine takes the shape (q = p + intercept >
+ * 1024, the cooperating engine switched off, or a launch too small for K + 1 instances) and its K + 1 sums went the way
+ * oemgpu_xval_dense_dev solves them.  Element r is what oemgpu_xval_dense_dev returns for column r to the accuracy of the sums (the y
+ * entries are added in another order).
+ * Refused before a device is looked for: what oemgpu_xval_dense_dev / _rm_dev and oemgpu_fit_dense_multi_dev refuse of these
+ * arguments, with their codes -- a NULL pointer, nfolds outside 2..512, a type_measure outside {0, 1}, m < 1, a stride pair of y that is
+ * neither form, bad options -- and OEMGPU_ERR_UNSUPPORTED for n <= p and for n - ceil(n / nfolds) <= p (the largest fold leaves its
+ * fit no more rows than columns); from the device: OEMGPU_ERR_ARG for a fold id outside 1..nfolds, OEMGPU_ERR_UNSUPPORTED for a fold
+ * that leaves n - fold <= p rows.  opts.interrupt is polled between the chunks (OEMGPU_ERR_INTERRUPTED). */
+int oemgpu_xval_dense_multi_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p,
+                                const double *y_dev, int64_t y_rs, int64_t y_cs, int32_t m,
+                                const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept,
+                                int32_t type_measure, const oemgpu_opts *o,
+                                double *beta, double *lambda_out, int32_t *niter, double *loss, double *d,
+                                double *cvm, double *cvsd, int32_t *route);
+/* The same on a row-major x read where it lies (the x arguments of oemgpu_xval_dense_rm_dev): the same bytes. */
+int oemgpu_xval_dense_multi_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p,
+                                   const double *y_dev, int64_t y_rs, int64_t y_cs, int32_t m,
+                                   const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept,
+                                   int32_t type_measure, const oemgpu_opts *o,
+                                   double *beta, double *lambda_out, int32_t *niter, double *loss, double *d,
+                                   double *cvm, double *cvsd, int32_t *route);
+/* HIP-event times (ms) of the last such call on this thread, taken while oemgpu_set_timing is on (the clock waits for the end of
+ * every phase; a phase that runs once per chunk of responses is added up): [0] fold order and the gathers of x and Y, [1] the fold
+ * Gram passes, [2] the fold X'Y pass, [3] the composition of the sums, [4] the paths, [5] the CV error.  All 0 with timing off. */
+#define OEMGPU_XVM_NPHASES 6
+int oemgpu_last_xval_multi_timings(double *ms /* OEMGPU_XVM_NPHASES */);
+/* Host-only plan of the two calls (pure arithmetic; the calls take their shape from the same function) for n rows, p columns, nfolds
+ * folds, m responses, npen element-wise penalties of nl lambdas and an intercept on a device of num_cu CUs:
+ * out[0] nb = responses per solve chunk, [1] solve chunks (none empty), [2] the batch engine (OEMGPU_ENGINE_ROWS / _COOP; 0: none),
+ * [3] route (0 / 1), [4] rows per chunk of the X'Y pass, [5] the most (fold) chunks that pass can have (n / rows rounded up, + nfolds:
+ * what its partials are sized for), [6] response blocks = reads of x by that pass, [7] responses per block, [8] workgroups per (fold,
+ * penalty, response) of the CV-error launch: floor(num_cu / (nfolds npen nb)), at most oemgpu_selftest_xval_cv_plan's, at least 1,
+ * [9] bytes of the single-response layout (fold order, fold-ordered x, fold moments), [10..17] bytes of: response 0 as a vector, the
+ * fold-ordered Y, the folds' first chunks, the X'Y partials, one chunk's composed sums (nb (nfolds + 1) (p + 2)^2 8), its fold
+ * tables (nb nfolds npen nl (p + 1) 8), its CV-error partials, its (cvm, cvsd); [18] the aux bytes of the call: [9] plus [10..17]
+ * each rounded up to 256, [19] the instances a batched launch may hold (multi_solve_plan's cap at q = p + 1).
+ * OEMGPU_ERR_ARG for non-positive arguments, nfolds outside 2..512 or a NULL out; OEMGPU_ERR_UNSUPPORTED for n <= p. */
+#define OEMGPU_XVM_PLAN_LEN 20
+int oemgpu_selftest_xval_multi_plan(int64_t n, int32_t p, int32_t nfolds, int32_t m, int32_t npen, int32_t nl, int32_t num_cu,
+                                    int64_t *out /* OEMGPU_XVM_PLAN_LEN */);
+/* Test infrastructure: the fold order, the fold Gram passes, the fold X'Y pass and the composition alone (nothing is fitted, n <= p is
+ * fine): moments_out_dev[m][nfolds][(p + 2)^2] (device) <- buffer (r, k) = the moment buffer about 0 of fold k's rows of (x, Y[:, r]),
+ * both triangles written.  dtype < 0: x_dev is column-major float64 with column stride ld; else row-major of that dtype. */
+int oemgpu_selftest_xval_multi_fold_moments_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ld, int32_t p,
+                                                const double *y_dev, int64_t y_rs, int64_t y_cs, int32_t m,
+                                                const int32_t *foldid_dev, int32_t nfolds, double *moments_out_dev);
+
 /* The eigenvalue step of the most recent solve (or oemgpu_eig_max_dev) on this context: *steps = Lanczos steps taken, *capped = 1
  * if the recurrence ran into its step cap (min(2 q, 288) for q <= 288, 256 / 512 on the larger engines) instead of stopping by its
  * rule or by breakdown -- d = 1.005 x the last Ritz value is then a lower estimate (the reference's Spectra call, tol 1e-10 and up

@@ -128,6 +128,16 @@ _SIGS = {
     "oemgpu_selftest_multi_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_selftest_multi_moments_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
                                                     C.c_int32, C.c_void_p]),
+    # xval.oem for many responses on one x: the loop of m oemgpu_xval_dense_dev / _rm_dev calls with one foldid
+    "oemgpu_xval_dense_multi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                              C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(OemgpuOpts)] + _OUT + [_dp, _dp, _ip]),
+    "oemgpu_xval_dense_multi_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+                                                 C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(OemgpuOpts)] + _OUT +
+                                       [_dp, _dp, _ip]),
+    "oemgpu_last_xval_multi_timings": (C.c_int, [_dp]),
+    "oemgpu_selftest_xval_multi_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "oemgpu_selftest_xval_multi_fold_moments_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                                              C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "oemgpu_fit_xtx_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _dp, C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_last_shift_in_effect": (C.c_int, [C.c_void_p]),
     "oemgpu_last_shift_advised": (C.c_int, [C.c_void_p]),

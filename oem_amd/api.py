@@ -1180,28 +1180,9 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
         if len(weights) != n:
             raise ValueError("length of weights not same as number of observations in x")
         wh = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
-    if penalty_factor is None:
-        penalty_factor = np.ones(p)
-    if varnames is None:
-        varnames = [f"V{i + 1}" for i in range(p)]
-    penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
-    if len(penalty_factor) != p:
-        raise ValueError("penalty.factor must have same length as number of columns in x")
-    if any("grp" in q for q in penalty) and len(np.ravel(groups)) != p:
-        raise ValueError("groups must have same length as number of columns in x")
-    groups, unique_groups, group_weights = _group_setup(penalty, groups, group_weights, p, bool(intercept))
-    if lambda_min_ratio is None:
-        lambda_min_ratio = 0.01 if n < p else 0.0001
-    _common_checks(nlambda, float(lambda_min_ratio), maxit, irls_maxit, tol, irls_tol)
-    lam_list = _lambda_list(lambda_, len(penalty))
-    if type_measure in ("default", "deviance"):                  # R/oem_xval.R:488-497
-        type_measure = "mse"
-    if type_measure not in ("mse", "mae"):
-        warnings.warn("Only 'mse', 'deviance' or 'mae'  available for Gaussian models; 'mse' used")
-        type_measure = "mse"
-    a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
-              compute_loss, penalty_factor, groups, unique_groups, group_weights, ngpus=ngpus, devices=devices,
-              upload_threads=upload_threads, interrupt=interrupt)
+    a, varnames, type_measure = _xval_options(n, p, penalty, type_measure, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups,
+                                              penalty_factor, group_weights, intercept, maxit, tol, irls_maxit, irls_tol, compute_loss,
+                                              varnames, ngpus, devices, upload_threads, interrupt)
     out = a.outputs(p + 1)
     cvm = np.zeros((a.npen, a.nl)); cvsd = np.zeros((a.npen, a.nl))
     fid = np.ascontiguousarray(foldid, dtype=np.int32)
@@ -1236,6 +1217,40 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
         L.check(lib.oemgpu_xval_dense(_dptr(xh), n, p, _dptr(yh), None if wh is None else _dptr(wh), _iptr(fid), int(nfolds),
                                       int(bool(standardize)),
                                       int(bool(intercept)), tm, C.byref(a.c), *out, _dptr(cvm), _dptr(cvsd)))
+    return _xval_result(a, penalty, varnames, n, p, cvm, cvsd, type_measure, fid)
+
+
+def _xval_options(n, p, penalty, type_measure, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups, penalty_factor, group_weights,
+                  intercept, maxit, tol, irls_maxit, irls_tol, compute_loss, varnames, ngpus, devices, upload_threads, interrupt):
+    """The option checks of xval.oem behind its checks of x, y and foldid (R/oem_xval.R:225-330, 488-497) -> (_Args, varnames,
+    type_measure as "mse" / "mae"): xval_oem and xval_oem_multi both pass through here, with the same sentences."""
+    if penalty_factor is None:
+        penalty_factor = np.ones(p)
+    if varnames is None:
+        varnames = [f"V{i + 1}" for i in range(p)]
+    penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
+    if len(penalty_factor) != p:
+        raise ValueError("penalty.factor must have same length as number of columns in x")
+    if any("grp" in q for q in penalty) and len(np.ravel(groups)) != p:
+        raise ValueError("groups must have same length as number of columns in x")
+    groups, unique_groups, group_weights = _group_setup(penalty, groups, group_weights, p, bool(intercept))
+    if lambda_min_ratio is None:
+        lambda_min_ratio = 0.01 if n < p else 0.0001
+    _common_checks(nlambda, float(lambda_min_ratio), maxit, irls_maxit, tol, irls_tol)
+    lam_list = _lambda_list(lambda_, len(penalty))
+    if type_measure in ("default", "deviance"):                  # R/oem_xval.R:488-497
+        type_measure = "mse"
+    if type_measure not in ("mse", "mae"):
+        warnings.warn("Only 'mse', 'deviance' or 'mae'  available for Gaussian models; 'mse' used")
+        type_measure = "mse"
+    a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
+              compute_loss, penalty_factor, groups, unique_groups, group_weights, ngpus=ngpus, devices=devices,
+              upload_threads=upload_threads, interrupt=interrupt)
+    return a, varnames, type_measure
+
+
+def _xval_result(a, penalty, varnames, n, p, cvm, cvsd, type_measure, fid):
+    """xval.oem's return value (R/oem_xval.R:430-460) from the outputs `a` holds (an _Args, or one response of many) and cvm / cvsd [npen, nl]"""
     res = _decorate(a, penalty, varnames, True, n, p)
     res["cvm"] = [cvm[k, :1].copy() if name == "ols" else cvm[k].copy() for k, name in enumerate(penalty)]
     res["cvsd"] = [cvsd[k, :1].copy() if name == "ols" else cvsd[k].copy() for k, name in enumerate(penalty)]
@@ -1246,6 +1261,129 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
     res["cvlo"] = [m - s for m, s in zip(res["cvm"], res["cvsd"])]
     res["best.model"] = penalty[res["model.min"] - 1]
     return res
+
+
+def xval_multi_plan(n, p, nfolds, m, npen=1, nl=100, num_cu=256):
+    """oemgpu_selftest_xval_multi_plan (pure host arithmetic) as a dict"""
+    out = (C.c_int64 * 20)()
+    L.check(L.lib().oemgpu_selftest_xval_multi_plan(int(n), int(p), int(nfolds), int(m), int(npen), int(nl), int(num_cu), out))
+    keys = ["nb", "solve_chunks", "engine", "route", "rows", "chunks_max", "passes", "block", "cv_nwg", "bytes_single", "bytes_col", "bytes_yp",
+            "bytes_cfirst", "bytes_part", "bytes_comp", "bytes_tab", "bytes_cvpart", "bytes_cvout", "bytes", "cap"]
+    return dict(zip(keys, [int(v) for v in out]))
+
+
+def xval_multi_timings():
+    """oemgpu_last_xval_multi_timings of this thread (ms; taken while oemgpu_set_timing is on) as a dict"""
+    out = (C.c_double * 6)()
+    L.check(L.lib().oemgpu_last_xval_multi_timings(out))
+    return dict(zip(["fold_order", "fold_gram", "fold_xty", "compose", "paths", "cv_error"], list(out)))
+
+
+def xval_multi_fold_moments(x, Y, foldid, nfolds):
+    """Test infrastructure: oemgpu_selftest_xval_multi_fold_moments_dev -> the composed fold buffers, numpy [m, nfolds, p + 2, p + 2]
+    indexed [r, k, i, j] = M[i, j] of fold k's rows of (x, Y[:, r]).  x as multi_moments takes it."""
+    import torch
+    if not _is_torch_cuda(x) or x.ndim != 2:
+        raise ValueError("x must be a 2-D torch tensor on a GPU")
+    n, p = x.shape
+    if x.dtype == torch.float64 and x.stride(0) == 1 and x.stride(1) >= n:
+        code, ld = -1, x.stride(1)
+    else:
+        code, ld = _rowmajor_dtype(x), x.stride(0)
+        if code is None:
+            raise ValueError("x must be column-major float64, or row-major float64 / float32 with unit column stride")
+    Yd, rs, cs = _device_responses(Y, x.device)
+    m = Yd.shape[1]
+    fd = torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=x.device)
+    out = torch.full((m, int(nfolds), p + 2, p + 2), float("nan"), dtype=torch.float64, device=x.device)
+    ctx = context(x.device.index)
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_selftest_xval_multi_fold_moments_dev(ctx, x.data_ptr(), code, n, ld, p, Yd.data_ptr(), rs, cs, m, fd.data_ptr(),
+                                                                int(nfolds), out.data_ptr()))
+    return out.cpu().numpy().transpose(0, 1, 3, 2).copy()            # (the buffers are column-major)
+
+
+def xval_oem_multi(x, Y, nfolds=10, foldid=None, type_measure=None, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=100,
+                   lambda_min_ratio=None, alpha=1.0, gamma=3.0, tau=0.5, groups=(), penalty_factor=None, group_weights=None,
+                   standardize=True, intercept=True, maxit=500, tol=1e-7, irls_maxit=100, irls_tol=1e-3, compute_loss=False, varnames=None,
+                   rng=None, ngpus=0, devices=None, interrupt=None):
+    """xval.oem for m responses on one resident x: [xval_oem(x, Y[:, r], foldid=foldid, ...) for r in range(m)] from one fold layout, one
+    gather of x, one set of fold Gram passes, one X'Y pass over the fold-ordered rows, and the (K + 1) m paths in batched launches
+    (include/oemgpu.h: oemgpu_xval_dense_multi_dev).  x: a dense torch device tensor, n x p with n > p >= 2, taken as
+    xval_oem takes it (column-major float64 and row-major float64 / float32 read in place).  Y: n x m, taken as oem_multi takes it.
+    foldid (values 1..nfolds; drawn once with `rng` when None) and a user lambda are shared by all responses.  xval_oem's other keyword
+    arguments and checks.  Returns a list of m results with xval_oem's keys (predict_xval, plot_xval and summary_xval take them) and one
+    more, `route`: 0 the response's K + 1 fits ran in a batched launch, 1 one launch (set) of their own, as xval_oem runs them."""
+    host_or_sparse = ("xval_oem_multi() takes a dense torch tensor on a GPU: a host or sparse x is cross-validated one response at a "
+                      "time with xval_oem()")
+    if isinstance(x, SparseX) or _is_scipy_sparse(x) or _is_torch_sparse(x):
+        raise ValueError(host_or_sparse)
+    if family not in ("gaussian", "binomial"):
+        raise ValueError("'arg' should be one of 'gaussian', 'binomial'")
+    penalty = _match_penalty(penalty)
+    if type_measure is None:
+        type_measure = "default"
+    elif type_measure not in _TYPE_MEASURES:
+        raise ValueError("'arg' should be one of " + ", ".join("'%s'" % t for t in _TYPE_MEASURES))
+    if family == "binomial":
+        raise ValueError("binomial models not yet supported for xval, use cv.oem() instead")
+    if len(weights) > 0:
+        raise ValueError("xval_oem_multi(): no observation weights; a weighted response is cross-validated with xval_oem(weights=)")
+    if ngpus or devices is not None:
+        raise ValueError("xval_oem_multi(): the rows of a resident x are not split over devices (ngpus / devices); xval_oem() splits a host x")
+    if getattr(Y, "ndim", None) != 2:
+        raise ValueError("Y must be a matrix of n rows and one column per response")
+    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("x must have at least two columns")
+    n, p = x.shape
+    m = int(Y.shape[1])
+    if m < 1:
+        raise ValueError("Y must have at least one column")
+    if p >= n:
+        raise ValueError("number of observations must be greater than the number of variables\n"
+                         "             for xval, use cv.oem instead, or, preferably, use another package such as\n"
+                         "             glmnet for the lasso, ncvreg for MCP/SCAD, or grpreg or gglasso for group lasso.")
+    if p < 2:
+        raise ValueError("x must have at least two columns")
+    if foldid is None:
+        g = np.random.default_rng() if rng is None else rng
+        foldid = g.permutation(np.resize(np.arange(1, int(nfolds) + 1), n))
+    else:
+        foldid = np.asarray(foldid).ravel()
+        nfolds = int(foldid.max())
+    if nfolds < 3:
+        raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
+    if Y.shape[0] != n or len(foldid) != n:
+        raise ValueError("x and y lengths do not match")
+    if not _is_torch_cuda(x):
+        raise ValueError(host_or_sparse)
+    a, varnames, type_measure = _xval_options(n, p, penalty, type_measure, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups,
+                                              penalty_factor, group_weights, intercept, maxit, tol, irls_maxit, irls_tol, compute_loss,
+                                              varnames, 0, None, 0, interrupt)
+    L.sync_switches()
+    import torch
+    X = _DeviceX(x, _xval_rowmajor_in_place)
+    Yd, rs, cs = _device_responses(Y, x.device)
+    fid = np.ascontiguousarray(foldid, dtype=np.int32)
+    fd = torch.as_tensor(fid, device=x.device)
+    beta = np.zeros((m, a.npen, a.nl, p + 1))
+    lam_out = np.zeros((m, a.npen, a.nl))
+    niter = np.zeros((m, a.npen, a.nl), dtype=np.int32)
+    loss = np.zeros((m, a.npen, a.nl))
+    d = np.zeros(m)
+    cvm = np.zeros((m, a.npen, a.nl)); cvsd = np.zeros((m, a.npen, a.nl))
+    route = np.zeros(m, dtype=np.int32)
+    ctx = context(x.device.index)
+    torch.cuda.current_stream(x.device).synchronize()
+    X.call("xval_dense_multi", ctx, Yd.data_ptr(), rs, cs, m, fd.data_ptr(), int(nfolds), int(bool(standardize)), int(bool(intercept)),
+           1 if type_measure == "mae" else 0, C.byref(a.c), _dptr(beta), _dptr(lam_out), _iptr(niter), _dptr(loss), _dptr(d), _dptr(cvm),
+           _dptr(cvsd), _iptr(route))
+    fits = []
+    for r in range(m):
+        fit = _xval_result(_OneOfMany(beta[r], lam_out[r], niter[r], loss[r], d[r]), penalty, varnames, n, p, cvm[r], cvsd[r], type_measure, fid)
+        fit["route"] = int(route[r])
+        fits.append(fit)
+    return fits
 
 
 

@@ -1253,10 +1253,12 @@ static size_t batch_ws_bytes(int p, int q, const oemgpu_opts *o, int nbatch)
 // launch that walks all their paths side by side (q <= SMALL_P_MAX).  Outputs as in run_paths.
 // cs != nullptr: observation weights -- the moments are those of the p + 1 data columns [sqrt(w) | sqrt(w) X] ((p + 3)^2 each) and
 // cs holds the unweighted column sums of squares and the row count of every instance (launch_finalize_weighted).
+// shared_lmax: every lambda grid from instance 0's X'Y -- or, with 0 < lmax_group < nbatch, instance b's from the first instance of its
+// group of lmax_group (xval_oem_multi: the K + 1 fits of every response on that response's full-data grid).
 static int solve_moments_batch(oemgpu_ctx *c, const double *moments, size_t mstride, int nbatch, int32_t p, int32_t semantics,
                                int32_t standardize, int32_t intercept, const oemgpu_opts *o,
                                double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, bool shared_lmax,
-                               const double *cs = nullptr, size_t cstride = 0, int32_t *shift_advised = nullptr)
+                               const double *cs = nullptr, size_t cstride = 0, int32_t *shift_advised = nullptr, int lmax_group = 0)
 {
     const int q = p + ((semantics != OEMGPU_SEM_DENSE && intercept) ? 1 : 0);
     Bump B;
@@ -1274,7 +1276,7 @@ static int solve_moments_batch(oemgpu_ctx *c, const double *moments, size_t mstr
     }
     char *f0 = c->ws + a_0;
     PathExtras x;
-    x.nbatch = nbatch; x.bstride = per / 8; x.shared_lmax = shared_lmax; x.shift_advised_out = shift_advised;
+    x.nbatch = nbatch; x.bstride = per / 8; x.shared_lmax = shared_lmax; x.lmax_group = lmax_group; x.shift_advised_out = shift_advised;
     return run_paths(c, B, (const double *)f0, (const double *)(f0 + o_xy), (const double *)(f0 + o_st), p, q, semantics, standardize,
                      intercept, o, nullptr, beta, lambda_out, niter, loss, d, x);
 }
@@ -1635,27 +1637,48 @@ static int xval_fold_moments(oemgpu_ctx *c, const XvalLay &L, const std::vector<
 // phase 2: mfold (and csq) in aux hold the per-fold moments of ALL rows; fold_tot[K] their fold sizes, n_tot the row count.
 // The full-data fit (ff = 0) and one fit per left-out fold on the lambdas of the first (ref src/oem_xval_dense.cpp:213-340);
 // the fold coefficients end in aux (bdev) for phase 3.
-static int xval_solve(oemgpu_ctx *c, const XvalLay &L, const int64_t *fold_tot, int64_t n_tot, int32_t standardize, int32_t intercept,
-                      const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+static int xval_fold_sizes_check(int K, int p, const int64_t *fold_tot, int64_t n_tot)
 {
-    const int K = L.K, p = L.p, npen = L.npen, nl = L.nl, q = p + (intercept ? 1 : 0);
-    const size_t mlen = L.mlen, cslen = L.cslen;
-    const bool weighted = L.weighted;
-    char *ax = c->aux;
-    double *mfold = (double *)(ax + L.a_mf), *bdev = (double *)(ax + L.a_b);
-    double *csq = (double *)(ax + L.a_cs), *cssum = csq + cslen * K;
     if (n_tot <= p) { set_error("dimension of x larger than number of observations"); return OEMGPU_ERR_UNSUPPORTED; }   // ref src/oem_xval_dense.h:690-731
     for (int k = 0; k < K; ++k)
         if (n_tot - fold_tot[k] <= p) { set_error("dimension of x larger than number of observations"); return OEMGPU_ERR_UNSUPPORTED; }  // ref :849-852
-    int rc = 0;
-    const size_t blen = (size_t)npen * nl * (p + 1), nk2 = (size_t)npen * nl;
-    std::vector<double> hb(blen * K);
+    return 0;
+}
+
+static int xval_solve_sums(oemgpu_ctx *c, const XvalLay &L, double *msum, const double *cssum, double *bdev, int32_t standardize, int32_t intercept,
+                           const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d);
+static int xval_solve(oemgpu_ctx *c, const XvalLay &L, const int64_t *fold_tot, int64_t n_tot, int32_t standardize, int32_t intercept,
+                      const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+{
+    const int K = L.K;
+    const size_t mlen = L.mlen, cslen = L.cslen;
+    const bool weighted = L.weighted;
+    char *ax = c->aux;
+    double *mfold = (double *)(ax + L.a_mf);
+    double *csq = (double *)(ax + L.a_cs), *cssum = csq + cslen * K;
+    int rc = xval_fold_sizes_check(K, L.p, fold_tot, n_tot);
+    if (rc) return rc;
     double *msum = (double *)(ax + L.a_ms);                      // [K + 1]: all folds, then all but fold ff
     for (int ff = 0; ff <= K; ++ff) {
         rc = launch_fold_sum(c->stream, mfold, K, mlen, ff, msum + mlen * ff);
         if (!rc && weighted) rc = launch_fold_sum(c->stream, csq, K, cslen, ff, cssum + cslen * ff);
         if (rc) return rc;
     }
+    return xval_solve_sums(c, L, msum, cssum, (double *)(ax + L.a_b), standardize, intercept, o, beta, lambda_out, niter, loss, d);
+}
+
+// The K + 1 fits of ONE response from its sums msum[K + 1] (all folds, then all but fold ff; device, outside the workspace; weighted: cssum
+// alike): the full-data fit into the outputs, the K fold fits on its lambdas into bdev[K][npen][nl][p + 1] (device) for phase 3.
+// xval_solve ends here, and so does every response of oemgpu_xval_dense_multi_dev that no batched launch takes (route 1).
+static int xval_solve_sums(oemgpu_ctx *c, const XvalLay &L, double *msum, const double *cssum, double *bdev, int32_t standardize, int32_t intercept,
+                           const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+{
+    const int K = L.K, p = L.p, npen = L.npen, nl = L.nl, q = p + (intercept ? 1 : 0);
+    const size_t mlen = L.mlen, cslen = L.cslen;
+    const bool weighted = L.weighted;
+    int rc = 0;
+    const size_t blen = (size_t)npen * nl * (p + 1), nk2 = (size_t)npen * nl;
+    std::vector<double> hb(blen * K);
     const bool coop_batch = q > SMALL_P_MAX && path_coop_eligible(q, false, o->compute_loss != 0, any_grp_count(o), K + 1) &&
                             path_coop_workgroups(q) * (K + 1) <= c->num_cu * 3 / 4;
     if (q <= SMALL_P_MAX || coop_batch) {
@@ -1804,6 +1827,278 @@ int oemgpu_xval_dense_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, in
 {
     return xval_dense_src("xval_dense_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, w_dev, foldid_dev, nfolds, standardize, intercept,
                           type_measure, o, beta, lambda_out, niter, loss, d, cvm, cvsd);
+}
+
+// ---------------------------------------------------------------------------------------------- xval.oem for many responses on one x
+//   What depends on x alone is made once -- the fold layout, the fold-ordered copy xp, the K fold Gram passes (response 0
+// riding as y) -- and so is one X'Y pass over the fold-ordered rows for all m responses (multi.hip, fold-segmented).  Per solve chunk of nb
+// responses: the nb (K + 1) composed sums in one launch, their paths in one batched launch (instance r (K + 1) + ff, every response's
+// fits on ITS full-data lambda grid: PathArgs::lmax_group), the CV error of the nb responses in one launch and one finish launch.
+// The buffers: XvalLay's for the shared part, then the regions below, in oemgpu_ctx::aux.
+struct XvalMultiLay {
+    XvalLay L;
+    MultiPlan xp;                                                 // the X'Y pass: blocks, groups, rows per chunk
+    MultiSolve sv;
+    CvErrPlan cv;                                                 // the CV-error launch of nb responses
+    int nb = 1, nsolve = 0, route = 1;
+    size_t b_col = 0, b_yp = 0, b_cf = 0, b_part = 0, b_comp = 0, b_tab = 0, b_cvpart = 0, b_cvout = 0;       // bytes
+    size_t a_col = 0, a_yp = 0, a_cf = 0, a_part = 0, a_comp = 0, a_tab = 0, a_cvpart = 0, a_cvout = 0, total = 0;
+};
+// nb_limit > 0: no more responses per chunk than that (the device's free memory)
+static XvalMultiLay xval_multi_layout(int num_cu, int64_t n, int p, int K, int m, int intercept, const oemgpu_opts *o, int nb_limit)
+{
+    XvalMultiLay V;
+    const int npen = o->npen, nl = nl_of(o), q = p + (intercept ? 1 : 0);
+    V.L = xval_layout(num_cu, n, p, K, npen, nl, false);
+    V.xp = multi_plan(n, p, m, num_cu);
+    V.sv = multi_solve_plan(num_cu, q, npen, any_grp_count(o));
+    // route 0: nb = floor(cap / (K + 1)) responses per batched launch; route 1: no batch engine takes the shape, or not even one
+    // response's K + 1 instances fit a launch -- every response's sums then go through xval_solve_sums, as xval.oem's do
+    V.route = (V.sv.engine != OEMGPU_ENGINE_NONE && V.sv.cap >= K + 1) ? 0 : 1;
+    int nb = V.route == 0 ? V.sv.cap / (K + 1) : 1;
+    if (nb > m) nb = m;
+    if (nb_limit > 0 && nb > nb_limit) nb = nb_limit;
+    V.nb = nb; V.nsolve = (m + nb - 1) / nb;
+    V.cv = cv_error_plan_many(n, p, K, npen, nl, nb, num_cu);
+    V.b_col = (size_t)n * 8;                                                       // response 0 as a contiguous vector (a row-major Y)
+    V.b_yp = (size_t)V.L.ldp * m * 8;                                              // Yp: the responses in fold order, column-major
+    V.b_cf = (size_t)(K + 1) * sizeof(int);                                        // first chunk of every fold
+    V.b_part = multi_fold_part_doubles(V.xp, K) * 8;                               // the X'Y panels of every (fold) chunk
+    V.b_comp = (size_t)nb * (K + 1) * V.L.mlen * 8;                                // one chunk's composed sums
+    V.b_tab = (size_t)nb * K * npen * nl * (p + 1) * 8;                            // its fold tables
+    V.b_cvpart = (size_t)nb * cv_part_doubles(V.cv.nwg, K, npen, nl) * 8;          // its CV-error partials
+    V.b_cvout = (size_t)nb * 2 * npen * nl * 8;                                    // (cvm, cvsd)
+    Bump A;
+    A.off = V.L.total;
+    V.a_col = A.take(V.b_col); V.a_yp = A.take(V.b_yp); V.a_cf = A.take(V.b_cf); V.a_part = A.take(V.b_part);
+    V.a_comp = A.take(V.b_comp); V.a_tab = A.take(V.b_tab); V.a_cvpart = A.take(V.b_cvpart); V.a_cvout = A.take(V.b_cvout);
+    V.total = A.off;
+    return V;
+}
+
+// HIP-event times of the last call's phases on this thread (oemgpu_set_timing on; added over the solve chunks; the clock waits for
+// every phase's end, so the timed call is not the fast one): fold order and gathers, fold Gram passes, fold X'Y, composition, paths, CV error
+static thread_local double g_xvm_ms[OEMGPU_XVM_NPHASES] = {0, 0, 0, 0, 0, 0};
+struct XvmClock {
+    oemgpu_ctx *c;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool on;
+    explicit XvmClock(oemgpu_ctx *c_) : c(c_), on(c_->timing)
+    {
+        if (on && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) on = false;
+    }
+    ~XvmClock() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    void begin() { if (on) (void)hipEventRecord(e0, c->stream); }
+    void end(int phase)
+    {
+        if (!on) return;
+        float f = 0.f;
+        (void)hipEventRecord(e1, c->stream);
+        if (hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&f, e0, e1) == hipSuccess) g_xvm_ms[phase] += f;
+    }
+};
+
+// phases 1-3: the rows of x and Y into fold order, the K fold Gram passes, the fold X'Y pass.  hf <- fold sizes [K] and starts [K].
+static int xval_multi_passes(oemgpu_ctx *c, const XvalMultiLay &V, const DenseSrc &X, const MultiY &Y, const int32_t *foldid_dev, int m,
+                             std::vector<int64_t> &hf, XvmClock &clk)
+{
+    const XvalLay &L = V.L;
+    const int K = L.K;
+    char *ax = c->aux;
+    double *col = (double *)(ax + V.a_col), *Yp = (double *)(ax + V.a_yp), *part = (double *)(ax + V.a_part);
+    int *cfirst = (int *)(ax + V.a_cf);
+    const int64_t *fold_n = (const int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
+    const double *y0 = Y.y;                                          // response 0 rides along as y
+    int rc = 0;
+    clk.begin();
+    if (Y.rs != 1) { if ((rc = launch_multi_column(c->stream, Y, L.n, 0, col))) return rc; y0 = col; }
+    if ((rc = xval_prepare(c, L, X, y0, nullptr, foldid_dev, hf, false))) return rc;         // (waits: the fold ids are valid from here on)
+    if ((rc = launch_gather_responses(c->stream, Y.y, Y.rs, Y.cs, L.n, m, (const int *)(ax + L.a_pos), Yp, L.ldp))) return rc;
+    clk.end(0);
+    clk.begin();
+    if ((rc = xval_fold_moments(c, L, hf, nullptr))) return rc;
+    clk.end(1);
+    // the chunks of the X'Y pass from the fold sizes: none straddles a fold, an empty fold has none
+    std::vector<int> cf(K + 1, 0);
+    for (int k = 0; k < K; ++k) {
+        const int64_t nc = (hf[k] + V.xp.rows - 1) / V.xp.rows;
+        if (cf[k] + nc > multi_fold_chunks_max(V.xp, K)) { set_error("internal: fold chunks beyond their scratch"); return OEMGPU_ERR_INTERNAL; }
+        cf[k + 1] = cf[k] + (int)nc;
+    }
+    OEM_HIP(hipMemcpyAsync(cfirst, cf.data(), sizeof(int) * (K + 1), hipMemcpyHostToDevice, c->stream));
+    OEM_HIP(hipStreamSynchronize(c->stream));                        // cf is a local
+    clk.begin();
+    rc = launch_multi_fold_xty(c->stream, V.xp, K, cf[K], (const double *)(ax + L.a_xp), L.ldp, Yp, fold_start, fold_n, cfirst, part);
+    clk.end(2);
+    return rc;
+}
+
+static int xval_dense_multi_src(const char *who, oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const double *y_dev, int64_t rs, int64_t cs,
+                                int32_t m, const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept, int32_t type_measure,
+                                const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, double *cvm,
+                                double *cvsd, int32_t *route)
+{
+    if (!c || !X.x || !y_dev || !foldid_dev || !beta || !lambda_out || !niter || !loss || !d || !cvm || !cvsd || !route) {
+        set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG;
+    }
+    const int K = nfolds;
+    int rc = dense_src_check(who, X, n, p);
+    if (!rc) rc = xval_check(c, X.x, y_dev, foldid_dev, n, n, p, K, intercept, type_measure, false, o);
+    if (!rc) rc = multi_y_check(who, n, rs, cs, m);
+    if (rc) return rc;
+    // the largest fold holds at least ceil(n / K) rows: its fit would keep n - that <= p of them (ref src/oem_xval_dense.h:690-731, 849-852)
+    if (n <= p || n - (n + K - 1) / K <= p) { set_error("dimension of x larger than number of observations"); return OEMGPU_ERR_UNSUPPORTED; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    XvalMultiLay V = xval_multi_layout(c->num_cu, n, p, K, m, intercept, o, 0);
+    {   // one chunk's sums, tables and partials grow with nb: fewer responses per chunk rather than an allocation that fails
+        size_t fre = 0, tot = 0;
+        if (hipMemGetInfo(&fre, &tot) == hipSuccess)
+            while (V.nb > 1 && V.total > fre + c->aux_bytes) V = xval_multi_layout(c->num_cu, n, p, K, m, intercept, o, V.nb / 2);
+    }
+    if (ctx_aux(c, V.total)) return OEMGPU_ERR_HIP;
+    for (double &v : g_xvm_ms) v = 0.0;
+    XvmClock clk(c);
+    const XvalLay &L = V.L;
+    std::vector<int64_t> hf;
+    if ((rc = xval_multi_passes(c, V, X, MultiY{y_dev, rs, cs}, foldid_dev, m, hf, clk))) return rc;
+    if ((rc = xval_fold_sizes_check(K, p, hf.data(), n))) return rc;
+    char *ax = c->aux;
+    const int npen = L.npen, nl = L.nl;
+    const size_t mlen = L.mlen, blen = (size_t)npen * nl * (p + 1), nk2 = (size_t)npen * nl;
+    const double *mfold = (const double *)(ax + L.a_mf), *part = (const double *)(ax + V.a_part), *Yp = (const double *)(ax + V.a_yp);
+    const int *cfirst = (const int *)(ax + V.a_cf);
+    const int64_t *fold_n = (const int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
+    double *comp = (double *)(ax + V.a_comp), *tab = (double *)(ax + V.a_tab), *cvpart = (double *)(ax + V.a_cvpart), *cvout = (double *)(ax + V.a_cvout);
+    auto interrupted = [&]() {
+        if (!(o->interrupt && o->interrupt(o->interrupt_arg))) return false;
+        set_error("interrupted by the caller");
+        return true;
+    };
+    std::vector<double> ab, al, aloss, ad, hb, hc;
+    std::vector<int32_t> an;
+    for (int r0 = 0; r0 < m; r0 += V.nb) {
+        const int nb = m - r0 < V.nb ? m - r0 : V.nb, ninst = nb * (K + 1);
+        if (r0 > 0 && interrupted()) return OEMGPU_ERR_INTERRUPTED;
+        clk.begin();
+        if ((rc = launch_multi_fold_compose(c->stream, V.xp, K, mfold, part, cfirst, r0, nb, false, comp))) return rc;
+        clk.end(3);
+        clk.begin();
+        if (V.route == 0) {
+            // instance b (K + 1) + ff: response r0 + b, all folds (ff = 0) or all but fold ff, on the lambda grid of instance b (K + 1)
+            ab.resize(blen * ninst); al.resize(nk2 * ninst); an.resize(nk2 * ninst); aloss.resize(nk2 * ninst); ad.resize(ninst); hb.resize(blen * K * nb);
+            rc = solve_moments_batch(c, comp, mlen, ninst, p, OEMGPU_SEM_XVAL, standardize, intercept, o, ab.data(), al.data(), an.data(), aloss.data(),
+                                     ad.data(), true, nullptr, 0, nullptr, K + 1);
+            if (rc) return rc;
+            for (int b = 0; b < nb; ++b) {
+                const size_t i0 = (size_t)b * (K + 1), r = (size_t)r0 + b;
+                memcpy(beta + blen * r, ab.data() + blen * i0, sizeof(double) * blen);
+                memcpy(lambda_out + nk2 * r, al.data() + nk2 * i0, sizeof(double) * nk2);
+                memcpy(niter + nk2 * r, an.data() + nk2 * i0, sizeof(int32_t) * nk2);
+                memcpy(loss + nk2 * r, aloss.data() + nk2 * i0, sizeof(double) * nk2);          // the full fit's (ref src/oem_xval_dense.cpp:296-301)
+                d[r] = ad[i0];
+                memcpy(hb.data() + blen * K * b, ab.data() + blen * (i0 + 1), sizeof(double) * blen * K);
+                route[r] = 0;
+            }
+            OEM_HIP(hipMemcpyAsync(tab, hb.data(), sizeof(double) * blen * K * nb, hipMemcpyHostToDevice, c->stream));
+        } else {
+            rc = xval_solve_sums(c, L, comp, nullptr, tab, standardize, intercept, o, beta + blen * r0, lambda_out + nk2 * r0, niter + nk2 * r0,
+                                 loss + nk2 * r0, d + r0);
+            if (rc) return rc;
+            route[r0] = 1;
+        }
+        clk.end(4);
+        clk.begin();
+        rc = launch_cv_error_many(c->stream, (const double *)(ax + L.a_xp), L.ldp, Yp + (size_t)L.ldp * r0, fold_start, fold_n, K, p, tab, npen, nl,
+                                  type_measure, V.cv, (double)n, nb, cvpart, cvout);
+        if (rc) return rc;
+        hc.resize(2 * nk2 * nb);
+        OEM_HIP(hipMemcpyAsync(hc.data(), cvout, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, c->stream));
+        OEM_HIP(hipStreamSynchronize(c->stream));                    // hb and hc are read and written by the copies above
+        clk.end(5);
+        for (int b = 0; b < nb; ++b)
+            for (int k = 0; k < npen; ++k) {
+                const int nlam = (o->penalty[k] == OEMGPU_OLS) ? 1 : nl;
+                for (int i = 0; i < nl; ++i) {
+                    const size_t ki = (size_t)k * nl + i, src = 2 * (nk2 * b + ki), dst = nk2 * ((size_t)r0 + b) + ki;
+                    cvm[dst] = i < nlam ? hc[src] : 0.0;
+                    cvsd[dst] = i < nlam ? hc[src + 1] : 0.0;
+                }
+            }
+    }
+    return 0;
+}
+
+int oemgpu_xval_dense_multi_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev, int64_t y_rs, int64_t y_cs,
+                                int32_t m, const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept, int32_t type_measure,
+                                const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, double *cvm,
+                                double *cvsd, int32_t *route)
+{
+    return xval_dense_multi_src("xval_dense_multi", c, dense_src_cm(x_dev, ld), n, p, y_dev, y_rs, y_cs, m, foldid_dev, nfolds, standardize, intercept,
+                                type_measure, o, beta, lambda_out, niter, loss, d, cvm, cvsd, route);
+}
+
+int oemgpu_xval_dense_multi_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev, int64_t y_rs,
+                                   int64_t y_cs, int32_t m, const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept,
+                                   int32_t type_measure, const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss,
+                                   double *d, double *cvm, double *cvsd, int32_t *route)
+{
+    return xval_dense_multi_src("xval_dense_multi_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, y_rs, y_cs, m, foldid_dev, nfolds, standardize,
+                                intercept, type_measure, o, beta, lambda_out, niter, loss, d, cvm, cvsd, route);
+}
+
+int oemgpu_last_xval_multi_timings(double *ms)
+{
+    if (!ms) { set_error("last_xval_multi_timings: NULL argument"); return OEMGPU_ERR_ARG; }
+    for (int i = 0; i < OEMGPU_XVM_NPHASES; ++i) ms[i] = g_xvm_ms[i];
+    return 0;
+}
+
+int oemgpu_selftest_xval_multi_plan(int64_t n, int32_t p, int32_t nfolds, int32_t m, int32_t npen, int32_t nl, int32_t num_cu, int64_t *out)
+{
+    if (n < 1 || p < 1 || m < 1 || npen < 1 || nl < 1 || num_cu < 1 || !out) { set_error("selftest_xval_multi_plan: bad argument"); return OEMGPU_ERR_ARG; }
+    if (int rc = xval_check_rows(n, n, nfolds, 0)) return rc;
+    if (n <= p) { set_error("selftest_xval_multi_plan: n <= p, which the call does not serve"); return OEMGPU_ERR_UNSUPPORTED; }
+    std::vector<int32_t> pen(npen, OEMGPU_LASSO);
+    oemgpu_opts o;
+    memset(&o, 0, sizeof o);
+    o.npen = npen; o.penalty = pen.data(); o.nlambda = nl;
+    const XvalMultiLay V = xval_multi_layout(num_cu, n, p, nfolds, m, 1, &o, 0);
+    const int64_t v[OEMGPU_XVM_PLAN_LEN] = {V.nb, V.nsolve, V.sv.engine, V.route, V.xp.rows, multi_fold_chunks_max(V.xp, nfolds), V.xp.npass, V.xp.mb, V.cv.nwg,
+                                            (int64_t)V.L.total, (int64_t)V.b_col, (int64_t)V.b_yp, (int64_t)V.b_cf, (int64_t)V.b_part, (int64_t)V.b_comp,
+                                            (int64_t)V.b_tab, (int64_t)V.b_cvpart, (int64_t)V.b_cvout, (int64_t)V.total, V.sv.cap};
+    for (int i = 0; i < OEMGPU_XVM_PLAN_LEN; ++i) out[i] = v[i];
+    return 0;
+}
+
+int oemgpu_selftest_xval_multi_fold_moments_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                                                int64_t y_rs, int64_t y_cs, int32_t m, const int32_t *foldid_dev, int32_t nfolds, double *moments_out_dev)
+{
+    const char *who = "selftest_xval_multi_fold_moments";
+    if (!c || !x_dev || !y_dev || !foldid_dev || !moments_out_dev) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    const DenseSrc X = dtype < 0 ? dense_src_cm((const double *)x_dev, ld) : dense_src_rm(x_dev, dtype, ld);
+    const int K = nfolds;
+    int rc = dense_src_check(who, X, n, p);
+    if (!rc) rc = xval_check_rows(n, n, K, 0);
+    if (!rc) rc = multi_y_check(who, n, y_rs, y_cs, m);
+    if (rc) return rc;
+    std::vector<int32_t> pen(1, OEMGPU_LASSO);
+    oemgpu_opts o;
+    memset(&o, 0, sizeof o);
+    o.npen = 1; o.penalty = pen.data(); o.nlambda = 1;
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const XvalMultiLay V = xval_multi_layout(c->num_cu, n, p, K, m, 1, &o, 1);
+    if (ctx_aux(c, V.total)) return OEMGPU_ERR_HIP;
+    XvmClock clk(c);
+    std::vector<int64_t> hf;
+    if ((rc = xval_multi_passes(c, V, X, MultiY{y_dev, y_rs, y_cs}, foldid_dev, m, hf, clk))) return rc;
+    const int step = 65535 / K;
+    for (int r0 = 0; r0 < m; r0 += step) {
+        const int nb = m - r0 < step ? m - r0 : step;
+        if ((rc = launch_multi_fold_compose(c->stream, V.xp, K, (const double *)(c->aux + V.L.a_mf), (const double *)(c->aux + V.a_part),
+                                            (const int *)(c->aux + V.a_cf), r0, nb, true, moments_out_dev + V.L.mlen * K * r0))) return rc;
+    }
+    OEM_HIP(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 // ---- the same three phases as separate calls, for row shards on several GPUs (one process per GPU; the caller sums the fold

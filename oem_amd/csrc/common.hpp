@@ -143,6 +143,8 @@ int launch_gather_rows(hipStream_t s, const double *x, int64_t n, int64_t ld, in
 // the same from a row-major x of OEMGPU_F64 / OEMGPU_F32 elements (row stride ldr); a row whose foldid is outside 1..K writes nothing
 int launch_gather_rows_rm(hipStream_t s, const void *x, int dtype, int64_t n, int64_t ldr, int p, const double *y, const int *foldid, int K,
                           const int *pos, double *xo, int64_t ldo, double *yo);
+// xval_oem_multi: Yp[pos[i] + r * ldo] <- Y(i, r) = y[i * rs + r * cs], every response into fold order (after the fold ids were found valid)
+int launch_gather_responses(hipStream_t s, const double *y, int64_t rs, int64_t cs, int64_t n, int m, const int *pos, double *yo, int64_t ldo);
 int launch_fold_sum(hipStream_t s, const double *M, int K, size_t len, int skip /* 1-based, 0: none */, double *out);
 // the shape of the CV-error launch (xval.hip: cv_error_plan; pure host arithmetic): K4 = p + 1 rounded up to a k-step of 4, ntile 16-lambda
 // tiles in `passes` passes of lt each, form CV_FORM_*, lds dynamic bytes, the coefficient rows in `chunks` LDS chunks of which the last
@@ -158,6 +160,12 @@ int launch_cv_error(hipStream_t s, const double *xp, int64_t ldp, const double *
                     int K, int p, const double *B, int npen, int nl, int mae, int wmode, const CvErrPlan &P, double n, double *part, double *out,
                     bool triples = false);
 int launch_cv_finish(hipStream_t s, const double *part, int nparts, int npen, int nl, double n, double *out, bool triples);
+// xval_oem_multi: nb responses on one fold-ordered x in one product launch and one finish launch (xval.hip: CvMany); P from
+// cv_error_plan_many, whose nwg divides the CUs by K * npen * nb.  Response r: y = Yp + r * ldp, table B + r * K * npen * nl * (p + 1),
+// partials part + r * cv_part_doubles(P.nwg, K, npen, nl), out + r * npen * nl * 2 <- (cvm, cvsd)
+CvErrPlan cv_error_plan_many(int64_t n, int p, int K, int npen, int nl, int nb, int num_cu);
+int launch_cv_error_many(hipStream_t s, const double *xp, int64_t ldp, const double *Yp, const int64_t *fold_start, const int64_t *fold_n,
+                         int K, int p, const double *B, int npen, int nl, int mae, const CvErrPlan &P, double n, int nb, double *part, double *out);
 // cv.oem, family = "gaussian": the same product from the same plan with one (count, mean, M2) per FOLD -- triples[K][npen][nl][3], (0, NaN, NaN)
 // in columns >= ncol[pen] and for empty folds -- and, with predmat != nullptr, yhat stored through inv (fold position -> caller's row, from
 // launch_fold_inverse) into predmat[npen][nl][n], NaN in columns >= ncol[pen]
@@ -296,6 +304,9 @@ struct PathArgs {
     // independent cold starts (ref src/oem_dense.cpp:243-244) -- so blockIdx.y = instance + nbatch * penalty; pen_lo / pen_hi are
     // the penalties this workgroup walks ([0, npen) without the split)
     int pen_split, pen_lo, pen_hi;
+    int lmax_group;          // > 0 (nbatch > 1, lmax_xy below = instance 0's xy): instance b takes lambda_zero from instance (b / lmax_group) * lmax_group
+                             // instead -- the K + 1 fits of one response among many (xval_oem_multi); 0: all from lmax_xy as it stands.  (In the
+                             // padding behind three ints: the size of the struct and every other offset are what they were.)
     const double *lmax_xy;   // not null: every instance takes lambda_zero from THIS xy (xval.oem: the grid of the full-data fit, ref src/oem_xval_dense.cpp:177-194)
     // not null (row-split kernel only): the outputs above point into PINNED HOST memory the device writes directly (the kernel only
     // ever stores to them), and the kernel leaves a copy of `stats` here as well -- no device-to-host copy node behind the kernel
@@ -326,6 +337,10 @@ constexpr unsigned PATH_TIMEOUT_ROUNDS = 1000u; // ... and gives up after that m
 constexpr int PATH_FAILED_TIMEOUT = 1, PATH_FAILED_ABORT = 2;
 
 // the problem instance of this workgroup (see PathArgs::nbatch); all scalar arithmetic
+// GRP = false: an instantiation that is never launched with a lambda group (PathArgs::lmax_group) and carries no code for one -- the
+// row-split kernel keeps the parent's code for single fits and ungrouped batches that way (it spills scalar registers, and one more
+// live scalar cost config 1's fit 14 us of 490)
+template <bool GRP = true>
 __device__ __forceinline__ PathArgs path_instance(PathArgs A)
 {
     const int nb = A.nbatch > 1 ? A.nbatch : 1;
@@ -339,6 +354,7 @@ __device__ __forceinline__ PathArgs path_instance(PathArgs A)
         A.beta = (double *)((char *)A.beta + ob); A.lambda_out = (double *)((char *)A.lambda_out + ob);
         A.loss = (double *)((char *)A.loss + ob); A.d_out = (double *)((char *)A.d_out + ob);
         A.niter = (int *)((char *)A.niter + ob);
+        if constexpr (GRP) { if (A.lmax_group > 0 && A.lmax_xy) A.lmax_xy += (b / A.lmax_group) * A.lmax_group * A.bs_xy; }
     }
     return A;
 }

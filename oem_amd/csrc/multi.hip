@@ -42,10 +42,18 @@ struct MultiRm {                             // row-major float64 / float32, row
     __device__ __forceinline__ double at(int64_t row, int col) const { return (double)x[row * ldr + col]; }
 };
 
+// FOLD (xval_oem_multi: X is the fold-ordered copy xp, y the fold-ordered Yp): the row chunks are those of the fold segments, fold k
+// owning chunks [cfirst[k], cfirst[k + 1]) of `rows` rows from fold_start[k] on -- none straddles a fold, none is empty (the host cuts
+// them from the fold sizes; an empty fold owns none), a segment may start on any row and have any length.  A lane without a row clamps
+// to the chunk's last row, so the padding rows between the segments (the gathers never write them) are never read.
+template <bool FOLD> struct MultiFolds {};
+template <> struct MultiFolds<true> { const int64_t *fold_start, *fold_n; const int *cfirst; int K; };
+
 // grid: (row chunks, column groups, response blocks)
-template <int LT, class SRC>
+template <int LT, class SRC, bool FOLD = false>
 __global__ __launch_bounds__(64 * MULTI_NW) void multi_xty_kernel(const SRC X, const double *__restrict__ y, int64_t rs, int64_t cs, int64_t n,
-                                                                  int p, int m, int64_t rows, int npass, double *__restrict__ part)
+                                                                  int p, int m, int64_t rows, int npass, double *__restrict__ part,
+                                                                  MultiFolds<FOLD> F)
 {
     constexpr int KC = LT >= 4 ? 4 : 8, MB = 16 * LT, CPW = MULTI_CPW;       // k-steps a lane has in flight at once
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, l16 = lane & 15, g = lane >> 4;
@@ -54,7 +62,15 @@ __global__ __launch_bounds__(64 * MULTI_NW) void multi_xty_kernel(const SRC X, c
     const int c0 = (cg * MULTI_NW + w) * CPW * 16;                           // this wave's first column of [X | 1]
     if (c0 > p) return;                                                       // (wave-uniform: nothing of [X | 1] here; wave 0 of group 0 always stays)
     const bool do_sq = cg == 0 && w == 0;
-    const int64_t r_lo = chunk * rows, r_end = r_lo + rows < n ? r_lo + rows : n;
+    int64_t r_lo = chunk * rows, r_end = r_lo + rows < n ? r_lo + rows : n, r_last = n - 1;
+    if constexpr (FOLD) {
+        int k = 0;
+        while (F.cfirst[k + 1] <= chunk) ++k;                                // (cfirst[K] = the number of chunks > chunk: k < K)
+        const int64_t seg_end = F.fold_start[k] + F.fold_n[k];
+        r_lo = F.fold_start[k] + (chunk - F.cfirst[k]) * rows;
+        r_end = r_lo + rows < seg_end ? r_lo + rows : seg_end;
+        r_last = r_end - 1;
+    }
     // Loads are never predicated: a lane whose element does not exist loads a clamped one that does (never padding) and SELECTS 0
     // instead, so every load of a batch of k-steps is in flight before the first MFMA waits (a load under a branch is waited for at the
     // branch's end, one load after the other: 3 to 4 times the kernel's time)
@@ -86,7 +102,7 @@ __global__ __launch_bounds__(64 * MULTI_NW) void multi_xty_kernel(const SRC X, c
             for (int k = 0; k < KC; ++k) {
                 const int64_t row = rb + 16 * g + s0 + k;
                 rok[k] = row < r_end;
-                const int64_t rowc = rok[k] ? row : n - 1;
+                const int64_t rowc = rok[k] ? row : r_last;
 #pragma unroll
                 for (int ct = 0; ct < CPW; ++ct) a[ct][k] = X.at(rowc, colc[ct]);
 #pragma unroll
@@ -166,6 +182,40 @@ __global__ __launch_bounds__(256) void multi_compose_kernel(const double *__rest
     out[(size_t)blockIdx.y * len + e] = v;
 }
 
+// xval_oem_multi.  grid: (ceil((p + 2)^2 / 256), instances).  Instance r * (K + 1) + ff of the solve chunk (r0 its first response):
+// "all folds" (ff = 0) or "all but fold ff" of response r0 + r -- the sum over the folds in ascending order, as xval.hip's
+// fold_sum_kernel takes it, of fold k's moment buffer mfold[k] with the y entries of the response composed in: fold k's chunk
+// partials added in chunk order first.  single: instance r * K + k is fold k's buffer alone (the selftest entry).  The x entries are
+// read from the valid (lower) triangle and written to both.
+__global__ __launch_bounds__(256) void multi_fold_compose_kernel(const double *__restrict__ mfold, const double *__restrict__ part, int p, int mb,
+                                                                 int npass, const int *__restrict__ cfirst, int K, int r0, int single,
+                                                                 double *__restrict__ out)
+{
+    const int q = p + 2;
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x, len = (size_t)q * q;
+    if (e >= len) return;
+    const int i = (int)(e % q), j = (int)(e / q), lo = i < j ? i : j, hi = i < j ? j : i;
+    int yrow = -1;
+    if (hi == p) yrow = lo;
+    else if (hi == p + 1 && lo == p) yrow = p + 1;
+    const int per = single ? K : K + 1, rl = blockIdx.y / per, ff = blockIdx.y - rl * per;
+    const int r = r0 + rl, blk = r / mb, within = r - blk * mb;
+    const double *src = part + ((size_t)blk * q + (yrow < 0 ? 0 : yrow)) * mb + within;
+    const size_t stride = (size_t)npass * q * mb, elo = (size_t)lo * q + hi;
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) {
+        if (single ? k != ff : k + 1 == ff) continue;
+        double v;
+        if (yrow < 0) v = mfold[(size_t)k * len + elo];
+        else {
+            v = 0.0;
+            for (int c = cfirst[k]; c < cfirst[k + 1]; ++c) v = c == cfirst[k] ? src[(size_t)c * stride] : v + src[(size_t)c * stride];
+        }
+        s += v;
+    }
+    out[(size_t)blockIdx.y * len + e] = s;
+}
+
 __global__ __launch_bounds__(256) void multi_column_kernel(const double *__restrict__ y, int64_t rs, int64_t cs, int64_t n, int r, double *__restrict__ out)
 {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = y[i * rs + (int64_t)r * cs];
@@ -176,16 +226,52 @@ int launch_xty_src(hipStream_t s, const MultiPlan &pl, const SRC &X, const Multi
 {
     const dim3 grid((unsigned)pl.nchunk, (unsigned)pl.cgroups, (unsigned)pl.npass), block(64 * MULTI_NW);
     switch (pl.lt) {
-    case 1: hipLaunchKernelGGL((multi_xty_kernel<1, SRC>), grid, block, 0, s, X, Y.y, Y.rs, Y.cs, pl.n, pl.p, pl.m, pl.rows, pl.npass, part); break;
-    case 2: hipLaunchKernelGGL((multi_xty_kernel<2, SRC>), grid, block, 0, s, X, Y.y, Y.rs, Y.cs, pl.n, pl.p, pl.m, pl.rows, pl.npass, part); break;
-    case 4: hipLaunchKernelGGL((multi_xty_kernel<4, SRC>), grid, block, 0, s, X, Y.y, Y.rs, Y.cs, pl.n, pl.p, pl.m, pl.rows, pl.npass, part); break;
+    case 1: hipLaunchKernelGGL((multi_xty_kernel<1, SRC>), grid, block, 0, s, X, Y.y, Y.rs, Y.cs, pl.n, pl.p, pl.m, pl.rows, pl.npass, part, MultiFolds<false>{}); break;
+    case 2: hipLaunchKernelGGL((multi_xty_kernel<2, SRC>), grid, block, 0, s, X, Y.y, Y.rs, Y.cs, pl.n, pl.p, pl.m, pl.rows, pl.npass, part, MultiFolds<false>{}); break;
+    case 4: hipLaunchKernelGGL((multi_xty_kernel<4, SRC>), grid, block, 0, s, X, Y.y, Y.rs, Y.cs, pl.n, pl.p, pl.m, pl.rows, pl.npass, part, MultiFolds<false>{}); break;
     default: set_error("internal: multi plan with %d response tiles", pl.lt); return OEMGPU_ERR_INTERNAL;
     }
     OEM_HIP(hipGetLastError());
     return 0;
 }
 
+template <int LT>
+int launch_fold_xty_lt(hipStream_t s, const MultiPlan &pl, int nchunk, const double *xp, int64_t ldp, const double *Yp, const MultiFolds<true> &F, double *part)
+{
+    const dim3 grid((unsigned)nchunk, (unsigned)pl.cgroups, (unsigned)pl.npass), block(64 * MULTI_NW);
+    hipLaunchKernelGGL((multi_xty_kernel<LT, MultiCm, true>), grid, block, 0, s, MultiCm{xp, ldp}, Yp, (int64_t)1, ldp, ldp, pl.p, pl.m, pl.rows,
+                       pl.npass, part, F);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
+
+int launch_multi_fold_xty(hipStream_t s, const MultiPlan &pl, int K, int nchunk, const double *xp, int64_t ldp, const double *Yp,
+                          const int64_t *fold_start, const int64_t *fold_n, const int *cfirst, double *part)
+{
+    if (nchunk < 1) return 0;                                                // (no row in any fold: nothing to add)
+    if (pl.cgroups > 65535 || pl.npass > 65535) { set_error("xval_multi: the X'Y pass has more workgroups than a launch takes"); return OEMGPU_ERR_UNSUPPORTED; }
+    const MultiFolds<true> F{fold_start, fold_n, cfirst, K};
+    switch (pl.lt) {
+    case 1: return launch_fold_xty_lt<1>(s, pl, nchunk, xp, ldp, Yp, F, part);
+    case 2: return launch_fold_xty_lt<2>(s, pl, nchunk, xp, ldp, Yp, F, part);
+    case 4: return launch_fold_xty_lt<4>(s, pl, nchunk, xp, ldp, Yp, F, part);
+    default: set_error("internal: multi plan with %d response tiles", pl.lt); return OEMGPU_ERR_INTERNAL;
+    }
+}
+
+int launch_multi_fold_compose(hipStream_t s, const MultiPlan &pl, int K, const double *mfold, const double *part, const int *cfirst, int r0, int nb,
+                              bool single, double *out)
+{
+    const size_t len = (size_t)(pl.p + 2) * (pl.p + 2);
+    const long long ninst = (long long)nb * (single ? K : K + 1);
+    if (ninst > 65535) { set_error("xval_multi: %lld composed buffers are more than a launch takes", ninst); return OEMGPU_ERR_UNSUPPORTED; }
+    hipLaunchKernelGGL(multi_fold_compose_kernel, dim3((unsigned)((len + 255) / 256), (unsigned)ninst), dim3(256), 0, s, mfold, part, pl.p, pl.mb,
+                       pl.npass, cfirst, K, r0, single ? 1 : 0, out);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
 
 MultiPlan multi_plan(int64_t n, int p, int m, int num_cu)
 {

@@ -29,6 +29,17 @@ MultiPlan multi_plan(int64_t n, int p, int m, int num_cu);
 int launch_multi_xty(hipStream_t s, const MultiPlan &pl, const DenseSrc &X, const MultiY &Y, double *part);
 // out[b] (b < nb, (p + 2)^2 doubles each) <- base with the y entries of response r0 + b: the partials added in chunk order
 int launch_multi_compose(hipStream_t s, const MultiPlan &pl, const double *base, const double *part, int r0, int nb, double *out);
+// xval_oem_multi: the same pass over the fold-ordered rows xp (column-major, leading dimension ldp) and Yp (alike), one launch for
+// all folds.  pl = multi_plan(n, p, m, ...): its blocks, groups and rows per chunk; fold k owns chunks [cfirst[k], cfirst[k + 1]) (device, K + 1
+// ints; nchunk = cfirst[K] <= multi_fold_chunks_max(pl, K), what `part` is sized for), chunk c of a fold its rows [c * rows, (c + 1) * rows).
+inline int64_t multi_fold_chunks_max(const MultiPlan &pl, int K) { return pl.nchunk + K; }      // sum_k ceil(n_k / rows) <= n / rows + K
+inline size_t multi_fold_part_doubles(const MultiPlan &pl, int K) { return (size_t)multi_fold_chunks_max(pl, K) * pl.npass * (size_t)(pl.p + 2) * pl.mb; }
+int launch_multi_fold_xty(hipStream_t s, const MultiPlan &pl, int K, int nchunk, const double *xp, int64_t ldp, const double *Yp,
+                          const int64_t *fold_start, const int64_t *fold_n, const int *cfirst, double *part);
+// out[r * (K + 1) + ff] (r < nb, ff <= K, (p + 2)^2 doubles each) <- the fold moments mfold[K] summed in fold order without fold ff (0: all),
+// response r0 + r's y entries composed in from the chunk partials; single: out[r * K + k] <- fold k's buffer alone
+int launch_multi_fold_compose(hipStream_t s, const MultiPlan &pl, int K, const double *mfold, const double *part, const int *cfirst, int r0, int nb,
+                              bool single, double *out);
 // out[i] <- Y(i, r), i < n: one response as the contiguous vector the single-response passes read
 int launch_multi_column(hipStream_t s, const MultiY &Y, int64_t n, int r, double *out);
 

@@ -1034,10 +1034,10 @@ __device__ __forceinline__ void iterate_rows_t(const PathArgs &A, const PenK &K,
         ++k;
     }
 }
-template <int NW, int CG, int CGL>
+template <int NW, int CG, int CGL, bool GRP = false>          // GRP: launched with a lambda group (common.hpp: path_instance)
 __global__ __launch_bounds__(NW * 64) void path_rows_kernel(PathArgs A_)
 {
-    const PathArgs A = path_instance(A_);
+    const PathArgs A = path_instance<GRP>(A_);
     typedef RowsCfg<NW, CG, CGL> C;
     constexpr int NBC = C::NBC;
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -1437,6 +1437,12 @@ static inline int path_grid_y(const PathArgs &a) { return (a.nbatch > 1 ? a.nbat
 template <int NW, int CG, int CGL = 0> int launch_rows(hipStream_t s, const PathArgs &a)
 {
     const size_t sh = (size_t)RowsCfg<NW, CG, CGL>::N_DBL * sizeof(double);
+    if (a.lmax_group > 0) {                                          // (xval_oem_multi's batches only)
+        if (sh > 64 * 1024 && lds_limit_once(reinterpret_cast<const void *>(&path_rows_kernel<NW, CG, CGL, true>), sh)) return OEMGPU_ERR_HIP;
+        hipLaunchKernelGGL((path_rows_kernel<NW, CG, CGL, true>), dim3(1, path_grid_y(a)), dim3(NW * 64), sh, s, a);
+        OEM_HIP(hipGetLastError());
+        return 0;
+    }
     if (sh > 64 * 1024 && lds_limit_once(reinterpret_cast<const void *>(&path_rows_kernel<NW, CG, CGL>), sh)) return OEMGPU_ERR_HIP;
     hipLaunchKernelGGL((path_rows_kernel<NW, CG, CGL>), dim3(1, path_grid_y(a)), dim3(NW * 64), sh, s, a);
     OEM_HIP(hipGetLastError());

@@ -637,6 +637,7 @@ static int bind_args(const Call &k, const PathPlan &P, const BlobAt &at, Bound &
     a.niter = (int *)(b.dstats + stats_len(p));
     a.work = (double *)(c->ws + b.a_work);
     a.lmax_xy = (nbatch > 1 && k.x.shared_lmax) ? k.xy : k.x.lmax_xy_dev;    // instance 0's X'Y; or the caller's (big.oem with p >= n: the scaled X'y)
+    a.lmax_group = (nbatch > 1 && k.x.shared_lmax && k.x.lmax_group > 0 && k.x.lmax_group < nbatch) ? k.x.lmax_group : 0;     // ... or the first instance's of b's group
     a.bs_xx = a.bs_xy = a.bs_stats = (long long)k.x.bstride; a.bs_out = (long long)P.out_stride; a.bs_work = (long long)P.work_d;
 
     b.st_gap = (size_t)((const char *)b.dout - (const char *)k.stats);

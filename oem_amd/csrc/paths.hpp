@@ -19,6 +19,7 @@ struct PathExtras {
     int nbatch = 1;
     size_t bstride = 0;
     bool shared_lmax = false;                // nbatch > 1: every lambda grid from instance 0's X'Y
+    int lmax_group = 0;                      // ... with shared_lmax, 0 < lmax_group < nbatch: instance b's from instance (b / lmax_group) * lmax_group (PathArgs::lmax_group)
     const WideArgs *wide = nullptr;          // the p >= n iteration through the standardised X itself (no Gram matrix: xx is NULL)
     const double *lmax_xy_dev = nullptr;     // the lambda grid from the caller's vector (big.oem with p >= n: the scaled X'y)
     double d_fixed = 0.0;

@@ -151,6 +151,21 @@ __global__ __launch_bounds__(256) void fold_gather_rm_kernel(const T *__restrict
     if (ct == 0 && cc == 0) yo[d] = y[i0 + r];
 }
 
+// xval_oem_multi: the rows of Y (element (i, r) at y[i * rs + r * cs], read where it lies) into fold order, Yp column-major with
+// leading dimension ldp -- a response is then the contiguous vector yp of the kernels above.  Run once the fold ids have been found
+// valid (every pos is set); the padding rows between the folds stay unwritten, as in xp, and nothing reads them.
+__global__ __launch_bounds__(256) void gather_responses_kernel(const double *__restrict__ y, int64_t rs, int64_t cs, int64_t n, int m,
+                                                               const int *__restrict__ pos, double *__restrict__ yo, int64_t ldo)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t d = pos[i];
+    const int r0 = blockIdx.y * GCB;
+#pragma unroll
+    for (int r = 0; r < GCB; ++r)
+        if (r0 + r < m) yo[(int64_t)(r0 + r) * ldo + d] = y[i * rs + (int64_t)(r0 + r) * cs];
+}
+
 // out = sum of the fold moments except fold `skip` (1-based; 0: none), in fold order (ref src/oem_xval_dense.h:733-742, 801-811)
 __global__ __launch_bounds__(256) void fold_sum_kernel(const double *__restrict__ M, int K, size_t len, int skip, double *__restrict__ out)
 {
@@ -243,24 +258,29 @@ constexpr size_t CV_LDS_MAX = 140 * 1024;   // the coefficient tile of a pass st
 // penalty's valid leading columns) get NaN.  Without PRED the trailing argument is empty and the kernel is what it was without it.
 template <bool PRED> struct CvPred {};
 template <> struct CvPred<true> { double *pred; const int *inv; const int *ncol; int64_t n; };
+// Many responses on one fold-ordered x (xval_oem_multi): grid.z = npen * nresp, response blockIdx.z / npen with its own y (yp + r * ystride),
+// its own table (B + r * bstride) and its own partials (part + r * pstride), each laid out as for one response -- so a response's sums are
+// taken in the order of the single-response launch of the same nwg.  nresp = 1 (every other caller): the kernel as it was.
+struct CvMany { int nresp; long long ystride, bstride, pstride; };
 template <int LT, int KC, bool SINGLE, bool CHUNK, bool PRED = false>
 __global__ __launch_bounds__(64 * CVW) void cv_error_kernel(const double *__restrict__ xp, int64_t ldp, const double *__restrict__ yp,
                                                             const int64_t *__restrict__ fold_start, const int64_t *__restrict__ fold_n,
                                                             int p, const double *__restrict__ B, int nl, int mae, int wmode,
-                                                            double *__restrict__ part, CvPred<PRED> pa)
+                                                            double *__restrict__ part, CvPred<PRED> pa, CvMany many)
 {
     // wmode (observation weights): xp has p + 1 data columns -- column 0 = sqrt(w), columns 1..p = sqrt(w) x -- and yp = sqrt(w) y, so
     // the squared residual of the scaled row IS w (y - yhat)^2 (ref src/oem_xval_dense.cpp:389-437); |.| takes one more sqrt(w).
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int k = blockIdx.y, pen = blockIdx.z, npen = gridDim.z, nwg = gridDim.x, wg = blockIdx.x;
+    const int npen = gridDim.z / many.nresp, resp = blockIdx.z / npen, pen = blockIdx.z - resp * npen;
+    const int k = blockIdx.y, nwg = gridDim.x, wg = blockIdx.x;
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, l16 = lane & 15, g = lane >> 4;
     const int Kd = p + 1, K4 = (Kd + 3) & ~3, nl16 = (nl + 15) & ~15, ntile = nl16 >> 4;
     constexpr int LW = 16 * LT;                       // lambdas per pass
     double *Bl = lds;                                 // [K4][LW]
     const int64_t start = fold_start[k], nk = fold_n[k];
-    const double *Bsrc = B + ((size_t)k * npen + pen) * nl * Kd;
-    const double *xk = xp + start, *yk = yp + start;
-    double *dst = part + ((((size_t)k * nwg + wg) * CVW + w) * npen + pen) * nl16 * 4;      // this wave's partial
+    const double *Bsrc = B + resp * many.bstride + ((size_t)k * npen + pen) * nl * Kd;
+    const double *xk = xp + start, *yk = yp + resp * many.ystride + start;
+    double *dst = part + resp * many.pstride + ((((size_t)k * nwg + wg) * CVW + w) * npen + pen) * nl16 * 4;      // this wave's partial
     const int64_t stride = (int64_t)nwg * CVW;
 
     auto load_a = [&](double (&a)[KC], int64_t rt, int c0) {
@@ -441,10 +461,13 @@ __device__ __forceinline__ CvSet cv_merge_partials(const double *__restrict__ pa
 // partials of all folds.
 // triples: out[npen][nl][3] <- (count, mean, M2) of the rows seen instead (row shards: the caller merges them, oemgpu_xval_merge).
 __global__ __launch_bounds__(64) void cv_finish_kernel(const double *__restrict__ part, int nparts, int npen, int nl, double n,
-                                                       double *__restrict__ out /* [npen][nl][2] */, int triples)
+                                                       double *__restrict__ out /* [npen][nl][2] */, int triples, long long pstride)
 {
+    // blockIdx.y: the response (one but for xval_oem_multi), its partials pstride doubles and its outputs npen * nl * (2 or 3) further on
     const int t = blockIdx.x, lane = threadIdx.x;
     const int pen = t / nl, lam = t - pen * nl, nl16 = (nl + 15) & ~15;
+    part += (long long)blockIdx.y * pstride;
+    out += (size_t)blockIdx.y * npen * nl * (triples ? 3 : 2);
     const CvSet a = cv_merge_partials(part, 0, nparts, npen, pen, nl16, lam, lane);
     if (lane == 0) {
         if (triples) { out[(size_t)t * 3] = a.na; out[(size_t)t * 3 + 1] = a.ma; out[(size_t)t * 3 + 2] = a.qa; }
@@ -504,6 +527,14 @@ int launch_gather_rows(hipStream_t s, const double *x, int64_t n, int64_t ld, in
 {
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n + 255) / 256), (p + GCB - 1) / GCB), dim3(256), 0, s, x, n, ld, p,
                        y, pos, xo, ldo, yo);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_gather_responses(hipStream_t s, const double *y, int64_t rs, int64_t cs, int64_t n, int m, const int *pos, double *yo, int64_t ldo)
+{
+    if ((m + GCB - 1) / GCB > 65535) { set_error("xval_multi: more responses than the gather of Y takes in one launch"); return OEMGPU_ERR_UNSUPPORTED; }
+    hipLaunchKernelGGL(gather_responses_kernel, dim3((unsigned)((n + 255) / 256), (m + GCB - 1) / GCB), dim3(256), 0, s, y, rs, cs, n, m, pos, yo, ldo);
     OEM_HIP(hipGetLastError());
     return 0;
 }
@@ -580,22 +611,31 @@ CvErrPlan cv_error_plan(int64_t n, int p, int K, int npen, int nl, int num_cu)
     P.nwg = nwg < 1 ? 1 : nwg;
     return P;
 }
+// nb responses in the grid: the CUs are divided among K * npen * nb (fold, penalty, response) triples, floored at one workgroup
+CvErrPlan cv_error_plan_many(int64_t n, int p, int K, int npen, int nl, int nb, int num_cu)
+{
+    CvErrPlan P = cv_error_plan(n, p, K, npen, nl, num_cu);
+    int nwg = (int)((int64_t)num_cu / ((int64_t)K * npen * (nb < 1 ? 1 : nb)));
+    if (nwg > P.nwg) nwg = P.nwg;                                                        // (the row-tile bound of cv_error_plan)
+    P.nwg = nwg < 1 ? 1 : nwg;
+    return P;
+}
 size_t cv_part_doubles(int nwg, int K, int npen, int nl) { return (size_t)nwg * K * CVW * npen * ((nl + 15) & ~15) * 4; }
 
 // pred != nullptr: the PRED instantiation (no weights there)
 template <int LT>
 static int launch_cv_lt(hipStream_t s, dim3 grid, size_t lds, int form, const double *xp, int64_t ldp, const double *yp,
                         const int64_t *fold_start, const int64_t *fold_n, int p, const double *B, int nl, int mae, int wmode, double *part,
-                        double *pred = nullptr, const int *inv = nullptr, const int *ncol = nullptr, int64_t n = 0)
+                        double *pred = nullptr, const int *inv = nullptr, const int *ncol = nullptr, int64_t n = 0, CvMany many = CvMany{1, 0, 0, 0})
 {
 #define OEM_CVK(KC, SINGLE, CHUNK)                                                                                                   \
     do {                                                                                                                             \
         if (pred) {                                                                                                                  \
             OEM_HIP(hipFuncSetAttribute((const void *)cv_error_kernel<LT, KC, SINGLE, CHUNK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL((cv_error_kernel<LT, KC, SINGLE, CHUNK, true>), grid, dim3(64 * CVW), lds, s, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, 0, part, CvPred<true>{pred, inv, ncol, n}); \
+            hipLaunchKernelGGL((cv_error_kernel<LT, KC, SINGLE, CHUNK, true>), grid, dim3(64 * CVW), lds, s, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, 0, part, CvPred<true>{pred, inv, ncol, n}, many); \
         } else {                                                                                                                     \
             OEM_HIP(hipFuncSetAttribute((const void *)cv_error_kernel<LT, KC, SINGLE, CHUNK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL((cv_error_kernel<LT, KC, SINGLE, CHUNK>), grid, dim3(64 * CVW), lds, s, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part, CvPred<false>{}); \
+            hipLaunchKernelGGL((cv_error_kernel<LT, KC, SINGLE, CHUNK>), grid, dim3(64 * CVW), lds, s, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part, CvPred<false>{}, many); \
         }                                                                                                                            \
     } while (0)
     if (form == CV_FORM_CHUNK) OEM_CVK(CV_KC, false, true);
@@ -609,11 +649,11 @@ static int launch_cv_lt(hipStream_t s, dim3 grid, size_t lds, int form, const do
 // the product alone: every wave's partial into part
 static int launch_cv_product(hipStream_t s, const double *xp, int64_t ldp, const double *yp, const int64_t *fold_start, const int64_t *fold_n,
                              int K, int p, const double *B, int npen, int nl, int mae, int wmode, const CvErrPlan &P, double *part,
-                             double *pred = nullptr, const int *inv = nullptr, const int *ncol = nullptr, int64_t n = 0)
+                             double *pred = nullptr, const int *inv = nullptr, const int *ncol = nullptr, int64_t n = 0, CvMany many = CvMany{1, 0, 0, 0})
 {
-    dim3 grid(P.nwg, K, npen);
+    dim3 grid(P.nwg, K, npen * many.nresp);
     int rc;
-#define OEM_CVLT(LT) case LT: rc = launch_cv_lt<LT>(s, grid, P.lds, P.form, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part, pred, inv, ncol, n); break
+#define OEM_CVLT(LT) case LT: rc = launch_cv_lt<LT>(s, grid, P.lds, P.form, xp, ldp, yp, fold_start, fold_n, p, B, nl, mae, wmode, part, pred, inv, ncol, n, many); break
     switch (P.lt) {
     OEM_CVLT(1); OEM_CVLT(2); OEM_CVLT(3); OEM_CVLT(4); OEM_CVLT(5); OEM_CVLT(6); OEM_CVLT(7);
     default: return OEMGPU_ERR_INTERNAL;
@@ -628,7 +668,23 @@ int launch_cv_error(hipStream_t s, const double *xp, int64_t ldp, const double *
 {
     int rc = launch_cv_product(s, xp, ldp, yp, fold_start, fold_n, K, p, B, npen, nl, mae, wmode, P, part);
     if (rc) return rc;
-    hipLaunchKernelGGL(cv_finish_kernel, dim3(npen * nl), dim3(64), 0, s, part, P.nwg * K * CVW, npen, nl, n, out, triples ? 1 : 0);
+    hipLaunchKernelGGL(cv_finish_kernel, dim3(npen * nl), dim3(64), 0, s, part, P.nwg * K * CVW, npen, nl, n, out, triples ? 1 : 0, 0LL);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+// nb responses in one product launch and one finish launch: response r reads yp + r * ldp (a column of the fold-ordered Yp) and
+// B + r * K * npen * nl * (p + 1), leaves its partials at part + r * cv_part_doubles(P.nwg, ...) and (cvm, cvsd) at out + r * npen * nl * 2.
+// P: cv_error_plan_many's (nwg divided among the responses).
+int launch_cv_error_many(hipStream_t s, const double *xp, int64_t ldp, const double *Yp, const int64_t *fold_start, const int64_t *fold_n,
+                         int K, int p, const double *B, int npen, int nl, int mae, const CvErrPlan &P, double n, int nb, double *part, double *out)
+{
+    if ((long long)npen * nb > 65535) { set_error("xval_multi: the CV-error launch has more (penalty, response) pairs than a launch takes"); return OEMGPU_ERR_UNSUPPORTED; }
+    const long long pstride = (long long)cv_part_doubles(P.nwg, K, npen, nl);
+    const CvMany many{nb, (long long)ldp, (long long)K * npen * nl * (p + 1), pstride};
+    int rc = launch_cv_product(s, xp, ldp, Yp, fold_start, fold_n, K, p, B, npen, nl, mae, 0, P, part, nullptr, nullptr, nullptr, 0, many);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cv_finish_kernel, dim3(npen * nl, nb), dim3(64), 0, s, part, P.nwg * K * CVW, npen, nl, n, out, 0, pstride);
     OEM_HIP(hipGetLastError());
     return 0;
 }
@@ -660,7 +716,7 @@ int launch_cv_fold_finish(hipStream_t s, const double *part, int per_fold, int K
 // the merge of launch_cv_error alone, for partials some other kernel wrote in the same layout (xval_sparse.hip)
 int launch_cv_finish(hipStream_t s, const double *part, int nparts, int npen, int nl, double n, double *out, bool triples)
 {
-    hipLaunchKernelGGL(cv_finish_kernel, dim3(npen * nl), dim3(64), 0, s, part, nparts, npen, nl, n, out, triples ? 1 : 0);
+    hipLaunchKernelGGL(cv_finish_kernel, dim3(npen * nl), dim3(64), 0, s, part, nparts, npen, nl, n, out, triples ? 1 : 0, 0LL);
     OEM_HIP(hipGetLastError());
     return 0;
 }
