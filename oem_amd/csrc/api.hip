@@ -3140,7 +3140,7 @@ static int spw_setup(oemgpu_ctx *c, const oemgpu_sparse_x *x, const int32_t *fol
     A.plan = spw_plan(n, p, x->nnz, 0, 0, c->num_cu, row_lanes, col_lanes);       // (the lanes; the long forms once the lines have been looked at)
     A.long_row_list = A.long_col_list = nullptr; A.n_long_rows = A.n_long_cols = 0;
     Bump X;
-    const size_t a_vec = X.take(sizeof(double) * (4 * (size_t)n + SPW_T_DOUBLES)), a_lr = X.take(sizeof(int32_t) * ((size_t)n + 1)),
+    const size_t a_vec = X.take(sizeof(double) * spw_vec_doubles(n)), a_lr = X.take(sizeof(int32_t) * ((size_t)n + 1)),
                  a_lc = X.take(sizeof(int32_t) * ((size_t)p + 1)), a_cnt = X.take(64);
     if (X.off != A.plan.ws_bytes) { set_error("internal: the sparse wide plan and its workspace disagree"); return OEMGPU_ERR_INTERNAL; }
     ctx_void_cv(c);

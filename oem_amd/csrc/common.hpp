@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/oemgpu.h"
+#include "path_large_layout.hpp"
 #include "switches.hpp"
 
 namespace oemgpu {
@@ -291,10 +292,10 @@ struct PathArgs {
                              // [6] exchange poison: cleared by the host before the launch, set to 1 by ANY workgroup whose exchange
                              //     timed out (a slot nobody else writes: the writer's stores cannot cover it up -- ADVICE r2)
                              // [7], [8] (row-split kernel only) OEM rounds run in the short form / in all, of penalty 0's path
-    // workspace for the large-p engine
+    // workspace for the large-p engine: path_large_work_doubles(p) doubles (its regions: path_large_layout.hpp, LargeWork)
     double *work;
-    // q > 1024 on the launch-per-iteration Gram engine: sympk_doubles(q) doubles for the packed lower triangle of XX and the partial
-    // vectors of its products (path_large.hip: sympk_*; a buffer of the context, outside the workspace frame); null: the row-streaming product
+    // q > 1024 on the launch-per-iteration Gram engine: sympk_doubles(q) doubles for the packed lower triangle of XX and what its products
+    // keep behind it (path_large_layout.hpp: SpkWork; a buffer of the context, outside the workspace frame); null: the row-streaming product
     double *sympk;
     // nbatch > 1 (p <= SMALL_P_MAX only): blockIdx.y selects one of nbatch independent problems that share everything above
     // except xx, xy, stats (element strides bs_xx, bs_xy, bs_stats), the outputs (byte stride bs_out) and work (bs_work)
@@ -376,8 +377,8 @@ bool path_small_takes_rows(const PathArgs &a);                    // will launch
 // in front of every Gram launch with the GPU idle
 int lds_limit_once(const void *fn, size_t bytes);
 int run_path_large(hipStream_t s, const PathArgs &a, double *host_scratch);   // any p: multi-launch engine
-size_t path_large_work_doubles(int p, int nsteps);
-size_t sympk_doubles(int q);                                      // 0 for q <= 1024
+size_t path_large_work_doubles(int p, int nsteps);                // large_work(p).total (path_large_layout.hpp)
+size_t sympk_doubles(int q);                                      // spk_work(q).total: 0 for q <= 1024
 int sympk_gemv_probe(hipStream_t s, const double *xx, int q, double *pk, const double *vec, double *out, int reps, double *us_per_product);
 // 288 < p <= 1024: one persistent launch of cooperating workgroups (path_coop.hip)
 bool path_coop_eligible(int q, bool has_sinv, bool compute_loss, int ngroups, int nbatch);
@@ -412,14 +413,7 @@ int launch_path_rowcoop(hipStream_t s, const PathArgs &a, void *xchg);
 // (ref src/oem_dense.h:363-366, 476-482, 513-521).  Layout of the standardised copy: `nb` row blocks of `rb` rows each (the last
 // may hold fewer), every block a column-major (64 nr) x p matrix of its own with zero padding rows -- a column of a block lives in
 // the registers of one wave (nr <= 32 doubles per lane).  n <= 2048: one block.
-struct WideLayout {
-    int nb;                  // row blocks
-    int rb;                  // data rows per block (block b holds rows [b rb, min(n, (b + 1) rb)))
-    int nr;                  // 64-row register slices per block: a block has 64 nr rows
-    __host__ __device__ long long npad() const { return 64LL * nr; }              // rows of one block
-    __host__ __device__ long long rows() const { return (long long)nb * 64 * nr; }  // rows of all blocks (vectors of this length)
-};
-WideLayout wide_layout(int64_t n);
+// (struct WideLayout, wide_layout(n), wide_workgroups(n, p): path_large_layout.hpp)
 struct WideArgs {
     const double *xs;        // standardised X: block b at xs + b * npad() * p
     const double *ys;        // standardised y, rows() entries in the same blocked order (padding zero)
@@ -442,7 +436,6 @@ struct WideArgs {
 // lines to a wave, four waves to a workgroup), or -- longer than SPW_LONG_PER_LANE L entries -- by a whole workgroup (the long
 // form, over a list of such lines made once per call).  Every sum has one fixed order.  The plan is pure host arithmetic.
 constexpr int SPW_LONG_PER_LANE = 32;
-constexpr int SPW_T_DOUBLES = 1024;      // the Lanczos table behind the engine's vectors (path_large.hip: 2 MAXL)
 struct SpwPlan {
     int route;               // sparse_wide_route
     int row_L, col_L;        // lanes per row / per column in the short form
@@ -461,7 +454,7 @@ struct SpwArgs {
     SpwPlan plan;
     const int32_t *long_row_list, *long_col_list;    // device: the lines of the long form
     int n_long_rows, n_long_cols;
-    double *vec;             // device: t | v | v_prev | w (n doubles each) | the Lanczos table
+    double *vec;             // device: spw_vec_doubles(n) doubles (path_large_layout.hpp: SpwVec)
     // cv.oem's fold fit (oemgpu_fit_sparse_wide_fold_res): not null -- the rows with foldid[i] == leave_out are left out of every row
     // pass and of the STATS pass, and nk, the kept rows (2 <= nk < n), stands wherever n enters the arithmetic
     const int32_t *foldid = nullptr;
@@ -481,8 +474,7 @@ int launch_spw_stats(hipStream_t s, const SpwArgs &A, const double *y, int stand
 int launch_spw_loss(hipStream_t s, const SpwArgs &A, const double *y, const double *b, int rows, int nk, double *t, double *part, double *loss);
 static const int WIDE_GRUN_MAX = 64;  // longest run (group) the fused group kernel takes
 static const int WIDE_MAX_N = 32768;         // 16 row blocks of 2048 rows
-int wide_workgroups(int n, int p);
-size_t wide_scratch_doubles(int n, int p);
+size_t wide_scratch_doubles(int n, int p);      // (its regions: path_large_layout.hpp, WideScratch)
 int launch_wide_standardize(hipStream_t s, const double *x, int64_t n, int64_t ld, int p, const double *y, int standardize, int intercept,
                             const WideLayout &lay, double *xs, double *ys, double *xy, double *stats);
 int launch_big_wide_scales(hipStream_t s, const double *x, int64_t n, int64_t ld, int p, const double *xy, double *stats, double *xy_std);

@@ -30,8 +30,7 @@ struct LState {
     double ak, d, theta, lmax;     // runs behind a product that has swept the caches, where every DEPENDENT load is an HBM round trip
     double lam;
 };
-static const int STATE_DBL = 16;
-static const int MAXL = 512;       // Lanczos steps kept
+static_assert(sizeof(LState) + 16 <= STATE_DBL * sizeof(double), "state block too small");
 
 // wave-uniform sum of v over the 64 lanes (same DPP scan as the small engine)
 template <int CTRL, int ROW_MASK> __device__ __forceinline__ double dppm(double v)
@@ -735,7 +734,6 @@ int launch_gemv_sym(hipStream_t s, const double *M, int q, const double *vec, do
 struct FState {
     int pp, i, it, done, fresh, pad0, pad1, pad2;
 };
-static const int FMAXB = 1024;          // flag words per parity
 
 template <int VPL>
 __global__ __launch_bounds__(256) void oem_fused_kernel(PathArgs A, FState *__restrict__ S, double *__restrict__ B,
@@ -848,7 +846,6 @@ __global__ __launch_bounds__(256) void oem_fused_kernel(PathArgs A, FState *__re
 //   bytes      per iteration: 4 q^2 + 4 q * 128 (blocks) + 8 q NBLK written, + 2 * 128 * NBLK * 8 B per workgroup re-read of the
 //              partials by the heads (L2 / Infinity Cache hits: the buffer is 1 MB).
 // ------------------------------------------------------------------------------------------------
-static const int SYM_TB = 128;
 #ifndef OEM_SYM_MINWG
 #define OEM_SYM_MINWG 2          // workgroups per CU the symmetric-tile kernels are compiled for (3 spills: 168 VGPRs do not hold both halves of a block)
 #endif
@@ -1105,10 +1102,6 @@ __global__ __launch_bounds__(256, OEM_SYM_MINWG) void oem_symfused_kernel(PathAr
 // g = XX beta from sympk_sum_kernel and run path_update_kernel / lanczos_update_kernel unchanged.
 // bytes per product: 4 q^2 + 512 q read + 8 q NBLK written and read again (q = 8,192: 272.6 + 4.2 + 4.2 MB).
 // ------------------------------------------------------------------------------------------------
-static const int SPK_TILE = SYM_TB * SYM_TB;             // doubles of a packed block (128 KiB)
-__host__ __device__ static inline int spk_nblk(int q) { return (q + SYM_TB - 1) / SYM_TB; }
-__host__ __device__ static inline size_t spk_ntile(int q) { const size_t nb = (size_t)spk_nblk(q); return nb * (nb + 1) / 2; }
-
 // block (I, J), J <= I, of workgroup b: row-major over the lower triangle
 __device__ __forceinline__ void spk_block(int b, int &I, int &J)
 {
@@ -1190,7 +1183,6 @@ __global__ __launch_bounds__(256, OEM_SYM_MINWG) void sympk_gemv_kernel(const do
 // the NBLK slots of SPK_HC = 32 coordinates per workgroup: thread (ch = tid / 32, l = tid % 32) adds slots [ch NBLK / 8, (ch + 1) NBLK / 8) of
 // coordinate l in slot order -- at q = 8,192 eight loads, all in flight at once: the kernel is one memory round trip -- and the eight
 // chunk sums meet as ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)): one fixed order, the same in the sum kernel and in the head
-constexpr int SPK_HC = 32;
 // (the chunk's part alone: slots [ch NBLK / 8, (ch + 1) NBLK / 8) of coordinate c, in slot order)
 __device__ __forceinline__ double spk_chunk_sum(const double *__restrict__ P, int nblk, int qpad, int c, int ch)
 {
@@ -1451,17 +1443,17 @@ __global__ __launch_bounds__(256) void sympk_head_kernel(PathArgs A, SState *__r
 // *us_per_product is the product kernel's own duration -- what bench.py prices against the HBM peak (oemgpu_selftest_sympk_gemv)
 int sympk_gemv_probe(hipStream_t s, const double *xx, int q, double *pk, const double *vec, double *out, int reps, double *us_per_product)
 {
-    const int nb = spk_nblk(q), qpad = nb * SYM_TB, nt = (int)spk_ntile(q);
-    double *P = pk + (size_t)nt * SPK_TILE;
+    const SpkWork L = spk_work(q);
+    double *P = pk + L.P.off;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     OEM_HIP(hipEventCreate(&e0));
     OEM_HIP(hipEventCreate(&e1));
-    hipLaunchKernelGGL(sympk_pack_kernel, dim3(nt), dim3(256), 0, s, xx, q, pk);
-    hipLaunchKernelGGL(sympk_gemv_kernel, dim3(nt), dim3(256), 0, s, pk, q, qpad, vec, P, (const int *)nullptr, (const int *)nullptr);     // (warm)
+    hipLaunchKernelGGL(sympk_pack_kernel, dim3(L.ntile), dim3(256), 0, s, xx, q, pk);
+    hipLaunchKernelGGL(sympk_gemv_kernel, dim3(L.ntile), dim3(256), 0, s, pk, q, L.qpad, vec, P, (const int *)nullptr, (const int *)nullptr);     // (warm)
     OEM_HIP(hipEventRecord(e0, s));
-    for (int k = 0; k < reps; ++k) hipLaunchKernelGGL(sympk_gemv_kernel, dim3(nt), dim3(256), 0, s, pk, q, qpad, vec, P, (const int *)nullptr, (const int *)nullptr);
+    for (int k = 0; k < reps; ++k) hipLaunchKernelGGL(sympk_gemv_kernel, dim3(L.ntile), dim3(256), 0, s, pk, q, L.qpad, vec, P, (const int *)nullptr, (const int *)nullptr);
     OEM_HIP(hipEventRecord(e1, s));
-    hipLaunchKernelGGL(sympk_sum_kernel, dim3(qpad / SPK_HC), dim3(256), 0, s, P, nb, q, qpad, out, (const int *)nullptr);
+    hipLaunchKernelGGL(sympk_sum_kernel, dim3(L.qpad / SPK_HC), dim3(256), 0, s, P, L.nblk, q, L.qpad, out, (const int *)nullptr);
     OEM_HIP(hipGetLastError());
     OEM_HIP(hipStreamSynchronize(s));
     float ms = 0.0f;
@@ -1471,14 +1463,7 @@ int sympk_gemv_probe(hipStream_t s, const double *xx, int q, double *pk, const d
     return 0;
 }
 
-size_t sympk_doubles(int q)
-{
-    if (q <= 1024) return 0;
-    const size_t nblk = (size_t)spk_nblk(q), qpad = nblk * SYM_TB;
-    // blocks | partial vectors P[NBLK][qpad] | B[2][qpad] | flags[2][FMAXB] ints | SState[2] | done word | nz32[2][qpad / 32] ints
-    // ... | gen: the head's parts of the sums over all coordinates [4][FMAXB] + its state words [2][4] (sympk_head_kernel<.., true>)
-    return spk_ntile(q) * SPK_TILE + nblk * qpad + 2 * qpad + FMAXB + 16 + 8 + qpad / 32 + 8 + 4 * FMAXB + 16;
-}
+size_t sympk_doubles(int q) { return spk_work(q).total; }      // (path_large_layout.hpp: SpkWork; 0 for q <= 1024)
 
 // ------------------------------------------------------------------------------------------------
 // Fused iteration, replicated-update form (group penalties, accelerate, compute.loss, scale.factor; same q): what crosses
@@ -1699,21 +1684,19 @@ __global__ void fused_init_kernel(FState *S, int npen)
     S[0] = z; S[1] = z; S[1].done = 0;
 }
 
-static size_t update_uf_doubles(int p) { return 2 * (size_t)(p + 8); }       // U[q] | F[ngroups <= q]
-static size_t sym_part_doubles(int p) { return p == 4096 ? 2 * (size_t)(p / SYM_TB) * p + 16 : 0; }
-
 size_t path_large_work_doubles(int p, int nsteps)
 {
     (void)nsteps;
-    // + fused engine: FState[2] (8 doubles), done word, beta[2][p+8], flags[2][FMAXB] ints
-    // + replicated-update engine: GState[2] (16 doubles), u[2][p+8] (beta[2] shared with the fused engine)
-    // + fused Lanczos: two copies each of v, v_prev, w
-    // + symmetric-tile engine (p = 4096): the partial vectors P[2][p / 128][p]
-    return (size_t)STATE_DBL + 5 * (size_t)(p + 8) + 2 * MAXL + 64 + 16 + 2 * (size_t)(p + 8) + FMAXB + 16 + 2 * (size_t)(p + 8) + 6 * (size_t)(p + 8) +
-           sym_part_doubles(p) + update_uf_doubles(p);
+    return large_work(p).total;                          // (path_large_layout.hpp: LargeWork)
 }
+// a region of a workspace as a pointer
+static double *in(double *base, const Region &r) { return base + r.off; }
+template <typename X> static X *in_as(double *base, const Region &r) { return reinterpret_cast<X *>(base + r.off); }
+static_assert(2 * sizeof(FState) <= 8 * sizeof(double) && 2 * sizeof(GState) <= 16 * sizeof(double) && 2 * sizeof(SState) <= 16 * sizeof(double),
+              "FState[2], GState[2] and SState[2] must fit their regions (path_large_layout.hpp)");
+
 // where path_update_kernel keeps U | F when they do not fit its LDS: the tail of the workspace
-static double *update_uf(const PathArgs &a) { return a.work + (path_large_work_doubles(a.p, 0) - update_uf_doubles(a.p)); }
+static double *update_uf(const PathArgs &a) { return in(a.work, large_work(a.p).uf); }
 // LDS bytes of the update kernel (U[q] | F[ngroups] for group operators), or 0 with *uf set when they go to global memory
 static size_t update_lds(const PathArgs &a, double **uf)
 {
@@ -1724,12 +1707,14 @@ static size_t update_lds(const PathArgs &a, double **uf)
     return sh;
 }
 
+// the iterations a path may take before the host gives up: `extra` per (penalty, lambda) for the launches that only move the state on
+static long long path_iteration_cap(const PathArgs &a, int extra) { return (long long)a.npen * a.nl * ((long long)a.maxit + extra) + 8; }
+
 // `enq(FB)` enqueues FB iterations (FB even: every batch starts at launch parity 0); they are captured ONCE into a hipGraph and replayed
 // until the device says done (eager launches are host-bound at ~3.5 us each); the host looks at one word per batch.
 template <typename F>
-static int replay_batches(hipStream_t s, F &&enq, const int *done_dev, int *hdone, long long max_it, const char *what)
+static int replay_batches(hipStream_t s, int FB, F &&enq, const int *done_dev, int *hdone, long long max_it, const char *what)
 {
-    const int FB = 128;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
@@ -1767,85 +1752,137 @@ extern "C" __attribute__((visibility("default"))) int oemgpu_diag_read_update(un
 }
 #endif
 
-// host_scratch: pinned host memory (>= 8 KB)
-int run_path_large(hipStream_t s, const PathArgs &a, double *host_scratch)
+// The host's look at a Lanczos recurrence after m steps, shared by every engine of this file.  hT: the pinned copy of T (alpha[MAXL] |
+// beta[MAXL]); dim: the dimension of the Krylov space (at most min(dim, MAXL) steps are taken); theta_prev: the previous look's theta
+// (<= 0: none).  The rules in their order: breakdown (T is exact); the stop rule of the register-resident engines (path_dev.hpp:
+// lanczos_converged) on the top Ritz values of the leading blocks T_{m-16}, T_{m-8}, T_m, which the host has for free -- moved by
+// <= 1e-14 relative over the last 8 steps, or two successive moves that decay so fast that their geometric tail is <= 1e-12
+// relative; stagnation between two looks.  capped: no rule has ended the recurrence and the steps do not span the whole Krylov space.
+struct LanczosLook {
+    double theta;
+    bool stop, capped;
+};
+static LanczosLook lanczos_look(const double *hT, int m, int dim, double theta_prev)
 {
-    const int q = a.p;
-    int dev = 0, num_cu = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    LState *st = reinterpret_cast<LState *>(a.work);
-    static_assert(sizeof(LState) + 16 <= STATE_DBL * sizeof(double), "state block too small");
-    double *beta = a.work + STATE_DBL, *g = beta + (q + 8), *v = g + (q + 8), *vp = v + (q + 8), *w = vp + (q + 8);
-    double *T = w + (q + 8);
-    OEM_HIP(hipMemsetAsync(a.work, 0, sizeof(double) * path_large_work_doubles(q, 0), s));
+    LanczosLook r;
+    r.stop = true; r.capped = false;
+    int mm = m;
+    for (int k = 0; k < m; ++k)
+        if (!(hT[MAXL + k] > 1e-13 * std::fabs(hT[k]))) { mm = k + 1; break; }     // breakdown: T is exact
+    const double theta = r.theta = tridiag_max_host(hT, hT + MAXL, mm);
+    if (mm < m) return r;
+    if (m >= 24) {
+        const double t1 = tridiag_max_host(hT, hT + MAXL, m - 8), t0 = tridiag_max_host(hT, hT + MAXL, m - 16);
+        const double mv = theta - t1, mvp = t1 - t0, ath = std::fabs(theta);
+        if (mv <= 1e-14 * ath || (mv < 0.01 * mvp && mv * mv <= OEM_LANCZOS_TAIL_TOL * ath * (mvp - mv))) return r;
+    }
+    if (theta_prev > 0 && std::fabs(theta - theta_prev) <= 1e-12 * std::fabs(theta)) return r;
+    r.stop = false;
+    r.capped = (dim < MAXL ? dim : MAXL) < dim;         // (the whole Krylov space is no cap)
+    return r;
+}
+// ... after the steps enqueued so far: T to the pinned copy, the stream drained, the look
+static int lanczos_look_on_stream(hipStream_t s, const double *T, double *hT, int m, int dim, double theta_prev, LanczosLook *look)
+{
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipMemcpyAsync(hT, T, sizeof(double) * 2 * MAXL, hipMemcpyDeviceToHost, s));
+    OEM_HIP(hipStreamSynchronize(s));
+    *look = lanczos_look(hT, m, dim, theta_prev);
+    return 0;
+}
 
-    // ---- eigenvalue step: Lanczos (GEMV + single-workgroup vector update), checked every
-    //      16 steps on the host, which is also the convergence test
-    const int mmax = q < MAXL ? q : MAXL;
-    double theta = 0.0, theta_prev = -1.0;
-    bool lz_capped = true;                              // cleared by whichever rule ends the recurrence
-    double *hT = host_scratch;
-    int m = 0;
-    // fused steps (one launch each) ping-pong between two copies of (v, v_prev, w) kept in their own area
-    // (measured at q = 4096: 35.7 us fused vs 23.8 + 7.9 + a boundary -- the replicated reductions over q numbers sit in
-    // front of the stream -- so the fused step is used where the launch count dominates)
-    const bool lz_fused = q <= 1024 && !sw().OEM_NO_FUSED.set;
-    const bool lz_full = (q == 512 || q == 1024 || q == 2048 || q == 4096) && (((uintptr_t)a.xx) & 15) == 0;
-    double *LZ = T + 2 * MAXL + 64 + 16 + 2 * (size_t)(q + 8) + FMAXB + 16 + 2 * (size_t)(q + 8);
-    double *Vc = LZ, *Vp = LZ + 2 * (size_t)(q + 8), *Wb = LZ + 4 * (size_t)(q + 8);
-    double *SP = LZ + 6 * (size_t)(q + 8);             // symmetric-tile engine: partial vectors P[2][q / 128][q]
-    // XX is symmetric: at q = 4096 the products read its lower triangle only (symgemv_kernel, oem_symfused_kernel)
-    const bool sym_ok = q == 4096 && (((uintptr_t)a.xx) & 15) == 0 && !sw().OEM_NO_SYM.set && !sw().OEM_NO_FUSED.set;
-    // ... and beyond 4096 a packed copy of it, made here (sympk_*: one contiguous sweep of 4 q^2 bytes per product)
-    // (1024 < q <= 4096 too: what the register-resident engines do not take -- groups that are not runs of neighbours, a timed-out persistent
-    // launch's second attempt -- used to run the row-streaming kernels with bounds logic at every q that is not 2048 or 4096: 50-60 us per
-    // iteration at q = 3,000; the packed blocks have no ragged edge)
-    const bool spk = q > 1024 && a.sympk != nullptr && !sw().OEM_NO_SYM.set;
-    const int spk_nb = spk_nblk(q), spk_qpad = spk_nb * SYM_TB, spk_nt = (int)spk_ntile(q);
-    double *spk_P = spk ? a.sympk + (size_t)spk_nt * SPK_TILE : nullptr, *spk_B = spk ? spk_P + (size_t)spk_nb * spk_qpad : nullptr;
-    bool spk_packed = false;
-    auto spk_pack = [&]() {                               // before the first product (never inside a graph capture)
-        if (spk_packed) return;
-        (void)hipMemsetAsync(spk_B, 0, sizeof(double) * (2 * (size_t)spk_qpad + FMAXB + 16 + 8 + spk_qpad / 32 + 8 + 4 * FMAXB + 16), s);
-        hipLaunchKernelGGL(sympk_pack_kernel, dim3(spk_nt), dim3(256), 0, s, a.xx, q, a.sympk);
-        spk_packed = true;
-    };
-    int *spk_nz = spk ? reinterpret_cast<int *>(spk_B + 2 * (size_t)spk_qpad + FMAXB + 16 + 8) : nullptr;      // nz32[2][qpad / 32] (the general form uses [0])
-    auto spk_gemv = [&](const double *vec, double *out, const int *done, const int *nz = nullptr) {
-        hipLaunchKernelGGL(sympk_gemv_kernel, dim3(spk_nt), dim3(256), 0, s, a.sympk, q, spk_qpad, vec, spk_P, done, nz);
-        if (out) hipLaunchKernelGGL(sympk_sum_kernel, dim3(spk_qpad / SPK_HC), dim3(256), 0, s, spk_P, spk_nb, q, spk_qpad, out, done);
-    };
-    auto sym_gemv = [&](const double *vec, double *out) {
+// One call of run_path_large: its arguments, PathArgs::work by its regions, and the products through the lower triangle of XX alone --
+// XX is symmetric: at q = 4096 the products read its lower triangle in place (symgemv_kernel, oem_symfused_kernel), and beyond 1024 a
+// packed copy of it, made here (sympk_*: one contiguous sweep of 4 q^2 bytes per product).
+// (1024 < q <= 4096 too: what the register-resident engines do not take -- groups that are not runs of neighbours, a timed-out persistent
+// launch's second attempt -- used to run the row-streaming kernels with bounds logic at every q that is not 2048 or 4096: 50-60 us per
+// iteration at q = 3,000; the packed blocks have no ragged edge)
+struct LargeRun {
+    hipStream_t s;
+    const PathArgs &a;
+    int q, num_cu;
+    LargeWork W;
+    SpkWork K;                                           // PathArgs::sympk by its regions
+    bool aligned, sym_ok, spk, packed = false;
+    int *hdone;
+
+    LargeRun(hipStream_t s_, const PathArgs &a_, double *host_scratch) : s(s_), a(a_), q(a_.p), num_cu(256), W(large_work(a_.p)), K(spk_work(a_.p))
+    {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev);
+        aligned = (((uintptr_t)a.xx) & 15) == 0;
+        sym_ok = q == 4096 && aligned && !sw().OEM_NO_SYM.set && !sw().OEM_NO_FUSED.set;
+        spk = q > 1024 && a.sympk != nullptr && !sw().OEM_NO_SYM.set;
+        hdone = reinterpret_cast<int *>(host_scratch);
+    }
+    double *work(const Region &r) const { return in(a.work, r); }
+    double *pk(const Region &r) const { return in(a.sympk, r); }
+    LState *st() const { return in_as<LState>(a.work, W.state); }
+    bool power_of_two_q() const { return q == 512 || q == 1024 || q == 2048 || q == 4096; }
+    int row_blocks() const { const int b = (q + 3) / 4; return b > num_cu * 2 ? num_cu * 2 : b; }      // workgroups of the row-streaming fused kernels
+    int *spk_nz() const { return spk ? in_as<int>(a.sympk, K.nz32) : nullptr; }      // nz32[2][qpad / 32] (the general form uses [0])
+
+    void spk_pack()                                      // before the first product (never inside a graph capture)
+    {
+        if (packed) return;
+        (void)hipMemsetAsync(a.sympk + K.zero_from, 0, sizeof(double) * K.zero_doubles, s);
+        hipLaunchKernelGGL(sympk_pack_kernel, dim3(K.ntile), dim3(256), 0, s, a.xx, q, a.sympk);
+        packed = true;
+    }
+    void spk_gemv(const double *vec, double *out, const int *done, const int *nz = nullptr) const
+    {
+        hipLaunchKernelGGL(sympk_gemv_kernel, dim3(K.ntile), dim3(256), 0, s, a.sympk, q, K.qpad, vec, pk(K.P), done, nz);
+        if (out) hipLaunchKernelGGL(sympk_sum_kernel, dim3(K.qpad / SPK_HC), dim3(256), 0, s, pk(K.P), K.nblk, q, K.qpad, out, done);
+    }
+    void sym_gemv(const double *vec, double *out)
+    {
         if (!sym_ok) { spk_pack(); spk_gemv(vec, out, nullptr); }
         else {
-            hipLaunchKernelGGL((symgemv_kernel<32>), dim3(sym_nwg(32)), dim3(256), 0, s, a.xx, vec, SP);
-            hipLaunchKernelGGL((symgemv_sum_kernel<32>), dim3(q / 128), dim3(128), 0, s, SP, out);
+            hipLaunchKernelGGL((symgemv_kernel<32>), dim3(sym_nwg(32)), dim3(256), 0, s, a.xx, vec, work(W.sym_part));
+            hipLaunchKernelGGL((symgemv_sum_kernel<32>), dim3(q / 128), dim3(128), 0, s, work(W.sym_part), out);
         }
-    };
+    }
+};
+
+// ---- eigenvalue step: Lanczos (GEMV + single-workgroup vector update, or both fused), checked every 16 steps on the host, which is
+//      also the convergence test.  theta: the top Ritz value; m: steps taken; capped: no rule ended the recurrence.
+// fused steps (one launch each) ping-pong between two copies of (v, v_prev, w) kept in their own area
+// (measured at q = 4096: 35.7 us fused vs 23.8 + 7.9 + a boundary -- the replicated reductions over q numbers sit in
+// front of the stream -- so the fused step is used where the launch count dominates)
+static int large_eigen_step(LargeRun &R, double *hT, double *theta_out, int *m_out, bool *capped_out)
+{
+    hipStream_t s = R.s;
+    const PathArgs &a = R.a;
+    const int q = R.q, mmax = q < MAXL ? q : MAXL;
+    double *v = R.work(R.W.v), *vp = R.work(R.W.vp), *w = R.work(R.W.w), *T = R.work(R.W.T);
+    double *Vc = R.work(R.W.Vc), *Vp = R.work(R.W.Vp), *Wb = R.work(R.W.Wb);
+    *theta_out = 0.0; *m_out = 0; *capped_out = true;
+    if (a.d_fixed > 0.0) { *theta_out = a.d_fixed / 1.005; *capped_out = false; return 0; }      // (the caller's d: no recurrence)
+    const bool lz_fused = q <= 1024 && !sw().OEM_NO_FUSED.set;
+    const bool lz_full = R.power_of_two_q() && R.aligned;
     void (*lzk)(const double *, int, int, double *, double *, double *, double *, int) = nullptr;
     if (lz_fused) {
         if (q <= 512) lzk = lz_full ? lanczos_fused_kernel<8, true> : lanczos_fused_kernel<8, false>;
         else lzk = lz_full ? lanczos_fused_kernel<16, true> : lanczos_fused_kernel<16, false>;
     }
-    int lblocks = (q + 3) / 4;
-    if (lblocks > num_cu * 2) lblocks = num_cu * 2;
+    const int lblocks = R.row_blocks();
     const size_t lsh = sizeof(double) * (size_t)(q + 8);
-    const bool d_given = a.d_fixed > 0.0;                // (the caller's d: no recurrence)
-    if (d_given) { theta = a.d_fixed / 1.005; lz_capped = false; }
-    else if (lz_fused) {
+    if (lz_fused) {
         hipLaunchKernelGGL(lanczos_init_kernel, dim3(1), dim3(1024), 0, s, q, Vc, Vp);
-        int rc = launch_gemv(s, a.xx, q, Vc, Wb, nullptr, num_cu);           // w_0 = M v_0; every later product is fused
+        int rc = launch_gemv(s, a.xx, q, Vc, Wb, nullptr, R.num_cu);         // w_0 = M v_0; every later product is fused
         if (rc) return rc;
     } else hipLaunchKernelGGL(lanczos_init_kernel, dim3(1), dim3(1024), 0, s, q, v, vp);
-    while (m < mmax && !d_given) {
+    double theta_prev = -1.0;
+    int m = 0;
+    while (m < mmax) {
         const int chunk = (mmax - m) < 16 ? (mmax - m) : 16;     // a host look costs about one step
         for (int k = 0; k < chunk; ++k, ++m) {
             if (lz_fused) hipLaunchKernelGGL(lzk, dim3(lblocks), dim3(256), lsh, s, a.xx, q, m, Vc, Vp, Wb, T, m & 1);
             else {
-                if (sym_ok || spk) sym_gemv(v, w);
+                if (R.sym_ok || R.spk) R.sym_gemv(v, w);
                 else {
-                    int rc = launch_gemv(s, a.xx, q, v, w, nullptr, num_cu);
+                    int rc = launch_gemv(s, a.xx, q, v, w, nullptr, R.num_cu);
                     if (rc) return rc;
                 }
                 if (q > 1024 && q <= 8192) hipLaunchKernelGGL(lanczos_update_reg_kernel<8>, dim3(1), dim3(1024), 0, s, q, m, v, vp, w, T);
@@ -1853,123 +1890,129 @@ int run_path_large(hipStream_t s, const PathArgs &a, double *host_scratch)
                 else hipLaunchKernelGGL(lanczos_update_kernel, dim3(1), dim3(1024), 0, s, q, m, v, vp, w, T);
             }
         }
-        OEM_HIP(hipGetLastError());
-        OEM_HIP(hipMemcpyAsync(hT, T, sizeof(double) * 2 * MAXL, hipMemcpyDeviceToHost, s));
-        OEM_HIP(hipStreamSynchronize(s));
-        int mm = m;
-        for (int k = 0; k < m; ++k)
-            if (!(hT[MAXL + k] > 1e-13 * std::fabs(hT[k]))) { mm = k + 1; break; }     // breakdown: T is exact
-        theta = tridiag_max_host(hT, hT + MAXL, mm);
-        if (mm < m) { lz_capped = false; break; }
-        // the stop rule of the register-resident engines (path_dev.hpp: lanczos_converged) on the top Ritz values of the leading
-        // blocks T_{m-16}, T_{m-8}, T_m, which the host has for free: moved by <= 1e-14 relative over the last 8 steps, or two
-        // successive moves that decay so fast that their geometric tail is <= 1e-12 relative
-        if (m >= 24) {
-            const double t1 = tridiag_max_host(hT, hT + MAXL, m - 8), t0 = tridiag_max_host(hT, hT + MAXL, m - 16);
-            const double mv = theta - t1, mvp = t1 - t0, ath = std::fabs(theta);
-            if (mv <= 1e-14 * ath || (mv < 0.01 * mvp && mv * mv <= OEM_LANCZOS_TAIL_TOL * ath * (mvp - mv))) { lz_capped = false; break; }
-        }
-        if (theta_prev > 0 && std::fabs(theta - theta_prev) <= 1e-12 * std::fabs(theta)) { lz_capped = false; break; }
-        theta_prev = theta;
+        LanczosLook look;
+        if (int rc = lanczos_look_on_stream(s, T, hT, m, q, theta_prev, &look)) return rc;
+        *theta_out = look.theta; *capped_out = look.capped;
+        if (look.stop) break;
+        theta_prev = look.theta;
     }
-    if (mmax >= q) lz_capped = false;                   // the whole Krylov space
-    const double d = d_given ? a.d_fixed : theta * 1.005;     // ref src/oem_dense.h:498
+    *m_out = m;
+    return 0;
+}
 
-    hipLaunchKernelGGL(path_init_kernel, dim3(1), dim3(1024), 0, s, a, st, beta, d, theta, m, lz_capped ? 1 : 0);
-    OEM_HIP(hipGetLastError());
-    if (a.npen == 0) return 0;
-
-    // ---- fused engine when the operators are row-local and nothing needs a global sum per iteration
+// Which engine runs the path behind the eigen step: decided from PathArgs, the alignment of XX, the switches and the packed buffer
+enum LargeEngine {
+    LARGE_FUSED,           // the operators are row-local and nothing needs a global sum per iteration: one launch per iteration
+                           // (oem_fused_kernel, at q = 4096 the symmetric-tile oem_symfused_kernel)
+    LARGE_HEAD_PAIRS,      // element-wise penalties at every other q > 1024: (head, product) pairs over the packed triangle
+                           // (... and group operators whose groups are runs of <= 32 neighbouring coordinates, PathArgs::grp_head: sympk_head_kernel<true>)
+                           // (... and Nesterov's step / compute.loss: their sums over all coordinates are taken one launch later, sympk_head_kernel<.., true>)
+    LARGE_REPLICATED,      // everything else up to q = 2048 (one launch per iteration, every workgroup thresholds the whole of u).
+                           // Beyond, the packed products + slot sum + update kernel are faster (tools/scattered_groups_time.py, grp.lasso with 60 scattered groups,
+                           // us per iteration: q = 3,000 65.9 -> 22.4, 4,096 47.0 -> 29.0; but 1,536 13.9 -> 15.7, 2,048 15.6 -> 15.8: three launches against one)
+    LARGE_UPDATE_PAIRS     // (product, update) pairs: whatever is left
+};
+static bool large_grp_head(const PathArgs &a) { return a.grp_head > 0 && a.grp_head <= 3 && a.ngroups > 0; }
+static LargeEngine large_engine(const LargeRun &R)
+{
+    const PathArgs &a = R.a;
+    const bool no_fused = sw().OEM_NO_FUSED.set;
     const bool elementwise = a.ngroups == 0 && !a.accelerate && !a.compute_loss && !a.sinv;
-    const bool fused_ok = elementwise && (q == 512 || q == 1024 || q == 2048 || q == 4096) &&
-                          (((uintptr_t)a.xx) & 15) == 0 && !sw().OEM_NO_FUSED.set;
-    if (fused_ok) {
-        double *fbase = T + 2 * MAXL + 64;
-        FState *S = reinterpret_cast<FState *>(fbase);
-        int *fdone = reinterpret_cast<int *>(fbase + 8);
-        double *Bv = fbase + 16;
-        int *flags = reinterpret_cast<int *>(Bv + 2 * (size_t)(q + 8));
-        int blocks = (q + 3) / 4;
-        if (blocks > num_cu * 2) blocks = num_cu * 2;
-        if (blocks > FMAXB) blocks = FMAXB;
-        const bool sym = sym_ok;
-        SState *SS = reinterpret_cast<SState *>(SP + 2 * (size_t)(q / SYM_TB) * q);      // behind the partial vectors (sym_part_doubles)
-        static_assert(2 * sizeof(SState) <= 16 * sizeof(double), "SState[2] must fit the 16 spare doubles of the partial area");
-        if (sym) hipLaunchKernelGGL(sym_init_kernel, dim3(1), dim3(1), 0, s, SS, a);
-        else hipLaunchKernelGGL(fused_init_kernel, dim3(1), dim3(1), 0, s, S, a.npen);
-        auto enq = [&](int count) {
-            for (int k = 0; k < count; ++k) {
-                const int par = k & 1;
-                if (sym) hipLaunchKernelGGL((oem_symfused_kernel<32>), dim3(sym_nwg(32)), dim3(256), 0, s, a, SS, Bv, SP, flags, fdone, par, d);
-                else if (q == 512) hipLaunchKernelGGL((oem_fused_kernel<8>), dim3(blocks), dim3(256), 0, s, a, S, Bv, flags, fdone, par, d);
-                else if (q == 1024) hipLaunchKernelGGL((oem_fused_kernel<16>), dim3(blocks), dim3(256), 0, s, a, S, Bv, flags, fdone, par, d);
-                else if (q == 2048) hipLaunchKernelGGL((oem_fused_kernel<32>), dim3(blocks), dim3(256), 0, s, a, S, Bv, flags, fdone, par, d);
-                else hipLaunchKernelGGL((oem_fused_kernel<64>), dim3(blocks), dim3(256), 0, s, a, S, Bv, flags, fdone, par, d);
-            }
-        };
-        return replay_batches(s, enq, fdone, reinterpret_cast<int *>(host_scratch), (long long)a.npen * a.nl * ((long long)a.maxit + 2) + 8, "fused engine");
-    }
+    if (elementwise && R.power_of_two_q() && R.aligned && !no_fused) return LARGE_FUSED;
+    if (R.spk && (a.ngroups == 0 || large_grp_head(a)) && R.K.qpad / SPK_HC <= FMAXB && !no_fused) return LARGE_HEAD_PAIRS;
+    if (R.q <= 4096 && !no_fused && !(R.spk && R.q > 2048)) return LARGE_REPLICATED;
+    return LARGE_UPDATE_PAIRS;
+}
 
-    // ---- element-wise penalties at every other q > 1024: (head, product) pairs over the packed triangle
-    // (... and group operators whose groups are runs of <= 32 neighbouring coordinates, PathArgs::grp_head: the same pairs, sympk_head_kernel<true>)
-    // (... and Nesterov's step / compute.loss: their sums over all coordinates are taken one launch later, sympk_head_kernel<.., true>)
-    const bool grp_head = a.grp_head > 0 && a.grp_head <= 3 && a.ngroups > 0;
+static int run_large_fused(LargeRun &R, double d)
+{
+    hipStream_t s = R.s;
+    const PathArgs &a = R.a;
+    const int q = R.q;
+    FState *S = in_as<FState>(a.work, R.W.fstate);
+    int *fdone = in_as<int>(a.work, R.W.fdone), *flags = in_as<int>(a.work, R.W.flags);
+    double *Bv = R.work(R.W.Bv), *SP = R.work(R.W.sym_part);
+    SState *SS = in_as<SState>(a.work, R.W.sym_state);               // behind the partial vectors
+    int blocks = R.row_blocks();
+    if (blocks > FMAXB) blocks = FMAXB;
+    const bool sym = R.sym_ok;
+    if (sym) hipLaunchKernelGGL(sym_init_kernel, dim3(1), dim3(1), 0, s, SS, a);
+    else hipLaunchKernelGGL(fused_init_kernel, dim3(1), dim3(1), 0, s, S, a.npen);
+    auto enq = [&](int count) {
+        for (int k = 0; k < count; ++k) {
+            const int par = k & 1;
+            if (sym) hipLaunchKernelGGL((oem_symfused_kernel<32>), dim3(sym_nwg(32)), dim3(256), 0, s, a, SS, Bv, SP, flags, fdone, par, d);
+            else if (q == 512) hipLaunchKernelGGL((oem_fused_kernel<8>), dim3(blocks), dim3(256), 0, s, a, S, Bv, flags, fdone, par, d);
+            else if (q == 1024) hipLaunchKernelGGL((oem_fused_kernel<16>), dim3(blocks), dim3(256), 0, s, a, S, Bv, flags, fdone, par, d);
+            else if (q == 2048) hipLaunchKernelGGL((oem_fused_kernel<32>), dim3(blocks), dim3(256), 0, s, a, S, Bv, flags, fdone, par, d);
+            else hipLaunchKernelGGL((oem_fused_kernel<64>), dim3(blocks), dim3(256), 0, s, a, S, Bv, flags, fdone, par, d);
+        }
+    };
+    return replay_batches(s, 128, enq, fdone, R.hdone, path_iteration_cap(a, 2), "fused engine");
+}
+
+static int run_large_head_pairs(LargeRun &R, double d)
+{
+    hipStream_t s = R.s;
+    const PathArgs &a = R.a;
+    const SpkWork &K = R.K;
     const bool head_gen = a.accelerate || a.compute_loss;
-    if (spk && (a.ngroups == 0 || grp_head) && spk_qpad / SPK_HC <= FMAXB && !sw().OEM_NO_FUSED.set) {
-        spk_pack();
-        int *flags = reinterpret_cast<int *>(spk_B + 2 * (size_t)spk_qpad);
-        SState *SS = reinterpret_cast<SState *>(spk_B + 2 * (size_t)spk_qpad + FMAXB);
-        int *fdone = reinterpret_cast<int *>(spk_B + 2 * (size_t)spk_qpad + FMAXB + 16);
-        int *nz32 = reinterpret_cast<int *>(spk_B + 2 * (size_t)spk_qpad + FMAXB + 16 + 8);      // [2][qpad / 32]: which 32-coordinate pieces of B[parity] hold a non-zero
-        double *gen = spk_B + 2 * (size_t)spk_qpad + FMAXB + 16 + 8 + spk_qpad / 32 + 8;          // the head's parts of the sums over all coordinates (zeroed with B)
-        hipLaunchKernelGGL(sym_init_kernel, dim3(1), dim3(1), 0, s, SS, a);
-        auto enq = [&](int count) {
-            for (int k = 0; k < count; ++k) {
-                const int par = k & 1;
-                const int hb = grp_head ? a.grp_head : 0;
-                void (*hk)(PathArgs, SState *, double *, const double *, int *, int *, int, double, int, int, int *, double *) =
-                    head_gen ? (hb == 0 ? sympk_head_kernel<0, true> : hb == 1 ? sympk_head_kernel<1, true> : hb == 2 ? sympk_head_kernel<2, true> : sympk_head_kernel<3, true>)
-                             : (hb == 0 ? sympk_head_kernel<0, false> : hb == 1 ? sympk_head_kernel<1, false> : hb == 2 ? sympk_head_kernel<2, false> : sympk_head_kernel<3, false>);
-                hipLaunchKernelGGL(hk, dim3(spk_qpad / SPK_HC), dim3(256), 0, s, a, SS, spk_B, spk_P, flags, fdone, par, d, spk_nb, spk_qpad, nz32, head_gen ? gen : (double *)nullptr);
-                hipLaunchKernelGGL(sympk_gemv_kernel, dim3(spk_nt), dim3(256), 0, s, a.sympk, q, spk_qpad, spk_B + (size_t)(par ^ 1) * spk_qpad, spk_P, fdone,
-                                   (const int *)(nz32 + (size_t)(par ^ 1) * (spk_qpad / SPK_HC)));
-            }
-        };
-        return replay_batches(s, enq, fdone, reinterpret_cast<int *>(host_scratch), (long long)a.npen * a.nl * ((long long)a.maxit + 2) + 8, "packed-triangle engine");
-    }
+    R.spk_pack();
+    double *P = R.pk(K.P), *B = R.pk(K.B);
+    int *flags = in_as<int>(a.sympk, K.flags), *fdone = in_as<int>(a.sympk, K.done);
+    SState *SS = in_as<SState>(a.sympk, K.sstate);
+    int *nz32 = in_as<int>(a.sympk, K.nz32);             // [2][qpad / 32]: which 32-coordinate pieces of B[parity] hold a non-zero
+    double *gen = R.pk(K.gen);                           // the head's parts of the sums over all coordinates (zeroed with B)
+    const int hb = large_grp_head(a) ? a.grp_head : 0;
+    void (*hk)(PathArgs, SState *, double *, const double *, int *, int *, int, double, int, int, int *, double *) =
+        head_gen ? (hb == 0 ? sympk_head_kernel<0, true> : hb == 1 ? sympk_head_kernel<1, true> : hb == 2 ? sympk_head_kernel<2, true> : sympk_head_kernel<3, true>)
+                 : (hb == 0 ? sympk_head_kernel<0, false> : hb == 1 ? sympk_head_kernel<1, false> : hb == 2 ? sympk_head_kernel<2, false> : sympk_head_kernel<3, false>);
+    hipLaunchKernelGGL(sym_init_kernel, dim3(1), dim3(1), 0, s, SS, a);
+    auto enq = [&](int count) {
+        for (int k = 0; k < count; ++k) {
+            const int par = k & 1;
+            hipLaunchKernelGGL(hk, dim3(K.qpad / SPK_HC), dim3(256), 0, s, a, SS, B, P, flags, fdone, par, d, K.nblk, K.qpad, nz32, head_gen ? gen : (double *)nullptr);
+            hipLaunchKernelGGL(sympk_gemv_kernel, dim3(K.ntile), dim3(256), 0, s, a.sympk, R.q, K.qpad, B + (size_t)(par ^ 1) * K.qpad, P, fdone,
+                               (const int *)(nz32 + (size_t)(par ^ 1) * (K.qpad / SPK_HC)));
+        }
+    };
+    return replay_batches(s, 128, enq, fdone, R.hdone, path_iteration_cap(a, 2), "packed-triangle engine");
+}
 
-    // ---- replicated-update fused engine: everything else up to q = 2048 (one launch per iteration, every workgroup thresholds the whole of u).
-    // Beyond, the packed products + slot sum + update kernel are faster (tools/scattered_groups_time.py, grp.lasso with 60 scattered groups,
-    // us per iteration: q = 3,000 65.9 -> 22.4, 4,096 47.0 -> 29.0; but 1,536 13.9 -> 15.7, 2,048 15.6 -> 15.8: three launches against one)
-    const bool rep_ok = q <= 4096 && !sw().OEM_NO_FUSED.set && !(spk && q > 2048);
-    if (rep_ok) {
-        double *fbase = T + 2 * MAXL + 64;
-        int *fdone = reinterpret_cast<int *>(fbase + 8);
-        double *Bv = fbase + 16;
-        double *gbase = Bv + 2 * (size_t)(q + 8) + FMAXB;
-        GState *S = reinterpret_cast<GState *>(gbase);
-        double *Uv = gbase + 16;
-        int blocks = (q + 3) / 4;
-        if (blocks > num_cu * 2) blocks = num_cu * 2;
-        const size_t shb = sizeof(double) * (size_t)(2 * q + (a.ngroups > 0 ? a.ngroups : 0) + 8);
-        const bool full = (q == 512 || q == 1024 || q == 2048 || q == 4096) && (((uintptr_t)a.xx) & 15) == 0;
-        // kernel for this q: VPL = 8, 16, 32 or 64 columns per lane
-        void (*kern)(PathArgs, GState *, double *, double *, int *, int, double);
-        if (q <= 512) kern = full ? oem_fused_rep_kernel<8, true> : oem_fused_rep_kernel<8, false>;
-        else if (q <= 1024) kern = full ? oem_fused_rep_kernel<16, true> : oem_fused_rep_kernel<16, false>;
-        else if (q <= 2048) kern = full ? oem_fused_rep_kernel<32, true> : oem_fused_rep_kernel<32, false>;
-        else kern = full ? oem_fused_rep_kernel<64, true> : oem_fused_rep_kernel<64, false>;
-        if (shb > 64 * 1024) OEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
-        hipLaunchKernelGGL(fused_rep_init_kernel, dim3(1), dim3(1), 0, s, S, a.npen, a.penalty, a.lambda_out);
-        auto enq = [&](int count) {
-            for (int k = 0; k < count; ++k) hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), shb, s, a, S, Uv, Bv, fdone, k & 1, d);
-        };
-        return replay_batches(s, enq, fdone, reinterpret_cast<int *>(host_scratch), (long long)a.npen * a.nl * ((long long)a.maxit + 3) + 8, "fused engine");
-    }
+static int run_large_replicated(LargeRun &R, double d)
+{
+    hipStream_t s = R.s;
+    const PathArgs &a = R.a;
+    const int q = R.q;
+    int *fdone = in_as<int>(a.work, R.W.fdone);
+    double *Bv = R.work(R.W.Bv), *Uv = R.work(R.W.Uv);
+    GState *S = in_as<GState>(a.work, R.W.gstate);
+    const int blocks = R.row_blocks();
+    const size_t shb = sizeof(double) * (size_t)(2 * q + (a.ngroups > 0 ? a.ngroups : 0) + 8);
+    const bool full = R.power_of_two_q() && R.aligned;
+    // kernel for this q: VPL = 8, 16, 32 or 64 columns per lane
+    void (*kern)(PathArgs, GState *, double *, double *, int *, int, double);
+    if (q <= 512) kern = full ? oem_fused_rep_kernel<8, true> : oem_fused_rep_kernel<8, false>;
+    else if (q <= 1024) kern = full ? oem_fused_rep_kernel<16, true> : oem_fused_rep_kernel<16, false>;
+    else if (q <= 2048) kern = full ? oem_fused_rep_kernel<32, true> : oem_fused_rep_kernel<32, false>;
+    else kern = full ? oem_fused_rep_kernel<64, true> : oem_fused_rep_kernel<64, false>;
+    if (shb > 64 * 1024) OEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
+    hipLaunchKernelGGL(fused_rep_init_kernel, dim3(1), dim3(1), 0, s, S, a.npen, a.penalty, a.lambda_out);
+    auto enq = [&](int count) {
+        for (int k = 0; k < count; ++k) hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), shb, s, a, S, Uv, Bv, fdone, k & 1, d);
+    };
+    return replay_batches(s, 128, enq, fdone, R.hdone, path_iteration_cap(a, 3), "fused engine");
+}
 
-    // ---- path: (gemv, update) pairs replayed in batches from a hipGraph (eager launches are host-bound at ~3.5 us
-    //      each); the host polls the done word once per batch.  Fusing the pair into one launch with a last-arriver
-    //      hand-off was measured and is NOT faster: the agent-scope release + acquire cost what the boundary costs.
+// (gemv, update) pairs replayed in batches from a hipGraph; the host polls the done word once per batch.  Fusing the pair into one
+// launch with a last-arriver hand-off was measured and is NOT faster: the agent-scope release + acquire cost what the boundary costs.
+static int run_large_update_pairs(LargeRun &R)
+{
+    hipStream_t s = R.s;
+    const PathArgs &a = R.a;
+    const int q = R.q;
+    LState *st = R.st();
+    double *beta = R.work(R.W.beta), *g = R.work(R.W.g);
     double *uf = nullptr;
     const size_t sh = update_lds(a, &uf);                            // (U and F exist for group operators only)
     // (1024 < q <= 8192: the operands in registers, every independent load of the kernel issued at once)
@@ -1980,15 +2023,38 @@ int run_path_large(hipStream_t s, const PathArgs &a, double *host_scratch)
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
         if (e != hipSuccess) { set_error("hipFuncSetAttribute(LDS %zu): %s", sh, hipGetErrorString(e)); return OEMGPU_ERR_HIP; }
     }
-    if (spk) spk_pack();
-    auto enqueue = [&](int count) {
+    if (R.spk) R.spk_pack();
+    int *nz = R.spk_nz();
+    auto enq = [&](int count) {
         for (int k = 0; k < count; ++k) {
-            if (spk) spk_gemv(beta, g, &st->done, spk_nz);            // (packed before the capture, below; blocks of zeros skipped by the update kernel's flags)
-            else (void)launch_gemv(s, a.xx, q, beta, g, &st->done, num_cu);
-            hipLaunchKernelGGL(updk, dim3(1), dim3(1024), sh, s, a, st, beta, g, uf, spk_nz);
+            if (R.spk) R.spk_gemv(beta, g, &st->done, nz);            // (packed before the capture, above; blocks of zeros skipped by the update kernel's flags)
+            else (void)launch_gemv(s, a.xx, q, beta, g, &st->done, R.num_cu);
+            hipLaunchKernelGGL(updk, dim3(1), dim3(1024), sh, s, a, st, beta, g, uf, nz);
         }
     };
-    return replay_batches(s, enqueue, &st->done, reinterpret_cast<int *>(host_scratch), (long long)a.npen * a.nl * ((long long)a.maxit + 2) + 8, "large-p engine");
+    return replay_batches(s, 128, enq, &st->done, R.hdone, path_iteration_cap(a, 2), "large-p engine");
+}
+
+// host_scratch: pinned host memory (>= 8 KB)
+int run_path_large(hipStream_t s, const PathArgs &a, double *host_scratch)
+{
+    LargeRun R(s, a, host_scratch);
+    OEM_HIP(hipMemsetAsync(a.work, 0, sizeof(double) * R.W.total, s));
+    double theta = 0.0;
+    int m = 0;
+    bool lz_capped = true;
+    if (int rc = large_eigen_step(R, host_scratch, &theta, &m, &lz_capped)) return rc;
+    const double d = a.d_fixed > 0.0 ? a.d_fixed : theta * 1.005;     // ref src/oem_dense.h:498
+    hipLaunchKernelGGL(path_init_kernel, dim3(1), dim3(1024), 0, s, a, R.st(), R.work(R.W.beta), d, theta, m, lz_capped ? 1 : 0);
+    OEM_HIP(hipGetLastError());
+    if (a.npen == 0) return 0;
+    switch (large_engine(R)) {
+    case LARGE_FUSED: return run_large_fused(R, d);
+    case LARGE_HEAD_PAIRS: return run_large_head_pairs(R, d);
+    case LARGE_REPLICATED: return run_large_replicated(R, d);
+    case LARGE_UPDATE_PAIRS: break;
+    }
+    return run_large_update_pairs(R);
 }
 
 // ================================================================================================
@@ -2009,37 +2075,10 @@ int run_path_large(hipStream_t s, const PathArgs &a, double *host_scratch)
 // ================================================================================================
 enum { W_EIG = 0, W_OEM = 1, W_XB = 2, W_XTV = 3 };
 
-static int wide_nr(int n)
-{
-    static const int sizes[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};
-    const int need = (n + 63) / 64;
-    for (int v : sizes) if (v >= need) return v;
-    return 0;
-}
-// waves per workgroup: as many as the combine buffer in LDS (NW x 64 NR doubles <= 64 KB) and the registers (3-4 NR doubles per
-// lane) allow -- a wave walks its columns one after the other (dot product -> wave sum -> operator -> update is a serial chain of
-// ~400 cycles per column), so the CU needs several waves per SIMD to keep loads in flight
-__host__ __device__ constexpr int wide_nw(int nr) { return nr <= 8 ? 16 : (nr <= 16 ? 8 : 4); }
-WideLayout wide_layout(int64_t n)
-{
-    WideLayout L;
-    L.nb = n <= 2048 ? 1 : (int)((n + 2047) / 2048);
-    L.rb = (int)((n + L.nb - 1) / L.nb);
-    L.nr = wide_nr(L.rb);
-    return L;
-}
-int wide_workgroups(int n, int p)
-{
-    const int nw = wide_nw(wide_layout(n).nr);
-    int w = (p + nw - 1) / nw;                           // small p is latency-bound: a column per wave, as many CUs as that gives
-    if (w > 256) w = 256;                                // one workgroup per CU: every partial vector is read back by the reduction
-    return w < 1 ? 1 : w;
-}
-// P[W][npad] | r | t | v | vp | w (rows() each) | T[2 MAXL + 64] | SState[2] (16) | done (2) | flags[2][FMAXB] ints | gb[nb][p + 8]
+// (wide_layout, wide_workgroups and the scratch's regions: path_large_layout.hpp)
 size_t wide_scratch_doubles(int n, int p)
 {
-    const WideLayout L = wide_layout(n);
-    const size_t own = (size_t)wide_workgroups(n, p) * L.npad() + 5 * (size_t)L.rows() + 2 * MAXL + 64 + 16 + 2 + FMAXB + 64 + (size_t)L.nb * (p + 8);
+    const size_t own = wide_scratch(n, p, wide_workgroups(n, p), wide_layout(n)).own_total;
     size_t coop = path_wcoop_xchg_doubles(n, p);               // the persistent engines' exchange buffers live in the same scratch
     if (path_wstream_xchg_doubles((int)n) > coop) coop = path_wstream_xchg_doubles((int)n);
     if (path_wres_xchg_doubles(n, p) > coop) coop = path_wres_xchg_doubles(n, p);
@@ -2437,16 +2476,16 @@ __global__ __launch_bounds__(256) void wide_block_sum_kernel(const double *__res
 }
 
 // lambda_max(X X'/n) of every p >= n engine of this file: Lanczos on vectors of `len` entries (v, v_prev, w; T the tridiagonal), the
-// product w = X (X' v) / n enqueued by `product()`, the host's look every 16 steps -- the breakdown rule (T is exact), the tail rule
-// of run_path_large, the stagnation rule -- and at most min(n, MAXL) steps.  hT: pinned host memory for T.
+// product w = X (X' v) / n enqueued by `product()`, the host's look every 16 steps (lanczos_look) and at most min(n, MAXL) steps.
+// hT: pinned host memory for T.
 // after_init(): enqueued between lanczos_init_kernel and the first product (a fold fit restricts the start vector to its kept rows there).
 template <typename F, typename G>
 static int lanczos_wide_host(hipStream_t s, int len, int n, double *v, double *vp, double *w, double *T, double *hT, F &&product,
                              double *theta_out, int *steps_out, bool *capped_out, G &&after_init)
 {
     const int mmax = n < MAXL ? n : MAXL;
-    double theta = 0.0, theta_prev = -1.0;
-    bool lz_capped = true;
+    LanczosLook look{0.0, false, true};
+    double theta_prev = -1.0;
     int m = 0;
     hipLaunchKernelGGL(lanczos_init_kernel, dim3(1), dim3(1024), 0, s, len, v, vp);
     after_init();
@@ -2456,24 +2495,11 @@ static int lanczos_wide_host(hipStream_t s, int len, int n, double *v, double *v
             product();
             hipLaunchKernelGGL(lanczos_update_kernel, dim3(1), dim3(1024), 0, s, len, m, v, vp, w, T);
         }
-        OEM_HIP(hipGetLastError());
-        OEM_HIP(hipMemcpyAsync(hT, T, sizeof(double) * 2 * MAXL, hipMemcpyDeviceToHost, s));
-        OEM_HIP(hipStreamSynchronize(s));
-        int mm = m;
-        for (int k = 0; k < m; ++k)
-            if (!(hT[MAXL + k] > 1e-13 * std::fabs(hT[k]))) { mm = k + 1; break; }     // breakdown: T is exact
-        theta = tridiag_max_host(hT, hT + MAXL, mm);
-        if (mm < m) { lz_capped = false; break; }
-        if (m >= 24) {                                                  // the stop rule of run_path_large
-            const double t1 = tridiag_max_host(hT, hT + MAXL, m - 8), t0 = tridiag_max_host(hT, hT + MAXL, m - 16);
-            const double mv = theta - t1, mvp = t1 - t0, ath = std::fabs(theta);
-            if (mv <= 1e-14 * ath || (mv < 0.01 * mvp && mv * mv <= OEM_LANCZOS_TAIL_TOL * ath * (mvp - mv))) { lz_capped = false; break; }
-        }
-        if (theta_prev > 0 && std::fabs(theta - theta_prev) <= 1e-12 * std::fabs(theta)) { lz_capped = false; break; }
-        theta_prev = theta;
+        if (int rc = lanczos_look_on_stream(s, T, hT, m, n, theta_prev, &look)) return rc;
+        if (look.stop) break;
+        theta_prev = look.theta;
     }
-    if (mmax >= n) lz_capped = false;
-    *theta_out = theta; *steps_out = m; *capped_out = lz_capped;
+    *theta_out = look.theta; *steps_out = m; *capped_out = look.capped;
     return 0;
 }
 template <typename F>
@@ -2493,13 +2519,14 @@ static int run_path_wide_blocks(hipStream_t s, const PathArgs &a, const WideArgs
 {
     const int q = a.p, n = wd.n, W = wide_workgroups(n, q), cpw = (q + W - 1) / W, nb = wd.lay.nb;
     constexpr int NT = 64 * wide_nw(NR);
-    const long long npad = 64 * NR, rows = wd.lay.rows();
-    double *P = wd.scratch, *t = P + (size_t)W * npad + rows, *v = t + rows, *vp = v + rows, *w = vp + rows;
-    double *T = w + rows;
-    double *gb = T + 2 * MAXL + 64 + 16 + 2 + FMAXB + 64;
-    LState *st = reinterpret_cast<LState *>(a.work);
-    double *beta = a.work + STATE_DBL, *g = beta + (q + 8);
-    OEM_HIP(hipMemsetAsync(a.work, 0, sizeof(double) * path_large_work_doubles(q, 0), s));
+    const long long npad = 64 * NR;
+    const WideScratch SC = wide_scratch(n, q, W, wd.lay);
+    const LargeWork LW = large_work(q);
+    double *P = in(wd.scratch, SC.P), *t = in(wd.scratch, SC.t), *v = in(wd.scratch, SC.v), *vp = in(wd.scratch, SC.vp), *w = in(wd.scratch, SC.w);
+    double *T = in(wd.scratch, SC.T), *gb = in(wd.scratch, SC.gb);
+    LState *st = in_as<LState>(a.work, LW.state);
+    double *beta = in(a.work, LW.beta), *g = in(a.work, LW.g);
+    OEM_HIP(hipMemsetAsync(a.work, 0, sizeof(double) * LW.total, s));
     OEM_HIP(hipMemsetAsync(wd.scratch, 0, sizeof(double) * wide_scratch_doubles(n, q), s));
     const size_t lds = sizeof(double) * ((size_t)wide_nw(NR) * (size_t)npad + 2 * (size_t)cpw);
     if (lds > 64 * 1024) {
@@ -2524,7 +2551,7 @@ static int run_path_wide_blocks(hipStream_t s, const PathArgs &a, const WideArgs
     double theta = 0.0;
     bool lz_capped = true;
     int m = 0;
-    if (int lrc = lanczos_wide_host(s, (int)rows, n, v, vp, w, T, host_scratch, [&] { xtv(v, g, nullptr); xb(g, w, nullptr); }, &theta, &m, &lz_capped)) return lrc;
+    if (int lrc = lanczos_wide_host(s, (int)wd.lay.rows(), n, v, vp, w, T, host_scratch, [&] { xtv(v, g, nullptr); xb(g, w, nullptr); }, &theta, &m, &lz_capped)) return lrc;
     const double d = theta * 1.005;                     // ref src/oem_dense.h:498
     OEM_HIP(hipMemsetAsync(g, 0, sizeof(double) * (size_t)(q + 8), s));
     hipLaunchKernelGGL(path_init_kernel, dim3(1), dim3(1024), 0, s, a, st, beta, d, theta, m, lz_capped ? 1 : 0);
@@ -2540,53 +2567,27 @@ static int run_path_wide_blocks(hipStream_t s, const PathArgs &a, const WideArgs
             hipLaunchKernelGGL(path_update_kernel<0>, dim3(1), dim3(1024), shu, s, a, st, beta, g, uf, (int *)nullptr);
         }
     };
-    const int FB = 16;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        enq(FB);
-        if (hipStreamEndCapture(s, &graph) != hipSuccess || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            graph = nullptr; exec = nullptr;
-            (void)hipGetLastError();
-        }
-    } else (void)hipGetLastError();
-    const long long max_it = (long long)a.npen * a.nl * ((long long)a.maxit + 3) + 8;
-    long long launched = 0;
-    int *hdone = reinterpret_cast<int *>(host_scratch);
-    int rc = 0;
-    for (;;) {
-        if (exec) { if (hipGraphLaunch(exec, s) != hipSuccess) { set_error("hipGraphLaunch failed"); rc = OEMGPU_ERR_HIP; break; } }
-        else enq(FB);
-        if (hipGetLastError() != hipSuccess) { set_error("wide engine: launch failed"); rc = OEMGPU_ERR_HIP; break; }
-        launched += FB;
-        if (hipMemcpyAsync(hdone, &st->done, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) { set_error("wide engine: device error"); rc = OEMGPU_ERR_HIP; break; }
-        if (*hdone) break;
-        if (caller_interrupted()) { set_error("interrupted by the caller"); rc = OEMGPU_ERR_INTERRUPTED; break; }
-        if (launched > max_it) { set_error("wide engine did not finish within %lld iterations", max_it); rc = OEMGPU_ERR_INTERNAL; break; }
-    }
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    return rc;
+    return replay_batches(s, 16, enq, (const int *)&st->done, reinterpret_cast<int *>(host_scratch), path_iteration_cap(a, 3), "wide engine");
 }
 
 template <int NR>
 static int run_path_wide_nr(hipStream_t s, const PathArgs &a, const WideArgs &wd, double *host_scratch)
-{    if (wd.lay.nb > 1) return run_path_wide_blocks<NR>(s, a, wd, host_scratch);
+{
+    if (wd.lay.nb > 1) return run_path_wide_blocks<NR>(s, a, wd, host_scratch);
 
     const int q = a.p, n = wd.n, W = wide_workgroups(n, q), cpw = (q + W - 1) / W;
     constexpr int NT = 64 * wide_nw(NR);
     const long long npad = 64 * NR;
     if (wd.lay.npad() != npad) { set_error("internal: wide engine padding"); return OEMGPU_ERR_INTERNAL; }
-    double *P = wd.scratch, *r = P + (size_t)W * npad, *t = r + npad, *v = t + npad, *vp = v + npad, *w = vp + npad;
-    double *T = w + npad;
-    SState *SS = reinterpret_cast<SState *>(T + 2 * MAXL + 64);
-    int *fdone = reinterpret_cast<int *>(T + 2 * MAXL + 64 + 16);
-    int *flags = reinterpret_cast<int *>(T + 2 * MAXL + 64 + 16 + 2);
-    LState *st = reinterpret_cast<LState *>(a.work);
-    double *beta = a.work + STATE_DBL, *g = beta + (q + 8);
-    OEM_HIP(hipMemsetAsync(a.work, 0, sizeof(double) * path_large_work_doubles(q, 0), s));
+    const WideScratch SC = wide_scratch(n, q, W, wd.lay);
+    const LargeWork LW = large_work(q);
+    double *P = in(wd.scratch, SC.P), *r = in(wd.scratch, SC.r), *t = in(wd.scratch, SC.t), *v = in(wd.scratch, SC.v), *vp = in(wd.scratch, SC.vp);
+    double *w = in(wd.scratch, SC.w), *T = in(wd.scratch, SC.T);
+    SState *SS = in_as<SState>(wd.scratch, SC.sstate);
+    int *fdone = in_as<int>(wd.scratch, SC.done), *flags = in_as<int>(wd.scratch, SC.flags);
+    LState *st = in_as<LState>(a.work, LW.state);
+    double *beta = in(a.work, LW.beta), *g = in(a.work, LW.g);
+    OEM_HIP(hipMemsetAsync(a.work, 0, sizeof(double) * LW.total, s));
     OEM_HIP(hipMemsetAsync(wd.scratch, 0, sizeof(double) * wide_scratch_doubles(n, q), s));
     const size_t lds = sizeof(double) * ((size_t)wide_nw(NR) * (size_t)npad + 2 * (size_t)cpw);
 #define OEM_WIDE_ATTR(MODE)                                                                                                       \
@@ -2639,36 +2640,11 @@ static int run_path_wide_nr(hipStream_t s, const PathArgs &a, const WideArgs &wd
             }
         }
     };
-    const int FB = (fused || gfused) ? 64 : 32;                      // even: every batch starts at parity 0
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        enq(FB);
-        if (hipStreamEndCapture(s, &graph) != hipSuccess || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            graph = nullptr; exec = nullptr;
-            (void)hipGetLastError();
-        }
-    } else (void)hipGetLastError();
-    const long long max_it = (long long)a.npen * a.nl * ((long long)a.maxit + 3) + 8;
-    long long launched = 0;
-    int *hdone = reinterpret_cast<int *>(host_scratch);
-    int rc = 0;
-    for (;;) {
-        if (exec) { if (hipGraphLaunch(exec, s) != hipSuccess) { set_error("hipGraphLaunch failed"); rc = OEMGPU_ERR_HIP; break; } }
-        else enq(FB);
-        if (hipGetLastError() != hipSuccess) { set_error("wide engine: launch failed"); rc = OEMGPU_ERR_HIP; break; }
-        launched += FB;
-        if (hipMemcpyAsync(hdone, (fused || gfused) ? fdone : &st->done, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) { set_error("wide engine: device error"); rc = OEMGPU_ERR_HIP; break; }
-        if (*hdone) break;
-        if (caller_interrupted()) { set_error("interrupted by the caller"); rc = OEMGPU_ERR_INTERRUPTED; break; }
-        if (launched > max_it) { set_error("wide engine did not finish within %lld iterations", max_it); rc = OEMGPU_ERR_INTERNAL; break; }
-    }
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    return rc;
+    const bool one_launch = fused || gfused;                         // batches of 64 / 32 (even: every batch starts at parity 0)
+    return replay_batches(s, one_launch ? 64 : 32, enq, one_launch ? (const int *)fdone : (const int *)&st->done, reinterpret_cast<int *>(host_scratch),
+                          path_iteration_cap(a, 3), "wide engine");
 }
+
 
 int run_path_wide(hipStream_t s, const PathArgs &a, const WideArgs &wd, double *host_scratch)
 {
@@ -2715,12 +2691,13 @@ int run_path_sparse_wide(hipStream_t s, const PathArgs &a, const SpwArgs &A, dou
 {
     const int q = a.p, n = A.n, nk = A.foldid ? A.nk : A.n;
     if (q != A.p || nk < 1 || nk > n) { set_error("internal: sparse wide engine dimensions"); return OEMGPU_ERR_INTERNAL; }
-    double *t = A.vec, *v = t + n, *vp = v + n, *w = vp + n, *T = w + n;
-    LState *st = reinterpret_cast<LState *>(a.work);
-    double *beta = a.work + STATE_DBL, *g = beta + (q + 8);
-    OEM_HIP(hipMemsetAsync(a.work, 0, sizeof(double) * path_large_work_doubles(q, 0), s));
-    static_assert(SPW_T_DOUBLES >= 2 * MAXL, "the Lanczos table fits the sparse engine's workspace");
-    OEM_HIP(hipMemsetAsync(A.vec, 0, sizeof(double) * (4 * (size_t)n + SPW_T_DOUBLES), s));
+    const SpwVec V = spw_vec(n);
+    const LargeWork LW = large_work(q);
+    double *t = in(A.vec, V.t), *v = in(A.vec, V.v), *vp = in(A.vec, V.vp), *w = in(A.vec, V.w), *T = in(A.vec, V.T);
+    LState *st = in_as<LState>(a.work, LW.state);
+    double *beta = in(a.work, LW.beta), *g = in(a.work, LW.g);
+    OEM_HIP(hipMemsetAsync(a.work, 0, sizeof(double) * LW.total, s));
+    OEM_HIP(hipMemsetAsync(A.vec, 0, sizeof(double) * V.total, s));
     const double rn = 1.0 / (double)nk;
     int rc = 0;
     // ---- d = 1.005 lambda_max(X X'/n)
@@ -2751,8 +2728,7 @@ int run_path_sparse_wide(hipStream_t s, const PathArgs &a, const SpwArgs &A, dou
             hipLaunchKernelGGL(path_update_kernel<0>, dim3(1), dim3(1024), shu, s, a, st, beta, g, uf, (int *)nullptr);
         }
     };
-    const long long max_it = (long long)a.npen * a.nl * ((long long)a.maxit + 3) + 8;
-    const int prc = replay_batches(s, enq, (const int *)&st->done, reinterpret_cast<int *>(host_scratch), max_it, "sparse wide engine");
+    const int prc = replay_batches(s, 128, enq, (const int *)&st->done, reinterpret_cast<int *>(host_scratch), path_iteration_cap(a, 3), "sparse wide engine");
     return prc ? prc : rc;
 }
 

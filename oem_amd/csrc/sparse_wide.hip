@@ -248,7 +248,7 @@ SpwPlan spw_plan(int64_t n, int p, int64_t nnz, int64_t longest_row, int64_t lon
     P.row_wgs = (int)((n * P.row_L + 255) / 256);
     P.col_wgs = (int)(((int64_t)p * P.col_L + 255) / 256);
     Bump B;
-    B.take(sizeof(double) * (4 * (size_t)n + SPW_T_DOUBLES));
+    B.take(sizeof(double) * spw_vec_doubles(n));
     B.take(sizeof(int32_t) * ((size_t)n + 1));
     B.take(sizeof(int32_t) * ((size_t)p + 1));
     B.take(64);
