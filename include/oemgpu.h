@@ -750,6 +750,55 @@ int oemgpu_logistic_cv_score_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t 
  * and Z blocks are the column-major call's.  OEMGPU_ERR_ARG on n, p, num_cu < 1, a dtype other than the two or a NULL out;
  * OEMGPU_ERR_UNSUPPORTED for p > 8191. */
 int oemgpu_selftest_logistic_rm_plan(int64_t n, int32_t p, int32_t dtype, int32_t intercept, int32_t num_cu, int64_t *out /* 8 */);
+/* Many binomial responses on one resident x: what m calls of oemgpu_fit_logistic_dense_dev / _rm_dev (`.Call("oem_fit_logistic_dense",
+ * ...)`, ref src/oem_logistic_dense.cpp:30-313, src/oem_logistic_dense.h:397-1094) with the columns of Y return, for hessian.type
+ * "upper.bound".  Y is read through its strides as oemgpu_fit_dense_multi_dev reads it: element (i, r) at y_dev[i y_rs + r y_cs],
+ * row-major (y_cs == 1, y_rs >= m) or column-major (y_rs == 1, y_cs >= n), its padding never loaded.  With the upper bound the
+ * reference builds X'WX at beta = 0 (h :964-965), where every W is 0.25: XX, d = 1.0005 lambda_max(XX) and A = dI - XX do not depend
+ * on y.  They are built ONCE per call (one weighted Gram pass, one Lanczos); the responses then run the reference's loops in
+ * lock-step, at most 64 at a time: one row pass over x per IRLS step for all of them (logistic_multi.hip: eta = X Bt and X'R as two
+ * FP64 MFMA products), one inner OEM launch with a workgroup per response, one stop launch and one host read.  A response that meets
+ * its IRLS stop is frozen for the rest of the lambda (nothing of it is written again; niter is its own step count); the skipped row
+ * pass of the first step of a later lambda (h :861) holds for all.  Every response has its own lambda grid (from its own max |X'y|);
+ * a user lambda is shared.  A response's results do not depend on the others, on its column index or on m.
+ * Outputs, response-major: beta[m][npen][nl][p + 1], lambda_out / niter / loss [m][npen][nl], d[m] (m equal values).
+ * Refused before a device is looked for: a NULL argument, m < 1 and Y strides that are neither layout (OEMGPU_ERR_ARG); what
+ * oemgpu_fit_logistic_dense_dev / _rm_dev refuse, with their codes; hessian_full = 1 (OEMGPU_ERR_UNSUPPORTED: "a full Hessian is one
+ * per response and step: fit each column with fit_logistic_dense"); p + intercept > 1024 (OEMGPU_ERR_UNSUPPORTED: beyond one
+ * workgroup the inner solve is a product of all responses).  OEMGPU_ERR_INTERRUPTED when opts->interrupt (polled once per lock-step
+ * IRLS step) returns non-zero. */
+int oemgpu_fit_logistic_dense_multi_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev, int64_t y_rs,
+                                        int64_t y_cs, int32_t m, int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit,
+                                        double irls_tol, const oemgpu_opts *opts, double *beta, double *lambda_out, int32_t *niter, double *loss,
+                                        double *d);
+int oemgpu_fit_logistic_dense_multi_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                                           int64_t y_rs, int64_t y_cs, int32_t m, int32_t standardize, int32_t intercept, int32_t hessian_full,
+                                           int32_t irls_maxit, double irls_tol, const oemgpu_opts *opts, double *beta, double *lambda_out,
+                                           int32_t *niter, double *loss, double *d);
+/* Host-only plan of the many-response binomial fit (pure arithmetic, runs without a GPU).  layout: 0 column-major x, 1 row-major.
+ * out[0] rows per chunk of the shared row pass (a multiple of 64 that depends on n and num_cu alone), out[1] chunks (chunk c = rows
+ * [c out[0], min(n, (c + 1) out[0]))), out[2] responses per block (16 out[3]), out[3] response tiles per block LT, out[4] the column
+ * band: the 64 out[9] columns a workgroup's accumulators cover (128, 256, 512 or 1024 by p), out[5] LDS bytes of a workgroup,
+ * out[6] MCH = 64, the responses of a lock-step chunk, out[7] lock-step chunks, out[8] response blocks of the widest chunk, out[9]
+ * 16-column tiles per wave, out[10 .. 13] workspace bytes: the panels of a row pass, what the call shares (s, XX, A), a chunk's state
+ * without its per-lambda tables, the Hessian pass's stages (out[6] of oemgpu_selftest_logistic_plan); out[14] their sum; out[15] 1
+ * if the inner solve keeps A in LDS.  OEMGPU_ERR_ARG on n, p, m, num_cu < 1, a layout other than the two or a NULL out;
+ * OEMGPU_ERR_UNSUPPORTED for p + intercept > 1024. */
+#define OEMGPU_LMULTI_PLAN_LEN 16
+int oemgpu_selftest_logistic_multi_plan(int64_t n, int32_t p, int32_t m, int32_t intercept, int32_t layout, int32_t num_cu,
+                                        int64_t *out /* OEMGPU_LMULTI_PLAN_LEN */);
+/* Test infrastructure: ONE shared row pass.  x_dev: column-major float64 (dtype < 0, ld the column stride) or row-major (dtype
+ * OEMGPU_F64 / OEMGPU_F32, ld the row stride); btilde_dev (device, mode 1): m x (p + intercept), response r's entries of beta o s
+ * contiguous with the intercept's first; mode 0: r = y (X'Y), mode 1: the IRLS quantities; live (host, m words, or NULL: all live);
+ * out_dev (device): [m][p + 2], response r's [sum r, X'r, sum of the loss terms] -- written for the live responses only. */
+int oemgpu_selftest_logistic_multi_rows_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                                            int64_t y_rs, int64_t y_cs, int32_t m, const double *btilde_dev, int32_t intercept, int32_t mode,
+                                            const int32_t *live, double *out_dev);
+/* Of this thread's last many-response binomial call (or row-pass selftest): out[0] lock-step IRLS steps, out[1] row passes (the X'Y
+ * passes not counted), out[2] response blocks of those passes that returned without reading x (all their responses frozen), out[3]
+ * inner OEM iterations over all responses, out[4] Gram builds, out[5] Lanczos runs, out[6 .. 8] ms of the row passes / the Gram build
+ * / the inner launches when the context is timing (else 0), out[9] wall ms. */
+int oemgpu_last_logistic_multi_stats(double *out /* 10 */);
 /* `.Call("oem_fit_logistic_sparse", ...)` (ref src/oem_logistic_sparse.cpp:30-313, src/oem_logistic_sparse.h): the binomial fit of a
  * compressed-sparse-column x (a dgCMatrix: colptr[p + 1] with colptr[0] = 0, non-decreasing; rowidx[nnz] in [0, n), strictly increasing
  * inside a column; values[nnz]; explicit zeros allowed).  opts, irls_maxit, irls_tol and the outputs as oemgpu_fit_logistic_dense.  The

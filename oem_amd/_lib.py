@@ -138,6 +138,16 @@ _SIGS = {
     "oemgpu_selftest_xval_multi_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_selftest_xval_multi_fold_moments_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
                                                               C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    # many binomial responses on one x: the loop of m oemgpu_fit_logistic_dense_dev / _rm_dev calls
+    "oemgpu_fit_logistic_dense_multi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(OemgpuOpts)] + _OUT),
+    "oemgpu_fit_logistic_dense_multi_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                                         C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                                         C.POINTER(OemgpuOpts)] + _OUT),
+    "oemgpu_selftest_logistic_multi_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "oemgpu_selftest_logistic_multi_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                                          C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, _ip, C.c_void_p]),
+    "oemgpu_last_logistic_multi_stats": (C.c_int, [_dp]),
     "oemgpu_fit_xtx_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _dp, C.POINTER(OemgpuOpts)] + _OUT),
     "oemgpu_last_shift_in_effect": (C.c_int, [C.c_void_p]),
     "oemgpu_last_shift_advised": (C.c_int, [C.c_void_p]),

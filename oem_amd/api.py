@@ -805,6 +805,138 @@ def oem_fit_logistic_dense(x, y, penalty=None, weights=(), lambda_=(), nlambda=1
     return res
 
 
+def _binary_columns_check(Y):
+    """R/oem.R:250-252 for every column of Y: at most two values.  A device Y is looked at on the device (a column has at most two
+    values iff each of its entries equals the column's minimum or its maximum) and never copied to the host."""
+    if _is_torch_cuda(Y):
+        import torch
+        lo, hi = Y.amin(dim=0, keepdim=True), Y.amax(dim=0, keepdim=True)
+        bad = torch.nonzero(((Y != lo) & (Y != hi)).any(dim=0)).reshape(-1)          # (a NaN equals neither: its column is named)
+        bad = [int(bad[0].item())] if bad.numel() else []
+    else:
+        Yh = np.asarray(Y, dtype=np.float64)
+        bad = [r for r in range(Yh.shape[1]) if len(np.unique(Yh[:, r])) > 2][:1]
+    if bad:
+        raise ValueError(f"y must be a binary outcome: column {bad[0]} of Y takes more than two values")
+
+
+def oem_fit_logistic_dense_multi(x, Y, penalty=None, weights=(), lambda_=(), nlambda=100, lambda_min_ratio=None, alpha=1.0, gamma=3.0,
+                                 tau=0.5, groups=(), penalty_factor=None, group_weights=None, standardize=True, intercept=True, maxit=500,
+                                 tol=1e-7, irls_maxit=100, irls_tol=1e-3, compute_loss=False, hessian_type="upper.bound", varnames=None,
+                                 interrupt=None):
+    """m binomial responses on one resident x: [oem_fit_logistic_dense(x, Y[:, r], **kw) for r in range(m)] with hessian_type
+    "upper.bound", from ONE weighted Gram pass and ONE Lanczos -- at beta = 0 every IRLS weight is 0.25, so X'WX, d and A do not depend
+    on y -- and one read of x per IRLS step for all responses that are still iterating (include/oemgpu.h:
+    oemgpu_fit_logistic_dense_multi_dev).  x: a dense torch tensor on a GPU with p + intercept <= 1024, taken as
+    oem_fit_logistic_dense takes it (row-major float64 / float32 read in place, else column-major float64).  Y: n x m, every column
+    with at most two values; a torch device tensor (float64 with a unit stride in one dimension: read where it lies, checked on the
+    device) or a host array (uploaded once).  oem_fit_logistic_dense's keyword arguments and checks; a user lambda is shared by all
+    responses.  Returns a list of m OemFitBinomial."""
+    L.sync_switches()
+    penalty = _match_penalty(penalty)
+    if hessian_type not in ("upper.bound", "full"):
+        raise ValueError("'arg' should be one of 'upper.bound', 'full'")
+    if getattr(Y, "ndim", None) != 2:
+        raise ValueError("Y must be a matrix of n rows and one column per response")
+    if len(weights) > 0:                                               # R/oem.R:244
+        raise L.OemgpuError(-4, "weights not implemented yet.")
+    host_or_sparse = ("oem_fit_logistic_dense_multi() takes a dense torch tensor on a GPU: a host or sparse x is fitted one response at a "
+                      "time with oem_fit_logistic_dense / oem_fit_logistic_sparse")
+    if isinstance(x, SparseX) or _is_scipy_sparse(x) or _is_torch_sparse(x):
+        raise ValueError(host_or_sparse)
+    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("x must have at least two columns")
+    n, p = x.shape
+    if p < 2:
+        raise ValueError("x must have at least two columns")
+    if Y.shape[0] != n:
+        raise ValueError("x and y lengths do not match")
+    m = int(Y.shape[1])
+    if m < 1:
+        raise ValueError("Y must have at least one column")
+    if hessian_type == "full":
+        raise ValueError("hessian_type='full' builds one Hessian per response and IRLS step: fit each column with oem_fit_logistic_dense")
+    if p + int(bool(intercept)) > 1024:
+        raise ValueError("oem_fit_logistic_dense_multi() serves p + intercept <= 1024: fit each column with oem_fit_logistic_dense")
+    _binary_columns_check(Y)
+    if not _is_torch_cuda(x):
+        raise ValueError(host_or_sparse)
+    if penalty_factor is None:
+        penalty_factor = np.ones(p)
+    penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
+    if len(penalty_factor) != p:
+        raise ValueError("penalty.factor must have same length as number of columns in x")
+    if varnames is None:
+        varnames = [f"V{i + 1}" for i in range(p)]
+    groups, unique_groups, group_weights = _group_setup(penalty, groups, group_weights, p, bool(intercept))
+    if lambda_min_ratio is None:
+        lambda_min_ratio = 0.01 if n < p else 0.0001
+    _common_checks(nlambda, float(lambda_min_ratio), maxit, irls_maxit, tol, irls_tol)
+    lam_list = _lambda_list(lambda_, len(penalty))
+    a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
+              compute_loss, penalty_factor, groups, unique_groups, group_weights, interrupt=interrupt)
+    import torch
+    X = _DeviceX(x, _logistic_rowmajor_in_place)                       # row-major float64 / float32: read where it lies
+    Yd, rs, cs = _device_responses(Y, x.device)
+    beta = np.zeros((m, a.npen, a.nl, p + 1))
+    lam_out = np.zeros((m, a.npen, a.nl))
+    niter = np.zeros((m, a.npen, a.nl), dtype=np.int32)
+    loss = np.zeros((m, a.npen, a.nl))
+    d = np.zeros(m)
+    ctx = context(x.device.index)
+    torch.cuda.current_stream(x.device).synchronize()
+    X.call("fit_logistic_dense_multi", ctx, Yd.data_ptr(), rs, cs, m, int(bool(standardize)), int(bool(intercept)), 0, int(irls_maxit),
+           float(irls_tol), C.byref(a.c), _dptr(beta), _dptr(lam_out), _iptr(niter), _dptr(loss), _dptr(d))
+    return [OemFitBinomial(_decorate(_OneOfMany(beta[r], lam_out[r], niter[r], loss[r], d[r]), penalty, varnames, True, n, p, family="binomial"))
+            for r in range(m)]
+
+
+def logistic_multi_plan(n, p, m, intercept=True, layout=0, num_cu=256):
+    """oemgpu_selftest_logistic_multi_plan (pure host arithmetic) as a dict"""
+    out = (C.c_int64 * 16)()
+    L.check(L.lib().oemgpu_selftest_logistic_multi_plan(int(n), int(p), int(m), int(bool(intercept)), int(layout), int(num_cu), out))
+    keys = ["rows", "row_chunks", "block", "lt", "band", "lds_bytes", "mch", "response_chunks", "blocks", "tiles_per_wave",
+            "panel_bytes", "shared_bytes", "chunk_bytes", "hessian_bytes", "bytes", "a_in_lds"]
+    return dict(zip(keys, [int(v) for v in out]))
+
+
+def logistic_multi_stats():
+    """oemgpu_last_logistic_multi_stats of this thread, as a dict (the ms are 0 unless the context is timing)"""
+    out = (C.c_double * 10)()
+    L.check(L.lib().oemgpu_last_logistic_multi_stats(out))
+    keys = ["steps", "row_passes", "blocks_skipped", "inner_iters", "grams", "lanczos", "rows_ms", "gram_ms", "inner_ms", "wall_ms"]
+    return dict(zip(keys, list(out)))
+
+
+def logistic_multi_rows(x, Y, btilde=None, intercept=True, mode=1, live=None, out=None):
+    """Test infrastructure: oemgpu_selftest_logistic_multi_rows_dev, ONE shared row pass -> numpy [m, p + 2], response r's
+    [sum r, X'r, sum of the loss terms].  x: a torch device tensor read where it lies (column-major float64, row-major float64 /
+    float32); Y: n x m as _device_responses reads it; btilde: [m, p + intercept] (mode 1); live: m words or None; out: a device
+    tensor [m, p + 2] the pass writes the live responses' rows of (default: NaN-filled)."""
+    import torch
+    if not _is_torch_cuda(x) or x.ndim != 2:
+        raise ValueError("x must be a 2-D torch tensor on a GPU")
+    n, p = x.shape
+    if x.dtype == torch.float64 and x.stride(0) == 1 and x.stride(1) >= n:
+        code, ld = -1, x.stride(1)
+    else:
+        code, ld = _rowmajor_dtype(x), x.stride(0)
+        if code is None:
+            raise ValueError("x must be column-major float64, or row-major float64 / float32 with unit column stride")
+    Yd, rs, cs = _device_responses(Y, x.device)
+    m = Yd.shape[1]
+    bt = None if btilde is None else torch.as_tensor(np.ascontiguousarray(btilde, dtype=np.float64), device=x.device)
+    if out is None:
+        out = torch.full((m, p + 2), float("nan"), dtype=torch.float64, device=x.device)
+    lv = None if live is None else np.ascontiguousarray(live, dtype=np.int32)
+    ctx = context(x.device.index)
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_selftest_logistic_multi_rows_dev(ctx, x.data_ptr(), code, n, ld, p, Yd.data_ptr(), rs, cs, m,
+                                                           0 if bt is None else bt.data_ptr(), int(bool(intercept)), int(mode), _iptr(lv),
+                                                           out.data_ptr()))
+    return out.cpu().numpy()
+
+
 class SparseX:
     """A scipy.sparse x resident on a GPU (oemgpu_sparse_x_create): the compressed columns as _csc_arrays leaves them, their chunk
     pointers and the compressed-row copy, uploaded and built once.  cv_oem(family="binomial") on a sparse x makes one and runs its full

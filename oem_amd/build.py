@@ -14,7 +14,7 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 OUT = HERE / "liboemgpu.so"
-SOURCES = ["api.hip", "paths.hip", "hoststream.hip", "gram.hip", "gram_sb.hip", "gram_wd.hip", "gram_rm.hip", "path_small.hip", "path_coop.hip", "path_symcoop.hip", "path_wcoop.hip", "path_wres.hip", "path_large.hip", "xval.hip", "xval_sparse.hip", "sparse.hip", "sparse_build.hip", "sparse_wide.hip", "wide.hip", "weighted.hip", "logistic.hip", "logistic_rm.hip", "logistic_sparse.hip", "logistic_cv.hip", "logistic_auc.hip", "predict.hip", "multi.hip"]
+SOURCES = ["api.hip", "paths.hip", "hoststream.hip", "gram.hip", "gram_sb.hip", "gram_wd.hip", "gram_rm.hip", "path_small.hip", "path_coop.hip", "path_symcoop.hip", "path_wcoop.hip", "path_wres.hip", "path_large.hip", "xval.hip", "xval_sparse.hip", "sparse.hip", "sparse_build.hip", "sparse_wide.hip", "wide.hip", "weighted.hip", "logistic.hip", "logistic_rm.hip", "logistic_sparse.hip", "logistic_cv.hip", "logistic_auc.hip", "predict.hip", "multi.hip", "logistic_multi.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 
 

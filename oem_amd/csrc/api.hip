@@ -1353,17 +1353,6 @@ static int multi_layout(const char *who, int num_cu, bool colmajor, int64_t n, i
     return 0;
 }
 
-static int multi_y_check(const char *who, int64_t n, int64_t rs, int64_t cs, int32_t m)
-{
-    if (m < 1) { set_error("%s: m < 1 (at least one response)", who); return OEMGPU_ERR_ARG; }
-    if (!((cs == 1 && rs >= m) || (rs == 1 && cs >= n))) {
-        set_error("%s: y strides (%lld, %lld) are neither a row-major n x m matrix (y_cs == 1, y_rs >= m) nor a column-major one (y_rs == 1, y_cs >= n)",
-                  who, (long long)rs, (long long)cs);
-        return OEMGPU_ERR_ARG;
-    }
-    return 0;
-}
-
 // the one moment pass about 0 (response 0 riding as y) into `base`, the X'Y pass into `part`
 static int multi_passes(oemgpu_ctx *c, const MultiLay &L, const DenseSrc &X, const MultiY &Y)
 {

@@ -30,10 +30,15 @@
 // leave_out is the fit on the rows with foldid != leave_out of the same resident X -- the MASKED row pass leaves those rows out (their Z
 // rows are zeros), logit_fold_scan_kernel counts the kept rows (n_eff, which stands where n enters the arithmetic) and maps the W floor's
 // IRLS index to the i-th kept row.
+// Many responses on one x (oemgpu_fit_logistic_dense_multi_dev / _rm_dev): logistic_irls_multi below runs the same
+// algorithm for the m columns of Y in lock-step -- XX, d and A once per call (at beta = 0 they hold no y), the row pass of a step for
+// all live responses from logistic_multi.hip, and this file's small kernels with a workgroup (or grid row) per response:
+// logit_inner_multi_kernel is logit_inner_kernel's body (logit_inner_solve) per response.
 // The host driver (logistic_irls) is shared with the sparse fit (logistic_sparse.hip): the passes over the data reach it as the stages of
 // a LogitData (logistic.hpp); DenseLogitData below is this file's, over a column-major x or (the readers of logistic_rm.hip) a row-major x of
 // float64 / float32 elements read where it lies (oemgpu_fit_logistic_dense_rm_dev, ..._fold_rm_dev; kernels: logistic_rm.hip).
 #include "logistic.hpp"
+#include "logistic_multi.hpp"
 #include "penalty_ops.hpp"
 
 #include <chrono>
@@ -322,9 +327,10 @@ __device__ void logit_threshold(const LogitPen &P, double *u, double *beta, int 
 }
 
 // one workgroup, q <= LOGIT_WG_MAX: u = A beta_prev + XY, next_beta, stopRule -- until the rule or maxit; st[ST_ITERS] += iterations
+// (the body of logit_inner_kernel and, with one workgroup per response, of logit_inner_multi_kernel; iters: the word it adds its count to)
 template <bool A_LDS>
-__global__ __launch_bounds__(1024) void logit_inner_kernel(const double *__restrict__ A, const double *__restrict__ xy, double *__restrict__ beta,
-                                                           int q, LogitPen P, int maxit, double tol, double *__restrict__ st)
+__device__ __forceinline__ void logit_inner_solve(const double *__restrict__ A, const double *__restrict__ xy, double *__restrict__ beta, int q,
+                                                  const LogitPen &P, int maxit, double tol, double *__restrict__ iters)
 {
     extern __shared__ double sh[];
     double *bp = sh, *u = sh + q, *bn = sh + 2 * q, *gf = sh + 3 * q, *As = sh + 3 * q + (P.ngroups > 0 ? P.ngroups : 1);
@@ -350,7 +356,89 @@ __global__ __launch_bounds__(1024) void logit_inner_kernel(const double *__restr
     }
     __syncthreads();
     if (i < q) beta[i] = bp[i];
-    if (i == 0) st[ST_ITERS] += (double)it;
+    if (i == 0) *iters += (double)it;
+}
+
+template <bool A_LDS>
+__global__ __launch_bounds__(1024) void logit_inner_kernel(const double *__restrict__ A, const double *__restrict__ xy, double *__restrict__ beta,
+                                                           int q, LogitPen P, int maxit, double tol, double *__restrict__ st)
+{
+    logit_inner_solve<A_LDS>(A, xy, beta, q, P, maxit, tol, st + ST_ITERS);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- many responses
+// logistic_irls_multi's small kernels: workgroup (or grid row) r is response r of the lock-step chunk -- its q entries of beta, xy,
+// beta_irls, its p + 2 of g, its PenK (its own lambda), its live word.  A frozen response (live[r] == 0) is skipped by every one.
+template <bool A_LDS>
+__global__ __launch_bounds__(1024) void logit_inner_multi_kernel(const double *__restrict__ A, const double *__restrict__ xy, double *__restrict__ beta,
+                                                                 int q, LogitPen P, const PenK *__restrict__ pk, int maxit, double tol,
+                                                                 const int *__restrict__ live, double *__restrict__ iters)
+{
+    const int r = blockIdx.x;
+    if (!live[r]) return;
+    P.k = pk[r];
+    logit_inner_solve<A_LDS>(A, xy + (size_t)r * q, beta + (size_t)r * q, q, P, maxit, tol, iters + r);
+}
+
+// logit_xy_kernel for response blockIdx.y
+__global__ __launch_bounds__(256) void logit_xy_multi_kernel(const double *__restrict__ xx, const double *__restrict__ beta, const double *__restrict__ g,
+                                                             const double *__restrict__ s, int p, int intercept, double n, int init,
+                                                             const int *__restrict__ live, double *__restrict__ xy)
+{
+    const int q = p + (intercept ? 1 : 0), r = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= q || !live[r]) return;
+    beta += (size_t)r * q; g += (size_t)r * (p + 2); xy += (size_t)r * q;
+    const bool icpt = intercept && i == 0;
+    const int j = i - (intercept ? 1 : 0);
+    if (init) { xy[i] = icpt ? g[0] / n : (g[1 + j] * s[j]) / n; return; }
+    const double gr = icpt ? g[0] / n : (g[1 + j] / n) * s[j];
+    double a = 0.0;
+    for (int k = 0; k < q; ++k) a = fma(xx[(size_t)k * q + i], beta[k], a);
+    xy[i] = a + gr;
+}
+
+// the step's start for the live responses: beta_irls <- beta, and Bt = beta o s with the intercept's entry as it is (the row pass reads it)
+__global__ __launch_bounds__(256) void logit_step_multi_kernel(const double *__restrict__ beta, const double *__restrict__ s, int q, int intercept,
+                                                               const int *__restrict__ live, double *__restrict__ birls, double *__restrict__ bt)
+{
+    const int r = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= q || !live[r]) return;
+    const size_t e = (size_t)r * q + i;
+    const double b = beta[e];
+    birls[e] = b;
+    bt[e] = (intercept && i == 0) ? b : b * s[i - (intercept ? 1 : 0)];
+}
+
+// IRLS stop of response blockIdx.x: stopw[r] = stopRule(beta, beta_irls, irls_tol); a response that stops is frozen here (live[r] = 0)
+__global__ __launch_bounds__(1024) void logit_irls_stop_multi_kernel(const double *__restrict__ b, const double *__restrict__ bi, int q, double tol,
+                                                                     int *__restrict__ live, int *__restrict__ stopw)
+{
+    const int r = blockIdx.x;
+    if (!live[r]) return;                                                     // (uniform: the word is written behind the barrier below)
+    b += (size_t)r * q; bi += (size_t)r * q;
+    int v = 0;
+    for (int i = threadIdx.x; i < q; i += 1024) v |= stop_violated(b[i], bi[i], tol);
+    const int viol = __syncthreads_or(v);
+    if (threadIdx.x == 0) { stopw[r] = viol ? 0 : 1; if (!viol) live[r] = 0; }
+}
+
+// logit_back_kernel for response blockIdx.y into its slot of bout; lossw[r] = the loss of its last own row pass
+__global__ __launch_bounds__(256) void logit_back_multi_kernel(const double *__restrict__ beta, const double *__restrict__ s, const double *__restrict__ g,
+                                                               int p, int intercept, size_t stride, double *__restrict__ out, double *__restrict__ lossw)
+{
+    const int r = blockIdx.y, q = p + (intercept ? 1 : 0);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i > p) return;
+    beta += (size_t)r * q; out += (size_t)r * stride;
+    if (i == 0) { out[0] = intercept ? beta[0] : 0.0; lossw[r] = g[(size_t)r * (p + 2) + p + 1]; return; }
+    out[i] = beta[(intercept ? 1 : 0) + i - 1] * s[i - 1];
+}
+
+__global__ void logit_fill_int_kernel(int *a, int n, int v)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) a[i] = v;
 }
 
 // launch form, after launch_gemv(A, beta_prev) -> u: u += XY, next_beta, stopRule; beta_prev <- beta; stop word set on convergence.
@@ -552,6 +640,92 @@ int logistic_check(int64_t n, int32_t p, int32_t intercept, int32_t hessian_full
 
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+// ---- what logistic_irls and logistic_irls_multi share on the host
+// penalty factors (0 for the intercept), groups ordered, group weights (default sqrt(size), 0 for group 0)
+struct LogitTables {
+    std::vector<double> pf, gw;
+    std::vector<int> perm, gstart, gof, gzero;
+    int ng = 0, nperm = 0;
+    int build(const oemgpu_opts *o, int p, int intercept)
+    {
+        const int o1 = intercept ? 1 : 0, q = p + o1;
+        pf.assign(q, 0.0);
+        for (int j = 0; j < p; ++j) pf[o1 + j] = o->penalty_factor[j];
+        if (intercept) pf[0] = 0.0;
+        bool any_grp = false;
+        for (int k = 0; k < o->npen; ++k) any_grp |= pen_is_grp(o->penalty[k]);
+        ng = any_grp ? o->ngroups : 0;
+        perm.clear(); gstart.assign(ng + 1, 0); gof.assign(q, -1); gzero.assign(ng > 0 ? ng : 1, 0);
+        gw.assign(ng > 0 ? ng : 1, 0.0);
+        if (any_grp) {
+            for (int g = 0; g < ng; ++g) {                       // get_group_indexes (h :397-439)
+                gstart[g] = (int)perm.size();
+                for (int v = 0; v < q; ++v)
+                    if (o->groups[v] == o->unique_groups[g]) { perm.push_back(v); if (gof[v] < 0) gof[v] = g; }
+                gstart[g + 1] = (int)perm.size();
+                gzero[g] = o->unique_groups[g] == 0;
+                gw[g] = o->n_group_weights > 0 ? o->group_weights[g] : (gzero[g] ? 0.0 : std::sqrt((double)(gstart[g + 1] - gstart[g])));
+            }
+        }
+        nperm = (int)perm.size();
+        if (nperm > q) { set_error("fit_logistic_dense: unique_groups has repeated ids"); return OEMGPU_ERR_ARG; }
+        return 0;
+    }
+};
+
+// cpp :164-171: exp(linspace(log lmax, log lmin))
+static void logit_lambda_base(const oemgpu_opts *o, double lmax, int nl, double *base)
+{
+    const double lmin = o->lambda_min_ratio * lmax, a = std::log(lmax), b = std::log(lmin);
+    for (int i = 0; i < nl; ++i) base[i] = std::exp(nl > 1 ? (i == nl - 1 ? b : a + (b - a) / (double)(nl - 1) * (double)i) : a);
+}
+
+// the lambda row of penalty k (cpp :205-225): the user's, or the base grid with the .net and nonconvex factors
+static void logit_lambda_row(const oemgpu_opts *o, int k, bool provided, const std::vector<double> &base, int nl, double *lam)
+{
+    if (provided) { for (int i = 0; i < nl; ++i) lam[i] = o->lambda_user[(size_t)k * nl + i]; return; }
+    const int pen = o->penalty[k];
+    const bool net = pen_is_net(pen), ncv = pen == OEMGPU_MCP || pen == OEMGPU_SCAD || pen == OEMGPU_MCP_NET || pen == OEMGPU_SCAD_NET ||
+                                            pen == OEMGPU_GRP_MCP || pen == OEMGPU_GRP_SCAD || pen == OEMGPU_GRP_MCP_NET || pen == OEMGPU_GRP_SCAD_NET;
+    for (int i = 0; i < nl; ++i) {
+        lam[i] = base[i];
+        if (net) {
+            lam[i] = base[i] / o->alpha;
+            if (ncv) {
+                const double fact = 3.5 - std::fmin(3.5, o->gamma) * 5.71425 / 8.0;
+                lam[i] = fact * base[i] / std::pow(o->alpha, 0.8);
+            }
+        }
+    }
+}
+
+// next_beta's constants of a penalty at lambda lamv (h :569-672)
+static PenK logit_penk(const oemgpu_opts *o, int pen, double lamv, double d)
+{
+    PenK pk;
+    const double al = o->alpha, ta = o->tau;
+    pk.gamma = o->gamma; pk.L1 = 0.0; pk.L = lamv; pk.D = d; pk.kind = K_SOFT;
+    const double Ln = lamv * al, Dn = d + (1.0 - al) * lamv;
+    switch (pen) {
+    case OEMGPU_LASSO: break;
+    case OEMGPU_OLS: pk.kind = K_OLS; break;
+    case OEMGPU_ELASTIC_NET: pk.L = Ln; pk.D = Dn; break;
+    case OEMGPU_SCAD: pk.kind = K_SCAD; break;
+    case OEMGPU_SCAD_NET: pk.kind = K_SCAD; pk.L = Ln; pk.D = Dn; if (al == 0.0) { pk.L = 0.0; pk.D = d + lamv; } break;
+    case OEMGPU_MCP: pk.kind = K_MCP; break;
+    case OEMGPU_MCP_NET: pk.kind = K_MCP; pk.L = Ln; pk.D = Dn; break;
+    case OEMGPU_GRP_LASSO: pk.kind = K_GRP; break;
+    case OEMGPU_GRP_LASSO_NET: pk.kind = K_GRP; pk.L = Ln; pk.D = Dn; break;
+    case OEMGPU_GRP_MCP: pk.kind = K_GRP_MCP; break;
+    case OEMGPU_GRP_SCAD: pk.kind = K_GRP_SCAD; break;
+    case OEMGPU_GRP_MCP_NET: pk.kind = K_GRP_MCP; pk.L = Ln; pk.D = Dn; break;
+    case OEMGPU_GRP_SCAD_NET: pk.kind = K_GRP_SCAD; pk.L = Ln; pk.D = Dn; break;
+    case OEMGPU_SPARSE_GRP_LASSO: pk.kind = K_SGL; pk.L = (1.0 - ta) * lamv; pk.L1 = ta * lamv; break;
+    default: break;
+    }
+    return pk;
+}
+
 namespace {
 
 // the dense x: one row pass per IRLS step (logit_rows_kernel); with a Hessian due the same pass writes the Z row blocks of the
@@ -679,27 +853,11 @@ int logistic_irls(oemgpu_ctx *c, LogitData &D, int64_t n, int32_t p, int32_t int
     const int nl = (o->lambda_user && o->nlambda_user > 0) ? o->nlambda_user : o->nlambda;
     const bool provided = o->lambda_user && o->nlambda_user > 0;
     const bool inner_wg = q <= LOGIT_WG_MAX;
-    // ---- host-side tables: penalty factors (0 for the intercept), groups ordered, group weights (default sqrt(size), 0 for group 0)
-    std::vector<double> pf(q);
-    for (int j = 0; j < p; ++j) pf[o1 + j] = o->penalty_factor[j];
-    if (intercept) pf[0] = 0.0;
-    bool any_grp = false;
-    for (int k = 0; k < o->npen; ++k) any_grp |= pen_is_grp(o->penalty[k]);
-    const int ng = any_grp ? o->ngroups : 0;
-    std::vector<int> perm, gstart(ng + 1, 0), gof(q, -1), gzero(ng > 0 ? ng : 1, 0);
-    std::vector<double> gw(ng > 0 ? ng : 1, 0.0);
-    if (any_grp) {
-        for (int g = 0; g < ng; ++g) {                       // get_group_indexes (h :397-439)
-            gstart[g] = (int)perm.size();
-            for (int v = 0; v < q; ++v)
-                if (o->groups[v] == o->unique_groups[g]) { perm.push_back(v); if (gof[v] < 0) gof[v] = g; }
-            gstart[g + 1] = (int)perm.size();
-            gzero[g] = o->unique_groups[g] == 0;
-            gw[g] = o->n_group_weights > 0 ? o->group_weights[g] : (gzero[g] ? 0.0 : std::sqrt((double)(gstart[g + 1] - gstart[g])));
-        }
-    }
-    const int nperm = (int)perm.size();
-    if (nperm > q) { set_error("fit_logistic_dense: unique_groups has repeated ids"); return OEMGPU_ERR_ARG; }
+    LogitTables T;
+    if (int trc = T.build(o, p, intercept)) return trc;
+    const std::vector<double> &pf = T.pf, &gw = T.gw;
+    const std::vector<int> &perm = T.perm, &gstart = T.gstart, &gof = T.gof, &gzero = T.gzero;
+    const int ng = T.ng, nperm = T.nperm;
     // ---- workspace (c->aux; oemgpu_eig_max_dev takes c->ws from its start): the driver's pieces, then the data stages'
     Bump B;
     const size_t a_s = B.take(8 * (size_t)p), a_b = B.take(8 * (size_t)q), a_bi = B.take(8 * (size_t)q),
@@ -742,10 +900,7 @@ int logistic_irls(oemgpu_ctx *c, LogitData &D, int64_t n, int32_t p, int32_t int
     double lmax = 0.0;
     for (int j = o1; j < q; ++j) lmax = std::fmax(lmax, std::fabs(hxy[j]));       // h :795-805
     std::vector<double> base(nl);
-    if (!provided) {                                                              // cpp :164-171: exp(linspace(log lmax, log lmin))
-        const double lmin = o->lambda_min_ratio * lmax, a = std::log(lmax), b = std::log(lmin);
-        for (int i = 0; i < nl; ++i) base[i] = std::exp(nl > 1 ? (i == nl - 1 ? b : a + (b - a) / (double)(nl - 1) * (double)i) : a);
-    }
+    if (!provided) logit_lambda_base(o, lmax, nl, base.data());
     LogitPen LP;
     LP.pf = (const double *)(W + a_pf); LP.gw = (const double *)(W + a_gw); LP.perm = (const int *)(W + a_perm);
     LP.gstart = (const int *)(W + a_gs); LP.gof = (const int *)(W + a_gof); LP.gzero = (const int *)(W + a_gz); LP.ngroups = ng;
@@ -773,21 +928,7 @@ int logistic_irls(oemgpu_ctx *c, LogitData &D, int64_t n, int32_t p, int32_t int
         const bool is_ols = pen == OEMGPU_OLS;
         const int nlk = is_ols ? 1 : nl;
         // the lambda row of this penalty (cpp :205-225)
-        if (provided) for (int i = 0; i < nl; ++i) lam[i] = o->lambda_user[(size_t)k * nl + i];
-        else {
-            const bool net = pen_is_net(pen), ncv = pen == OEMGPU_MCP || pen == OEMGPU_SCAD || pen == OEMGPU_MCP_NET || pen == OEMGPU_SCAD_NET ||
-                                                    pen == OEMGPU_GRP_MCP || pen == OEMGPU_GRP_SCAD || pen == OEMGPU_GRP_MCP_NET || pen == OEMGPU_GRP_SCAD_NET;
-            for (int i = 0; i < nl; ++i) {
-                lam[i] = base[i];
-                if (net) {
-                    lam[i] = base[i] / o->alpha;
-                    if (ncv) {
-                        const double fact = 3.5 - std::fmin(3.5, o->gamma) * 5.71425 / 8.0;
-                        lam[i] = fact * base[i] / std::pow(o->alpha, 0.8);
-                    }
-                }
-            }
-        }
+        logit_lambda_row(o, k, provided, base, nl, lam.data());
         for (int i = 0; i < nl; ++i) lambda_out[(size_t)k * nl + i] = lam[i];
         OEM_HIP(hipMemsetAsync(beta, 0, 8 * (size_t)q, s));                        // init(): cold start (h :813)
         for (int li = 0; li < nlk && !rc && !interrupted; ++li) {
@@ -820,30 +961,7 @@ int logistic_irls(oemgpu_ctx *c, LogitData &D, int64_t n, int32_t p, int32_t int
                     OEM_HIP(hipGetLastError());
                 }
                 // the OEM loop at this lambda (h :1010-1022)
-                PenK pk;
-                {
-                    const double lamv = lam[li], al = o->alpha, ta = o->tau;
-                    pk.gamma = o->gamma; pk.L1 = 0.0; pk.L = lamv; pk.D = d; pk.kind = K_SOFT;
-                    const double Ln = lamv * al, Dn = d + (1.0 - al) * lamv;
-                    switch (pen) {
-                    case OEMGPU_LASSO: break;
-                    case OEMGPU_OLS: pk.kind = K_OLS; break;
-                    case OEMGPU_ELASTIC_NET: pk.L = Ln; pk.D = Dn; break;
-                    case OEMGPU_SCAD: pk.kind = K_SCAD; break;
-                    case OEMGPU_SCAD_NET: pk.kind = K_SCAD; pk.L = Ln; pk.D = Dn; if (al == 0.0) { pk.L = 0.0; pk.D = d + lamv; } break;
-                    case OEMGPU_MCP: pk.kind = K_MCP; break;
-                    case OEMGPU_MCP_NET: pk.kind = K_MCP; pk.L = Ln; pk.D = Dn; break;
-                    case OEMGPU_GRP_LASSO: pk.kind = K_GRP; break;
-                    case OEMGPU_GRP_LASSO_NET: pk.kind = K_GRP; pk.L = Ln; pk.D = Dn; break;
-                    case OEMGPU_GRP_MCP: pk.kind = K_GRP_MCP; break;
-                    case OEMGPU_GRP_SCAD: pk.kind = K_GRP_SCAD; break;
-                    case OEMGPU_GRP_MCP_NET: pk.kind = K_GRP_MCP; pk.L = Ln; pk.D = Dn; break;
-                    case OEMGPU_GRP_SCAD_NET: pk.kind = K_GRP_SCAD; pk.L = Ln; pk.D = Dn; break;
-                    case OEMGPU_SPARSE_GRP_LASSO: pk.kind = K_SGL; pk.L = (1.0 - ta) * lamv; pk.L1 = ta * lamv; break;
-                    default: break;
-                    }
-                }
-                LP.k = pk;
+                LP.k = logit_penk(o, pen, lam[li], d);
                 rc = stage(&g_logit_stats.ms_inner, [&]() -> int {
                     if (inner_wg) {
                         const bool alds = q <= LOGIT_A_LDS_Q;
@@ -963,6 +1081,305 @@ static int logistic_fit_checked(const char *who, bool fold, oemgpu_ctx *c, const
                             lambda_out, niter, loss, d);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- many responses on one x
+struct LogitMultiStats {
+    double steps = 0, row_passes = 0, blocks_skipped = 0, inner_iters = 0, grams = 0, lanczos = 0, ms_rows = 0, ms_gram = 0, ms_inner = 0, wall_ms = 0;
+};
+static thread_local LogitMultiStats g_lm_stats;
+
+// response blocks of a row pass whose responses are all frozen (the kernel returns before it reads x)
+static int lm_blocks_skipped(const LogitMultiPlan &pl, const std::vector<int> &live)
+{
+    int k = 0;
+    for (int b = 0; b < pl.npass; ++b) {
+        bool any = false;
+        for (int r = b * pl.mb; r < pl.mc && r < (b + 1) * pl.mb; ++r) any |= live[(size_t)r] != 0;
+        k += any ? 0 : 1;
+    }
+    return k;
+}
+
+// logistic_irls (hessian.type "upper.bound") for the m columns of Y in lock-step.  With the upper bound the Hessian is
+// built at beta = 0, where every W is 0.25 and the floor cannot bite: XX, d and A do not depend on y, and the reference's rebuild at the
+// start of every penalty returns the same matrix.  So: s, XX (DenseLogitData's own Hessian pass with response 0 riding as y), ONE
+// Lanczos and A once per call; then, per chunk of at most LMULTI_MCH responses, the X'Y pass and every response's own lambda grid, and
+// per penalty and lambda the IRLS steps of all its live responses from one row pass (logistic_multi.hip), one inner launch (a
+// workgroup per response), one stop launch and ONE host read of the stop words.  A response that meets the IRLS stop is frozen for
+// the rest of the lambda: no kernel writes its beta, xy, g or Bt again, and its niter is that step's.  The skipped row pass at
+// (i = 0, li > 0) holds for all at once: every response solves at the new lambda on the xy of its last own pass.
+static int logistic_irls_multi(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const MultiY &Y, int32_t m, int32_t standardize, int32_t intercept,
+                               int32_t irls_maxit, double irls_tol, const oemgpu_opts *o, double *beta_out, double *lambda_out, int32_t *niter,
+                               double *loss_out, double *d_out)
+{
+    const double t_start = now_ms();
+    g_lm_stats = LogitMultiStats();
+    const int q = p + (intercept ? 1 : 0), o1 = intercept ? 1 : 0;
+    const bool provided = o->lambda_user && o->nlambda_user > 0;
+    const int nl = provided ? o->nlambda_user : o->nlambda, npen = o->npen;
+    LogitTables T;
+    if (int trc = T.build(o, p, intercept)) return trc;
+    const int ng = T.ng, ng1 = ng > 0 ? ng : 1;
+    const int mch = m < LMULTI_MCH ? m : LMULTI_MCH;
+    const LogitMultiPlan PW = logit_multi_plan(n, p, mch, c->num_cu);          // (the widest chunk: its panels bound every chunk's)
+    DenseLogitData D(c, X, n, p, nullptr, standardize, intercept, 0);
+    // ---- workspace (c->aux): what the call shares, one chunk's state, the Hessian pass's stages
+    Bump B;
+    const size_t a_s = B.take(8 * (size_t)p), a_xx = B.take(8 * (size_t)q * q), a_a = B.take(8 * (size_t)q * q), a_z = B.take(8 * (size_t)q),
+                 a_g0 = B.take(8 * (size_t)(p + 2)), a_col = Y.rs != 1 ? B.take(8 * (size_t)n) : 0;
+    const size_t a_b = B.take(8 * (size_t)mch * q), a_bi = B.take(8 * (size_t)mch * q), a_xy = B.take(8 * (size_t)mch * q),
+                 a_bt = B.take(8 * (size_t)mch * q), a_g = B.take(8 * (size_t)mch * (p + 2)), a_live = B.take(4 * (size_t)mch),
+                 a_stop = B.take(4 * (size_t)mch), a_it = B.take(8 * (size_t)mch), a_loss = B.take(8 * (size_t)mch),
+                 a_pk = B.take(sizeof(PenK) * (size_t)nl * mch), a_part = B.take(8 * PW.part_doubles), a_out = B.take(8 * (size_t)mch * nl * (p + 1));
+    const size_t a_pf = B.take(8 * (size_t)q), a_gw = B.take(8 * (size_t)ng1), a_perm = B.take(4 * (size_t)(q + 1)), a_gs = B.take(4 * (size_t)(ng + 1)),
+                 a_gof = B.take(4 * (size_t)q), a_gz = B.take(4 * (size_t)ng1);
+    const size_t a_data = B.take(D.ws_bytes());
+    ctx_void_cv(c);
+    if (ctx_grow(c, &c->aux, &c->aux_bytes, B.off)) return OEMGPU_ERR_HIP;
+    char *W = c->aux;
+    double *sc = (double *)(W + a_s), *xx = (double *)(W + a_xx), *A = (double *)(W + a_a), *zero = (double *)(W + a_z), *g0 = (double *)(W + a_g0),
+           *beta = (double *)(W + a_b), *birls = (double *)(W + a_bi), *xy = (double *)(W + a_xy), *bt = (double *)(W + a_bt), *g = (double *)(W + a_g),
+           *iters = (double *)(W + a_it), *lossw = (double *)(W + a_loss), *part = (double *)(W + a_part), *bout = (double *)(W + a_out);
+    int *live = (int *)(W + a_live), *stopw = (int *)(W + a_stop);
+    PenK *pkd = (PenK *)(W + a_pk);
+    hipStream_t s = c->stream;
+    OEM_HIP(hipMemcpyAsync(W + a_pf, T.pf.data(), 8 * (size_t)q, hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemcpyAsync(W + a_gw, T.gw.data(), 8 * T.gw.size(), hipMemcpyHostToDevice, s));
+    if (T.nperm) OEM_HIP(hipMemcpyAsync(W + a_perm, T.perm.data(), 4 * (size_t)T.nperm, hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemcpyAsync(W + a_gs, T.gstart.data(), 4 * T.gstart.size(), hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemcpyAsync(W + a_gof, T.gof.data(), 4 * (size_t)q, hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemcpyAsync(W + a_gz, T.gzero.data(), 4 * T.gzero.size(), hipMemcpyHostToDevice, s));
+    OEM_HIP(hipStreamSynchronize(s));                                           // (the tables are the host's again)
+    LogitPen LP;
+    LP.pf = (const double *)(W + a_pf); LP.gw = (const double *)(W + a_gw); LP.perm = (const int *)(W + a_perm);
+    LP.gstart = (const int *)(W + a_gs); LP.gof = (const int *)(W + a_gof); LP.gzero = (const int *)(W + a_gz); LP.ngroups = ng;
+    LP.k = PenK{K_SOFT, 0.0, 1.0, 0.0, 0.0};
+    hipEvent_t ev[2];
+    const bool timing = c->timing;
+    if (timing) { OEM_HIP(hipEventCreate(&ev[0])); OEM_HIP(hipEventCreate(&ev[1])); }
+    auto stage = [&](double *acc, auto &&fn) -> int {
+        if (timing) (void)hipEventRecord(ev[0], s);
+        int r = fn();
+        if (r) return r;
+        if (timing) {
+            (void)hipEventRecord(ev[1], s);
+            if (hipEventSynchronize(ev[1]) != hipSuccess) { set_error("hipEventSynchronize failed"); return OEMGPU_ERR_HIP; }
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+            *acc += ms;
+        }
+        return 0;
+    };
+    auto finish = [&](int r) -> int {
+        if (timing) { (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]); }
+        if (r) (void)hipStreamSynchronize(s);
+        return r;
+    };
+    // ---- once per call: s, XX at beta = 0, d = 1.0005 lambda_max (h :514), A = dI - XX
+    int rc = 0;
+    D.y = Y.y;
+    if (Y.rs != 1) {
+        double *col = (double *)(W + a_col);
+        if ((rc = launch_multi_column(s, Y, n, 0, col))) return finish(rc);
+        D.y = col;
+    }
+    rc = D.bind(W + a_data);
+    if (!rc) rc = D.scale(sc);
+    if (rc) return finish(rc);
+    OEM_HIP(hipMemsetAsync(zero, 0, 8 * (size_t)q, s));
+    double d = 0.0;
+    rc = stage(&g_lm_stats.ms_gram, [&]() -> int {
+        int r = D.hessian(zero, sc, 0, g0, xx);
+        if (r) return r;
+        double lm = 0.0;
+        r = oemgpu_eig_max_dev(c, xx, q, &lm);                                  // (synchronises)
+        if (r) return r;
+        d = lm * 1.0005;
+        hipLaunchKernelGGL(logit_a_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, xx, q, d, A);
+        OEM_HIP(hipGetLastError());
+        return 0;
+    });
+    if (rc) return finish(rc);
+    g_lm_stats.grams = 1; g_lm_stats.lanczos = 1;
+    const bool alds = q <= LOGIT_A_LDS_Q;
+    const size_t lds_inner = 8 * (size_t)(3 * q + ng1 + (alds ? q * q : 0));
+    if (lds_limit_once(alds ? reinterpret_cast<const void *>(&logit_inner_multi_kernel<true>) : reinterpret_cast<const void *>(&logit_inner_multi_kernel<false>),
+                       lds_inner))
+        return finish(OEMGPU_ERR_HIP);
+    std::vector<double> hxy((size_t)mch * q), lam((size_t)mch * nl), hloss((size_t)mch), hit((size_t)mch);
+    std::vector<std::vector<double>> baser((size_t)mch, std::vector<double>((size_t)nl));
+    std::vector<PenK> pkh((size_t)nl * mch);
+    std::vector<int> hlive((size_t)mch), hstop((size_t)mch), nit((size_t)mch);
+    const size_t nk = (size_t)npen * nl, blen = nk * (size_t)(p + 1);
+    bool interrupted = false;
+    for (int r0 = 0; r0 < m && !interrupted; r0 += mch) {
+        const int mc = m - r0 < mch ? m - r0 : mch;
+        const LogitMultiPlan pl = logit_multi_plan(n, p, mc, c->num_cu);
+        const MultiY Yc{Y.y + (int64_t)r0 * Y.cs, Y.rs, Y.cs};
+        const dim3 gq((unsigned)((q + 255) / 256), (unsigned)mc);
+        auto set_live = [&]() -> int {
+            hipLaunchKernelGGL(logit_fill_int_kernel, dim3((mc + 255) / 256), dim3(256), 0, s, live, mc, 1);
+            OEM_HIP(hipGetLastError());
+            std::fill(hlive.begin(), hlive.begin() + mc, 1);
+            return 0;
+        };
+        // ---- init_oem per response: XY = s o X'Y / n, lambda_0 = max |XY| over the non-intercept slots (h :762-805)
+        if ((rc = set_live())) return finish(rc);
+        OEM_HIP(hipMemsetAsync(iters, 0, 8 * (size_t)mc, s));
+        rc = stage(&g_lm_stats.ms_rows, [&]() -> int {
+            int r = launch_logit_multi_rows(s, pl, X, Yc, nullptr, intercept, 0, live, part);
+            if (!r) r = launch_logit_multi_reduce(s, pl, part, live, g);
+            return r;
+        });
+        if (rc) return finish(rc);
+        hipLaunchKernelGGL(logit_xy_multi_kernel, gq, dim3(256), 0, s, xx, beta, g, sc, p, intercept, (double)n, 1, live, xy);
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipMemcpyAsync(hxy.data(), xy, 8 * (size_t)mc * q, hipMemcpyDeviceToHost, s));
+        OEM_HIP(hipStreamSynchronize(s));
+        for (int r = 0; r < mc; ++r) {
+            double lmax = 0.0;
+            for (int j = o1; j < q; ++j) lmax = std::fmax(lmax, std::fabs(hxy[(size_t)r * q + j]));
+            if (!provided) logit_lambda_base(o, lmax, nl, baser[(size_t)r].data());
+        }
+        for (int k = 0; k < npen && !interrupted; ++k) {
+            const int pen = o->penalty[k];
+            const int nlk = pen == OEMGPU_OLS ? 1 : nl;
+            for (int r = 0; r < mc; ++r) {
+                double *lr = lam.data() + (size_t)r * nl;
+                logit_lambda_row(o, k, provided, baser[(size_t)r], nl, lr);
+                for (int i = 0; i < nl; ++i) {
+                    lambda_out[((size_t)(r0 + r) * npen + k) * nl + i] = lr[i];
+                    pkh[(size_t)i * mc + r] = logit_penk(o, pen, lr[i], d);
+                }
+            }
+            OEM_HIP(hipMemcpy(pkd, pkh.data(), sizeof(PenK) * (size_t)nl * mc, hipMemcpyHostToDevice));
+            OEM_HIP(hipMemsetAsync(beta, 0, 8 * (size_t)mc * q, s));                 // init(): cold start (h :813)
+            OEM_HIP(hipMemsetAsync(bout, 0, 8 * (size_t)mc * nl * (p + 1), s));
+            for (int li = 0; li < nlk && !interrupted; ++li) {
+                if ((rc = set_live())) return finish(rc);
+                int nlive = mc;
+                for (int i = 0; i < irls_maxit && nlive > 0; ++i) {
+                    if (o->interrupt && o->interrupt(o->interrupt_arg)) { interrupted = true; break; }
+                    hipLaunchKernelGGL(logit_step_multi_kernel, gq, dim3(256), 0, s, beta, sc, q, intercept, live, birls, bt);
+                    OEM_HIP(hipGetLastError());
+                    if (!(i == 0 && li > 0)) {
+                        rc = stage(&g_lm_stats.ms_rows, [&]() -> int {
+                            int r = launch_logit_multi_rows(s, pl, X, Yc, bt, intercept, 1, live, part);
+                            if (!r) r = launch_logit_multi_reduce(s, pl, part, live, g);
+                            return r;
+                        });
+                        if (rc) return finish(rc);
+                        g_lm_stats.row_passes += 1;
+                        g_lm_stats.blocks_skipped += lm_blocks_skipped(pl, hlive);
+                        hipLaunchKernelGGL(logit_xy_multi_kernel, gq, dim3(256), 0, s, xx, beta, g, sc, p, intercept, (double)n, 0, live, xy);
+                        OEM_HIP(hipGetLastError());
+                    }
+                    // the OEM loop at this lambda (h :1010-1022): one workgroup per live response, A shared
+                    rc = stage(&g_lm_stats.ms_inner, [&]() -> int {
+                        const PenK *pk = pkd + (size_t)li * mc;
+                        if (alds) {
+                            hipLaunchKernelGGL(logit_inner_multi_kernel<true>, dim3(mc), dim3(1024), lds_inner, s, A, xy, beta, q, LP, pk, o->maxit, o->tol, live, iters);
+                        } else {
+                            hipLaunchKernelGGL(logit_inner_multi_kernel<false>, dim3(mc), dim3(1024), lds_inner, s, A, xy, beta, q, LP, pk, o->maxit, o->tol, live, iters);
+                        }
+                        OEM_HIP(hipGetLastError());
+                        return 0;
+                    });
+                    if (rc) return finish(rc);
+                    hipLaunchKernelGGL(logit_irls_stop_multi_kernel, dim3(mc), dim3(1024), 0, s, beta, birls, q, irls_tol, live, stopw);
+                    OEM_HIP(hipGetLastError());
+                    OEM_HIP(hipMemcpyAsync(hstop.data(), stopw, 4 * (size_t)mc, hipMemcpyDeviceToHost, s));
+                    OEM_HIP(hipStreamSynchronize(s));                              // the one host sync of a lock-step IRLS step
+                    g_lm_stats.steps += 1;
+                    for (int r = 0; r < mc; ++r)
+                        if (hlive[(size_t)r] && hstop[(size_t)r]) { hlive[(size_t)r] = 0; nit[(size_t)r] = i + 1; --nlive; }
+                }
+                if (interrupted) break;
+                for (int r = 0; r < mc; ++r)
+                    if (hlive[(size_t)r]) nit[(size_t)r] = irls_maxit + 1;             // the cap (h :1035)
+                hipLaunchKernelGGL(logit_back_multi_kernel, dim3((p + 1 + 255) / 256, mc), dim3(256), 0, s, beta, sc, g, p, intercept, (size_t)nl * (p + 1),
+                                   bout + (size_t)li * (p + 1), lossw);
+                OEM_HIP(hipGetLastError());
+                if (o->compute_loss) {                                              // the loss of the LAST prob computed: of its last own row pass
+                    OEM_HIP(hipMemcpyAsync(hloss.data(), lossw, 8 * (size_t)mc, hipMemcpyDeviceToHost, s));
+                    OEM_HIP(hipStreamSynchronize(s));
+                }
+                for (int r = 0; r < mc; ++r) {
+                    const size_t e = ((size_t)(r0 + r) * npen + k) * nl + li;
+                    niter[e] = nit[(size_t)r];
+                    loss_out[e] = o->compute_loss ? hloss[(size_t)r] : 1e99;
+                }
+            }
+            if (interrupted) break;
+            for (int r = 0; r < mc; ++r)
+                for (int li = nlk; li < nl; ++li) { const size_t e = ((size_t)(r0 + r) * npen + k) * nl + li; niter[e] = 0; loss_out[e] = 0.0; }
+            OEM_HIP(hipStreamSynchronize(s));
+            OEM_HIP(hipMemcpy2D(beta_out + blen * r0 + (size_t)k * nl * (p + 1), 8 * blen, bout, 8 * (size_t)nl * (p + 1), 8 * (size_t)nl * (p + 1), mc,
+                                hipMemcpyDeviceToHost));
+        }
+        if (interrupted) break;
+        OEM_HIP(hipMemcpy(hit.data(), iters, 8 * (size_t)mc, hipMemcpyDeviceToHost));
+        for (int r = 0; r < mc; ++r) { g_lm_stats.inner_iters += hit[(size_t)r]; d_out[r0 + r] = d; }
+    }
+    if (interrupted) { (void)finish(1); set_error("interrupted"); return OEMGPU_ERR_INTERRUPTED; }
+    g_lm_stats.wall_ms = now_ms() - t_start;
+    return finish(0);
+}
+
+// the checks of the two many-response entries, before a device is looked for; then the fit
+static int logistic_multi_checked(const char *who, oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const double *y_dev, int64_t rs, int64_t cs,
+                                  int32_t m, int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol,
+                                  const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+{
+    if (!c || !X.x || !y_dev || !o || !beta || !lambda_out || !niter || !loss || !d) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    int rc = multi_y_check(who, n, rs, cs, m);
+    if (!rc) rc = dense_src_check(who, X, n, p);
+    if (!rc) rc = logistic_check(n, p, intercept, hessian_full, irls_maxit, irls_tol, o);
+    if (rc) return rc;
+    if (hessian_full) {
+        set_error("%s: a full Hessian is one per response and step: fit each column with fit_logistic_dense", who);
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    if (p + (intercept ? 1 : 0) > LOGIT_WG_MAX) {
+        set_error("%s: p + intercept > %d is not supported (beyond one workgroup the inner solve is a product of all responses): fit each column with "
+                  "fit_logistic_dense", who, LOGIT_WG_MAX);
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    return logistic_irls_multi(c, X, n, p, MultiY{y_dev, rs, cs}, m, standardize, intercept, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
+}
+
+// one row pass of logistic_multi.hip for the kernel tests: out[r] (p + 2 doubles) for the live responses, chunk of responses after chunk
+static int logistic_multi_rows_selftest(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const MultiY &Y, int32_t m, const double *bt, int32_t intercept,
+                                        int32_t mode, const int32_t *live_host, double *out)
+{
+    g_lm_stats = LogitMultiStats();
+    const int q = p + (intercept ? 1 : 0);
+    const int mch = m < LMULTI_MCH ? m : LMULTI_MCH;
+    const LogitMultiPlan PW = logit_multi_plan(n, p, mch, c->num_cu);
+    Bump B;
+    const size_t a_part = B.take(8 * PW.part_doubles), a_live = B.take(4 * (size_t)m);
+    ctx_void_cv(c);
+    if (ctx_grow(c, &c->aux, &c->aux_bytes, B.off)) return OEMGPU_ERR_HIP;
+    double *part = (double *)(c->aux + a_part);
+    int *live = (int *)(c->aux + a_live);
+    std::vector<int> hl((size_t)m, 1);
+    if (live_host) for (int r = 0; r < m; ++r) hl[(size_t)r] = live_host[r] != 0;
+    OEM_HIP(hipMemcpy(live, hl.data(), 4 * (size_t)m, hipMemcpyHostToDevice));
+    for (int r0 = 0; r0 < m; r0 += mch) {
+        const int mc = m - r0 < mch ? m - r0 : mch;
+        const LogitMultiPlan pl = logit_multi_plan(n, p, mc, c->num_cu);
+        const std::vector<int> lc(hl.begin() + r0, hl.begin() + r0 + mc);
+        int rc = launch_logit_multi_rows(c->stream, pl, X, MultiY{Y.y + (int64_t)r0 * Y.cs, Y.rs, Y.cs}, mode ? bt + (size_t)r0 * q : nullptr, intercept, mode,
+                                         live + r0, part);
+        if (!rc) rc = launch_logit_multi_reduce(c->stream, pl, part, live + r0, out + (size_t)r0 * (p + 2));
+        if (rc) return rc;
+        g_lm_stats.row_passes += 1;
+        g_lm_stats.blocks_skipped += lm_blocks_skipped(pl, lc);
+    }
+    OEM_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 }  // namespace oemgpu
 
 using namespace oemgpu;
@@ -1012,6 +1429,66 @@ int oemgpu_selftest_logistic_rm_plan(int64_t n, int32_t p, int32_t dtype, int32_
     const LogitRmPlan R = logit_rm_plan(p);
     out[0] = R.nband; out[1] = R.bw; out[2] = p - (int64_t)(R.nband - 1) * R.bw; out[3] = (int64_t)R.lds_total;
     out[4] = P.ch; out[5] = P.nchunk; out[6] = P.rbz; out[7] = P.nzblk;
+    return 0;
+}
+
+int oemgpu_fit_logistic_dense_multi_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev, int64_t y_rs,
+                                        int64_t y_cs, int32_t m, int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit,
+                                        double irls_tol, const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+{
+    return logistic_multi_checked("fit_logistic_dense_multi", c, dense_src_cm(x_dev, ld), n, p, y_dev, y_rs, y_cs, m, standardize, intercept, hessian_full,
+                                  irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
+}
+
+int oemgpu_fit_logistic_dense_multi_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                                           int64_t y_rs, int64_t y_cs, int32_t m, int32_t standardize, int32_t intercept, int32_t hessian_full,
+                                           int32_t irls_maxit, double irls_tol, const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter,
+                                           double *loss, double *d)
+{
+    return logistic_multi_checked("fit_logistic_dense_multi_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, y_rs, y_cs, m, standardize, intercept,
+                                  hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
+}
+
+int oemgpu_selftest_logistic_multi_plan(int64_t n, int32_t p, int32_t m, int32_t intercept, int32_t layout, int32_t num_cu, int64_t *out)
+{
+    if (n < 1 || p < 1 || m < 1 || num_cu < 1 || (layout != 0 && layout != 1) || !out) { set_error("selftest_logistic_multi_plan: bad argument"); return OEMGPU_ERR_ARG; }
+    const int q = p + (intercept ? 1 : 0);
+    if (q > LOGIT_WG_MAX) { set_error("selftest_logistic_multi_plan: p + intercept > %d is not supported", LOGIT_WG_MAX); return OEMGPU_ERR_UNSUPPORTED; }
+    const int mch = m < LMULTI_MCH ? m : LMULTI_MCH;
+    const LogitMultiPlan pl = logit_multi_plan(n, p, mch, num_cu);
+    const LogitPlan P = logit_plan(n, p, intercept, num_cu);
+    const size_t shared = 8 * ((size_t)p + 2 * (size_t)q * q + (size_t)q + (size_t)(p + 2)) + (layout == 1 ? 8 * (size_t)256 * p : 0);   // s, XX, A, beta = 0, g; the scale pass's partials
+    const size_t chunk = 8 * ((size_t)mch * q * 4 + (size_t)mch * (p + 2) + 3 * (size_t)mch) + sizeof(PenK) * (size_t)mch;
+    out[0] = pl.rows; out[1] = pl.nchunk; out[2] = pl.mb; out[3] = pl.lt; out[4] = pl.band; out[5] = (int64_t)pl.lds_bytes; out[6] = LMULTI_MCH;
+    out[7] = (m + LMULTI_MCH - 1) / LMULTI_MCH; out[8] = pl.npass; out[9] = pl.tpw;
+    out[10] = (int64_t)(8 * pl.part_doubles); out[11] = (int64_t)shared; out[12] = (int64_t)chunk; out[13] = (int64_t)P.ws_bytes;
+    out[14] = out[10] + out[11] + out[12] + out[13];
+    out[15] = q <= LOGIT_A_LDS_Q;
+    return 0;
+}
+
+int oemgpu_selftest_logistic_multi_rows_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                                            int64_t y_rs, int64_t y_cs, int32_t m, const double *btilde_dev, int32_t intercept, int32_t mode,
+                                            const int32_t *live, double *out_dev)
+{
+    const char *who = "selftest_logistic_multi_rows";
+    if (!c || !x_dev || !y_dev || !out_dev || (mode && !btilde_dev)) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    if (n < 1 || p < 1 || (mode != 0 && mode != 1)) { set_error("%s: bad argument", who); return OEMGPU_ERR_ARG; }
+    const DenseSrc X = dtype < 0 ? dense_src_cm((const double *)x_dev, ld) : dense_src_rm(x_dev, dtype, ld);
+    int rc = multi_y_check(who, n, y_rs, y_cs, m);
+    if (!rc) rc = dense_src_check(who, X, n, p);
+    if (rc) return rc;
+    if (p > LMULTI_P_MAX) { set_error("%s: p > %d is not supported", who, LMULTI_P_MAX); return OEMGPU_ERR_UNSUPPORTED; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    return logistic_multi_rows_selftest(c, X, n, p, MultiY{y_dev, y_rs, y_cs}, m, btilde_dev, intercept, mode, live, out_dev);
+}
+
+int oemgpu_last_logistic_multi_stats(double *out)
+{
+    if (!out) { set_error("last_logistic_multi_stats: NULL"); return OEMGPU_ERR_ARG; }
+    const LogitMultiStats &s = g_lm_stats;
+    out[0] = s.steps; out[1] = s.row_passes; out[2] = s.blocks_skipped; out[3] = s.inner_iters; out[4] = s.grams; out[5] = s.lanczos;
+    out[6] = s.ms_rows; out[7] = s.ms_gram; out[8] = s.ms_inner; out[9] = s.wall_ms;
     return 0;
 }
 

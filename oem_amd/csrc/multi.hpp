@@ -1,6 +1,7 @@
 // multi.hpp -- many responses on one dense x (multi.hip): the plan of the X'Y pass and its launches; the driver is api.hip's fit_dense_multi_src.
 #pragma once
 
+#include "common.hpp"
 #include "dense_src.hpp"
 
 namespace oemgpu {
@@ -14,6 +15,18 @@ struct MultiY {
     const double *y;
     int64_t rs, cs;
 };
+
+// the one rule of Y's strides (the many-response entries refuse anything else before a device is looked for)
+inline int multi_y_check(const char *who, int64_t n, int64_t rs, int64_t cs, int32_t m)
+{
+    if (m < 1) { set_error("%s: m < 1 (at least one response)", who); return OEMGPU_ERR_ARG; }
+    if (!((cs == 1 && rs >= m) || (rs == 1 && cs >= n))) {
+        set_error("%s: y strides (%lld, %lld) are neither a row-major n x m matrix (y_cs == 1, y_rs >= m) nor a column-major one (y_rs == 1, y_cs >= n)",
+                  who, (long long)rs, (long long)cs);
+        return OEMGPU_ERR_ARG;
+    }
+    return 0;
+}
 
 // The X'Y pass as pure host arithmetic (oemgpu_selftest_multi_plan): rows are cut into `nchunk` chunks of `rows` rows (a multiple of
 // 64; the last may be short, none is empty), the responses into `npass` blocks of mb = 16 lt, the columns of [X | 1] into `cgroups`
