@@ -775,6 +775,47 @@ int oemgpu_fit_logistic_dense_multi_rm_dev(oemgpu_ctx *ctx, const void *x_dev, i
                                            int64_t y_rs, int64_t y_cs, int32_t m, int32_t standardize, int32_t intercept, int32_t hessian_full,
                                            int32_t irls_maxit, double irls_tol, const oemgpu_opts *opts, double *beta, double *lambda_out,
                                            int32_t *niter, double *loss, double *d);
+/* The fold fits of a cross-validation over many binomial responses, in the same lock-step.  Instance i < ninst is
+ * response resp[i] of Y fitted on the rows with foldid_dev[row] != leave_out[i] (0: every row) -- what
+ * oemgpu_fit_logistic_dense_fold_dev / _fold_rm_dev return for that column and fold, and oemgpu_fit_logistic_dense_dev / _rm_dev
+ * for leave_out 0.  foldid_dev: n device words in [1, nfolds]; resp, leave_out: host arrays of ninst words, in any order, repeats
+ * allowed.  Per distinct leave_out value (a group) the call builds s, X'WX at beta = 0 on the kept rows, d and A once (one Gram pass
+ * and one Lanczos per group); every instance then rides the shared row pass as one column with its own row mask, has its own lambda
+ * grid from its own masked X'y (a user lambda is shared) and its group's n_eff wherever n enters.  An instance's results do not depend
+ * on the other instances or on the order of the list.  The columns of a row pass share the rows they load: x must be finite on
+ * EVERY row, also on rows that only some instances leave out (the single fold entry never loads a left-out row).
+ * Outputs, instance-major: beta[ninst][npen][nl][p + 1], lambda_out / niter / loss [ninst][npen][nl], d[ninst] (its group's),
+ * nobs[ninst] (the rows of its fit).
+ * Refused before any fit, nothing written: what oemgpu_fit_logistic_dense_multi_dev refuses, with its codes (a full Hessian and
+ * p + intercept > 1024 included); a NULL foldid_dev, resp, leave_out or nobs, nfolds < 3 ("nfolds must be bigger than 3; nfolds=10
+ * recommended"), ninst < 1, a leave_out outside [0, nfolds], a resp outside [0, m) (OEMGPU_ERR_ARG); a fold id outside [1, nfolds]
+ * (OEMGPU_ERR_ARG, found on the device); p + intercept >= the rows outside a fold that an instance leaves out (OEMGPU_ERR_UNSUPPORTED,
+ * naming the fold).  oemgpu_last_logistic_multi_stats: out[4] = out[5] = the number of groups. */
+int oemgpu_fit_logistic_dense_multi_fold_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev, int64_t y_rs,
+                                             int64_t y_cs, int32_t m, const int32_t *foldid_dev, int32_t nfolds, int32_t ninst, const int32_t *resp,
+                                             const int32_t *leave_out, int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit,
+                                             double irls_tol, const oemgpu_opts *opts, double *beta, double *lambda_out, int32_t *niter, double *loss,
+                                             double *d, int64_t *nobs);
+int oemgpu_fit_logistic_dense_multi_fold_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                                                int64_t y_rs, int64_t y_cs, int32_t m, const int32_t *foldid_dev, int32_t nfolds, int32_t ninst,
+                                                const int32_t *resp, const int32_t *leave_out, int32_t standardize, int32_t intercept,
+                                                int32_t hessian_full, int32_t irls_maxit, double irls_tol, const oemgpu_opts *opts, double *beta,
+                                                double *lambda_out, int32_t *niter, double *loss, double *d, int64_t *nobs);
+/* Host-only workspace plan of a fold call with ninst instances in ngroups groups (pure arithmetic).  out[0] rows per chunk of the row
+ * pass, out[1] chunks, out[2] instances of the widest lock-step chunk (at most 64), out[3] lock-step chunks, out[4] ngroups,
+ * out[5 .. 9] bytes: the panels of a row pass; the groups (s, XX, A and the row count of each: 8 ngroups (p + 2 q^2 + 1)); what the
+ * call shares besides; a chunk's state without its per-lambda tables; the Hessian pass's stages; out[10] their sum.  OEMGPU_ERR_ARG
+ * on an argument < 1, a layout other than 0 / 1 or a NULL out; OEMGPU_ERR_UNSUPPORTED for p + intercept > 1024. */
+#define OEMGPU_LMULTI_FOLD_PLAN_LEN 11
+int oemgpu_selftest_logistic_multi_fold_plan(int64_t n, int32_t p, int32_t ninst, int32_t ngroups, int32_t intercept, int32_t layout, int32_t num_cu,
+                                             int64_t *out /* OEMGPU_LMULTI_FOLD_PLAN_LEN */);
+/* Test infrastructure: ONE masked row pass of ncol columns.  Column t is response ycol[t] of Y (t itself when ycol is NULL, and then
+ * ncol == m) on the rows with foldid_dev[row] != leave[t]; leave, ycol, live: host arrays of ncol words; btilde_dev: ncol x (p +
+ * intercept); out_dev: [ncol][p + 2].  The rest as oemgpu_selftest_logistic_multi_rows_dev. */
+int oemgpu_selftest_logistic_multi_rows_fold_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ld, int32_t p,
+                                                 const double *y_dev, int64_t y_rs, int64_t y_cs, int32_t m, const int32_t *foldid_dev, int32_t ncol,
+                                                 const int32_t *leave, const int32_t *ycol, const double *btilde_dev, int32_t intercept, int32_t mode,
+                                                 const int32_t *live, double *out_dev);
 /* Host-only plan of the many-response binomial fit (pure arithmetic, runs without a GPU).  layout: 0 column-major x, 1 row-major.
  * out[0] rows per chunk of the shared row pass (a multiple of 64 that depends on n and num_cu alone), out[1] chunks (chunk c = rows
  * [c out[0], min(n, (c + 1) out[0]))), out[2] responses per block (16 out[3]), out[3] response tiles per block LT, out[4] the column

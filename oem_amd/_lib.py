@@ -144,6 +144,18 @@ _SIGS = {
     "oemgpu_fit_logistic_dense_multi_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
                                                          C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                                          C.POINTER(OemgpuOpts)] + _OUT),
+    # the fold fits of a cross-validation over many binomial responses: instances (response, fold left out) in the same lock-step
+    "oemgpu_fit_logistic_dense_multi_fold_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+                                                           C.c_int32, C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                           C.c_double, C.POINTER(OemgpuOpts)] + _OUT + [C.POINTER(C.c_int64)]),
+    "oemgpu_fit_logistic_dense_multi_fold_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                                              C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, C.c_int32, C.c_int32,
+                                                              C.c_int32, C.c_int32, C.c_double, C.POINTER(OemgpuOpts)] + _OUT + [C.POINTER(C.c_int64)]),
+    "oemgpu_selftest_logistic_multi_fold_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                           C.POINTER(C.c_int64)]),
+    "oemgpu_selftest_logistic_multi_rows_fold_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                                               C.c_int64, C.c_int32, C.c_void_p, C.c_int32, _ip, _ip, C.c_void_p, C.c_int32, C.c_int32, _ip,
+                                                               C.c_void_p]),
     "oemgpu_selftest_logistic_multi_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_selftest_logistic_multi_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
                                                           C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, _ip, C.c_void_p]),

@@ -832,6 +832,16 @@ def oem_fit_logistic_dense_multi(x, Y, penalty=None, weights=(), lambda_=(), nla
     with at most two values; a torch device tensor (float64 with a unit stride in one dimension: read where it lies, checked on the
     device) or a host array (uploaded once).  oem_fit_logistic_dense's keyword arguments and checks; a user lambda is shared by all
     responses.  Returns a list of m OemFitBinomial."""
+    return _logistic_multi_fit("oem_fit_logistic_dense_multi", x, Y, None, penalty, weights, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups,
+                               penalty_factor, group_weights, standardize, intercept, maxit, tol, irls_maxit, irls_tol, compute_loss, hessian_type,
+                               varnames, interrupt)
+
+
+def _logistic_multi_fit(who, x, Y, fold, penalty, weights, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups, penalty_factor, group_weights,
+                        standardize, intercept, maxit, tol, irls_maxit, irls_tol, compute_loss, hessian_type, varnames, interrupt):
+    """oem_fit_logistic_dense_multi (fold None: one fit per column of Y) and oem_fit_logistic_dense_multi_folds (fold = (foldid,
+    instances or None)): the checks, which raise before a device is looked for, then the one call.  Returns the list of fits, one per
+    response or per instance."""
     L.sync_switches()
     penalty = _match_penalty(penalty)
     if hessian_type not in ("upper.bound", "full"):
@@ -840,7 +850,7 @@ def oem_fit_logistic_dense_multi(x, Y, penalty=None, weights=(), lambda_=(), nla
         raise ValueError("Y must be a matrix of n rows and one column per response")
     if len(weights) > 0:                                               # R/oem.R:244
         raise L.OemgpuError(-4, "weights not implemented yet.")
-    host_or_sparse = ("oem_fit_logistic_dense_multi() takes a dense torch tensor on a GPU: a host or sparse x is fitted one response at a "
+    host_or_sparse = (f"{who}() takes a dense torch tensor on a GPU: a host or sparse x is fitted one response at a "
                       "time with oem_fit_logistic_dense / oem_fit_logistic_sparse")
     if isinstance(x, SparseX) or _is_scipy_sparse(x) or _is_torch_sparse(x):
         raise ValueError(host_or_sparse)
@@ -857,10 +867,37 @@ def oem_fit_logistic_dense_multi(x, Y, penalty=None, weights=(), lambda_=(), nla
     if hessian_type == "full":
         raise ValueError("hessian_type='full' builds one Hessian per response and IRLS step: fit each column with oem_fit_logistic_dense")
     if p + int(bool(intercept)) > 1024:
-        raise ValueError("oem_fit_logistic_dense_multi() serves p + intercept <= 1024: fit each column with oem_fit_logistic_dense")
+        raise ValueError(f"{who}() serves p + intercept <= 1024: fit each column with oem_fit_logistic_dense")
     _binary_columns_check(Y)
     if not _is_torch_cuda(x):
         raise ValueError(host_or_sparse)
+    resp = leave = None
+    if fold is not None:
+        foldid, instances = fold
+        if _is_torch_cuda(foldid):
+            import torch
+            if foldid.dtype != torch.int32 or foldid.ndim != 1 or not foldid.is_contiguous():
+                raise ValueError("foldid on a device must be a contiguous int32 vector")
+            fd, nf_len, nfolds = foldid, int(foldid.shape[0]), (int(foldid.max().item()) if foldid.numel() else 0)
+        else:
+            fh = np.ascontiguousarray(np.asarray(foldid).ravel(), dtype=np.int32)
+            fd, nf_len, nfolds = None, len(fh), (int(fh.max()) if len(fh) else 0)
+        if nf_len != n:
+            raise ValueError("x and y lengths do not match")
+        if nfolds < 3:
+            raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
+        if instances is None:
+            instances = [(r, k) for r in range(m) for k in range(nfolds + 1)]
+        instances = [(int(r), int(k)) for r, k in instances]
+        if len(instances) < 1:
+            raise ValueError("instances must name at least one (response, fold) pair")
+        for r, k in instances:
+            if not 0 <= r < m:
+                raise ValueError(f"instance ({r}, {k}): the response must be in [0, {m})")
+            if not 0 <= k <= nfolds:
+                raise ValueError(f"instance ({r}, {k}): the fold left out must be in [0, {nfolds}] (0: the full fit)")
+        resp = np.ascontiguousarray([r for r, _ in instances], dtype=np.int32)
+        leave = np.ascontiguousarray([k for _, k in instances], dtype=np.int32)
     if penalty_factor is None:
         penalty_factor = np.ones(p)
     penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
@@ -878,17 +915,48 @@ def oem_fit_logistic_dense_multi(x, Y, penalty=None, weights=(), lambda_=(), nla
     import torch
     X = _DeviceX(x, _logistic_rowmajor_in_place)                       # row-major float64 / float32: read where it lies
     Yd, rs, cs = _device_responses(Y, x.device)
-    beta = np.zeros((m, a.npen, a.nl, p + 1))
-    lam_out = np.zeros((m, a.npen, a.nl))
-    niter = np.zeros((m, a.npen, a.nl), dtype=np.int32)
-    loss = np.zeros((m, a.npen, a.nl))
-    d = np.zeros(m)
+    nfit = m if fold is None else len(resp)
+    beta = np.zeros((nfit, a.npen, a.nl, p + 1))
+    lam_out = np.zeros((nfit, a.npen, a.nl))
+    niter = np.zeros((nfit, a.npen, a.nl), dtype=np.int32)
+    loss = np.zeros((nfit, a.npen, a.nl))
+    d = np.zeros(nfit)
+    nobs = np.full(nfit, n, dtype=np.int64)
     ctx = context(x.device.index)
-    torch.cuda.current_stream(x.device).synchronize()
-    X.call("fit_logistic_dense_multi", ctx, Yd.data_ptr(), rs, cs, m, int(bool(standardize)), int(bool(intercept)), 0, int(irls_maxit),
-           float(irls_tol), C.byref(a.c), _dptr(beta), _dptr(lam_out), _iptr(niter), _dptr(loss), _dptr(d))
-    return [OemFitBinomial(_decorate(_OneOfMany(beta[r], lam_out[r], niter[r], loss[r], d[r]), penalty, varnames, True, n, p, family="binomial"))
-            for r in range(m)]
+    scal = (int(bool(standardize)), int(bool(intercept)), 0, int(irls_maxit), float(irls_tol), C.byref(a.c))
+    outs = (_dptr(beta), _dptr(lam_out), _iptr(niter), _dptr(loss), _dptr(d))
+    if fold is None:
+        torch.cuda.current_stream(x.device).synchronize()
+        X.call("fit_logistic_dense_multi", ctx, Yd.data_ptr(), rs, cs, m, *scal, *outs)
+    else:
+        if fd is None:
+            fd = torch.as_tensor(fh, device=x.device)
+        torch.cuda.current_stream(x.device).synchronize()
+        X.call("fit_logistic_dense_multi_fold", ctx, Yd.data_ptr(), rs, cs, m, fd.data_ptr(), nfolds, nfit, _iptr(resp), _iptr(leave), *scal, *outs,
+               nobs.ctypes.data_as(C.POINTER(C.c_int64)))
+    return [OemFitBinomial(_decorate(_OneOfMany(beta[r], lam_out[r], niter[r], loss[r], d[r]), penalty, varnames, True, int(nobs[r]), p, family="binomial"))
+            for r in range(nfit)]
+
+
+def oem_fit_logistic_dense_multi_folds(x, Y, foldid, instances=None, penalty=None, weights=(), lambda_=(), nlambda=100, lambda_min_ratio=None, alpha=1.0,
+                                       gamma=3.0, tau=0.5, groups=(), penalty_factor=None, group_weights=None, standardize=True, intercept=True,
+                                       maxit=500, tol=1e-7, irls_maxit=100, irls_tol=1e-3, compute_loss=False, hessian_type="upper.bound",
+                                       varnames=None, interrupt=None):
+    """The full and fold fits of a cross-validation over the m columns of Y, from ONE lock-step call on the resident x
+    (oemgpu_fit_logistic_dense_multi_fold_dev).  Instance (r, k) is response r fitted on the rows with foldid != k,
+    k = 0 the full fit: what oem_fit_logistic_dense(x, Y[:, r]) and its fold form return, with nobs the rows kept.  One Gram pass and
+    one Lanczos per distinct k; every instance rides the shared row pass as a masked column.  foldid: n ids in [1, K], a host array or
+    an int32 device tensor; K is its largest id.  instances: a list of (r, k) pairs -> the list of their fits, in that order; None: all
+    m (K + 1) pairs -> m lists [full, fold 1, ..., fold K].  x, Y and the keyword arguments are oem_fit_logistic_dense_multi's, with its
+    checks and refusals; also refused: K < 3, len(foldid) != n, an r outside [0, m), a k outside [0, K], a fold that keeps no more than
+    p + intercept rows.  x must be finite on every row, also on rows that only some instances leave out."""
+    fits = _logistic_multi_fit("oem_fit_logistic_dense_multi_folds", x, Y, (foldid, instances), penalty, weights, lambda_, nlambda, lambda_min_ratio,
+                               alpha, gamma, tau, groups, penalty_factor, group_weights, standardize, intercept, maxit, tol, irls_maxit, irls_tol,
+                               compute_loss, hessian_type, varnames, interrupt)
+    if instances is not None:
+        return fits
+    per = len(fits) // int(Y.shape[1])
+    return [fits[r * per:(r + 1) * per] for r in range(int(Y.shape[1]))]
 
 
 def logistic_multi_plan(n, p, m, intercept=True, layout=0, num_cu=256):
@@ -935,6 +1003,53 @@ def logistic_multi_rows(x, Y, btilde=None, intercept=True, mode=1, live=None, ou
                                                            0 if bt is None else bt.data_ptr(), int(bool(intercept)), int(mode), _iptr(lv),
                                                            out.data_ptr()))
     return out.cpu().numpy()
+
+
+def logistic_multi_rows_fold(x, Y, foldid, leave, btilde=None, intercept=True, mode=1, live=None, out=None, ycol=None):
+    """Test infrastructure: oemgpu_selftest_logistic_multi_rows_fold_dev, ONE masked row pass -> numpy [ncol, p + 2].  Column t is
+    response ycol[t] of Y (t itself without ycol) on the rows with foldid != leave[t].  foldid: n ids (host array or int32 device
+    tensor); leave, ycol: ncol words; the rest as logistic_multi_rows."""
+    import torch
+    if not _is_torch_cuda(x) or x.ndim != 2:
+        raise ValueError("x must be a 2-D torch tensor on a GPU")
+    n, p = x.shape
+    if x.dtype == torch.float64 and x.stride(0) == 1 and x.stride(1) >= n:
+        code, ld = -1, x.stride(1)
+    else:
+        code, ld = _rowmajor_dtype(x), x.stride(0)
+        if code is None:
+            raise ValueError("x must be column-major float64, or row-major float64 / float32 with unit column stride")
+    Yd, rs, cs = _device_responses(Y, x.device)
+    m = Yd.shape[1]
+    fd = foldid if _is_torch_cuda(foldid) else torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=x.device)
+    if fd.dtype != torch.int32 or fd.shape != (n,) or not fd.is_contiguous():
+        raise ValueError("foldid must be n contiguous int32 ids")
+    lv = np.ascontiguousarray(leave, dtype=np.int32).ravel()
+    ncol = len(lv)
+    yc = None if ycol is None else np.ascontiguousarray(ycol, dtype=np.int32).ravel()
+    if yc is not None and len(yc) != ncol:
+        raise ValueError("ycol and leave must have one entry per column")
+    bt = None if btilde is None else torch.as_tensor(np.ascontiguousarray(btilde, dtype=np.float64), device=x.device)
+    if bt is not None and bt.shape[0] != ncol:
+        raise ValueError("btilde must have one row per column")
+    if out is None:
+        out = torch.full((ncol, p + 2), float("nan"), dtype=torch.float64, device=x.device)
+    lw = None if live is None else np.ascontiguousarray(live, dtype=np.int32)
+    ctx = context(x.device.index)
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_selftest_logistic_multi_rows_fold_dev(ctx, x.data_ptr(), code, n, ld, p, Yd.data_ptr(), rs, cs, m, fd.data_ptr(), ncol,
+                                                                _iptr(lv), _iptr(yc), 0 if bt is None else bt.data_ptr(), int(bool(intercept)),
+                                                                int(mode), _iptr(lw), out.data_ptr()))
+    return out.cpu().numpy()
+
+
+def logistic_multi_fold_plan(n, p, ninst, ngroups, intercept=True, layout=0, num_cu=256):
+    """oemgpu_selftest_logistic_multi_fold_plan (pure host arithmetic) as a dict"""
+    out = (C.c_int64 * 11)()
+    L.check(L.lib().oemgpu_selftest_logistic_multi_fold_plan(int(n), int(p), int(ninst), int(ngroups), int(bool(intercept)), int(layout), int(num_cu), out))
+    keys = ["rows", "row_chunks", "chunk_instances", "instance_chunks", "groups", "panel_bytes", "group_bytes", "shared_bytes", "chunk_bytes",
+            "hessian_bytes", "bytes"]
+    return dict(zip(keys, [int(v) for v in out]))
 
 
 class SparseX:
@@ -1987,6 +2102,65 @@ def _cv_oem_binomial_on(fit, score, device, n, p, yh, penalty, type_measure, nfo
     res["best.model"] = penalty[res["model.min"] - 1]
     res["penalty"] = list(penalty)
     return res
+
+
+def cv_oem_logistic_multi(x, Y, penalty=None, lambda_=None, type_measure=None, nfolds=10, foldid=None, grouped=True, keep=False, rng=None, **kw):
+    """[cv_oem(x, Y[:, r], family="binomial", foldid=f, ...) for r in range(m)] for the m binomial responses of Y on one resident x, with
+    ONE foldid f for all of them (drawn once when not given) and ONE call that makes all m (K + 1) fits in lock-step
+    (oem_fit_logistic_dense_multi_folds).  From the fits on it is cv_oem's own code (_cv_oem_binomial_on): the held-out
+    rows of response r are scored by logistic_cv_score / logistic_cv_auc on the device column Y[:, r], once per response.  Every element
+    has cv_oem's keys (predict_cv, plot_cv and summary_cv take it) and one more, "route" = "multi_folds".  x: a dense torch tensor on a
+    GPU with p + intercept <= 1024; the keyword arguments are oem_fit_logistic_dense_multi's.  ValueErrors before a device is looked for:
+    hessian_type="full", weights, a host or sparse x, ngpus / devices, p + intercept > 1024, len(lambda_) < 2, nfolds < 3."""
+    penalty = _match_penalty(penalty)
+    if type_measure is None:
+        type_measure = "default"
+    elif type_measure not in _TYPE_MEASURES:
+        raise ValueError("'arg' should be one of " + ", ".join("'%s'" % t for t in _TYPE_MEASURES))
+    if lambda_ is not None and len(lambda_) < 2:
+        raise ValueError("Need more than one value of lambda for cv.oem")
+    for drop in ("accelerate", "ncores"):            # oem() arguments the binomial fit has no use for (no Nesterov step, no OpenMP)
+        kw.pop(drop, None)
+    if kw.pop("ngpus", 0) or kw.pop("devices", None) is not None:
+        raise ValueError("cv_oem_logistic_multi() runs on the one device that holds x: ngpus / devices are not served")
+    if len(kw.pop("weights", ())) > 0:
+        raise ValueError("weights not implemented yet.")
+    if kw.get("hessian_type", "upper.bound") == "full":
+        raise ValueError("hessian_type='full' builds one Hessian per response and IRLS step: call cv_oem(family='binomial') for each column")
+    if isinstance(x, SparseX) or _is_scipy_sparse(x) or _is_torch_sparse(x) or not _is_torch_cuda(x):
+        raise ValueError("cv_oem_logistic_multi() takes a dense torch tensor on a GPU: a host or sparse x is cross-validated one response at a "
+                         "time with cv_oem(family='binomial')")
+    if getattr(x, "ndim", 0) != 2 or x.shape[1] < 2:
+        raise ValueError("x must have at least two columns")
+    if getattr(Y, "ndim", None) != 2:
+        raise ValueError("Y must be a matrix of n rows and one column per response")
+    n, p = x.shape
+    if Y.shape[0] != n:
+        raise ValueError("x and y lengths do not match")
+    if p + int(bool(kw.get("intercept", True))) > 1024:
+        raise ValueError("cv_oem_logistic_multi() serves p + intercept <= 1024: call cv_oem(family='binomial') for each column")
+    if foldid is None:
+        if int(nfolds) < 3:
+            raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
+        g = np.random.default_rng() if rng is None else rng
+        foldid = g.permutation(np.resize(np.arange(1, int(nfolds) + 1), n))
+    else:
+        foldid = np.asarray(foldid.cpu() if _is_torch_cuda(foldid) else foldid).ravel()
+    import torch
+    lam_arg = () if lambda_ is None else lambda_
+    fits = oem_fit_logistic_dense_multi_folds(x, Y, foldid, penalty=penalty, lambda_=lam_arg, **kw)
+    xd = _DeviceX(x, _logistic_rowmajor_in_place).resident
+    Yd, _, _ = _device_responses(Y, xd.device)
+    out = []
+    for r, mine in enumerate(fits):
+        yd = Yd[:, r].contiguous()
+        yh = yd.cpu().numpy()
+        res = _cv_oem_binomial_on(lambda fd, nf, leave_out, mine=mine: mine[leave_out],
+                                  lambda fd, nf, coef, yd=yd, **k: logistic_cv_score(xd, yd, fd, nf, coef, **k), xd.device, n, p, yh, penalty,
+                                  type_measure, nfolds, foldid, grouped, keep, rng, yd)
+        res["route"] = "multi_folds"
+        out.append(res)
+    return out
 
 
 def _cv_gaussian_resident(x, penalty, kw, foldid, nfolds):

@@ -34,6 +34,9 @@
 // algorithm for the m columns of Y in lock-step -- XX, d and A once per call (at beta = 0 they hold no y), the row pass of a step for
 // all live responses from logistic_multi.hip, and this file's small kernels with a workgroup (or grid row) per response:
 // logit_inner_multi_kernel is logit_inner_kernel's body (logit_inner_solve) per response.
+// Their cross-validation (oemgpu_fit_logistic_dense_multi_fold_dev / _rm_dev): the same driver over INSTANCES (response,
+// fold left out) -- s, XX, d and A once per distinct fold left out (a group), every instance a masked column of the shared row pass,
+// the small kernels picking their instance's group.
 // The host driver (logistic_irls) is shared with the sparse fit (logistic_sparse.hip): the passes over the data reach it as the stages of
 // a LogitData (logistic.hpp); DenseLogitData below is this file's, over a column-major x or (the readers of logistic_rm.hip) a row-major x of
 // float64 / float32 elements read where it lies (oemgpu_fit_logistic_dense_rm_dev, ..._fold_rm_dev; kernels: logistic_rm.hip).
@@ -44,6 +47,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 namespace oemgpu {
@@ -369,25 +373,30 @@ __global__ __launch_bounds__(1024) void logit_inner_kernel(const double *__restr
 // ---------------------------------------------------------------------------------------------------------------- many responses
 // logistic_irls_multi's small kernels: workgroup (or grid row) r is response r of the lock-step chunk -- its q entries of beta, xy,
 // beta_irls, its p + 2 of g, its PenK (its own lambda), its live word.  A frozen response (live[r] == 0) is skipped by every one.
+// grp[r] is the GROUP of instance r: the fold it leaves out decides its s, XX, A and its number of rows nv[grp[r]],
+// which lie group after group (p, q q, q q doubles and one double each); the plain call has the one group 0.
 template <bool A_LDS>
 __global__ __launch_bounds__(1024) void logit_inner_multi_kernel(const double *__restrict__ A, const double *__restrict__ xy, double *__restrict__ beta,
                                                                  int q, LogitPen P, const PenK *__restrict__ pk, int maxit, double tol,
-                                                                 const int *__restrict__ live, double *__restrict__ iters)
+                                                                 const int *__restrict__ live, const int *__restrict__ grp, double *__restrict__ iters)
 {
     const int r = blockIdx.x;
     if (!live[r]) return;
     P.k = pk[r];
-    logit_inner_solve<A_LDS>(A, xy + (size_t)r * q, beta + (size_t)r * q, q, P, maxit, tol, iters + r);
+    logit_inner_solve<A_LDS>(A + (size_t)grp[r] * q * q, xy + (size_t)r * q, beta + (size_t)r * q, q, P, maxit, tol, iters + r);
 }
 
 // logit_xy_kernel for response blockIdx.y
 __global__ __launch_bounds__(256) void logit_xy_multi_kernel(const double *__restrict__ xx, const double *__restrict__ beta, const double *__restrict__ g,
-                                                             const double *__restrict__ s, int p, int intercept, double n, int init,
-                                                             const int *__restrict__ live, double *__restrict__ xy)
+                                                             const double *__restrict__ s, int p, int intercept, const double *__restrict__ nv, int init,
+                                                             const int *__restrict__ live, const int *__restrict__ grp, double *__restrict__ xy)
 {
     const int q = p + (intercept ? 1 : 0), r = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= q || !live[r]) return;
+    const int gi = grp[r];
+    const double n = nv[gi];
+    xx += (size_t)gi * q * q; s += (size_t)gi * p;
     beta += (size_t)r * q; g += (size_t)r * (p + 2); xy += (size_t)r * q;
     const bool icpt = intercept && i == 0;
     const int j = i - (intercept ? 1 : 0);
@@ -400,14 +409,15 @@ __global__ __launch_bounds__(256) void logit_xy_multi_kernel(const double *__res
 
 // the step's start for the live responses: beta_irls <- beta, and Bt = beta o s with the intercept's entry as it is (the row pass reads it)
 __global__ __launch_bounds__(256) void logit_step_multi_kernel(const double *__restrict__ beta, const double *__restrict__ s, int q, int intercept,
-                                                               const int *__restrict__ live, double *__restrict__ birls, double *__restrict__ bt)
+                                                               const int *__restrict__ live, const int *__restrict__ grp, double *__restrict__ birls,
+                                                               double *__restrict__ bt)
 {
     const int r = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= q || !live[r]) return;
     const size_t e = (size_t)r * q + i;
     const double b = beta[e];
     birls[e] = b;
-    bt[e] = (intercept && i == 0) ? b : b * s[i - (intercept ? 1 : 0)];
+    bt[e] = (intercept && i == 0) ? b : b * s[(size_t)grp[r] * (q - (intercept ? 1 : 0)) + i - (intercept ? 1 : 0)];
 }
 
 // IRLS stop of response blockIdx.x: stopw[r] = stopRule(beta, beta_irls, irls_tol); a response that stops is frozen here (live[r] = 0)
@@ -425,12 +435,13 @@ __global__ __launch_bounds__(1024) void logit_irls_stop_multi_kernel(const doubl
 
 // logit_back_kernel for response blockIdx.y into its slot of bout; lossw[r] = the loss of its last own row pass
 __global__ __launch_bounds__(256) void logit_back_multi_kernel(const double *__restrict__ beta, const double *__restrict__ s, const double *__restrict__ g,
-                                                               int p, int intercept, size_t stride, double *__restrict__ out, double *__restrict__ lossw)
+                                                               int p, int intercept, size_t stride, const int *__restrict__ grp, double *__restrict__ out,
+                                                               double *__restrict__ lossw)
 {
     const int r = blockIdx.y, q = p + (intercept ? 1 : 0);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i > p) return;
-    beta += (size_t)r * q; out += (size_t)r * stride;
+    beta += (size_t)r * q; out += (size_t)r * stride; s += (size_t)grp[r] * p;
     if (i == 0) { out[0] = intercept ? beta[0] : 0.0; lossw[r] = g[(size_t)r * (p + 2) + p + 1]; return; }
     out[i] = beta[(intercept ? 1 : 0) + i - 1] * s[i - 1];
 }
@@ -1099,20 +1110,26 @@ static int lm_blocks_skipped(const LogitMultiPlan &pl, const std::vector<int> &l
     return k;
 }
 
-// logistic_irls (hessian.type "upper.bound") for the m columns of Y in lock-step.  With the upper bound the Hessian is
-// built at beta = 0, where every W is 0.25 and the floor cannot bite: XX, d and A do not depend on y, and the reference's rebuild at the
-// start of every penalty returns the same matrix.  So: s, XX (DenseLogitData's own Hessian pass with response 0 riding as y), ONE
-// Lanczos and A once per call; then, per chunk of at most LMULTI_MCH responses, the X'Y pass and every response's own lambda grid, and
-// per penalty and lambda the IRLS steps of all its live responses from one row pass (logistic_multi.hip), one inner launch (a
-// workgroup per response), one stop launch and ONE host read of the stop words.  A response that meets the IRLS stop is frozen for
-// the rest of the lambda: no kernel writes its beta, xy, g or Bt again, and its niter is that step's.  The skipped row pass at
-// (i = 0, li > 0) holds for all at once: every response solves at the new lambda on the xy of its last own pass.
-static int logistic_irls_multi(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const MultiY &Y, int32_t m, int32_t standardize, int32_t intercept,
-                               int32_t irls_maxit, double irls_tol, const oemgpu_opts *o, double *beta_out, double *lambda_out, int32_t *niter,
-                               double *loss_out, double *d_out)
+// logistic_irls (hessian.type "upper.bound") for a list of INSTANCES in lock-step.  Instance i is response
+// resp[i] of Y fitted on the rows with foldid != leave[i] (leave 0, or no foldid at all: every row); the plain many-response call is
+// the list (r, 0), r < m.  With the upper bound the Hessian is built at beta = 0, where every W is 0.25 and the floor cannot bite: XX, d
+// and A hold no y, only the rows kept, and the reference's rebuild at the start of every penalty returns the same matrix.  So, per
+// distinct leave value (a GROUP): s, XX (DenseLogitData's own scale and Hessian passes, masked by set_fold as the single fold fit's,
+// with response 0 riding as y), ONE Lanczos and A, once per call; then, per chunk of at most LMULTI_MCH instances, the X'Y pass and
+// every instance's own lambda grid, and per penalty and lambda the IRLS steps of all its live instances from one row pass
+// (logistic_multi.hip, masked per column), one inner launch (a workgroup per instance, on its group's A), one stop launch and ONE
+// host read of the stop words.  An instance that meets the IRLS stop is frozen for the rest of the lambda: no kernel writes its beta,
+// xy, g or Bt again, and its niter is that step's.  The skipped row pass at (i = 0, li > 0) holds for all at once: every instance
+// solves at the new lambda on the xy of its last own pass.  No instance's result depends on the others or on the list's order.
+// Outputs are indexed by instance; nobs (or null): the rows of its fit.
+static int logistic_irls_multi(const char *who, oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const MultiY &Y, const int32_t *foldid, int32_t nfolds,
+                               int32_t ninst, const int32_t *resp, const int32_t *leave, int32_t standardize, int32_t intercept, int32_t irls_maxit,
+                               double irls_tol, const oemgpu_opts *o, double *beta_out, double *lambda_out, int32_t *niter, double *loss_out, double *d_out,
+                               int64_t *nobs)
 {
     const double t_start = now_ms();
     g_lm_stats = LogitMultiStats();
+    const int m = ninst;
     const int q = p + (intercept ? 1 : 0), o1 = intercept ? 1 : 0;
     const bool provided = o->lambda_user && o->nlambda_user > 0;
     const int nl = provided ? o->nlambda_user : o->nlambda, npen = o->npen;
@@ -1121,25 +1138,58 @@ static int logistic_irls_multi(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int3
     const int ng = T.ng, ng1 = ng > 0 ? ng : 1;
     const int mch = m < LMULTI_MCH ? m : LMULTI_MCH;
     const LogitMultiPlan PW = logit_multi_plan(n, p, mch, c->num_cu);          // (the widest chunk: its panels bound every chunk's)
-    DenseLogitData D(c, X, n, p, nullptr, standardize, intercept, 0);
-    // ---- workspace (c->aux): what the call shares, one chunk's state, the Hessian pass's stages
+    // ---- the groups: the distinct leave values in ascending order; igrp[i]: instance i's
+    std::vector<int> gleave, igrp((size_t)m, 0);
+    if (foldid) {
+        std::vector<int> of((size_t)nfolds + 1, -1);
+        for (int i = 0; i < m; ++i) of[(size_t)leave[i]] = 0;
+        for (int k = 0; k <= nfolds; ++k)
+            if (of[(size_t)k] == 0) { of[(size_t)k] = (int)gleave.size(); gleave.push_back(k); }
+        for (int i = 0; i < m; ++i) igrp[(size_t)i] = of[(size_t)leave[i]];
+    } else {
+        gleave.push_back(0);
+    }
+    const int G = (int)gleave.size();
+    // every group's look at foldid before any fit: the ids' range, its rows, p + intercept < its rows
+    std::vector<std::unique_ptr<DenseLogitData>> Ds;
+    std::vector<double> hnv((size_t)G), hd((size_t)G, 0.0);
+    for (int gi = 0; gi < G; ++gi) {
+        Ds.emplace_back(new DenseLogitData(c, X, n, p, nullptr, standardize, intercept, 0));
+        DenseLogitData &D = *Ds.back();
+        if (foldid) {
+            const int k = gleave[(size_t)gi];
+            int rc = 0;
+            if (k > 0) rc = D.set_fold(foldid, nfolds, k, irls_maxit);
+            else { std::vector<int64_t> none; int64_t all = 0; rc = logit_fold_scan(c, who, foldid, n, nfolds, 0, 0, &all, &none); }   // (the ids' range; the fit is the plain one)
+            if (rc) return rc;
+            if ((int64_t)q >= D.n_eff) {
+                set_error("%s: p + intercept >= the %lld rows outside fold %d is not supported (the reference's XWXt branch, "
+                          "ref src/oem_logistic_dense.h:524-566)", who, (long long)D.n_eff, k);
+                return OEMGPU_ERR_UNSUPPORTED;
+            }
+        }
+        hnv[(size_t)gi] = (double)D.n_eff;
+    }
+    // ---- workspace (c->aux): what the groups hold, one chunk's state, the Hessian pass's stages
     Bump B;
-    const size_t a_s = B.take(8 * (size_t)p), a_xx = B.take(8 * (size_t)q * q), a_a = B.take(8 * (size_t)q * q), a_z = B.take(8 * (size_t)q),
-                 a_g0 = B.take(8 * (size_t)(p + 2)), a_col = Y.rs != 1 ? B.take(8 * (size_t)n) : 0;
+    const size_t a_s = B.take(8 * (size_t)G * p), a_xx = B.take(8 * (size_t)G * q * q), a_a = B.take(8 * (size_t)G * q * q), a_nv = B.take(8 * (size_t)G),
+                 a_z = B.take(8 * (size_t)q), a_g0 = B.take(8 * (size_t)(p + 2)), a_col = Y.rs != 1 ? B.take(8 * (size_t)n) : 0;
     const size_t a_b = B.take(8 * (size_t)mch * q), a_bi = B.take(8 * (size_t)mch * q), a_xy = B.take(8 * (size_t)mch * q),
                  a_bt = B.take(8 * (size_t)mch * q), a_g = B.take(8 * (size_t)mch * (p + 2)), a_live = B.take(4 * (size_t)mch),
-                 a_stop = B.take(4 * (size_t)mch), a_it = B.take(8 * (size_t)mch), a_loss = B.take(8 * (size_t)mch),
+                 a_stop = B.take(4 * (size_t)mch), a_grp = B.take(4 * (size_t)mch), a_lv = B.take(4 * (size_t)mch), a_yc = B.take(4 * (size_t)mch),
+                 a_it = B.take(8 * (size_t)mch), a_loss = B.take(8 * (size_t)mch),
                  a_pk = B.take(sizeof(PenK) * (size_t)nl * mch), a_part = B.take(8 * PW.part_doubles), a_out = B.take(8 * (size_t)mch * nl * (p + 1));
     const size_t a_pf = B.take(8 * (size_t)q), a_gw = B.take(8 * (size_t)ng1), a_perm = B.take(4 * (size_t)(q + 1)), a_gs = B.take(4 * (size_t)(ng + 1)),
                  a_gof = B.take(4 * (size_t)q), a_gz = B.take(4 * (size_t)ng1);
-    const size_t a_data = B.take(D.ws_bytes());
+    const size_t a_data = B.take(Ds[0]->ws_bytes());
     ctx_void_cv(c);
     if (ctx_grow(c, &c->aux, &c->aux_bytes, B.off)) return OEMGPU_ERR_HIP;
     char *W = c->aux;
-    double *sc = (double *)(W + a_s), *xx = (double *)(W + a_xx), *A = (double *)(W + a_a), *zero = (double *)(W + a_z), *g0 = (double *)(W + a_g0),
-           *beta = (double *)(W + a_b), *birls = (double *)(W + a_bi), *xy = (double *)(W + a_xy), *bt = (double *)(W + a_bt), *g = (double *)(W + a_g),
-           *iters = (double *)(W + a_it), *lossw = (double *)(W + a_loss), *part = (double *)(W + a_part), *bout = (double *)(W + a_out);
-    int *live = (int *)(W + a_live), *stopw = (int *)(W + a_stop);
+    double *sc = (double *)(W + a_s), *xx = (double *)(W + a_xx), *A = (double *)(W + a_a), *nv = (double *)(W + a_nv), *zero = (double *)(W + a_z),
+           *g0 = (double *)(W + a_g0), *beta = (double *)(W + a_b), *birls = (double *)(W + a_bi), *xy = (double *)(W + a_xy), *bt = (double *)(W + a_bt),
+           *g = (double *)(W + a_g), *iters = (double *)(W + a_it), *lossw = (double *)(W + a_loss), *part = (double *)(W + a_part),
+           *bout = (double *)(W + a_out);
+    int *live = (int *)(W + a_live), *stopw = (int *)(W + a_stop), *grp = (int *)(W + a_grp), *lvd = (int *)(W + a_lv), *ycd = (int *)(W + a_yc);
     PenK *pkd = (PenK *)(W + a_pk);
     hipStream_t s = c->stream;
     OEM_HIP(hipMemcpyAsync(W + a_pf, T.pf.data(), 8 * (size_t)q, hipMemcpyHostToDevice, s));
@@ -1148,6 +1198,7 @@ static int logistic_irls_multi(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int3
     OEM_HIP(hipMemcpyAsync(W + a_gs, T.gstart.data(), 4 * T.gstart.size(), hipMemcpyHostToDevice, s));
     OEM_HIP(hipMemcpyAsync(W + a_gof, T.gof.data(), 4 * (size_t)q, hipMemcpyHostToDevice, s));
     OEM_HIP(hipMemcpyAsync(W + a_gz, T.gzero.data(), 4 * T.gzero.size(), hipMemcpyHostToDevice, s));
+    OEM_HIP(hipMemcpyAsync(nv, hnv.data(), 8 * (size_t)G, hipMemcpyHostToDevice, s));
     OEM_HIP(hipStreamSynchronize(s));                                           // (the tables are the host's again)
     LogitPen LP;
     LP.pf = (const double *)(W + a_pf); LP.gw = (const double *)(W + a_gw); LP.perm = (const int *)(W + a_perm);
@@ -1174,32 +1225,36 @@ static int logistic_irls_multi(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int3
         if (r) (void)hipStreamSynchronize(s);
         return r;
     };
-    // ---- once per call: s, XX at beta = 0, d = 1.0005 lambda_max (h :514), A = dI - XX
+    // ---- once per call and group: s, XX at beta = 0, d = 1.0005 lambda_max (h :514), A = dI - XX
     int rc = 0;
-    D.y = Y.y;
+    const double *y0 = Y.y;
     if (Y.rs != 1) {
         double *col = (double *)(W + a_col);
         if ((rc = launch_multi_column(s, Y, n, 0, col))) return finish(rc);
-        D.y = col;
+        y0 = col;
     }
-    rc = D.bind(W + a_data);
-    if (!rc) rc = D.scale(sc);
-    if (rc) return finish(rc);
     OEM_HIP(hipMemsetAsync(zero, 0, 8 * (size_t)q, s));
-    double d = 0.0;
-    rc = stage(&g_lm_stats.ms_gram, [&]() -> int {
-        int r = D.hessian(zero, sc, 0, g0, xx);
-        if (r) return r;
-        double lm = 0.0;
-        r = oemgpu_eig_max_dev(c, xx, q, &lm);                                  // (synchronises)
-        if (r) return r;
-        d = lm * 1.0005;
-        hipLaunchKernelGGL(logit_a_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, xx, q, d, A);
-        OEM_HIP(hipGetLastError());
-        return 0;
-    });
-    if (rc) return finish(rc);
-    g_lm_stats.grams = 1; g_lm_stats.lanczos = 1;
+    for (int gi = 0; gi < G; ++gi) {
+        DenseLogitData &D = *Ds[(size_t)gi];
+        double *scg = sc + (size_t)gi * p, *xxg = xx + (size_t)gi * q * q, *Ag = A + (size_t)gi * q * q;
+        D.y = y0;
+        rc = D.bind(W + a_data);                                                // (the groups take the stages' buffers in turn, on one stream)
+        if (!rc) rc = D.scale(scg);
+        if (rc) return finish(rc);
+        rc = stage(&g_lm_stats.ms_gram, [&]() -> int {
+            int r = D.hessian(zero, scg, 0, g0, xxg);
+            if (r) return r;
+            double lm = 0.0;
+            r = oemgpu_eig_max_dev(c, xxg, q, &lm);                             // (synchronises)
+            if (r) return r;
+            hd[(size_t)gi] = lm * 1.0005;
+            hipLaunchKernelGGL(logit_a_kernel, dim3((q + 255) / 256, q), dim3(256), 0, s, xxg, q, hd[(size_t)gi], Ag);
+            OEM_HIP(hipGetLastError());
+            return 0;
+        });
+        if (rc) return finish(rc);
+        g_lm_stats.grams += 1; g_lm_stats.lanczos += 1;
+    }
     const bool alds = q <= LOGIT_A_LDS_Q;
     const size_t lds_inner = 8 * (size_t)(3 * q + ng1 + (alds ? q * q : 0));
     if (lds_limit_once(alds ? reinterpret_cast<const void *>(&logit_inner_multi_kernel<true>) : reinterpret_cast<const void *>(&logit_inner_multi_kernel<false>),
@@ -1208,13 +1263,25 @@ static int logistic_irls_multi(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int3
     std::vector<double> hxy((size_t)mch * q), lam((size_t)mch * nl), hloss((size_t)mch), hit((size_t)mch);
     std::vector<std::vector<double>> baser((size_t)mch, std::vector<double>((size_t)nl));
     std::vector<PenK> pkh((size_t)nl * mch);
-    std::vector<int> hlive((size_t)mch), hstop((size_t)mch), nit((size_t)mch);
+    std::vector<int> hlive((size_t)mch), hstop((size_t)mch), nit((size_t)mch), hyc((size_t)mch);
     const size_t nk = (size_t)npen * nl, blen = nk * (size_t)(p + 1);
     bool interrupted = false;
     for (int r0 = 0; r0 < m && !interrupted; r0 += mch) {
         const int mc = m - r0 < mch ? m - r0 : mch;
         const LogitMultiPlan pl = logit_multi_plan(n, p, mc, c->num_cu);
-        const MultiY Yc{Y.y + (int64_t)r0 * Y.cs, Y.rs, Y.cs};
+        // the plain call reads its chunk's columns of Y where they lie; a fold call reads column resp[i] for instance i, masked
+        const MultiY Yc{foldid ? Y.y : Y.y + (int64_t)resp[r0] * Y.cs, Y.rs, Y.cs};
+        LogitMultiFold FM;
+        const LogitMultiFold *fm = nullptr;
+        OEM_HIP(hipMemcpyAsync(grp, igrp.data() + r0, 4 * (size_t)mc, hipMemcpyHostToDevice, s));
+        if (foldid) {
+            for (int r = 0; r < mc; ++r) hyc[(size_t)r] = resp[r0 + r];
+            OEM_HIP(hipMemcpyAsync(lvd, leave + r0, 4 * (size_t)mc, hipMemcpyHostToDevice, s));
+            OEM_HIP(hipMemcpyAsync(ycd, hyc.data(), 4 * (size_t)mc, hipMemcpyHostToDevice, s));
+            OEM_HIP(hipStreamSynchronize(s));                                   // (hyc is the host's again)
+            FM.foldid = foldid; FM.leave = lvd; FM.ycol = ycd;
+            fm = &FM;
+        }
         const dim3 gq((unsigned)((q + 255) / 256), (unsigned)mc);
         auto set_live = [&]() -> int {
             hipLaunchKernelGGL(logit_fill_int_kernel, dim3((mc + 255) / 256), dim3(256), 0, s, live, mc, 1);
@@ -1222,16 +1289,16 @@ static int logistic_irls_multi(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int3
             std::fill(hlive.begin(), hlive.begin() + mc, 1);
             return 0;
         };
-        // ---- init_oem per response: XY = s o X'Y / n, lambda_0 = max |XY| over the non-intercept slots (h :762-805)
+        // ---- init_oem per instance: XY = s o X'Y / n, lambda_0 = max |XY| over the non-intercept slots (h :762-805)
         if ((rc = set_live())) return finish(rc);
         OEM_HIP(hipMemsetAsync(iters, 0, 8 * (size_t)mc, s));
         rc = stage(&g_lm_stats.ms_rows, [&]() -> int {
-            int r = launch_logit_multi_rows(s, pl, X, Yc, nullptr, intercept, 0, live, part);
+            int r = launch_logit_multi_rows(s, pl, X, Yc, nullptr, intercept, 0, live, part, fm);
             if (!r) r = launch_logit_multi_reduce(s, pl, part, live, g);
             return r;
         });
         if (rc) return finish(rc);
-        hipLaunchKernelGGL(logit_xy_multi_kernel, gq, dim3(256), 0, s, xx, beta, g, sc, p, intercept, (double)n, 1, live, xy);
+        hipLaunchKernelGGL(logit_xy_multi_kernel, gq, dim3(256), 0, s, xx, beta, g, sc, p, intercept, nv, 1, live, grp, xy);
         OEM_HIP(hipGetLastError());
         OEM_HIP(hipMemcpyAsync(hxy.data(), xy, 8 * (size_t)mc * q, hipMemcpyDeviceToHost, s));
         OEM_HIP(hipStreamSynchronize(s));
@@ -1248,7 +1315,7 @@ static int logistic_irls_multi(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int3
                 logit_lambda_row(o, k, provided, baser[(size_t)r], nl, lr);
                 for (int i = 0; i < nl; ++i) {
                     lambda_out[((size_t)(r0 + r) * npen + k) * nl + i] = lr[i];
-                    pkh[(size_t)i * mc + r] = logit_penk(o, pen, lr[i], d);
+                    pkh[(size_t)i * mc + r] = logit_penk(o, pen, lr[i], hd[(size_t)igrp[(size_t)(r0 + r)]]);
                 }
             }
             OEM_HIP(hipMemcpy(pkd, pkh.data(), sizeof(PenK) * (size_t)nl * mc, hipMemcpyHostToDevice));
@@ -1259,27 +1326,27 @@ static int logistic_irls_multi(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int3
                 int nlive = mc;
                 for (int i = 0; i < irls_maxit && nlive > 0; ++i) {
                     if (o->interrupt && o->interrupt(o->interrupt_arg)) { interrupted = true; break; }
-                    hipLaunchKernelGGL(logit_step_multi_kernel, gq, dim3(256), 0, s, beta, sc, q, intercept, live, birls, bt);
+                    hipLaunchKernelGGL(logit_step_multi_kernel, gq, dim3(256), 0, s, beta, sc, q, intercept, live, grp, birls, bt);
                     OEM_HIP(hipGetLastError());
                     if (!(i == 0 && li > 0)) {
                         rc = stage(&g_lm_stats.ms_rows, [&]() -> int {
-                            int r = launch_logit_multi_rows(s, pl, X, Yc, bt, intercept, 1, live, part);
+                            int r = launch_logit_multi_rows(s, pl, X, Yc, bt, intercept, 1, live, part, fm);
                             if (!r) r = launch_logit_multi_reduce(s, pl, part, live, g);
                             return r;
                         });
                         if (rc) return finish(rc);
                         g_lm_stats.row_passes += 1;
                         g_lm_stats.blocks_skipped += lm_blocks_skipped(pl, hlive);
-                        hipLaunchKernelGGL(logit_xy_multi_kernel, gq, dim3(256), 0, s, xx, beta, g, sc, p, intercept, (double)n, 0, live, xy);
+                        hipLaunchKernelGGL(logit_xy_multi_kernel, gq, dim3(256), 0, s, xx, beta, g, sc, p, intercept, nv, 0, live, grp, xy);
                         OEM_HIP(hipGetLastError());
                     }
-                    // the OEM loop at this lambda (h :1010-1022): one workgroup per live response, A shared
+                    // the OEM loop at this lambda (h :1010-1022): one workgroup per live instance, on its group's A
                     rc = stage(&g_lm_stats.ms_inner, [&]() -> int {
                         const PenK *pk = pkd + (size_t)li * mc;
                         if (alds) {
-                            hipLaunchKernelGGL(logit_inner_multi_kernel<true>, dim3(mc), dim3(1024), lds_inner, s, A, xy, beta, q, LP, pk, o->maxit, o->tol, live, iters);
+                            hipLaunchKernelGGL(logit_inner_multi_kernel<true>, dim3(mc), dim3(1024), lds_inner, s, A, xy, beta, q, LP, pk, o->maxit, o->tol, live, grp, iters);
                         } else {
-                            hipLaunchKernelGGL(logit_inner_multi_kernel<false>, dim3(mc), dim3(1024), lds_inner, s, A, xy, beta, q, LP, pk, o->maxit, o->tol, live, iters);
+                            hipLaunchKernelGGL(logit_inner_multi_kernel<false>, dim3(mc), dim3(1024), lds_inner, s, A, xy, beta, q, LP, pk, o->maxit, o->tol, live, grp, iters);
                         }
                         OEM_HIP(hipGetLastError());
                         return 0;
@@ -1297,7 +1364,7 @@ static int logistic_irls_multi(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int3
                 for (int r = 0; r < mc; ++r)
                     if (hlive[(size_t)r]) nit[(size_t)r] = irls_maxit + 1;             // the cap (h :1035)
                 hipLaunchKernelGGL(logit_back_multi_kernel, dim3((p + 1 + 255) / 256, mc), dim3(256), 0, s, beta, sc, g, p, intercept, (size_t)nl * (p + 1),
-                                   bout + (size_t)li * (p + 1), lossw);
+                                   grp, bout + (size_t)li * (p + 1), lossw);
                 OEM_HIP(hipGetLastError());
                 if (o->compute_loss) {                                              // the loss of the LAST prob computed: of its last own row pass
                     OEM_HIP(hipMemcpyAsync(hloss.data(), lossw, 8 * (size_t)mc, hipMemcpyDeviceToHost, s));
@@ -1318,21 +1385,40 @@ static int logistic_irls_multi(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int3
         }
         if (interrupted) break;
         OEM_HIP(hipMemcpy(hit.data(), iters, 8 * (size_t)mc, hipMemcpyDeviceToHost));
-        for (int r = 0; r < mc; ++r) { g_lm_stats.inner_iters += hit[(size_t)r]; d_out[r0 + r] = d; }
+        for (int r = 0; r < mc; ++r) {
+            const int gi = igrp[(size_t)(r0 + r)];
+            g_lm_stats.inner_iters += hit[(size_t)r];
+            d_out[r0 + r] = hd[(size_t)gi];
+            if (nobs) nobs[r0 + r] = (int64_t)hnv[(size_t)gi];
+        }
     }
     if (interrupted) { (void)finish(1); set_error("interrupted"); return OEMGPU_ERR_INTERRUPTED; }
     g_lm_stats.wall_ms = now_ms() - t_start;
     return finish(0);
 }
 
-// the checks of the two many-response entries, before a device is looked for; then the fit
+// the checks of the many-response entries, before a device is looked for; then the fit.  foldid_dev null: the plain call, the
+// instances (r, 0) for r < m; else the list (resp[i], leave_out[i]) of ninst instances
 static int logistic_multi_checked(const char *who, oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const double *y_dev, int64_t rs, int64_t cs,
-                                  int32_t m, int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol,
-                                  const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
+                                  int32_t m, bool fold, const int32_t *foldid_dev, int32_t nfolds, int32_t ninst, const int32_t *resp, const int32_t *leave_out,
+                                  int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit, double irls_tol,
+                                  const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int64_t *nobs)
 {
-    if (!c || !X.x || !y_dev || !o || !beta || !lambda_out || !niter || !loss || !d) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    if (fold && ninst < 1) { set_error("%s: ninst must be at least 1", who); return OEMGPU_ERR_ARG; }
+    if (!c || !X.x || !y_dev || !o || !beta || !lambda_out || !niter || !loss || !d || (fold && (!foldid_dev || !resp || !leave_out || !nobs))) {
+        set_error("%s: NULL argument", who);
+        return OEMGPU_ERR_ARG;
+    }
     int rc = multi_y_check(who, n, rs, cs, m);
-    if (!rc) rc = dense_src_check(who, X, n, p);
+    if (rc) return rc;
+    if (fold) {
+        if (nfolds < 3) { set_error("nfolds must be bigger than 3; nfolds=10 recommended"); return OEMGPU_ERR_ARG; }            // ref R/cv_oem.R:126-127
+        for (int i = 0; i < ninst; ++i) {
+            if (leave_out[i] < 0 || leave_out[i] > nfolds) { set_error("%s: leave_out must be in [0, nfolds]", who); return OEMGPU_ERR_ARG; }
+            if (resp[i] < 0 || resp[i] >= m) { set_error("%s: resp must be in [0, m)", who); return OEMGPU_ERR_ARG; }
+        }
+    }
+    rc = dense_src_check(who, X, n, p);
     if (!rc) rc = logistic_check(n, p, intercept, hessian_full, irls_maxit, irls_tol, o);
     if (rc) return rc;
     if (hessian_full) {
@@ -1345,32 +1431,46 @@ static int logistic_multi_checked(const char *who, oemgpu_ctx *c, const DenseSrc
         return OEMGPU_ERR_UNSUPPORTED;
     }
     if (set_device(c)) return OEMGPU_ERR_HIP;
-    return logistic_irls_multi(c, X, n, p, MultiY{y_dev, rs, cs}, m, standardize, intercept, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
+    if (fold)
+        return logistic_irls_multi(who, c, X, n, p, MultiY{y_dev, rs, cs}, foldid_dev, nfolds, ninst, resp, leave_out, standardize, intercept, irls_maxit,
+                                   irls_tol, o, beta, lambda_out, niter, loss, d, nobs);
+    std::vector<int32_t> all((size_t)m), none((size_t)m, 0);
+    for (int r = 0; r < m; ++r) all[(size_t)r] = r;
+    return logistic_irls_multi(who, c, X, n, p, MultiY{y_dev, rs, cs}, nullptr, 0, m, all.data(), none.data(), standardize, intercept, irls_maxit, irls_tol,
+                               o, beta, lambda_out, niter, loss, d, nullptr);
 }
 
-// one row pass of logistic_multi.hip for the kernel tests: out[r] (p + 2 doubles) for the live responses, chunk of responses after chunk
+// one row pass of logistic_multi.hip for the kernel tests: out[r] (p + 2 doubles) for the live columns, chunk of columns after chunk.
+// foldid null: column r is response r of Y on every row; else column r is response ycol[r] (r without ycol) on the rows with
+// foldid != leave[r] (ycol, leave, live_host: host words)
 static int logistic_multi_rows_selftest(oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const MultiY &Y, int32_t m, const double *bt, int32_t intercept,
-                                        int32_t mode, const int32_t *live_host, double *out)
+                                        int32_t mode, const int32_t *live_host, double *out, const int32_t *foldid = nullptr, const int32_t *leave = nullptr,
+                                        const int32_t *ycol = nullptr)
 {
     g_lm_stats = LogitMultiStats();
     const int q = p + (intercept ? 1 : 0);
     const int mch = m < LMULTI_MCH ? m : LMULTI_MCH;
     const LogitMultiPlan PW = logit_multi_plan(n, p, mch, c->num_cu);
     Bump B;
-    const size_t a_part = B.take(8 * PW.part_doubles), a_live = B.take(4 * (size_t)m);
+    const size_t a_part = B.take(8 * PW.part_doubles), a_live = B.take(4 * (size_t)m), a_lv = B.take(4 * (size_t)m), a_yc = B.take(4 * (size_t)m);
     ctx_void_cv(c);
     if (ctx_grow(c, &c->aux, &c->aux_bytes, B.off)) return OEMGPU_ERR_HIP;
     double *part = (double *)(c->aux + a_part);
-    int *live = (int *)(c->aux + a_live);
+    int *live = (int *)(c->aux + a_live), *lvd = (int *)(c->aux + a_lv), *ycd = (int *)(c->aux + a_yc);
     std::vector<int> hl((size_t)m, 1);
     if (live_host) for (int r = 0; r < m; ++r) hl[(size_t)r] = live_host[r] != 0;
     OEM_HIP(hipMemcpy(live, hl.data(), 4 * (size_t)m, hipMemcpyHostToDevice));
+    if (foldid) {
+        OEM_HIP(hipMemcpy(lvd, leave, 4 * (size_t)m, hipMemcpyHostToDevice));
+        if (ycol) OEM_HIP(hipMemcpy(ycd, ycol, 4 * (size_t)m, hipMemcpyHostToDevice));
+    }
     for (int r0 = 0; r0 < m; r0 += mch) {
         const int mc = m - r0 < mch ? m - r0 : mch;
         const LogitMultiPlan pl = logit_multi_plan(n, p, mc, c->num_cu);
         const std::vector<int> lc(hl.begin() + r0, hl.begin() + r0 + mc);
-        int rc = launch_logit_multi_rows(c->stream, pl, X, MultiY{Y.y + (int64_t)r0 * Y.cs, Y.rs, Y.cs}, mode ? bt + (size_t)r0 * q : nullptr, intercept, mode,
-                                         live + r0, part);
+        const LogitMultiFold FM{foldid, lvd + r0, ycol ? ycd + r0 : nullptr};
+        const MultiY Yc{(foldid && ycol) ? Y.y : Y.y + (int64_t)r0 * Y.cs, Y.rs, Y.cs};
+        int rc = launch_logit_multi_rows(c->stream, pl, X, Yc, mode ? bt + (size_t)r0 * q : nullptr, intercept, mode, live + r0, part, foldid ? &FM : nullptr);
         if (!rc) rc = launch_logit_multi_reduce(c->stream, pl, part, live + r0, out + (size_t)r0 * (p + 2));
         if (rc) return rc;
         g_lm_stats.row_passes += 1;
@@ -1436,8 +1536,8 @@ int oemgpu_fit_logistic_dense_multi_dev(oemgpu_ctx *c, const double *x_dev, int6
                                         int64_t y_cs, int32_t m, int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit,
                                         double irls_tol, const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d)
 {
-    return logistic_multi_checked("fit_logistic_dense_multi", c, dense_src_cm(x_dev, ld), n, p, y_dev, y_rs, y_cs, m, standardize, intercept, hessian_full,
-                                  irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
+    return logistic_multi_checked("fit_logistic_dense_multi", c, dense_src_cm(x_dev, ld), n, p, y_dev, y_rs, y_cs, m, false, nullptr, 0, 0, nullptr, nullptr,
+                                  standardize, intercept, hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d, nullptr);
 }
 
 int oemgpu_fit_logistic_dense_multi_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
@@ -1445,8 +1545,50 @@ int oemgpu_fit_logistic_dense_multi_rm_dev(oemgpu_ctx *c, const void *x_dev, int
                                            int32_t irls_maxit, double irls_tol, const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter,
                                            double *loss, double *d)
 {
-    return logistic_multi_checked("fit_logistic_dense_multi_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, y_rs, y_cs, m, standardize, intercept,
-                                  hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d);
+    return logistic_multi_checked("fit_logistic_dense_multi_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, y_rs, y_cs, m, false, nullptr, 0, 0, nullptr,
+                                  nullptr, standardize, intercept, hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d, nullptr);
+}
+
+int oemgpu_fit_logistic_dense_multi_fold_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev, int64_t y_rs,
+                                             int64_t y_cs, int32_t m, const int32_t *foldid_dev, int32_t nfolds, int32_t ninst, const int32_t *resp,
+                                             const int32_t *leave_out, int32_t standardize, int32_t intercept, int32_t hessian_full, int32_t irls_maxit,
+                                             double irls_tol, const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d,
+                                             int64_t *nobs)
+{
+    return logistic_multi_checked("fit_logistic_dense_multi_fold", c, dense_src_cm(x_dev, ld), n, p, y_dev, y_rs, y_cs, m, true, foldid_dev, nfolds, ninst, resp,
+                                  leave_out, standardize, intercept, hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d, nobs);
+}
+
+int oemgpu_fit_logistic_dense_multi_fold_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev,
+                                                int64_t y_rs, int64_t y_cs, int32_t m, const int32_t *foldid_dev, int32_t nfolds, int32_t ninst,
+                                                const int32_t *resp, const int32_t *leave_out, int32_t standardize, int32_t intercept, int32_t hessian_full,
+                                                int32_t irls_maxit, double irls_tol, const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter,
+                                                double *loss, double *d, int64_t *nobs)
+{
+    return logistic_multi_checked("fit_logistic_dense_multi_fold_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, y_rs, y_cs, m, true, foldid_dev, nfolds,
+                                  ninst, resp, leave_out, standardize, intercept, hessian_full, irls_maxit, irls_tol, o, beta, lambda_out, niter, loss, d, nobs);
+}
+
+// the workspace of a fold call as pure host arithmetic: ninst instances in ngroups groups (the distinct leave_out values)
+int oemgpu_selftest_logistic_multi_fold_plan(int64_t n, int32_t p, int32_t ninst, int32_t ngroups, int32_t intercept, int32_t layout, int32_t num_cu,
+                                             int64_t *out)
+{
+    if (n < 1 || p < 1 || ninst < 1 || ngroups < 1 || num_cu < 1 || (layout != 0 && layout != 1) || !out) {
+        set_error("selftest_logistic_multi_fold_plan: bad argument");
+        return OEMGPU_ERR_ARG;
+    }
+    const int q = p + (intercept ? 1 : 0);
+    if (q > LOGIT_WG_MAX) { set_error("selftest_logistic_multi_fold_plan: p + intercept > %d is not supported", LOGIT_WG_MAX); return OEMGPU_ERR_UNSUPPORTED; }
+    const int mch = ninst < LMULTI_MCH ? ninst : LMULTI_MCH;
+    const LogitMultiPlan pl = logit_multi_plan(n, p, mch, num_cu);
+    const LogitPlan P = logit_plan(n, p, intercept, num_cu);
+    const size_t groups = 8 * (size_t)ngroups * ((size_t)p + 2 * (size_t)q * q + 1);                      // s, XX, A and the rows of every group
+    const size_t shared = 8 * ((size_t)q + (size_t)(p + 2)) + (layout == 1 ? 8 * (size_t)256 * p : 0);    // beta = 0, g; the scale pass's partials
+    const size_t chunk = 8 * ((size_t)mch * q * 4 + (size_t)mch * (p + 2) + 2 * (size_t)mch) + 4 * 5 * (size_t)mch + sizeof(PenK) * (size_t)mch;
+    out[0] = pl.rows; out[1] = pl.nchunk; out[2] = mch; out[3] = (ninst + LMULTI_MCH - 1) / LMULTI_MCH; out[4] = ngroups;
+    out[5] = (int64_t)(8 * pl.part_doubles); out[6] = (int64_t)groups; out[7] = (int64_t)shared; out[8] = (int64_t)chunk; out[9] = (int64_t)P.ws_bytes;
+    out[10] = out[5] + out[6] + out[7] + out[8] + out[9];
+    return 0;
 }
 
 int oemgpu_selftest_logistic_multi_plan(int64_t n, int32_t p, int32_t m, int32_t intercept, int32_t layout, int32_t num_cu, int64_t *out)
@@ -1481,6 +1623,26 @@ int oemgpu_selftest_logistic_multi_rows_dev(oemgpu_ctx *c, const void *x_dev, in
     if (p > LMULTI_P_MAX) { set_error("%s: p > %d is not supported", who, LMULTI_P_MAX); return OEMGPU_ERR_UNSUPPORTED; }
     if (set_device(c)) return OEMGPU_ERR_HIP;
     return logistic_multi_rows_selftest(c, X, n, p, MultiY{y_dev, y_rs, y_cs}, m, btilde_dev, intercept, mode, live, out_dev);
+}
+
+int oemgpu_selftest_logistic_multi_rows_fold_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                                                 int64_t y_rs, int64_t y_cs, int32_t m, const int32_t *foldid_dev, int32_t ncol, const int32_t *leave,
+                                                 const int32_t *ycol, const double *btilde_dev, int32_t intercept, int32_t mode, const int32_t *live,
+                                                 double *out_dev)
+{
+    const char *who = "selftest_logistic_multi_rows_fold";
+    if (!c || !x_dev || !y_dev || !foldid_dev || !leave || !out_dev || (mode && !btilde_dev)) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    if (n < 1 || p < 1 || ncol < 1 || (mode != 0 && mode != 1) || (!ycol && ncol != m)) { set_error("%s: bad argument", who); return OEMGPU_ERR_ARG; }
+    const DenseSrc X = dtype < 0 ? dense_src_cm((const double *)x_dev, ld) : dense_src_rm(x_dev, dtype, ld);
+    int rc = multi_y_check(who, n, y_rs, y_cs, m);
+    if (!rc) rc = dense_src_check(who, X, n, p);
+    if (rc) return rc;
+    if (ycol)
+        for (int t = 0; t < ncol; ++t)
+            if (ycol[t] < 0 || ycol[t] >= m) { set_error("%s: ycol must be in [0, m)", who); return OEMGPU_ERR_ARG; }
+    if (p > LMULTI_P_MAX) { set_error("%s: p > %d is not supported", who, LMULTI_P_MAX); return OEMGPU_ERR_UNSUPPORTED; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    return logistic_multi_rows_selftest(c, X, n, p, MultiY{y_dev, y_rs, y_cs}, ncol, btilde_dev, intercept, mode, live, out_dev, foldid_dev, leave, ycol);
 }
 
 int oemgpu_last_logistic_multi_stats(double *out)

@@ -56,11 +56,18 @@ struct LmRm {                                // row-major float64 / float32, row
 };
 
 // grid: (row chunks, response blocks)
-template <int TPW, int LT, class SRC>
+// MASKED (the fold instances of a cross-validation): column t of the pass is response F.ycol[t] of Y (t itself without
+// F.ycol) on the rows with F.foldid[row] != F.leave[t].  The mask is one more term of step L's selection -- a left-out row takes r = 0
+// and adds nothing to the sums of r and of the loss -- and the two products are what they were: such a row adds x . 0 to the X'r chain,
+// which is why a column with leave = 0, or with an id no row carries, has the bytes of the unmasked pass, and why a column's bytes do
+// not depend on its companions' leave.  The columns of a block share their A operand: a row that one column leaves out is still loaded
+// for the others, so x must be finite on every row of the call (a NaN in a left-out row reaches X'r as NaN . 0).  The unmasked
+// instantiations are the code they were before MASKED existed.
+template <int TPW, int LT, class SRC, bool MASKED>
 __global__ __launch_bounds__(64 * LMULTI_NW) void logit_multi_rows_kernel(const SRC X, const double *__restrict__ y, int64_t rs, int64_t cs, int64_t n,
                                                                           int p, int m, const double *__restrict__ bt, int intercept, int mode,
                                                                           const int *__restrict__ live, int64_t rows, int npass,
-                                                                          double *__restrict__ part)
+                                                                          double *__restrict__ part, const LogitMultiFold F)
 {
     constexpr int RT = TPW == 16 ? 2 : 4 / LT, MB = 16 * LT, SB = 16 * RT;     // SB MB <= 1024; 32 rows at TPW = 16, whose Bt and X'r fill the registers
     __shared__ double lds[5 * 1024];
@@ -103,11 +110,13 @@ __global__ __launch_bounds__(64 * LMULTI_NW) void logit_multi_rows_kernel(const 
     double b0[LT], rsum[LT], lsum[LT];
     int64_t yoff[LT];
     bool yok[LT];
+    int lv[LT];                                                               // MASKED: the fold this column leaves out
 #pragma unroll
     for (int t = 0; t < LT; ++t) {
         const int r = rbase + 16 * t + ll, rc = r < m ? r : m - 1;
         yok[t] = r < m;
-        yoff[t] = (int64_t)rc * cs;
+        yoff[t] = (int64_t)((MASKED && F.ycol) ? F.ycol[rc] : rc) * cs;
+        lv[t] = MASKED ? F.leave[rc] : 0;
         b0[t] = (mode && intercept) ? bt[(size_t)rc * q] : 0.0;
         rsum[t] = 0.0; lsum[t] = 0.0;
     }
@@ -181,6 +190,7 @@ __global__ __launch_bounds__(64 * LMULTI_NW) void logit_multi_rows_kernel(const 
             const int64_t row = sb0 + rl;
             const bool ok = row < r_end;
             const int64_t rc = ok ? row : r_last;
+            const int fid = MASKED ? F.foldid[rc] : 0;
 #pragma unroll
             for (int t = 0; t < LT; ++t) {
                 const double yi = y[rc * rs + yoff[t]];
@@ -193,7 +203,7 @@ __global__ __launch_bounds__(64 * LMULTI_NW) void logit_multi_rows_kernel(const 
                     if (yi == 1.0) lt = prob > 1e-5 ? log(1.0 / prob) : log(1.0 / 1e-5);
                     else lt = prob <= 1.0 - 1e-5 ? log(1.0 / (1.0 - prob)) : log(1.0 / 1e-5);
                 }
-                const bool use = ok && yok[t];
+                const bool use = MASKED ? (ok && yok[t] && fid != lv[t]) : (ok && yok[t]);
                 r = use ? r : 0.0;
                 rsum[t] += r;
                 lsum[t] += use ? lt : 0.0;
@@ -275,25 +285,31 @@ __global__ __launch_bounds__(256) void logit_multi_reduce_kernel(const double *_
 
 template <int TPW, int LT, class SRC>
 int rows_launch(hipStream_t s, const LogitMultiPlan &pl, const SRC &X, const MultiY &Y, const double *bt, int intercept, int mode, const int *live,
-                double *part)
+                double *part, const LogitMultiFold *fold)
 {
-    hipLaunchKernelGGL((logit_multi_rows_kernel<TPW, LT, SRC>), dim3((unsigned)pl.nchunk, (unsigned)pl.npass), dim3(64 * LMULTI_NW), 0, s, X, Y.y, Y.rs,
-                       Y.cs, pl.n, pl.p, pl.mc, bt, intercept, mode, live, pl.rows, pl.npass, part);
+    const dim3 grid((unsigned)pl.nchunk, (unsigned)pl.npass), wg(64 * LMULTI_NW);
+    if (fold)
+        hipLaunchKernelGGL((logit_multi_rows_kernel<TPW, LT, SRC, true>), grid, wg, 0, s, X, Y.y, Y.rs, Y.cs, pl.n, pl.p, pl.mc, bt, intercept, mode, live,
+                           pl.rows, pl.npass, part, *fold);
+    else
+        hipLaunchKernelGGL((logit_multi_rows_kernel<TPW, LT, SRC, false>), grid, wg, 0, s, X, Y.y, Y.rs, Y.cs, pl.n, pl.p, pl.mc, bt, intercept, mode, live,
+                           pl.rows, pl.npass, part, LogitMultiFold{});
     OEM_HIP(hipGetLastError());
     return 0;
 }
 
 template <class SRC>
-int rows_src(hipStream_t s, const LogitMultiPlan &pl, const SRC &X, const MultiY &Y, const double *bt, int intercept, int mode, const int *live, double *part)
+int rows_src(hipStream_t s, const LogitMultiPlan &pl, const SRC &X, const MultiY &Y, const double *bt, int intercept, int mode, const int *live, double *part,
+             const LogitMultiFold *fold)
 {
     switch (pl.tpw * 8 + pl.lt) {
-    case 2 * 8 + 1: return rows_launch<2, 1>(s, pl, X, Y, bt, intercept, mode, live, part);
-    case 2 * 8 + 4: return rows_launch<2, 4>(s, pl, X, Y, bt, intercept, mode, live, part);
-    case 4 * 8 + 1: return rows_launch<4, 1>(s, pl, X, Y, bt, intercept, mode, live, part);
-    case 4 * 8 + 4: return rows_launch<4, 4>(s, pl, X, Y, bt, intercept, mode, live, part);
-    case 8 * 8 + 1: return rows_launch<8, 1>(s, pl, X, Y, bt, intercept, mode, live, part);
-    case 8 * 8 + 2: return rows_launch<8, 2>(s, pl, X, Y, bt, intercept, mode, live, part);
-    case 16 * 8 + 1: return rows_launch<16, 1>(s, pl, X, Y, bt, intercept, mode, live, part);
+    case 2 * 8 + 1: return rows_launch<2, 1>(s, pl, X, Y, bt, intercept, mode, live, part, fold);
+    case 2 * 8 + 4: return rows_launch<2, 4>(s, pl, X, Y, bt, intercept, mode, live, part, fold);
+    case 4 * 8 + 1: return rows_launch<4, 1>(s, pl, X, Y, bt, intercept, mode, live, part, fold);
+    case 4 * 8 + 4: return rows_launch<4, 4>(s, pl, X, Y, bt, intercept, mode, live, part, fold);
+    case 8 * 8 + 1: return rows_launch<8, 1>(s, pl, X, Y, bt, intercept, mode, live, part, fold);
+    case 8 * 8 + 2: return rows_launch<8, 2>(s, pl, X, Y, bt, intercept, mode, live, part, fold);
+    case 16 * 8 + 1: return rows_launch<16, 1>(s, pl, X, Y, bt, intercept, mode, live, part, fold);
     default: set_error("internal: logistic multi plan with %d column tiles per wave and %d response tiles", pl.tpw, pl.lt); return OEMGPU_ERR_INTERNAL;
     }
 }
@@ -321,12 +337,12 @@ LogitMultiPlan logit_multi_plan(int64_t n, int p, int mc, int num_cu)
 }
 
 int launch_logit_multi_rows(hipStream_t s, const LogitMultiPlan &pl, const DenseSrc &X, const MultiY &Y, const double *bt, int intercept, int mode,
-                            const int *live, double *part)
+                            const int *live, double *part, const LogitMultiFold *fold)
 {
     if (pl.nchunk > 0x7fffffffLL || pl.npass > 65535) { set_error("logistic_multi: the row pass has more workgroups than a launch takes"); return OEMGPU_ERR_UNSUPPORTED; }
-    if (X.colmajor()) return rows_src(s, pl, LmCm{X.cm(), X.ld}, Y, bt, intercept, mode, live, part);
-    if (X.dtype == OEMGPU_F32) return rows_src(s, pl, LmRm<float>{(const float *)X.x, X.ld}, Y, bt, intercept, mode, live, part);
-    return rows_src(s, pl, LmRm<double>{(const double *)X.x, X.ld}, Y, bt, intercept, mode, live, part);
+    if (X.colmajor()) return rows_src(s, pl, LmCm{X.cm(), X.ld}, Y, bt, intercept, mode, live, part, fold);
+    if (X.dtype == OEMGPU_F32) return rows_src(s, pl, LmRm<float>{(const float *)X.x, X.ld}, Y, bt, intercept, mode, live, part, fold);
+    return rows_src(s, pl, LmRm<double>{(const double *)X.x, X.ld}, Y, bt, intercept, mode, live, part, fold);
 }
 
 int launch_logit_multi_reduce(hipStream_t s, const LogitMultiPlan &pl, const double *part, const int *live, double *g)

@@ -21,11 +21,19 @@ struct LogitMultiPlan {
 };
 LogitMultiPlan logit_multi_plan(int64_t n, int p, int mc, int num_cu);
 
-// One row pass for the mc responses Y(., 0 .. mc) (Y.y points at the chunk's first response).  bt: mc x q, response r's q = p +
+// The fold mask of a row pass: column t is response ycol[t] of Y (t itself when ycol is null) on the rows with
+// foldid[row] != leave[t].  foldid: n device words; leave, ycol: mc device words.  A leave no row carries (0 among ids in [1, K]) keeps
+// every row: the bytes of the unmasked pass.  The columns of a block share the rows they load: x must be finite on every row.
+struct LogitMultiFold {
+    const int32_t *foldid = nullptr;
+    const int *leave = nullptr, *ycol = nullptr;
+};
+
+// One row pass for the mc responses Y(., 0 .. mc) (Y.y points at the chunk's first response; with fold->ycol at the columns' base).  bt: mc x q, response r's q = p +
 // intercept entries of beta o s contiguous, the intercept's first (mode 1; not read in mode 0: r = y).  live: mc device words; a block
 // whose responses are all frozen returns at once.  Every other workgroup writes its whole panel.
 int launch_logit_multi_rows(hipStream_t s, const LogitMultiPlan &pl, const DenseSrc &X, const MultiY &Y, const double *bt, int intercept, int mode,
-                            const int *live, double *part);
+                            const int *live, double *part, const LogitMultiFold *fold = nullptr);
 // g[r] (p + 2 doubles: [sum r, X'r, sum loss]) <- the panels added in chunk order, for the live responses only
 int launch_logit_multi_reduce(hipStream_t s, const LogitMultiPlan &pl, const double *part, const int *live, double *g);
 
