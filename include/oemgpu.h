@@ -525,6 +525,95 @@ int oemgpu_selftest_xval_multi_fold_moments_dev(oemgpu_ctx *ctx, const void *x_d
                                                 const double *y_dev, int64_t y_rs, int64_t y_cs, int32_t m,
                                                 const int32_t *foldid_dev, int32_t nfolds, double *moments_out_dev);
 
+/* cv.oem, family = "gaussian", for m responses on ONE dense x: it replaces the loop of m (oemgpu_fit_dense_dev, oemgpu_cv_fold_fits_dev,
+ * oemgpu_cv_score_dev) triples with the same foldid -- cv.oem's K + 1 calls of oem() per response (R/cv_oem.R:105, 129-175), the
+ * prediction loop and the per-fold means of cv.oemfit_gaussian (R/cv_oem.R:349-423) and predict.oem's lambda.interp (R/utils.R:64-144).
+ * Here: the fold layout, the gathers of x and Y, the K fold Gram passes and the ONE fold X'Y pass of oemgpu_xval_dense_multi_dev, once;
+ * then, per chunk of nb responses: their nb (K + 1) sums "all folds" / "all but fold ff" in one launch, the nb (K + 1) paths in one
+ * batched launch of at most 513 instances under oem()'s own semantics -- every instance its own standardisation, y scale and lambda
+ * grid from its own kept rows (instance r (K + 1) + ff) -- the index table of lambda.interp on the host (O(nb K npen nl) scalars:
+ * (left, right, frac) of every fold grid at the valid leading lambdas of the full fit's, ncol = the count of full-grid lambdas >= the
+ * largest of the folds' smallest), the interpolation beta[left] frac + beta[right] (1 - frac) on the device (rows from ncol on zero),
+ * and the held-out rows of the nb responses scored in one launch and one finish launch.  A user lambda grid and foldid are shared by
+ * all responses; there are no observation weights.  The sums are taken in a fixed order: two calls return the same bytes, and so do
+ * the three layouts of x.
+ * Outputs (host): beta[m][npen][nl][p + 1], lambda_out / niter / loss [m][npen][nl], d[m]: the m full fits as
+ * oemgpu_fit_dense_multi_dev lays them out; ncol[m][npen]; triples[m][nfolds][npen][nl][3] = (count, mean, M2) of every fold's
+ * errors, (0, NaN, NaN) in columns >= ncol and for a fold without rows, as oemgpu_cv_score_dev writes them; fold_n[nfolds]; route[m]:
+ * 0 the response's K + 1 fits ran in a batched launch, 1 no batch engine takes the shape (p > 1024, the cooperating engine switched
+ * off, or a launch too small for K + 1 instances) and its K + 1 sums were solved one after another, 2 one of its K + 1 solves advised
+ * the shifted moment pass (a column or y with mean^2 > 256 var): nothing else is returned for that response (its ncol are 0) and the
+ * caller runs the single route with its own shift rule on it (oemgpu_fit_dense_dev, oemgpu_cv_fold_fits_dev, oemgpu_cv_score_dev).
+ * Optional (NULL, or host): fold_beta[m][nfolds][npen][nl][p + 1], fold_lambda / fold_niter [m][nfolds][npen][nl], the fold fits
+ * themselves; predmat[m][npen][nl][n], yhat of every row from the fit that left its fold out, in the caller's row order, NaN from ncol
+ * on (with it every chunk holds nb npen nl n doubles more on the device).
+ * Refused before a device is looked for: what oemgpu_xval_dense_multi_dev refuses of these arguments, with its codes -- a NULL
+ * pointer, nfolds outside 2..512, a type_measure outside {0, 1}, m < 1, a stride pair of y that is neither form, bad options
+ * (OEMGPU_ERR_ARG) -- and OEMGPU_ERR_UNSUPPORTED for n <= p, for n - ceil(n / nfolds) <= p and for OEMGPU_OLS among the penalties (a
+ * grid of one lambda: cv.oem's rule for it is served fold by fold, oemgpu_fit_dense_dev); from the device: OEMGPU_ERR_ARG for a
+ * fold id outside 1..nfolds, OEMGPU_ERR_UNSUPPORTED naming the fold that leaves n - fold <= p rows.  A fold id in 1..nfolds that never
+ * occurs is allowed, as in oemgpu_cv_fold_fits_dev: that fold's fit is the fit of all rows and its triples are (0, NaN, NaN).
+ * opts.interrupt is polled between the chunks (OEMGPU_ERR_INTERRUPTED). */
+int oemgpu_cv_dense_multi_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p,
+                              const double *y_dev, int64_t y_rs, int64_t y_cs, int32_t m,
+                              const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept,
+                              int32_t type_measure, const oemgpu_opts *o,
+                              double *beta, double *lambda_out, int32_t *niter, double *loss, double *d,
+                              int32_t *ncol, double *triples, int64_t *fold_n, int32_t *route,
+                              double *fold_beta, double *fold_lambda, int32_t *fold_niter, double *predmat);
+/* The same on a row-major x read where it lies (the x arguments of oemgpu_xval_dense_multi_rm_dev; R/cv_oem.R:129-175, 349-423): the
+ * same bytes, the same refusals and codes, and those of the row-major entries on dtype, ldr and alignment. */
+int oemgpu_cv_dense_multi_rm_dev(oemgpu_ctx *ctx, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p,
+                                 const double *y_dev, int64_t y_rs, int64_t y_cs, int32_t m,
+                                 const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept,
+                                 int32_t type_measure, const oemgpu_opts *o,
+                                 double *beta, double *lambda_out, int32_t *niter, double *loss, double *d,
+                                 int32_t *ncol, double *triples, int64_t *fold_n, int32_t *route,
+                                 double *fold_beta, double *fold_lambda, int32_t *fold_niter, double *predmat);
+/* HIP-event times (ms) of the last such call on this thread, taken while oemgpu_set_timing is on (the clock waits for the end of every
+ * phase; a phase that runs once per chunk of responses is added up): [0] fold order and the gathers of x and Y, [1] the fold Gram
+ * passes, [2] the fold X'Y pass, [3] the composition of the sums, [4] the paths (R/cv_oem.R:129-175), [5] the interpolation
+ * (R/utils.R:64-144; its uploads included), [6] the scoring (R/cv_oem.R:349-423; its downloads included).  All 0 with timing off.
+ * OEMGPU_ERR_ARG for a NULL ms. */
+#define OEMGPU_CVM_NPHASES 7
+int oemgpu_last_cv_multi_timings(double *ms /* OEMGPU_CVM_NPHASES */);
+/* Host-only plan of the two calls (pure arithmetic, runs without a GPU; the calls take their shape from the same function: how
+ * R/cv_oem.R:129-175's K + 1 fits per response are grouped into launches and what R/cv_oem.R:349-423's tables take on the device) for n rows,
+ * p columns, nfolds folds, m responses, npen element-wise penalties of nl lambdas on a device of num_cu CUs, with (keep != 0) or without
+ * predmat, at most nb_limit responses per chunk (0: no limit of the caller's): out[0..19] the fields of oemgpu_selftest_xval_multi_plan
+ * in its order, with the solve plan read at q = p (oem()'s solve centres the intercept out: [0] nb, [1] chunks, [2] engine, [3] route,
+ * [8] the CV-error workgroups and [19] the cap are this call's; [4..7] and [9..13] are those of xval_oem_multi), [18] the aux bytes up to
+ * there; [20..25] bytes of: one chunk's raw fold tables (= [15]), its index table (nb nfolds npen nl 16), its ncol (nb npen 4), the
+ * inverse fold map (4 per fold-ordered row), its prediction block (nb npen nl n 8 with keep, else 0), its per-fold triples (nb nfolds
+ * npen nl 24); [26] the aux bytes of the call: [18] plus [20..25] each rounded up to 256.
+ * OEMGPU_ERR_ARG for non-positive arguments, a negative nb_limit, nfolds outside 2..512 or a NULL out; OEMGPU_ERR_UNSUPPORTED for n <= p. */
+#define OEMGPU_CVM_PLAN_LEN 27
+int oemgpu_selftest_cv_multi_plan(int64_t n, int32_t p, int32_t nfolds, int32_t m, int32_t npen, int32_t nl, int32_t num_cu, int32_t keep,
+                                  int32_t nb_limit, int64_t *out /* OEMGPU_CVM_PLAN_LEN */);
+/* Test infrastructure, host-only: from now on this thread's oemgpu_cv_dense_multi_dev / _rm_dev calls take at most nb_limit responses
+ * per chunk (0: no limit again), as if the device's free memory had asked for it -- the path that brings triples and predmat down in
+ * several copies (R/cv_oem.R:376-391: the prediction matrix).  OEMGPU_ERR_ARG for a negative nb_limit. */
+int oemgpu_selftest_cv_multi_nb_limit(int32_t nb_limit);
+/* Host-only (runs without a GPU): the index table of the call above from grids of the caller's -- lam_full[npen][nl] one full fit's
+ * lambdas, lam_fold[nfolds][npen][nl] its fold fits' (descending) -> left / right / frac [nfolds][npen][nl] and ncol[npen]:
+ * lambda.interp (R/utils.R:64-87) of every fold grid at the ncol leading lambdas of the full grid, (0, 0, 1) from ncol on.
+ * OEMGPU_ERR_ARG for a NULL pointer or a non-positive count. */
+int oemgpu_selftest_cv_interp(int32_t nfolds, int32_t npen, int32_t nl, const double *lam_full, const double *lam_fold,
+                              int32_t *left, int32_t *right, double *frac, int32_t *ncol);
+/* Test infrastructure, the many-response form of oemgpu_selftest_cv_score_dev (R/cv_oem.R:376-391): the fold layout, the gathers of x
+ * (column-major) and Y, then the interpolation and the scoring of the call above alone, nb responses per launch, on tables of the
+ * caller's; nothing is fitted, so a fold may leave fewer rows than columns.  coef[m][nfolds][npen][nl][p + 1] (host), ncol[m][npen]
+ * (host).  left / right / frac ([m][nfolds][npen][nl], host) all NULL: coef is scored as it is; else coef goes through the
+ * interpolation kernel first and table_out (NULL or host, coef's shape) <- what it wrote.  triples[m][nfolds][npen][nl][3] (host);
+ * predmat_dev NULL or DEVICE [m][npen][nl][n].  OEMGPU_ERR_ARG for a NULL pointer, p / npen / nl / nb < 1, nfolds outside 2..512, a
+ * type_measure outside {0, 1}, m < 1 or a bad stride pair of y, an ncol outside 0..nl, an index outside 0..nl-1, and, from the device,
+ * a fold id outside 1..nfolds. */
+int oemgpu_selftest_cv_score_multi_dev(oemgpu_ctx *ctx, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev,
+                                       int64_t y_rs, int64_t y_cs, int32_t m, const int32_t *foldid_dev, int32_t nfolds,
+                                       const double *coef, int32_t npen, int32_t nl, const int32_t *ncol, int32_t type_measure, int32_t nb,
+                                       const int32_t *left, const int32_t *right, const double *frac, double *table_out,
+                                       double *triples, double *predmat_dev);
+
 /* The eigenvalue step of the most recent solve (or oemgpu_eig_max_dev) on this context: *steps = Lanczos steps taken, *capped = 1
  * if the recurrence ran into its step cap (min(2 q, 288) for q <= 288, 256 / 512 on the larger engines) instead of stopping by its
  * rule or by breakdown -- d = 1.005 x the last Ritz value is then a lower estimate (the reference's Spectra call, tol 1e-10 and up

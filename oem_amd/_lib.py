@@ -138,6 +138,21 @@ _SIGS = {
     "oemgpu_selftest_xval_multi_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "oemgpu_selftest_xval_multi_fold_moments_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
                                                               C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    # cv.oem for many Gaussian responses on one x: the loop of m cv_oem calls with one foldid
+    "oemgpu_cv_dense_multi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                            C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(OemgpuOpts)] + _OUT +
+                                  [_ip, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp, _ip, _dp]),
+    "oemgpu_cv_dense_multi_rm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+                                               C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(OemgpuOpts)] + _OUT +
+                                     [_ip, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp, _ip, _dp]),
+    "oemgpu_last_cv_multi_timings": (C.c_int, [_dp]),
+    "oemgpu_selftest_cv_multi_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                C.POINTER(C.c_int64)]),
+    "oemgpu_selftest_cv_multi_nb_limit": (C.c_int, [C.c_int32]),
+    "oemgpu_selftest_cv_interp": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _ip, _ip, _dp, _ip]),
+    "oemgpu_selftest_cv_score_multi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                                     C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, _ip, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp,
+                                                     C.c_void_p]),
     # many binomial responses on one x: the loop of m oemgpu_fit_logistic_dense_dev / _rm_dev calls
     "oemgpu_fit_logistic_dense_multi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
                                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(OemgpuOpts)] + _OUT),

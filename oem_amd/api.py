@@ -2530,6 +2530,262 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
     return res
 
 
+def _cv_weighted_stats_many(cvraw, w, N):
+    """_cv_weighted_stats for many tables at once, no loop over the columns: cvraw[..., K, nl] (NaN = no entry), w[K], N broadcast
+    against [..., nl] -> (cvm, cvsd)[..., nl], the same values (a column without an entry: NaN)."""
+    cvraw = np.asarray(cvraw, dtype=np.float64)
+    wt = np.asarray(w, dtype=np.float64)[:, None]
+
+    def wmean(a):
+        ok = ~np.isnan(a)
+        den = np.where(ok, wt, 0.0).sum(axis=-2)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(den > 0, np.where(ok, a * wt, 0.0).sum(axis=-2) / den, np.nan)
+    cvm = wmean(cvraw)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cvsd = np.sqrt(wmean((cvraw - cvm[..., None, :]) ** 2) / (np.asarray(N, dtype=np.float64) - 1))
+    return cvm, cvsd
+
+
+def _cv_gaussian_triple_stats_many(fold_n, triples, ncol_last, grouped):
+    """_cv_gaussian_triple_stats for R responses at once: triples[R, K, npen, nl, 3], ncol_last[R] (the valid columns of every response's
+    LAST model: the nlams rule of R/cv_oem.R:386-389) -> (cvm, cvsd)[R, npen, nl], the same values.  Not grouped: oemgpu_xval_merge's
+    sequential Chan update over the folds, one numpy step per fold."""
+    triples = np.asarray(triples, dtype=np.float64)
+    R, K, nmodels, nl = triples.shape[:4]
+    if grouped:
+        N = np.where(np.arange(nl)[None, :] < np.asarray(ncol_last).reshape(R, 1), float(K), 0.0)       # good.sum(axis=0)
+        return _cv_weighted_stats_many(triples[..., 1].transpose(0, 2, 1, 3), np.asarray(fold_n, dtype=np.float64), N[:, None, :])
+    na, ma, qa = (np.zeros((R, nmodels, nl)) for _ in range(3))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for s in range(K):
+            nb, mb, qb = triples[:, s, :, :, 0], triples[:, s, :, :, 1], triples[:, s, :, :, 2]
+            some, first = nb > 0.0, na <= 0.0
+            nn, dl = na + nb, mb - ma
+            m2 = ma + dl * (nb / nn)
+            q2 = qa + (qb + dl * dl * (na * nb / nn))
+            ma = np.where(some, np.where(first, mb, m2), ma)
+            qa = np.where(some, np.where(first, qb, q2), qa)
+            na = np.where(some, np.where(first, nb, nn), na)
+        cvm = ma.copy()
+        cvsd = np.where(na > 1.0, np.sqrt(np.maximum(qa, 0.0) / (na - 1.0)) / np.sqrt(na), 0.0)
+    none = triples[..., 0].sum(axis=1) == 0
+    cvm[none] = np.nan; cvsd[none] = np.nan
+    return cvm, cvsd
+
+
+def cv_multi_plan(n, p, nfolds, m, npen=1, nl=100, num_cu=256, keep=False, nb_limit=0):
+    """oemgpu_selftest_cv_multi_plan (pure host arithmetic) as a dict: xval_multi_plan's keys (the solve plan read at q = p) and the
+    regions cv_oem_multi adds"""
+    out = (C.c_int64 * 27)()
+    L.check(L.lib().oemgpu_selftest_cv_multi_plan(int(n), int(p), int(nfolds), int(m), int(npen), int(nl), int(num_cu), int(bool(keep)), int(nb_limit), out))
+    keys = ["nb", "solve_chunks", "engine", "route", "rows", "chunks_max", "passes", "block", "cv_nwg", "bytes_single", "bytes_col", "bytes_yp",
+            "bytes_cfirst", "bytes_part", "bytes_comp", "bytes_tab", "bytes_cvpart", "bytes_cvout", "bytes_xval", "cap", "bytes_raw", "bytes_idx",
+            "bytes_ncol", "bytes_inv", "bytes_pred", "bytes_tri", "bytes"]
+    return dict(zip(keys, [int(v) for v in out]))
+
+
+def cv_multi_nb_limit(nb_limit):
+    """Test infrastructure: oemgpu_selftest_cv_multi_nb_limit -- this thread's cv_oem_multi calls take at most nb_limit responses per
+    chunk from now on (0: no limit)"""
+    L.check(L.lib().oemgpu_selftest_cv_multi_nb_limit(int(nb_limit)))
+
+
+def cv_multi_timings():
+    """oemgpu_last_cv_multi_timings of this thread (ms; taken while oemgpu_set_timing is on) as a dict"""
+    out = (C.c_double * 7)()
+    L.check(L.lib().oemgpu_last_cv_multi_timings(out))
+    return dict(zip(["fold_order", "fold_gram", "fold_xty", "compose", "paths", "interp", "score"], list(out)))
+
+
+def cv_multi_interp_table(lam_full, lam_fold):
+    """oemgpu_selftest_cv_interp (needs no GPU): lam_full[npen, nl], lam_fold[K, npen, nl] -> (left, right, frac)[K, npen, nl], ncol[npen]"""
+    lam_full = np.ascontiguousarray(lam_full, dtype=np.float64)
+    lam_fold = np.ascontiguousarray(lam_fold, dtype=np.float64)
+    K, npen, nl = lam_fold.shape
+    if lam_full.shape != (npen, nl):
+        raise ValueError("lam_full must be [npen, nl] and lam_fold [K, npen, nl]")
+    left, right = np.zeros((K, npen, nl), dtype=np.int32), np.zeros((K, npen, nl), dtype=np.int32)
+    frac, ncol = np.zeros((K, npen, nl)), np.zeros(npen, dtype=np.int32)
+    L.check(L.lib().oemgpu_selftest_cv_interp(K, npen, nl, _dptr(lam_full), _dptr(lam_fold), _iptr(left), _iptr(right), _dptr(frac), _iptr(ncol)))
+    return left, right, frac, ncol
+
+
+def cv_multi_score(x, Y, foldid, nfolds, coef, ncol, type_measure="mse", nb=1, interp=None, predmat=None, ctx=None):
+    """Test infrastructure: oemgpu_selftest_cv_score_multi_dev.  x: a column-major float64 device tensor; coef[m, K, npen, nl, p + 1] and
+    ncol[m, npen] on the host; interp = (left, right, frac)[m, K, npen, nl] sends coef through the interpolation kernel first; predmat:
+    None or a float64 device tensor of m npen nl n elements, written in place.  -> (triples[m, K, npen, nl, 3], the table the
+    interpolation wrote or None)"""
+    import torch
+    ptr, n, p, ld, keepalive = _device_matrix(x)
+    Yd, rs, cs = _device_responses(Y, x.device)
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    m, K, npen, nl = coef.shape[:4]
+    ncol = np.ascontiguousarray(ncol, dtype=np.int32)
+    if coef.shape != (Yd.shape[1], int(nfolds), npen, nl, p + 1) or ncol.shape != (m, npen):
+        raise ValueError("coef must be [m, nfolds, npen, nl, p + 1] and ncol [m, npen]")
+    fd = torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=x.device)
+    triples = np.zeros((m, K, npen, nl, 3))
+    table = None
+    lp = rp = fp = tp = None
+    if interp is not None:
+        left, right, frac = (np.ascontiguousarray(interp[0], dtype=np.int32), np.ascontiguousarray(interp[1], dtype=np.int32),
+                             np.ascontiguousarray(interp[2], dtype=np.float64))
+        if left.shape != (m, K, npen, nl) or right.shape != left.shape or frac.shape != left.shape:
+            raise ValueError("interp must be three arrays [m, nfolds, npen, nl]")
+        table = np.full(coef.shape, np.nan)
+        lp, rp, fp, tp = _iptr(left), _iptr(right), _dptr(frac), _dptr(table)
+    if predmat is not None and (predmat.dtype != torch.float64 or not predmat.is_contiguous() or predmat.numel() != m * npen * nl * n):
+        raise ValueError("predmat must be a contiguous float64 device tensor of m npen nl n elements")
+    ctx = context(x.device.index) if ctx is None else ctx
+    torch.cuda.current_stream(x.device).synchronize()
+    L.check(L.lib().oemgpu_selftest_cv_score_multi_dev(ctx, ptr, n, ld, p, Yd.data_ptr(), rs, cs, m, fd.data_ptr(), K, _dptr(coef), npen, nl,
+                                                       _iptr(ncol), int(type_measure == "mae"), int(nb), lp, rp, fp, tp, _dptr(triples),
+                                                       predmat.data_ptr() if predmat is not None else None))
+    return triples, table
+
+
+def _cv_multi_call(x, Y, fid, nfolds, a, standardize, intercept, type_measure, keep, fold_fits=False):
+    """oemgpu_cv_dense_multi_dev / _rm_dev -> a dict of the arrays it fills (include/oemgpu.h has their shapes)"""
+    import torch
+    n, p = x.shape
+    X = _DeviceX(x, _xval_rowmajor_in_place)
+    Yd, rs, cs = _device_responses(Y, x.device)
+    m, K, npen, nl = Yd.shape[1], int(nfolds), a.npen, a.nl
+    fd = torch.as_tensor(fid, device=x.device)
+    o = {"beta": np.zeros((m, npen, nl, p + 1)), "lambda": np.zeros((m, npen, nl)), "niter": np.zeros((m, npen, nl), dtype=np.int32),
+         "loss": np.zeros((m, npen, nl)), "d": np.zeros(m), "ncol": np.zeros((m, npen), dtype=np.int32), "triples": np.zeros((m, K, npen, nl, 3)),
+         "fold_n": np.zeros(K, dtype=np.int64), "route": np.zeros(m, dtype=np.int32)}
+    if fold_fits:
+        o.update({"fold_beta": np.zeros((m, K, npen, nl, p + 1)), "fold_lambda": np.zeros((m, K, npen, nl)),
+                  "fold_niter": np.zeros((m, K, npen, nl), dtype=np.int32)})
+    if keep:
+        o["predmat"] = np.zeros((m, npen, nl, n))
+    ctx = context(x.device.index)
+    torch.cuda.current_stream(x.device).synchronize()
+    X.call("cv_dense_multi", ctx, Yd.data_ptr(), rs, cs, m, fd.data_ptr(), K, int(standardize), int(intercept), int(type_measure == "mae"),
+           C.byref(a.c), _dptr(o["beta"]), _dptr(o["lambda"]), _iptr(o["niter"]), _dptr(o["loss"]), _dptr(o["d"]), _iptr(o["ncol"]),
+           _dptr(o["triples"]), o["fold_n"].ctypes.data_as(C.POINTER(C.c_int64)), _iptr(o["route"]),
+           _dptr(o["fold_beta"]) if fold_fits else None, _dptr(o["fold_lambda"]) if fold_fits else None,
+           _iptr(o["fold_niter"]) if fold_fits else None, _dptr(o["predmat"]) if keep else None)
+    return o
+
+
+def cv_oem_multi(x, Y, penalty=None, lambda_=None, type_measure=None, nfolds=10, foldid=None, grouped=True, keep=False, rng=None, **kw):
+    """cv.oem (family = "gaussian") for m responses on one resident x: [cv_oem(x, Y[:, r], foldid=foldid, ...) for r in range(m)] from
+    one fold layout, one gather of x, one set of fold Gram passes, one X'Y pass over the fold-ordered rows, the (K + 1) m fits -- every
+    one on its own standardisation and lambda grid, as oem() fits the kept rows -- in batched launches, the fold tables interpolated
+    onto every full fit's grid and the held-out rows scored on the device (include/oemgpu.h: oemgpu_cv_dense_multi_dev).
+    x: a dense torch device tensor, n x p with n > p >= 2, taken as xval_oem_multi takes it (column-major float64 and row-major float64
+    / float32 read in place).  Y: n x m, taken as oem_multi takes it.  foldid (values 1..nfolds; drawn once with `rng` when None) and a
+    user lambda_ are shared by all responses; **kw are oem()'s options, as cv_oem passes them.  Returns a list of m results with
+    cv_oem's keys (predict_cv, plot_cv and summary_cv take them) and one more, `route`: 0 the response's K + 1 fits ran in a batched
+    launch, 1 they were solved one after another inside the call, 2 one of them advised the shifted moment pass and the response went
+    through cv_oem() itself.  ValueErrors before any device work: a host or sparse x, weights, ngpus / devices, "ols", family =
+    "binomial", n <= p, a Y that is not n x m, len(lambda_) < 2, nfolds < 3, a fold that keeps no more rows than columns."""
+    who = "cv_oem_multi()"
+    host_or_sparse = (who + " takes a dense torch tensor on a GPU: a host or sparse x is cross-validated one response at a time with cv_oem()")
+    if isinstance(x, SparseX) or _is_scipy_sparse(x) or _is_torch_sparse(x):
+        raise ValueError(host_or_sparse)
+    family = kw.pop("family", "gaussian")
+    if family not in ("gaussian", "binomial"):
+        raise ValueError("'arg' should be one of 'gaussian', 'binomial'")
+    if family == "binomial":
+        raise ValueError(who + " serves family = \"gaussian\": binomial responses are cross-validated with cv_oem_logistic_multi()")
+    penalty = _match_penalty(penalty)
+    if type_measure is None:
+        type_measure = "default"
+    elif type_measure not in _TYPE_MEASURES:
+        raise ValueError("'arg' should be one of " + ", ".join("'%s'" % t for t in _TYPE_MEASURES))
+    if lambda_ is not None and len(lambda_) < 2:
+        raise ValueError("Need more than one value of lambda for cv.oem")
+    if len(kw.pop("weights", ())) > 0:
+        raise ValueError(who + ": no observation weights (cv_oem() has none for family = \"gaussian\" either; xval_oem(weights=) cross-validates a weighted response)")
+    if kw.get("ngpus") or kw.get("devices") is not None:
+        raise ValueError(who + ": the rows of a resident x are not split over devices (ngpus / devices); cv_oem() on a host x takes them")
+    if "ols" in penalty:
+        raise ValueError(who + ": the \"ols\" penalty is not served; cv_oem() takes it, one response at a time")
+    kw.pop("parallel", None)                                      # (cv_oem's resident route accepts and ignores it)
+    if getattr(Y, "ndim", None) != 2:
+        raise ValueError("Y must be a matrix of n rows and one column per response")
+    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("x must have at least two columns")
+    n, p = x.shape
+    m = int(Y.shape[1])
+    if m < 1:
+        raise ValueError("Y must have at least one column")
+    if Y.shape[0] != n:
+        raise ValueError("x and y lengths do not match")
+    if n <= p:
+        raise ValueError(who + " serves n > p only: with n <= p cross-validate each column with cv_oem(x, Y[:, r])")
+    if p < 2:
+        raise ValueError("x must have at least two columns")
+    if foldid is None:
+        g = np.random.default_rng() if rng is None else rng
+        foldid = g.permutation(np.resize(np.arange(1, int(nfolds) + 1), n))
+    else:
+        foldid = np.asarray(foldid).ravel()
+        nfolds = int(foldid.max())
+    if nfolds < 3:
+        raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
+    if len(foldid) != n or not np.issubdtype(foldid.dtype, np.integer) or foldid.min() < 1 or nfolds > 512:
+        raise ValueError("foldid must hold one integer in 1..nfolds per row of x, nfolds at most 512")
+    kept = n - np.bincount(foldid, minlength=nfolds + 1)[1:]
+    if np.any(kept <= p):
+        i = int(np.argmax(kept <= p))
+        raise ValueError(f"{who}: fold {i + 1} leaves {int(kept[i])} rows for {p} columns; cv_oem() sends such folds to its host loop, "
+                         "one response at a time")
+    if not _is_torch_cuda(x):
+        raise ValueError(host_or_sparse)
+    lam_arg = () if lambda_ is None else lambda_
+    a, varnames, standardize, intercept = oem(x, Y, penalty=penalty, lambda_=lam_arg, _args_only=True, **kw)
+    if type_measure in ("default", "deviance"):
+        type_measure = "mse"
+    if type_measure not in ("mse", "mae"):
+        warnings.warn("Only 'mse', 'deviance' or 'mae'  available for Gaussian models; 'mse' used")
+        type_measure = "mse"
+    fid = np.ascontiguousarray(foldid, dtype=np.int32)
+    o = _cv_multi_call(x, Y, fid, nfolds, a, standardize, intercept, type_measure, keep)
+    if n / nfolds < 3 and grouped:
+        warnings.warn("Option grouped=FALSE enforced in cv.glmnet, since < 3 observations per fold")
+        grouped = False
+    nmodels, nl = len(penalty), a.nl
+    own = np.flatnonzero(o["route"] != 2)
+    if len(own):
+        cvm_all, cvsd_all = _cv_gaussian_triple_stats_many(o["fold_n"], o["triples"][own], o["ncol"][own, -1], grouped)
+    out = [None] * m
+    for i, r in enumerate(own):
+        fit0 = _decorate(_OneOfMany(o["beta"][r], o["lambda"][r], o["niter"][r], o["loss"][r], o["d"][r]), penalty, varnames, True, n, p)
+        nz = [np.array([0 if v is None else len(v) for v in predict(fit0, type="nonzero", which_model=k)]) for k in range(nmodels)]
+        lam = [np.asarray(l, dtype=np.float64) for l in fit0["lambda"]]
+        cvm, cvsd = list(cvm_all[i]), list(cvsd_all[i])
+        nas = np.zeros(nl, dtype=bool)
+        for k in range(nmodels):
+            nas |= np.isnan(cvsd[k])
+        if nas.any():
+            cvm = [c[~nas] for c in cvm]; cvsd = [c[~nas] for c in cvsd]
+            nz = [c[~nas] for c in nz]; lam = [l[~nas] for l in lam]
+        res = OemFit()
+        res.update({"lambda": lam, "cvm": cvm, "cvsd": cvsd, "cvup": [u + v for u, v in zip(cvm, cvsd)],
+                    "cvlo": [u - v for u, v in zip(cvm, cvsd)], "nzero": nz,
+                    "name": {"mse": "Mean-Squared Error", "mae": "Mean Absolute Error"}[type_measure], "oem.fit": fit0})
+        if keep:
+            res["fit.preval"] = [np.ascontiguousarray(pm.T) for pm in o["predmat"][r]]; res["foldid"] = foldid
+        res.update(_getmin(lam, cvm, cvsd))
+        res["best.model"] = penalty[res["model.min"] - 1]
+        res["penalty"] = list(penalty)
+        res["route"] = int(o["route"][r])
+        out[r] = res
+    for r in np.flatnonzero(o["route"] == 2):                        # the single route, with its own shift rule
+        with warnings.catch_warnings():
+            warnings.filterwarnings("ignore", message=".*grouped=FALSE enforced.*")           # (given once, above)
+            res = cv_oem(x, Y[:, int(r)], penalty=penalty, lambda_=lambda_, type_measure=type_measure, nfolds=nfolds, foldid=foldid,
+                         grouped=grouped, keep=keep, **kw)
+        res["route"] = 2
+        out[r] = res
+    return out
+
+
 def predict_cv(fit, newx=None, which_model="best.model", s="lambda.min", **kw):
     """predict.cv.oem, R/methods.R (same selection rules as predict.xval.oem, on the full-data fit `oem.fit`)."""
     if isinstance(s, str):

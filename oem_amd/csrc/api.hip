@@ -1834,10 +1834,13 @@ struct XvalMultiLay {
     size_t a_col = 0, a_yp = 0, a_cf = 0, a_part = 0, a_comp = 0, a_tab = 0, a_cvpart = 0, a_cvout = 0, total = 0;
 };
 // nb_limit > 0: no more responses per chunk than that (the device's free memory)
-static XvalMultiLay xval_multi_layout(int num_cu, int64_t n, int p, int K, int m, int intercept, const oemgpu_opts *o, int nb_limit)
+// dense_sem (cv_oem_multi): the solves are oem()'s (OEMGPU_SEM_DENSE: the intercept is centred out, q = p)
+// nb_exact > 0 (a call that solves nothing: the scoring self-test): that many responses per chunk, whatever the solve plan holds
+static XvalMultiLay xval_multi_layout(int num_cu, int64_t n, int p, int K, int m, int intercept, const oemgpu_opts *o, int nb_limit,
+                                      bool dense_sem = false, int nb_exact = 0)
 {
     XvalMultiLay V;
-    const int npen = o->npen, nl = nl_of(o), q = p + (intercept ? 1 : 0);
+    const int npen = o->npen, nl = nl_of(o), q = p + ((intercept && !dense_sem) ? 1 : 0);
     V.L = xval_layout(num_cu, n, p, K, npen, nl, false);
     V.xp = multi_plan(n, p, m, num_cu);
     V.sv = multi_solve_plan(num_cu, q, npen, any_grp_count(o));
@@ -1845,6 +1848,7 @@ static XvalMultiLay xval_multi_layout(int num_cu, int64_t n, int p, int K, int m
     // response's K + 1 instances fit a launch -- every response's sums then go through xval_solve_sums, as xval.oem's do
     V.route = (V.sv.engine != OEMGPU_ENGINE_NONE && V.sv.cap >= K + 1) ? 0 : 1;
     int nb = V.route == 0 ? V.sv.cap / (K + 1) : 1;
+    if (nb_exact > 0) nb = nb_exact;
     if (nb > m) nb = m;
     if (nb_limit > 0 && nb > nb_limit) nb = nb_limit;
     V.nb = nb; V.nsolve = (m + nb - 1) / nb;
@@ -1872,7 +1876,8 @@ struct XvmClock {
     oemgpu_ctx *c;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     bool on;
-    explicit XvmClock(oemgpu_ctx *c_) : c(c_), on(c_->timing)
+    double *ms;                                                   // the phase sums: xval_oem_multi's, or cv_oem_multi's (their first three phases are the same)
+    explicit XvmClock(oemgpu_ctx *c_, double *ms_ = g_xvm_ms) : c(c_), on(c_->timing), ms(ms_)
     {
         if (on && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) on = false;
     }
@@ -1883,7 +1888,7 @@ struct XvmClock {
         if (!on) return;
         float f = 0.f;
         (void)hipEventRecord(e1, c->stream);
-        if (hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&f, e0, e1) == hipSuccess) g_xvm_ms[phase] += f;
+        if (hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&f, e0, e1) == hipSuccess) ms[phase] += f;
     }
 };
 
@@ -2417,6 +2422,369 @@ int oemgpu_selftest_cv_score_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, 
     rc = cv_lay_out(c, V, dense_src_cm(x_dev, ld), y_dev, foldid_dev, false, hf);
     if (rc) return rc;
     return oemgpu_cv_score_dev(c, n, p, nfolds, coef, npen, nl, ncol, type_measure, triples, predmat_dev);
+}
+
+// ---------------------------------------------------------------------------------------------- cv.oem for many Gaussian responses on one x
+//   cv.oem's K + 1 calls of oem() per response (R/cv_oem.R:105, 129-175) and cv.oemfit_gaussian's prediction loop
+// (:349-423) for all m responses from xval_multi_passes' ONE fold layout, gather, K fold Gram passes and fold X'Y pass.  Per chunk of nb
+// responses: the nb (K + 1) composed sums, their paths in one batched launch under oem()'s own semantics (every instance its own
+// standardisation, y scale and lambda grid: OEMGPU_SEM_DENSE, no shared lmax), the index table of lambda.interp (R/utils.R:64-144) on the
+// host, the interpolation and the per-fold scoring on the device.  The buffers: XvalMultiLay's, then the regions below, in oemgpu_ctx::aux.
+struct CvMultiLay {
+    XvalMultiLay V;
+    size_t b_raw = 0, b_idx = 0, b_ncol = 0, b_inv = 0, b_pred = 0, b_tri = 0;                                       // bytes
+    size_t a_raw = 0, a_idx = 0, a_ncol = 0, a_inv = 0, a_pred = 0, a_tri = 0, total = 0;
+};
+static CvMultiLay cv_multi_layout(int num_cu, int64_t n, int p, int K, int m, const oemgpu_opts *o, int nb_limit, bool keep, int nb_exact = 0)
+{
+    CvMultiLay W;
+    W.V = xval_multi_layout(num_cu, n, p, K, m, 1, o, nb_limit, true, nb_exact);
+    const size_t nb = (size_t)W.V.nb, npen = (size_t)o->npen, nl = (size_t)nl_of(o);
+    W.b_raw = W.V.b_tab;                                                            // the chunk's fold tables as they were fitted
+    W.b_idx = nb * K * npen * nl * sizeof(CvInterpIdx);                             // the index table
+    W.b_ncol = nb * npen * sizeof(int);
+    W.b_inv = (size_t)W.V.L.ldp * sizeof(int);                                      // fold position -> caller's row
+    W.b_pred = keep ? nb * npen * nl * (size_t)n * 8 : 0;                           // one chunk's yhat, in the caller's row order
+    W.b_tri = nb * K * npen * nl * 3 * 8;                                           // its per-fold triples
+    Bump A;
+    A.off = W.V.total;
+    W.a_raw = A.take(W.b_raw); W.a_idx = A.take(W.b_idx); W.a_ncol = A.take(W.b_ncol); W.a_inv = A.take(W.b_inv);
+    W.a_pred = A.take(W.b_pred); W.a_tri = A.take(W.b_tri);
+    W.total = A.off;
+    return W;
+}
+
+static thread_local double g_cvm_ms[OEMGPU_CVM_NPHASES] = {0, 0, 0, 0, 0, 0, 0};
+// Test infrastructure (oemgpu_selftest_cv_multi_nb_limit): at most that many responses per chunk in this thread's calls, as if the
+// device's free memory had asked for it; 0: no limit
+static thread_local int g_cvm_nb_limit = 0;
+
+// np.interp(x, xp, 0..k-1) for an ascending xp: the operations of numpy's compiled loop, in its order
+static double cv_np_interp(double x, const double *xp, int k)
+{
+    if (x <= xp[0]) return 0.0;
+    if (x >= xp[k - 1]) return (double)(k - 1);
+    int lo = 0, hi = k - 1;                                          // xp[lo] <= x < xp[hi]
+    while (hi - lo > 1) { const int mid = (lo + hi) / 2; if (x >= xp[mid]) lo = mid; else hi = mid; }
+    if (xp[lo] == x) return (double)lo;
+    const double slope = 1.0 / (xp[lo + 1] - xp[lo]);
+    return slope * (x - xp[lo]) + (double)lo;
+}
+// lambda.interp (R/utils.R:64-87, glmnet's) of the k lambdas `lam` at the ns values s: api._lambda_interp's operations in its order
+static void cv_lambda_interp(const double *lam, int k, const double *s, int ns, CvInterpIdx *out, std::vector<double> &lamn)
+{
+    if (k == 1) { for (int j = 0; j < ns; ++j) out[j] = CvInterpIdx{0, 0, 1.0}; return; }
+    double lo = lam[0], hi = lam[0];
+    for (int i = 1; i < k; ++i) { if (lam[i] < lo) lo = lam[i]; if (lam[i] > hi) hi = lam[i]; }
+    const double span = lam[0] - lam[k - 1];
+    lamn.resize(k);
+    for (int i = 0; i < k; ++i) lamn[i] = (lam[0] - lam[i]) / span;
+    for (int j = 0; j < ns; ++j) {
+        double sj = s[j];
+        if (sj < lo) sj = lo;
+        if (sj > hi) sj = hi;
+        const double sfrac = (lam[0] - sj) / span;
+        const double coord = cv_np_interp(sfrac, lamn.data(), k);
+        int left = (int)std::floor(coord), right = (int)std::ceil(coord);
+        if (!(left >= 0)) left = 0;                                  // (a NaN grid: the indices stay inside the table, the values are NaN)
+        if (left > k - 1) left = k - 1;
+        if (!(right >= 0)) right = 0;
+        if (right > k - 1) right = k - 1;
+        out[j] = CvInterpIdx{left, right, left == right ? 1.0 : (sfrac - lamn[right]) / (lamn[left] - lamn[right])};
+    }
+}
+// One response: the index table idx[K][npen][nl] and ncol[npen] from the full fit's grid lam0[npen][nl] and the fold grids
+// lamf[K][npen][nl] -- ncol = the count of lam0 >= max over folds of the fold grid's minimum (R/cv_oem.R:364-375: no extrapolation)
+static void cv_interp_table(const oemgpu_opts *o, int K, const double *lam0, const double *lamf, CvInterpIdx *idx, int32_t *ncol)
+{
+    const int npen = o->npen, nl = nl_of(o);
+    std::vector<double> lamn;
+    for (int k = 0; k < npen; ++k) {
+        const int nlam = nl;                                         // ("ols", a grid of one, is refused by the entries)
+        double floor_ = 0.0;
+        for (int ff = 0; ff < K; ++ff) {
+            const double *g = lamf + ((size_t)ff * npen + k) * nl;
+            double mn = g[0];
+            for (int i = 1; i < nlam; ++i) if (g[i] < mn) mn = g[i];
+            if (ff == 0 || mn > floor_) floor_ = mn;
+        }
+        const double *s = lam0 + (size_t)k * nl;
+        int nc = 0;
+        while (nc < nlam && s[nc] >= floor_) ++nc;                   // (the grids descend: the valid columns lead)
+        ncol[k] = nc;
+        for (int ff = 0; ff < K; ++ff) {
+            CvInterpIdx *row = idx + ((size_t)ff * npen + k) * nl;
+            cv_lambda_interp(lamf + ((size_t)ff * npen + k) * nl, nlam, s, nc, row, lamn);
+            for (int j = nc; j < nl; ++j) row[j] = CvInterpIdx{0, 0, 1.0};
+        }
+    }
+}
+
+static int cv_dense_multi_src(const char *who, oemgpu_ctx *c, const DenseSrc &X, int64_t n, int32_t p, const double *y_dev, int64_t rs, int64_t cs,
+                              int32_t m, const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept, int32_t type_measure,
+                              const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int32_t *ncol,
+                              double *triples, int64_t *fold_n_out, int32_t *route, double *fold_beta, double *fold_lambda, int32_t *fold_niter,
+                              double *predmat)
+{
+    if (!c || !X.x || !y_dev || !foldid_dev || !beta || !lambda_out || !niter || !loss || !d || !ncol || !triples || !fold_n_out || !route) {
+        set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG;
+    }
+    const int K = nfolds;
+    int rc = dense_src_check(who, X, n, p);
+    if (!rc) rc = xval_check(c, X.x, y_dev, foldid_dev, n, n, p, K, 0, type_measure, false, o);       // (oem()'s semantics: q = p)
+    if (!rc) rc = multi_y_check(who, n, rs, cs, m);
+    if (rc) return rc;
+    // the largest fold holds at least ceil(n / K) rows: some fold fit is then not the Gram form whatever the ids are
+    if (n <= p || n - (n + K - 1) / K <= p) {
+        set_error("%s: %lld rows in %d folds leave some fit no more rows than the %d columns (the fit of p >= n is not this call's: "
+                  "oemgpu_fit_dense_dev fold by fold)", who, (long long)n, K, p);
+        return OEMGPU_ERR_UNSUPPORTED;
+    }
+    for (int k = 0; k < o->npen; ++k)
+        if (o->penalty[k] == OEMGPU_OLS) {
+            set_error("%s: the \"ols\" penalty is not served (its one-lambda grid is oemgpu_fit_dense_dev's, fold by fold)", who);
+            return OEMGPU_ERR_UNSUPPORTED;
+        }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    const bool keep = predmat != nullptr;
+    CvMultiLay W = cv_multi_layout(c->num_cu, n, p, K, m, o, g_cvm_nb_limit, keep);
+    {   // one chunk's sums, tables, predictions and partials grow with nb: fewer responses per chunk rather than an allocation that fails
+        size_t fre = 0, tot = 0;
+        if (hipMemGetInfo(&fre, &tot) == hipSuccess)
+            while (W.V.nb > 1 && W.total > fre + c->aux_bytes) W = cv_multi_layout(c->num_cu, n, p, K, m, o, W.V.nb / 2, keep);
+    }
+    if (ctx_aux(c, W.total)) return OEMGPU_ERR_HIP;
+    for (double &v : g_cvm_ms) v = 0.0;
+    XvmClock clk(c, g_cvm_ms);
+    const XvalMultiLay &V = W.V;
+    const XvalLay &L = V.L;
+    std::vector<int64_t> hf;
+    if ((rc = xval_multi_passes(c, V, X, MultiY{y_dev, rs, cs}, foldid_dev, m, hf, clk))) return rc;
+    for (int k = 0; k < K; ++k) {
+        fold_n_out[k] = hf[k];
+        if (n - hf[k] <= p) {
+            set_error("%s: fold %d leaves %lld rows for %d columns (the fit of p >= n is not this call's)", who, k + 1, (long long)(n - hf[k]), p);
+            return OEMGPU_ERR_UNSUPPORTED;
+        }
+    }
+    char *ax = c->aux;
+    const int npen = L.npen, nl = L.nl;
+    const size_t mlen = L.mlen, blen = (size_t)npen * nl * (p + 1), nk2 = (size_t)npen * nl;
+    const double *mfold = (const double *)(ax + L.a_mf), *part = (const double *)(ax + V.a_part), *Yp = (const double *)(ax + V.a_yp);
+    const int *cfirst = (const int *)(ax + V.a_cf);
+    const int64_t *fold_n = (const int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
+    double *comp = (double *)(ax + V.a_comp), *tab = (double *)(ax + V.a_tab), *cvpart = (double *)(ax + V.a_cvpart);
+    double *raw = (double *)(ax + W.a_raw), *pred = keep ? (double *)(ax + W.a_pred) : nullptr, *tri = (double *)(ax + W.a_tri);
+    CvInterpIdx *idx_dev = (CvInterpIdx *)(ax + W.a_idx);
+    int *ncol_dev = (int *)(ax + W.a_ncol), *inv = (int *)(ax + W.a_inv);
+    if (keep) if ((rc = launch_fold_inverse(c->stream, (const int *)(ax + L.a_pos), n, L.ldp, inv))) return rc;
+    auto interrupted = [&]() {
+        if (!(o->interrupt && o->interrupt(o->interrupt_arg))) return false;
+        set_error("interrupted by the caller");
+        return true;
+    };
+    std::vector<double> ab, al, aloss, ad, hb;
+    std::vector<int32_t> an, adv, hn;
+    std::vector<CvInterpIdx> hidx;
+    for (int r0 = 0; r0 < m; r0 += V.nb) {
+        const int nb = m - r0 < V.nb ? m - r0 : V.nb, ninst = nb * (K + 1);
+        if (r0 > 0 && interrupted()) return OEMGPU_ERR_INTERRUPTED;
+        clk.begin();
+        if ((rc = launch_multi_fold_compose(c->stream, V.xp, K, mfold, part, cfirst, r0, nb, false, comp))) return rc;
+        clk.end(3);
+        // ---- the paths: instance b (K + 1) + ff is response r0 + b on all folds (ff = 0) or on all but fold ff, each as oem() fits it
+        clk.begin();
+        ab.resize(blen * ninst); al.resize(nk2 * ninst); an.resize(nk2 * ninst); aloss.resize(nk2 * ninst); ad.resize(ninst); adv.assign(ninst, 0);
+        if (V.route == 0) {
+            rc = solve_moments_batch(c, comp, mlen, ninst, p, OEMGPU_SEM_DENSE, standardize, intercept, o, ab.data(), al.data(), an.data(), aloss.data(),
+                                     ad.data(), false, nullptr, 0, adv.data());
+            if (rc) return rc;
+        } else {
+            for (int i = 0; i < ninst; ++i) {
+                rc = solve_moments_impl(c, comp + mlen * i, nullptr, p, OEMGPU_SEM_DENSE, standardize, intercept, o, ab.data() + blen * i, al.data() + nk2 * i,
+                                        an.data() + nk2 * i, aloss.data() + nk2 * i, ad.data() + i, nullptr);
+                if (rc) return rc;
+                adv[i] = c->shift_advised ? 1 : 0;
+            }
+        }
+        clk.end(4);
+        // ---- the full fits out, the index tables of lambda.interp (host: O(nb K npen nl) scalars)
+        hb.resize(blen * K * nb); hidx.resize(nk2 * K * nb); hn.assign((size_t)npen * nb, 0);
+        for (int b = 0; b < nb; ++b) {
+            const size_t i0 = (size_t)b * (K + 1), r = (size_t)r0 + b;
+            bool shifted = false;
+            for (int ff = 0; ff <= K; ++ff) shifted = shifted || adv[i0 + ff] != 0;
+            memcpy(hb.data() + blen * K * b, ab.data() + blen * (i0 + 1), sizeof(double) * blen * K);
+            if (shifted) {                                           // oem()'s shifted pass is the single route's: reported, nothing scored
+                route[r] = 2;
+                for (size_t t = 0; t < nk2 * K; ++t) hidx[nk2 * K * b + t] = CvInterpIdx{0, 0, 1.0};
+                for (int k = 0; k < npen; ++k) ncol[(size_t)npen * r + k] = 0;
+                continue;
+            }
+            route[r] = V.route;
+            memcpy(beta + blen * r, ab.data() + blen * i0, sizeof(double) * blen);
+            memcpy(lambda_out + nk2 * r, al.data() + nk2 * i0, sizeof(double) * nk2);
+            memcpy(niter + nk2 * r, an.data() + nk2 * i0, sizeof(int32_t) * nk2);
+            memcpy(loss + nk2 * r, aloss.data() + nk2 * i0, sizeof(double) * nk2);
+            d[r] = ad[i0];
+            if (fold_beta) memcpy(fold_beta + blen * K * r, ab.data() + blen * (i0 + 1), sizeof(double) * blen * K);
+            if (fold_lambda) memcpy(fold_lambda + nk2 * K * r, al.data() + nk2 * (i0 + 1), sizeof(double) * nk2 * K);
+            if (fold_niter) memcpy(fold_niter + nk2 * K * r, an.data() + nk2 * (i0 + 1), sizeof(int32_t) * nk2 * K);
+            cv_interp_table(o, K, al.data() + nk2 * i0, al.data() + nk2 * (i0 + 1), hidx.data() + nk2 * K * b, hn.data() + (size_t)npen * b);
+            for (int k = 0; k < npen; ++k) ncol[(size_t)npen * r + k] = hn[(size_t)npen * b + k];
+        }
+        // ---- the interpolation on the device: raw fold tables, index table and ncol up, tab <- beta[left] frac + beta[right] (1 - frac)
+        clk.begin();
+        OEM_HIP(hipMemcpyAsync(raw, hb.data(), sizeof(double) * blen * K * nb, hipMemcpyHostToDevice, c->stream));
+        OEM_HIP(hipMemcpyAsync(idx_dev, hidx.data(), sizeof(CvInterpIdx) * nk2 * K * nb, hipMemcpyHostToDevice, c->stream));
+        OEM_HIP(hipMemcpyAsync(ncol_dev, hn.data(), sizeof(int) * (size_t)npen * nb, hipMemcpyHostToDevice, c->stream));
+        if ((rc = launch_cv_interp(c->stream, raw, idx_dev, ncol_dev, nb, K, npen, nl, p, tab))) return rc;
+        clk.end(5);
+        // ---- the held-out rows of the nb responses scored where they lie: per-fold (count, mean, M2), yhat with predmat
+        clk.begin();
+        rc = launch_cv_fold_error_many(c->stream, (const double *)(ax + L.a_xp), L.ldp, Yp + (size_t)L.ldp * r0, fold_start, fold_n, K, p, tab, npen, nl,
+                                       type_measure, V.cv, nb, cvpart, ncol_dev, tri, pred, inv, n);
+        if (rc) return rc;
+        OEM_HIP(hipMemcpyAsync(triples + 3 * nk2 * K * r0, tri, sizeof(double) * 3 * nk2 * K * nb, hipMemcpyDeviceToHost, c->stream));
+        if (keep) OEM_HIP(hipMemcpyAsync(predmat + nk2 * (size_t)n * r0, pred, sizeof(double) * nk2 * (size_t)n * nb, hipMemcpyDeviceToHost, c->stream));
+        OEM_HIP(hipStreamSynchronize(c->stream));                    // hb, hidx and hn are read by the copies above
+        clk.end(6);
+    }
+    return 0;
+}
+
+int oemgpu_cv_dense_multi_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev, int64_t y_rs, int64_t y_cs,
+                              int32_t m, const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept, int32_t type_measure,
+                              const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d, int32_t *ncol,
+                              double *triples, int64_t *fold_n, int32_t *route, double *fold_beta, double *fold_lambda, int32_t *fold_niter,
+                              double *predmat)
+{
+    return cv_dense_multi_src("cv_dense_multi", c, dense_src_cm(x_dev, ld), n, p, y_dev, y_rs, y_cs, m, foldid_dev, nfolds, standardize, intercept,
+                              type_measure, o, beta, lambda_out, niter, loss, d, ncol, triples, fold_n, route, fold_beta, fold_lambda, fold_niter, predmat);
+}
+
+int oemgpu_cv_dense_multi_rm_dev(oemgpu_ctx *c, const void *x_dev, int32_t dtype, int64_t n, int64_t ldr, int32_t p, const double *y_dev, int64_t y_rs,
+                                 int64_t y_cs, int32_t m, const int32_t *foldid_dev, int32_t nfolds, int32_t standardize, int32_t intercept,
+                                 int32_t type_measure, const oemgpu_opts *o, double *beta, double *lambda_out, int32_t *niter, double *loss, double *d,
+                                 int32_t *ncol, double *triples, int64_t *fold_n, int32_t *route, double *fold_beta, double *fold_lambda,
+                                 int32_t *fold_niter, double *predmat)
+{
+    return cv_dense_multi_src("cv_dense_multi_rm", c, dense_src_rm(x_dev, dtype, ldr), n, p, y_dev, y_rs, y_cs, m, foldid_dev, nfolds, standardize,
+                              intercept, type_measure, o, beta, lambda_out, niter, loss, d, ncol, triples, fold_n, route, fold_beta, fold_lambda, fold_niter,
+                              predmat);
+}
+
+int oemgpu_last_cv_multi_timings(double *ms)
+{
+    if (!ms) { set_error("last_cv_multi_timings: NULL argument"); return OEMGPU_ERR_ARG; }
+    for (int i = 0; i < OEMGPU_CVM_NPHASES; ++i) ms[i] = g_cvm_ms[i];
+    return 0;
+}
+
+int oemgpu_selftest_cv_multi_plan(int64_t n, int32_t p, int32_t nfolds, int32_t m, int32_t npen, int32_t nl, int32_t num_cu, int32_t keep,
+                                  int32_t nb_limit, int64_t *out)
+{
+    if (n < 1 || p < 1 || m < 1 || npen < 1 || nl < 1 || num_cu < 1 || nb_limit < 0 || !out) { set_error("selftest_cv_multi_plan: bad argument"); return OEMGPU_ERR_ARG; }
+    if (int rc = xval_check_rows(n, n, nfolds, 0)) return rc;
+    if (n <= p) { set_error("selftest_cv_multi_plan: n <= p, which the call does not serve"); return OEMGPU_ERR_UNSUPPORTED; }
+    std::vector<int32_t> pen(npen, OEMGPU_LASSO);
+    oemgpu_opts o;
+    memset(&o, 0, sizeof o);
+    o.npen = npen; o.penalty = pen.data(); o.nlambda = nl;
+    const CvMultiLay W = cv_multi_layout(num_cu, n, p, nfolds, m, &o, nb_limit, keep != 0);
+    const XvalMultiLay &V = W.V;
+    const int64_t v[OEMGPU_CVM_PLAN_LEN] = {V.nb, V.nsolve, V.sv.engine, V.route, V.xp.rows, multi_fold_chunks_max(V.xp, nfolds), V.xp.npass, V.xp.mb, V.cv.nwg,
+                                            (int64_t)V.L.total, (int64_t)V.b_col, (int64_t)V.b_yp, (int64_t)V.b_cf, (int64_t)V.b_part, (int64_t)V.b_comp,
+                                            (int64_t)V.b_tab, (int64_t)V.b_cvpart, (int64_t)V.b_cvout, (int64_t)V.total, V.sv.cap,
+                                            (int64_t)W.b_raw, (int64_t)W.b_idx, (int64_t)W.b_ncol, (int64_t)W.b_inv, (int64_t)W.b_pred, (int64_t)W.b_tri,
+                                            (int64_t)W.total};
+    for (int i = 0; i < OEMGPU_CVM_PLAN_LEN; ++i) out[i] = v[i];
+    return 0;
+}
+
+int oemgpu_selftest_cv_multi_nb_limit(int32_t nb_limit)
+{
+    if (nb_limit < 0) { set_error("selftest_cv_multi_nb_limit: a negative limit"); return OEMGPU_ERR_ARG; }
+    g_cvm_nb_limit = nb_limit;
+    return 0;
+}
+
+int oemgpu_selftest_cv_interp(int32_t nfolds, int32_t npen, int32_t nl, const double *lam_full, const double *lam_fold, int32_t *left, int32_t *right,
+                              double *frac, int32_t *ncol)
+{
+    if (nfolds < 1 || npen < 1 || nl < 1 || !lam_full || !lam_fold || !left || !right || !frac || !ncol) { set_error("selftest_cv_interp: bad argument"); return OEMGPU_ERR_ARG; }
+    std::vector<int32_t> pen(npen, OEMGPU_LASSO);
+    oemgpu_opts o;
+    memset(&o, 0, sizeof o);
+    o.npen = npen; o.penalty = pen.data(); o.nlambda = nl;
+    std::vector<CvInterpIdx> idx((size_t)nfolds * npen * nl);
+    cv_interp_table(&o, nfolds, lam_full, lam_fold, idx.data(), ncol);
+    for (size_t t = 0; t < idx.size(); ++t) { left[t] = idx[t].left; right[t] = idx[t].right; frac[t] = idx[t].frac; }
+    return 0;
+}
+
+// Test infrastructure: the fold layout, the gathers and the many-response scoring alone on tables of the caller's (nothing is fitted, so
+// a fold may leave fewer rows than columns); with raw_dev == 0 the tables are scored as they are, else they go through cv_interp_kernel first
+int oemgpu_selftest_cv_score_multi_dev(oemgpu_ctx *c, const double *x_dev, int64_t n, int64_t ld, int32_t p, const double *y_dev, int64_t y_rs,
+                                       int64_t y_cs, int32_t m, const int32_t *foldid_dev, int32_t nfolds, const double *coef, int32_t npen, int32_t nl,
+                                       const int32_t *ncol, int32_t type_measure, int32_t nb, const int32_t *left, const int32_t *right,
+                                       const double *frac, double *table_out, double *triples, double *predmat_dev)
+{
+    const char *who = "selftest_cv_score_multi";
+    if (!c || !x_dev || !y_dev || !foldid_dev || !coef || !ncol || !triples) { set_error("%s: NULL argument", who); return OEMGPU_ERR_ARG; }
+    if (p < 1 || npen < 1 || nl < 1 || nb < 1) { set_error("%s: bad p, npen, nl or nb", who); return OEMGPU_ERR_ARG; }
+    if ((left || right || frac) && !(left && right && frac)) { set_error("%s: left, right and frac go together", who); return OEMGPU_ERR_ARG; }
+    const int K = nfolds;
+    int rc = xval_check_rows(n, ld, K, type_measure);
+    if (!rc) rc = multi_y_check(who, n, y_rs, y_cs, m);
+    if (rc) return rc;
+    const size_t nk2 = (size_t)npen * nl, blen = nk2 * (p + 1);
+    for (size_t t = 0; t < (size_t)m * npen; ++t)
+        if (ncol[t] < 0 || ncol[t] > nl) { set_error("%s: ncol[%d] = %d is outside 0..%d", who, (int)t, ncol[t], nl); return OEMGPU_ERR_ARG; }
+    if (left)
+        for (size_t t = 0; t < (size_t)m * K * nk2; ++t)
+            if (left[t] < 0 || left[t] >= nl || right[t] < 0 || right[t] >= nl) { set_error("%s: an index outside 0..nl-1", who); return OEMGPU_ERR_ARG; }
+    if (set_device(c)) return OEMGPU_ERR_HIP;
+    std::vector<int32_t> pen(npen, OEMGPU_LASSO);
+    oemgpu_opts o;
+    memset(&o, 0, sizeof o);
+    o.npen = npen; o.penalty = pen.data(); o.nlambda = nl;
+    if (nb > m) nb = m;
+    const CvMultiLay W = cv_multi_layout(c->num_cu, n, p, K, m, &o, 0, false, nb);       // (nothing is solved: the chunk is the caller's nb)
+    if (ctx_aux(c, W.total)) return OEMGPU_ERR_HIP;
+    const XvalLay &L = W.V.L;
+    char *ax = c->aux;
+    std::vector<int64_t> hf;
+    double *Yp = (double *)(ax + W.V.a_yp), *tab = (double *)(ax + W.V.a_tab), *raw = (double *)(ax + W.a_raw), *tri = (double *)(ax + W.a_tri);
+    const MultiY Y{y_dev, y_rs, y_cs};
+    const double *y0 = y_dev;                                        // response 0 rides along as y
+    if (y_rs != 1) { if ((rc = launch_multi_column(c->stream, Y, n, 0, (double *)(ax + W.V.a_col)))) return rc; y0 = (const double *)(ax + W.V.a_col); }
+    if ((rc = xval_prepare(c, L, dense_src_cm(x_dev, ld), y0, nullptr, foldid_dev, hf, false))) return rc;
+    if ((rc = launch_gather_responses(c->stream, y_dev, y_rs, y_cs, n, m, (const int *)(ax + L.a_pos), Yp, L.ldp))) return rc;
+    const int64_t *fold_n = (const int64_t *)(ax + L.a_fn), *fold_start = fold_n + K;
+    CvInterpIdx *idx_dev = (CvInterpIdx *)(ax + W.a_idx);
+    int *ncol_dev = (int *)(ax + W.a_ncol), *inv = (int *)(ax + W.a_inv);
+    if (predmat_dev) if ((rc = launch_fold_inverse(c->stream, (const int *)(ax + L.a_pos), n, L.ldp, inv))) return rc;
+    std::vector<CvInterpIdx> hidx;
+    for (int r0 = 0; r0 < m; r0 += nb) {
+        const int cb = m - r0 < nb ? m - r0 : nb;
+        OEM_HIP(hipMemcpyAsync(ncol_dev, ncol + (size_t)npen * r0, sizeof(int) * (size_t)npen * cb, hipMemcpyHostToDevice, c->stream));
+        if (left) {
+            hidx.resize((size_t)cb * K * nk2);
+            for (size_t t = 0; t < hidx.size(); ++t) { const size_t g = (size_t)r0 * K * nk2 + t; hidx[t] = CvInterpIdx{left[g], right[g], frac[g]}; }
+            OEM_HIP(hipMemcpyAsync(raw, coef + blen * K * r0, sizeof(double) * blen * K * cb, hipMemcpyHostToDevice, c->stream));
+            OEM_HIP(hipMemcpyAsync(idx_dev, hidx.data(), sizeof(CvInterpIdx) * hidx.size(), hipMemcpyHostToDevice, c->stream));
+            if ((rc = launch_cv_interp(c->stream, raw, idx_dev, ncol_dev, cb, K, npen, nl, p, tab))) return rc;
+            if (table_out) OEM_HIP(hipMemcpyAsync(table_out + blen * K * r0, tab, sizeof(double) * blen * K * cb, hipMemcpyDeviceToHost, c->stream));
+        } else OEM_HIP(hipMemcpyAsync(tab, coef + blen * K * r0, sizeof(double) * blen * K * cb, hipMemcpyHostToDevice, c->stream));
+        rc = launch_cv_fold_error_many(c->stream, (const double *)(ax + L.a_xp), L.ldp, Yp + (size_t)L.ldp * r0, fold_start, fold_n, K, p, tab, npen, nl,
+                                       type_measure, W.V.cv, cb, (double *)(ax + W.V.a_cvpart), ncol_dev, tri,
+                                       predmat_dev ? predmat_dev + nk2 * (size_t)n * r0 : nullptr, inv, n);
+        if (rc) return rc;
+        OEM_HIP(hipMemcpyAsync(triples + 3 * nk2 * K * r0, tri, sizeof(double) * 3 * nk2 * K * cb, hipMemcpyDeviceToHost, c->stream));
+        OEM_HIP(hipStreamSynchronize(c->stream));
+    }
+    return 0;
 }
 
 // rows [r0, r1) of the host data resident on the context's device: x (leading dimension *ld), y, foldid and the weights

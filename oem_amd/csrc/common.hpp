@@ -175,6 +175,15 @@ int launch_cv_fold_error(hipStream_t s, const double *xp, int64_t ldp, const dou
                          int K, int p, const double *B, int npen, int nl, int mae, const CvErrPlan &P, double *part, const int *ncol,
                          double *triples, double *predmat, const int *inv, int64_t n);
 int launch_cv_fold_finish(hipStream_t s, const double *part, int per_fold, int K, int npen, int nl, const int *ncol, double *triples);
+// cv_oem_multi: launch_cv_fold_error for nb responses in one product launch and one finish launch (P from cv_error_plan_many).  Response r:
+// y = Yp + r * ldp, table B + r * K * npen * nl * (p + 1), ncol + r * npen, triples + r * K * npen * nl * 3, predmat + r * npen * nl * n
+int launch_cv_fold_error_many(hipStream_t s, const double *xp, int64_t ldp, const double *Yp, const int64_t *fold_start, const int64_t *fold_n,
+                              int K, int p, const double *B, int npen, int nl, int mae, const CvErrPlan &P, int nb, double *part, const int *ncol,
+                              double *triples, double *predmat, const int *inv, int64_t n);
+// cv_oem_multi: tab[nb][K][npen][nl][p + 1] <- raw[left] frac + raw[right] (1 - frac) per column j < ncol[r][pen] (idx[nb][K][npen][nl]: the
+// host's lambda.interp of fold grid k of response r at the full fit's lambda j), zero from ncol on
+struct CvInterpIdx { int left, right; double frac; };
+int launch_cv_interp(hipStream_t s, const double *raw, const CvInterpIdx *idx, const int *ncol, int nb, int K, int npen, int nl, int p, double *tab);
 
 // ------------------------------------------------------------------ xval.oem on a sparse x (xval_sparse.hip, sparse.hip)
 // The ONE host plan of the call (pure arithmetic): the route of sparse_route, the fold-ordered layout (fold segments start on multiples of

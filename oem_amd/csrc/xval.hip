@@ -365,11 +365,12 @@ __global__ __launch_bounds__(64 * CVW) void cv_error_kernel(const double *__rest
                 if constexpr (PRED) {
                     const int64_t orig = ok ? (int64_t)pa.inv[start + row] : -1;
                     if (orig >= 0 && orig < pa.n) {
-                        const int ncolp = pa.ncol[pen];
+                        // blockIdx.z = resp * npen + pen: response resp's block of pred ([npen][nl][n] each) and its row of ncol
+                        const int ncolp = pa.ncol[blockIdx.z];
 #pragma unroll
                         for (int t = 0; t < LT; ++t) {
                             const int lam = l0 * 16 + 16 * t + l16;
-                            if (lam < nl) pa.pred[((size_t)pen * nl + lam) * pa.n + orig] = lam < ncolp ? acc[t][r] : __builtin_nan("");
+                            if (lam < nl) pa.pred[((size_t)blockIdx.z * nl + lam) * pa.n + orig] = lam < ncolp ? acc[t][r] : __builtin_nan("");
                         }
                     }
                 }
@@ -482,10 +483,14 @@ __global__ __launch_bounds__(64) void cv_finish_kernel(const double *__restrict_
 // merges that fold's nwg * CVW wave partials -- they are laid out [K][nwg][CVW] -- as above; out[K][npen][nl][3] <- (count, mean, M2),
 // (0, NaN, NaN) for a column >= ncol[pen] (not valid for that penalty) and for a fold without rows.
 __global__ __launch_bounds__(64) void cv_fold_finish_kernel(const double *__restrict__ part, int per_fold, int npen, int nl,
-                                                            const int *__restrict__ ncol, double *__restrict__ out)
+                                                            const int *__restrict__ ncol, double *__restrict__ out, long long pstride)
 {
+    // blockIdx.z: the response (one but for cv_oem_multi), its partials pstride doubles, its ncol row npen and its block K npen nl 3 further on
     const int t = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
     const int pen = t / nl, lam = t - pen * nl, nl16 = (nl + 15) & ~15;
+    part += (long long)blockIdx.z * pstride;
+    ncol += (size_t)blockIdx.z * npen;
+    out += (size_t)blockIdx.z * gridDim.y * npen * nl * 3;
     CvSet a;
     if (lam < ncol[pen]) a = cv_merge_partials(part, k * per_fold, per_fold, npen, pen, nl16, lam, lane);
     if (lane == 0) {
@@ -493,6 +498,28 @@ __global__ __launch_bounds__(64) void cv_fold_finish_kernel(const double *__rest
         const bool some = a.na > 0.0;
         o[0] = some ? a.na : 0.0; o[1] = some ? a.ma : __builtin_nan(""); o[2] = some ? a.qa : __builtin_nan("");
     }
+}
+
+// cv_oem_multi: the fold tables of a chunk of responses, each on ITS OWN lambda grid, onto the grids of the responses' full fits
+// (predict.oem's lambda.interp, R/utils.R:64-144, R/cv_oem.R:364-391).  raw / tab: [nb][K][npen][nl][p + 1]; idx[nb][K][npen][nl] the
+// (left, right, frac) the host worked out from the grids; ncol[nb][npen] the valid leading columns.  One workgroup per (column, fold,
+// response x penalty), threads over the p + 1 coefficients: tab = raw[left] frac + raw[right] (1 - frac), zero from ncol on.  Every
+// entry is written by one thread: no atomics, the same bytes every time.
+__global__ __launch_bounds__(256) void cv_interp_kernel(const double *__restrict__ raw, const CvInterpIdx *__restrict__ idx,
+                                                        const int *__restrict__ ncol, int npen, int nl, int Kd, double *__restrict__ tab)
+{
+    const int j = blockIdx.x, k = blockIdx.y, K = gridDim.y, z = blockIdx.z, resp = z / npen, pen = z - resp * npen;
+    const size_t col0 = (((size_t)resp * K + k) * npen + pen) * nl;         // column 0 of this (response, fold, penalty)
+    double *dst = tab + (col0 + j) * Kd;
+    if (j >= ncol[z]) {
+        for (int i = threadIdx.x; i < Kd; i += blockDim.x) dst[i] = 0.0;
+        return;
+    }
+    const CvInterpIdx e = idx[col0 + j];
+    const bool ok = e.left >= 0 && e.left < nl && e.right >= 0 && e.right < nl;       // (the host's table: never read beyond the block)
+    const double *bl = raw + (col0 + (ok ? e.left : 0)) * Kd, *br = raw + (col0 + (ok ? e.right : 0)) * Kd;
+    const double f = e.frac, g = 1.0 - e.frac;
+    for (int i = threadIdx.x; i < Kd; i += blockDim.x) dst[i] = ok ? bl[i] * f + br[i] * g : __builtin_nan("");
 }
 
 // inv[fold position] = the caller's row (the inverse of fold_pos_kernel's map; the padding between the folds stays unset and is never read)
@@ -708,7 +735,33 @@ int launch_cv_fold_error(hipStream_t s, const double *xp, int64_t ldp, const dou
 // the per-fold merge of launch_cv_fold_error alone, for partials [K][per_fold][npen][nl16][4] some other kernel wrote (xval_sparse.hip)
 int launch_cv_fold_finish(hipStream_t s, const double *part, int per_fold, int K, int npen, int nl, const int *ncol, double *triples)
 {
-    hipLaunchKernelGGL(cv_fold_finish_kernel, dim3(npen * nl, K), dim3(64), 0, s, part, per_fold, npen, nl, ncol, triples);
+    hipLaunchKernelGGL(cv_fold_finish_kernel, dim3(npen * nl, K), dim3(64), 0, s, part, per_fold, npen, nl, ncol, triples, 0LL);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+// launch_cv_fold_error for nb responses in one product launch and one finish launch (cv_oem_multi): response r reads Yp + r * ldp and
+// B + r * K * npen * nl * (p + 1) and ncol + r * npen, leaves its partials at part + r * cv_part_doubles(P.nwg, ...), its triples at
+// triples + r * K * npen * nl * 3 and, with predmat, yhat of its rows at predmat + r * npen * nl * n.  P: cv_error_plan_many's.
+int launch_cv_fold_error_many(hipStream_t s, const double *xp, int64_t ldp, const double *Yp, const int64_t *fold_start, const int64_t *fold_n,
+                              int K, int p, const double *B, int npen, int nl, int mae, const CvErrPlan &P, int nb, double *part, const int *ncol,
+                              double *triples, double *predmat, const int *inv, int64_t n)
+{
+    if ((long long)npen * nb > 65535 || nb > 65535) { set_error("cv_multi: the CV-error launch has more (penalty, response) pairs than a launch takes"); return OEMGPU_ERR_UNSUPPORTED; }
+    const long long pstride = (long long)cv_part_doubles(P.nwg, K, npen, nl);
+    const CvMany many{nb, (long long)ldp, (long long)K * npen * nl * (p + 1), pstride};
+    int rc = launch_cv_product(s, xp, ldp, Yp, fold_start, fold_n, K, p, B, npen, nl, mae, 0, P, part, predmat, inv, ncol, n, many);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cv_fold_finish_kernel, dim3(npen * nl, K, nb), dim3(64), 0, s, part, P.nwg * CVW, npen, nl, ncol, triples, pstride);
+    OEM_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_cv_interp(hipStream_t s, const double *raw, const CvInterpIdx *idx, const int *ncol, int nb, int K, int npen, int nl, int p, double *tab)
+{
+    if ((long long)npen * nb > 65535 || K > 65535) { set_error("cv_multi: the interpolation launch has more (penalty, response) pairs than a launch takes"); return OEMGPU_ERR_UNSUPPORTED; }
+    const int Kd = p + 1, threads = Kd >= 256 ? 256 : (Kd + 63) / 64 * 64;
+    hipLaunchKernelGGL(cv_interp_kernel, dim3(nl, K, npen * nb), dim3(threads), 0, s, raw, idx, ncol, npen, nl, Kd, tab);
     OEM_HIP(hipGetLastError());
     return 0;
 }
