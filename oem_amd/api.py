@@ -482,6 +482,32 @@ def context(device=None, stream=None):
 
 
 # ------------------------------------------------------------------------------------------ oem()
+def _fit_options(n, p, penalty, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups, penalty_factor, group_weights, maxit, tol,
+                 irls_maxit, irls_tol, varnames, zero_group, groups_sentence=False, accelerate=False, compute_loss=False, **device):
+    """The option prologue of every fit entry behind its checks of x and y (R/oem.R:268-404, R/oem_xtx.R:180-300, R/big_oem.R:200-330,
+    R/oem_xval.R:225-330) -> (_Args, varnames).  What differs between the entries is in the arguments (the table in DESIGN.md 1):
+    zero_group, whether the intercept adds group 0 (_group_setup); groups_sentence, whether the length of `groups` has a sentence of its
+    own before _group_setup; accelerate and compute_loss, which some entries fix; **device, the ngpus / devices / upload_threads /
+    interrupt that the entry has."""
+    if penalty_factor is None:
+        penalty_factor = np.ones(p)
+    penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
+    if varnames is None:
+        varnames = [f"V{i + 1}" for i in range(p)]
+    if len(penalty_factor) != p:
+        raise ValueError("penalty.factor must have same length as number of columns in x")
+    if groups_sentence and any("grp" in q for q in penalty) and len(np.ravel(groups)) != p:
+        raise ValueError("groups must have same length as number of columns in x")
+    groups, unique_groups, group_weights = _group_setup(penalty, groups, group_weights, p, zero_group)
+    if lambda_min_ratio is None:
+        lambda_min_ratio = 0.01 if n < p else 0.0001
+    _common_checks(nlambda, float(lambda_min_ratio), maxit, irls_maxit, tol, irls_tol)
+    lam_list = _lambda_list(lambda_, len(penalty))
+    a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, accelerate,
+              compute_loss, penalty_factor, groups, unique_groups, group_weights, **device)
+    return a, varnames
+
+
 def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=100, lambda_min_ratio=None,
         alpha=1.0, gamma=3.0, tau=0.5, groups=(), penalty_factor=None, group_weights=None, standardize=True,
         intercept=True, maxit=500, tol=1e-7, irls_maxit=100, irls_tol=1e-3, accelerate=False, ncores=-1,
@@ -518,22 +544,11 @@ def oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlambda=1
         raise ValueError("x and y lengths do not match")
     if family == "binomial":
         raise NotImplementedError("family='binomial' is outside the dense Gaussian hot path (ref src/oem_logistic_dense.cpp)")
-    if penalty_factor is None:
-        penalty_factor = np.ones(p)
-    penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
-    if varnames is None:
-        varnames = [f"V{i + 1}" for i in range(p)]
-    if len(penalty_factor) != p:
-        raise ValueError("penalty.factor must have same length as number of columns in x")
-    groups, unique_groups, group_weights = _group_setup(penalty, groups, group_weights, p, bool(intercept) and is_sparse)   # R/oem.R:296-338
-    if lambda_min_ratio is None:
-        lambda_min_ratio = 0.01 if n < p else 0.0001
-    _common_checks(nlambda, float(lambda_min_ratio), maxit, irls_maxit, tol, irls_tol)
-    lam_list = _lambda_list(lambda_, len(penalty))
-    a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, accelerate,
-              compute_loss, penalty_factor, groups, unique_groups, group_weights, ngpus=ngpus, devices=devices,
-              upload_threads=upload_threads, interrupt=interrupt)
-    if _args_only:                                                     # cv_oem's resident route: the option block of this call, nothing run
+    a, varnames = _fit_options(n, p, penalty, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups, penalty_factor, group_weights,
+                               maxit, tol, irls_maxit, irls_tol, varnames, bool(intercept) and is_sparse,                # R/oem.R:296-338
+                               accelerate=accelerate, compute_loss=compute_loss, ngpus=ngpus, devices=devices,
+                               upload_threads=upload_threads, interrupt=interrupt)
+    if _args_only:                                                    # cv_oem's resident route: the option block of this call, nothing run
         if is_sparse:
             a.c.accelerate = 0                                         # oemSparse has no acceleration
         return a, varnames, bool(standardize), bool(intercept)
@@ -603,6 +618,24 @@ class _OneOfMany:
 
     def __init__(self, beta, lam_out, niter, loss, d):
         self.beta, self.lam_out, self.niter, self.loss, self.d = beta, lam_out, niter, loss, C.c_double(float(d))
+
+
+class _ManyOut:
+    """The outputs of a call that makes m fits with the option block `a`: what _Args.outputs allocates, with a leading m"""
+
+    def __init__(self, m, a, rows):
+        self.beta = np.zeros((m, a.npen, a.nl, rows))
+        self.lam_out = np.zeros((m, a.npen, a.nl))
+        self.niter = np.zeros((m, a.npen, a.nl), dtype=np.int32)
+        self.loss = np.zeros((m, a.npen, a.nl))
+        self.d = np.zeros(m)
+
+    def pointers(self):
+        """the five result pointers in the order of the C ABI"""
+        return [_dptr(self.beta), _dptr(self.lam_out), _iptr(self.niter), _dptr(self.loss), _dptr(self.d)]
+
+    def one(self, r):
+        return _OneOfMany(self.beta[r], self.lam_out[r], self.niter[r], self.loss[r], self.d[r])
 
 
 def _device_responses(Y, device):
@@ -690,19 +723,14 @@ def oem_multi(x, Y, family="gaussian", weights=(), ngpus=0, devices=None, **kw):
     import torch
     X = _DeviceX(x, _rowmajor_in_place)
     Yd, rs, cs = _device_responses(Y, x.device)
-    beta = np.zeros((m, a.npen, a.nl, p + 1))
-    lam_out = np.zeros((m, a.npen, a.nl))
-    niter = np.zeros((m, a.npen, a.nl), dtype=np.int32)
-    loss = np.zeros((m, a.npen, a.nl))
-    d = np.zeros(m)
+    out = _ManyOut(m, a, p + 1)
     route = np.zeros(m, dtype=np.int32)
     ctx = context(x.device.index)
     torch.cuda.current_stream(x.device).synchronize()
-    X.call("fit_dense_multi", ctx, Yd.data_ptr(), rs, cs, m, int(standardize), int(intercept), C.byref(a.c),
-           _dptr(beta), _dptr(lam_out), _iptr(niter), _dptr(loss), _dptr(d), _iptr(route))
+    X.call("fit_dense_multi", ctx, Yd.data_ptr(), rs, cs, m, int(standardize), int(intercept), C.byref(a.c), *out.pointers(), _iptr(route))
     fits = []
     for r in range(m):
-        fit = _decorate(_OneOfMany(beta[r], lam_out[r], niter[r], loss[r], d[r]), penalty, varnames, True, n, p)
+        fit = _decorate(out.one(r), penalty, varnames, True, n, p)
         fit["route"] = int(route[r])
         fits.append(fit)
     return fits
@@ -766,20 +794,8 @@ def oem_fit_logistic_dense(x, y, penalty=None, weights=(), lambda_=(), nlambda=1
         raise ValueError("x and y lengths do not match")
     if len(np.unique(yh)) > 2:                                         # R/oem.R:250-252
         raise ValueError("y must be a binary outcome")
-    if penalty_factor is None:
-        penalty_factor = np.ones(p)
-    penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
-    if len(penalty_factor) != p:
-        raise ValueError("penalty.factor must have same length as number of columns in x")
-    if varnames is None:
-        varnames = [f"V{i + 1}" for i in range(p)]
-    groups, unique_groups, group_weights = _group_setup(penalty, groups, group_weights, p, bool(intercept))
-    if lambda_min_ratio is None:
-        lambda_min_ratio = 0.01 if n < p else 0.0001
-    _common_checks(nlambda, float(lambda_min_ratio), maxit, irls_maxit, tol, irls_tol)
-    lam_list = _lambda_list(lambda_, len(penalty))
-    a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
-              compute_loss, penalty_factor, groups, unique_groups, group_weights, interrupt=interrupt)
+    a, varnames = _fit_options(n, p, penalty, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups, penalty_factor, group_weights,
+                               maxit, tol, irls_maxit, irls_tol, varnames, bool(intercept), compute_loss=compute_loss, interrupt=interrupt)
     hf = 1 if hessian_type == "full" else 0
     lib = L.lib()
     if _is_torch_cuda(x):
@@ -898,33 +914,17 @@ def _logistic_multi_fit(who, x, Y, fold, penalty, weights, lambda_, nlambda, lam
                 raise ValueError(f"instance ({r}, {k}): the fold left out must be in [0, {nfolds}] (0: the full fit)")
         resp = np.ascontiguousarray([r for r, _ in instances], dtype=np.int32)
         leave = np.ascontiguousarray([k for _, k in instances], dtype=np.int32)
-    if penalty_factor is None:
-        penalty_factor = np.ones(p)
-    penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
-    if len(penalty_factor) != p:
-        raise ValueError("penalty.factor must have same length as number of columns in x")
-    if varnames is None:
-        varnames = [f"V{i + 1}" for i in range(p)]
-    groups, unique_groups, group_weights = _group_setup(penalty, groups, group_weights, p, bool(intercept))
-    if lambda_min_ratio is None:
-        lambda_min_ratio = 0.01 if n < p else 0.0001
-    _common_checks(nlambda, float(lambda_min_ratio), maxit, irls_maxit, tol, irls_tol)
-    lam_list = _lambda_list(lambda_, len(penalty))
-    a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
-              compute_loss, penalty_factor, groups, unique_groups, group_weights, interrupt=interrupt)
+    a, varnames = _fit_options(n, p, penalty, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups, penalty_factor, group_weights,
+                               maxit, tol, irls_maxit, irls_tol, varnames, bool(intercept), compute_loss=compute_loss, interrupt=interrupt)
     import torch
     X = _DeviceX(x, _logistic_rowmajor_in_place)                       # row-major float64 / float32: read where it lies
     Yd, rs, cs = _device_responses(Y, x.device)
     nfit = m if fold is None else len(resp)
-    beta = np.zeros((nfit, a.npen, a.nl, p + 1))
-    lam_out = np.zeros((nfit, a.npen, a.nl))
-    niter = np.zeros((nfit, a.npen, a.nl), dtype=np.int32)
-    loss = np.zeros((nfit, a.npen, a.nl))
-    d = np.zeros(nfit)
+    out = _ManyOut(nfit, a, p + 1)
     nobs = np.full(nfit, n, dtype=np.int64)
     ctx = context(x.device.index)
     scal = (int(bool(standardize)), int(bool(intercept)), 0, int(irls_maxit), float(irls_tol), C.byref(a.c))
-    outs = (_dptr(beta), _dptr(lam_out), _iptr(niter), _dptr(loss), _dptr(d))
+    outs = out.pointers()
     if fold is None:
         torch.cuda.current_stream(x.device).synchronize()
         X.call("fit_logistic_dense_multi", ctx, Yd.data_ptr(), rs, cs, m, *scal, *outs)
@@ -934,8 +934,7 @@ def _logistic_multi_fit(who, x, Y, fold, penalty, weights, lambda_, nlambda, lam
         torch.cuda.current_stream(x.device).synchronize()
         X.call("fit_logistic_dense_multi_fold", ctx, Yd.data_ptr(), rs, cs, m, fd.data_ptr(), nfolds, nfit, _iptr(resp), _iptr(leave), *scal, *outs,
                nobs.ctypes.data_as(C.POINTER(C.c_int64)))
-    return [OemFitBinomial(_decorate(_OneOfMany(beta[r], lam_out[r], niter[r], loss[r], d[r]), penalty, varnames, True, int(nobs[r]), p, family="binomial"))
-            for r in range(nfit)]
+    return [OemFitBinomial(_decorate(out.one(r), penalty, varnames, True, int(nobs[r]), p, family="binomial")) for r in range(nfit)]
 
 
 def oem_fit_logistic_dense_multi_folds(x, Y, foldid, instances=None, penalty=None, weights=(), lambda_=(), nlambda=100, lambda_min_ratio=None, alpha=1.0,
@@ -1194,20 +1193,8 @@ def oem_fit_logistic_sparse(x, y, penalty=None, weights=(), lambda_=(), nlambda=
         raise ValueError("x and y lengths do not match")
     if len(np.unique(yh)) > 2:                                         # R/oem.R:250-252
         raise ValueError("y must be a binary outcome")
-    if penalty_factor is None:
-        penalty_factor = np.ones(p)
-    penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
-    if len(penalty_factor) != p:
-        raise ValueError("penalty.factor must have same length as number of columns in x")
-    if varnames is None:
-        varnames = [f"V{i + 1}" for i in range(p)]
-    groups, unique_groups, group_weights = _group_setup(penalty, groups, group_weights, p, bool(intercept))
-    if lambda_min_ratio is None:
-        lambda_min_ratio = 0.01 if n < p else 0.0001
-    _common_checks(nlambda, float(lambda_min_ratio), maxit, irls_maxit, tol, irls_tol)
-    lam_list = _lambda_list(lambda_, len(penalty))
-    a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
-              compute_loss, penalty_factor, groups, unique_groups, group_weights, interrupt=interrupt)
+    a, varnames = _fit_options(n, p, penalty, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups, penalty_factor, group_weights,
+                               maxit, tol, irls_maxit, irls_tol, varnames, bool(intercept), compute_loss=compute_loss, interrupt=interrupt)
     if _fold is None and isinstance(x, SparseX):                       # the fit on a handle: leave_out = 0, the bits of the plain call
         import torch
         _fold = (x, None, 3, 0, torch.as_tensor(yh, device=x.device))
@@ -1257,25 +1244,12 @@ def oem_xtx(xtx, xty, family="gaussian", penalty=None, lambda_=(), nlambda=100, 
         raise ValueError("xtx must have at least two columns")
     if family == "binomial":
         raise ValueError("binomial not implemented yet")
-    if penalty_factor is None:
-        penalty_factor = np.ones(p)
-    penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
-    if varnames is None:
-        varnames = [f"V{i + 1}" for i in range(p)]
-    if len(penalty_factor) != p:
-        raise ValueError("penalty.factor must have same length as number of columns in x")
-    if any("grp" in q for q in penalty) and len(np.ravel(groups)) != p:
-        raise ValueError("groups must have same length as number of columns in x")
-    groups, unique_groups, group_weights = _group_setup(penalty, groups, group_weights, p, False)
-    if lambda_min_ratio is None:
-        lambda_min_ratio = 0.0001
-    _common_checks(nlambda, float(lambda_min_ratio), maxit, irls_maxit, tol, irls_tol)
-    lam_list = _lambda_list(lambda_, len(penalty))
+    a, varnames = _fit_options(p, p, penalty, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups, penalty_factor, group_weights,
+                               maxit, tol, irls_maxit, irls_tol, varnames, False, groups_sentence=True,   # (no n: the ratio's default is 0.0001)
+                               interrupt=interrupt)
     sf = np.asarray(scale_factor, dtype=np.float64).ravel()
     if sf.size > 0 and sf.size != p:
         raise ValueError("scale.factor must be same length as xty (nvars)")
-    a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
-              False, penalty_factor, groups, unique_groups, group_weights, interrupt=interrupt)
     lib = L.lib()
     if _is_torch_cuda(xtx):
         import torch
@@ -1318,23 +1292,9 @@ def big_oem(x, y, family="gaussian", penalty=None, weights=(), lambda_=(), nlamb
         raise ValueError("weights not implemented yet.")
     if len(yshards) != len(shards) or sum(len(v) for v in yshards) != n:
         raise ValueError("x and y lengths do not match")
-    if penalty_factor is None:
-        penalty_factor = np.ones(p)
-    penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
-    if varnames is None:
-        varnames = [f"V{i + 1}" for i in range(p)]
-    if len(penalty_factor) != p:
-        raise ValueError("penalty.factor must have same length as number of columns in x")
-    if any("grp" in q for q in penalty) and len(np.ravel(groups)) != p:
-        raise ValueError("groups must have same length as number of columns in x")
-    groups, unique_groups, group_weights = _group_setup(penalty, groups, group_weights, p, bool(intercept))
-    if lambda_min_ratio is None:
-        lambda_min_ratio = 0.01 if n < p else 0.0001
-    _common_checks(nlambda, float(lambda_min_ratio), maxit, irls_maxit, tol, irls_tol)
-    lam_list = _lambda_list(lambda_, len(penalty))
-    a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
-              compute_loss, penalty_factor, groups, unique_groups, group_weights, ngpus=ngpus, devices=devices,
-              upload_threads=upload_threads, interrupt=interrupt)
+    a, varnames = _fit_options(n, p, penalty, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups, penalty_factor, group_weights,
+                               maxit, tol, irls_maxit, irls_tol, varnames, bool(intercept), groups_sentence=True, compute_loss=compute_loss,
+                               ngpus=ngpus, devices=devices, upload_threads=upload_threads, interrupt=interrupt)
     xs = [np.asfortranarray(s, dtype=np.float64) for s in shards]
     ys = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1)) for v in yshards]
     ns = (C.c_int64 * len(xs))(*[s.shape[0] for s in xs])
@@ -1365,6 +1325,47 @@ def _getmin(lam, cvm, cvsd):
 
 
 _TYPE_MEASURES = ("mse", "deviance", "class", "auc", "mae")
+_GAUSSIAN_NAMES = {"mse": "Mean-Squared Error", "mae": "Mean Absolute Error"}
+
+
+def _check_type_measure(type_measure):
+    """match.arg(type.measure) of xval.oem and cv.oem: "default" when none is given"""
+    if type_measure is None:
+        return "default"
+    if type_measure not in _TYPE_MEASURES:
+        raise ValueError("'arg' should be one of " + ", ".join("'%s'" % t for t in _TYPE_MEASURES))
+    return type_measure
+
+
+def _fold_ids(foldid, nfolds, n, rng):
+    """(foldid, nfolds): the ids drawn with `rng` as sample(rep(seq(nfolds), length = n)), or the caller's and their largest"""
+    if foldid is None:
+        g = np.random.default_rng() if rng is None else rng
+        foldid = g.permutation(np.resize(np.arange(1, int(nfolds) + 1), n))
+    else:
+        foldid = np.asarray(foldid).ravel()
+        nfolds = int(foldid.max())
+    if nfolds < 3:
+        raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
+    return foldid, nfolds
+
+
+def _gaussian_measure(type_measure):
+    """"mse" or "mae" for a Gaussian model (R/oem_xval.R:488-497, R/cv_oem.R:357-363)"""
+    if type_measure in ("default", "deviance"):
+        return "mse"
+    if type_measure not in ("mse", "mae"):
+        warnings.warn("Only 'mse', 'deviance' or 'mae'  available for Gaussian models; 'mse' used")
+        return "mse"
+    return type_measure
+
+
+def _ungrouped_if_small(n, nfolds, grouped):
+    """`grouped`, or False where a fold holds fewer than three observations (R/cv_oem.R:405-411)"""
+    if n / nfolds < 3 and grouped:
+        warnings.warn("Option grouped=FALSE enforced in cv.glmnet, since < 3 observations per fold")
+        return False
+    return grouped
 
 
 def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family="gaussian", penalty=None, weights=(),
@@ -1387,10 +1388,7 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
     if family not in ("gaussian", "binomial"):
         raise ValueError("'arg' should be one of 'gaussian', 'binomial'")
     penalty = _match_penalty(penalty)
-    if type_measure is None:
-        type_measure = "default"
-    elif type_measure not in _TYPE_MEASURES:
-        raise ValueError("'arg' should be one of " + ", ".join("'%s'" % t for t in _TYPE_MEASURES))
+    type_measure = _check_type_measure(type_measure)
     if family == "binomial":
         raise ValueError("binomial models not yet supported for xval, use cv.oem() instead")
     if getattr(x, "ndim", 0) != 2 and not isinstance(x, SparseX):
@@ -1402,15 +1400,8 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
                          "             glmnet for the lasso, ncvreg for MCP/SCAD, or grpreg or gglasso for group lasso.")
     if p < 2:
         raise ValueError("x must have at least two columns")
-    if foldid is None:
-        g = np.random.default_rng() if rng is None else rng
-        foldid = g.permutation(np.resize(np.arange(1, int(nfolds) + 1), n))
-    else:
-        foldid = np.asarray(foldid).ravel()
-        nfolds = int(foldid.max())
-    if nfolds < 3:
-        raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
-    on_handle = isinstance(x, SparseX)                           # the resident columns: oemgpu_xval_sparse_res, nothing uploaded but y and foldid
+    foldid, nfolds = _fold_ids(foldid, nfolds, n, rng)
+    on_handle = isinstance(x, SparseX)                          # the resident columns: oemgpu_xval_sparse_res, nothing uploaded but y and foldid
     if on_handle:
         x.handle                                                 # (a closed SparseX raises here)
     sparse = _is_scipy_sparse(x) or on_handle                    # R/oem_xval.R:196-201 stops here; :500 names the routine served now
@@ -1427,9 +1418,10 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
         if len(weights) != n:
             raise ValueError("length of weights not same as number of observations in x")
         wh = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
-    a, varnames, type_measure = _xval_options(n, p, penalty, type_measure, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups,
-                                              penalty_factor, group_weights, intercept, maxit, tol, irls_maxit, irls_tol, compute_loss,
-                                              varnames, ngpus, devices, upload_threads, interrupt)
+    a, varnames = _fit_options(n, p, penalty, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups, penalty_factor, group_weights,
+                               maxit, tol, irls_maxit, irls_tol, varnames, bool(intercept), groups_sentence=True, compute_loss=compute_loss,
+                               ngpus=ngpus, devices=devices, upload_threads=upload_threads, interrupt=interrupt)
+    type_measure = _gaussian_measure(type_measure)
     out = a.outputs(p + 1)
     cvm = np.zeros((a.npen, a.nl)); cvsd = np.zeros((a.npen, a.nl))
     fid = np.ascontiguousarray(foldid, dtype=np.int32)
@@ -1467,41 +1459,12 @@ def xval_oem(x, y, nfolds=10, foldid=None, type_measure=None, ncores=-1, family=
     return _xval_result(a, penalty, varnames, n, p, cvm, cvsd, type_measure, fid)
 
 
-def _xval_options(n, p, penalty, type_measure, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups, penalty_factor, group_weights,
-                  intercept, maxit, tol, irls_maxit, irls_tol, compute_loss, varnames, ngpus, devices, upload_threads, interrupt):
-    """The option checks of xval.oem behind its checks of x, y and foldid (R/oem_xval.R:225-330, 488-497) -> (_Args, varnames,
-    type_measure as "mse" / "mae"): xval_oem and xval_oem_multi both pass through here, with the same sentences."""
-    if penalty_factor is None:
-        penalty_factor = np.ones(p)
-    if varnames is None:
-        varnames = [f"V{i + 1}" for i in range(p)]
-    penalty_factor = np.asarray(penalty_factor, dtype=np.float64).ravel()
-    if len(penalty_factor) != p:
-        raise ValueError("penalty.factor must have same length as number of columns in x")
-    if any("grp" in q for q in penalty) and len(np.ravel(groups)) != p:
-        raise ValueError("groups must have same length as number of columns in x")
-    groups, unique_groups, group_weights = _group_setup(penalty, groups, group_weights, p, bool(intercept))
-    if lambda_min_ratio is None:
-        lambda_min_ratio = 0.01 if n < p else 0.0001
-    _common_checks(nlambda, float(lambda_min_ratio), maxit, irls_maxit, tol, irls_tol)
-    lam_list = _lambda_list(lambda_, len(penalty))
-    if type_measure in ("default", "deviance"):                  # R/oem_xval.R:488-497
-        type_measure = "mse"
-    if type_measure not in ("mse", "mae"):
-        warnings.warn("Only 'mse', 'deviance' or 'mae'  available for Gaussian models; 'mse' used")
-        type_measure = "mse"
-    a = _Args(penalty, lam_list, int(np.ravel(nlambda)[0]), lambda_min_ratio, alpha, gamma, tau, tol, maxit, False,
-              compute_loss, penalty_factor, groups, unique_groups, group_weights, ngpus=ngpus, devices=devices,
-              upload_threads=upload_threads, interrupt=interrupt)
-    return a, varnames, type_measure
-
-
 def _xval_result(a, penalty, varnames, n, p, cvm, cvsd, type_measure, fid):
     """xval.oem's return value (R/oem_xval.R:430-460) from the outputs `a` holds (an _Args, or one response of many) and cvm / cvsd [npen, nl]"""
     res = _decorate(a, penalty, varnames, True, n, p)
     res["cvm"] = [cvm[k, :1].copy() if name == "ols" else cvm[k].copy() for k, name in enumerate(penalty)]
     res["cvsd"] = [cvsd[k, :1].copy() if name == "ols" else cvsd[k].copy() for k, name in enumerate(penalty)]
-    res["name"] = {"mse": "Mean-Squared Error", "mae": "Mean Absolute Error"}[type_measure]
+    res["name"] = _GAUSSIAN_NAMES[type_measure]
     res["foldid"] = fid
     res.update(_getmin([l[:len(c)] for l, c in zip(res["lambda"], res["cvm"])], res["cvm"], res["cvsd"]))
     res["cvup"] = [m + s for m, s in zip(res["cvm"], res["cvsd"])]
@@ -1568,10 +1531,7 @@ def xval_oem_multi(x, Y, nfolds=10, foldid=None, type_measure=None, family="gaus
     if family not in ("gaussian", "binomial"):
         raise ValueError("'arg' should be one of 'gaussian', 'binomial'")
     penalty = _match_penalty(penalty)
-    if type_measure is None:
-        type_measure = "default"
-    elif type_measure not in _TYPE_MEASURES:
-        raise ValueError("'arg' should be one of " + ", ".join("'%s'" % t for t in _TYPE_MEASURES))
+    type_measure = _check_type_measure(type_measure)
     if family == "binomial":
         raise ValueError("binomial models not yet supported for xval, use cv.oem() instead")
     if len(weights) > 0:
@@ -1592,42 +1552,31 @@ def xval_oem_multi(x, Y, nfolds=10, foldid=None, type_measure=None, family="gaus
                          "             glmnet for the lasso, ncvreg for MCP/SCAD, or grpreg or gglasso for group lasso.")
     if p < 2:
         raise ValueError("x must have at least two columns")
-    if foldid is None:
-        g = np.random.default_rng() if rng is None else rng
-        foldid = g.permutation(np.resize(np.arange(1, int(nfolds) + 1), n))
-    else:
-        foldid = np.asarray(foldid).ravel()
-        nfolds = int(foldid.max())
-    if nfolds < 3:
-        raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
+    foldid, nfolds = _fold_ids(foldid, nfolds, n, rng)
     if Y.shape[0] != n or len(foldid) != n:
         raise ValueError("x and y lengths do not match")
     if not _is_torch_cuda(x):
         raise ValueError(host_or_sparse)
-    a, varnames, type_measure = _xval_options(n, p, penalty, type_measure, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups,
-                                              penalty_factor, group_weights, intercept, maxit, tol, irls_maxit, irls_tol, compute_loss,
-                                              varnames, 0, None, 0, interrupt)
+    a, varnames = _fit_options(n, p, penalty, lambda_, nlambda, lambda_min_ratio, alpha, gamma, tau, groups, penalty_factor, group_weights,
+                               maxit, tol, irls_maxit, irls_tol, varnames, bool(intercept), groups_sentence=True, compute_loss=compute_loss,
+                               interrupt=interrupt)
+    type_measure = _gaussian_measure(type_measure)
     L.sync_switches()
     import torch
     X = _DeviceX(x, _xval_rowmajor_in_place)
     Yd, rs, cs = _device_responses(Y, x.device)
     fid = np.ascontiguousarray(foldid, dtype=np.int32)
     fd = torch.as_tensor(fid, device=x.device)
-    beta = np.zeros((m, a.npen, a.nl, p + 1))
-    lam_out = np.zeros((m, a.npen, a.nl))
-    niter = np.zeros((m, a.npen, a.nl), dtype=np.int32)
-    loss = np.zeros((m, a.npen, a.nl))
-    d = np.zeros(m)
+    out = _ManyOut(m, a, p + 1)
     cvm = np.zeros((m, a.npen, a.nl)); cvsd = np.zeros((m, a.npen, a.nl))
     route = np.zeros(m, dtype=np.int32)
     ctx = context(x.device.index)
     torch.cuda.current_stream(x.device).synchronize()
     X.call("xval_dense_multi", ctx, Yd.data_ptr(), rs, cs, m, fd.data_ptr(), int(nfolds), int(bool(standardize)), int(bool(intercept)),
-           1 if type_measure == "mae" else 0, C.byref(a.c), _dptr(beta), _dptr(lam_out), _iptr(niter), _dptr(loss), _dptr(d), _dptr(cvm),
-           _dptr(cvsd), _iptr(route))
+           1 if type_measure == "mae" else 0, C.byref(a.c), *out.pointers(), _dptr(cvm), _dptr(cvsd), _iptr(route))
     fits = []
     for r in range(m):
-        fit = _xval_result(_OneOfMany(beta[r], lam_out[r], niter[r], loss[r], d[r]), penalty, varnames, n, p, cvm[r], cvsd[r], type_measure, fid)
+        fit = _xval_result(out.one(r), penalty, varnames, n, p, cvm[r], cvsd[r], type_measure, fid)
         fit["route"] = int(route[r])
         fits.append(fit)
     return fits
@@ -2008,15 +1957,7 @@ def _cv_oem_binomial_on(fit, score, device, n, p, yh, penalty, type_measure, nfo
     import torch
     fit0 = fit(None, 0, 0)
     nmodels = len(penalty)
-    nz = [np.array([0 if v is None else len(v) for v in predict(fit0, type="nonzero", which_model=m)]) for m in range(nmodels)]
-    if foldid is None:
-        g = np.random.default_rng() if rng is None else rng
-        foldid = g.permutation(np.resize(np.arange(1, int(nfolds) + 1), n))
-    else:
-        foldid = np.asarray(foldid).ravel()
-        nfolds = int(foldid.max())
-    if nfolds < 3:
-        raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
+    foldid, nfolds = _fold_ids(foldid, nfolds, n, rng)
     if len(foldid) != n:
         raise ValueError("x and y lengths do not match")
     fd = torch.as_tensor(np.ascontiguousarray(foldid, dtype=np.int32), device=device)
@@ -2028,9 +1969,7 @@ def _cv_oem_binomial_on(fit, score, device, n, p, yh, penalty, type_measure, nfo
         warnings.warn("Too few (< 10) observations per fold for type.measure='auc' in cv.lognet; changed to type.measure='deviance'. "
                       "Alternatively, use smaller value for nfolds")
         type_measure = "deviance"
-    if n / nfolds < 3 and grouped:
-        warnings.warn("Option grouped=FALSE enforced in cv.glmnet, since < 3 observations per fold")
-        grouped = False
+    grouped = _ungrouped_if_small(n, nfolds, grouped)
     lam = [np.asarray(l, dtype=np.float64) for l in fit0["lambda"]]
     nl = len(lam[0])
     which_lam = [lam[m] >= max(np.min(o["lambda"][m]) for o in outlist) for m in range(nmodels)]     # no extrapolation to smaller lambdas
@@ -2086,22 +2025,7 @@ def _cv_oem_binomial_on(fit, score, device, n, p, yh, penalty, type_measure, nfo
             with np.errstate(invalid="ignore", divide="ignore"):
                 cs[:k] = np.sqrt(np.maximum((s2 - 2.0 * cm[:k] * s1 + n * cm[:k] ** 2) / n, 0.0) / (n - 1))
         cvm.append(cm); cvsd.append(cs)
-    nas = np.zeros(nl, dtype=bool)
-    for m in range(nmodels):
-        nas |= np.isnan(cvsd[m])
-    if nas.any():
-        cvm = [c[~nas] for c in cvm]; cvsd = [c[~nas] for c in cvsd]
-        nz = [c[~nas] for c in nz]; lam = [l[~nas] for l in lam]
-    res = OemFit()
-    name = _BINOMIAL_NAMES[type_measure]
-    res.update({"lambda": lam, "cvm": cvm, "cvsd": cvsd, "cvup": [a + b for a, b in zip(cvm, cvsd)],
-                "cvlo": [a - b for a, b in zip(cvm, cvsd)], "nzero": nz, "name": name, "oem.fit": fit0})
-    if keep:
-        res["fit.preval"] = predlist; res["foldid"] = foldid
-    res.update(_getmin(lam, [-c for c in cvm] if name == "AUC" else cvm, cvsd))
-    res["best.model"] = penalty[res["model.min"] - 1]
-    res["penalty"] = list(penalty)
-    return res
+    return _cv_result(fit0, penalty, lam, cvm, cvsd, _BINOMIAL_NAMES[type_measure], predlist if keep else None, foldid)
 
 
 def cv_oem_logistic_multi(x, Y, penalty=None, lambda_=None, type_measure=None, nfolds=10, foldid=None, grouped=True, keep=False, rng=None, **kw):
@@ -2113,10 +2037,7 @@ def cv_oem_logistic_multi(x, Y, penalty=None, lambda_=None, type_measure=None, n
     GPU with p + intercept <= 1024; the keyword arguments are oem_fit_logistic_dense_multi's.  ValueErrors before a device is looked for:
     hessian_type="full", weights, a host or sparse x, ngpus / devices, p + intercept > 1024, len(lambda_) < 2, nfolds < 3."""
     penalty = _match_penalty(penalty)
-    if type_measure is None:
-        type_measure = "default"
-    elif type_measure not in _TYPE_MEASURES:
-        raise ValueError("'arg' should be one of " + ", ".join("'%s'" % t for t in _TYPE_MEASURES))
+    type_measure = _check_type_measure(type_measure)
     if lambda_ is not None and len(lambda_) < 2:
         raise ValueError("Need more than one value of lambda for cv.oem")
     for drop in ("accelerate", "ncores"):            # oem() arguments the binomial fit has no use for (no Nesterov step, no OpenMP)
@@ -2142,8 +2063,7 @@ def cv_oem_logistic_multi(x, Y, penalty=None, lambda_=None, type_measure=None, n
     if foldid is None:
         if int(nfolds) < 3:
             raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
-        g = np.random.default_rng() if rng is None else rng
-        foldid = g.permutation(np.resize(np.arange(1, int(nfolds) + 1), n))
+        foldid, _ = _fold_ids(None, nfolds, n, rng)
     else:
         foldid = np.asarray(foldid.cpu() if _is_torch_cuda(foldid) else foldid).ravel()
     import torch
@@ -2398,6 +2318,28 @@ def _cv_weighted_stats(cvraw, w, N):
     return cvm, cvsd
 
 
+def _cv_result(fit0, penalty, lam, cvm, cvsd, name, predlist=None, foldid=None):
+    """cv.oem's return value (R/cv_oem.R:190-221) from the full fit, its lambdas and cvm / cvsd per model: the columns where any
+    model's cvsd is NaN leave cvm, cvsd, nzero and lambda; `name` is the measure's ("AUC" is the one that getmin maximises);
+    predlist (keep=TRUE) goes in as fit.preval, with foldid"""
+    nz = [np.array([0 if v is None else len(v) for v in predict(fit0, type="nonzero", which_model=m)]) for m in range(len(penalty))]
+    nas = np.zeros(len(lam[0]), dtype=bool)
+    for c in cvsd:
+        nas |= np.isnan(c)
+    if nas.any():
+        cvm = [c[~nas] for c in cvm]; cvsd = [c[~nas] for c in cvsd]
+        nz = [c[~nas] for c in nz]; lam = [l[~nas] for l in lam]
+    res = OemFit()
+    res.update({"lambda": lam, "cvm": cvm, "cvsd": cvsd, "cvup": [a + b for a, b in zip(cvm, cvsd)],
+                "cvlo": [a - b for a, b in zip(cvm, cvsd)], "nzero": nz, "name": name, "oem.fit": fit0})
+    if predlist is not None:
+        res["fit.preval"] = predlist; res["foldid"] = foldid
+    res.update(_getmin(lam, [-c for c in cvm] if name == "AUC" else cvm, cvsd))
+    res["best.model"] = penalty[res["model.min"] - 1]
+    res["penalty"] = list(penalty)
+    return res
+
+
 def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfolds=10, foldid=None, grouped=True, keep=False,
            rng=None, parallel=False, family="gaussian", **kw):
     """cv.oem(): R/cv_oem.R:56-221 with cv.oemfit_gaussian (:349-423) and cvcompute (R/utils.R:128-144): K + 1 calls of oem(),
@@ -2441,10 +2383,7 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
     if family not in ("gaussian", "binomial"):
         raise ValueError("'arg' should be one of 'gaussian', 'binomial'")
     penalty = _match_penalty(penalty)
-    if type_measure is None:
-        type_measure = "default"
-    elif type_measure not in _TYPE_MEASURES:
-        raise ValueError("'arg' should be one of " + ", ".join("'%s'" % t for t in _TYPE_MEASURES))
+    type_measure = _check_type_measure(type_measure)
     if lambda_ is not None and len(lambda_) < 2:
         raise ValueError("Need more than one value of lambda for cv.oem")
     x = _sparse_tensor_arg(x)
@@ -2468,14 +2407,7 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
     lam_arg = () if lambda_ is None else lambda_
     if not on_sparse:
         fit0 = oem(x, y, penalty=penalty, lambda_=lam_arg, **kw)
-    if foldid is None:
-        g = np.random.default_rng() if rng is None else rng
-        foldid = g.permutation(np.resize(np.arange(1, int(nfolds) + 1), n))
-    else:
-        foldid = np.asarray(foldid).ravel()
-        nfolds = int(foldid.max())
-    if nfolds < 3:
-        raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
+    foldid, nfolds = _fold_ids(foldid, nfolds, n, rng)
     resident = on_sparse or _cv_gaussian_resident(x, penalty, kw, foldid, nfolds)
     if on_sparse and x.shape[0] <= x.shape[1]:                    # n <= p: the full fit and the K masked fold fits over the handle's non-zeros
         fit0, outlist, dev = _cv_gaussian_sparse_wide_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw)
@@ -2485,13 +2417,8 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
         outlist, dev = _cv_gaussian_fold_fits(x, y, foldid, nfolds, penalty, lam_arg, kw)
     else:
         outlist, xh, yh = _cv_gaussian_host_fits(x, y, foldid, nfolds, penalty, lam_arg, kw, parallel)
-    nz = [np.array([0 if v is None else len(v) for v in predict(fit0, type="nonzero", which_model=m)]) for m in range(len(penalty))]
     # cv.oemfit_gaussian
-    if type_measure in ("default", "deviance"):
-        type_measure = "mse"
-    if type_measure not in ("mse", "mae"):
-        warnings.warn("Only 'mse', 'deviance' or 'mae'  available for Gaussian models; 'mse' used")
-        type_measure = "mse"
+    type_measure = _gaussian_measure(type_measure)
     lam = [np.asarray(l, dtype=np.float64) for l in fit0["lambda"]]
     nmodels = len(penalty)
     which_lam = [lam[m] >= max(np.min(o["lambda"][m]) for o in outlist) for m in range(nmodels)]     # no extrapolation to smaller lambdas
@@ -2505,29 +2432,12 @@ def cv_oem(x, y, penalty=None, weights=(), lambda_=None, type_measure=None, nfol
             for m in range(nmodels):
                 preds = predict(outlist[i - 1], xh[rows], s=lam[m][which_lam[m]], which_model=m)
                 predlist[m][rows, :int(which_lam[m].sum())] = preds
-    if n / nfolds < 3 and grouped:
-        warnings.warn("Option grouped=FALSE enforced in cv.glmnet, since < 3 observations per fold")
-        grouped = False
+    grouped = _ungrouped_if_small(n, nfolds, grouped)
     if resident:
         cvm, cvsd = _cv_gaussian_triple_stats(dev, triples, nlams, grouped)
     else:
         cvm, cvsd = _cv_gaussian_host_stats(predlist, yh, foldid, nfolds, nlams, type_measure, grouped)
-    nas = np.zeros(len(lam[0]), dtype=bool)
-    for m in range(nmodels):
-        nas |= np.isnan(cvsd[m])
-    if nas.any():
-        cvm = [c[~nas] for c in cvm]; cvsd = [c[~nas] for c in cvsd]
-        nz = [c[~nas] for c in nz]; lam = [l[~nas] for l in lam]
-    res = OemFit()
-    res.update({"lambda": lam, "cvm": cvm, "cvsd": cvsd, "cvup": [a + b for a, b in zip(cvm, cvsd)],
-                "cvlo": [a - b for a, b in zip(cvm, cvsd)], "nzero": nz,
-                "name": {"mse": "Mean-Squared Error", "mae": "Mean Absolute Error"}[type_measure], "oem.fit": fit0})
-    if keep:
-        res["fit.preval"] = predlist; res["foldid"] = foldid
-    res.update(_getmin(lam, cvm, cvsd))
-    res["best.model"] = penalty[res["model.min"] - 1]
-    res["penalty"] = list(penalty)
-    return res
+    return _cv_result(fit0, penalty, lam, cvm, cvsd, _GAUSSIAN_NAMES[type_measure], predlist if keep else None, foldid)
 
 
 def _cv_weighted_stats_many(cvraw, w, N):
@@ -2646,15 +2556,17 @@ def cv_multi_score(x, Y, foldid, nfolds, coef, ncol, type_measure="mse", nb=1, i
 
 
 def _cv_multi_call(x, Y, fid, nfolds, a, standardize, intercept, type_measure, keep, fold_fits=False):
-    """oemgpu_cv_dense_multi_dev / _rm_dev -> a dict of the arrays it fills (include/oemgpu.h has their shapes)"""
+    """oemgpu_cv_dense_multi_dev / _rm_dev -> a dict of the arrays it fills (include/oemgpu.h has their shapes); "outputs" is the
+    _ManyOut behind beta, lambda, niter, loss and d"""
     import torch
     n, p = x.shape
     X = _DeviceX(x, _xval_rowmajor_in_place)
     Yd, rs, cs = _device_responses(Y, x.device)
     m, K, npen, nl = Yd.shape[1], int(nfolds), a.npen, a.nl
     fd = torch.as_tensor(fid, device=x.device)
-    o = {"beta": np.zeros((m, npen, nl, p + 1)), "lambda": np.zeros((m, npen, nl)), "niter": np.zeros((m, npen, nl), dtype=np.int32),
-         "loss": np.zeros((m, npen, nl)), "d": np.zeros(m), "ncol": np.zeros((m, npen), dtype=np.int32), "triples": np.zeros((m, K, npen, nl, 3)),
+    out = _ManyOut(m, a, p + 1)
+    o = {"beta": out.beta, "lambda": out.lam_out, "niter": out.niter, "loss": out.loss, "d": out.d, "outputs": out,
+         "ncol": np.zeros((m, npen), dtype=np.int32), "triples": np.zeros((m, K, npen, nl, 3)),
          "fold_n": np.zeros(K, dtype=np.int64), "route": np.zeros(m, dtype=np.int32)}
     if fold_fits:
         o.update({"fold_beta": np.zeros((m, K, npen, nl, p + 1)), "fold_lambda": np.zeros((m, K, npen, nl)),
@@ -2664,7 +2576,7 @@ def _cv_multi_call(x, Y, fid, nfolds, a, standardize, intercept, type_measure, k
     ctx = context(x.device.index)
     torch.cuda.current_stream(x.device).synchronize()
     X.call("cv_dense_multi", ctx, Yd.data_ptr(), rs, cs, m, fd.data_ptr(), K, int(standardize), int(intercept), int(type_measure == "mae"),
-           C.byref(a.c), _dptr(o["beta"]), _dptr(o["lambda"]), _iptr(o["niter"]), _dptr(o["loss"]), _dptr(o["d"]), _iptr(o["ncol"]),
+           C.byref(a.c), *out.pointers(), _iptr(o["ncol"]),
            _dptr(o["triples"]), o["fold_n"].ctypes.data_as(C.POINTER(C.c_int64)), _iptr(o["route"]),
            _dptr(o["fold_beta"]) if fold_fits else None, _dptr(o["fold_lambda"]) if fold_fits else None,
            _iptr(o["fold_niter"]) if fold_fits else None, _dptr(o["predmat"]) if keep else None)
@@ -2693,10 +2605,7 @@ def cv_oem_multi(x, Y, penalty=None, lambda_=None, type_measure=None, nfolds=10,
     if family == "binomial":
         raise ValueError(who + " serves family = \"gaussian\": binomial responses are cross-validated with cv_oem_logistic_multi()")
     penalty = _match_penalty(penalty)
-    if type_measure is None:
-        type_measure = "default"
-    elif type_measure not in _TYPE_MEASURES:
-        raise ValueError("'arg' should be one of " + ", ".join("'%s'" % t for t in _TYPE_MEASURES))
+    type_measure = _check_type_measure(type_measure)
     if lambda_ is not None and len(lambda_) < 2:
         raise ValueError("Need more than one value of lambda for cv.oem")
     if len(kw.pop("weights", ())) > 0:
@@ -2720,14 +2629,7 @@ def cv_oem_multi(x, Y, penalty=None, lambda_=None, type_measure=None, nfolds=10,
         raise ValueError(who + " serves n > p only: with n <= p cross-validate each column with cv_oem(x, Y[:, r])")
     if p < 2:
         raise ValueError("x must have at least two columns")
-    if foldid is None:
-        g = np.random.default_rng() if rng is None else rng
-        foldid = g.permutation(np.resize(np.arange(1, int(nfolds) + 1), n))
-    else:
-        foldid = np.asarray(foldid).ravel()
-        nfolds = int(foldid.max())
-    if nfolds < 3:
-        raise ValueError("nfolds must be bigger than 3; nfolds=10 recommended")
+    foldid, nfolds = _fold_ids(foldid, nfolds, n, rng)
     if len(foldid) != n or not np.issubdtype(foldid.dtype, np.integer) or foldid.min() < 1 or nfolds > 512:
         raise ValueError("foldid must hold one integer in 1..nfolds per row of x, nfolds at most 512")
     kept = n - np.bincount(foldid, minlength=nfolds + 1)[1:]
@@ -2739,41 +2641,19 @@ def cv_oem_multi(x, Y, penalty=None, lambda_=None, type_measure=None, nfolds=10,
         raise ValueError(host_or_sparse)
     lam_arg = () if lambda_ is None else lambda_
     a, varnames, standardize, intercept = oem(x, Y, penalty=penalty, lambda_=lam_arg, _args_only=True, **kw)
-    if type_measure in ("default", "deviance"):
-        type_measure = "mse"
-    if type_measure not in ("mse", "mae"):
-        warnings.warn("Only 'mse', 'deviance' or 'mae'  available for Gaussian models; 'mse' used")
-        type_measure = "mse"
+    type_measure = _gaussian_measure(type_measure)
     fid = np.ascontiguousarray(foldid, dtype=np.int32)
     o = _cv_multi_call(x, Y, fid, nfolds, a, standardize, intercept, type_measure, keep)
-    if n / nfolds < 3 and grouped:
-        warnings.warn("Option grouped=FALSE enforced in cv.glmnet, since < 3 observations per fold")
-        grouped = False
-    nmodels, nl = len(penalty), a.nl
+    grouped = _ungrouped_if_small(n, nfolds, grouped)
     own = np.flatnonzero(o["route"] != 2)
     if len(own):
         cvm_all, cvsd_all = _cv_gaussian_triple_stats_many(o["fold_n"], o["triples"][own], o["ncol"][own, -1], grouped)
     out = [None] * m
     for i, r in enumerate(own):
-        fit0 = _decorate(_OneOfMany(o["beta"][r], o["lambda"][r], o["niter"][r], o["loss"][r], o["d"][r]), penalty, varnames, True, n, p)
-        nz = [np.array([0 if v is None else len(v) for v in predict(fit0, type="nonzero", which_model=k)]) for k in range(nmodels)]
+        fit0 = _decorate(o["outputs"].one(r), penalty, varnames, True, n, p)
         lam = [np.asarray(l, dtype=np.float64) for l in fit0["lambda"]]
-        cvm, cvsd = list(cvm_all[i]), list(cvsd_all[i])
-        nas = np.zeros(nl, dtype=bool)
-        for k in range(nmodels):
-            nas |= np.isnan(cvsd[k])
-        if nas.any():
-            cvm = [c[~nas] for c in cvm]; cvsd = [c[~nas] for c in cvsd]
-            nz = [c[~nas] for c in nz]; lam = [l[~nas] for l in lam]
-        res = OemFit()
-        res.update({"lambda": lam, "cvm": cvm, "cvsd": cvsd, "cvup": [u + v for u, v in zip(cvm, cvsd)],
-                    "cvlo": [u - v for u, v in zip(cvm, cvsd)], "nzero": nz,
-                    "name": {"mse": "Mean-Squared Error", "mae": "Mean Absolute Error"}[type_measure], "oem.fit": fit0})
-        if keep:
-            res["fit.preval"] = [np.ascontiguousarray(pm.T) for pm in o["predmat"][r]]; res["foldid"] = foldid
-        res.update(_getmin(lam, cvm, cvsd))
-        res["best.model"] = penalty[res["model.min"] - 1]
-        res["penalty"] = list(penalty)
+        res = _cv_result(fit0, penalty, lam, list(cvm_all[i]), list(cvsd_all[i]), _GAUSSIAN_NAMES[type_measure],
+                         [np.ascontiguousarray(pm.T) for pm in o["predmat"][r]] if keep else None, foldid)
         res["route"] = int(o["route"][r])
         out[r] = res
     for r in np.flatnonzero(o["route"] == 2):                        # the single route, with its own shift rule
